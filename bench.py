@@ -7,12 +7,16 @@ history hand-over — on synthetic input (the Cornell box, scripted static camer
 resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p] [--halo exchange|redundant]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...`; the frame is split into N row strips (strong scaling, BASELINE.json configs[3]).
 
-Prints ONE JSON line (rank 0): metric Mray/s over the whole frame time, ms per frame, the HBM
-roofline of the a-trous kernel measured live with HIP events, and the CPU oracle timed beside it.
+Prints ONE JSON line (rank 0): metric Mray/s over the whole frame time, ms per frame, and the HBM
+roofline of the a-trous kernel measured live with HIP events in the same K steps.  A plain run measures
+only that; --full adds the legs behind it (two frames in flight, the presented frame, 1080p and the
+1,152,000-triangle lattice beside 4K, the multi-rank legs) and the CPU oracle timed beside the GPU.
+--dump-outputs DIR writes the frame the last timed step finished as DIR/frame.npy (rgb float32).
 """
 from __future__ import annotations
 
@@ -39,6 +43,9 @@ WORKLOADS = {
     "instanced": dict(width=3840, height=2160, max_segments=8, iterations=5, instanced=True),
 }
 PREWARM_SECONDS = 0.3
+# --dump-outputs: frames of at most DUMP_PIXELS pixels are written whole; larger ones (4K: 8,294,400 pixels) as the DUMP_PIXELS
+# pixels drawn with DUMP_SEED (rgb float32 24 MB + their flat indices as float64 16 MB)
+DUMP_PIXELS, DUMP_SEED = 1 << 21, 20261016
 _INSTANCED = {}  # the configs[4] scene, built once per process
 # VALU issue, measured on this part (scripts/micro/valu_rate.hip -> profiles/r03_valu_issue_micro.txt, wall clock at 8 waves
 # per SIMD): the fastest wave64 VALU instruction occupies a SIMD for 1.06 ns (v_xor_b32; v_mul_f32 1.12, a dependent
@@ -82,9 +89,51 @@ def _scene_kwargs(wl):
     return dict(mesh=(vx, ti), instance_xforms=xf, cameraOrigin=cam, z_far=zfar, lightPos=(1.0, float(cam[1]), float(cam[2]) - 8.0))
 
 
+def _rewind(app, camera, light):
+    """the application back at its first frame (frame 0 reads no history; the device planes it leaves stale are only read
+    by frames > 0), with the camera and light it started with"""
+    import ctypes
+    app.frameCount = 0
+    app.cameraOrigin[:] = camera
+    app.lightPos[:] = light
+    app.cameraMoved = False
+    ctypes.memset(ctypes.addressof(app.pushConstants), 0, ctypes.sizeof(app.pushConstants))
+    app._upload_initial_ubo()
+    app.initializeSceneConstants()
+
+
+def dump_outputs(app, out_dir, world, torch, dist):
+    """--dump-outputs: the frame the last step finished (rgb of the PREVIOUS plane after the history hand-over) as
+    out_dir/frame.npy, float32 — [H, W, 3] when the frame has at most DUMP_PIXELS pixels, else [DUMP_PIXELS, 3] at the flat
+    pixel indices in out_dir/frame_pixel_index.npy (ascending, float64).  Several ranks: every rank fills in the pixels of its
+    own rows, rank 0 writes."""
+    import numpy as np
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi
+    W, H = app.render_width, app.render_height
+    whole = W * H <= DUMP_PIXELS
+    idx = np.arange(W * H) if whole else np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, DUMP_PIXELS, replace=False))
+    y0, y1 = app.plan.own
+    rows = getattr(app.backend, "final_image_rows", None)   # two frames in flight: the finished frame is in the other context
+    img = rows(y0, y1) if rows else app.backend.readback_rows(abi.PLANE_PREVIOUS, y0, y1)
+    mine = (idx >= y0 * W) & (idx < y1 * W)
+    vals = np.zeros((len(idx), 3), np.float32)
+    vals[mine] = img[..., :3].reshape(-1, 3)[idx[mine] - y0 * W]
+    if dist is not None and world > 1:
+        t = torch.from_numpy(vals).to("cpu" if dist.get_backend() == "gloo" else "cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # one rank holds each pixel, the others add zeros: the sum is exact
+        vals = t.cpu().numpy()
+        if dist.get_rank() != 0:
+            return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), vals.reshape(H, W, 3) if whole else vals)
+    if not whole:
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+
+
 def run_gpu(wl, args, rank, world, steps, warmup, torch, dist, collect_kernels=True, in_flight=1, halo=None, present="default",
-            camera_keys=None):
-    """one measured run; halo / present / camera_keys override the command line (the `also` legs of a multi-rank run)"""
+            camera_keys=None, dump=None):
+    """one measured run; halo / present / camera_keys override the command line (the `also` legs of a multi-rank run); dump: a
+    directory for dump_outputs"""
     halo = halo or args.halo
     present = args.present if present == "default" else present
     camera_keys = args.camera_keys if camera_keys is None else camera_keys
@@ -126,6 +175,7 @@ def run_gpu(wl, args, rank, world, steps, warmup, torch, dist, collect_kernels=T
     # round 1 paid that); every 8th frame in long runs, and never fewer than 8 sampled frames (or all of them) in short ones
     timing_period = max(1, min(8, steps // 8))
     if args.prewarm_seconds > 0:
+        camera0, light0 = app.cameraOrigin.copy(), app.lightPos.copy()
         ctx.timing_enable(timing_period if collect_kernels else 0)
         t_wake = time.perf_counter()
         n_wake = 0
@@ -141,6 +191,12 @@ def run_gpu(wl, args, rank, world, steps, warmup, torch, dist, collect_kernels=T
                 c.sync()
         ctx.timing_collect()
         ctx.timing_enable(0)
+        if fixed is None:
+            # one process: the wake-up ran for a time, not a number of frames; rewound to frame 0, the W + K frames that
+            # follow (their rays, the --dump-outputs frame) depend on the arguments only (always an even number of wake-up
+            # frames: the parity of the frame number, which picks the context / present image, is unchanged)
+            _rewind(app, camera0, light0)
+            frame_no[0] = 0
     for _ in range(warmup):
         draw()
     fence()
@@ -172,6 +228,8 @@ def run_gpu(wl, args, rank, world, steps, warmup, torch, dist, collect_kernels=T
         r = torch.tensor([rays], dtype=torch.int64, device="cuda")
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
         rays = int(r.item())
+    if dump:
+        dump_outputs(app, dump, world, torch, dist)
     plan = app.plan
     app.backend.close()
     return elapsed, rays, kern, plan, timed_frames
@@ -510,10 +568,11 @@ def main():
                          "timing protocol, not the interconnect")
     ap.add_argument("--frames-in-flight", type=int, choices=[1, 2], default=1,
                     help="2: the timed run itself uses app.PipelinedBackend (no per-kernel timing, roofline null); "
-                         "the default run reports it under also.two_frames_in_flight")
+                         "a --full run of one frame in flight reports it under also.two_frames_in_flight")
     ap.add_argument("--prewarm-seconds", type=float, default=PREWARM_SECONDS,
-                    help="untimed device wake-up before the W warm-up steps (0 makes the rendered frame numbers, and "
-                         "with them the ray counts, a function of --steps/--warmup only)")
+                    help="untimed device wake-up before the W warm-up steps (one process: rendered for this long, then the "
+                         "application is rewound to frame 0; several ranks: a fixed number of frames, none with 0), so that the "
+                         "rendered frames, their ray counts and --dump-outputs are a function of the arguments only")
     ap.add_argument("--flags", type=lambda v: int(v, 0), default=0,
                     help="RTPT_FLAG_* bits for A/B runs (0x400 = one kernel per a-trous iteration, no chaining)")
     ap.add_argument("--camera-keys", default="",
@@ -525,12 +584,23 @@ def main():
                          "and, with several ranks, the converted strips gathered on rank 0; f32 = the float strips gathered "
                          "as they are; none = the frame stays where the final pass left it.  auto: none on one GPU (the "
                          "frame is already whole), rgba8 on several (a frame that is never assembled cannot be presented)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the legs under `also` (two frames in flight; one GPU: "
+                         "the presented frame and, at 4K, 1080p and the 1,152,000-triangle lattice; several ranks: the frame left "
+                         "distributed, the float gather, the other halo mode, a moving camera) and the CPU oracle baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the legs under `also`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last one finished as DIR/frame.npy (rgb float32; a frame of "
+                         "more than 2^21 pixels as a fixed seeded sample of them, indices in DIR/frame_pixel_index.npy)")
     ap.add_argument("--secondary-timeout", type=float, default=300.0,
                     help="several ranks: seconds the legs behind the headline measurement may take before rank 0 prints the line "
                          "without them and every rank exits (a watchdog against a message that never arrives)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.emulate_strip or args.emulate_balance):
+        ap.error("--dump-outputs writes the frame of the headline run; --emulate-strip / --emulate-balance have none")
+    secondary = args.full and not args.no_secondary
+    cpu_baselines = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -579,7 +649,7 @@ def main():
                           "kernels": kernel_report(kern, wl, plan, timed_frames)}))
         return
     elapsed, rays, kern, plan, timed_frames = run_gpu(wl, args, rank, world, args.steps, args.warmup, torch, dist,
-                                                      in_flight=args.frames_in_flight)
+                                                      in_flight=args.frames_in_flight, dump=args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     host_ms = HOST_SECONDS[0] / args.steps * 1e3
     result = None
@@ -666,9 +736,9 @@ def main():
     # Several ranks: the legs behind the headline measurement exercise point-to-point messages (halo rows, history bands, the
     # float gather) that a one-GPU box can only rehearse over gloo.  If one of them never comes back on the real
     # interconnect, rank 0 still prints the line it has (with a note under `also`), and every rank leaves.
-    watchdog = _arm_watchdog(result, rank, args.secondary_timeout) if dist is not None and world > 1 and not args.no_secondary else None
+    watchdog = _arm_watchdog(result, rank, args.secondary_timeout) if dist is not None and world > 1 and secondary else None
     try:
-        if not args.no_secondary and args.frames_in_flight == 1:
+        if secondary and args.frames_in_flight == 1:
             # the same workload with two frames in flight (app.PipelinedBackend): throughput only, the per-kernel
             # durations above come from the serial run because overlapping frames stretch every kernel
             e3, r3, _, _, _ = run_gpu(wl, args, rank, world, args.steps, args.warmup, torch, dist, collect_kernels=False,
@@ -677,7 +747,7 @@ def main():
                 result.setdefault("also", {})["two_frames_in_flight"] = {
                     "value": round(r3 / e3 / 1e6, 2), "unit": "Mray/s", "ms_per_step": round(e3 / args.steps * 1e3, 4),
                     "fps": round(args.steps / e3, 1)}
-        if world > 1 and not args.no_secondary:
+        if world > 1 and secondary:
             # the legs a scaling run must see (every rank takes part): the frame left distributed, the float gather, the RCCL
             # halo exchange (k rows per neighbour per iteration instead of redundant rows), and a camera that moves every
             # frame (history bands travel between strips).  Same steps/warm-up, throughput only.
@@ -714,12 +784,12 @@ def main():
             result.setdefault("also", {})["_error"] = f"secondary legs abandoned: {ex!r}"
             os.write(_STDOUT_FD[0] if _STDOUT_FD else 1, (json.dumps(result) + "\n").encode())
         os._exit(0)
-    if world == 1 and rank == 0 and not args.no_secondary and args.present is None:
+    if world == 1 and rank == 0 and secondary and args.present is None:
         e6, r6, k6, p6, tf6 = run_gpu(wl, args, 0, 1, args.steps, args.warmup, torch, None, present="rgba8")
         result.setdefault("also", {})["with_present_rgba8"] = {
             "value": round(r6 / e6 / 1e6, 2), "unit": "Mray/s", "ms_per_step": round(e6 / args.steps * 1e3, 4),
             "k_present_us": kernel_report(k6, wl, p6, tf6).get("k_present", {}).get("avg_us")}
-    if world == 1 and rank == 0 and not args.no_secondary and args.workload == "4k":
+    if world == 1 and rank == 0 and secondary and args.workload == "4k":
         e2, r2, k2, p2, tf2 = run_gpu(WORKLOADS["1080p"], args, 0, 1, args.steps, args.warmup, torch, None)
         kr2 = kernel_report(k2, WORKLOADS["1080p"], p2, tf2)
         result.setdefault("also", {})["cornell-1080p-1spp-4seg-5atrous"] = {
@@ -732,7 +802,7 @@ def main():
                                   in_flight=2)
         result["also"]["cornell-1080p-1spp-4seg-5atrous"]["two_frames_in_flight"] = {
             "value": round(r4 / e4 / 1e6, 2), "ms_per_step": round(e4 / args.steps * 1e3, 4)}
-    if world == 1 and rank == 0 and not args.no_secondary and args.workload == "4k":
+    if world == 1 and rank == 0 and secondary and args.workload == "4k":
         # BASELINE.json configs[4] beside the headline (its defining 8-GPU deployment is the driver's to launch: --workload
         # instanced --gpus 8): the 1,152,000-triangle lattice on this one GPU, per-kernel durations, the traversal's committed
         # PMC figures, and the CPU oracle on a bounded pixel sample of the same frame
@@ -745,10 +815,10 @@ def main():
                 "traversal": traversal_report()}
         if kr7.get("k_pathtrace"):  # (absent when K0 + K1 share the launch)
             inst["pathtrace_kernel_mray_s"] = round(r7 / si / (kr7["k_pathtrace"]["avg_us"] * 1e-6) / 1e6, 1)
-        if not args.no_cpu_baseline:
+        if cpu_baselines:
             inst["cpu_baseline"] = cpu_baseline("instanced")
         result.setdefault("also", {})["instanced-4k-1spp-8seg-5atrous"] = inst
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and cpu_baselines:
         result["cpu_baseline"] = cpu_baseline(args.workload)
     if watchdog is not None:
         watchdog.cancel()

@@ -52,4 +52,4 @@ for wl in ("4k", "1080p"):
 json.dump(t, open(f"{out}/traffic.json", "w"), indent=1)
 print(json.dumps(t))
 PY
-python3 bench.py --steps 200 --warmup 20 > "$OUT/4k_bench.json" 2> "$OUT/4k_bench.err" && echo "bench 4k done"
+python3 bench.py --steps 200 --warmup 20 --full > "$OUT/4k_bench.json" 2> "$OUT/4k_bench.err" && echo "bench 4k done"

@@ -41,10 +41,10 @@ def test_single_rank_line(hip_lib):
 
 
 def test_default_line_carries_the_stress_configuration_and_both_cpu_baselines(hip_lib):
-    """`python bench.py` as the driver runs it (short): the headline is BASELINE configs[2]; `also` carries configs[1] and —
+    """`python bench.py --full` (short): the headline is BASELINE configs[2]; `also` carries configs[1] and —
     round 4 — configs[4] (1,152,000 triangles) with per-kernel times, the traversal's committed PMC figures and a CPU baseline
     of its own from a bounded pixel sample; `cpu_baseline` of the headline is still there; K0 + K1 + K2 are one kernel."""
-    d = _run([sys.executable, "bench.py", "--steps", "16", "--warmup", "2"])
+    d = _run([sys.executable, "bench.py", "--steps", "16", "--warmup", "2", "--full"])
     assert REQUIRED | {"cpu_baseline", "also"} <= set(d) and d["config"]["workload"].startswith("cornell-4k")
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 1 and d["cpu_baseline"]["cores"] >= 1
     assert "k_gbuffer_pathtrace" in d["kernels"] and "k_pathtrace" not in d["kernels"]
@@ -54,6 +54,26 @@ def test_default_line_carries_the_stress_configuration_and_both_cpu_baselines(hi
     cb = inst["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "Mray/s" and 0 < cb["value"] < 1 and "brute force" in cb["sample"]
     assert "cornell-1080p-1spp-4seg-5atrous" in d["also"]
+
+
+def test_plain_line_is_the_headline_and_dumps_the_same_frame_every_run(hip_lib, tmp_path):
+    """a plain run measures the headline only (no `also`, no CPU baseline) over exactly --steps steps, and --dump-outputs
+    writes the frame its last step finished: the untimed wake-up renders for a time and is then rewound, so a run with it
+    and one without it write the same frame bit for bit.  At 4K the frame is written as a fixed sample of its pixels."""
+    import numpy as np
+    base = [sys.executable, "bench.py", "--workload", "1080p", "--steps", "8", "--warmup", "2"]
+    a = _run(base + ["--dump-outputs", str(tmp_path / "a")])
+    assert REQUIRED <= set(a) and "also" not in a and "cpu_baseline" not in a and a["steps"] == 8 and a["ms_per_step"] > 0
+    b = _run(base + ["--prewarm-seconds", "0", "--dump-outputs", str(tmp_path / "b")])
+    fa = np.load(tmp_path / "a" / "frame.npy")
+    assert fa.dtype == np.float32 and fa.shape == (1080, 1920, 3) and np.isfinite(fa).all() and fa.mean() > 0
+    assert fa.tobytes() == np.load(tmp_path / "b" / "frame.npy").tobytes() and a["rays_per_frame"] == b["rays_per_frame"]
+    k = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "k")])
+    assert "also" not in k and "cpu_baseline" not in k and k["config"]["workload"].startswith("cornell-4k")
+    fk, ik = np.load(tmp_path / "k" / "frame.npy"), np.load(tmp_path / "k" / "frame_pixel_index.npy")
+    assert fk.dtype == np.float32 and fk.shape == (1 << 21, 3) and np.isfinite(fk).all() and fk.mean() > 0
+    assert ik.dtype == np.float64 and ik.shape == (1 << 21,) and np.all(np.diff(ik) > 0) and 0 <= ik[0] and ik[-1] < 3840 * 2160
+    assert sum(f.stat().st_size for f in (tmp_path / "k").iterdir()) <= 64 << 20
 
 
 def test_balanced_strips_render_the_same_frames(hip_lib):
@@ -95,22 +115,25 @@ def test_multi_rank_line_carries_every_secondary_leg(hip_lib):
     guards them (tests/test_host_logic.py::test_bench_watchdog) left no note"""
     full = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                  "--master-port", str(_port()), "bench.py", "--gpus", "2", "--workload", "1080p", "--steps", "6", "--warmup", "1",
-                 "--rehearse-on-one-gpu", "--prewarm-seconds", "0"])
+                 "--rehearse-on-one-gpu", "--prewarm-seconds", "0", "--full"])
     assert REQUIRED <= set(full) and full["n_gpus"] == 2
     assert "_watchdog" not in full["also"] and "_error" not in full["also"]
     assert {"two_frames_in_flight", "without_output_gather", "with_f32_gather", "halo_exchange", "moving_camera"} <= set(full["also"])
 
 
 @pytest.mark.parametrize("halo", ["redundant", "exchange"])
-def test_two_rank_rehearsal_counts_the_same_rays(hip_lib, halo):
+def test_two_rank_rehearsal_counts_the_same_rays(hip_lib, tmp_path, halo):
     one = _run([sys.executable, "bench.py", "--workload", "1080p", "--steps", "6", "--warmup", "1", "--no-cpu-baseline",
-                "--no-secondary", "--prewarm-seconds", "0"])
+                "--no-secondary", "--prewarm-seconds", "0", "--dump-outputs", str(tmp_path / "one")])
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                 "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--workload", "1080p", "--steps", "6",
-                "--warmup", "1", "--rehearse-on-one-gpu", "--halo", halo, "--no-secondary", "--prewarm-seconds", "0"])
+                "--warmup", "1", "--rehearse-on-one-gpu", "--halo", halo, "--no-secondary", "--prewarm-seconds", "0",
+                "--dump-outputs", str(tmp_path / "two")])
     assert two["n_gpus"] == 2 and halo in two["config"]["parallelism"]
     # the frame sequence is deterministic (RNG seeded by pixel + frame) and both runs render the same frame numbers
     assert two["rays_per_frame"] == one["rays_per_frame"]
+    # ... and the two strips of the last frame, assembled by --dump-outputs, are the single-context frame bit for bit
+    assert (tmp_path / "two" / "frame.npy").read_bytes() == (tmp_path / "one" / "frame.npy").read_bytes()
 
 
 @pytest.mark.parametrize("mode,flags,in_flight", [("redundant", 0, 1), ("exchange", 0, 1), ("redundant", 0x100, 1), ("redundant", 0x81, 1),

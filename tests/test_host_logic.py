@@ -196,3 +196,57 @@ def test_bench_watchdog():
     assert line["metric"] == "m" and "did not finish" in line["also"]["_watchdog"]
     out = subprocess.run([sys.executable, "-c", code % 1], cwd=ROOT, capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and out.stdout == ""
+
+
+def test_bench_rewind_replays_the_first_frames():
+    """bench.py's wake-up renders for a time, not a number of frames, and then rewinds the application: the frames after the
+    rewind hand the backend the same push constants and UBOs as the first frames of a new application (the camera and light
+    moved during the wake-up included)"""
+    import bench
+    script = [(), ("E",), ("J", "D"), ()]
+    be = Recorder()
+    app = PathTracingApplication(be, 64, 48, maxWaveletIteration=3)
+    camera0, light0 = app.cameraOrigin.copy(), app.lightPos.copy()
+    app.run(len(script), script)
+    first = list(be.calls)
+    app.run(6, [("W", "I")] * 6)
+    bench._rewind(app, camera0, light0)
+    be.calls.clear()
+    app.run(len(script), script)
+    assert be.calls == first and app.frameCount == len(script)
+
+
+class _Finished:
+    """the backend protocol's readback of the finished frame: pixel (x, y) of the frame holds (x, y, x * y, -1)"""
+    def __init__(self, W, H):
+        y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+        self.frame = np.stack([x, y, x * y, -np.ones_like(x)], axis=-1)
+
+    def readback_rows(self, plane, y0, y1):
+        assert plane == abi.PLANE_PREVIOUS
+        return self.frame[y0:y1]
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: rgb float32 of the finished frame, whole, or at a seeded ascending sample of distinct pixel indices when
+    the frame exceeds DUMP_PIXELS — the same sample every run"""
+    import types
+
+    import bench
+    W, H = 40, 30
+    be = _Finished(W, H)
+    app = types.SimpleNamespace(render_width=W, render_height=H, plan=StripPlan(H, 1, 0, 3), backend=be)
+    bench.dump_outputs(app, str(tmp_path / "whole"), 1, None, None)
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and got.tobytes() == be.frame[..., :3].tobytes()
+    assert not (tmp_path / "whole" / "frame_pixel_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(app, str(tmp_path / d), 1, None, None)
+    vals, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixel_index.npy")
+    assert vals.dtype == np.float32 and vals.shape == (100, 3) and idx.dtype == np.float64 and idx.shape == (100,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < W * H and np.array_equal(idx, np.round(idx))
+    i = idx.astype(np.int64)
+    assert vals.tobytes() == be.frame.reshape(-1, 4)[i, :3].tobytes()
+    assert np.load(tmp_path / "b" / "frame.npy").tobytes() == vals.tobytes()
+    assert np.load(tmp_path / "b" / "frame_pixel_index.npy").tobytes() == idx.tobytes()
