@@ -406,12 +406,18 @@ int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint3
  *   [4] triangles not referenced exactly once, [5] boxes that do not contain their subtree,
  *   [6] device (16-bit grid) boxes that do not contain the binary32 box, [7] dangling child references */
 int rtpt_util_bvh_check(const float* tris, uint32_t n_tris, uint64_t stats[8]);
+/* rtpt_util_bvh_check with the builder's mode chosen: pairs != 0 builds over the fan pairs (2q, 2q + 1) as
+ * rtpt_scene_upload does for a scene made of them (n_tris must be even) and then also counts in stats[7] every leaf
+ * that is not exactly one such pair from an even slot (cnt 2, leaf_order[first] even, leaf_order[first + 1] the next id):
+ * the pairs-mode traversal reads one pair record per leaf.  pairs == 0 is rtpt_util_bvh_check. */
+int rtpt_util_bvh_check_pairs(const float* tris, uint32_t n_tris, int pairs, uint64_t stats[8]);
 /* The structure as it stands ON THE DEVICE of a context — after rtpt_scene_upload, or after a changed ubo->model re-posed
  * the scene and refit the tree inside rtpt_gbuffer (on the device, on the context's stream, without a host
  * synchronisation: refit.hip) — read back and checked on the host (blocks).
  *   stats[0] nodes, [1] leaves, [2] deepest level, [3] largest leaf, [4] triangles not referenced exactly once,
  *   [5] decoded device boxes that do not contain every vertex below them, [6] boxes reaching beyond the padded scene,
- *   [7] dangling child references */
+ *   [7] dangling child references, and when the tree was built over fan pairs, leaves that are not one pair (as
+ *   rtpt_util_bvh_check_pairs) */
 int rtpt_debug_bvh_check(rtpt_ctx* ctx, uint64_t stats[8]);
 /* the same invariants after a REFIT: the tree is built over `built_for` and refit to `moved` (the same n_tris
  * triangles after an animated model matrix, rtpt_gbuffer) — topology and leaf order kept, boxes recomputed */

@@ -94,7 +94,7 @@ SYMBOLS = [
     "rtpt_plane_ptr", "rtpt_plane_bytes", "rtpt_set_external_history", "rtpt_stream_wait", "rtpt_scene_upload", "rtpt_gbuffer", "rtpt_temporal_gradient",
     "rtpt_raytrace", "rtpt_temporal_filter", "rtpt_end_frame", "rtpt_sync", "rtpt_readback", "rtpt_set_plane",
     "rtpt_reset_counters", "rtpt_set_count_rows", "rtpt_enable_debug", "rtpt_timing_enable", "rtpt_timing_collect", "rtpt_kernel_name",
-    "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check",
+    "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check", "rtpt_util_bvh_check_pairs",
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target",
 ]
@@ -151,6 +151,7 @@ def load() -> C.CDLL:
         "rtpt_selftest_trace": [vp, vp, sz, vp, vp],
         "rtpt_util_load_obj": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_util_bvh_check": [vp, u32, C.POINTER(C.c_uint64 * 8)],
+        "rtpt_util_bvh_check_pairs": [vp, u32, C.c_int, C.POINTER(C.c_uint64 * 8)],
         "rtpt_scene_set_materials": [vp, vp, u32, vp, u32],
         "rtpt_util_bvh_refit_check": [vp, vp, u32, C.POINTER(C.c_uint64 * 8)],
         "rtpt_debug_bvh_check": [vp, C.POINTER(C.c_uint64 * 8)],
@@ -424,15 +425,18 @@ class Context:
         return ids, ts
 
 
-def bvh_check(tris: np.ndarray, built_for: np.ndarray | None = None) -> dict:
+def bvh_check(tris: np.ndarray, built_for: np.ndarray | None = None, pairs: bool = False) -> dict:
     """host-only self check of the BVH builder + device node packing (needs no GPU): see rtpt_util_bvh_check;
-    with `built_for` the tree is built over those triangles and REFIT to `tris` (rtpt_util_bvh_refit_check)"""
+    with `built_for` the tree is built over those triangles and REFIT to `tris` (rtpt_util_bvh_refit_check); with `pairs`
+    it is built over the fan pairs (2q, 2q + 1) and every leaf must be one of them (rtpt_util_bvh_check_pairs)"""
     tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
     st = (C.c_uint64 * 8)()
     if built_for is not None:
         built_for = np.ascontiguousarray(built_for, np.float32).reshape(-1, 9)
         assert built_for.shape == tris.shape
         _check(load().rtpt_util_bvh_refit_check(_ptr(built_for), _ptr(tris), len(tris), C.byref(st)))
+    elif pairs:
+        _check(load().rtpt_util_bvh_check_pairs(_ptr(tris), len(tris), 1, C.byref(st)))
     else:
         _check(load().rtpt_util_bvh_check(_ptr(tris), len(tris), C.byref(st)))
     keys = ("nodes", "leaves", "max_depth", "largest_leaf", "bad_triangle_refs", "loose_boxes", "loose_device_boxes", "bad_child_refs")

@@ -52,6 +52,13 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   if (static_cast<uint64_t>(total) * 48u >= (1ull << 32) || bvh.nodes.size() >= (1ull << 27))
     return fail(RTPT_E_INVALID, "scene too large for the traversal's 32-bit record offsets (more than 89,478,485 triangles)");
   if (bvh.leaf_order.size() != total) return fail(RTPT_E_INVALID, "internal: BVH lost triangles");
+  if (leaf_pairs)  // the pairs-mode leaf test reads one pair record per leaf: a leaf of any other shape would be misread
+    for (const rt::BvhNode& nd : bvh.nodes)
+      for (int side = 0; side < 2; side++) {
+        const uint32_t idx = side ? nd.ridx : nd.lidx, cnt = side ? nd.rcnt : nd.lcnt;
+        if (idx != rt::kBvhEmpty && cnt && !rt::pair_leaf_ok(idx, cnt, bvh.leaf_order.data(), total))
+          return fail(RTPT_E_INVALID, "internal: a pairs-mode BVH leaf is not one fan pair (2q, 2q + 1) from an even slot");
+      }
 
   HIP_TRY(hipStreamSynchronize(c->stream));
   int rc;

@@ -204,6 +204,7 @@ int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
           stats[7]++;
           continue;
         }
+        if (c->leaf_pairs && !rt::pair_leaf_ok(first, cnt, leaf.data(), n)) stats[7]++;  // read as ONE pair record
         for (uint32_t j = 0; j < cnt; j++)
           for (int v = 0; v < 3; v++)
             for (int a = 0; a < 3; a++) {
@@ -249,10 +250,11 @@ int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
   return RTPT_OK;
 }
 
-static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n, uint64_t stats[8]) {
+static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n, bool pairs, uint64_t stats[8]) {
   if (!tris || !stats || n == 0) return fail(RTPT_E_INVALID, "NULL argument / empty scene");
+  if (pairs && n % 2) return fail(RTPT_E_INVALID, "pairs mode needs an even triangle count (fan pairs 2q, 2q + 1)");
   rt::Bvh bvh;
-  rt::build_bvh(build_tris ? build_tris : tris, n, bvh);
+  rt::build_bvh(build_tris ? build_tris : tris, n, bvh, 1e-5f, pairs);
   if (build_tris) rt::refit_bvh(tris, n, bvh);  // same topology, boxes recomputed for the moved triangles
   std::vector<rt::BvhNodeQ> q;
   const rt::BvhGrid g = rt::pack_quantised_nodes(bvh, q);
@@ -321,6 +323,7 @@ static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n
           stats[7]++;
           continue;
         }
+        if (pairs && !rt::pair_leaf_ok(idx, cnt, bvh.leaf_order.data(), bvh.leaf_order.size())) stats[7]++;
         cb = tri_bounds(idx, cnt);
       } else {
         if (idx >= bvh.nodes.size()) continue;
@@ -344,10 +347,13 @@ static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n
   return RTPT_OK;
 }
 
-int rtpt_util_bvh_check(const float* tris, uint32_t n, uint64_t stats[8]) { return bvh_check_impl(nullptr, tris, n, stats); }
+int rtpt_util_bvh_check(const float* tris, uint32_t n, uint64_t stats[8]) { return bvh_check_impl(nullptr, tris, n, false, stats); }
+int rtpt_util_bvh_check_pairs(const float* tris, uint32_t n, int pairs, uint64_t stats[8]) {
+  return bvh_check_impl(nullptr, tris, n, pairs != 0, stats);
+}
 int rtpt_util_bvh_refit_check(const float* built_for, const float* moved, uint32_t n, uint64_t stats[8]) {
   if (!built_for) return fail(RTPT_E_INVALID, "NULL argument");
-  return bvh_check_impl(built_for, moved, n, stats);
+  return bvh_check_impl(built_for, moved, n, false, stats);
 }
 
 int rtpt_util_load_obj(const char* path, float* xyz, uint32_t* n_verts, uint32_t* idx, uint32_t* n_tris) {

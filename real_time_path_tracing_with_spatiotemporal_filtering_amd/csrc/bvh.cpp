@@ -335,8 +335,11 @@ BvhGrid pack_quantised_nodes(const Bvh& bvh, std::vector<BvhNodeQ>& out) {
   }
   // the decoded face is ONE binary32 fma, fma(q, cell, origin) — the same expression in the device refit (refit.hip) and in
   // the checkers (api_selftest.hip): step until THAT value is on the outer side.  The traversal computes
-  // q * (cell / d) + (origin - o) / d instead; what lies between the two is a few ulp of the coordinate, two orders of
-  // magnitude below the padding of the boxes, which is what absorbs it.
+  // q * (cell / d) + (origin - o) / d instead.  What lies between the two is NOT bounded by the coordinate: the rounding
+  // of (origin - o) / d is ~2^-24 |origin - o| / |d|, and the triangle test's own rounding of o - v0 is of the same size,
+  // while the padding (1e-5 x the scene's size) plus the grid's outward rounding (< one cell) is fixed.  The padding
+  // absorbs the gap for an origin within a few scene diagonals; beyond ~100 of them it would not, so the traversal adds a
+  // per-ray margin proportional to |origin - o| (kernels.hip, closest_hit_bvh).
   auto decode = [&](double q, int a) { return std::fmaf(static_cast<float>(q), g.cell[a], g.origin[a]); };
   auto qdown = [&](float x, int a) -> uint16_t {
     double q = std::floor((static_cast<double>(x) - static_cast<double>(g.origin[a])) / cell[a]);

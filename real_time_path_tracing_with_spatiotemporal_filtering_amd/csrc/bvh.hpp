@@ -80,6 +80,14 @@ BvhGrid pack_quantised_nodes(const Bvh& bvh, std::vector<BvhNodeQ>& out);
 // traversal tests them with the shared-edge pair test.  n must be even.
 void build_bvh(const float* tris, uint32_t n, Bvh& out, float pad_rel = 1e-5f, bool pairs = false);
 
+// The leaf layout a tree built with pairs = true must have, because the traversal's pairs-mode leaf test reads exactly ONE
+// 80-byte pair record per leaf, at slot first / 2, whatever the leaf's count (kernels.hip: closest_hit_bvh<true>): the leaf
+// is the two triangles 2q, 2q + 1 of one fan pair, in this order, from an even slot.
+inline bool pair_leaf_ok(uint32_t first, uint32_t cnt, const uint32_t* leaf_order, size_t n_slots) {
+  return cnt == 2 && !(first & 1u) && static_cast<size_t>(first) + 1 < n_slots && !(leaf_order[first] & 1u) &&
+         leaf_order[first + 1] == leaf_order[first] + 1u;
+}
+
 // Same topology and leaf order, new vertex positions (an animated `model` matrix, main.cpp:1469): recomputes every
 // child box bottom-up from the moved triangles, the scene bounds and the padding.  The tree stays valid for any motion;
 // its quality is that of the pose it was built for.

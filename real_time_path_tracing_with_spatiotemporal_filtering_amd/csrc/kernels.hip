@@ -314,7 +314,16 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
   using cflt = const __attribute__((address_space(4))) float;
   cflt* gr = (cflt*)sc.bvh_grid;
   const f3 inv{gr[3] * rd.x, gr[4] * rd.y, gr[5] * rd.z};
+  // The slab distances round (origin - o) / d, and the triangle test rounds o - v0: both errors grow with the origin's
+  // distance from the scene, while the boxes' padding (1e-5 x the scene's size, bvh.cpp) does not.  Past ~100 scene
+  // diagonals a ray the triangle test accepts at a vertex on a box's edge could find that box's interval empty and the
+  // box culled.  So every box is widened per ray by a margin of 2^-19 (32 ulp) of the origin's L1 distance from the grid
+  // origin, in position units: on axis a that is pm |1 / d_a| in t, folded into the near and far offsets (oin, oif), so
+  // the node step is unchanged.  For an origin inside the scene the margin is below the padding.
+  const float pm = 0x1p-19f * (__builtin_fabsf(gr[0] - o.x) + __builtin_fabsf(gr[1] - o.y) + __builtin_fabsf(gr[2] - o.z));
   const f3 oi{(gr[0] - o.x) * rd.x, (gr[1] - o.y) * rd.y, (gr[2] - o.z) * rd.z};
+  const f3 mg{pm * __builtin_fabsf(rd.x), pm * __builtin_fabsf(rd.y), pm * __builtin_fabsf(rd.z)};
+  const f3 oin{oi.x - mg.x, oi.y - mg.y, oi.z - mg.z}, oif{oi.x + mg.x, oi.y + mg.y, oi.z + mg.z};
   struct { uint32_t x, y, z; } const rot{rd.x < 0.0f ? 16u : 0u, rd.y < 0.0f ? 16u : 0u, rd.z < 0.0f ? 16u : 0u};
   int sp = 0;
   uint32_t cur = 0;  // root pair
@@ -404,20 +413,21 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
     // the min / max pair per axis that sorted the two distances (12 per node) becomes one v_alignbit_b32 (6 per node).
     // Same values: fma(q, inv, oi) is monotonic in q, increasing for inv > 0 and decreasing for inv < 0 (|d| is clamped away
     // from 0 above, so inv is never 0 or NaN), so min(t(min), t(max)) IS t of the half selected here, bit for bit.
-    auto near_far = [&](uint32_t w, uint32_t rot_, float inv_, float oi_, float& tn_, float& tf_) {
+    // The near plane takes the offset widened towards the ray (oin), the far one the offset widened away from it (oif).
+    auto near_far = [&](uint32_t w, uint32_t rot_, float inv_, float oin_, float oif_, float& tn_, float& tf_) {
       const uint32_t q = __builtin_amdgcn_alignbit(w, w, rot_);
-      tn_ = fmaf_(static_cast<float>(q & 0xFFFFu), inv_, oi_);
-      tf_ = fmaf_(static_cast<float>(q >> 16), inv_, oi_);
+      tn_ = fmaf_(static_cast<float>(q & 0xFFFFu), inv_, oin_);
+      tf_ = fmaf_(static_cast<float>(q >> 16), inv_, oif_);
     };
     float n0, n1, n2, f0, f1, f2;
-    near_far(a.x, rot.x, inv.x, oi.x, n0, f0);
-    near_far(a.y, rot.y, inv.y, oi.y, n1, f1);
-    near_far(a.z, rot.z, inv.z, oi.z, n2, f2);
+    near_far(a.x, rot.x, inv.x, oin.x, oif.x, n0, f0);
+    near_far(a.y, rot.y, inv.y, oin.y, oif.y, n1, f1);
+    near_far(a.z, rot.z, inv.z, oin.z, oif.z, n2, f2);
     tl = __builtin_fmaxf(__builtin_fmaxf(n0, n1), __builtin_fmaxf(n2, 0.0f));
     const bool sl = tl <= __builtin_fminf(__builtin_fminf(f0, f1), __builtin_fminf(f2, tb));
-    near_far(a.w, rot.x, inv.x, oi.x, n0, f0);
-    near_far(b.x, rot.y, inv.y, oi.y, n1, f1);
-    near_far(b.y, rot.z, inv.z, oi.z, n2, f2);
+    near_far(a.w, rot.x, inv.x, oin.x, oif.x, n0, f0);
+    near_far(b.x, rot.y, inv.y, oin.y, oif.y, n1, f1);
+    near_far(b.y, rot.z, inv.z, oin.z, oif.z, n2, f2);
     tr = __builtin_fmaxf(__builtin_fmaxf(n0, n1), __builtin_fmaxf(n2, 0.0f));
     const bool sr = tr <= __builtin_fminf(__builtin_fminf(f0, f1), __builtin_fminf(f2, tb));
     const bool hl = sl & (cl != kBvhEmpty), hr = sr & (cr != kBvhEmpty);

@@ -65,3 +65,58 @@ def test_tessellated_lattice(cornell):
     st = abi.bvh_check(tris)
     _ok(st, len(tris))
     assert st["max_depth"] <= 24
+
+
+# ------------------------------------------------------------------------------ pairs mode
+# A scene made of fan pairs (2q, 2q + 1) = (a, b, c), (a, c, d) is built over the pairs (rtpt_scene_upload), and the
+# traversal's pairs-mode leaf test reads exactly ONE pair record per leaf whatever the leaf's count: every leaf must be
+# the two triangles of one pair, in order, from an even slot.  rtpt_util_bvh_check_pairs counts any other leaf in
+# bad_child_refs.
+def _fan_pairs(quads):
+    """(n, 4, 3) quad corners a, b, c, d -> (2n, 9) triangles (a, b, c), (a, c, d)"""
+    q = np.asarray(quads, np.float32)
+    return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 1).reshape(-1, 9)
+
+
+def _ok_pairs(tris):
+    st = abi.bvh_check(tris, pairs=True)
+    _ok(st, len(tris))
+    assert st["largest_leaf"] == 2 and st["leaves"] == len(tris) // 2, st  # one pair per leaf, every pair a leaf
+    return st
+
+
+def _grid_quads(g, height):
+    x, z = np.meshgrid(np.linspace(-1, 1, g + 1), np.linspace(-1, 1, g + 1), indexing="ij")
+    p = np.stack([x, height(x, z), z], -1)
+    return np.stack([p[:-1, :-1], p[1:, :-1], p[1:, 1:], p[:-1, 1:]], 2).reshape(-1, 4, 3)
+
+
+def test_pairs_tessellated_lattice(cornell):
+    from oracle import oracle as O
+    xyz, idx, _ = cornell
+    vx, ti = scenes.tessellate_quads(xyz, idx, 6)
+    tris = O.flatten(vx, ti, scenes.lattice_xforms(3, 3, 3, 2.8))
+    _ok_pairs(tris)
+
+
+def test_pairs_heightfield_and_sphere():
+    _ok_pairs(_fan_pairs(_grid_quads(40, lambda x, z: 0.3 * np.sin(5 * x) * np.cos(3 * z) + 0.2 * x * z)))  # non-planar
+    th, ph = np.meshgrid(np.linspace(0, np.pi, 25), np.linspace(0, 2 * np.pi, 49), indexing="ij")
+    p = np.stack([np.sin(th) * np.cos(ph), np.cos(th), np.sin(th) * np.sin(ph)], -1)
+    quads = np.stack([p[:-1, :-1], p[1:, :-1], p[1:, 1:], p[:-1, 1:]], 2).reshape(-1, 4, 3)  # pole quads: one half degenerate
+    _ok_pairs(_fan_pairs(quads))
+
+
+def test_pairs_degenerate_layouts():
+    # identical centroids (the SAH finds no split: the median fallback must still keep pairs whole), a flat grid
+    same = _fan_pairs(np.tile(np.array([[[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]]], np.float32), (301, 1, 1)))
+    _ok_pairs(same)
+    _ok_pairs(_fan_pairs(_grid_quads(50, lambda x, z: np.zeros_like(x))))
+    for n in (1, 2, 3, 33):  # the single-leaf root {leaf, absent} and the smallest trees
+        _ok_pairs(_fan_pairs(_grid_quads(6, lambda x, z: 0.1 * x * z)[:n]))
+
+
+def test_pairs_mode_needs_an_even_count():
+    tris = np.random.default_rng(5).uniform(-1, 1, (7, 9)).astype(np.float32)
+    with pytest.raises(abi.RtptError):
+        abi.bvh_check(tris, pairs=True)
