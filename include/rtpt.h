@@ -143,7 +143,9 @@ typedef struct rtpt_config {
   uint32_t row_begin, row_end;   /* rows stored by this context (0,height on one GPU);
                                     multi-GPU strips allocate strip +- halo rows */
   uint32_t max_segments;         /* raytrace.comp.glsl:204 (32) */
-  uint32_t samples_per_pixel;    /* raytrace.comp.glsl:306 (1) */
+  uint32_t samples_per_pixel;    /* raytrace.comp.glsl:306 (1).  > 1 is an extension: every sample draws fresh bounce
+                                    directions from one stream per pixel, whereas the reference text (rngState by value, :200)
+                                    would replay sample 0's */
   int32_t sigma_n;               /* temporalFiltering.comp.glsl:203 (128; integer exponent) */
   float sigma_z;                 /* :204 (1.0) */
   float sigma_l;                 /* :205 (4.0) */

@@ -234,6 +234,33 @@ def raytrace(cfg, pc: PushConstants, tris, y0=0, y1=None, want_hit_id=True, tri_
     return img, int(rc.value), hid
 
 
+class SeqDump(C.Structure):
+    """oracle_seq_dump, rtpt_oracle.h"""
+    _fields_ = [("seq_id", C.c_void_p), ("seq_n", C.c_void_p), ("seq_end", C.c_void_p), ("max_rec", C.c_uint32),
+                ("dir0", C.c_void_p)]
+
+
+END_LIGHT, END_SKY, END_BOUND = 1, 2, 3
+
+
+def raytrace_seq(cfg, pc: PushConstants, tris):
+    """raytrace() plus the per-pixel path dump: (image, rays, hit_id, seq_id[H,W,max_rec] uint16, seq_n[H,W], seq_end[H,W],
+    dir0[H,W,3]) with max_rec = max_segments * samples_per_pixel"""
+    W, H = cfg.width, cfg.height
+    max_rec = int(cfg.max_segments) * int(cfg.samples_per_pixel)
+    img = np.zeros((H, W, 4), np.float32)
+    hid = np.zeros((H, W), np.uint32)
+    seq_id = np.zeros((H, W, max_rec), np.uint16)
+    seq_n = np.zeros((H, W), np.int32)
+    seq_end = np.zeros((H, W), np.uint8)
+    rc = C.c_uint64(0)
+    dir0 = np.zeros((H, W, 3), np.float32)
+    d = SeqDump(seq_id.ctypes.data, seq_n.ctypes.data, seq_end.ctypes.data, max_rec, dir0.ctypes.data)
+    lib().oracle_raytrace_seq(C.byref(cfg), C.byref(pc), _p(tris), C.c_uint32(len(tris)), C.c_uint32(0), C.c_uint32(H),
+                              _p(img), C.byref(rc), _p(hid), C.byref(d))
+    return img, int(rc.value), hid, seq_id, seq_n, seq_end, dir0
+
+
 def moments(cfg, pc: PushConstants, ubo: Ubo, traced, vis, worldpos, lut_prev, prev_vis, moments_prev, y0=0, y1=None):
     """extension EXT_VARIANCE: (moments[H,W,4] = m1, m2, n, var; variance[H,W])"""
     W, H = cfg.width, cfg.height

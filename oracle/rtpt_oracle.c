@@ -579,7 +579,7 @@ void oracle_raytrace(const oracle_config* cfg, const oracle_push_constants* pc, 
  * normal-keyed colours (raytrace.comp.glsl:155-163) */
 static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                          uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image,
-                         uint64_t* raycount, uint32_t* hit_id) {
+                         uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
   const int W = (int)cfg->width, H = (int)cfg->height;
   vec3 light_c = v3(pc->lightPos[0], pc->lightPos[1], pc->lightPos[2]); /* :279 */
   vec3 light_col = v3(pc->currentCameraColor[0] * cfg->light_intensity, pc->currentCameraColor[1] * cfg->light_intensity,
@@ -593,7 +593,12 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
       uint32_t rng = oracle_rng_seed((uint32_t)x, (uint32_t)y, pc->frameNumber, pc->sample_batch); /* :297 */
       vec3 sum = v3(0.f, 0.f, 0.f);
       uint32_t first_id = 0;
-      for (uint32_t smp = 0; smp < cfg->samples_per_pixel; smp++) { /* :307 */
+      uint32_t n_rec = 0; /* closest-hit queries of this pixel, all samples (dump only) */
+      uint8_t end_code = ORACLE_END_BOUND;
+      /* the reference runs one sample (:306).  samples_per_pixel > 1 is an EXTENSION, not :307's behaviour: &rng goes through
+       * the bounces here, so every sample draws fresh directions; the reference text passes rngState by value (:200) and
+       * would replay sample 0's bounce draws, only the jitter stream of :314 continuing */
+      for (uint32_t smp = 0; smp < cfg->samples_per_pixel; smp++) {
         vec3 o = cam;
         float gx, gy;
         random_gaussian(&rng, &gx, &gy);
@@ -603,13 +608,23 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
         float uy = -(dm_fma(2.0f, cy, -fh) / fh); /* :316 */
         vec3 d = v3_normalize(v3(slope * ux, slope * uy, -1.0f)); /* :319-320 */
         vec3 acc = v3(1.f, 1.f, 1.f);                             /* :201 */
+        if (dump && dump->dir0 && smp == 0) {
+          float* q = dump->dir0 + 3 * ((uint64_t)y * W + x);
+          q[0] = d.x; q[1] = d.y; q[2] = d.z;
+        }
         for (uint32_t seg = 0; seg < cfg->max_segments; seg++) {  /* :204 */
           float t, b1, b2;
           float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
           uint32_t id = oracle_closest_hit(tris, n, oo, dd, cfg->ray_tmax, &t, &b1, &b2); /* :208-222 */
           rays_total++;
           if (seg == 0 && smp == 0) first_id = id;
+          if (dump) {
+            if (n_rec < dump->max_rec) dump->seq_id[((uint64_t)y * W + x) * dump->max_rec + n_rec] = (uint16_t)id;
+            n_rec++;
+            end_code = ORACLE_END_BOUND;
+          }
           if (ray_hits_light(o, d, light_c, cfg->light_radius)) { /* :226 — not compared with t */
+            end_code = ORACLE_END_LIGHT;
             if (seg == 0) {
               acc = v3_mul(acc, v3(light_col.x / cfg->first_hit_light_divisor, light_col.y / cfg->first_hit_light_divisor,
                                    light_col.z / cfg->first_hit_light_divisor)); /* :229 */
@@ -646,6 +661,7 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
             d = v3_normalize(v3(dm_fma(r, c, nrm.x), dm_fma(r, s, nrm.y), nrm.z + u)); /* :259-261 */
           } else {
             acc = v3_mul(acc, sky_color(d)); /* :266 */
+            end_code = ORACLE_END_SKY;
             break;
           }
         }
@@ -658,6 +674,10 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
       image[4 * i + 2] = sum.z / ns;
       image[4 * i + 3] = 0.0f; /* :343 */
       if (hit_id) hit_id[i] = first_id;
+      if (dump) {
+        dump->seq_n[i] = (int32_t)n_rec;
+        if (dump->seq_end) dump->seq_end[i] = end_code; /* of the last sample */
+      }
     }
   if (raycount) __atomic_fetch_add(raycount, rays_total, __ATOMIC_RELAXED); /* chunks of one call share it */
 }
@@ -672,15 +692,21 @@ typedef struct {
   float* image;
   uint64_t* raycount;
   uint32_t* hit_id;
+  const oracle_seq_dump* dump;
 } raytrace_mat_args;
 
 static void raytrace_mat_range(void* ctx, int64_t a, int64_t b) {
   const raytrace_mat_args* A = (const raytrace_mat_args*)ctx;
-  raytrace_mat_rows(A->cfg, A->pc, A->tris, A->n, A->tri_mat, A->n_base, (uint32_t)a, (uint32_t)b, A->image, A->raycount, A->hit_id);
+  raytrace_mat_rows(A->cfg, A->pc, A->tris, A->n, A->tri_mat, A->n_base, (uint32_t)a, (uint32_t)b, A->image, A->raycount, A->hit_id, A->dump);
 }
 
 void oracle_raytrace_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id) {
-  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id};
+  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, NULL};
+  run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
+}
+
+void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
+  raytrace_mat_args A = {cfg, pc, tris, n, NULL, 0, image, raycount, hit_id, dump};
   run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
 }
 

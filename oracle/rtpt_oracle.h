@@ -3,8 +3,9 @@
  * reference's per-frame compute chain, one function per shader, each citing the GLSL it
  * follows.  PARITY UNPINNED by reference fixtures: the reference has no tests, golden images or
  * runnable build in this environment; this oracle is pinned by the
- * known-answer vectors derivable from the reference sources (tests/test_oracle_kat.py) and by
- * line-by-line citation.
+ * known-answer vectors derivable from the reference sources (tests/test_oracle_kat.py), by
+ * line-by-line citation, and by the reference's own compute shader text executed on the CPU
+ * (oracle/refshader/, tests/test_reference_shaders.py).
  */
 #ifndef RTPT_ORACLE_H
 #define RTPT_ORACLE_H
@@ -18,7 +19,7 @@ extern "C" {
 typedef struct oracle_config {
   uint32_t width, height;        /* main.cpp:52-53 */
   uint32_t max_segments;         /* raytrace.comp.glsl:204 */
-  uint32_t samples_per_pixel;    /* raytrace.comp.glsl:306 */
+  uint32_t samples_per_pixel;    /* raytrace.comp.glsl:306 (1); > 1 is an extension (see oracle_raytrace) */
   int32_t sigma_n;               /* temporalFiltering.comp.glsl:203 */
   float sigma_z, sigma_l;        /* :204-205 */
   float alpha;                   /* :243 */
@@ -127,6 +128,22 @@ void oracle_raytrace(const oracle_config* cfg, const oracle_push_constants* pc, 
 void oracle_raytrace_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                          uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image,
                          uint64_t* raycount, uint32_t* hit_id);
+/* K2 with a per-pixel dump of the path (tests/test_reference_shaders.py compares it with a run of the reference's shader
+ * text): seq_id[pixel * max_rec + k] = primitive id + 1 (0 = none) of the pixel's k-th closest-hit query (samples follow
+ * each other), seq_n[pixel] = number of queries, seq_end[pixel] (nullable) = how the last sample's path ended. */
+#define ORACLE_END_LIGHT 1 /* :226-235 */
+#define ORACLE_END_SKY 2   /* :266-267 */
+#define ORACLE_END_BOUND 3 /* :204 */
+typedef struct oracle_seq_dump {
+  uint16_t* seq_id;
+  int32_t* seq_n;
+  uint8_t* seq_end;
+  uint32_t max_rec;
+  float* dir0; /* nullable: 3 floats per pixel, the first sample's normalised primary direction (:319-320) */
+} oracle_seq_dump;
+void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
+                         uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount,
+                         uint32_t* hit_id, const oracle_seq_dump* dump);
 /* K3: temporalFiltering.comp.glsl:191-265, one iteration.  `in` is the colorImage snapshot (D1),
  * `out` receives the filtered colour (k < max) or the blend (k == max).  prev_pixel (nullable,
  * 2 ints per pixel) receives previousPixelPos when k == max. */

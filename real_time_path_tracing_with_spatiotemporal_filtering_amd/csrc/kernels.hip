@@ -880,7 +880,8 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
   // per-pixel sample accumulators and RNG state between samples: behind the shared region, allocated (by
-  // launch_pathtrace) only when spp > 1 — the reference runs 1 spp (raytrace.comp.glsl:306)
+  // launch_pathtrace) only when spp > 1 — the reference runs 1 spp (raytrace.comp.glsl:306); spp > 1 is an EXTENSION, see
+  // the note at the rng_pix store below
   float* const sum_r = reinterpret_cast<float*>(stack + a.multi_off);
   float* const sum_g = sum_r + kPtThreads;
   float* const sum_b = sum_g + kPtThreads;
@@ -975,7 +976,11 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
             sum_r[pix] += acc.x;  // :325 (one path per pixel at a time: no race)
             sum_g[pix] += acc.y;
             sum_b[pix] += acc.z;
-            rng_pix[pix] = rng;  // :307 the next sample of this pixel continues the same stream
+            // EXTENSION (not the reference's behaviour): the next sample of this pixel continues the stream after this
+            // sample's bounce draws.  The reference text takes rngState by value into the bounce loop
+            // (raytrace.comp.glsl:200), so with NUM_SAMPLES > 1 it would replay sample 0's bounce draws and only the jitter
+            // stream of :314 would continue (tests/test_reference_shaders.py::test_samples_per_pixel_is_an_extension)
+            rng_pix[pix] = rng;
           }
         }
       }

@@ -1,6 +1,7 @@
 """A second, independent transcription of the reference's shaders — vectorised numpy in float64, written from the GLSL
-text with libm's pow/exp/sqrt — against the C oracle (contract arithmetic in binary32).  The reference cannot be run
-here, so this does not pin the oracle to the reference's *output*; it does pin it against transcription
+text with libm's pow/exp/sqrt — against the C oracle (contract arithmetic in binary32).  This is a second READING of the
+text (tests/test_reference_shaders.py executes the text itself); it does not pin the oracle to the reference's *output*
+(the application cannot run here); it does pin it against transcription
 mistakes: two differently written restatements of the same GLSL must agree to binary32 accuracy, and integer
 observables must agree except where a value sits on a rounding boundary."""
 import numpy as np
