@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RTPT_ABI_VERSION 4
+#define RTPT_ABI_VERSION 5
 
 /* ---- status codes -------------------------------------------------------------------- */
 #define RTPT_OK 0
@@ -136,6 +136,15 @@ typedef struct rtpt_visibility_data {
                                               Gaussian (1 2 1 / 2 4 2 / 1 2 1) / 16 of the variance plane around the pixel.
                                               On strip contexts the traced rows must reach 3 rows beyond every row whose variance
                                               an iteration reads (the hosts' strip plans do that: strips.py / host/strips.cpp). */
+
+#define RTPT_FLAG_DEVICE_BVH_BUILD 0x1000u /* rtpt_scene_upload builds the tree on the device (csrc/bvh_build.hip: a linear BVH
+                                              over 63-bit Morton keys) instead of running the 32-bin SAH builder on one CPU
+                                              thread.  Same node format, same traversal, same pixels (boxes only cull and
+                                              order); what changes is cost: the upload no longer stalls for the host build
+                                              (0.3 s of tree construction for 1,152,000 triangles), and a Morton tree traces somewhat
+                                              slower than the SAH tree.  RTPT_DEVICE_BVH=1 in rtpt_create's environment sets it
+                                              too.  A device-built tree has no host copy: it is always refit on the device,
+                                              RTPT_HOST_REFIT does not apply to it.  ABI version 5 */
 
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
@@ -267,6 +276,36 @@ typedef struct rtpt_material {
 } rtpt_material;
 int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material* materials,
                              uint32_t n_materials);
+
+/* What built the tree that is on the device now.  (A struct tag without a typedef: the entry point below carries the
+ * same name, and C keeps tags and functions apart.) */
+enum { RTPT_BVH_BUILDER_HOST_SAH = 0, RTPT_BVH_BUILDER_DEVICE_LBVH = 1 };
+enum { RTPT_BVH_FALLBACK_NONE = 0, RTPT_BVH_FALLBACK_DEPTH = 1 };
+struct rtpt_scene_build_info {
+  uint32_t builder, fallback; /* RTPT_BVH_BUILDER_*, and why it is not the one asked for: RTPT_BVH_FALLBACK_* */
+  uint32_t n_primitives;      /* what the tree was built over: fan pairs (leaf_pairs) or triangles */
+  uint32_t n_nodes, depth;    /* child-pair nodes; level of the deepest leaf (the root pair's children are at 1) */
+  uint32_t leaf_pairs;        /* 1: every leaf is one fan pair (2q, 2q + 1) */
+  float build_ms;             /* tree construction alone.  Device: HIP events around the builder's kernels, the refit that
+                                 fills the boxes and the leaf records (includes the one small readback in between).
+                                 Host: the clock around the SAH build and the node packing */
+  float upload_ms;            /* the whole rtpt_scene_upload / rtpt_scene_rebuild call, host clock */
+};
+/* RTPT_E_NO_SCENE before an upload.  After a device build it waits for that build's events. */
+int rtpt_scene_build_info(rtpt_ctx* ctx, struct rtpt_scene_build_info* out);
+/* With RTPT_FLAG_DEVICE_BVH_BUILD, rtpt_scene_upload keeps flattening the mesh and detecting fan pairs on the host, uploads
+ * the triangles and builds the tree on the device, with one small readback (depth, node count, nodes per height) where the
+ * host path has its final synchronisation.  A radix tree over 63 key bits and 32 tie-breaking bits can be deeper than
+ * the traversal's 48-entry stack (nearly coincident geometry at very different scales): the upload then builds
+ * with the host builder in the same call, returns RTPT_OK and reports HOST_SAH / FALLBACK_DEPTH.
+ *
+ * rtpt_scene_rebuild builds a NEW tree on the device over the triangles as currently posed (a refit keeps the topology
+ * of the pose the tree was built for, however far the model has moved since) and replaces nodes, leaf order and leaf
+ * records; un-posed triangles, model, LUTs, materials and history stay.  Allowed on any scene whatever built its tree
+ * (afterwards it is a device tree, whatever the flag says); RTPT_E_NO_SCENE without one.  Frames after it equal the
+ * frames without it bit for bit: it changes cost only.  Blocks for the readback.  If the new tree would be deeper than
+ * the stack the old one stays and the call returns RTPT_E_INVALID. */
+int rtpt_scene_rebuild(rtpt_ctx* ctx);
 
 /* ---- per-frame passes, one call per reference dispatch ----------------------------------- */
 
@@ -437,6 +476,7 @@ static_assert(offsetof(rtpt_push_constants, waveletIteration) == 92, "waveletIte
 static_assert(offsetof(rtpt_push_constants, maxWaveletIteration) == 96, "maxWaveletIteration@96");
 static_assert(sizeof(rtpt_ubo) == 384, "UniformBufferObject is 384 bytes (main.cpp:82-90)");
 static_assert(sizeof(rtpt_visibility_data) == 48, "VisibilityData stride 48 (std430)");
+static_assert(sizeof(struct rtpt_scene_build_info) == 32, "rtpt_scene_build_info is 32 bytes");
 #endif
 
 #endif /* RTPT_H */

@@ -26,6 +26,9 @@ FLAG_SINGLE_LAUNCH_PATHS = 0x200
 FLAG_NO_FILTER_FUSION = 0x400
 FLAG_EXT_SVGF_VARIANCE = 0x800
 FLAG_EXT_MASK = 0x9F0
+FLAG_DEVICE_BVH_BUILD = 0x1000  # rtpt_scene_upload builds the tree on the device (csrc/bvh_build.hip)
+BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
+BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
 DEBUG_HIT_ID, DEBUG_PREV_PIXEL = 0x1, 0x2
 
 # rtpt_plane
@@ -73,6 +76,14 @@ class Material(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("emission", C.c_float * 3)]
 
 
+class SceneBuildInfo(C.Structure):
+    """struct rtpt_scene_build_info (32 bytes)."""
+    _fields_ = [
+        ("builder", C.c_uint32), ("fallback", C.c_uint32), ("n_primitives", C.c_uint32), ("n_nodes", C.c_uint32),
+        ("depth", C.c_uint32), ("leaf_pairs", C.c_uint32), ("build_ms", C.c_float), ("upload_ms", C.c_float),
+    ]
+
+
 class Config(C.Structure):
     """rtpt_config."""
     _fields_ = [
@@ -86,7 +97,7 @@ class Config(C.Structure):
     ]
 
 
-assert C.sizeof(PushConstants) == 112 and C.sizeof(Ubo) == 384
+assert C.sizeof(PushConstants) == 112 and C.sizeof(Ubo) == 384 and C.sizeof(SceneBuildInfo) == 32
 
 # every symbol include/rtpt.h declares (tests check the header and this list agree)
 SYMBOLS = [
@@ -96,7 +107,7 @@ SYMBOLS = [
     "rtpt_reset_counters", "rtpt_set_count_rows", "rtpt_enable_debug", "rtpt_timing_enable", "rtpt_timing_collect", "rtpt_kernel_name",
     "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check", "rtpt_util_bvh_check_pairs",
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
-    "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target",
+    "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
 ]
 
 _lib = None
@@ -155,6 +166,8 @@ def load() -> C.CDLL:
         "rtpt_scene_set_materials": [vp, vp, u32, vp, u32],
         "rtpt_util_bvh_refit_check": [vp, vp, u32, C.POINTER(C.c_uint64 * 8)],
         "rtpt_debug_bvh_check": [vp, C.POINTER(C.c_uint64 * 8)],
+        "rtpt_scene_build_info": [vp, C.POINTER(SceneBuildInfo)],
+        "rtpt_scene_rebuild": [vp],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
     }
     for name, args in sigs.items():
@@ -315,6 +328,16 @@ class Context:
             ni = len(xf)
         _check(self._lib.rtpt_scene_upload(self._h, _ptr(xyz), len(xyz), _ptr(idx), len(idx), _ptr(xf), ni))
         self.n_tris = len(idx) * max(ni, 1)
+
+    def scene_build_info(self) -> dict:
+        """what built the tree that is on the device now (rtpt_scene_build_info): builder, fallback, counts, milliseconds"""
+        info = SceneBuildInfo()
+        _check(self._lib.rtpt_scene_build_info(self._h, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in SceneBuildInfo._fields_}
+
+    def scene_rebuild(self):
+        """a new tree, built on the device over the triangles as currently posed (rtpt_scene_rebuild)"""
+        _check(self._lib.rtpt_scene_rebuild(self._h))
 
     def set_materials(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
         """per-triangle material indices + (Kd, Ke) rows; None returns to the reference's normal-keyed colours"""

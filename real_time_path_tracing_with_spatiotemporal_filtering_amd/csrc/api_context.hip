@@ -333,6 +333,9 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   // tuning knobs for A/B runs on the box (never needed for correctness: every setting computes the same pixels)
   if (const char* v = std::getenv("RTPT_NO_TRI_PAIRS")) c->no_pairing = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_HOST_REFIT")) c->host_refit = std::atoi(v) != 0;
+  c->device_bvh = (cfg->flags & RTPT_FLAG_DEVICE_BVH_BUILD) != 0;
+  if (const char* v = std::getenv("RTPT_DEVICE_BVH")) c->device_bvh = c->device_bvh || std::atoi(v) != 0;
+  if (const char* v = std::getenv("RTPT_LBVH_ORDER")) c->lbvh_by_height = !std::strcmp(v, "height");
   if (const char* v = std::getenv("RTPT_NO_TRACE_FUSION")) c->fuse_trace = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_TRACE_POOL")) c->trace_pool = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_PT_WINDOW")) c->trace_window = static_cast<uint32_t>(std::max(0, std::atoi(v)));
@@ -370,6 +373,8 @@ int rtpt_destroy(rtpt_ctx* c) {
   }
   for (auto& e : c->event_pool) (void)hipEventDestroy(e);
   if (c->handoff_event) (void)hipEventDestroy(c->handoff_event);
+  for (hipEvent_t e : c->build_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& b : c->color) free_buf(b);
   for (auto& b : c->vis) free_buf(b);
   free_buf(c->normals);
@@ -382,7 +387,7 @@ int rtpt_destroy(rtpt_ctx* c) {
   for (auto& b : c->lut) free_buf(b);
   for (Buf* b : {&c->worldpos, &c->gradient, &c->depth, &c->prev_pixel, &c->hit_id, &c->raycount, &c->normal_tab, &c->pair_tab, &c->tris,
                  &c->leaf_order, &c->isect_id, &c->isect_leaf, &c->shade, &c->nodes, &c->materials, &c->obj_tris_dev, &c->refit_order,
-                 &c->refit_fbox, &c->bvh_grid_dev, &c->ray_tab})
+                 &c->refit_fbox, &c->bvh_grid_dev, &c->ray_tab, &c->bvh_build_scratch, &c->bvh_build_header})
     free_buf(*b);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;

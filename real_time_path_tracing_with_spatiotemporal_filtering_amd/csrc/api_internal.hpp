@@ -98,6 +98,14 @@ struct rtpt_ctx {
   std::vector<uint32_t> refit_level_first;  // slice of refit_order per height (levels + 1 entries)
   uint32_t n_nodes = 0;
   bool host_refit = false;  // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
+  // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
+  bool device_bvh = false;   // rtpt_scene_upload builds the tree on the device
+  bool lbvh_by_height = false;  // RTPT_LBVH_ORDER=height: the device builder's other node numbering (A/B; same pixels)
+  bool device_tree = false;  // the tree on the device now was built there: bvh_host is empty, every refit runs on the device
+  Buf bvh_build_scratch, bvh_build_header;  // the builder's work area (grows, never shrinks) and its readback words
+  struct rtpt_scene_build_info build_info {};
+  hipEvent_t build_ev[2] = {nullptr, nullptr};  // around a device build; read lazily by rtpt_scene_build_info
+  bool build_ms_pending = false;
   bool use_bvh = false;
   rt::BvhGrid bvh_grid{};
   int bvh_depth = 0;

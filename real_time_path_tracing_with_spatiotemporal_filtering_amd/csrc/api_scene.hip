@@ -2,6 +2,172 @@
 // :687-742), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
 #include "api_internal.hpp"
 
+#include <chrono>
+
+namespace {
+
+double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+rt::ScenePrepArgs scene_prep_args(const rtpt_ctx* c, uint32_t total, bool leaf_pairs) {
+  rt::ScenePrepArgs sp;
+  sp.n_tris = total;
+  sp.tris = static_cast<const float*>(c->tris.ptr);
+  sp.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
+  sp.isect_id = static_cast<float4*>(c->isect_id.ptr);
+  sp.isect_leaf = static_cast<float4*>(c->isect_leaf.ptr);
+  sp.shade = static_cast<float4*>(c->shade.ptr);
+  sp.leaf_pairs = leaf_pairs ? 1u : 0u;
+  return sp;
+}
+
+// The tree over c->tris (`total` triangles as they stand on the device) built on the device (bvh_build.hip) and swapped
+// into the context: nodes, leaf order, nodes by height, depth; then the refit that fills boxes and grid and the leaf
+// records.  Built aside, so a tree deeper than the traversal stack (*too_deep, RTPT_OK) or an error leaves the context's
+// tree as it was.  The stream must be idle on entry (buffers are replaced); synchronises ONCE, for the readback of
+// kLbvhHeaderWords dwords.  Needs c->tris, c->isect_*, c->shade and c->bvh_grid_dev allocated for `total`.
+int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_deep) {
+  *too_deep = false;
+  const uint32_t w = leaf_pairs ? 2u : 1u, n_prims = total / w, n_nodes = n_prims > 1 ? n_prims - 1 : 1;
+  // the traversal addresses leaf records and nodes as base + 32-bit byte offset (48 bytes per triangle at most, 32 per node)
+  if (static_cast<uint64_t>(total) * 48u >= (1ull << 32) || n_nodes >= (1u << 27))
+    return fail(RTPT_E_INVALID, "scene too large for the traversal's 32-bit record offsets (more than 89,478,485 triangles)");
+  const size_t need = rt::lbvh_scratch_bytes(n_prims, c->lbvh_by_height);
+  if (!need) return fail(RTPT_E_DEVICE, "device BVH build: the sort's temporary-storage query failed");
+  int rc;
+  if (c->bvh_build_scratch.bytes < need && (rc = alloc_buf(c->bvh_build_scratch, need))) return rc;
+  if (!c->bvh_build_header.ptr && (rc = alloc_buf(c->bvh_build_header, rt::kLbvhHeaderWords * 4))) return rc;
+  for (hipEvent_t& e : c->build_ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  Buf nodes, leaf_order, refit_order, fbox;
+  auto drop = [&]() {
+    for (Buf* b : {&nodes, &leaf_order, &refit_order, &fbox}) free_buf(*b);
+  };
+  if ((rc = alloc_buf(nodes, static_cast<size_t>(n_nodes) * sizeof(rt::BvhNodeQ))) || (rc = alloc_buf(leaf_order, static_cast<size_t>(total) * 4)) ||
+      (rc = alloc_buf(refit_order, static_cast<size_t>(n_nodes) * 4)) || (rc = alloc_buf(fbox, static_cast<size_t>(n_nodes) * 12 * sizeof(float)))) {
+    drop();
+    return rc;
+  }
+  rt::LbvhArgs la;
+  la.n_prims = n_prims;
+  la.prim_w = w;
+  la.tris = static_cast<const float*>(c->tris.ptr);
+  la.nodes = static_cast<rt::BvhNodeQ*>(nodes.ptr);
+  la.leaf_order = static_cast<uint32_t*>(leaf_order.ptr);
+  la.refit_order = static_cast<uint32_t*>(refit_order.ptr);
+  la.header = static_cast<uint32_t*>(c->bvh_build_header.ptr);
+  la.by_height = c->lbvh_by_height ? 1u : 0u;
+  uint32_t header[rt::kLbvhHeaderWords];
+  hipError_t e = hipEventRecord(c->build_ev[0], c->stream);
+  if (e == hipSuccess) e = rt::launch_lbvh_build(la, c->bvh_build_scratch.ptr, c->bvh_build_scratch.bytes, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(header, c->bvh_build_header.ptr, sizeof header, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    drop();
+    return fail(RTPT_E_DEVICE, std::string("device BVH build: ") + hipGetErrorString(e));
+  }
+  const uint32_t depth = header[0];
+  uint32_t counted = 0, levels = 0;
+  for (uint32_t h = 0; h < rt::kLbvhMaxLevels; h++) {
+    counted += header[2 + h];
+    if (header[2 + h]) levels = h + 1;
+  }
+  if (depth >= static_cast<uint32_t>(rt::kBvhMaxDepth)) {
+    drop();
+    *too_deep = true;
+    return RTPT_OK;
+  }
+  if (header[1] != n_nodes || counted != n_nodes || levels != std::max(depth, 1u)) {
+    drop();
+    return fail(RTPT_E_INVALID, "internal: the device BVH build lost nodes");
+  }
+  // the replaced tree is freed at the end: hipFree waits for the device, and the refit below should not wait behind it
+  Buf old[4] = {c->nodes, c->leaf_order, c->refit_order, c->refit_fbox};
+  c->nodes = nodes;
+  c->leaf_order = leaf_order;
+  c->refit_order = refit_order;
+  c->refit_fbox = fbox;
+  c->n_nodes = n_nodes;
+  c->refit_level_first.assign(static_cast<size_t>(levels) + 1, 0);
+  for (uint32_t h = 0; h < levels; h++) c->refit_level_first[h + 1] = c->refit_level_first[h] + header[2 + h];
+  c->bvh_depth = static_cast<int>(depth);
+  c->leaf_pairs = leaf_pairs;
+  c->device_tree = true;
+  rt::RefitArgs ra;
+  ra.tris = static_cast<const float*>(c->tris.ptr);
+  ra.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
+  ra.order = static_cast<const uint32_t*>(c->refit_order.ptr);
+  ra.nodes = static_cast<rt::BvhNodeQ*>(c->nodes.ptr);
+  ra.fbox = static_cast<float*>(c->refit_fbox.ptr);
+  ra.grid = static_cast<float*>(c->bvh_grid_dev.ptr);
+  rt::launch_refit(ra, c->refit_level_first.data(), static_cast<int>(levels), n_nodes, 1e-5f, c->stream);
+  rt::launch_scene_prepare(scene_prep_args(c, total, leaf_pairs), c->stream);
+  const int rcl = launch_check("device BVH build");
+  const hipError_t ee = hipEventRecord(c->build_ev[1], c->stream);
+  for (Buf& b : old) free_buf(b);
+  c->bvh_host = rt::Bvh{};  // a device-built tree has no host copy (tens of megabytes to unmap for a large scene: after the events)
+  free_buf(c->stack_spill);  // sized by the depth of the tree that was replaced
+  c->stack_spill_blocks = 0;
+  if (rcl) return rcl;
+  HIP_TRY(ee);
+  c->build_ms_pending = true;
+  c->build_info.builder = RTPT_BVH_BUILDER_DEVICE_LBVH;
+  c->build_info.fallback = RTPT_BVH_FALLBACK_NONE;
+  c->build_info.n_primitives = n_prims;
+  c->build_info.n_nodes = n_nodes;
+  c->build_info.depth = depth;
+  c->build_info.leaf_pairs = leaf_pairs ? 1u : 0u;
+  c->build_info.build_ms = 0.f;
+  return RTPT_OK;
+}
+
+// what rtpt_scene_upload leaves behind once the new scene is on the device (either builder)
+void commit_uploaded_scene(rtpt_ctx* c, std::vector<float>& tris, uint32_t total, uint32_t n_tris, bool paired_all) {
+  c->n_tris = total;
+  c->n_base_tris = n_tris;
+  free_buf(c->materials);  // materials belong to the mesh that was replaced
+  if (total <= static_cast<uint32_t>(rt::kCullMaxTris))
+    c->host_tris = tris;
+  else
+    c->host_tris.clear();
+  c->tris_paired = paired_all && total <= static_cast<uint32_t>(rt::kCullMaxTris);  // the brute-force loops
+  c->obj_tris.swap(tris);
+  for (int i = 0; i < 16; i++) c->model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  c->model_version++;
+  c->use_bvh = (total > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);
+  c->lut_prev_valid = false;
+  c->lut_version[0] = c->lut_version[1] = ~0ull;
+  c->tables_valid = false;
+  c->normals_y0 = c->normals_y1 = 0;  // the per-pixel normal plane belongs to the previous scene
+}
+
+// rtpt_scene_upload with RTPT_FLAG_DEVICE_BVH_BUILD: the flattened triangles go up, the tree is built there
+int upload_device_tree(rtpt_ctx* c, std::vector<float>& tris, uint32_t total, uint32_t n_tris, bool paired_all, bool leaf_pairs, bool* too_deep) {
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = alloc_buf(c->tris, tris.size() * sizeof(float)))) return rc;
+  if ((rc = alloc_buf(c->obj_tris_dev, tris.size() * sizeof(float)))) return rc;
+  if ((rc = alloc_buf(c->isect_id, static_cast<size_t>(total) * 48))) return rc;
+  if ((rc = alloc_buf(c->isect_leaf, static_cast<size_t>(total) * 48))) return rc;
+  if ((rc = alloc_buf(c->shade, static_cast<size_t>(total) * 48))) return rc;
+  if ((rc = alloc_buf(c->normal_tab, (static_cast<size_t>(total) + 1) * 32))) return rc;  // normals, then per-id areas
+  if ((rc = alloc_buf(c->pair_tab, total + 1 <= 64 ? (static_cast<size_t>(total) + 1) * (total + 1) * 4 : 0))) return rc;
+  for (int i = 0; i < 2; i++)
+    if ((rc = alloc_buf(c->lut[i], (static_cast<size_t>(total) + 1) * sizeof(rtpt_visibility_data)))) return rc;
+  if ((rc = alloc_buf(c->bvh_grid_dev, 8 * sizeof(float)))) return rc;
+  c->n_tris = 0;  // the previous scene's buffers are gone: no scene until this one is complete
+  HIP_TRY(hipMemcpyAsync(c->tris.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->obj_tris_dev.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->lut[i].ptr, 0, c->lut[i].bytes, c->stream));
+  // the builder's readback synchronises behind these copies, so the staging vector may die at return
+  if ((rc = device_build_tree(c, total, leaf_pairs, too_deep)) || *too_deep) return rc;
+  commit_uploaded_scene(c, tris, total, n_tris, paired_all);
+  return RTPT_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------ scene
@@ -14,6 +180,7 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
     if (idx[i] >= n_verts) return fail(RTPT_E_INVALID, "index out of range");
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
+  const double t_call = now_ms();
   const uint32_t ni = (xf && n_instances) ? n_instances : 1;
   const uint64_t total64 = static_cast<uint64_t>(ni) * n_tris;
   if (total64 >= 0xFFFFFFF0ull) return fail(RTPT_E_INVALID, "too many triangles");
@@ -45,6 +212,18 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
     paired_all = std::memcmp(ta, tb, 12) == 0 && std::memcmp(ta + 6, tb + 3, 12) == 0;
   }
   const bool leaf_pairs = paired_all && !c->no_pairing;
+  uint32_t fallback = RTPT_BVH_FALLBACK_NONE;
+  if (c->device_bvh) {
+    bool too_deep = false;
+    const int rcd = upload_device_tree(c, tris, total, n_tris, paired_all, leaf_pairs, &too_deep);
+    if (rcd) return rcd;
+    if (!too_deep) {
+      c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
+      return RTPT_OK;
+    }
+    fallback = RTPT_BVH_FALLBACK_DEPTH;  // a radix tree deeper than the traversal stack: the host builder bounds its depth
+  }
+  const double t_build = now_ms();
   rt::Bvh bvh;  // built aside: a failed upload leaves the context's scene (and the topology a later refit uses) untouched
   rt::build_bvh(tris.data(), total, bvh, 1e-5f, leaf_pairs);
   if (bvh.max_depth >= rt::kBvhMaxDepth) return fail(RTPT_E_INVALID, "BVH deeper than the traversal stack");
@@ -69,6 +248,7 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   if ((rc = alloc_buf(c->shade, static_cast<size_t>(total) * 48))) return rc;
   std::vector<rt::BvhNodeQ> nodes_h;
   c->bvh_grid = rt::pack_quantised_nodes(bvh, nodes_h);
+  const double build_ms = now_ms() - t_build;
   if ((rc = alloc_buf(c->nodes, nodes_h.size() * sizeof(rt::BvhNodeQ)))) return rc;
   if ((rc = alloc_buf(c->normal_tab, (static_cast<size_t>(total) + 1) * 32))) return rc;  // normals, then per-id areas
   if ((rc = alloc_buf(c->pair_tab, total + 1 <= 64 ? (static_cast<size_t>(total) + 1) * (total + 1) * 4 : 0))) return rc;
@@ -121,28 +301,22 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   rt::launch_scene_prepare(sp, c->stream);
   if ((rc = launch_check("scene_prepare"))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
-  c->n_tris = total;
-  c->n_base_tris = n_tris;
-  free_buf(c->materials);  // materials belong to the mesh that was replaced
   free_buf(c->stack_spill);  // sized by the depth of the tree that was replaced
   c->stack_spill_blocks = 0;
-  if (total <= static_cast<uint32_t>(rt::kCullMaxTris))
-    c->host_tris = tris;
-  else
-    c->host_tris.clear();
-  c->tris_paired = paired_all && total <= static_cast<uint32_t>(rt::kCullMaxTris);  // the brute-force loops
-  c->leaf_pairs = leaf_pairs;                                                        // the tree that was just built
-  c->obj_tris.swap(tris);
-  c->bvh_host = std::move(bvh);  // only now: the upload succeeded
-  for (int i = 0; i < 16; i++) c->model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-  c->model_version++;
-  c->use_bvh = (total > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);
-  c->use_bvh = (total > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);
+  c->leaf_pairs = leaf_pairs;  // the tree that was just built
   c->bvh_depth = bvh.max_depth;
-  c->lut_prev_valid = false;
-  c->lut_version[0] = c->lut_version[1] = ~0ull;
-  c->tables_valid = false;
-  c->normals_y0 = c->normals_y1 = 0;  // the per-pixel normal plane belongs to the previous scene
+  c->device_tree = false;
+  c->build_ms_pending = false;
+  c->build_info.builder = RTPT_BVH_BUILDER_HOST_SAH;
+  c->build_info.fallback = fallback;
+  c->build_info.n_primitives = leaf_pairs ? total / 2 : total;
+  c->build_info.n_nodes = c->n_nodes;
+  c->build_info.depth = static_cast<uint32_t>(bvh.max_depth);
+  c->build_info.leaf_pairs = leaf_pairs ? 1u : 0u;
+  c->build_info.build_ms = static_cast<float>(build_ms);
+  c->bvh_host = std::move(bvh);  // only now: the upload succeeded
+  commit_uploaded_scene(c, tris, total, n_tris, paired_all);
+  c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
   return RTPT_OK;
 }
 
@@ -157,7 +331,9 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
 int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
   const uint32_t total = c->n_tris;
   const bool ident = is_identity(model);
-  if (c->use_bvh && !c->host_refit && c->obj_tris_dev.ptr && c->refit_order.ptr) {
+  // a device-built tree has no host copy (bvh_host is empty): it is refit on the device whatever traces the scene —
+  // also the small scenes that trace by brute force, whose host_tris are still re-posed on the host below
+  if (((c->use_bvh && !c->host_refit) || c->device_tree) && c->obj_tris_dev.ptr && c->refit_order.ptr) {
     // everything on the device and on the context's stream: no upload, no synchronisation (refit.hip)
     rt::RefitModel rm;
     std::memcpy(rm.m, model, sizeof rm.m);
@@ -241,6 +417,36 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
 }
 
 extern "C" {
+
+int rtpt_scene_build_info(rtpt_ctx* c, struct rtpt_scene_build_info* out) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (c->build_ms_pending) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->build_ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->build_ev[0], c->build_ev[1]));
+    c->build_info.build_ms = ms;
+    c->build_ms_pending = false;
+  }
+  *out = c->build_info;
+  return RTPT_OK;
+}
+
+int rtpt_scene_rebuild(rtpt_ctx* c) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!c->n_tris || !c->nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  const double t_call = now_ms();
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the tree's buffers are replaced
+  bool too_deep = false;
+  const int rc = device_build_tree(c, c->n_tris, c->leaf_pairs, &too_deep);
+  if (rc) return rc;
+  if (too_deep) return fail(RTPT_E_INVALID, "the rebuilt BVH would be deeper than the traversal stack: the tree was kept");
+  c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
+  return RTPT_OK;
+}
 
 int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material* materials,
                              uint32_t n_materials) {

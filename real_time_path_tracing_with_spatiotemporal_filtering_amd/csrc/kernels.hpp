@@ -270,6 +270,21 @@ struct RefitArgs {
 void launch_pose(uint32_t n_verts, const float* src, float* dst, const RefitModel& m, hipStream_t s);
 // level_first[h] .. level_first[h + 1]: the slice of `order` holding the nodes of height h (n_levels + 1 entries)
 void launch_refit(const RefitArgs& a, const uint32_t* level_first, int n_levels, uint32_t n_nodes, float pad_rel, hipStream_t s);
+// device-side LBVH build (bvh_build.hip): the topology only — launch_refit + launch_scene_prepare fill boxes, grid and records
+constexpr uint32_t kLbvhMaxLevels = 128;                  // heights the histogram distinguishes (63 + 32 key bits: at most 95)
+constexpr uint32_t kLbvhHeaderWords = 2 + kLbvhMaxLevels;  // [0] depth, [1] nodes, [2 + h] nodes of height h: ONE readback
+struct LbvhArgs {
+  uint32_t n_prims;       // primitives: fan pairs (2q, 2q + 1) when prim_w == 2, triangles when 1
+  uint32_t prim_w;
+  const float* tris;      // n_prims x prim_w x 9 world-space floats
+  BvhNodeQ* nodes;        // max(n_prims - 1, 1) nodes: references set, boxes zero
+  uint32_t* leaf_order;   // n_prims x prim_w
+  uint32_t* refit_order;  // the nodes sorted by height
+  uint32_t* header;       // kLbvhHeaderWords
+  uint32_t by_height;     // A/B: number the nodes by descending height instead of pre-order (RTPT_LBVH_ORDER=height)
+};
+size_t lbvh_scratch_bytes(uint32_t n_prims, bool by_height);  // 0: the sort's size query failed
+hipError_t launch_lbvh_build(const LbvhArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s);
 // gather isect records into class order: out[t] = isect_id[ids[t]] (3 float4 each), n entries
 void launch_lut(const LutArgs& a, hipStream_t s);
 void launch_gbuffer(const GbufferArgs& a, hipStream_t s);

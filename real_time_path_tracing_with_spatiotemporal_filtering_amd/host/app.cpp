@@ -719,6 +719,17 @@ uint64_t PathTracingApplication::bytesSent() const {
   return (transport_ ? transport_->bytes_sent() : 0) + (presentTransport_ ? presentTransport_->bytes_sent() : 0);
 }
 
+std::string PathTracingApplication::buildLine() {
+  rtpt_ctx* c = multi() ? (ranks_.empty() ? nullptr : ranks_.front().ctxs[0]) : ctxs_[0];
+  struct rtpt_scene_build_info bi;
+  check(rtpt_scene_build_info(c, &bi), "rtpt_scene_build_info");
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "rtpt_app: BVH over %u %s built by %s%s: %u nodes, depth %u, build %.3f ms, upload %.3f ms", bi.n_primitives,
+                bi.leaf_pairs ? "fan pairs" : "triangles", bi.builder == RTPT_BVH_BUILDER_DEVICE_LBVH ? "device LBVH" : "host SAH",
+                bi.fallback == RTPT_BVH_FALLBACK_DEPTH ? " (device tree too deep)" : "", bi.n_nodes, bi.depth, bi.build_ms, bi.upload_ms);
+  return buf;
+}
+
 void PathTracingApplication::sync() {
   if (multi()) {
     for (auto& rs : ranks_)

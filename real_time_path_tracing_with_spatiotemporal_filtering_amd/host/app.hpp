@@ -78,6 +78,7 @@ class PathTracingApplication {
   // width*height*4 bytes B,G,R,A (rgba8) or width*height*16 bytes of floats (f32).  Empty on the other ranks' processes.
   std::vector<unsigned char> readPresented();
   uint64_t rayCount();
+  std::string buildLine();                     // what built the acceleration structure, and how long it took (rtpt_scene_build_info)
   uint64_t bytesSent() const;                  // strips: bytes this process sent (halo rows + history bands)
   // host-only (no GPU, no context): the strip plan of every rank and, per scripted frame, the previous-frame rows each
   // rank's final pass can reach — as one JSON object; what the CPU tests compare with the Python mirror

@@ -20,6 +20,7 @@ static void usage(const char* argv0) {
       "          [--scene file.obj] [--script \"keys0,keys1,...\"] [--dump out.pfm] [--exact-filter]\n"
       "          [--tessellate n] [--lattice NXxNYxNZ [--pitch P] | --instances file] [--dump-scene out.bin]\n"
       "          [--frames-in-flight 1|2]\n"
+      "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
       "          [--present none|rgba8|f32 [--dump-present out.raw]]\n"
       "          [--plan-only   (print the strip plan and the history bands of the scripted frames as JSON; needs no GPU)]\n"
@@ -77,6 +78,7 @@ int main(int argc, char** argv) {
     }
     else if (!std::strcmp(argv[i], "--dump")) dump = need("--dump");
     else if (!std::strcmp(argv[i], "--exact-filter")) opt.flags |= RTPT_FLAG_EXACT_FILTER;
+    else if (!std::strcmp(argv[i], "--device-bvh")) opt.flags |= RTPT_FLAG_DEVICE_BVH_BUILD;
     else if (!std::strcmp(argv[i], "--frames-in-flight")) opt.frames_in_flight = std::atoi(need("--frames-in-flight"));
     else if (!std::strcmp(argv[i], "--ranks")) opt.ranks = std::atoi(need("--ranks"));
     else if (!std::strcmp(argv[i], "--rank")) opt.rank = std::atoi(need("--rank"));
@@ -128,6 +130,7 @@ int main(int argc, char** argv) {
     app.initVulkan();
     if (!dump_scene.empty()) app.dumpScene(dump_scene);
     app.sync();
+    std::printf("%s\n", app.buildLine().c_str());
     auto t0 = std::chrono::steady_clock::now();
     for (int f = 0; f < frames; f++) app.drawScene(static_cast<size_t>(f) < script.size() ? script[static_cast<size_t>(f)] : "");
     app.sync();

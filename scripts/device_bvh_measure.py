@@ -1,0 +1,102 @@
+"""Device-side BVH build (csrc/bvh_build.hip) against the host SAH builder, on the GPU in front of you:
+
+* build_ms / upload_ms of rtpt_scene_upload for the Cornell box, a 3,000-triangle soup and the 1,152,000-triangle lattice
+  (BASELINE configs[4]), each builder, after one warm-up upload (code objects load lazily);
+* on the lattice under a sheared model: the frame time with the refit tree, the cost of rtpt_scene_rebuild, the frame time
+  with the rebuilt tree — the figure that says when a rebuild pays.
+
+    python scripts/device_bvh_measure.py [--frames 30] [--small]      # one JSON line per measurement
+    rocprofv3 --kernel-trace --stats -d out -- python scripts/device_bvh_measure.py --builds-only   # the per-kernel split
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--small", action="store_true", help="1080p frames instead of 4K")
+    ap.add_argument("--builds-only", action="store_true")
+    args = ap.parse_args()
+    try:
+        import torch
+        torch.cuda.is_available()
+    except Exception:
+        pass
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi, scenes
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd.app import DEFAULT_SCENE, HipBackend, PathTracingApplication
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd.strips import StripPlan
+    D = abi.FLAG_DEVICE_BVH_BUILD
+    xyz, idx = abi.load_obj(DEFAULT_SCENE)
+    rng = np.random.default_rng(707)
+    c = rng.uniform(-0.8, 0.8, (3000, 1, 3))
+    soup = ((c + rng.normal(0, 0.08, (3000, 3, 3))).astype(np.float32).reshape(-1, 3), np.arange(9000, dtype=np.uint32).reshape(-1, 3))
+    vx, ti, xf, cam, zfar = scenes.instanced_cornell(xyz, idx)
+    cases = {"cornell": (xyz, idx, None), "soup3000": soup + (None,), "lattice": (vx, ti, xf)}
+
+    def upload(flags, mesh):
+        cfg = abi.config_default(64, 64)
+        cfg.flags = flags
+        with abi.Context(cfg) as ctx:
+            t0 = time.perf_counter()
+            ctx.scene_upload(*mesh)
+            wall = (time.perf_counter() - t0) * 1e3
+            return dict(ctx.scene_build_info(), wall_ms=round(wall, 3))
+
+    upload(D, cases["soup3000"])  # warm-up
+    upload(0, cases["soup3000"])
+    for name, mesh in cases.items():
+        for rep in range(2):
+            for label, flags in (("device", D), ("host", 0)):
+                print(json.dumps({"what": "upload", "scene": name, "asked": label, "rep": rep, **upload(flags, mesh)}), flush=True)
+    if args.builds_only:
+        return
+
+    w, h = (1920, 1080) if args.small else (3840, 2160)
+    n = 5
+    shear = np.eye(4)
+    shear[:3, :3] = [[1.0, 0.8, 0.0], [0.0, 1.0, 0.0], [0.6, 0.0, 1.0]]
+    shear = np.ascontiguousarray(shear.astype(np.float32).T).ravel()
+    for upload_flags in (0, D):
+        be = HipBackend(w, h, StripPlan(h, 1, 0, n), max_segments=8, flags=upload_flags)
+        app = PathTracingApplication(be, w, h, n, cameraOrigin=cam, z_far=zfar, lightPos=(1.0, float(cam[1]), float(cam[2]) - 8.0))
+        app.objVertices, app.objIndices = vx, ti
+        app.buildAccelerationStructure(xf)
+        ctx = be.ctx
+
+        def frames(k):
+            for _ in range(5):
+                app.drawScene(())
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(k):
+                app.drawScene(())
+            ctx.sync()
+            return (time.perf_counter() - t0) * 1e3 / k
+
+        base = frames(args.frames)
+        app.modelMatrix = shear
+        refit = frames(args.frames)
+        t0 = time.perf_counter()
+        ctx.scene_rebuild()
+        ctx.sync()
+        rebuild_wall = (time.perf_counter() - t0) * 1e3
+        info = ctx.scene_build_info()
+        rebuilt = frames(args.frames)
+        print(json.dumps({"what": "rebuild_vs_refit", "scene": "lattice sheared", "size": [w, h], "uploaded_by": "device" if upload_flags else "host",
+                          "ms_per_frame_identity": round(base, 4), "ms_per_frame_refit_tree": round(refit, 4),
+                          "ms_per_frame_rebuilt_tree": round(rebuilt, 4), "rebuild_wall_ms": round(rebuild_wall, 3),
+                          "rebuild_build_ms": round(info["build_ms"], 3), "depth": info["depth"]}), flush=True)
+        be.close()
+
+
+if __name__ == "__main__":
+    main()
