@@ -307,6 +307,20 @@ int rtpt_scene_build_info(rtpt_ctx* ctx, struct rtpt_scene_build_info* out);
  * the stack the old one stays and the call returns RTPT_E_INVALID. */
 int rtpt_scene_rebuild(rtpt_ctx* ctx);
 
+/* Frame reuse.  K0 and K1 (rtpt_gbuffer, rtpt_temporal_gradient) read the camera, the light, the posed scene and the LUTs
+ * and nothing that changes from frame to frame by itself: no frame number, no random stream.  While all of those rest,
+ * both passes would store the bytes their planes already hold, so the context launches neither and rtpt_raytrace runs
+ * the tracing kernel alone; every plane, the ray count and the finished frame equal those of a context that runs them.
+ * The id plane rotates at rtpt_end_frame, so the third consecutive frame with equal inputs is the first one served.
+ * A plane's content counts as known only while the passes are its only writer: rtpt_set_plane, rtpt_plane_ptr (the
+ * caller can write through the pointer: write before the next rtpt_gbuffer, or ask again), rtpt_bind_plane,
+ * rtpt_resize, rtpt_set_stream with another stream and rtpt_enable_debug with another mask make the next frame compute
+ * it again, and a plane bound with rtpt_bind_plane is never reused.
+ * RTPT_NO_FRAME_REUSE=1 in the environment of rtpt_create turns all of it off.
+ * out: [0] frames whose K0 + K1 were not launched, [1] and [2] reserved for a cached reprojection of the final pass (0),
+ * [3] plane tags invalidated. */
+int rtpt_debug_reuse_info(rtpt_ctx* ctx, uint64_t out[4]);
+
 /* ---- per-frame passes, one call per reference dispatch ----------------------------------- */
 
 /* drawVisbilityBuffer (main.cpp:1187-1199; visibility.{vert,geom,frag}.glsl): id, world

@@ -108,6 +108,7 @@ SYMBOLS = [
     "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check", "rtpt_util_bvh_check_pairs",
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
+    "rtpt_debug_reuse_info",
 ]
 
 _lib = None
@@ -168,6 +169,7 @@ def load() -> C.CDLL:
         "rtpt_debug_bvh_check": [vp, C.POINTER(C.c_uint64 * 8)],
         "rtpt_scene_build_info": [vp, C.POINTER(SceneBuildInfo)],
         "rtpt_scene_rebuild": [vp],
+        "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
     }
     for name, args in sigs.items():
@@ -338,6 +340,12 @@ class Context:
     def scene_rebuild(self):
         """a new tree, built on the device over the triangles as currently posed (rtpt_scene_rebuild)"""
         _check(self._lib.rtpt_scene_rebuild(self._h))
+
+    def reuse_info(self) -> dict:
+        """frame reuse as observed so far (rtpt_debug_reuse_info)"""
+        out = (C.c_uint64 * 4)()
+        _check(self._lib.rtpt_debug_reuse_info(self._h, C.byref(out)))
+        return dict(zip(("frames_skipped", "reproj_stores", "reproj_loads", "tags_invalidated"), (int(v) for v in out)))
 
     def set_materials(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
         """per-triangle material indices + (Kd, Ke) rows; None returns to the reference's normal-keyed colours"""

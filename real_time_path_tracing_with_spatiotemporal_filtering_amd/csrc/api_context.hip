@@ -240,6 +240,7 @@ static int alloc_planes(rtpt_ctx* c) {
   if (rc == RTPT_OK && !c->raycount.ptr) rc = alloc_buf(c->raycount, 8 * rt::kRayCounters);
   for (auto& b : c->path_queue) free_buf(b);  // sized per frame: re-created by the next rtpt_raytrace
   free_buf(c->normals);  // sized per frame: re-created by the next rtpt_gbuffer
+  reuse_invalidate(c, nullptr);  // new, cleared planes
   c->normals_y0 = c->normals_y1 = 0;
   if (c->cfg.flags & RTPT_FLAG_EXT_VARIANCE) {
     for (int i = 0; i < 2 && rc == RTPT_OK; i++) rc = alloc_buf(c->moments[i], px * 16);
@@ -337,6 +338,7 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   if (const char* v = std::getenv("RTPT_DEVICE_BVH")) c->device_bvh = c->device_bvh || std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_LBVH_ORDER")) c->lbvh_by_height = !std::strcmp(v, "height");
   if (const char* v = std::getenv("RTPT_NO_TRACE_FUSION")) c->fuse_trace = std::atoi(v) == 0;
+  if (const char* v = std::getenv("RTPT_NO_FRAME_REUSE")) c->frame_reuse = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_TRACE_POOL")) c->trace_pool = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_PT_WINDOW")) c->trace_window = static_cast<uint32_t>(std::max(0, std::atoi(v)));
   if (const char* v = std::getenv("RTPT_CHAIN_G1")) c->filter_policy.chain_g_pin = std::atoi(v);
@@ -419,7 +421,9 @@ int rtpt_resize(rtpt_ctx* c, uint32_t width, uint32_t height, uint32_t row_begin
 int rtpt_set_stream(rtpt_ctx* c, void* hip_stream) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   FLUSH_FILTER(c);
-  c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
+  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
+  if (s != c->stream) reuse_invalidate(c, nullptr);  // a reused plane was written on the other stream, in no order with this one
+  c->stream = s;
   return RTPT_OK;
 }
 
@@ -435,6 +439,7 @@ int rtpt_plane_ptr(rtpt_ctx* c, rtpt_plane which, void** device_ptr) {
   FLUSH_FILTER(c);  // roles rotate when recorded iterations run
   Buf* b = plane_buf(c, which);
   if (!b) return fail(RTPT_E_INVALID, "unknown plane");
+  reuse_invalidate(c, b);  // the caller can write through the pointer
   *device_ptr = b->ptr;
   return RTPT_OK;
 }
@@ -446,6 +451,7 @@ int rtpt_bind_plane(rtpt_ctx* c, rtpt_plane which, void* device_ptr, size_t byte
   if (!b || which == RTPT_PLANE_RAYCOUNT || which == RTPT_PLANE_LUT || which == RTPT_PLANE_LUT_PREV)
     return fail(RTPT_E_INVALID, "plane cannot be bound");
   const size_t need = plane_size(c, which);
+  reuse_invalidate(c, b);
   if (device_ptr == nullptr) {
     if (b->owned) return RTPT_OK;
     return alloc_buf(*b, need);
@@ -521,7 +527,16 @@ int rtpt_enable_debug(rtpt_ctx* c, uint32_t mask) {
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->prev_pixel.ptr, 0, c->pixels() * 8, c->stream));
   }
+  if (mask != c->debug_mask) reuse_invalidate(c, nullptr);  // what the passes write changes with the mask
   c->debug_mask = mask;
+  return RTPT_OK;
+}
+
+// frame reuse, observed: [0] frames whose K0 + K1 were not launched, [1], [2] reserved (a cached reprojection of the final
+// pass: not built in, 0), [3] plane tags invalidated
+int rtpt_debug_reuse_info(rtpt_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  for (int i = 0; i < 4; i++) out[i] = c->reuse_info[i];
   return RTPT_OK;
 }
 
@@ -572,6 +587,7 @@ int rtpt_set_plane(rtpt_ctx* c, rtpt_plane which, const void* src, size_t bytes)
   const size_t need = plane_size(c, which);
   if (bytes < need) return fail(RTPT_E_INVALID, "source too small");
   HIP_TRY(hipSetDevice(c->device));
+  reuse_invalidate(c, b);
   HIP_TRY(hipMemcpyAsync(b->ptr, src, need, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int i = 0; i < 3; i++)

@@ -52,6 +52,35 @@ struct TimedLaunch {
   hipEvent_t start, stop;
 };
 
+// Frame reuse: K0 and K1 are functions of what these keys hold and of nothing else (no frame number, no random stream), so a
+// plane that still carries the key of the pass about to write it already holds that pass's output.  Compared as bytes
+// (new_key zero-fills the padding); a float that compares equal with other bits (-0) only costs a recomputation.
+struct K0Key {
+  float org[3], c0[3], c1[3], c2[3];  // camera origin and basis
+  float PV[16], p00, p11, tmax;
+  int32_t W, H, row_base, y0, y1;
+  int32_t normals_on;                 // the per-pixel normal plane is written too
+  uint64_t model_version, scene_gen;
+};
+struct K1Key {
+  K0Key k0;
+  float cam[3], light[3], light_prev[3], color[3], color_prev[3];
+  int32_t y0, y1;
+  uint64_t lut_version[2];            // of LUT and LUT_PREV, in that order
+};
+template <class K>
+inline K new_key() {
+  K k;
+  std::memset(&k, 0, sizeof k);
+  return k;
+}
+template <class K>
+struct PlaneTag {  // what a plane the context owns holds: the output of the pass with this key, over the key's rows
+  bool valid = false;
+  K key;
+  bool holds(const K& k) const { return valid && std::memcmp(&key, &k, sizeof k) == 0; }
+};
+
 
 }  // namespace rtpt_impl
 using namespace rtpt_impl;
@@ -146,6 +175,16 @@ struct rtpt_ctx {
   // recorded K0 (+ K1): rtpt_raytrace right behind them launches all three as one grid (kernels.hip: k_gbuffer_pathtrace);
   // RTPT_NO_TRACE_FUSION=1 (read at rtpt_create) keeps K0 + K1 a launch of their own for A/B runs
   bool fuse_trace = true;
+  // Frame reuse (api_passes.hip: reuse_covers): while camera, light and scene rest, the recorded K0 + K1 would rewrite the
+  // planes with the bytes they hold, so neither is launched.  vis[] rotates at rtpt_end_frame — the buffer about to be
+  // written holds the frame before last — hence the third consecutive frame with equal keys is the first one served.
+  // RTPT_NO_FRAME_REUSE=1 (read at rtpt_create) turns it off.
+  bool frame_reuse = true;
+  uint64_t scene_gen = 0;  // bumped by everything that changes the geometry or the tree the passes traverse
+  K1Key pending_key;       // of pending_gb (k0 from rtpt_gbuffer, the rest once rtpt_temporal_gradient joined it)
+  PlaneTag<K0Key> tag_vis[2], tag_worldpos, tag_depth, tag_normals;
+  PlaneTag<K1Key> tag_gradient;
+  uint64_t reuse_info[4] = {0, 0, 0, 0};  // rtpt_debug_reuse_info
   // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (kernels.hip: k_pathtrace_pool): RTPT_TRACE_POOL
   // (read at rtpt_create); path_pool = the workgroups' slabs, allocated on first use
   bool trace_pool = false;
@@ -187,6 +226,8 @@ namespace rtpt_impl {
 // K3 iterations recorded by rtpt_temporal_filter are launched before anything else looks at or changes the planes
 int filter_flush(rtpt_ctx* c, bool fuse);
 int gbuffer_flush(rtpt_ctx* c);
+// frame reuse: something other than K0 / K1 may write plane b (NULL: any plane) — its tag no longer describes it
+void reuse_invalidate(rtpt_ctx* c, const Buf* b);
 #define FLUSH_FILTER(c)                              \
   do {                                               \
     int rcf_ = gbuffer_flush(c);                     \

@@ -3,6 +3,81 @@
 // the filter iterations until the last one arrives (api_internal.hpp: FLUSH_FILTER).
 #include "api_internal.hpp"
 
+namespace rtpt_impl {
+void reuse_invalidate(rtpt_ctx* c, const Buf* b) {
+  auto kill = [&](auto& tag, const Buf* of) {
+    if ((!b || b == of) && tag.valid) {
+      tag.valid = false;
+      c->reuse_info[3]++;
+    }
+  };
+  kill(c->tag_vis[0], &c->vis[0]);
+  kill(c->tag_vis[1], &c->vis[1]);
+  kill(c->tag_worldpos, &c->worldpos);
+  kill(c->tag_depth, &c->depth);
+  kill(c->tag_normals, &c->normals);
+  kill(c->tag_gradient, &c->gradient);
+  // K1 reads both LUT buffers, and their version does not see a write through a pointer handed out
+  if (b == &c->lut[0] || b == &c->lut[1]) kill(c->tag_gradient, b);
+}
+}  // namespace rtpt_impl
+
+namespace {
+
+// the key of the K0 call `a` was built for (api_internal.hpp: K0Key)
+K0Key gbuffer_key(const rtpt_ctx* c, const rt::GbufferArgs& a) {
+  K0Key k = new_key<K0Key>();
+  std::memcpy(k.org, a.org, sizeof k.org);
+  std::memcpy(k.c0, a.c0, sizeof k.c0);
+  std::memcpy(k.c1, a.c1, sizeof k.c1);
+  std::memcpy(k.c2, a.c2, sizeof k.c2);
+  std::memcpy(k.PV, a.PV, sizeof k.PV);
+  k.p00 = a.p00;
+  k.p11 = a.p11;
+  k.tmax = a.tmax;
+  k.W = a.g.W;
+  k.H = a.g.H;
+  k.row_base = a.g.row_base;
+  k.y0 = a.g.y0;
+  k.y1 = a.g.y1;
+  k.normals_on = a.normals ? 1 : 0;
+  k.model_version = c->model_version;
+  k.scene_gen = c->scene_gen;
+  return k;
+}
+
+// the planes K0 (+ K1 when a.grad_on) of `a` writes now carry `key`; NULL, or a plane the context does not own (its owner can
+// write it unseen): they carry nothing
+void tag_outputs(rtpt_ctx* c, const rt::GbufferArgs& a, const K1Key* key) {
+  auto set = [&](auto& tag, const Buf& b, const auto* k) {
+    if (tag.valid) c->reuse_info[3] += (!k || !b.owned) ? 1 : 0;
+    tag.valid = k && b.owned && c->frame_reuse;
+    if (tag.valid) tag.key = *k;
+  };
+  const K0Key* k0 = key ? &key->k0 : nullptr;
+  for (int i = 0; i < 2; i++)
+    if (a.vis == c->vis[i].ptr) set(c->tag_vis[i], c->vis[i], k0);
+  set(c->tag_worldpos, c->worldpos, k0);
+  set(c->tag_depth, c->depth, k0);
+  if (a.normals) set(c->tag_normals, c->normals, k0);
+  if (a.grad_on) set(c->tag_gradient, c->gradient, key);
+}
+
+// would the recorded K0 + K1 rewrite every plane with the bytes it holds?  All or nothing: one plane that does not carry the
+// key of its pass and both passes run
+bool reuse_covers(const rtpt_ctx* c) {
+  const rt::GbufferArgs& a = c->pending_gb;
+  const K1Key& k = c->pending_key;
+  if (!c->frame_reuse || !a.grad_on) return false;
+  if (k.lut_version[0] == ~0ull || k.lut_version[1] == ~0ull) return false;  // injected LUT content
+  const int v = a.vis == c->vis[0].ptr ? 0 : 1;
+  if (a.vis != c->vis[v].ptr || !c->tag_vis[v].holds(k.k0)) return false;
+  if (!c->tag_worldpos.holds(k.k0) || !c->tag_depth.holds(k.k0) || !c->tag_gradient.holds(k)) return false;
+  return !a.normals || c->tag_normals.holds(k.k0);
+}
+
+}  // namespace
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------ K0
@@ -102,6 +177,7 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
       int rc2 = alloc_buf(c->normals, c->pixels() * 16);
       if (rc2) return rc2;
       c->normals_y0 = c->normals_y1 = 0;
+      reuse_invalidate(c, &c->normals);
     }
     a.normals = static_cast<float4*>(c->normals.ptr);
     // rows written so far this frame (strips call the pass once per range; a new frame starts a new range)
@@ -123,8 +199,11 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
     // any other entry point launches it first
     c->pending_gb = a;
     c->pending_gb_valid = true;
+    c->pending_key = new_key<K1Key>();
+    c->pending_key.k0 = gbuffer_key(c, a);
     return RTPT_OK;
   }
+  tag_outputs(c, a, nullptr);  // launched unrecorded: the planes are rewritten, nothing keeps track of with what
   {
     Timer tm(c, RTPT_K_GBUFFER);
     rt::launch_gbuffer(a, c->stream);
@@ -140,6 +219,11 @@ int gbuffer_flush(rtpt_ctx* c) {
   c->pending_gb_valid = false;
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (reuse_covers(c)) {  // every plane already holds what this launch would store
+    c->reuse_info[0]++;
+    return RTPT_OK;
+  }
+  tag_outputs(c, c->pending_gb, &c->pending_key);
   {
     Timer tm(c, c->pending_gb.grad_on ? RTPT_K_GBUFFER_GRADIENT : RTPT_K_GBUFFER);
     rt::launch_gbuffer(c->pending_gb, c->stream);
@@ -173,6 +257,18 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
     g.lut = static_cast<const float4*>(c->lut[c->lut_cur].ptr);
     g.lut_prev = static_cast<const float4*>(c->lut[c->lut_cur ^ 1].ptr);
     g.grad = static_cast<float4*>(c->gradient.ptr);
+    {
+      K1Key& k = c->pending_key;
+      std::memcpy(k.cam, g.g_cam, sizeof k.cam);
+      std::memcpy(k.light, g.g_light, sizeof k.light);
+      std::memcpy(k.light_prev, g.g_light_prev, sizeof k.light_prev);
+      std::memcpy(k.color, g.g_color, sizeof k.color);
+      std::memcpy(k.color_prev, g.g_color_prev, sizeof k.color_prev);
+      k.y0 = g.grad_y0;
+      k.y1 = g.grad_y1;
+      k.lut_version[0] = c->lut_version[c->lut_cur];
+      k.lut_version[1] = c->lut_version[c->lut_cur ^ 1];
+    }
     int rcq = filter_flush(c, false);
     if (rcq) return rcq;
     // stays recorded: rtpt_raytrace normally follows at once (main.cpp:1107) and takes both passes into its launch; any other
@@ -197,6 +293,7 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
   a.normal_tab = static_cast<const float4*>(c->normal_tab.ptr);
   a.area_tab = a.normal_tab + (c->n_tris + 1);
   a.grad = static_cast<float4*>(c->gradient.ptr);
+  reuse_invalidate(c, &c->gradient);  // launched unrecorded
   {
     Timer tm(c, RTPT_K_GRADIENT);
     rt::launch_gradient(a, c->stream);
@@ -278,16 +375,25 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   c->final_swapped = false;
   c->image_alias = false;
   // K0 (+ K1) recorded right before this call run inside this launch, behind the tracing tiles (kernels.hip: k_gbuffer_pathtrace)
-  const bool fused = c->pending_gb_valid && c->fuse_trace && rt::pathtrace_fuses_gbuffer(a, c->pending_gb);
-  if (!fused && (rc = gbuffer_flush(c))) return rc;
+  const bool joined = c->pending_gb_valid && c->fuse_trace && rt::pathtrace_fuses_gbuffer(a, c->pending_gb);
+  if (!joined && (rc = gbuffer_flush(c))) return rc;
+  // frame reuse: the planes hold what the recorded passes would store, so the launch carries the tracing tiles only — the
+  // un-fused kernel, which takes the depth for the traced image's alpha from the depth plane.  It is still timed as the launch
+  // that serves K0 + K1 + K2
+  const bool reused = joined && reuse_covers(c);
+  const bool fused = joined && !reused;
   if ((rc = ensure_stack_spill(c, std::max<size_t>(frame_blocks(c), rt::pathtrace_grid_blocks(a, fused ? &c->pending_gb : nullptr))))) return rc;
   a.scene = scene_view(c);
-  if (fused) {
+  if (joined) {
     c->pending_gb.scene = a.scene;  // the spill area may have moved since the G-buffer call was recorded
     c->pending_gb_valid = false;
+    if (reused)
+      c->reuse_info[0]++;
+    else
+      tag_outputs(c, c->pending_gb, &c->pending_key);
   }
   {
-    Timer tm(c, fused ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
+    Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, c->stream);
   }
   return launch_check(fused ? "gbuffer + temporal_gradient + raytrace" : "raytrace");

@@ -135,6 +135,7 @@ void commit_uploaded_scene(rtpt_ctx* c, std::vector<float>& tris, uint32_t total
   c->obj_tris.swap(tris);
   for (int i = 0; i < 16; i++) c->model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
   c->model_version++;
+  c->scene_gen++;
   c->use_bvh = (total > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);
   c->lut_prev_valid = false;
   c->lut_version[0] = c->lut_version[1] = ~0ull;
@@ -372,6 +373,7 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
     }
     std::memcpy(c->model, model, sizeof c->model);
     c->model_version++;
+  c->scene_gen++;
     c->tables_valid = false;
     return RTPT_OK;
   }
@@ -412,6 +414,7 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
   if (total <= static_cast<uint32_t>(rt::kCullMaxTris)) c->host_tris.swap(tris);
   std::memcpy(c->model, model, sizeof c->model);
   c->model_version++;
+  c->scene_gen++;
   c->tables_valid = false;  // per-id normals and pair weights follow the posed triangles
   return RTPT_OK;
 }
@@ -440,6 +443,7 @@ int rtpt_scene_rebuild(rtpt_ctx* c) {
   FLUSH_FILTER(c);
   const double t_call = now_ms();
   HIP_TRY(hipStreamSynchronize(c->stream));  // the tree's buffers are replaced
+  c->scene_gen++;  // another tree may resolve a tie between equally near triangles differently
   bool too_deep = false;
   const int rc = device_build_tree(c, c->n_tris, c->leaf_pairs, &too_deep);
   if (rc) return rc;
