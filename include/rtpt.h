@@ -145,6 +145,17 @@ typedef struct rtpt_visibility_data {
                                               slower than the SAH tree.  RTPT_DEVICE_BVH=1 in rtpt_create's environment sets it
                                               too.  A device-built tree has no host copy: it is always refit on the device,
                                               RTPT_HOST_REFIT does not apply to it.  ABI version 5 */
+#define RTPT_FLAG_DEVICE_BVH_SAH 0x2000u   /* together with RTPT_FLAG_DEVICE_BVH_BUILD (alone it is ignored): the device build is
+                                              the SAH builder of csrc/bvh_build_sah.hip, a level-synchronous restatement of the
+                                              host's 32-bin SAH builder that reproduces the host's tree node for node (same
+                                              child references, same leaf order up to the order inside a two-triangle leaf), so
+                                              the frame costs what it costs with the host-built tree (measured equal within the
+                                              run-to-run spread) and the build runs on the device.
+                                              rtpt_scene_upload and rtpt_scene_rebuild both use it; it blocks one to three times
+                                              per level of the tree for a readback of a few words.  No depth fallback: the tree has
+                                              the host tree's (bounded) depth.  RTPT_DEVICE_BVH=sah in rtpt_create's environment
+                                              sets both bits.  Purely additive (a flag bit, a builder value, one debug entry
+                                              point): the ABI version stays 5 */
 
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
@@ -281,8 +292,9 @@ int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32
  * same name, and C keeps tags and functions apart.) */
 enum { RTPT_BVH_BUILDER_HOST_SAH = 0, RTPT_BVH_BUILDER_DEVICE_LBVH = 1 };
 enum { RTPT_BVH_FALLBACK_NONE = 0, RTPT_BVH_FALLBACK_DEPTH = 1 };
+enum { RTPT_BUILDER_DEVICE_SAH = 2 }; /* a third value of `builder`: RTPT_FLAG_DEVICE_BVH_SAH built the tree */
 struct rtpt_scene_build_info {
-  uint32_t builder, fallback; /* RTPT_BVH_BUILDER_*, and why it is not the one asked for: RTPT_BVH_FALLBACK_* */
+  uint32_t builder, fallback; /* RTPT_BVH_BUILDER_* or RTPT_BUILDER_DEVICE_SAH, and why it is not the one asked for: RTPT_BVH_FALLBACK_* */
   uint32_t n_primitives;      /* what the tree was built over: fan pairs (leaf_pairs) or triangles */
   uint32_t n_nodes, depth;    /* child-pair nodes; level of the deepest leaf (the root pair's children are at 1) */
   uint32_t leaf_pairs;        /* 1: every leaf is one fan pair (2q, 2q + 1) */
@@ -474,6 +486,13 @@ int rtpt_util_bvh_check_pairs(const float* tris, uint32_t n_tris, int pairs, uin
  *   [7] dangling child references, and when the tree was built over fan pairs, leaves that are not one pair (as
  *   rtpt_util_bvh_check_pairs) */
 int rtpt_debug_bvh_check(rtpt_ctx* ctx, uint64_t stats[8]);
+/* The TOPOLOGY of that structure, read back (blocks): child_refs[2 i], child_refs[2 i + 1] = the left and right child
+ * reference of node i in node order (bit 31 set: leaf, (first slot << 2) | (count - 1); clear: node index; 0xFFFFFFFF: absent),
+ * leaf_order[slot] = triangle id.  Two calls like the loaders: with both arrays NULL it stores the counts (nodes, leaf
+ * slots = triangles); with arrays, *n_nodes and *n_leaf_ids say how many entries they hold (2 x *n_nodes references) and
+ * must be at least the counts.  Two trees are the same tree exactly when these arrays are equal, whatever built them.
+ * RTPT_E_NO_SCENE before an upload, RTPT_E_INVALID on a NULL context or count pointer or a short array. */
+int rtpt_debug_bvh_topology(rtpt_ctx* ctx, uint32_t* child_refs, uint32_t* n_nodes, uint32_t* leaf_order, uint32_t* n_leaf_ids);
 /* the same invariants after a REFIT: the tree is built over `built_for` and refit to `moved` (the same n_tris
  * triangles after an animated model matrix, rtpt_gbuffer) — topology and leaf order kept, boxes recomputed */
 int rtpt_util_bvh_refit_check(const float* built_for, const float* moved, uint32_t n_tris, uint64_t stats[8]);

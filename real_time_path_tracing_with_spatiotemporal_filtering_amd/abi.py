@@ -27,7 +27,9 @@ FLAG_NO_FILTER_FUSION = 0x400
 FLAG_EXT_SVGF_VARIANCE = 0x800
 FLAG_EXT_MASK = 0x9F0
 FLAG_DEVICE_BVH_BUILD = 0x1000  # rtpt_scene_upload builds the tree on the device (csrc/bvh_build.hip)
+FLAG_DEVICE_BVH_SAH = 0x2000  # with FLAG_DEVICE_BVH_BUILD: the device SAH builder, the host's tree node for node (csrc/bvh_build_sah.hip)
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
+BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
 DEBUG_HIT_ID, DEBUG_PREV_PIXEL = 0x1, 0x2
 
@@ -108,7 +110,7 @@ SYMBOLS = [
     "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check", "rtpt_util_bvh_check_pairs",
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
-    "rtpt_debug_reuse_info",
+    "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology",
 ]
 
 _lib = None
@@ -169,6 +171,7 @@ def load() -> C.CDLL:
         "rtpt_debug_bvh_check": [vp, C.POINTER(C.c_uint64 * 8)],
         "rtpt_scene_build_info": [vp, C.POINTER(SceneBuildInfo)],
         "rtpt_scene_rebuild": [vp],
+        "rtpt_debug_bvh_topology": [vp, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
     }
@@ -382,6 +385,15 @@ class Context:
 
     def sync(self):
         _check(self._lib.rtpt_sync(self._h))
+
+    def debug_bvh_topology(self):
+        """(child_refs [n_nodes, 2], leaf_order [n_tris]) of the tree as it stands on the device (rtpt_debug_bvh_topology)"""
+        nn, nl = C.c_uint32(0), C.c_uint32(0)
+        _check(self._lib.rtpt_debug_bvh_topology(self._h, None, C.byref(nn), None, C.byref(nl)))
+        refs = np.empty((nn.value, 2), np.uint32)
+        leaf = np.empty(nl.value, np.uint32)
+        _check(self._lib.rtpt_debug_bvh_topology(self._h, refs.ctypes.data_as(C.c_void_p), C.byref(nn), leaf.ctypes.data_as(C.c_void_p), C.byref(nl)))
+        return refs, leaf
 
     def debug_bvh_check(self):
         """the acceleration structure as it stands on the device (after an upload or a device-side refit), checked on the host"""

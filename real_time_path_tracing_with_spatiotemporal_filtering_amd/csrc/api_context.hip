@@ -335,7 +335,13 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   if (const char* v = std::getenv("RTPT_NO_TRI_PAIRS")) c->no_pairing = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_HOST_REFIT")) c->host_refit = std::atoi(v) != 0;
   c->device_bvh = (cfg->flags & RTPT_FLAG_DEVICE_BVH_BUILD) != 0;
-  if (const char* v = std::getenv("RTPT_DEVICE_BVH")) c->device_bvh = c->device_bvh || std::atoi(v) != 0;
+  c->device_bvh_sah = c->device_bvh && (cfg->flags & RTPT_FLAG_DEVICE_BVH_SAH) != 0;  // alone the bit is ignored
+  if (const char* v = std::getenv("RTPT_DEVICE_BVH")) {
+    if (!std::strcmp(v, "sah"))
+      c->device_bvh = c->device_bvh_sah = true;
+    else
+      c->device_bvh = c->device_bvh || std::atoi(v) != 0;
+  }
   if (const char* v = std::getenv("RTPT_LBVH_ORDER")) c->lbvh_by_height = !std::strcmp(v, "height");
   if (const char* v = std::getenv("RTPT_NO_TRACE_FUSION")) c->fuse_trace = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_NO_FRAME_REUSE")) c->frame_reuse = std::atoi(v) == 0;

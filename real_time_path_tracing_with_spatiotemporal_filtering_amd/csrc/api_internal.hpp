@@ -129,6 +129,7 @@ struct rtpt_ctx {
   bool host_refit = false;  // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
   // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
   bool device_bvh = false;   // rtpt_scene_upload builds the tree on the device
+  bool device_bvh_sah = false;  // ... with the SAH builder (bvh_build_sah.hip): RTPT_FLAG_DEVICE_BVH_SAH too, or RTPT_DEVICE_BVH=sah
   bool lbvh_by_height = false;  // RTPT_LBVH_ORDER=height: the device builder's other node numbering (A/B; same pixels)
   bool device_tree = false;  // the tree on the device now was built there: bvh_host is empty, every refit runs on the device
   Buf bvh_build_scratch, bvh_build_header;  // the builder's work area (grows, never shrinks) and its readback words

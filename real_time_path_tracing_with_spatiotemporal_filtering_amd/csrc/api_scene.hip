@@ -22,18 +22,22 @@ rt::ScenePrepArgs scene_prep_args(const rtpt_ctx* c, uint32_t total, bool leaf_p
   return sp;
 }
 
-// The tree over c->tris (`total` triangles as they stand on the device) built on the device (bvh_build.hip) and swapped
+// The tree over c->tris (`total` triangles as they stand on the device) built on the device (bvh_build.hip, or
+// bvh_build_sah.hip with c->device_bvh_sah: fewer nodes than primitives - 1 where a leaf holds two triangles) and swapped
 // into the context: nodes, leaf order, nodes by height, depth; then the refit that fills boxes and grid and the leaf
 // records.  Built aside, so a tree deeper than the traversal stack (*too_deep, RTPT_OK) or an error leaves the context's
-// tree as it was.  The stream must be idle on entry (buffers are replaced); synchronises ONCE, for the readback of
-// kLbvhHeaderWords dwords.  Needs c->tris, c->isect_*, c->shade and c->bvh_grid_dev allocated for `total`.
+// tree as it was.  The stream must be idle on entry (buffers are replaced).  The LBVH synchronises ONCE, for the
+// readback of kLbvhHeaderWords dwords; the SAH build also synchronises inside launch_sah_build, once at its start and one to
+// three times per level of the tree (its segment counts come back to the host).  Needs c->tris, c->isect_*, c->shade and c->bvh_grid_dev allocated for `total`.
 int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_deep) {
   *too_deep = false;
-  const uint32_t w = leaf_pairs ? 2u : 1u, n_prims = total / w, n_nodes = n_prims > 1 ? n_prims - 1 : 1;
+  const bool sah = c->device_bvh_sah;
+  const uint32_t w = leaf_pairs ? 2u : 1u, n_prims = total / w;
+  uint32_t n_nodes = n_prims > 1 ? n_prims - 1 : 1;  // the SAH builder may write fewer: its header says how many
   // the traversal addresses leaf records and nodes as base + 32-bit byte offset (48 bytes per triangle at most, 32 per node)
   if (static_cast<uint64_t>(total) * 48u >= (1ull << 32) || n_nodes >= (1u << 27))
     return fail(RTPT_E_INVALID, "scene too large for the traversal's 32-bit record offsets (more than 89,478,485 triangles)");
-  const size_t need = rt::lbvh_scratch_bytes(n_prims, c->lbvh_by_height);
+  const size_t need = sah ? rt::sah_scratch_bytes(n_prims) : rt::lbvh_scratch_bytes(n_prims, c->lbvh_by_height);
   if (!need) return fail(RTPT_E_DEVICE, "device BVH build: the sort's temporary-storage query failed");
   int rc;
   if (c->bvh_build_scratch.bytes < need && (rc = alloc_buf(c->bvh_build_scratch, need))) return rc;
@@ -60,7 +64,9 @@ int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_de
   la.by_height = c->lbvh_by_height ? 1u : 0u;
   uint32_t header[rt::kLbvhHeaderWords];
   hipError_t e = hipEventRecord(c->build_ev[0], c->stream);
-  if (e == hipSuccess) e = rt::launch_lbvh_build(la, c->bvh_build_scratch.ptr, c->bvh_build_scratch.bytes, c->stream);
+  if (e == hipSuccess)
+    e = sah ? rt::launch_sah_build(la, c->bvh_build_scratch.ptr, c->bvh_build_scratch.bytes, c->stream)
+            : rt::launch_lbvh_build(la, c->bvh_build_scratch.ptr, c->bvh_build_scratch.bytes, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(header, c->bvh_build_header.ptr, sizeof header, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
@@ -78,6 +84,7 @@ int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_de
     *too_deep = true;
     return RTPT_OK;
   }
+  if (sah && header[1] >= 1 && header[1] <= n_nodes) n_nodes = header[1];
   if (header[1] != n_nodes || counted != n_nodes || levels != std::max(depth, 1u)) {
     drop();
     return fail(RTPT_E_INVALID, "internal: the device BVH build lost nodes");
@@ -112,7 +119,7 @@ int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_de
   if (rcl) return rcl;
   HIP_TRY(ee);
   c->build_ms_pending = true;
-  c->build_info.builder = RTPT_BVH_BUILDER_DEVICE_LBVH;
+  c->build_info.builder = sah ? static_cast<uint32_t>(RTPT_BUILDER_DEVICE_SAH) : static_cast<uint32_t>(RTPT_BVH_BUILDER_DEVICE_LBVH);
   c->build_info.fallback = RTPT_BVH_FALLBACK_NONE;
   c->build_info.n_primitives = n_prims;
   c->build_info.n_nodes = n_nodes;

@@ -250,6 +250,32 @@ int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
   return RTPT_OK;
 }
 
+int rtpt_debug_bvh_topology(rtpt_ctx* c, uint32_t* child_refs, uint32_t* n_nodes, uint32_t* leaf_order, uint32_t* n_leaf_ids) {
+  if (!c || !n_nodes || !n_leaf_ids) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->n_tris || !c->nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const uint32_t n = c->n_tris, nn = c->n_nodes;
+  if (!child_refs && !leaf_order) {
+    *n_nodes = nn;
+    *n_leaf_ids = n;
+    return RTPT_OK;
+  }
+  if (!child_refs || !leaf_order) return fail(RTPT_E_INVALID, "both arrays, or neither");
+  if (*n_nodes < nn || *n_leaf_ids < n) return fail(RTPT_E_INVALID, "arrays shorter than the counts the first call returned");
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  std::vector<rt::BvhNodeQ> q(nn);
+  HIP_TRY(hipMemcpyAsync(q.data(), c->nodes.ptr, q.size() * sizeof(rt::BvhNodeQ), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(leaf_order, c->leaf_order.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (uint32_t i = 0; i < nn; i++) {
+    child_refs[2 * static_cast<size_t>(i)] = q[i].lref;
+    child_refs[2 * static_cast<size_t>(i) + 1] = q[i].rref;
+  }
+  *n_nodes = nn;
+  *n_leaf_ids = n;
+  return RTPT_OK;
+}
+
 static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n, bool pairs, uint64_t stats[8]) {
   if (!tris || !stats || n == 0) return fail(RTPT_E_INVALID, "NULL argument / empty scene");
   if (pairs && n % 2) return fail(RTPT_E_INVALID, "pairs mode needs an even triangle count (fan pairs 2q, 2q + 1)");

@@ -52,10 +52,7 @@ struct Child {
 // SAH bins per axis.  K0 + K1 + K2 on the 1.15 M-triangle frame (profiles/r04_bvh_bins_ab.txt): 16: 2 896 us, 32: 2 856,
 // 64: 2 863, 128: 2 871; the build of that scene takes ~0.5 s with any of them.  SAH node cost 0.75 / 1.0 / 1.5: the same tree
 // (2 896); 2.0: 3 003; 3.0: 3 033.
-#ifndef RTPT_BVH_BINS
-#define RTPT_BVH_BINS 32
-#endif
-constexpr int kBins = RTPT_BVH_BINS;
+constexpr int kBins = kBvhBins;  // bvh.hpp
 
 struct Builder {
   std::vector<Prim> prims;

@@ -22,6 +22,10 @@ constexpr uint32_t kBvhEmpty = 0xFFFFFFFFu;
 #ifndef RTPT_BVH_NODE_COST
 #define RTPT_BVH_NODE_COST 1.5f
 #endif
+#ifndef RTPT_BVH_BINS
+#define RTPT_BVH_BINS 32
+#endif
+constexpr int kBvhBins = RTPT_BVH_BINS;  // SAH bins per axis (bvh.cpp; the device restatement bvh_build_sah.hip reads the same value)
 constexpr int kBvhMinLeaf = RTPT_BVH_MIN_LEAF;  // groups this small are always leaves
 constexpr float kNodeCost = RTPT_BVH_NODE_COST;  // cost of a node visit in triangle tests (SAH leaf decision)
 constexpr int kBvhMaxLeaf = RTPT_BVH_MAX_LEAF;  // triangles per leaf (the leaf reference encodes count - 1 in 2 bits)

@@ -285,6 +285,11 @@ struct LbvhArgs {
 };
 size_t lbvh_scratch_bytes(uint32_t n_prims, bool by_height);  // 0: the sort's size query failed
 hipError_t launch_lbvh_build(const LbvhArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s);
+// device-side SAH build (bvh_build_sah.hip): the host builder's tree, node for node; the same outputs in the same formats
+// (nodes: at most n_prims - 1 are written, header[1] says how many; by_height is ignored).  Synchronises the stream once at
+// the start and one to three times per level of the tree (three while a level still has segments larger than a workgroup).
+size_t sah_scratch_bytes(uint32_t n_prims);  // 0: the sort's size query failed
+hipError_t launch_sah_build(const LbvhArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s);
 // gather isect records into class order: out[t] = isect_id[ids[t]] (3 float4 each), n entries
 void launch_lut(const LutArgs& a, hipStream_t s);
 void launch_gbuffer(const GbufferArgs& a, hipStream_t s);

@@ -725,7 +725,7 @@ std::string PathTracingApplication::buildLine() {
   check(rtpt_scene_build_info(c, &bi), "rtpt_scene_build_info");
   char buf[256];
   std::snprintf(buf, sizeof buf, "rtpt_app: BVH over %u %s built by %s%s: %u nodes, depth %u, build %.3f ms, upload %.3f ms", bi.n_primitives,
-                bi.leaf_pairs ? "fan pairs" : "triangles", bi.builder == RTPT_BVH_BUILDER_DEVICE_LBVH ? "device LBVH" : "host SAH",
+                bi.leaf_pairs ? "fan pairs" : "triangles", bi.builder == RTPT_BUILDER_DEVICE_SAH ? "device SAH" : bi.builder == RTPT_BVH_BUILDER_DEVICE_LBVH ? "device LBVH" : "host SAH",
                 bi.fallback == RTPT_BVH_FALLBACK_DEPTH ? " (device tree too deep)" : "", bi.n_nodes, bi.depth, bi.build_ms, bi.upload_ms);
   return buf;
 }

@@ -21,6 +21,7 @@ static void usage(const char* argv0) {
       "          [--tessellate n] [--lattice NXxNYxNZ [--pitch P] | --instances file] [--dump-scene out.bin]\n"
       "          [--frames-in-flight 1|2]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
+      "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
       "          [--present none|rgba8|f32 [--dump-present out.raw]]\n"
       "          [--plan-only   (print the strip plan and the history bands of the scripted frames as JSON; needs no GPU)]\n"
@@ -79,6 +80,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--dump")) dump = need("--dump");
     else if (!std::strcmp(argv[i], "--exact-filter")) opt.flags |= RTPT_FLAG_EXACT_FILTER;
     else if (!std::strcmp(argv[i], "--device-bvh")) opt.flags |= RTPT_FLAG_DEVICE_BVH_BUILD;
+    else if (!std::strcmp(argv[i], "--device-bvh-sah")) opt.flags |= RTPT_FLAG_DEVICE_BVH_BUILD | RTPT_FLAG_DEVICE_BVH_SAH;
     else if (!std::strcmp(argv[i], "--frames-in-flight")) opt.frames_in_flight = std::atoi(need("--frames-in-flight"));
     else if (!std::strcmp(argv[i], "--ranks")) opt.ranks = std::atoi(need("--ranks"));
     else if (!std::strcmp(argv[i], "--rank")) opt.rank = std::atoi(need("--rank"));

@@ -1,12 +1,14 @@
-"""Device-side BVH build (csrc/bvh_build.hip) against the host SAH builder, on the GPU in front of you:
+"""Device-side BVH builds (csrc/bvh_build.hip: LBVH; csrc/bvh_build_sah.hip: the host's SAH tree built on the device) against
+the host SAH builder, on the GPU in front of you:
 
 * build_ms / upload_ms of rtpt_scene_upload for the Cornell box, a 3,000-triangle soup and the 1,152,000-triangle lattice
   (BASELINE configs[4]), each builder, after one warm-up upload (code objects load lazily);
 * on the lattice under a sheared model: the frame time with the refit tree, the cost of rtpt_scene_rebuild, the frame time
-  with the rebuilt tree — the figure that says when a rebuild pays.
+  with the rebuilt tree — the figure that says when a rebuild pays; once per builder that can rebuild.
 
     python scripts/device_bvh_measure.py [--frames 30] [--small]      # one JSON line per measurement
     rocprofv3 --kernel-trace --stats -d out -- python scripts/device_bvh_measure.py --builds-only   # the per-kernel split
+    ... --builds-only --builders device_sah --scenes lattice --reps 1      # of one builder on one scene
 """
 import argparse
 import json
@@ -25,6 +27,9 @@ def main():
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--small", action="store_true", help="1080p frames instead of 4K")
     ap.add_argument("--builds-only", action="store_true")
+    ap.add_argument("--builders", default="device,device_sah,host", help="comma list of device, device_sah, host (uploads and rebuild legs)")
+    ap.add_argument("--scenes", default="cornell,soup3000,lattice", help="comma list of the upload scenes")
+    ap.add_argument("--reps", type=int, default=2)
     args = ap.parse_args()
     try:
         import torch
@@ -35,6 +40,7 @@ def main():
     from real_time_path_tracing_with_spatiotemporal_filtering_amd.app import DEFAULT_SCENE, HipBackend, PathTracingApplication
     from real_time_path_tracing_with_spatiotemporal_filtering_amd.strips import StripPlan
     D = abi.FLAG_DEVICE_BVH_BUILD
+    S = D | abi.FLAG_DEVICE_BVH_SAH
     xyz, idx = abi.load_obj(DEFAULT_SCENE)
     rng = np.random.default_rng(707)
     c = rng.uniform(-0.8, 0.8, (3000, 1, 3))
@@ -52,10 +58,14 @@ def main():
             return dict(ctx.scene_build_info(), wall_ms=round(wall, 3))
 
     upload(D, cases["soup3000"])  # warm-up
+    upload(S, cases["soup3000"])
     upload(0, cases["soup3000"])
+    builders = [(label, flags) for label, flags in (("device", D), ("device_sah", S), ("host", 0)) if label in args.builders.split(",")]
     for name, mesh in cases.items():
-        for rep in range(2):
-            for label, flags in (("device", D), ("host", 0)):
+        if name not in args.scenes.split(","):
+            continue
+        for rep in range(args.reps):
+            for label, flags in builders:
                 print(json.dumps({"what": "upload", "scene": name, "asked": label, "rep": rep, **upload(flags, mesh)}), flush=True)
     if args.builds_only:
         return
@@ -65,7 +75,7 @@ def main():
     shear = np.eye(4)
     shear[:3, :3] = [[1.0, 0.8, 0.0], [0.0, 1.0, 0.0], [0.6, 0.0, 1.0]]
     shear = np.ascontiguousarray(shear.astype(np.float32).T).ravel()
-    for upload_flags in (0, D):
+    for upload_flags in [flags for _, flags in builders[::-1]]:
         be = HipBackend(w, h, StripPlan(h, 1, 0, n), max_segments=8, flags=upload_flags)
         app = PathTracingApplication(be, w, h, n, cameraOrigin=cam, z_far=zfar, lightPos=(1.0, float(cam[1]), float(cam[2]) - 8.0))
         app.objVertices, app.objIndices = vx, ti
@@ -91,7 +101,8 @@ def main():
         rebuild_wall = (time.perf_counter() - t0) * 1e3
         info = ctx.scene_build_info()
         rebuilt = frames(args.frames)
-        print(json.dumps({"what": "rebuild_vs_refit", "scene": "lattice sheared", "size": [w, h], "uploaded_by": "device" if upload_flags else "host",
+        print(json.dumps({"what": "rebuild_vs_refit", "scene": "lattice sheared", "size": [w, h], "uploaded_by": {0: "host", D: "device", S: "device_sah"}[upload_flags],
+                          "rebuilt_by": "device_sah" if upload_flags == S else "device",
                           "ms_per_frame_identity": round(base, 4), "ms_per_frame_refit_tree": round(refit, 4),
                           "ms_per_frame_rebuilt_tree": round(rebuilt, 4), "rebuild_wall_ms": round(rebuild_wall, 3),
                           "rebuild_build_ms": round(info["build_ms"], 3), "depth": info["depth"]}), flush=True)
