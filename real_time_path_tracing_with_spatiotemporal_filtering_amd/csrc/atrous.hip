@@ -18,8 +18,11 @@
 // (colour + depth) plus the 4-byte id instead of three separate planes — 36 instead of 40 bytes of
 // HBM traffic per pixel and a third fewer load instructions.  The final pass writes alpha 0 again;
 // the C-ABI layer hides the convention (rtpt_readback masks alpha, rtpt_set_plane re-stamps depth).
+#include <cstdlib>
+
 #include "device_common.hpp"
 #include "lds_dma.hpp"
+#include "select.hpp"
 
 #ifndef RTPT_TILE_TIMELINE
 #define RTPT_TILE_TIMELINE 0  // timeline build (scripts/tile_timeline.py): when the workgroups of the single-pass launches lived
@@ -389,10 +392,7 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
 // Normal weights pow(max(0, dot(n_p, n_q)), sigma_n) (:62) depend only on the id pair, so k_lut
 // tabulates them once per frame ((T+1)^2 floats, same arithmetic) and the block copies the table to
 // LDS: one ds_read_b32 per tap replaces the compare/branch/gather/pow sequence.
-#ifndef RTPT_COMB_M
-#define RTPT_COMB_M 2
-#endif
-constexpr int kCombM = RTPT_COMB_M;  // output rows per wave
+constexpr int kCombM = 2;       // output rows per wave
 constexpr int kPairMax = 64;    // ids (T+1) for which the pair table is kept in LDS
 
 // The kernel.  The kShWaves waves of a block filter kShWaves CONSECUTIVE chunks of one comb: 4M outputs
@@ -404,24 +404,8 @@ constexpr int kPairMax = 64;    // ids (T+1) for which the pair table is kept in
 // kernel was fabric-bound at 72-76 us.  Sharing brought it to 66-69 us.  Sweep at 4K, k = 5:
 // (M, waves, 64-px segments per wave row) = (2,4,1) 67 us, (3,4,1) 74, (2,8,1) 68, (1,8,1) 71,
 // (2,4,2) 66-77, (2,8,2) 72-88.)
-#ifndef RTPT_COMB_WAVES
-#define RTPT_COMB_WAVES 4
-#endif
-#ifndef RTPT_COMB_PRIO
-#define RTPT_COMB_PRIO 1  // waves run at priority 3 while they issue an item's DMAs: 4K 67.0 -> 65.5 us (in-process A/B)
-#endif
-#ifndef RTPT_COMB_NT_STORE
-#define RTPT_COMB_NT_STORE 1  // non-temporal stores for the k < N passes (the pass does not re-read its output): 65 -> 62.5 us
-                              // in a frame; a pass repeated on the SAME buffers drops to 54 us (77 %) because its input then stays
-                              // in the 256 MB memory-side cache — in a frame the input was just written by the previous pass.
-                              // Tried without gain: nt on the final pass's store, nt on the staging loads (66-69 us),
-                              // alternating the walk direction per pass so a pass starts on the rows written last
-#endif
-#ifndef RTPT_COMB_HALVES
-#define RTPT_COMB_HALVES 1
-#endif
-constexpr int kShWaves = RTPT_COMB_WAVES;    // waves (consecutive chunks) per block
-constexpr int kShHalves = RTPT_COMB_HALVES;  // 64-px segments per wave row: the 2k-column halo is paid once per 64*kShHalves px
+constexpr int kShWaves = 4;   // waves (consecutive chunks) per block
+constexpr int kShHalves = 1;  // 64-px segments per wave row: the 2k-column halo is paid once per 64*kShHalves px
 constexpr int kShThreads = 64 * kShWaves;
 
 // NRM = true is the variant for scenes whose id-pair table does not fit LDS (more than 63 triangles, i.e. every
@@ -434,21 +418,12 @@ constexpr int kShThreads = 64 * kShWaves;
 // 2^(k-1), passed as a.stride) run in this kernel too — the same comb staging with 2R halo rows per workgroup and 2R*s
 // halo columns per segment, and the arithmetic of k_atrous_ext (h kept per tap, correctly-rounded final division), so
 // the two are bit-identical.  25 taps are 25 LDS reads here instead of 75 global loads per pixel.
-#ifndef RTPT_FINAL_WAVES
-#define RTPT_FINAL_WAVES 1  // id-pair final pass: waves per SIMD to squeeze the registers for (A/B: 4 by itself)
-#endif
-#ifndef RTPT_COMB_MIN_WAVES
-#define RTPT_COMB_MIN_WAVES 0
-#endif
+constexpr int kFinalWaves = 1;  // id-pair final pass: waves per SIMD to squeeze the registers for (A/B: 4 by itself)
 template <int CWp, bool FINAL, bool EXACT, bool NRM = false, int R = 1, bool EXTA = false, bool VAR = false>
 __global__ __launch_bounds__(kShThreads)
-#if RTPT_COMB_MIN_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_COMB_MIN_WAVES)))
-#else
 // the per-pixel-normal final pass sits at the edge of six waves per SIMD (79-81 VGPRs as the surrounding code changes;
 // 142-147 us with six waves, 169-176 us with five at 4K): pin it.  Every other instantiation keeps what it gets.
-__attribute__((amdgpu_waves_per_eu(FINAL && NRM && R == 1 && !EXTA && !VAR && !EXACT ? 6 : (FINAL && !NRM && R == 1 && !EXTA && !VAR && !EXACT ? RTPT_FINAL_WAVES : 1))))
-#endif
+__attribute__((amdgpu_waves_per_eu(FINAL && NRM && R == 1 && !EXTA && !VAR && !EXACT ? 6 : (FINAL && !NRM && R == 1 && !EXTA && !VAR && !EXACT ? kFinalWaves : 1))))
 void k_atrous_comb_sh(AtrousArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 #if RTPT_TILE_TIMELINE
@@ -530,9 +505,9 @@ void k_atrous_comb_sh(AtrousArgs a) {
   // every wave is done reading the previous group's rows before anybody overwrites them
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-#if RTPT_COMB_PRIO
-  __builtin_amdgcn_s_setprio(3);  // issue this item's DMAs ahead of the other waves' arithmetic
-#endif
+  // waves run at priority 3 while they issue an item's DMAs, ahead of the other waves' arithmetic: 4K 67.0 -> 65.5 us
+  // (in-process A/B)
+  __builtin_amdgcn_s_setprio(3);
   // wave w stages rows w*M+1 .. w*M+M; wave 0 also row 0, the last wave also row 4M+1
   const int j_lo = wave * kCombM + (wave == 0 ? 0 : R);
   const int j_hi = wave * kCombM + kCombM + R - 1 + (wave == kShWaves - 1 ? R : 0);
@@ -564,20 +539,15 @@ void k_atrous_comb_sh(AtrousArgs a) {
       if (use_var) dma_b32(rvar, o4[kShHalves], lds_var + (cj + 64u * kShHalves) * 4u);
     }
   }
-#if RTPT_COMB_PRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
   // final pass: world positions fetched with the staging DMA and the history ahead of the taps.  Measured at 4K: it pays
   // in the per-pixel-normal variant (1.15M triangles: 155.8 -> 144.1 us; its taps compute x^128 per tap and leave time to
   // hide the fetch) and costs in the id-pair variant (110.5 -> 125.6 us: the 2 KiB of world positions per wave lengthen the
-  // wait in front of the workgroup barrier, which the other workgroups' taps no longer cover)
-#ifndef RTPT_FINAL_EARLY
-#define RTPT_FINAL_EARLY NRM
-#endif
+  // wait in front of the workgroup barrier, which the other workgroups' taps no longer cover) — so NRM decides.
   // FINAL: the world positions of this wave's output pixels depend on nothing staged — fetch them now, in flight together
   // with the DMA and waited for by the same vmcnt(0)
   f3 wp_pre[kCombM * kShHalves];
-  if (FINAL && RTPT_FINAL_EARLY) {
+  if (FINAL && NRM) {
 #pragma unroll
     for (int mh = 0; mh < kCombM * kShHalves; mh++) {
       const int m = mh / kShHalves, hf = mh % kShHalves;
@@ -611,7 +581,7 @@ void k_atrous_comb_sh(AtrousArgs a) {
     // the history fetch is in flight under the taps' arithmetic
     int ppx = x, ppy = y;
     f3 hc{0.f, 0.f, 0.f};  // D2: out-of-image history fetch returns 0
-    if (FINAL && RTPT_FINAL_EARLY) {
+    if (FINAL && NRM) {
       if (!(idp < 1)) {
         const f3 wp = wp_pre[mh];
         const f3 va = xyz(a.lut_prev[3 * idp]), vb = xyz(a.lut_prev[3 * idp + 1]), vc = xyz(a.lut_prev[3 * idp + 2]);  // :223-233
@@ -693,18 +663,16 @@ void k_atrous_comb_sh(AtrousArgs a) {
     }
     if (EXTA && use_var && a.var_out) a.var_out[ip] = vsum / (den * den);
     if (!FINAL) {
-#if RTPT_COMB_NT_STORE
-      {
-        typedef float v4f_ __attribute__((ext_vector_type(4)));
-        v4f_ o4 = {filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp};
-        __builtin_nontemporal_store(o4, reinterpret_cast<v4f_*>(a.out + ip));  // :152; not re-read by this pass
-      }
-#else
-      a.out[ip] = make_float4(filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp);  // :152 (+ depth in alpha)
-#endif
+      // non-temporal stores for the k < N passes (the pass does not re-read its output): 65 -> 62.5 us in a frame; a pass
+      // repeated on the SAME buffers drops to 54 us (77 %) because its input then stays in the 256 MB memory-side cache —
+      // in a frame the input was just written by the previous pass.  Tried without gain: nt on the final pass's store, nt
+      // on the staging loads (66-69 us), alternating the walk direction per pass so a pass starts on the rows written last
+      typedef float v4f_ __attribute__((ext_vector_type(4)));
+      v4f_ o4 = {filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp};  // :152 (+ depth in alpha)
+      __builtin_nontemporal_store(o4, reinterpret_cast<v4f_*>(a.out + ip));
       continue;
     }
-    if (!RTPT_FINAL_EARLY) {
+    if (!NRM) {
       // :213-239 reprojection — exact arithmetic: the truncated pixel coordinate is an integer observable
       if (!(idp < 1)) {
         const f3 wp = xyz(a.worldpos[ip]);
@@ -741,15 +709,7 @@ void k_atrous_comb_sh(AtrousArgs a) {
       blend = f3{fmaf_(filtered.x, alpha, hc.x * oma), fmaf_(filtered.y, alpha, hc.y * oma),
                  fmaf_(filtered.z, alpha, hc.z * oma)};  // :254
     }
-#if RTPT_COMB_NT_STORE > 1
-    {
-      typedef float v4f_ __attribute__((ext_vector_type(4)));
-      v4f_ o4 = {blend.x, blend.y, blend.z, 0.0f};
-      __builtin_nontemporal_store(o4, reinterpret_cast<v4f_*>(a.out + ip));  // :263 (D1: distinct buffer)
-    }
-#else
     a.out[ip] = make_float4(blend.x, blend.y, blend.z, 0.0f);  // :263 (D1: distinct buffer)
-#endif
     // main.cpp:1338-1361, fused: the blit reads exactly the value stored above (alpha 0), k_present's conversion
     // (not in the per-pixel-normal variant: its final pass sits at 79 VGPRs = 6 waves per SIMD, and the store's operands
     // cost it a wave — 142 -> 176 us at 4K; k_present serves those scenes)
@@ -805,60 +765,75 @@ void launch_stamp_depth(const FrameGeom& g, float4* color, const float* depth, h
   hipLaunchKernelGGL(k_stamp_depth, grid_for(g), dim3(kBlockX, kBlockY), 0, s, g, color, depth);
 }
 
+// THE two lists of k_atrous_comb_sh instantiations (each x FINAL x EXACT): the plain family (id-pair table or per-pixel
+// normals, 3x3 taps; a staged row is 64 + 2 k cells) and the extension family (EXTA; id-pair table only; 64 + 2 R s cells,
+// R = 2: 5x5 taps; VAR: the variance plane staged too).  prepare_device_atrous() raises the LDS limit of every entry;
+// launch_atrous() and ext_staged() take the narrowest row that holds a launch's halo from them.
+template <int CW, bool NRM, int R = 1, bool EXTA = false, bool VAR = false>
+struct CombInst {
+  static constexpr int cw = CW, r = R;
+  static constexpr bool nrm = NRM, exta = EXTA, var = VAR;
+};
+constexpr int kCombW = kBlockX * kShHalves;  // pixels per wave row
+using CombInsts = type_list<CombInst<kCombW + 8, false>, CombInst<kCombW + 16, false>, CombInst<kCombW + 32, false>,
+                            CombInst<kCombW + 8, true>, CombInst<kCombW + 16, true>, CombInst<kCombW + 32, true>>;
+using CombExtInsts = type_list<CombInst<72, false, 1, true, false>, CombInst<96, false, 1, true, false>,
+                               CombInst<72, false, 1, true, true>, CombInst<96, false, 1, true, true>,
+                               CombInst<72, false, 2, true, false>, CombInst<96, false, 2, true, false>, CombInst<128, false, 2, true, false>,
+                               CombInst<72, false, 2, true, true>, CombInst<96, false, 2, true, true>, CombInst<128, false, 2, true, true>>;
+// the narrowest staged row (cells) the list has for (nrm, r, var) that holds `need` cells; 0: none
+template <class... E>
+constexpr int comb_row(type_list<E...>, int need, bool nrm, int r, bool var) {
+  int cw = 0;
+  ((cw = E::nrm == nrm && E::r == r && E::var == var && E::cw >= need && (cw == 0 || E::cw < cw) ? E::cw : cw), ...);
+  return cw;
+}
+static_assert(comb_row(CombInsts{}, kCombW + 2 * 16, false, 1, false) != 0 && comb_row(CombInsts{}, kCombW + 2 * 16, true, 1, false) != 0,
+              "launch_atrous() stages every stride up to 16");
+template <class I, class FIN, class EX>
+constexpr auto comb_kernel(I, FIN, EX) {
+  return &k_atrous_comb_sh<I::cw, FIN::value, EX::value, I::nrm, I::r, I::exta, I::var>;
+}
+
 // Kernels that ask for more than 64 KiB of dynamic LDS need the attribute raised once per DEVICE (it is a
 // property of the function on the current device, not of the process): rtpt_create calls this after
 // hipSetDevice, so contexts on different GPUs of one process are independent.
-template <int CW, bool NRM>
-static hipError_t comb_attrs() {
-  constexpr int kMax = 160 * 1024;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, true, true, NRM>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, false, true, NRM>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, true, false, NRM>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, false, false, NRM>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  return e;
-}
-template <int CW, int RR, bool VV>
-static hipError_t comb_ext_attrs() {
-  constexpr int kMax = 160 * 1024;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, false, true, false, RR, true, VV>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, false, false, false, RR, true, VV>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, true, true, false, RR, true, VV>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_comb_sh<CW, true, false, false, RR, true, VV>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  return e;
-}
 hipError_t prepare_device_atrous() {
-  {
-    hipError_t e = comb_ext_attrs<72, 1, false>();
-    if (e == hipSuccess) e = comb_ext_attrs<96, 1, false>();
-    if (e == hipSuccess) e = comb_ext_attrs<72, 2, false>();
-    if (e == hipSuccess) e = comb_ext_attrs<96, 2, false>();
-    if (e == hipSuccess) e = comb_ext_attrs<128, 2, false>();
-    if (e == hipSuccess) e = comb_ext_attrs<72, 1, true>();
-    if (e == hipSuccess) e = comb_ext_attrs<96, 1, true>();
-    if (e == hipSuccess) e = comb_ext_attrs<72, 2, true>();
-    if (e == hipSuccess) e = comb_ext_attrs<96, 2, true>();
-    if (e == hipSuccess) e = comb_ext_attrs<128, 2, true>();
-    if (e != hipSuccess) return e;
-  }
-  constexpr int b = kBlockX * kShHalves;
-  hipError_t e = comb_attrs<b + 8, false>();
-  if (e == hipSuccess) e = comb_attrs<b + 16, false>();
-  if (e == hipSuccess) e = comb_attrs<b + 32, false>();
-  if (e == hipSuccess) e = comb_attrs<b + 8, true>();
-  if (e == hipSuccess) e = comb_attrs<b + 16, true>();
-  if (e == hipSuccess) e = comb_attrs<b + 32, true>();
+  hipError_t e = hipSuccess;
+  auto raise = [&](auto inst) {
+    each_final_exact([&](auto fin, auto ex) {
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(comb_kernel(inst, fin, ex)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+  };
+  visit_all(CombExtInsts{}, raise);
+  visit_all(CombInsts{}, raise);
   return e;
+}
+// the entry (cw, nrm, r, var) of `list`, FINAL x EXACT as asked; false: the list has no such entry
+template <class List>
+static bool launch_comb(List list, int cw, bool nrm, int r, bool var, bool final_pass, dim3 grid, size_t lds, const AtrousArgs& a, hipStream_t s) {
+  return visit_first(list, [&](auto inst) {
+    using I = decltype(inst);
+    if (I::cw != cw || I::nrm != nrm || I::r != r || I::var != var) return false;
+    with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
+      hipLaunchKernelGGL(comb_kernel(inst, fin, ex), grid, dim3(kBlockX, kShWaves), lds, s, a);
+    });
+    return true;
+  });
 }
 
 // true when a FINAL launch of `a` runs in the LDS-staged kernel, whose epilogue can also write the swapchain format
 // (AtrousArgs::present); every other final variant leaves the blit to k_present
 // the extension modes run LDS-staged (k_atrous_comb_sh<..., R, EXTA>) when the scene has an id-pair table and the halo
 // 2 R s fits the widest staged row: every flag combination, final pass included (round 3; before: tap shapes of k < N only)
+static int ext_row(const AtrousArgs& a) {  // the staged row of an extension-mode launch, 0: its halo fits none
+  const int R = (a.ext & kExtGauss5) ? 2 : 1;
+  return comb_row(CombExtInsts{}, kBlockX + 2 * R * a.stride, false, R, (a.ext & kExtVariance) && a.var_in);
+}
 static bool ext_staged(const AtrousArgs& a) {
   const int np = static_cast<int>(a.n_tris) + 1;
-  const int R = (a.ext & kExtGauss5) ? 2 : 1;
-  // staged row strides instantiated: 72 / 96 for 3x3 taps (strides <= 16), 72 / 96 / 128 for 5x5 taps
-  return a.ext && !a.direct && a.pair_tab && np <= kPairMax && a.stride >= 1 && kBlockX + 2 * R * a.stride <= (R == 1 ? 96 : 128);
+  return a.ext && !a.direct && a.pair_tab && np <= kPairMax && a.stride >= 1 && ext_row(a) != 0;
 }
 bool atrous_final_fuses_present(const AtrousArgs& a) {
   const int np = static_cast<int>(a.n_tris) + 1;
@@ -899,44 +874,14 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
       a.tiles_y = (chunks + kShWaves - 1) / kShWaves;
       const int n_cu = a.n_cu > 0 ? a.n_cu : 256;
       const uint32_t nlb = static_cast<uint32_t>(a.tiles_x) * static_cast<uint32_t>(a.tiles_y) * static_cast<uint32_t>(sk);
-      const int need = seg_w + 2 * R * sk;
-      const int cw = need <= 72 ? 72 : (need <= 96 ? 96 : 128);  // staged row strides the kernel is instantiated for
+      const int cw = ext_row(a);  // != 0: ext_staged()
       const bool use_var = (a.ext & kExtVariance) && a.var_in;
       const size_t lds = static_cast<size_t>((np * np * 4 + 15) & ~15) + static_cast<size_t>(kShWaves * kCombM + 2 * R) * cw * (use_var ? 24 : 20);
       uint32_t per_cu = static_cast<uint32_t>((160u * 1024u) / lds);
       if (per_cu > 32u / kShWaves) per_cu = 32u / kShWaves;
       if (per_cu < 1u) per_cu = 1u;
       const uint32_t per_xcd = comb_blocks_per_xcd(nlb, static_cast<uint32_t>((n_cu + 7) / 8) * per_cu);
-      const dim3 grid(per_xcd * 8u), sblock(kBlockX, kShWaves);
-#define RTPT_LAUNCH_EXT(CW, RR, VV)                                                                                 \
-  do {                                                                                                              \
-    if (final_pass) {                                                                                               \
-      if (a.exact)                                                                                                  \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, true, true, false, RR, true, VV>), grid, sblock, lds, s, a);      \
-      else                                                                                                          \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, true, false, false, RR, true, VV>), grid, sblock, lds, s, a);     \
-    } else if (a.exact)                                                                                             \
-      hipLaunchKernelGGL((k_atrous_comb_sh<CW, false, true, false, RR, true, VV>), grid, sblock, lds, s, a);       \
-    else                                                                                                            \
-      hipLaunchKernelGGL((k_atrous_comb_sh<CW, false, false, false, RR, true, VV>), grid, sblock, lds, s, a);      \
-  } while (0)
-#define RTPT_LAUNCH_EXT_CW(RR, VV)                   \
-  do {                                               \
-    if (cw == 72) RTPT_LAUNCH_EXT(72, RR, VV);       \
-    else if (cw == 96) RTPT_LAUNCH_EXT(96, RR, VV);  \
-    else RTPT_LAUNCH_EXT(128, RR, VV);               \
-  } while (0)
-      if (R == 2) {
-        if (use_var) RTPT_LAUNCH_EXT_CW(2, true); else RTPT_LAUNCH_EXT_CW(2, false);
-      } else if (cw <= 96) {  // R == 1: 64 + 2 s <= 96 for every stride the staged kernel takes (s <= 16)
-        if (use_var) {
-          if (cw == 72) RTPT_LAUNCH_EXT(72, 1, true); else RTPT_LAUNCH_EXT(96, 1, true);
-        } else {
-          if (cw == 72) RTPT_LAUNCH_EXT(72, 1, false); else RTPT_LAUNCH_EXT(96, 1, false);
-        }
-      }
-#undef RTPT_LAUNCH_EXT_CW
-#undef RTPT_LAUNCH_EXT
+      if (!launch_comb(CombExtInsts{}, cw, false, R, use_var, final_pass, dim3(per_xcd * 8u), lds, a, s)) std::abort();  // unreachable: cw is an entry's
       return;
     }
   }
@@ -945,33 +890,22 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
     a.tiles_x = static_cast<int32_t>(g2.x);
     a.tiles_y = static_cast<int32_t>(g2.y);
     dim3 grid(g2.x * g2.y);
-    if (a.exact) {
-      if (final_pass)
-        hipLaunchKernelGGL((k_atrous_ext<true, true>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((k_atrous_ext<false, true>), grid, block, 0, s, a);
-    } else {
-      if (final_pass)
-        hipLaunchKernelGGL((k_atrous_ext<true, false>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((k_atrous_ext<false, false>), grid, block, 0, s, a);
-    }
+    with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
+      hipLaunchKernelGGL((k_atrous_ext<decltype(fin)::value, decltype(ex)::value>), grid, block, 0, s, a);
+    });
     return;
   }
   const bool pair_mode = a.pair_tab && np <= kPairMax;
   const bool nrm_mode = !pair_mode && a.normals != nullptr;
   if (!a.direct && (pair_mode || nrm_mode) && a.k >= 1 && a.k <= 16) {
-    const int seg_w = kBlockX * kShHalves;
-    a.tiles_x = (a.g.W + seg_w - 1) / seg_w;
+    a.tiles_x = (a.g.W + kCombW - 1) / kCombW;
     const int nrows = a.g.y1 - a.g.y0;
     const int chunks = (nrows + kCombM * a.k - 1) / (kCombM * a.k);
     a.tiles_y = (chunks + kShWaves - 1) / kShWaves;  // chunk groups (kShWaves consecutive chunks per block)
     const int n_cu = a.n_cu > 0 ? a.n_cu : 256;  // of the context's device (rtpt_create)
     const uint32_t nlb = static_cast<uint32_t>(a.tiles_x) * static_cast<uint32_t>(a.tiles_y) * static_cast<uint32_t>(a.k);
-    // staged row stride (cells): segment + 2k, rounded to the template instances
-    const int need = seg_w + 2 * a.k;
-    const int base_w = seg_w;
-    const int cw = need <= base_w + 8 ? base_w + 8 : (need <= base_w + 16 ? base_w + 16 : base_w + 32);
+    // staged row stride (cells): segment + 2k, rounded to the template instances (k <= 16: one fits)
+    const int cw = comb_row(CombInsts{}, kCombW + 2 * a.k, nrm_mode, 1, false);
     const size_t lds = nrm_mode ? static_cast<size_t>(kShWaves * kCombM + 2) * cw * 32
                                 : static_cast<size_t>((np * np * 4 + 15) & ~15) + static_cast<size_t>(kShWaves * kCombM + 2) * cw * 20;
     // persistent grid: as many blocks per CU as 160 KiB of LDS and 32 waves admit
@@ -979,54 +913,16 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
     if (per_cu > 32u / kShWaves) per_cu = 32u / kShWaves;
     if (per_cu < 1u) per_cu = 1u;
     const uint32_t per_xcd = comb_blocks_per_xcd(nlb, static_cast<uint32_t>((n_cu + 7) / 8) * per_cu);
-    dim3 grid(per_xcd * 8u), sblock(kBlockX, kShWaves);
-#define RTPT_LAUNCH_COMB(CW, NRM)                                                                          \
-  do {                                                                                                \
-    if (a.exact) {                                                                                    \
-      if (final_pass)                                                                                 \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, true, true, NRM>), grid, sblock, lds, s, a);              \
-      else                                                                                            \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, false, true, NRM>), grid, sblock, lds, s, a);             \
-    } else {                                                                                          \
-      if (final_pass)                                                                                 \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, true, false, NRM>), grid, sblock, lds, s, a);             \
-      else                                                                                            \
-        hipLaunchKernelGGL((k_atrous_comb_sh<CW, false, false, NRM>), grid, sblock, lds, s, a);            \
-    }                                                                                                 \
-  } while (0)
-    if (nrm_mode) {
-      if (cw == base_w + 8)
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 8, true);
-      else if (cw == base_w + 16)
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 16, true);
-      else
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 32, true);
-    } else {
-      if (cw == base_w + 8)
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 8, false);
-      else if (cw == base_w + 16)
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 16, false);
-      else
-        RTPT_LAUNCH_COMB(kBlockX * kShHalves + 32, false);
-    }
-#undef RTPT_LAUNCH_COMB
+    if (!launch_comb(CombInsts{}, cw, nrm_mode, 1, false, final_pass, dim3(per_xcd * 8u), lds, a, s)) std::abort();  // unreachable: cw is an entry's
     return;
   }
   const dim3 g2 = grid_for(a.g);
   a.tiles_x = static_cast<int32_t>(g2.x);
   a.tiles_y = static_cast<int32_t>(g2.y);
   dim3 grid(g2.x * g2.y);
-  if (a.exact) {
-    if (final_pass)
-      hipLaunchKernelGGL((k_atrous<true, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_atrous<false, true>), grid, block, 0, s, a);
-  } else {
-    if (final_pass)
-      hipLaunchKernelGGL((k_atrous<true, false>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_atrous<false, false>), grid, block, 0, s, a);
-  }
+  with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
+    hipLaunchKernelGGL((k_atrous<decltype(fin)::value, decltype(ex)::value>), grid, block, 0, s, a);
+  });
 }
 
 }  // namespace rt

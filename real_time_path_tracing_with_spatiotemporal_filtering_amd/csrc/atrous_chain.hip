@@ -28,8 +28,7 @@
 
 #include "device_common.hpp"
 #include "lds_dma.hpp"
-
-#include <type_traits>
+#include "select.hpp"
 
 #ifndef RTPT_TILE_TIMELINE
 #define RTPT_TILE_TIMELINE 0  // timeline build (scripts/tile_timeline.py): when the workgroups of a launch lived, one workgroup's steps
@@ -46,17 +45,11 @@ namespace {
 #undef RTPT_SPAN_DEVICE
 #endif
 
-#ifndef RTPT_CHAIN_G
-#define RTPT_CHAIN_G 3
-#endif
-constexpr int kChG = RTPT_CHAIN_G;  // rows per level per step = waves per level / 2 (the default; chain_g() picks per pair).
+constexpr int kChG = 3;              // rows per level per step = waves per level / 2 (the default; chain_g() picks per pair).
                                     // 4K pair launches, both pairs averaged: 1: 107.9 us, 2: 100.4, 3: 97.7, 4: 103.1 (more waves
                                     // per workgroup hide more latency until the rings cost a workgroup per CU).  Per pair
                                     // (profiles/r03_chain_g_ab.csv): (1,2): 2: 90.1, 3: 95.2, 4: 90.4; (3,4): 2: 107.2, 3: 97.5, 4: 111.0
-#ifndef RTPT_CHAIN_P
-#define RTPT_CHAIN_P 1
-#endif
-constexpr int kChP = RTPT_CHAIN_P;  // steps between staging an input row and its first use.  Measured at 4K (pair launches
+constexpr int kChP = 1;              // steps between staging an input row and its first use.  Measured at 4K (pair launches
                                     // averaged): 1: 100.7 us, 2: 103.6, 3: 104.1 — with two workgroups per CU the other one's
                                     // arithmetic already covers the DMA flight, and every extra step costs G ring rows of LDS
 constexpr int kChCols = 128;        // columns a level computes at most: two waves per row
@@ -344,6 +337,30 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
   }
 }
 
+// THE list of k_atrous_chain instantiations (each x FINAL x EXACT): levels, rows per level and step, first stride (0: read
+// a.k).  prepare_device_atrous_chain() raises the LDS limit of every entry, launch_atrous_chain() launches the entry
+// (levels, g, a.k) when there is one and the generic (levels, g, 0) otherwise, atrous_chain_supported() reads the widest
+// G per level count from it.  Strides are compile-time constants for the pairs a default frame runs (N = 5: (1,2) and
+// (3,4)), for (4,5), the pair that may end a frame of N = 5 in its FINAL pass, and for the triple (1,2,3).
+template <int L, int G, int K0>
+struct ChainInst {
+  static constexpr int levels = L, g = G, k0 = K0;
+  static_assert(128 * L * G <= 1024, "two waves per row and level: the workgroup must fit 1024 threads");
+};
+using ChainInsts = type_list<ChainInst<2, 3, 0>, ChainInst<2, 3, 1>, ChainInst<2, 3, 3>, ChainInst<2, 3, 4>,
+                             ChainInst<2, 2, 0>, ChainInst<2, 2, 1>,  // the pair (1,2) on tall frames
+                             ChainInst<2, 4, 0>, ChainInst<2, 4, 1>, ChainInst<2, 4, 3>, ChainInst<2, 4, 4>,  // short row segments
+                             ChainInst<3, 2, 0>, ChainInst<3, 2, 1>>;
+template <class... E>
+constexpr bool chain_has(type_list<E...>, int levels, int g, int k0) {
+  return ((E::levels == levels && E::g == g && E::k0 == k0) || ...);
+}
+template <class... E>
+constexpr int chain_g_max(type_list<E...>, int levels) {  // the most rows per step chain_g() may pick; 0: no such chain
+  int m = 0;
+  ((m = E::levels == levels && E::g > m ? E::g : m), ...);
+  return m;
+}
 
 #ifndef RTPT_AB_VARIANTS
 #define RTPT_AB_VARIANTS 0
@@ -368,9 +385,13 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
 //     workgroup, still two workgroups per CU, a quarter fewer steps for the same fill.  Round 4, profiles/r04_chain_g_ab.txt:
 //     the 300-row strip 25.0 -> 21.9 us per pair, 1080p 32.9 -> 31.9, where the 4K frame loses (103 against 97.7).
 // RTPT_CHAIN_G1 (read by rtpt_create, FilterPolicy::chain_g_pin) pins 2, 3 or 4 for A/B runs and tests.
+// Returns 2 for a triple and 2, kChG, 3 or 4 for a pair: each of these needs its generic entry, what a launch falls back to.
+static_assert(chain_has(ChainInsts{}, 3, 2, 0) && chain_has(ChainInsts{}, 2, 2, 0) && chain_has(ChainInsts{}, 2, kChG, 0) &&
+                  chain_has(ChainInsts{}, 2, 3, 0) && chain_has(ChainInsts{}, 2, 4, 0),
+              "ChainInsts lacks a K0 = 0 entry for a (levels, G) that chain_g() returns");
 static int chain_g(int k0, int levels, int n_strips, int rows, int n_cu, int pin) {
   if (levels == 3) return 2;  // two waves per row and level: three levels fit a workgroup of 1 024 threads with two rows per step only
-  if (levels != 2 || kChG != 3) return kChG;
+  if (levels != 2) return kChG;
   if (pin >= 12 && pin <= 14) {  // 12 / 13 / 14: pin the pair (1,2) alone to 2 / 3 / 4 (A/B)
     if (k0 == 1) return pin - 10;
     pin = 0;
@@ -423,24 +444,15 @@ int atrous_chain_strip_width(int k0, int levels) {
   return kChCols - 2 * e0;
 }
 
-template <int L, int G, int K0>
-static hipError_t chain_attrs() {
-  constexpr int kMax = 160 * 1024;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_chain<L, false, false, G, K0>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_chain<L, false, true, G, K0>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_chain<L, true, false, G, K0>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_atrous_chain<L, true, true, G, K0>), hipFuncAttributeMaxDynamicSharedMemorySize, kMax);
-  return e;
-}
 hipError_t prepare_device_atrous_chain() {
-  hipError_t e = chain_attrs<2, kChG, 0>();
-  if (e == hipSuccess) e = (chain_attrs<2, kChG, 3>());  // the pair (3,4)
-  if (e == hipSuccess) e = (chain_attrs<2, kChG, 1>());
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 2, 1>());  // the pair (1,2) on tall frames
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 2, 0>());
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 4, 0>());  // short row segments (strips, small frames): chain_g()
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 4, 1>());
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 4, 3>());
+  hipError_t e = hipSuccess;
+  visit_all(ChainInsts{}, [&](auto inst) {
+    using I = decltype(inst);
+    each_final_exact([&](auto fin, auto ex) {
+      const void* k = reinterpret_cast<const void*>(&k_atrous_chain<I::levels, decltype(fin)::value, decltype(ex)::value, I::g, I::k0>);
+      if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+  });
 #if RTPT_AB_VARIANTS
   constexpr int kMaxLds = 160 * 1024;
 #define RTPT_SW_ATTR(GG)                                                                                                              \
@@ -449,18 +461,13 @@ hipError_t prepare_device_atrous_chain() {
   RTPT_SW_ATTR(2) RTPT_SW_ATTR(3) RTPT_SW_ATTR(4) RTPT_SW_ATTR(6)
 #undef RTPT_SW_ATTR
 #endif
-  if (e == hipSuccess) e = (chain_attrs<3, 2, 0>());
-  if (e == hipSuccess) e = (chain_attrs<3, 2, 1>());                 // (1,2,3)
-  if (e == hipSuccess) e = (chain_attrs<2, kChG, 4>());              // (4,5), the pair that may end a frame of N = 5 in its FINAL pass
-  if (e == hipSuccess && kChG == 3) e = (chain_attrs<2, 4, 4>());
   return e;
 }
 
 // true when `levels` consecutive iterations from stride k0 can run as one chain on this scene
 bool atrous_chain_supported(int k0, int levels, uint32_t n_tris) {
-  if (levels < 2 || levels > 3 || k0 < 1) return false;
-  const int g_max = levels == 3 ? 2 : (levels == 2 && kChG == 3 ? 4 : kChG);  // the most rows per step chain_g() picks
-  if (128 * levels * (levels == 3 ? 2 : kChG) > 1024) return false;  // two waves per row and level: the workgroup must fit 1024 threads
+  const int g_max = chain_g_max(ChainInsts{}, levels);  // (every entry fits a workgroup of 1024 threads: ChainInst)
+  if (g_max == 0 || k0 < 1) return false;
   if (n_tris + 1 > 64) return false;  // id-pair table in LDS (the per-pixel-normal variant is not chained)
   if (atrous_chain_strip_width(k0, levels) < 64) return false;
   return chain_lds(k0, levels, n_tris, g_max) <= 160 * 1024;
@@ -580,50 +587,18 @@ void launch_atrous_chain(const AtrousArgs& a0, int levels, bool final_pass, cons
     return;
   }
 #endif
-#define RTPT_LAUNCH_CHAIN(LV, GG, KK)                                                              \
-  do {                                                                                             \
-    if (a.exact) {                                                                                 \
-      if (final_pass)                                                                              \
-        hipLaunchKernelGGL((k_atrous_chain<LV, true, true, GG, KK>), grid, block, lds, s, a, sg);      \
-      else                                                                                         \
-        hipLaunchKernelGGL((k_atrous_chain<LV, false, true, GG, KK>), grid, block, lds, s, a, sg);     \
-    } else {                                                                                       \
-      if (final_pass)                                                                              \
-        hipLaunchKernelGGL((k_atrous_chain<LV, true, false, GG, KK>), grid, block, lds, s, a, sg);     \
-      else                                                                                         \
-        hipLaunchKernelGGL((k_atrous_chain<LV, false, false, GG, KK>), grid, block, lds, s, a, sg);    \
-    }                                                                                              \
-  } while (0)
-  // strides as compile-time constants for the pairs a default frame runs (N = 5: (1,2) and (3,4)); RTPT_CHAIN_GENERIC=1
-  // runs the generic instantiation for A/B and for the test that the two agree
-  const bool generic = pol.chain_generic != 0;
-  if (levels == 2 && g == 4 && kChG == 3) {
-    if (a.k == 1 && !generic)
-      RTPT_LAUNCH_CHAIN(2, 4, 1);
-    else if (a.k == 3 && !generic)
-      RTPT_LAUNCH_CHAIN(2, 4, 3);
-    else if (a.k == 4 && !generic)
-      RTPT_LAUNCH_CHAIN(2, 4, 4);
-    else
-      RTPT_LAUNCH_CHAIN(2, 4, 0);
-  } else if (levels == 2 && a.k == 4 && !generic && g == kChG) {
-    RTPT_LAUNCH_CHAIN(2, kChG, 4);
-  } else if (levels == 2 && a.k == 1 && !generic) {
-    if (g == 2 && kChG == 3)
-      RTPT_LAUNCH_CHAIN(2, 2, 1);
-    else
-      RTPT_LAUNCH_CHAIN(2, kChG, 1);
-  } else if (levels == 2 && a.k == 3 && !generic)
-    RTPT_LAUNCH_CHAIN(2, kChG, 3);
-  else if (levels == 2 && g == 2 && kChG == 3)
-    RTPT_LAUNCH_CHAIN(2, 2, 0);
-  else if (levels == 2)
-    RTPT_LAUNCH_CHAIN(2, kChG, 0);
-  else if (a.k == 1 && !generic)
-    RTPT_LAUNCH_CHAIN(3, 2, 1);
-  else
-    RTPT_LAUNCH_CHAIN(3, 2, 0);
-#undef RTPT_LAUNCH_CHAIN
+  // RTPT_CHAIN_GENERIC=1 runs the generic instantiation for A/B and for the test that the two agree
+  auto launch = [&](int k0) {
+    return visit_first(ChainInsts{}, [&](auto inst) {
+      using I = decltype(inst);
+      if (I::levels != levels || I::g != g || I::k0 != k0) return false;
+      with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
+        hipLaunchKernelGGL((k_atrous_chain<I::levels, decltype(fin)::value, decltype(ex)::value, I::g, I::k0>), grid, block, lds, s, a, sg);
+      });
+      return true;
+    });
+  };
+  if (!(pol.chain_generic == 0 && launch(a.k)) && !launch(0)) std::abort();  // unreachable: the assertion at chain_g()
 }
 
 }  // namespace rt

@@ -13,22 +13,10 @@ namespace rt {
 constexpr uint32_t kBvhEmpty = 0xFFFFFFFFu;
 // Triangles per leaf: 2 (one fan pair, or two single triangles) since the end of round 4 — K0 + K1 + K2 on the 1.15 M-triangle
 // frame 2 852 us with 4, 2 825 with 2 (profiles/r04_bvh_bins_ab.txt): a leaf is then ONE 80-byte record and its test has no loop.
-#ifndef RTPT_BVH_MAX_LEAF
-#define RTPT_BVH_MAX_LEAF 2
-#endif
-#ifndef RTPT_BVH_MIN_LEAF
-#define RTPT_BVH_MIN_LEAF 1
-#endif
-#ifndef RTPT_BVH_NODE_COST
-#define RTPT_BVH_NODE_COST 1.5f
-#endif
-#ifndef RTPT_BVH_BINS
-#define RTPT_BVH_BINS 32
-#endif
-constexpr int kBvhBins = RTPT_BVH_BINS;  // SAH bins per axis (bvh.cpp; the device restatement bvh_build_sah.hip reads the same value)
-constexpr int kBvhMinLeaf = RTPT_BVH_MIN_LEAF;  // groups this small are always leaves
-constexpr float kNodeCost = RTPT_BVH_NODE_COST;  // cost of a node visit in triangle tests (SAH leaf decision)
-constexpr int kBvhMaxLeaf = RTPT_BVH_MAX_LEAF;  // triangles per leaf (the leaf reference encodes count - 1 in 2 bits)
+constexpr int kBvhMaxLeaf = 2;  // triangles per leaf (the leaf reference encodes count - 1 in 2 bits)
+constexpr int kBvhBins = 32;  // SAH bins per axis (bvh.cpp; the device restatement bvh_build_sah.hip reads the same value)
+constexpr int kBvhMinLeaf = 1;  // groups this small are always leaves
+constexpr float kNodeCost = 1.5f;  // cost of a node visit in triangle tests (SAH leaf decision)
 constexpr int kBvhMaxDepth = 48;  // traversal stack capacity (entries per lane)
 
 // 64 bytes.  A child with cnt > 0 is a leaf: idx = offset of its first record in leaf order.

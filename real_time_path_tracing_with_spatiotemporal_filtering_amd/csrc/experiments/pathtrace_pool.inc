@@ -120,7 +120,7 @@ __device__ __forceinline__ void extend_pool(const SceneView& sc, const float4* r
       const unsigned long long mw = __ballot(walk);
       if (!mw) break;
       const unsigned long long ml = __ballot((cur & kLeafBit) && cur != kSentinel);
-      if (__builtin_popcountll(ml) >= RTPT_BVH_LEAF_RATIO * __builtin_popcountll(mw) && ml) break;
+      if (__builtin_popcountll(ml) >= kBvhLeafRatio * __builtin_popcountll(mw) && ml) break;
       if (walk) {
         const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(sc.nodes) + (cur << 5));
         const uint4 a = np[0], b = np[1];
@@ -171,9 +171,7 @@ __device__ __forceinline__ void extend_pool(const SceneView& sc, const float4* r
 
 template <bool GB>
 __global__ __launch_bounds__(kPtThreads)
-#if RTPT_PT_BVH_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_PT_BVH_WAVES, RTPT_PT_BVH_WAVES)))
-#endif
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace_pool(PathtraceArgs a, GbufferArgs g) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   if (GB && blockIdx.y >= a.tiles_y) {  // the G-buffer's tiles behind the tracing ones (k_gbuffer_pathtrace)

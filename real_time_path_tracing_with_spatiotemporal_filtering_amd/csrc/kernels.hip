@@ -9,6 +9,7 @@
 //
 // No MFMA anywhere: nothing on this path is a dense contraction.  Compile with -ffp-contract=off.
 #include "device_common.hpp"
+#include "select.hpp"
 
 namespace rt {
 namespace {
@@ -177,14 +178,10 @@ __device__ __forceinline__ void closest_hit_brute(const SceneView& sc, f3 o, f3 
   using cv4f = const __attribute__((address_space(4))) v4f;
   cv4f* rec = (cv4f*)sc.isect_id;
   const uint32_t n = sc.n_tris;
-#ifndef RTPT_BRUTE_UNROLL
-#define RTPT_BRUTE_UNROLL 8  // triangles whose records are fetched per batch of scalar loads; K2 at 4K: 2: 517, 4: 505, 8: 499, 16: 498 us
-#endif
-#ifndef RTPT_PAIR_UNROLL
-#define RTPT_PAIR_UNROLL 8  // faces whose records are fetched per batch of scalar loads; K2 at 4K: 2: 384.7, 4: 378.1, 8: 376.3, 16: 376.0 us
-#endif
+  constexpr int kBruteUnroll = 8;  // triangles whose records are fetched per batch of scalar loads; K2 at 4K: 2: 517, 4: 505, 8: 499, 16: 498 us
+  constexpr int kPairUnroll = 8;   // faces whose records are fetched per batch of scalar loads; K2 at 4K: 2: 384.7, 4: 378.1, 8: 376.3, 16: 376.0 us
   if (sc.paired) {  // wave-uniform
-#pragma unroll RTPT_PAIR_UNROLL
+#pragma unroll kPairUnroll
     for (uint32_t i = 0; i < n; i += 2) {
       const v4f a0 = rec[3 * i], a1 = rec[3 * i + 1], a2 = rec[3 * i + 2], b1 = rec[3 * i + 4], b2 = rec[3 * i + 5];
       tri_pair_test(o, d, make_float4(a0.x, a0.y, a0.z, a0.w), make_float4(a1.x, a1.y, a1.z, a1.w), make_float4(a2.x, a2.y, a2.z, a2.w),
@@ -192,7 +189,7 @@ __device__ __forceinline__ void closest_hit_brute(const SceneView& sc, f3 o, f3 
     }
     return;
   }
-#pragma unroll RTPT_BRUTE_UNROLL
+#pragma unroll kBruteUnroll
   for (uint32_t i = 0; i < n; i++) {
     const v4f a0 = rec[3 * i], a1 = rec[3 * i + 1], a2 = rec[3 * i + 2];
     tri_test<false>(o, d, make_float4(a0.x, a0.y, a0.z, a0.w), make_float4(a1.x, a1.y, a1.z, a1.w),
@@ -203,18 +200,13 @@ __device__ __forceinline__ void closest_hit_brute(const SceneView& sc, f3 o, f3 
 // Pixels of a 64 x 4 tile a wave starts on: not row w of the tile but the 16 x 4 block of columns [16 w, 16 w + 16).  Rays that
 // start through neighbouring pixels walk the same BVH nodes, and a block's rays diverge later than a row's (node-loop lane
 // utilisation of the primary rays 0.66 -> 0.77, profiles/r04_wave_block_ab.txt); on small scenes the block's padded
-// screen rectangle meets fewer triangle bounds than a 64-pixel span's.  1: blocks, 0: rows (A/B builds).
-#ifndef RTPT_WAVE_BLOCK
-#define RTPT_WAVE_BLOCK 1
-#endif
-constexpr int kWaveW = RTPT_WAVE_BLOCK ? 16 : 64, kWaveH = RTPT_WAVE_BLOCK ? 4 : 1;  // a wave's footprint in its tile
+// screen rectangle meets fewer triangle bounds than a 64-pixel span's.
+constexpr int kWaveW = 16, kWaveH = 4;  // a wave's footprint in its tile
 __device__ __forceinline__ uint32_t tile_pixel(int wave, uint32_t lane) {  // index (row << 6 | column) within the tile
-  if (RTPT_WAVE_BLOCK) return ((lane >> 4) << 6) | (static_cast<uint32_t>(wave) << 4) | (lane & 15u);
-  return (static_cast<uint32_t>(wave) << 6) | lane;
+  return ((lane >> 4) << 6) | (static_cast<uint32_t>(wave) << 4) | (lane & 15u);
 }
-// first column / row of wave `wave`'s footprint, relative to its tile
-__device__ __forceinline__ int wave_x0(int wave) { return RTPT_WAVE_BLOCK ? 16 * wave : 0; }
-__device__ __forceinline__ int wave_y0(int wave) { return RTPT_WAVE_BLOCK ? 0 : wave; }
+// first column of wave `wave`'s footprint, relative to its tile (its first row is the tile's)
+__device__ __forceinline__ int wave_x0(int wave) { return kWaveW * wave; }
 // Primary rays of one wave (the kWaveW x kWaveH pixels from (x0, y0)) can only hit triangles whose padded
 // screen bounds meet that rectangle.  Lane i classifies triangle i (n <= 64) and the ballot is the
 // candidate set; must be called with the whole wave converged (before any early return).
@@ -263,15 +255,8 @@ __device__ __forceinline__ void closest_hit_brute_set(const SceneView& sc, unsig
 // inv = cell / d and oi = (origin - o) / d a slab distance is one convert + one fma: t = q * inv + oi.
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kSentinel = 0xFFFFFFFEu;
-#ifndef RTPT_GRAD_NT_STORE
-#define RTPT_GRAD_NT_STORE 1
-#endif
-#ifndef RTPT_BVH_LEAF_RATIO
-#define RTPT_BVH_LEAF_RATIO 2  // 0: 2981 us, 1: 2734, 2: 2714, 3: 2728 for K2 on the 1.15M-triangle frame (profiles/r04_bvh_ab.txt)
-#endif
-#ifndef RTPT_LEAF_BATCH
-#define RTPT_LEAF_BATCH 2  // 1: 3.72 ms, 2: 3.65 ms, 4: 4.79 ms (registers) on the 1.15M-triangle trace
-#endif
+constexpr int kBvhLeafRatio = 2;  // waiting lanes per walking lane at which the node loop hands over.  Plain while-while: 2981 us, 1: 2734, 2: 2714, 3: 2728 for K2 on the 1.15M-triangle frame (profiles/r04_bvh_ab.txt)
+constexpr int kLeafBatch = 2;     // 1: 3.72 ms, 2: 3.65 ms, 4: 4.79 ms (registers) on the 1.15M-triangle trace
 
 // Profiling builds (never the shipped library): -DRTPT_BVH_COUNT=1 counts the trips and active lanes of the traversal's loops
 // (scripts/bvh_count.py), -DRTPT_TILE_TIMELINE=1 records when every K0 / K2 workgroup starts and ends (scripts/tile_timeline.py).
@@ -370,14 +355,13 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
       }
       return;
     }
-#if RTPT_LEAF_BATCH > 1
-    // fetch the records of RTPT_LEAF_BATCH triangles before testing any of them: one memory round trip per
+    // fetch the records of kLeafBatch triangles before testing any of them: one memory round trip per
     // batch instead of one per triangle (indices past the leaf are clamped to its last triangle and skipped)
-    for (uint32_t j0 = 0; j0 < cnt; j0 += RTPT_LEAF_BATCH) {
-      float4 rec[RTPT_LEAF_BATCH][3];
-      uint32_t id[RTPT_LEAF_BATCH];
+    for (uint32_t j0 = 0; j0 < cnt; j0 += kLeafBatch) {
+      float4 rec[kLeafBatch][3];
+      uint32_t id[kLeafBatch];
 #pragma unroll
-      for (uint32_t u = 0; u < RTPT_LEAF_BATCH; u++) {
+      for (uint32_t u = 0; u < kLeafBatch; u++) {
         const uint32_t j = j0 + u < cnt ? j0 + u : cnt - 1u;
         const float4* r = sc.isect_leaf + 3 * static_cast<size_t>(first + j);
         rec[u][0] = r[0];
@@ -386,15 +370,9 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
         id[u] = sc.leaf_ids[first + j];
       }
 #pragma unroll
-      for (uint32_t u = 0; u < RTPT_LEAF_BATCH; u++)
+      for (uint32_t u = 0; u < kLeafBatch; u++)
         if (j0 + u < cnt) tri_test<true>(o, d, rec[u][0], rec[u][1], rec[u][2], id[u] + 1, h);
     }
-#else
-    for (uint32_t j = 0; j < cnt; j++) {
-      const float4* r = sc.isect_leaf + 3 * static_cast<size_t>(first + j);
-      tri_test<true>(o, d, r[0], r[1], r[2], sc.leaf_ids[first + j] + 1, h);
-    }
-#endif
   };
   auto node_step = [&]() {
 #if RTPT_BVH_COUNT
@@ -443,9 +421,8 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
       cur = pop();
     }
   };
-#if RTPT_BVH_LEAF_RATIO
   // while-while with an early hand-over: the node loop stops not only when every lane holds a leaf (or is done) but as
-  // soon as the lanes waiting with a leaf outnumber the lanes still walking RTPT_BVH_LEAF_RATIO to one — the few walkers
+  // soon as the lanes waiting with a leaf outnumber the lanes still walking kBvhLeafRatio to one — the few walkers
   // sit out one leaf test instead of the many waiting out the walkers' remaining steps
   while (cur != kSentinel) {
     while (true) {
@@ -454,7 +431,7 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
       if (!mw) break;
       // lanes of this loop that are not walking hold a leaf (or have just run out of nodes): they wait
       const int nw = __builtin_popcountll(mw), na = __builtin_popcountll(__ballot(true));
-      if (na - nw >= RTPT_BVH_LEAF_RATIO * nw) break;
+      if (na - nw >= kBvhLeafRatio * nw) break;
       if (walk) node_step();
     }
     if ((cur & kLeafBit) && cur != kSentinel) {  // a leaf
@@ -462,15 +439,6 @@ __device__ __forceinline__ void closest_hit_bvh(const SceneView& sc, f3 o, f3 d,
       cur = pop();
     }
   }
-#else
-  while (cur != kSentinel) {
-    while (!(cur & kLeafBit)) node_step();  // interior (kSentinel has bit 31 set)
-    if (cur != kSentinel) {  // a leaf
-      test_leaf(cur);
-      cur = pop();
-    }
-  }
-#endif
 }
 
 template <int BVH>
@@ -609,15 +577,11 @@ __device__ __forceinline__ float gradient_lambda(uint32_t id, f3 wp, const float
 }
 
 __device__ __forceinline__ void store_gradient(float4* grad, size_t i, float lam) {
-#if RTPT_GRAD_NT_STORE
   // nothing on the reference's path reads the gradient again (its consumer is commented out,
   // temporalFiltering.comp.glsl:247-248): keep the 133 MB out of the caches the filter passes need
   typedef float v4f_ __attribute__((ext_vector_type(4)));
   v4f_ g4 = {lam, lam, lam, 0.0f};
   __builtin_nontemporal_store(g4, reinterpret_cast<v4f_*>(grad + i));
-#else
-  grad[i] = make_float4(lam, lam, lam, 0.0f);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -693,7 +657,7 @@ __device__ __forceinline__ void gbuffer_tile(const GbufferArgs& a, uint32_t bx, 
   unsigned long long cand = 0;
   if (!BVH && a.cull)
     cand = span_candidates(a.bounds, a.scene.n_tris, static_cast<int>(bx) * kBlockX + wave_x0(static_cast<int>(threadIdx.y)),
-                           a.g.y0 + static_cast<int>(by) * kBlockY + wave_y0(static_cast<int>(threadIdx.y)));
+                           a.g.y0 + static_cast<int>(by) * kBlockY);
   if (x >= a.g.W || y >= a.g.y1) return;
   gbuffer_pixel<BVH>(a, x, y, cand, stack, tid, kThreads, alpha_image, ay0, ay1);
 }
@@ -757,10 +721,7 @@ __device__ __forceinline__ void store_rgb(float4* px, f3 c) {
 // last wave of every later segment, but every compaction is a workgroup barrier on the slowest wave.  Swept at
 // 4K (Cornell 4 segments / 1.15M triangles 8 segments, k_pathtrace): 2 rows 862 us / 4.18 ms, 3 rows 569 / 4.04,
 // 4 rows 517 / 3.99, 8 rows 540 / 4.23, 16 rows 728 / 5.80.
-#ifndef RTPT_PT_ROWS
-#define RTPT_PT_ROWS 4
-#endif
-constexpr int kPtRows = RTPT_PT_ROWS;
+constexpr int kPtRows = 4;
 constexpr int kPtThreads = kBlockX * kPtRows;
 // One path segment after its closest-hit query (raytrace.comp.glsl:226-267): the unoccluded light test, the sky, or a
 // diffuse bounce.  Returns true when the path ended (its colour is then `acc`).
@@ -862,12 +823,7 @@ struct PathState {  // SoA in LDS, one slot per thread
 // The kernel needs its 8 waves per SIMD to hide the scalar-load latency of the brute-force loop; left alone the
 // compiler keeps 106 SGPRs of kernel arguments live (7 waves).  Measured at 4K: 6 / 7 (compiler's choice) / 8 waves
 // 506 / 505 / 479 us (a few dwords of scalar spills are cheaper than the lost wave).
-#ifndef RTPT_PT_WAVES
-#define RTPT_PT_WAVES 8
-#endif
-#ifndef RTPT_PT_CENTER_OUT
-#define RTPT_PT_CENTER_OUT 1
-#endif
+constexpr int kPtWaves = 8;
 // GB: the launch also holds the workgroups of K0 (+ K1) (k_gbuffer_pathtrace below), which put the G-buffer depth into the
 // traced image's alpha themselves: a path that ends stores the 12 bytes of its colour only.  The launch's grid is then
 // taller than the tile grid (a.tiles_y rows of tiles).
@@ -893,7 +849,6 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.y));
   const uint32_t lane = threadIdx.x;
   if (tid == 0) block_rays = 0;
-#if RTPT_PT_CENTER_OUT
   // workgroups are dispatched in the order of their linear index; tiles are taken column by column from the middle of
   // the frame outwards, so the last ones dispatched — the tail of the launch — are the outermost columns, where (camera
   // facing the scene) the paths are short.  A frame of a few thousand tiles is only ~2 generations of workgroups.
@@ -907,9 +862,6 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
     by_ = t_ / gridDim.x;
   }
 #endif
-#else
-  const uint32_t bx_ = blockIdx.x, by_ = blockIdx.y;
-#endif
 #if RTPT_TILE_TIMELINE
   TimelineScope tl_(1, by_ * gridDim.x + bx_);  // indexed by tile
 #endif
@@ -918,7 +870,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
   const f3 light_c = ld3(a.light_c);
   unsigned int rays = 0;
   unsigned long long cand = 0;  // candidate triangles of this wave's (jittered) primary rays
-  if (!BVH && a.cull) cand = span_candidates(a.bounds, a.scene.n_tris, tile_x0 + wave_x0(wave), tile_y0 + wave_y0(wave));
+  if (!BVH && a.cull) cand = span_candidates(a.bounds, a.scene.n_tris, tile_x0 + wave_x0(wave), tile_y0);
 
   // per-thread path registers
   const uint32_t pix0 = tile_pixel(wave, lane);  // the pixel this thread starts on
@@ -1059,22 +1011,16 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
 // SceneView::stack_lds); with the stack's LDS share cut to 16 entries the registers set the limit.  1.15M-triangle trace,
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
-#ifndef RTPT_PT_BVH_WAVES
-#define RTPT_PT_BVH_WAVES 8
-#endif
+constexpr int kPtBvhWaves = 8;
 template <int BVH, bool COMPACT>
 __global__ __launch_bounds__(kPtThreads)
-#if RTPT_PT_BVH_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_PT_BVH_WAVES, RTPT_PT_BVH_WAVES)))
-#endif
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a) {
   pathtrace_tile<BVH, COMPACT, false>(a);
 }
 template <bool COMPACT>
 __global__ __launch_bounds__(kPtThreads)
-#if RTPT_PT_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_PT_WAVES, RTPT_PT_WAVES)))
-#endif
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a) {
   pathtrace_tile<false, COMPACT, false>(a);
 }
@@ -1088,9 +1034,7 @@ void k_pathtrace_small(PathtraceArgs a) {
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
 template <int BVH>
 __global__ __launch_bounds__(kPtThreads)
-#if RTPT_PT_BVH_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_PT_BVH_WAVES, RTPT_PT_BVH_WAVES)))
-#endif
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
   if (blockIdx.y < a.tiles_y) {
     pathtrace_tile<BVH, true, true>(a);
@@ -1103,9 +1047,7 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
   }
 }
 __global__ __launch_bounds__(kPtThreads)
-#if RTPT_PT_WAVES
-__attribute__((amdgpu_waves_per_eu(RTPT_PT_WAVES, RTPT_PT_WAVES)))
-#endif
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g) {
   if (blockIdx.y < a.tiles_y) {
     pathtrace_tile<0, true, true>(a);
@@ -1300,6 +1242,18 @@ __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const
 #undef RTPT_INSTR_HOST
 #endif
 
+// f(mode) with the scene's closest-hit mode as a compile-time constant: 2 BVH over fan pairs, 1 BVH over triangles, 0 brute
+// force (closest_hit<BVH>; the brute-force tile kernels have names of their own, *_small, for their occupancy pin)
+template <class F>
+static void with_scene_mode(const SceneView& sc, F&& f) {
+  if (sc.use_bvh && sc.leaf_pairs)
+    f(std::integral_constant<int, 2>{});
+  else if (sc.use_bvh)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 0>{});
+}
+
 void launch_scene_prepare(const ScenePrepArgs& a, hipStream_t s) {
   if (!a.n_tris) return;
   hipLaunchKernelGGL(k_scene_prepare, dim3((a.n_tris + 255) / 256), dim3(256), 0, s, a);
@@ -1317,12 +1271,10 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
 }
 void launch_gbuffer(const GbufferArgs& a, hipStream_t s) {
   if (a.g.y1 <= a.g.y0) return;
-  if (a.scene.use_bvh && a.scene.leaf_pairs)
-    hipLaunchKernelGGL(k_gbuffer<2>, grid_for(a.g), dim3(kBlockX, kBlockY), a.scene.stack_lds * kThreads * 4, s, a);
-  else if (a.scene.use_bvh)
-    hipLaunchKernelGGL(k_gbuffer<1>, grid_for(a.g), dim3(kBlockX, kBlockY), a.scene.stack_lds * kThreads * 4, s, a);
-  else
-    hipLaunchKernelGGL(k_gbuffer<0>, grid_for(a.g), dim3(kBlockX, kBlockY), 0, s, a);
+  with_scene_mode(a.scene, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    hipLaunchKernelGGL(k_gbuffer<M>, grid_for(a.g), dim3(kBlockX, kBlockY), M ? a.scene.stack_lds * kThreads * 4 : 0, s, a);
+  });
 }
 void launch_gradient(const GradientArgs& a, hipStream_t s) {
   if (a.g.y1 <= a.g.y0) return;
@@ -1384,28 +1336,23 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t
       hipLaunchKernelGGL((k_pathtrace_pool<false>), grid, block, dyn, s, b, GbufferArgs{});
   } else
 #endif
-  if (gb) {
-    if (a.scene.use_bvh && a.scene.leaf_pairs)
-      hipLaunchKernelGGL((k_gbuffer_pathtrace<2>), grid, block, dyn, s, b, *gb);
-    else if (a.scene.use_bvh)
-      hipLaunchKernelGGL((k_gbuffer_pathtrace<1>), grid, block, dyn, s, b, *gb);
-    else
-      hipLaunchKernelGGL(k_gbuffer_pathtrace_small, grid, block, dyn, s, b, *gb);
-  } else if (a.compact) {
-    if (a.scene.use_bvh && a.scene.leaf_pairs)
-      hipLaunchKernelGGL((k_pathtrace<2, true>), grid, block, dyn, s, b);
-    else if (a.scene.use_bvh)
-      hipLaunchKernelGGL((k_pathtrace<1, true>), grid, block, dyn, s, b);
-    else
-      hipLaunchKernelGGL((k_pathtrace_small<true>), grid, block, dyn, s, b);
-  } else {
-    if (a.scene.use_bvh && a.scene.leaf_pairs)
-      hipLaunchKernelGGL((k_pathtrace<2, false>), grid, block, dyn, s, b);
-    else if (a.scene.use_bvh)
-      hipLaunchKernelGGL((k_pathtrace<1, false>), grid, block, dyn, s, b);
-    else
-      hipLaunchKernelGGL((k_pathtrace_small<false>), grid, block, dyn, s, b);
-  }
+  with_scene_mode(a.scene, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    if (gb) {
+      if constexpr (M != 0)
+        hipLaunchKernelGGL((k_gbuffer_pathtrace<M>), grid, block, dyn, s, b, *gb);
+      else
+        hipLaunchKernelGGL(k_gbuffer_pathtrace_small, grid, block, dyn, s, b, *gb);
+      return;
+    }
+    with_bool(a.compact != 0, [&](auto compact) {
+      constexpr bool C = decltype(compact)::value;
+      if constexpr (M != 0)
+        hipLaunchKernelGGL((k_pathtrace<M, C>), grid, block, dyn, s, b);
+      else
+        hipLaunchKernelGGL((k_pathtrace_small<C>), grid, block, dyn, s, b);
+    });
+  });
   if (!split) return;
   const int n_cu = a.n_cu > 0 ? a.n_cu : 256;  // of the context's device (rtpt_create)
   const dim3 qgrid(static_cast<uint32_t>(n_cu) * 8u);
@@ -1421,12 +1368,7 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t
     c.q_out = more ? a.queue[cur ^ 1] : nullptr;
     c.q_out_count = more ? a.queue_count + (cur ^ 1) * kPathQueues : nullptr;
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
-    if (a.scene.use_bvh && a.scene.leaf_pairs)
-      hipLaunchKernelGGL((k_pathtrace_queue<2>), qgrid, block, dyn_queue, s, c);
-    else if (a.scene.use_bvh)
-      hipLaunchKernelGGL((k_pathtrace_queue<1>), qgrid, block, dyn_queue, s, c);
-    else
-      hipLaunchKernelGGL((k_pathtrace_queue<0>), qgrid, block, dyn_queue, s, c);
+    with_scene_mode(a.scene, [&](auto mode) { hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value>), qgrid, block, dyn_queue, s, c); });
     if (end >= a.max_segments) break;
   }
 }
@@ -1444,12 +1386,10 @@ void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, 
                            float* out_t, hipStream_t s) {
   if (!n) return;
   dim3 grid((n + kThreads - 1) / kThreads), block(kThreads);
-  if (scene.use_bvh && scene.leaf_pairs)
-    hipLaunchKernelGGL(k_selftest_trace<2>, grid, block, scene.stack_lds * kThreads * 4, s, scene, rays, n, tmax, out_id, out_t);
-  else if (scene.use_bvh)
-    hipLaunchKernelGGL(k_selftest_trace<1>, grid, block, scene.stack_lds * kThreads * 4, s, scene, rays, n, tmax, out_id, out_t);
-  else
-    hipLaunchKernelGGL(k_selftest_trace<0>, grid, block, 0, s, scene, rays, n, tmax, out_id, out_t);
+  with_scene_mode(scene, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    hipLaunchKernelGGL(k_selftest_trace<M>, grid, block, M ? scene.stack_lds * kThreads * 4 : 0, s, scene, rays, n, tmax, out_id, out_t);
+  });
 }
 
 }  // namespace rt

@@ -223,17 +223,11 @@ void launch_var_prefilter(const FrameGeom& g, int rows_stored, const float* var,
 // more than the denser waves win (1.15M triangles, 8 segments: 3.65 -> 3.80 ms with a window of 4).  Windows shorter
 // than the BASELINE configs' 4 segments lose everywhere, also on the 270-row strip of an 8-rank job (k_pathtrace
 // 89 us in one launch, 108 / 115 us with windows of 3 / 2): the hand-over costs more than the drain tail it removes.
-#ifndef RTPT_PT_PHASE0
-#define RTPT_PT_PHASE0 4
-#endif
-#ifndef RTPT_PATH_QUEUES
-#define RTPT_PATH_QUEUES 1  // 1 / 8 / 16 / 64 regions: reference frame 352 / 403 / 421 / 418 us, 4K 32 segments 1421 / 1434 / 1441 / 1429
-#endif
-constexpr uint32_t kPathQueues = RTPT_PATH_QUEUES;  // regions (and counters) per queue buffer
-#ifndef RTPT_PT_BVH_MULT
-#define RTPT_PT_BVH_MULT 2
-#endif
-inline uint32_t pt_first_window(bool use_bvh) { return use_bvh ? RTPT_PT_BVH_MULT * RTPT_PT_PHASE0 : RTPT_PT_PHASE0; }
+constexpr uint32_t kPtPhase0 = 4, kPtBvhMult = 2;
+inline uint32_t pt_first_window(bool use_bvh) { return use_bvh ? kPtBvhMult * kPtPhase0 : kPtPhase0; }
+// regions (and counters) per queue buffer.  1 / 8 / 16 / 64 regions: reference frame 352 / 403 / 421 / 418 us, 4K 32 segments
+// 1421 / 1434 / 1441 / 1429
+constexpr uint32_t kPathQueues = 1;
 
 constexpr uint32_t kRayCounters = 256;  // RAYCOUNT is kept as this many partial sums (power of two), added up at readback
 
