@@ -20,6 +20,7 @@
 // the C-ABI layer hides the convention (rtpt_readback masks alpha, rtpt_set_plane re-stamps depth).
 #include <cstdlib>
 
+#include "atrous_math.hpp"
 #include "device_common.hpp"
 #include "lds_dma.hpp"
 #include "select.hpp"
@@ -38,26 +39,6 @@ namespace {
 #include "experiments/span_instrumentation.inc"
 #undef RTPT_SPAN_DEVICE
 #endif
-
-// main.cpp:1338-1361 vkCmdBlitImage image (RGBA32F) -> swapchain image (B8G8R8A8_UNORM): the float -> UNORM
-// conversion clamps to [0,1] and quantises; defined here as trunc(x*255 + 0.5) with separate multiply and add (the
-// file is compiled -ffp-contract=off), NaN -> 0 (max(NaN, 0) = 0), which is what output.to_unorm8 / the oracle compute.
-__device__ __forceinline__ uint32_t unorm8(float x) {
-  const float c = fminf(fmaxf(x, 0.0f), 1.0f);
-  return static_cast<uint32_t>(c * 255.0f + 0.5f);
-}
-
-
-// x^n for the normal weight (temporalFiltering.comp.glsl:62).  The reference's exponent is 128: seven squarings,
-// written straight-line — exact::powi's square-and-multiply LOOP yields the same products in the same order but
-// runs its control flow on the CU's single scalar unit, which made per-tap use of it SALU-bound.
-__device__ __forceinline__ float pow_sigma(float x, int n) {
-  if (n == 128) {
-    const float x2 = x * x, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8, x32 = x16 * x16, x64 = x32 * x32;
-    return x64 * x64;
-  }
-  return exact::powi(x, n);
-}
 
 // XCD-aware tile mapping.  Workgroups are dealt round-robin over the 8 XCDs (block b and b+8 share an
 // XCD and its private 4 MiB L2).  The stencil re-reads every input row at y-k, y and y+k, so the three
@@ -108,9 +89,9 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
   const uint32_t idp = a.vis[rowp + x];
   const float4 np4 = a.normal_tab[idp];
   const f3 np = xyz(np4);
+  const EdgeStop es{a.sigma_z, a.sigma_l, a.cz, a.cl};
   f3 num{0.f, 0.f, 0.f};
   float den = 0.f;
-  const float h = 1.0f / 9.0f;  // temporalFiltering.comp.glsl:145
   int qxs[3], qys[3];
 #pragma unroll
   for (int i = 0; i < 3; i++) {
@@ -124,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
     for (int j = 0; j < 3; j++) {  // :133
       float w;
       f3 cq;
-      if (i == 1 && j == 1 && k > 0) {
+      if (i == 1 && j == 1) {
         // centre tap: q == p, so both exponentials are exactly 1 and w = pow(max(0,dot(np,np)),sigma_n)
         cq = cp;
         w = np4.w;
@@ -133,7 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
         const int qx = qxs[i];
         const float4 cq4 = a.in[rowq + qx];
         cq = xyz(cq4);
-        const float dq = cq4.w;  // rgbd
         const uint32_t idq = a.vis[rowq + qx];
         float wn;
         if (idq == idp) {
@@ -142,62 +122,21 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
           const f3 nq = xyz(a.normal_tab[idq]);
           wn = pow_sigma(glsl_max(0.0f, exact::dot(np, nq)), a.sigma_n);  // :62
         }
-        const f3 dc = cp - cq;
-        if (EXACT) {
-          const float wd = exact::exp_(-__builtin_fabsf(dp - dq) / a.sigma_z);  // :67-68
-          const float wl = exact::exp_(-exact::length(dc) / a.sigma_l);         // :73
-          w = (wn * wd) * wl;                                                   // :77
-        } else {
-          // exp(-|dz|/sz) * exp(-|dc|/sl) = exp2(|dz| * cz + |dc| * cl), cz/cl = -log2(e)/sigma
-          const float e = fmaf_(__builtin_fabsf(dp - dq), a.cz, fast::sqrt_(exact::dot(dc, dc)) * a.cl);
-          w = wn * __builtin_amdgcn_exp2f(e);
-        }
+        w = edge_weight<EXACT>(es, wn, cp, cq, dp, cq4.w);  // rgbd
       }
-      if (EXACT) {
-        const float hw = h * w;
-        num = f3{fmaf_(hw, cq.x, num.x), fmaf_(hw, cq.y, num.y), fmaf_(hw, cq.z, num.z)};  // :146
-        den = den + hw;                                                                    // :147
-      } else {
-        // h = 1/9 scales numerator and denominator alike; the fast path drops it
-        num = f3{fmaf_(w, cq.x, num.x), fmaf_(w, cq.y, num.y), fmaf_(w, cq.z, num.z)};
-        den = den + w;
-      }
+      tap_add<EXACT>(num, den, w, cq);
     }
   }
-  f3 filtered;
-  if (EXACT) {
-    filtered = f3{num.x / den, num.y / den, num.z / den};  // :150
-  } else {
-    const float rd = fast::rcp_(den);
-    filtered = num * rd;
-  }
+  const f3 filtered = normalise<EXACT>(num, den);
   if (!FINAL) {
     a.out[rowp + x] = make_float4(filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp);  // :152 (+ depth in alpha)
     return;
   }
-  // :213-239 reprojection — exact arithmetic: the truncated pixel coordinate is an integer observable
-  int ppx = x, ppy = y;
-  if (!(idp < 1)) {
-    const f3 wp = xyz(a.worldpos[rowp + x]);
-    const f3 va = xyz(a.lut_prev[3 * idp]), vb = xyz(a.lut_prev[3 * idp + 1]), vc = xyz(a.lut_prev[3 * idp + 2]);  // :223-233
-    const f3 bc = bary_coords(wp, va, vb, vc);
-    const f3 wpp = bary_mix(bc, va, vb, vc);  // :236
-    const float clx = exact::mat_row_point(a.PVprev, 0, wpp), cly = exact::mat_row_point(a.PVprev, 1, wpp),
-                clw = exact::mat_row_point(a.PVprev, 3, wpp);
-    const float ndx = clx / clw, ndy = cly / clw;                      // :183
-    ppx = exact::f2i(fmaf_(ndx, 0.5f, 0.5f) * static_cast<float>(W));  // :186,:238
-    ppy = exact::f2i(fmaf_(ndy, 0.5f, 0.5f) * static_cast<float>(H));
-  }
+  int ppx, ppy;
+  reproject_pixel(W, H, a.PVprev, idp, xyz(a.worldpos[rowp + x]), a.lut_prev, x, y, ppx, ppy);  // :213-239
   if (a.prev_pixel) a.prev_pixel[rowp + x] = make_int2(ppx, ppy);
-  f3 blend = filtered;  // :258
-  if (a.frame > 0) {    // :251
-    f3 hc{0.f, 0.f, 0.f};  // D2: out-of-image history fetch returns 0
-    if (ppx >= 0 && ppx < W && ppy >= a.hist_y0 && ppy < a.hist_y1)
-      hc = xyz(a.history[static_cast<size_t>(ppy - a.hist_row_base) * W + ppx]);
-    const float oma = 1.0f - a.alpha;
-    blend = f3{fmaf_(filtered.x, a.alpha, hc.x * oma), fmaf_(filtered.y, a.alpha, hc.y * oma),
-               fmaf_(filtered.z, a.alpha, hc.z * oma)};  // :254
-  }
+  f3 blend = filtered;                                                          // :258
+  if (a.frame > 0) blend = temporal_blend(filtered, history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base), a.alpha);  // :251-254
   a.out[rowp + x] = make_float4(blend.x, blend.y, blend.z, 0.0f);  // :263 (D1: distinct buffer)
 }
 
@@ -206,10 +145,7 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
 // use — the 5x5 gaussianKernel2D table (temporalFiltering.comp.glsl:93-99), 2^(k-1) tap stride, the
 // gradient-adaptive alpha (:247-248, commented out) and a disocclusion test on previousVisibilityBuffer
 // (main.cpp:1367: copied every frame, never read).  Opt-in and outside the reference's behaviour, so this is
-// one generic direct-load kernel (same tap arithmetic as k_atrous) rather than a tuned one.
-__constant__ float kGauss5[5][5] = {{1, 4, 7, 4, 1}, {4, 16, 26, 16, 4}, {7, 26, 41, 26, 7}, {4, 16, 26, 16, 4}, {1, 4, 7, 4, 1}};
-
-__device__ __forceinline__ float luminance(f3 c) { return fmaf_(0.0722f, c.z, fmaf_(0.7152f, c.y, 0.2126f * c.x)); }
+// one generic direct-load kernel (k_atrous_ext, atrous_math.hpp's arithmetic like every other) rather than a tuned one.
 
 // RTPT_FLAG_EXT_VARIANCE (extension, see include/rtpt.h): first and second luminance moments accumulated along the
 // reprojected pixel, history length, and the variance the filter iterations are guided by.
@@ -310,12 +246,9 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
   const f3 np = xyz(np4);
   f3 num{0.f, 0.f, 0.f};
   float den = 0.f, vsum = 0.f;
-  // variance guidance (RTPT_FLAG_EXT_VARIANCE): the colour term compares luminances, scaled by the pixel's own
-  // standard deviation
   const bool use_var = (a.ext & kExtVariance) && a.var_in;
-  const float lum_p = luminance(cp);
-  const float lum_scale = use_var ? fmaf_(a.sigma_l, exact::sqrt_(glsl_max((a.var_scale ? a.var_scale : a.var_in)[rowp + x], 0.0f)), 1e-4f) : 1.0f;
-  const float cl_var = -1.44269504088896341f * fast::rcp_(lum_scale);
+  const EdgeStop es{a.sigma_z, a.sigma_l, a.cz, a.cl};
+  const VarGuide vg = var_guide(a.sigma_l, cp, use_var, use_var ? (a.var_scale ? a.var_scale : a.var_in)[rowp + x] : 0.0f);
   for (int i = -R; i <= R; i++) {    // :132
     for (int j = -R; j <= R; j++) {  // :133
       int qx = x + i * k, qy = y + j * k;  // :135
@@ -324,30 +257,17 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
       const size_t rowq = static_cast<size_t>(qy - a.g.row_base) * W;
       const float4 cq4 = a.in[rowq + qx];
       const f3 cq = xyz(cq4);
-      const float dq = cq4.w;
       const uint32_t idq = a.vis[rowq + qx];
       const f3 nq = xyz(a.normal_tab[idq]);
       const float wn = pow_sigma(glsl_max(0.0f, exact::dot(np, nq)), a.sigma_n);  // :62
-      const f3 dc = cp - cq;
-      float w;
-      if (EXACT) {
-        const float wd = exact::exp_(-__builtin_fabsf(dp - dq) / a.sigma_z);  // :67-68
-        const float wl = use_var ? exact::exp_(-__builtin_fabsf(lum_p - luminance(cq)) / lum_scale)
-                                 : exact::exp_(-exact::length(dc) / a.sigma_l);  // :73
-        w = (wn * wd) * wl;                                                   // :77
-      } else {
-        const float dl = use_var ? __builtin_fabsf(lum_p - luminance(cq)) * cl_var : fast::sqrt_(exact::dot(dc, dc)) * a.cl;
-        const float e = fmaf_(__builtin_fabsf(dp - dq), a.cz, dl);
-        w = wn * __builtin_amdgcn_exp2f(e);
-      }
-      const float h = gauss ? kGauss5[i + 2][j + 2] * (1.0f / 273.0f) : 1.0f / 9.0f;  // :145
+      const float w = edge_weight<EXACT>(es, wn, cp, cq, dp, cq4.w, use_var, vg);
+      const float h = gauss ? gauss5(i, j) * (1.0f / 273.0f) : 1.0f / 9.0f;  // :145
       const float hw = h * w;
-      num = f3{fmaf_(hw, cq.x, num.x), fmaf_(hw, cq.y, num.y), fmaf_(hw, cq.z, num.z)};  // :146
-      den = den + hw;                                                                    // :147
+      tap_add_h(num, den, hw, cq);
       if (use_var) vsum = fmaf_(hw * hw, a.var_in[rowq + qx], vsum);
     }
   }
-  const f3 filtered = f3{num.x / den, num.y / den, num.z / den};  // :150
+  const f3 filtered = normalise<true>(num, den);
   if (use_var && a.var_out) a.var_out[rowp + x] = vsum / (den * den);
   if (!FINAL) {
     a.out[rowp + x] = make_float4(filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp);
@@ -357,29 +277,17 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
   reproject_pixel(W, H, a.PVprev, idp, xyz(a.worldpos[rowp + x]), a.lut_prev, x, y, ppx, ppy);
   if (a.prev_pixel) a.prev_pixel[rowp + x] = make_int2(ppx, ppy);
   bool use_history = a.frame > 0;  // :251
-  const bool inside = ppx >= 0 && ppx < W && ppy >= 0 && ppy < H;
-  if (use_history && (a.ext & kExtDisocclusion)) {
-    // same primitive at the reprojected pixel; rows this context does not hold count as disoccluded
-    use_history = inside && ppy >= a.pvis_y0 && ppy < a.pvis_y1 &&
-                  a.prev_vis[static_cast<size_t>(ppy - a.pvis_row_base) * W + ppx] == idp;
-  }
+  if (use_history && (a.ext & kExtDisocclusion))
+    use_history = same_primitive_at(a.prev_vis, W, H, a.pvis_row_base, a.pvis_y0, a.pvis_y1, ppx, ppy, idp);
   f3 blend = filtered;  // :258
   if (use_history) {
-    f3 hc{0.f, 0.f, 0.f};  // D2
-    if (ppx >= 0 && ppx < W && ppy >= a.hist_y0 && ppy < a.hist_y1)
-      hc = xyz(a.history[static_cast<size_t>(ppy - a.hist_row_base) * W + ppx]);
-    float alpha = a.alpha, oma = 1.0f - a.alpha;
-    if (a.ext & kExtAdaptiveAlpha) {  // :247-248
-      const float g = a.gradient[rowp + x].x;
-      alpha = fmaf_(1.0f - g, alpha, g);
-      oma = 1.0f - alpha;
-    }
-    blend = f3{fmaf_(filtered.x, alpha, hc.x * oma), fmaf_(filtered.y, alpha, hc.y * oma), fmaf_(filtered.z, alpha, hc.z * oma)};  // :254
+    const f3 hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
+    float alpha = a.alpha;
+    if (a.ext & kExtAdaptiveAlpha) alpha = adaptive_alpha(alpha, a.gradient[rowp + x].x);
+    blend = temporal_blend(filtered, hc, alpha);
   }
   a.out[rowp + x] = make_float4(blend.x, blend.y, blend.z, 0.0f);
 }
-
-
 
 // "Comb" kernel.
 //
@@ -462,28 +370,14 @@ void k_atrous_comb_sh(AtrousArgs a) {
   const uint32_t xcd = blockIdx.x & 7u, jx = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
   const uint32_t x_lo = static_cast<uint32_t>((static_cast<uint64_t>(nlb) * xcd) >> 3);
   const uint32_t x_hi = static_cast<uint32_t>((static_cast<uint64_t>(nlb) * (xcd + 1)) >> 3);
-  const uint32_t lb_lo = x_lo + static_cast<uint32_t>((static_cast<uint64_t>(x_hi - x_lo) * jx) / per_xcd);
-  const uint32_t lb_hi = x_lo + static_cast<uint32_t>((static_cast<uint64_t>(x_hi - x_lo) * (jx + 1)) / per_xcd);
   const int row_lo = a.g.row_base, row_hi = a.g.row_base + a.rows_stored - 1;
   const bool tail_lane = lane < 2 * R * k;  // columns 64 .. 64+2Rk-1
-  const float h = 1.0f / 9.0f;  // :145
-  // (residue, column, chunk group) of lb_lo, then advanced incrementally (scalar adds, no divisions)
-  int r = static_cast<int>(lb_lo / per_res);
-  int bx, cg;
-  {
-    const uint32_t rem = lb_lo - static_cast<uint32_t>(r) * per_res;
-    bx = static_cast<int>(rem / static_cast<uint32_t>(a.tiles_y));
-    cg = static_cast<int>(rem - static_cast<uint32_t>(bx) * static_cast<uint32_t>(a.tiles_y));
-  }
-  r = __builtin_amdgcn_readfirstlane(r);
-  bx = __builtin_amdgcn_readfirstlane(bx);
-  cg = __builtin_amdgcn_readfirstlane(cg);
+  const EdgeStop es{a.sigma_z, a.sigma_l, a.cz, a.cl};
 
   // row-major list (residue, chunk group, column), dealt to the XCD's blocks item by item: the blocks
   // resident on an XCD work on a few consecutive row bands at any time, so the column halos of x-neighbours
   // and the rows shared by consecutive bands meet in that XCD's L2 (PMC: 245 -> 200 MB fetched per 4K
   // launch against round 2's order, each block walking down a column; 4K 66-72 -> 64-68 us, 1080p 20.5 -> 18.5 us)
-  (void)lb_lo; (void)lb_hi; (void)r; (void)bx; (void)cg;
 #pragma unroll 1
   for (uint32_t lb = x_lo + jx; lb < x_hi; lb += per_xcd) {
   const uint32_t r_u = lb / per_res, rem_u = lb - r_u * per_res;
@@ -577,31 +471,16 @@ void k_atrous_comb_sh(AtrousArgs a) {
     const uint32_t idp = NRM ? (FINAL ? a.vis[ip] : 0u) : ids[cc];  // NRM: the id is only needed for the reprojection
     const float* prow = pairw + idp * NP;
     const float wself = NRM ? np4.w : prow[idp];
-    // FINAL: reproject first (:213-239 — exact arithmetic: the truncated pixel coordinate is an integer observable) so that
-    // the history fetch is in flight under the taps' arithmetic
+    // FINAL: reproject first (:213-239) so that the history fetch is in flight under the taps' arithmetic
     int ppx = x, ppy = y;
-    f3 hc{0.f, 0.f, 0.f};  // D2: out-of-image history fetch returns 0
+    f3 hc{0.f, 0.f, 0.f};
     if (FINAL && NRM) {
-      if (!(idp < 1)) {
-        const f3 wp = wp_pre[mh];
-        const f3 va = xyz(a.lut_prev[3 * idp]), vb = xyz(a.lut_prev[3 * idp + 1]), vc = xyz(a.lut_prev[3 * idp + 2]);  // :223-233
-        const f3 bc = bary_coords(wp, va, vb, vc);
-        const f3 wpp = bary_mix(bc, va, vb, vc);  // :236
-        const float clx = exact::mat_row_point(a.PVprev, 0, wpp), cly = exact::mat_row_point(a.PVprev, 1, wpp),
-                    clw = exact::mat_row_point(a.PVprev, 3, wpp);
-        const float ndx = clx / clw, ndy = cly / clw;                      // :183
-        ppx = exact::f2i(fmaf_(ndx, 0.5f, 0.5f) * static_cast<float>(W));  // :186,:238
-        ppy = exact::f2i(fmaf_(ndy, 0.5f, 0.5f) * static_cast<float>(H));
-      }
-      if (a.frame > 0 && ppx >= 0 && ppx < W && ppy >= a.hist_y0 && ppy < a.hist_y1)  // :251,:253
-        hc = xyz(a.history[static_cast<size_t>(ppy - a.hist_row_base) * W + ppx]);
+      reproject_pixel(W, H, a.PVprev, idp, wp_pre[mh], a.lut_prev, x, y, ppx, ppy);
+      if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);  // :251,:253
     }
     f3 num{0.f, 0.f, 0.f};
     float den = 0.f, vsum = 0.f;
-    // variance guidance (k_atrous_ext's arithmetic): the colour term compares luminances, scaled by the pixel's own deviation
-    const float lum_p = use_var ? luminance(cp) : 0.0f;
-    const float lum_scale = use_var ? fmaf_(a.sigma_l, exact::sqrt_(glsl_max(a.var_scale ? a.var_scale[ip] : varp[cc], 0.0f)), 1e-4f) : 1.0f;
-    const float cl_var = -1.44269504088896341f * fast::rcp_(lum_scale);
+    const VarGuide vg = var_guide(a.sigma_l, cp, use_var, use_var ? (a.var_scale ? a.var_scale[ip] : varp[cc]) : 0.0f);
 #pragma unroll
     for (int i = -R; i <= R; i++) {  // :132 (x offset outer: the reference's accumulation order)
 #pragma unroll
@@ -615,52 +494,24 @@ void k_atrous_comb_sh(AtrousArgs a) {
           const int qi = cc + jj * CWp + i * k;
           const float4 cq4 = col[qi];
           cq = xyz(cq4);
-          const float dq = cq4.w;
           float wn;
           if (NRM) {
             // :62 (pow_sigma: with exact::powi's loop this variant was SALU-bound at 166 us)
             wn = pow_sigma(glsl_max(0.0f, exact::dot(np, xyz(nrm[qi]))), a.sigma_n);
           } else
             wn = prow[ids[qi]];  // :62 via the id-pair table
-          const f3 dc = cp - cq;
-          if (EXACT) {
-            const float wd = exact::exp_(-__builtin_fabsf(dp - dq) / a.sigma_z);  // :67-68
-            const float wl = (EXTA && use_var) ? exact::exp_(-__builtin_fabsf(lum_p - luminance(cq)) / lum_scale)
-                                               : exact::exp_(-exact::length(dc) / a.sigma_l);         // :73
-            w = (wn * wd) * wl;                                                   // :77
-          } else {
-            // exp(-|dz|/sz) * exp(-|dc|/sl) = exp2(|dz| * cz + |dc| * cl), cz/cl = -log2(e)/sigma
-            const float dl = (EXTA && use_var) ? __builtin_fabsf(lum_p - luminance(cq)) * cl_var : fast::sqrt_(exact::dot(dc, dc)) * a.cl;
-            const float e = fmaf_(__builtin_fabsf(dp - dq), a.cz, dl);
-            w = wn * __builtin_amdgcn_exp2f(e);
-          }
+          w = edge_weight<EXACT>(es, wn, cp, cq, dp, cq4.w, use_var, vg);
         }
         if (EXTA) {
-          // k_atrous_ext's accumulation: the tap's own h (gaussianKernel2D / 273, :93-99, or 1/9, :145) stays in
-          constexpr float kG5[5] = {1.f, 4.f, 7.f, 4.f, 1.f}, kG5m[5] = {4.f, 16.f, 26.f, 16.f, 4.f}, kG5c[5] = {7.f, 26.f, 41.f, 26.f, 7.f};
-          const float g = R == 2 ? ((i == 0) ? kG5c[jj + 2] : ((i == -1 || i == 1) ? kG5m[jj + 2] : kG5[jj + 2])) : 9.0f;
-          const float hh = R == 2 ? g * (1.0f / 273.0f) : 1.0f / 9.0f;
-          const float hw = hh * w;
-          num = f3{fmaf_(hw, cq.x, num.x), fmaf_(hw, cq.y, num.y), fmaf_(hw, cq.z, num.z)};  // :146
-          den = den + hw;                                                                    // :147
+          // the extension family keeps the tap's own h (gaussianKernel2D / 273, :93-99, or 1/9, :145)
+          const float hw = (R == 2 ? gauss5(i, jj) * (1.0f / 273.0f) : 1.0f / 9.0f) * w;
+          tap_add_h(num, den, hw, cq);
           if (use_var) vsum = fmaf_(hw * hw, varp[cc + jj * CWp + i * k], vsum);
-        } else if (EXACT) {
-          const float hw = h * w;
-          num = f3{fmaf_(hw, cq.x, num.x), fmaf_(hw, cq.y, num.y), fmaf_(hw, cq.z, num.z)};  // :146
-          den = den + hw;                                                                    // :147
-        } else {
-          // h = 1/9 scales numerator and denominator alike; the fast path drops it
-          num = f3{fmaf_(w, cq.x, num.x), fmaf_(w, cq.y, num.y), fmaf_(w, cq.z, num.z)};
-          den = den + w;
-        }
+        } else
+          tap_add<EXACT>(num, den, w, cq);
       }
     }
-    f3 filtered;
-    if (EXACT || EXTA) {
-      filtered = f3{num.x / den, num.y / den, num.z / den};  // :150
-    } else {
-      filtered = num * fast::rcp_(den);
-    }
+    const f3 filtered = normalise<EXACT || EXTA>(num, den);
     if (EXTA && use_var && a.var_out) a.var_out[ip] = vsum / (den * den);
     if (!FINAL) {
       // non-temporal stores for the k < N passes (the pass does not re-read its output): 65 -> 62.5 us in a frame; a pass
@@ -673,48 +524,25 @@ void k_atrous_comb_sh(AtrousArgs a) {
       continue;
     }
     if (!NRM) {
-      // :213-239 reprojection — exact arithmetic: the truncated pixel coordinate is an integer observable
-      if (!(idp < 1)) {
-        const f3 wp = xyz(a.worldpos[ip]);
-        const f3 va = xyz(a.lut_prev[3 * idp]), vb = xyz(a.lut_prev[3 * idp + 1]), vc = xyz(a.lut_prev[3 * idp + 2]);  // :223-233
-        const f3 bc = bary_coords(wp, va, vb, vc);
-        const f3 wpp = bary_mix(bc, va, vb, vc);  // :236
-        const float clx = exact::mat_row_point(a.PVprev, 0, wpp), cly = exact::mat_row_point(a.PVprev, 1, wpp),
-                    clw = exact::mat_row_point(a.PVprev, 3, wpp);
-        const float ndx = clx / clw, ndy = cly / clw;                      // :183
-        ppx = exact::f2i(fmaf_(ndx, 0.5f, 0.5f) * static_cast<float>(W));  // :186,:238
-        ppy = exact::f2i(fmaf_(ndy, 0.5f, 0.5f) * static_cast<float>(H));
-      }
-      if (a.frame > 0 && ppx >= 0 && ppx < W && ppy >= a.hist_y0 && ppy < a.hist_y1)
-        hc = xyz(a.history[static_cast<size_t>(ppy - a.hist_row_base) * W + ppx]);
+      reproject_pixel(W, H, a.PVprev, idp, xyz(a.worldpos[ip]), a.lut_prev, x, y, ppx, ppy);  // :213-239
+      if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
     }
     if (a.prev_pixel) a.prev_pixel[ip] = make_int2(ppx, ppy);
-    f3 blend = filtered;  // :258
+    f3 blend = filtered;             // :258
     bool use_history = a.frame > 0;  // :251
     float alpha = a.alpha;
-    if (EXTA) {  // the final pass of the extension modes (k_atrous_ext's epilogue)
-      if (use_history && (a.ext & kExtDisocclusion)) {
-        // same primitive at the reprojected pixel; rows this context does not hold count as disoccluded
-        const bool inside = ppx >= 0 && ppx < W && ppy >= 0 && ppy < H;
-        use_history = inside && ppy >= a.pvis_y0 && ppy < a.pvis_y1 &&
-                      a.prev_vis[static_cast<size_t>(ppy - a.pvis_row_base) * W + ppx] == idp;
-      }
-      if (a.ext & kExtAdaptiveAlpha) {  // :247-248
-        const float g = a.gradient[ip].x;
-        alpha = fmaf_(1.0f - g, alpha, g);
-      }
+    if (EXTA) {  // the final pass of the extension modes
+      if (use_history && (a.ext & kExtDisocclusion))
+        use_history = same_primitive_at(a.prev_vis, W, H, a.pvis_row_base, a.pvis_y0, a.pvis_y1, ppx, ppy, idp);
+      if (a.ext & kExtAdaptiveAlpha) alpha = adaptive_alpha(alpha, a.gradient[ip].x);
     }
-    if (use_history) {
-      const float oma = 1.0f - alpha;
-      blend = f3{fmaf_(filtered.x, alpha, hc.x * oma), fmaf_(filtered.y, alpha, hc.y * oma),
-                 fmaf_(filtered.z, alpha, hc.z * oma)};  // :254
-    }
+    if (use_history) blend = temporal_blend(filtered, hc, alpha);
     a.out[ip] = make_float4(blend.x, blend.y, blend.z, 0.0f);  // :263 (D1: distinct buffer)
     // main.cpp:1338-1361, fused: the blit reads exactly the value stored above (alpha 0), k_present's conversion
     // (not in the per-pixel-normal variant: its final pass sits at 79 VGPRs = 6 waves per SIMD, and the store's operands
     // cost it a wave — 142 -> 176 us at 4K; k_present serves those scenes)
     if (!NRM && a.present && y >= a.present_y0 && y < a.present_y1)  // index = ip minus a wave-uniform row offset: no new per-lane address
-      (a.present - static_cast<ptrdiff_t>(a.present_y0 - a.g.row_base) * W)[ip] = unorm8(blend.z) | (unorm8(blend.y) << 8) | (unorm8(blend.x) << 16);
+      (a.present - static_cast<ptrdiff_t>(a.present_y0 - a.g.row_base) * W)[ip] = pack_bgra8(blend, 0.0f);
   }
   }  // work list
 }
@@ -734,7 +562,7 @@ __global__ __launch_bounds__(kThreads) void k_present(FrameGeom g, const float4*
   const int y = g.y0 + blockIdx.y * kBlockY + threadIdx.y;
   if (x >= g.W || y >= g.y1) return;
   const float4 c = image[static_cast<size_t>(y - g.row_base) * g.W + x];
-  dst[static_cast<size_t>(y - g.y0) * g.W + x] = unorm8(c.z) | (unorm8(c.y) << 8) | (unorm8(c.x) << 16) | (unorm8(c.w) << 24);
+  dst[static_cast<size_t>(y - g.y0) * g.W + x] = pack_bgra8(xyz(c), c.w);
 }
 
 }  // namespace
@@ -838,9 +666,8 @@ static bool ext_staged(const AtrousArgs& a) {
 bool atrous_final_fuses_present(const AtrousArgs& a) {
   const int np = static_cast<int>(a.n_tris) + 1;
   const bool pair_mode = a.pair_tab && np <= kPairMax;
-  const bool nrm_mode = !pair_mode && a.normals != nullptr;
   if (a.ext) return ext_staged(a);
-  (void)nrm_mode;  // the per-pixel-normal final pass does not carry the store (register budget, see the kernel)
+  // (pair mode only: the per-pixel-normal final pass does not carry the store — register budget, see the kernel)
   return !a.direct && pair_mode && a.k >= 1 && a.k <= 16;
 }
 

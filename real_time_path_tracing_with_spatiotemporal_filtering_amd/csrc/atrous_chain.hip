@@ -2,7 +2,7 @@
 // launch: iteration k reads what iteration k-1 wrote, so run back to back every pass costs a 16 B/px store and a
 // 20 B/px load that exist only to carry the intermediate image through HBM.  Here the intermediates live in LDS.
 //
-// Per-pixel arithmetic is the single-pass kernel's (temporalFiltering.comp.glsl:118-155: 3x3 taps at stride k,
+// Per-pixel arithmetic is the single-pass kernel's (atrous_math.hpp; temporalFiltering.comp.glsl:118-155: 3x3 taps at stride k,
 // x offset outer / y offset inner, same weights, same accumulation order), and an intermediate is the same binary32
 // value whether it rests in HBM or in LDS — so the chain is bit-identical to the separate passes, in the exact and in
 // the fast weight arithmetic (tests compare the two bit for bit at full size).
@@ -26,6 +26,7 @@
 // (one v_med3 per task), so every staged cell of every level holds exactly what the clamped fetch would return.
 #include <cstdlib>
 
+#include "atrous_math.hpp"
 #include "device_common.hpp"
 #include "lds_dma.hpp"
 #include "select.hpp"
@@ -187,7 +188,6 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
   span_.mark(1);
 #endif
 
-  const float h9 = 1.0f / 9.0f;  // :145
 #pragma unroll 1
   for (int t = 0; t < T; t++) {
     // 1. stage the input rows of this step (consumed kChP steps from now)
@@ -246,26 +246,9 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
               const int qi = rowb[jj + 1] + (i + 1) * st;
               const float4 cq4 = scol[qi];
               cq = xyz(cq4);
-              const float dq = cq4.w;
-              const float wn = prow[sids[qi]];  // :62 via the id-pair table
-              const f3 dc = cp - cq;
-              if (EXACT) {
-                const float wd = exact::exp_(-__builtin_fabsf(dp - dq) / a.sigma_z);  // :67-68
-                const float wl = exact::exp_(-exact::length(dc) / a.sigma_l);         // :73
-                w = (wn * wd) * wl;                                                   // :77
-              } else {
-                const float e = fmaf_(__builtin_fabsf(dp - dq), a.cz, fast::sqrt_(exact::dot(dc, dc)) * a.cl);
-                w = wn * __builtin_amdgcn_exp2f(e);
-              }
+              w = edge_weight<EXACT>(EdgeStop{a.sigma_z, a.sigma_l, a.cz, a.cl}, prow[sids[qi]], cp, cq, dp, cq4.w);  // :62 via the id-pair table
             }
-            if (EXACT) {
-              const float hw_ = h9 * w;
-              num = f3{fmaf_(hw_, cq.x, num.x), fmaf_(hw_, cq.y, num.y), fmaf_(hw_, cq.z, num.z)};  // :146
-              den = den + hw_;                                                                       // :147
-            } else {
-              num = f3{fmaf_(w, cq.x, num.x), fmaf_(w, cq.y, num.y), fmaf_(w, cq.z, num.z)};
-              den = den + w;
-            }
+            tap_add<EXACT>(num, den, w, cq);
           }
         }
         // the two (three) instantiations differ only in constants; left alone, the optimiser sinks them back into ONE body
@@ -280,11 +263,7 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
         taps(std::integral_constant<int, K0 ? K0 + 1 : 0>{});
       else
         taps(std::integral_constant<int, K0 ? K0 + 2 : 0>{});
-      f3 filtered;
-      if (EXACT)
-        filtered = f3{num.x / den, num.y / den, num.z / den};  // :150
-      else
-        filtered = num * fast::rcp_(den);
+      const f3 filtered = normalise<EXACT>(num, den);
       if (!last) {
         // :152 into the next level's ring instead of filteredImageBuffer / image
         const int di = slot_d * kChCols + colv;
@@ -297,19 +276,13 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
           v4f_ o4 = {filtered.x, filtered.y, filtered.z, a.alpha_zero ? 0.0f : dp};
           __builtin_nontemporal_store(o4, reinterpret_cast<v4f_*>(a.out + ip));  // :152; nothing in this launch re-reads it
         } else {
-          // :213-263 reprojection + temporal blend, exact arithmetic (the truncated pixel is an integer observable)
+          // :213-263 reprojection + temporal blend
           int ppx, ppy;
           reproject_pixel(W, H, a.PVprev, idp, xyz(a.worldpos[ip]), a.lut_prev, xv, y, ppx, ppy);
           if (a.prev_pixel) a.prev_pixel[ip] = make_int2(ppx, ppy);
-          f3 blend = filtered;  // :258
-          if (a.frame > 0) {    // :251
-            f3 hc{0.f, 0.f, 0.f};  // D2
-            if (ppx >= 0 && ppx < W && ppy >= a.hist_y0 && ppy < a.hist_y1)
-              hc = xyz(a.history[static_cast<size_t>(ppy - a.hist_row_base) * W + ppx]);
-            const float oma = 1.0f - a.alpha;
-            blend = f3{fmaf_(filtered.x, a.alpha, hc.x * oma), fmaf_(filtered.y, a.alpha, hc.y * oma),
-                       fmaf_(filtered.z, a.alpha, hc.z * oma)};  // :254
-          }
+          f3 blend = filtered;                                                                  // :258
+          if (a.frame > 0)                                                                      // :251-254
+            blend = temporal_blend(filtered, history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base), a.alpha);
           a.out[ip] = make_float4(blend.x, blend.y, blend.z, 0.0f);  // :263 (D1: distinct buffer)
         }
       }

@@ -37,57 +37,30 @@ struct SwRow {
   SwCell l, m, r;  // columns x - s, x, x + s
 };
 
-template <bool EXACT>
-__device__ __forceinline__ void sw_tap(const AtrousArgs& a, const float* prow, f3 cp, float dp, const SwCell& q, f3& num, float& den) {
-  const f3 cq{q.r, q.g, q.b};
-  const float dq = q.d;
-  const float wn = prow[q.id];  // :62 via the id-pair table
-  const f3 dc = cp - cq;
-  if (EXACT) {
-    const float wd = exact::exp_(-__builtin_fabsf(dp - dq) / a.sigma_z);  // :67-68
-    const float wl = exact::exp_(-exact::length(dc) / a.sigma_l);         // :73
-    const float hw_ = (1.0f / 9.0f) * ((wn * wd) * wl);                   // :77, :145
-    num = f3{fmaf_(hw_, cq.x, num.x), fmaf_(hw_, cq.y, num.y), fmaf_(hw_, cq.z, num.z)};  // :146
-    den = den + hw_;                                                                       // :147
-  } else {
-    const float e = fmaf_(__builtin_fabsf(dp - dq), a.cz, fast::sqrt_(exact::dot(dc, dc)) * a.cl);
-    const float w = wn * __builtin_amdgcn_exp2f(e);
-    num = f3{fmaf_(w, cq.x, num.x), fmaf_(w, cq.y, num.y), fmaf_(w, cq.z, num.z)};
-    den = den + w;
-  }
-}
-
 // temporalFiltering.comp.glsl:118-155 for one pixel whose 3x3 taps sit in registers: A = row y - s, B = row y, C = row y + s
 template <bool EXACT>
-__device__ __forceinline__ f3 sw_filter(const AtrousArgs& a, const float* pairw, int NP, const SwRow& A, const SwRow& B, const SwRow& C) {
+__device__ __forceinline__ f3 sw_filter(EdgeStop es, const float* pairw, int NP, const SwRow& A, const SwRow& B, const SwRow& C) {
   const f3 cp{B.m.r, B.m.g, B.m.b};
   const float dp = B.m.d;
   const uint32_t idp = B.m.id;
   const float* prow = pairw + idp * NP;
   f3 num{0.f, 0.f, 0.f};
   float den = 0.f;
+  auto tap = [&](const SwCell& q) {
+    const f3 cq{q.r, q.g, q.b};
+    tap_add<EXACT>(num, den, edge_weight<EXACT>(es, prow[q.id], cp, cq, dp, q.d), cq);  // :62 via the id-pair table
+  };
   // :132-133: x offset outer, y offset inner
-  sw_tap<EXACT>(a, prow, cp, dp, A.l, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, B.l, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, C.l, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, A.m, num, den);
-  {
-    const float w = prow[idp];  // centre tap: q == p, both exponentials are exactly 1
-    if (EXACT) {
-      const float hw_ = (1.0f / 9.0f) * w;
-      num = f3{fmaf_(hw_, cp.x, num.x), fmaf_(hw_, cp.y, num.y), fmaf_(hw_, cp.z, num.z)};
-      den = den + hw_;
-    } else {
-      num = f3{fmaf_(w, cp.x, num.x), fmaf_(w, cp.y, num.y), fmaf_(w, cp.z, num.z)};
-      den = den + w;
-    }
-  }
-  sw_tap<EXACT>(a, prow, cp, dp, C.m, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, A.r, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, B.r, num, den);
-  sw_tap<EXACT>(a, prow, cp, dp, C.r, num, den);
-  if (EXACT) return f3{num.x / den, num.y / den, num.z / den};  // :150
-  return num * fast::rcp_(den);
+  tap(A.l);
+  tap(B.l);
+  tap(C.l);
+  tap(A.m);
+  tap_add<EXACT>(num, den, prow[idp], cp);  // centre tap: q == p, both exponentials are exactly 1
+  tap(C.m);
+  tap(A.r);
+  tap(B.r);
+  tap(C.r);
+  return normalise<EXACT>(num, den);  // :150
 }
 
 template <bool EXACT, int G>
@@ -213,7 +186,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 896), amdgpu_waves_per
   auto emit = [&](const SwRow& A, const SwRow& B, const SwRow& C) {
     const int y = next_y;
     next_y += sl;
-    const f3 filtered = sw_filter<EXACT>(a, pairw, NP, A, B, C);
+    const f3 filtered = sw_filter<EXACT>(EdgeStop{a.sigma_z, a.sigma_l, a.cz, a.cl}, pairw, NP, A, B, C);
     const float dp = B.m.d;
     if (lw == 0) {
       // :152 into the next level's ring instead of filteredImageBuffer
