@@ -157,6 +157,17 @@ typedef struct rtpt_visibility_data {
                                               sets both bits.  Purely additive (a flag bit, a builder value, one debug entry
                                               point): the ABI version stays 5 */
 
+#define RTPT_FLAG_DEVICE_FLATTEN 0x4000u   /* together with RTPT_FLAG_DEVICE_BVH_BUILD (alone it is ignored, like the SAH bit), for
+                                              scenes of more than 64 triangles (smaller ones need the triangles on the host for
+                                              their screen bounds and keep the host path): rtpt_scene_upload copies only the mesh
+                                              and the instance transforms (12 n_verts + 12 n_tris + 48 n_instances bytes), expands
+                                              them into triangles and detects the fan pairs on the device (csrc/scene_flatten.hip:
+                                              the host's arithmetic and the host's memcmp, so the same bits and the same decision),
+                                              then builds there.  One word (paired or not) is read back before the build.  If the
+                                              LBVH comes back deeper than the stack the upload falls back to the host path in the
+                                              same call (host flatten + host SAH, HOST_SAH / FALLBACK_DEPTH).  Same tree, same
+                                              pixels; what changes is the cost of an upload.  Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -305,8 +316,8 @@ struct rtpt_scene_build_info {
 };
 /* RTPT_E_NO_SCENE before an upload.  After a device build it waits for that build's events. */
 int rtpt_scene_build_info(rtpt_ctx* ctx, struct rtpt_scene_build_info* out);
-/* With RTPT_FLAG_DEVICE_BVH_BUILD, rtpt_scene_upload keeps flattening the mesh and detecting fan pairs on the host, uploads
- * the triangles and builds the tree on the device, with one small readback (depth, node count, nodes per height) where the
+/* With RTPT_FLAG_DEVICE_BVH_BUILD, rtpt_scene_upload keeps flattening the mesh and detecting fan pairs on the host
+ * (RTPT_FLAG_DEVICE_FLATTEN moves both to the device too), uploads the triangles and builds the tree on the device, with one small readback (depth, node count, nodes per height) where the
  * host path has its final synchronisation.  A radix tree over 63 key bits and 32 tie-breaking bits can be deeper than
  * the traversal's 48-entry stack (nearly coincident geometry at very different scales): the upload then builds
  * with the host builder in the same call, returns RTPT_OK and reports HOST_SAH / FALLBACK_DEPTH.
@@ -318,6 +329,32 @@ int rtpt_scene_build_info(rtpt_ctx* ctx, struct rtpt_scene_build_info* out);
  * frames without it bit for bit: it changes cost only.  Blocks for the readback.  If the new tree would be deeper than
  * the stack the old one stays and the call returns RTPT_E_INVALID. */
 int rtpt_scene_rebuild(rtpt_ctx* ctx);
+
+/* Replace ALL instance transforms of the uploaded mesh (n_instances x 12 floats, 3x4 row-major, as rtpt_scene_upload takes
+ * them): instances move between frames without a new upload.  Call it between rtpt_end_frame and the next rtpt_gbuffer.
+ * n_instances must equal the upload's count (a scene uploaded without transforms has count 1); triangle ids, LUT sizes,
+ * materials, the model matrix and the history stay.  The next rtpt_gbuffer rebuilds the LUT, LUT_PREV keeps the previous
+ * frame's pose (what K1 and the reprojection read), and frame reuse does not serve that frame.
+ * Cost: scenes that are refit on the device (every BVH scene unless RTPT_HOST_REFIT=1, and every device-built tree — the
+ * scenes whose changed ubo->model costs +0.27 ms) copy 48 bytes per instance and run flatten -> pose (current model) ->
+ * refit -> leaf records on the context's stream, without a host synchronisation; the first call on a scene that was not
+ * uploaded with RTPT_FLAG_DEVICE_FLATTEN also copies the mesh to the device, once.  Other scenes (brute force,
+ * RTPT_HOST_REFIT=1) are flattened again on the host and take the host path of a changed model (blocks).
+ * A refit keeps the TOPOLOGY of the pose the tree was built for: pixels stay exact however far the instances move (boxes
+ * only cull and order), tracing gets slower as boxes of unrelated instances start to overlap.  After large moves the
+ * caller may call rtpt_scene_rebuild.  Fan pairs stay fan pairs (both triangles share the vertices, the transform and
+ * the arithmetic); transforms that would separate a pair straddling two instances (odd triangle count, coincident
+ * instances) are refused.
+ * RTPT_E_NO_SCENE before an upload, RTPT_E_INVALID for NULL arguments or another count; a failed call leaves the scene
+ * untouched. */
+int rtpt_scene_set_instances(rtpt_ctx* ctx, const float* instance_xforms, uint32_t n_instances);
+
+/* How the last rtpt_scene_upload / rtpt_scene_set_instances moved the geometry, so that a test can tell the device path
+ * from a host path that computes the same pixels.
+ * out: [0] host-to-device bytes of geometry (mesh, transforms, triangles; not the tree) copied by that call,
+ * [1] 1 if the triangles the scene now stands on were flattened on the device by that call, [2] 1 if its fan-pair decision
+ * was taken on the device, [3] rtpt_scene_set_instances calls served without a host synchronisation since rtpt_create. */
+int rtpt_debug_upload_info(rtpt_ctx* ctx, uint64_t out[4]);
 
 /* Frame reuse.  K0 and K1 (rtpt_gbuffer, rtpt_temporal_gradient) read the camera, the light, the posed scene and the LUTs
  * and nothing that changes from frame to frame by itself: no frame number, no random stream.  While all of those rest,

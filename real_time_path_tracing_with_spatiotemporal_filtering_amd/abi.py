@@ -28,6 +28,7 @@ FLAG_EXT_SVGF_VARIANCE = 0x800
 FLAG_EXT_MASK = 0x9F0
 FLAG_DEVICE_BVH_BUILD = 0x1000  # rtpt_scene_upload builds the tree on the device (csrc/bvh_build.hip)
 FLAG_DEVICE_BVH_SAH = 0x2000  # with FLAG_DEVICE_BVH_BUILD: the device SAH builder, the host's tree node for node (csrc/bvh_build_sah.hip)
+FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms -> triangles and the fan-pair test on the device (csrc/scene_flatten.hip)
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -110,7 +111,7 @@ SYMBOLS = [
     "rtpt_selftest_math", "rtpt_selftest_exhaustive", "rtpt_selftest_div", "rtpt_selftest_trace", "rtpt_util_look_at", "rtpt_util_perspective", "rtpt_util_load_obj", "rtpt_util_bvh_check", "rtpt_util_bvh_check_pairs",
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
-    "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology",
+    "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
 ]
 
 _lib = None
@@ -173,6 +174,8 @@ def load() -> C.CDLL:
         "rtpt_scene_rebuild": [vp],
         "rtpt_debug_bvh_topology": [vp, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
+        "rtpt_scene_set_instances": [vp, vp, u32],
+        "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
     }
     for name, args in sigs.items():
@@ -333,6 +336,18 @@ class Context:
             ni = len(xf)
         _check(self._lib.rtpt_scene_upload(self._h, _ptr(xyz), len(xyz), _ptr(idx), len(idx), _ptr(xf), ni))
         self.n_tris = len(idx) * max(ni, 1)
+
+    def scene_set_instances(self, instance_xforms: np.ndarray):
+        """replace all instance transforms of the uploaded mesh ([n, 12] or [n, 3, 4], the upload's count): the scene is
+        flattened, posed and refit again, on the device where a changed model matrix is (rtpt_scene_set_instances)"""
+        xf = np.ascontiguousarray(instance_xforms, np.float32).reshape(-1, 12)
+        _check(self._lib.rtpt_scene_set_instances(self._h, _ptr(xf), len(xf)))
+
+    def debug_upload_info(self) -> dict:
+        """how the last scene_upload / scene_set_instances moved the geometry (rtpt_debug_upload_info)"""
+        out = (C.c_uint64 * 4)()
+        _check(self._lib.rtpt_debug_upload_info(self._h, C.byref(out)))
+        return dict(zip(("h2d_bytes", "device_flatten", "device_pairs", "moves_without_sync"), (int(v) for v in out)))
 
     def scene_build_info(self) -> dict:
         """what built the tree that is on the device now (rtpt_scene_build_info): builder, fallback, counts, milliseconds"""

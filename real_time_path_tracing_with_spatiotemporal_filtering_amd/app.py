@@ -71,6 +71,9 @@ class HipBackend:
     def scene_upload(self, xyz, idx, xforms=None):
         self.ctx.scene_upload(xyz, idx, xforms)
 
+    def scene_set_instances(self, xforms):
+        self.ctx.scene_set_instances(xforms)
+
     def gbuffer(self, ubo, y0, y1):
         self.ctx.gbuffer(ubo, y0, y1)
 
@@ -243,6 +246,10 @@ class PipelinedBackend:
         for b in self.be:
             b.scene_upload(xyz, idx, xforms)
 
+    def scene_set_instances(self, xforms):
+        for b in self.be:   # both contexts trace the scene: each is re-posed on its own stream
+            b.scene_set_instances(xforms)
+
     def gbuffer(self, ubo, y0, y1):
         self.cur.gbuffer(ubo, y0, y1)
 
@@ -375,6 +382,8 @@ class PathTracingApplication:
         self.lightPos = np.array(lightPos, np.float32)                 # main.cpp:70
         self.lightColor = np.array(lightColor, np.float32)             # main.cpp:72
         self.cameraMoved = False
+        self._instances_moved = None     # frame of the last setInstanceTransforms call
+        self._bounds_after_move = None   # ... and the bounds sceneBounds returns to once that frame is drawn
         # ubo.model: the reference recomputes it every frame as the identity (main.cpp:1469); an animated scene sets
         # modelMatrix (16 floats, column-major, affine) before drawScene — SURVEY 8(f) rank 4
         self.modelMatrix = np.eye(4, dtype=np.float32).ravel()
@@ -395,17 +404,32 @@ class PathTracingApplication:
     def buildAccelerationStructure(self, instance_xforms=None):
         """main.cpp:687-742 — one BLAS, identity instance unless transforms are given."""
         self.backend.scene_upload(self.objVertices, self.objIndices, instance_xforms)
-        # world-space bounds of the scene (strips bound the reprojection reach with them, strips.reprojection_rows)
+        self.sceneBounds = self._instance_bounds(instance_xforms)
+        self._instances_moved = self._bounds_after_move = None   # a new scene: no move pending
+
+    def _instance_bounds(self, instance_xforms):
+        """world-space bounds of the scene (strips bound the reprojection reach with them, strips.reprojection_rows)"""
         v = np.asarray(self.objVertices, np.float64).reshape(-1, 3)
         v = v[np.unique(np.asarray(self.objIndices).ravel())]
         if instance_xforms is None:
-            self.sceneBounds = (v.min(0), v.max(0))
-        else:
-            m = np.asarray(instance_xforms, np.float64).reshape(-1, 3, 4)
-            c = np.array([[x, y, z] for x in (v[:, 0].min(), v[:, 0].max()) for y in (v[:, 1].min(), v[:, 1].max())
-                          for z in (v[:, 2].min(), v[:, 2].max())])
-            w = np.einsum("nij,kj->nki", m[:, :, :3], c) + m[:, None, :, 3]
-            self.sceneBounds = (w.reshape(-1, 3).min(0), w.reshape(-1, 3).max(0))
+            return v.min(0), v.max(0)
+        m = np.asarray(instance_xforms, np.float64).reshape(-1, 3, 4)
+        c = np.array([[x, y, z] for x in (v[:, 0].min(), v[:, 0].max()) for y in (v[:, 1].min(), v[:, 1].max())
+                      for z in (v[:, 2].min(), v[:, 2].max())])
+        w = np.einsum("nij,kj->nki", m[:, :, :3], c) + m[:, None, :, 3]
+        return w.reshape(-1, 3).min(0), w.reshape(-1, 3).max(0)
+
+    def setInstanceTransforms(self, instance_xforms):
+        """Move the instances of the uploaded mesh before the next drawScene (rtpt_scene_set_instances; no counterpart in
+        the reference, whose one instance never moves).  The frame of the change reprojects from the old pose to the new
+        one, so for that frame sceneBounds is the union of both and the frame counts as moved (_camera_static): strip
+        ranks exchange history and guide bands exactly as for a changed model matrix."""
+        self.backend.scene_set_instances(instance_xforms)
+        new = self._instance_bounds(instance_xforms)
+        old = self.sceneBounds   # of the pose last drawn (or, while an earlier move is still pending, a box around it)
+        self.sceneBounds = (np.minimum(old[0], new[0]), np.maximum(old[1], new[1]))
+        self._bounds_after_move = new
+        self._instances_moved = self.frameCount
 
     def _perspective(self):
         proj = abi.perspective(np.float32(FOV) * 2, np.float32(self.render_width) / np.float32(self.render_height),
@@ -591,6 +615,8 @@ class PathTracingApplication:
         """every pixel reprojects onto itself: view, proj AND model unchanged since the previous frame (an animated
         model matrix moves pixels across strips exactly like a camera move does)"""
         u = self.ubo
+        if self._instances_moved == self.frameCount:   # setInstanceTransforms: moved like a changed model
+            return False
         return (list(u.view) == list(u.viewPrev) and list(u.proj) == list(u.projPrev)
                 and list(u.model) == list(u.modelPrev))
 
@@ -658,7 +684,15 @@ class PathTracingApplication:
             self.drawSceneToImage()
             self.applyTemporalFiltering()
             self.copyImageToSwapChainsCurrentImage()
+        self._end_instance_move()
         self.frameCount += 1
+
+    def _end_instance_move(self):
+        """the frame of a setInstanceTransforms call is over: the bounds are the new pose's alone (callers that drive the
+        passes themselves and count frameCount by hand call this too, or leave the wider bounds in place: still bounds)"""
+        if self._bounds_after_move is not None and self._instances_moved == self.frameCount:
+            self.sceneBounds = self._bounds_after_move
+            self._bounds_after_move = None
 
     def run(self, frames: int, script=None):
         """mainLoop (main.cpp:301) for a fixed number of frames; script[f] = keys held on frame f."""

@@ -342,6 +342,7 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
     else
       c->device_bvh = c->device_bvh || std::atoi(v) != 0;
   }
+  c->device_flatten = c->device_bvh && (cfg->flags & RTPT_FLAG_DEVICE_FLATTEN) != 0;  // alone the bit is ignored
   if (const char* v = std::getenv("RTPT_LBVH_ORDER")) c->lbvh_by_height = !std::strcmp(v, "height");
   if (const char* v = std::getenv("RTPT_NO_TRACE_FUSION")) c->fuse_trace = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_NO_FRAME_REUSE")) c->frame_reuse = std::atoi(v) == 0;
@@ -395,8 +396,13 @@ int rtpt_destroy(rtpt_ctx* c) {
   for (auto& b : c->lut) free_buf(b);
   for (Buf* b : {&c->worldpos, &c->gradient, &c->depth, &c->prev_pixel, &c->hit_id, &c->raycount, &c->normal_tab, &c->pair_tab, &c->tris,
                  &c->leaf_order, &c->isect_id, &c->isect_leaf, &c->shade, &c->nodes, &c->materials, &c->obj_tris_dev, &c->refit_order,
-                 &c->refit_fbox, &c->bvh_grid_dev, &c->ray_tab, &c->bvh_build_scratch, &c->bvh_build_header})
+                 &c->refit_fbox, &c->bvh_grid_dev, &c->ray_tab, &c->bvh_build_scratch, &c->bvh_build_header, &c->mesh_xyz_dev,
+                 &c->mesh_idx_dev, &c->xf_dev, &c->pair_word})
     free_buf(*b);
+  for (auto& st : c->xf_stage) {
+    if (st.done) (void)hipEventDestroy(st.done);
+    if (st.host) (void)hipHostFree(st.host);
+  }
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return RTPT_OK;
@@ -543,6 +549,12 @@ int rtpt_enable_debug(rtpt_ctx* c, uint32_t mask) {
 int rtpt_debug_reuse_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 4; i++) out[i] = c->reuse_info[i];
+  return RTPT_OK;
+}
+
+int rtpt_debug_upload_info(rtpt_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  for (int i = 0; i < 4; i++) out[i] = c->upload_info[i];
   return RTPT_OK;
 }
 

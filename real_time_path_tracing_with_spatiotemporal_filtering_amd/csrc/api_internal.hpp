@@ -125,6 +125,24 @@ struct rtpt_ctx {
   float ray_tab_p00 = 0.f, ray_tab_p11 = 0.f;
   uint32_t ray_tab_w = 0, ray_tab_h = 0;
   std::vector<uint32_t> refit_level_first;  // slice of refit_order per height (levels + 1 entries)
+  // instances (scene_flatten.hip): the mesh and its instance transforms, resident on the device for RTPT_FLAG_DEVICE_FLATTEN
+  // uploads and from the first rtpt_scene_set_instances on (12 n_verts + 12 n_tris + 48 n_instances bytes); the host keeps
+  // the mesh too (the host path re-flattens from it).  xf_stage: pinned staging for the transforms of a call, two in turn,
+  // so that the copy needs no synchronisation and the caller's array may die at return
+  Buf mesh_xyz_dev, mesh_idx_dev, xf_dev, pair_word;
+  std::vector<float> mesh_xyz;
+  std::vector<uint32_t> mesh_idx;
+  uint32_t n_instances = 0;  // of the upload; 1 with has_xf false: uploaded without transforms
+  bool has_xf = false;
+  bool device_flatten = false;  // RTPT_FLAG_DEVICE_FLATTEN (with device_bvh)
+  struct XfStage {
+    void* host = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+    bool pending = false;
+  } xf_stage[2];
+  int xf_stage_cur = 0;
+  uint64_t upload_info[4] = {0, 0, 0, 0};  // rtpt_debug_upload_info
   uint32_t n_nodes = 0;
   bool host_refit = false;  // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
   // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
@@ -144,7 +162,8 @@ struct rtpt_ctx {
   bool no_pairing = false;   // RTPT_NO_TRI_PAIRS=1: A/B switch
   std::vector<float> host_tris;  // flattened world-space triangles, kept for small scenes (screen bounds)
   // animated model matrix (main.cpp:1469 recomputes ubo.model every frame; it is the identity there): the scene as
-  // uploaded (object space = instance transforms applied, model not), its BVH topology, and the model it is posed with
+  // uploaded (object space = instance transforms applied, model not), its BVH topology, and the model it is posed with.
+  // obj_tris is kept where the host reads it: scenes small enough for screen bounds and scenes re-posed on the host
   std::vector<float> obj_tris;
   rt::Bvh bvh_host;
   float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -251,6 +270,7 @@ bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], c
 bool is_identity(const float* m);
 int launch_check(const char* what);
 int apply_model(rtpt_ctx* c, const float* model);  // api_scene.hip
+bool refits_on_device(const rtpt_ctx* c);         // api_scene.hip: a changed pose stays on the device and on the stream
 
 // HIP events around a launch on the launch stream, every rtpt_timing_enable(period)-th frame (rtpt_timing_collect)
 struct Timer {

@@ -1,5 +1,6 @@
 // api_scene.hip — the scene side of the C ABI: rtpt_scene_upload (loadMesh + buildAccelerationStructure, main.cpp:409-462,
-// :687-742), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
+// :687-742; flattened on the host, or on the device: scene_flatten.hip), instances that move between frames
+// (rtpt_scene_set_instances), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
 #include "api_internal.hpp"
 
 #include <chrono>
@@ -20,6 +21,17 @@ rt::ScenePrepArgs scene_prep_args(const rtpt_ctx* c, uint32_t total, bool leaf_p
   sp.shade = static_cast<float4*>(c->shade.ptr);
   sp.leaf_pairs = leaf_pairs ? 1u : 0u;
   return sp;
+}
+
+rt::RefitArgs refit_args(const rtpt_ctx* c) {
+  rt::RefitArgs ra;
+  ra.tris = static_cast<const float*>(c->tris.ptr);
+  ra.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
+  ra.order = static_cast<const uint32_t*>(c->refit_order.ptr);
+  ra.nodes = static_cast<rt::BvhNodeQ*>(c->nodes.ptr);
+  ra.fbox = static_cast<float*>(c->refit_fbox.ptr);
+  ra.grid = static_cast<float*>(c->bvh_grid_dev.ptr);
+  return ra;
 }
 
 // The tree over c->tris (`total` triangles as they stand on the device) built on the device (bvh_build.hip, or
@@ -101,14 +113,7 @@ int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_de
   c->bvh_depth = static_cast<int>(depth);
   c->leaf_pairs = leaf_pairs;
   c->device_tree = true;
-  rt::RefitArgs ra;
-  ra.tris = static_cast<const float*>(c->tris.ptr);
-  ra.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
-  ra.order = static_cast<const uint32_t*>(c->refit_order.ptr);
-  ra.nodes = static_cast<rt::BvhNodeQ*>(c->nodes.ptr);
-  ra.fbox = static_cast<float*>(c->refit_fbox.ptr);
-  ra.grid = static_cast<float*>(c->bvh_grid_dev.ptr);
-  rt::launch_refit(ra, c->refit_level_first.data(), static_cast<int>(levels), n_nodes, 1e-5f, c->stream);
+  rt::launch_refit(refit_args(c), c->refit_level_first.data(), static_cast<int>(levels), n_nodes, 1e-5f, c->stream);
   rt::launch_scene_prepare(scene_prep_args(c, total, leaf_pairs), c->stream);
   const int rcl = launch_check("device BVH build");
   const hipError_t ee = hipEventRecord(c->build_ev[1], c->stream);
@@ -129,33 +134,91 @@ int device_build_tree(rtpt_ctx* c, uint32_t total, bool leaf_pairs, bool* too_de
   return RTPT_OK;
 }
 
-// what rtpt_scene_upload leaves behind once the new scene is on the device (either builder)
-void commit_uploaded_scene(rtpt_ctx* c, std::vector<float>& tris, uint32_t total, uint32_t n_tris, bool paired_all) {
+// the mesh and the instance transforms of one rtpt_scene_upload call
+struct MeshIn {
+  const float* xyz;
+  uint32_t n_verts;
+  const uint32_t* idx;
+  uint32_t n_tris;
+  const float* xf;  // NULL: one identity instance
+  uint32_t ni;      // instances (1 without transforms)
+};
+
+// triangle t of instance inst, un-posed: xf[inst] * xyz[idx[3 t + k]].  THE arithmetic of the flattened scene: k_flatten
+// (scene_flatten.hip) and oracle_flatten state the same expression, so the three agree bit for bit
+inline void flatten_tri(const float* xyz, const uint32_t* idx, const float* xf, uint32_t inst, uint32_t t, float* o) {
+  for (int k = 0; k < 3; k++, o += 3) {
+    const float* v = xyz + 3 * static_cast<size_t>(idx[3 * static_cast<size_t>(t) + k]);
+    if (xf) {
+      const float* m = xf + 12 * static_cast<size_t>(inst);
+      for (int r = 0; r < 3; r++)
+        o[r] = rt::fmaf_(m[4 * r + 2], v[2], rt::fmaf_(m[4 * r + 1], v[1], m[4 * r] * v[0])) + m[4 * r + 3];
+    } else {
+      o[0] = v[0];
+      o[1] = v[1];
+      o[2] = v[2];
+    }
+  }
+}
+
+// flattened world-space triangle soup, id = instance * n_tris + t  (one identity instance in the
+// reference, main.cpp:728-741)
+void host_flatten(const float* xyz, const uint32_t* idx, uint32_t n_tris, const float* xf, uint32_t ni, float* out) {
+  for (uint32_t inst = 0; inst < ni; inst++)
+    for (uint32_t t = 0; t < n_tris; t++) flatten_tri(xyz, idx, xf, inst, t, out + 9 * (static_cast<size_t>(inst) * n_tris + t));
+}
+
+// fan pair (a, b, c), (a, c, d): the posed records are computed from these vertices with one arithmetic, so bitwise
+// equality here is bitwise equality of v0 and of e2_A / e1_B on the device, whatever the model matrix
+inline bool fan_pair(const float* ta, const float* tb) { return std::memcmp(ta, tb, 12) == 0 && std::memcmp(ta + 6, tb + 3, 12) == 0; }
+
+bool host_fan_pairs(const float* tris, uint32_t total) {
+  bool paired_all = total >= 2 && total % 2 == 0;
+  for (uint32_t q = 0; paired_all && q < total / 2; q++) paired_all = fan_pair(tris + 18 * static_cast<size_t>(q), tris + 18 * static_cast<size_t>(q) + 9);
+  return paired_all;
+}
+
+// what rtpt_scene_upload leaves behind once the new scene is on the device (either builder); `tris` may be empty when
+// the triangles were flattened on the device (then nothing on the host reads them)
+int commit_uploaded_scene(rtpt_ctx* c, const MeshIn& in, std::vector<float>& tris, uint32_t total, bool paired_all) {
+  try {
+    c->mesh_xyz.assign(in.xyz, in.xyz + 3 * static_cast<size_t>(in.n_verts));
+    c->mesh_idx.assign(in.idx, in.idx + 3 * static_cast<size_t>(in.n_tris));
+  } catch (const std::bad_alloc&) {
+    c->n_tris = 0;
+    return fail(RTPT_E_NOMEM, "host allocation failed (mesh copy)");
+  }
+  c->n_instances = in.ni;
+  c->has_xf = in.xf != nullptr;
   c->n_tris = total;
-  c->n_base_tris = n_tris;
+  c->n_base_tris = in.n_tris;
   free_buf(c->materials);  // materials belong to the mesh that was replaced
   if (total <= static_cast<uint32_t>(rt::kCullMaxTris))
     c->host_tris = tris;
   else
     c->host_tris.clear();
   c->tris_paired = paired_all && total <= static_cast<uint32_t>(rt::kCullMaxTris);  // the brute-force loops
-  c->obj_tris.swap(tris);
   for (int i = 0; i < 16; i++) c->model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
   c->model_version++;
   c->scene_gen++;
   c->use_bvh = (total > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);
+  if (total <= static_cast<uint32_t>(rt::kCullMaxTris) || !refits_on_device(c))
+    c->obj_tris.swap(tris);
+  else
+    std::vector<float>().swap(c->obj_tris);  // posed on the device from obj_tris_dev: the host copy is never read
   c->lut_prev_valid = false;
   c->lut_version[0] = c->lut_version[1] = ~0ull;
   c->tables_valid = false;
   c->normals_y0 = c->normals_y1 = 0;  // the per-pixel normal plane belongs to the previous scene
+  return RTPT_OK;
 }
 
-// rtpt_scene_upload with RTPT_FLAG_DEVICE_BVH_BUILD: the flattened triangles go up, the tree is built there
-int upload_device_tree(rtpt_ctx* c, std::vector<float>& tris, uint32_t total, uint32_t n_tris, bool paired_all, bool leaf_pairs, bool* too_deep) {
-  HIP_TRY(hipStreamSynchronize(c->stream));
+// the device buffers of a scene of `total` triangles whose tree is built on the device
+int alloc_device_scene(rtpt_ctx* c, uint32_t total) {
   int rc;
-  if ((rc = alloc_buf(c->tris, tris.size() * sizeof(float)))) return rc;
-  if ((rc = alloc_buf(c->obj_tris_dev, tris.size() * sizeof(float)))) return rc;
+  const size_t tri_bytes = static_cast<size_t>(total) * 9 * sizeof(float);
+  if ((rc = alloc_buf(c->tris, tri_bytes))) return rc;
+  if ((rc = alloc_buf(c->obj_tris_dev, tri_bytes))) return rc;
   if ((rc = alloc_buf(c->isect_id, static_cast<size_t>(total) * 48))) return rc;
   if ((rc = alloc_buf(c->isect_leaf, static_cast<size_t>(total) * 48))) return rc;
   if ((rc = alloc_buf(c->shade, static_cast<size_t>(total) * 48))) return rc;
@@ -163,14 +226,82 @@ int upload_device_tree(rtpt_ctx* c, std::vector<float>& tris, uint32_t total, ui
   if ((rc = alloc_buf(c->pair_tab, total + 1 <= 64 ? (static_cast<size_t>(total) + 1) * (total + 1) * 4 : 0))) return rc;
   for (int i = 0; i < 2; i++)
     if ((rc = alloc_buf(c->lut[i], (static_cast<size_t>(total) + 1) * sizeof(rtpt_visibility_data)))) return rc;
-  if ((rc = alloc_buf(c->bvh_grid_dev, 8 * sizeof(float)))) return rc;
+  return alloc_buf(c->bvh_grid_dev, 8 * sizeof(float));
+}
+
+// the mesh and room for its transforms, resident on the device: what k_flatten reads
+int alloc_device_mesh(rtpt_ctx* c, uint32_t n_verts, uint32_t n_tris, uint32_t ni) {
+  int rc;
+  if ((rc = alloc_buf(c->mesh_xyz_dev, static_cast<size_t>(n_verts) * 12))) return rc;
+  if ((rc = alloc_buf(c->mesh_idx_dev, static_cast<size_t>(n_tris) * 12))) return rc;
+  return alloc_buf(c->xf_dev, static_cast<size_t>(ni) * 48);
+}
+
+void drop_device_mesh(rtpt_ctx* c) {
+  for (Buf* b : {&c->mesh_xyz_dev, &c->mesh_idx_dev, &c->xf_dev}) free_buf(*b);
+}
+
+rt::FlattenArgs flatten_args(const rtpt_ctx* c, uint32_t n_tris, uint32_t total, bool with_xf) {
+  rt::FlattenArgs fa;
+  fa.n_tris = n_tris;
+  fa.n_out_verts = total * 3;
+  fa.xyz = static_cast<const float*>(c->mesh_xyz_dev.ptr);
+  fa.idx = static_cast<const uint32_t*>(c->mesh_idx_dev.ptr);
+  fa.xf = with_xf ? static_cast<const float*>(c->xf_dev.ptr) : nullptr;
+  fa.out = static_cast<float*>(c->obj_tris_dev.ptr);
+  return fa;
+}
+
+// rtpt_scene_upload with RTPT_FLAG_DEVICE_BVH_BUILD: the flattened triangles go up, the tree is built there
+int upload_device_tree(rtpt_ctx* c, const MeshIn& in, std::vector<float>& tris, uint32_t total, bool paired_all, bool leaf_pairs, bool* too_deep) {
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = alloc_device_scene(c, total))) return rc;
+  drop_device_mesh(c);  // of the scene that is replaced
   c->n_tris = 0;  // the previous scene's buffers are gone: no scene until this one is complete
   HIP_TRY(hipMemcpyAsync(c->tris.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->obj_tris_dev.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  c->upload_info[0] += 2 * tris.size() * sizeof(float);
   for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->lut[i].ptr, 0, c->lut[i].bytes, c->stream));
   // the builder's readback synchronises behind these copies, so the staging vector may die at return
   if ((rc = device_build_tree(c, total, leaf_pairs, too_deep)) || *too_deep) return rc;
-  commit_uploaded_scene(c, tris, total, n_tris, paired_all);
+  return commit_uploaded_scene(c, in, tris, total, paired_all);
+}
+
+// ... with RTPT_FLAG_DEVICE_FLATTEN too: only the mesh and the transforms go up; triangles and the fan-pair decision are
+// made there (scene_flatten.hip), one word comes back before the build because the primitive width depends on it
+int upload_device_flatten(rtpt_ctx* c, const MeshIn& in, uint32_t total, bool* too_deep) {
+  // every kernel below indexes 3 x total vertices in 32 bits; the traversal's own limit is tighter and is checked first
+  if (static_cast<uint64_t>(total) * 48u >= (1ull << 32))
+    return fail(RTPT_E_INVALID, "scene too large for the traversal's 32-bit record offsets (more than 89,478,485 triangles)");
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = alloc_device_scene(c, total)) || (rc = alloc_device_mesh(c, in.n_verts, in.n_tris, in.ni))) return rc;
+  if (!c->pair_word.ptr && (rc = alloc_buf(c->pair_word, 4))) return rc;
+  c->n_tris = 0;  // the previous scene's buffers are gone: no scene until this one is complete
+  HIP_TRY(hipMemcpyAsync(c->mesh_xyz_dev.ptr, in.xyz, static_cast<size_t>(in.n_verts) * 12, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->mesh_idx_dev.ptr, in.idx, static_cast<size_t>(in.n_tris) * 12, hipMemcpyHostToDevice, c->stream));
+  if (in.xf) HIP_TRY(hipMemcpyAsync(c->xf_dev.ptr, in.xf, static_cast<size_t>(in.ni) * 48, hipMemcpyHostToDevice, c->stream));
+  c->upload_info[0] += static_cast<uint64_t>(in.n_verts) * 12 + static_cast<uint64_t>(in.n_tris) * 12 + (in.xf ? static_cast<uint64_t>(in.ni) * 48 : 0);
+  rt::launch_flatten(flatten_args(c, in.n_tris, total, in.xf != nullptr), c->stream);
+  const bool even = total >= 2 && total % 2 == 0;
+  uint32_t word = 0;
+  if (even) {
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->pair_word.ptr), 1, 1, c->stream));
+    rt::launch_fan_pairs(total / 2, static_cast<const float*>(c->obj_tris_dev.ptr), static_cast<uint32_t*>(c->pair_word.ptr), c->stream);
+    HIP_TRY(hipMemcpyAsync(&word, c->pair_word.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  rt::RefitModel rm{};  // a fresh upload stands under the identity model: tris = obj_tris_dev
+  rm.identity = 1;
+  rt::launch_pose(total * 3, static_cast<const float*>(c->obj_tris_dev.ptr), static_cast<float*>(c->tris.ptr), rm, c->stream);
+  for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->lut[i].ptr, 0, c->lut[i].bytes, c->stream));
+  if ((rc = launch_check("device flatten"))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the pair word; the caller's arrays may die at return
+  const bool paired_all = even && word == 1u;
+  if ((rc = device_build_tree(c, total, paired_all && !c->no_pairing, too_deep)) || *too_deep) return rc;
+  std::vector<float> none;
+  if ((rc = commit_uploaded_scene(c, in, none, total, paired_all))) return rc;
+  c->upload_info[1] = c->upload_info[2] = 1;
   return RTPT_OK;
 }
 
@@ -189,41 +320,31 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
   const double t_call = now_ms();
-  const uint32_t ni = (xf && n_instances) ? n_instances : 1;
+  if (!(xf && n_instances)) xf = nullptr;
+  const uint32_t ni = xf ? n_instances : 1;
   const uint64_t total64 = static_cast<uint64_t>(ni) * n_tris;
   if (total64 >= 0xFFFFFFF0ull) return fail(RTPT_E_INVALID, "too many triangles");
   const uint32_t total = static_cast<uint32_t>(total64);
-  // flattened world-space triangle soup, id = instance * n_tris + t  (one identity instance in the
-  // reference, main.cpp:728-741)
-  std::vector<float> tris(static_cast<size_t>(total) * 9);
-  for (uint32_t inst = 0; inst < ni; inst++)
-    for (uint32_t t = 0; t < n_tris; t++)
-      for (int k = 0; k < 3; k++) {
-        const float* v = xyz + 3 * static_cast<size_t>(idx[3 * t + k]);
-        float* o = tris.data() + 9 * (static_cast<size_t>(inst) * n_tris + t) + 3 * k;
-        if (xf && n_instances) {
-          const float* m = xf + 12 * static_cast<size_t>(inst);
-          for (int r = 0; r < 3; r++)
-            o[r] = rt::fmaf_(m[4 * r + 2], v[2], rt::fmaf_(m[4 * r + 1], v[1], m[4 * r] * v[0])) + m[4 * r + 3];
-        } else {
-          o[0] = v[0];
-          o[1] = v[1];
-          o[2] = v[2];
-        }
-      }
-  // fan pairs (a, b, c), (a, c, d): the posed records are computed from these vertices with one arithmetic, so bitwise
-  // equality here is bitwise equality of v0 and of e2_A / e1_B on the device, whatever the model matrix
-  bool paired_all = total >= 2 && total % 2 == 0;
-  for (uint32_t q = 0; paired_all && q < total / 2; q++) {
-    const float* ta = tris.data() + 18 * static_cast<size_t>(q);
-    const float* tb = ta + 9;
-    paired_all = std::memcmp(ta, tb, 12) == 0 && std::memcmp(ta + 6, tb + 3, 12) == 0;
-  }
-  const bool leaf_pairs = paired_all && !c->no_pairing;
+  const MeshIn in{xyz, n_verts, idx, n_tris, xf, ni};
+  c->upload_info[0] = c->upload_info[1] = c->upload_info[2] = 0;
   uint32_t fallback = RTPT_BVH_FALLBACK_NONE;
-  if (c->device_bvh) {
+  if (c->device_bvh && c->device_flatten && total > static_cast<uint32_t>(rt::kCullMaxTris)) {
     bool too_deep = false;
-    const int rcd = upload_device_tree(c, tris, total, n_tris, paired_all, leaf_pairs, &too_deep);
+    const int rcd = upload_device_flatten(c, in, total, &too_deep);
+    if (rcd) return rcd;
+    if (!too_deep) {
+      c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
+      return RTPT_OK;
+    }
+    fallback = RTPT_BVH_FALLBACK_DEPTH;  // as below: the host path, flatten included, in the same call
+  }
+  std::vector<float> tris(static_cast<size_t>(total) * 9);
+  host_flatten(xyz, idx, n_tris, xf, ni, tris.data());
+  const bool paired_all = host_fan_pairs(tris.data(), total);
+  const bool leaf_pairs = paired_all && !c->no_pairing;
+  if (c->device_bvh && fallback == RTPT_BVH_FALLBACK_NONE) {
+    bool too_deep = false;
+    const int rcd = upload_device_tree(c, in, tris, total, paired_all, leaf_pairs, &too_deep);
     if (rcd) return rcd;
     if (!too_deep) {
       c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
@@ -262,6 +383,8 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   if ((rc = alloc_buf(c->pair_tab, total + 1 <= 64 ? (static_cast<size_t>(total) + 1) * (total + 1) * 4 : 0))) return rc;
   for (int i = 0; i < 2; i++)
     if ((rc = alloc_buf(c->lut[i], (static_cast<size_t>(total) + 1) * sizeof(rtpt_visibility_data)))) return rc;
+  drop_device_mesh(c);  // of the scene that is replaced
+  c->upload_info[0] += 2 * tris.size() * sizeof(float);  // tris here, obj_tris_dev below
   HIP_TRY(hipMemcpyAsync(c->tris.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->leaf_order.ptr, bvh.leaf_order.data(), static_cast<size_t>(total) * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->nodes.ptr, nodes_h.data(), nodes_h.size() * sizeof(rt::BvhNodeQ), hipMemcpyHostToDevice, c->stream));
@@ -298,15 +421,7 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   HIP_TRY(hipMemcpyAsync(c->obj_tris_dev.ptr, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->refit_order.ptr, order_h.data(), order_h.size() * 4, hipMemcpyHostToDevice, c->stream));
   for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->lut[i].ptr, 0, c->lut[i].bytes, c->stream));
-  rt::ScenePrepArgs sp;
-  sp.n_tris = total;
-  sp.tris = static_cast<const float*>(c->tris.ptr);
-  sp.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
-  sp.isect_id = static_cast<float4*>(c->isect_id.ptr);
-  sp.isect_leaf = static_cast<float4*>(c->isect_leaf.ptr);
-  sp.shade = static_cast<float4*>(c->shade.ptr);
-  sp.leaf_pairs = leaf_pairs ? 1u : 0u;
-  rt::launch_scene_prepare(sp, c->stream);
+  rt::launch_scene_prepare(scene_prep_args(c, total, leaf_pairs), c->stream);
   if ((rc = launch_check("scene_prepare"))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
   free_buf(c->stack_spill);  // sized by the depth of the tree that was replaced
@@ -323,7 +438,7 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
   c->build_info.leaf_pairs = leaf_pairs ? 1u : 0u;
   c->build_info.build_ms = static_cast<float>(build_ms);
   c->bvh_host = std::move(bvh);  // only now: the upload succeeded
-  commit_uploaded_scene(c, tris, total, n_tris, paired_all);
+  if ((rc = commit_uploaded_scene(c, in, tris, total, paired_all))) return rc;
   c->build_info.upload_ms = static_cast<float>(now_ms() - t_call);
   return RTPT_OK;
 }
@@ -335,38 +450,34 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
 // triangles, the device records are rebuilt.  Every pass — K0, K2, the LUT — sees the posed geometry.
 }  // extern "C"
 
-// ubo.model changed (main.cpp:1469 recomputes it every frame; an animated scene passes another one): re-pose the scene
-int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
+// a device-built tree has no host copy (bvh_host is empty): it is refit on the device whatever traces the scene —
+// also the small scenes that trace by brute force, whose host_tris are still re-posed on the host
+bool rtpt_impl::refits_on_device(const rtpt_ctx* c) {
+  return ((c->use_bvh && !c->host_refit) || c->device_tree) && c->obj_tris_dev.ptr && c->refit_order.ptr;
+}
+
+namespace {
+
+// The posed scene follows its inputs: the un-posed triangles (obj_tris_dev / obj_tris — they change with
+// rtpt_scene_set_instances) and the model (it changes with ubo.model, rtpt_gbuffer).  Whichever of the two changed, this is
+// the one routine that re-poses, refits and rebuilds the records, and marks LUT, tables and frame reuse stale.
+int repose_scene(rtpt_ctx* c, const float* model) {
   const uint32_t total = c->n_tris;
   const bool ident = is_identity(model);
-  // a device-built tree has no host copy (bvh_host is empty): it is refit on the device whatever traces the scene —
-  // also the small scenes that trace by brute force, whose host_tris are still re-posed on the host below
-  if (((c->use_bvh && !c->host_refit) || c->device_tree) && c->obj_tris_dev.ptr && c->refit_order.ptr) {
+  const bool small = total <= static_cast<uint32_t>(rt::kCullMaxTris);
+  if ((small || !refits_on_device(c)) && c->obj_tris.size() != static_cast<size_t>(total) * 9)
+    return fail(RTPT_E_INVALID, "internal: the host copy of the un-posed triangles is missing");
+  if (refits_on_device(c)) {
     // everything on the device and on the context's stream: no upload, no synchronisation (refit.hip)
     rt::RefitModel rm;
     std::memcpy(rm.m, model, sizeof rm.m);
     rm.identity = ident ? 1 : 0;
     rt::launch_pose(total * 3, static_cast<const float*>(c->obj_tris_dev.ptr), static_cast<float*>(c->tris.ptr), rm, c->stream);
-    rt::RefitArgs ra;
-    ra.tris = static_cast<const float*>(c->tris.ptr);
-    ra.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
-    ra.order = static_cast<const uint32_t*>(c->refit_order.ptr);
-    ra.nodes = static_cast<rt::BvhNodeQ*>(c->nodes.ptr);
-    ra.fbox = static_cast<float*>(c->refit_fbox.ptr);
-    ra.grid = static_cast<float*>(c->bvh_grid_dev.ptr);
-    rt::launch_refit(ra, c->refit_level_first.data(), static_cast<int>(c->refit_level_first.size()) - 1, c->n_nodes, 1e-5f, c->stream);
-    rt::ScenePrepArgs sp;
-    sp.n_tris = total;
-    sp.tris = static_cast<const float*>(c->tris.ptr);
-    sp.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
-    sp.isect_id = static_cast<float4*>(c->isect_id.ptr);
-    sp.isect_leaf = static_cast<float4*>(c->isect_leaf.ptr);
-    sp.shade = static_cast<float4*>(c->shade.ptr);
-    sp.leaf_pairs = c->leaf_pairs ? 1u : 0u;
-    rt::launch_scene_prepare(sp, c->stream);
+    rt::launch_refit(refit_args(c), c->refit_level_first.data(), static_cast<int>(c->refit_level_first.size()) - 1, c->n_nodes, 1e-5f, c->stream);
+    rt::launch_scene_prepare(scene_prep_args(c, total, c->leaf_pairs), c->stream);
     int rcd = launch_check("device refit");
     if (rcd) return rcd;
-    if (total <= static_cast<uint32_t>(rt::kCullMaxTris)) {
+    if (small) {
       // a small scene forced onto the BVH path: the screen bounds (unused while it is) still follow the pose
       c->host_tris.resize(static_cast<size_t>(total) * 9);
       for (size_t v = 0; v < static_cast<size_t>(total) * 3; v++) {
@@ -380,7 +491,7 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
     }
     std::memcpy(c->model, model, sizeof c->model);
     c->model_version++;
-  c->scene_gen++;
+    c->scene_gen++;
     c->tables_valid = false;
     return RTPT_OK;
   }
@@ -406,19 +517,11 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
   const float grid_h[8] = {c->bvh_grid.origin[0], c->bvh_grid.origin[1], c->bvh_grid.origin[2], c->bvh_grid.cell[0],
                            c->bvh_grid.cell[1], c->bvh_grid.cell[2], 0.f, 0.f};
   HIP_TRY(hipMemcpyAsync(c->bvh_grid_dev.ptr, grid_h, sizeof grid_h, hipMemcpyHostToDevice, c->stream));
-  rt::ScenePrepArgs sp;
-  sp.n_tris = total;
-  sp.tris = static_cast<const float*>(c->tris.ptr);
-  sp.leaf_order = static_cast<const uint32_t*>(c->leaf_order.ptr);
-  sp.isect_id = static_cast<float4*>(c->isect_id.ptr);
-  sp.isect_leaf = static_cast<float4*>(c->isect_leaf.ptr);
-  sp.shade = static_cast<float4*>(c->shade.ptr);
-  sp.leaf_pairs = c->leaf_pairs ? 1u : 0u;
-  rt::launch_scene_prepare(sp, c->stream);
+  rt::launch_scene_prepare(scene_prep_args(c, total, c->leaf_pairs), c->stream);
   int rc = launch_check("scene_prepare");
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
-  if (total <= static_cast<uint32_t>(rt::kCullMaxTris)) c->host_tris.swap(tris);
+  if (small) c->host_tris.swap(tris);
   std::memcpy(c->model, model, sizeof c->model);
   c->model_version++;
   c->scene_gen++;
@@ -426,7 +529,119 @@ int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) {
   return RTPT_OK;
 }
 
+// the transforms of one rtpt_scene_set_instances call, to xf_dev through pinned memory: a copy the stream runs in order,
+// that neither waits for the stream nor reads the caller's array after the call.  Two staging buffers in turn; the event
+// waited for belongs to the call before last (long finished unless the host runs two whole frames ahead)
+int stage_transforms(rtpt_ctx* c, const float* xf, size_t bytes) {
+  rtpt_ctx::XfStage& st = c->xf_stage[c->xf_stage_cur];
+  if (!st.done) HIP_TRY(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+  if (st.pending) {
+    HIP_TRY(hipEventSynchronize(st.done));
+    st.pending = false;
+  }
+  if (st.bytes < bytes) {
+    if (st.host) (void)hipHostFree(st.host);
+    st.host = nullptr;
+    st.bytes = 0;
+    if (hipHostMalloc(&st.host, bytes, hipHostMallocDefault) != hipSuccess) return fail(RTPT_E_NOMEM, "pinned host allocation failed");
+    st.bytes = bytes;
+  }
+  std::memcpy(st.host, xf, bytes);
+  HIP_TRY(hipMemcpyAsync(c->xf_dev.ptr, st.host, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(st.done, c->stream));
+  st.pending = true;
+  c->xf_stage_cur ^= 1;
+  return RTPT_OK;
+}
+
+}  // namespace
+
+// ubo.model changed (main.cpp:1469 recomputes it every frame; an animated scene passes another one): re-pose the scene
+int rtpt_impl::apply_model(rtpt_ctx* c, const float* model) { return repose_scene(c, model); }
+
 extern "C" {
+
+int rtpt_scene_set_instances(rtpt_ctx* c, const float* xf, uint32_t n_instances) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!xf) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n_instances != c->n_instances)
+    return fail(RTPT_E_INVALID, "the instance count is the upload's (1 for a scene uploaded without transforms): upload again to change it");
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  const uint32_t total = c->n_tris, nt = c->n_base_tris, ni = n_instances;
+  const float* mx = c->mesh_xyz.data();
+  const uint32_t* mi = c->mesh_idx.data();
+  // A refit keeps the topology, pairs included.  A pair inside one instance stays a pair (the same vertices through the
+  // same transform and arithmetic); one that straddles two instances (odd triangle count) was a pair by coincidence
+  if ((c->leaf_pairs || c->tris_paired) && (nt & 1u))
+    for (uint32_t b = 0; b + 1 < ni; b++) {
+      if ((static_cast<uint64_t>(b + 1) * nt - 1) & 1u) continue;  // the last triangle of instance b has an odd id: it ends a pair
+      float ta[9], tb[9];
+      flatten_tri(mx, mi, xf, b, nt - 1, ta);
+      flatten_tri(mx, mi, xf, b + 1, 0, tb);
+      if (!fan_pair(ta, tb))
+        return fail(RTPT_E_INVALID, "these transforms separate a fan pair that straddles two instances: upload the scene again");
+    }
+  const bool small = total <= static_cast<uint32_t>(rt::kCullMaxTris);
+  const bool on_device = refits_on_device(c);
+  std::vector<float> obj;  // the host's un-posed triangles, where the host reads them (as commit_uploaded_scene keeps them)
+  bool paired = c->tris_paired;
+  if (small || !on_device) {
+    obj.resize(static_cast<size_t>(total) * 9);
+    host_flatten(mx, mi, nt, xf, ni, obj.data());
+    paired = host_fan_pairs(obj.data(), total) && small;  // the brute-force loops
+  }
+  uint64_t bytes = 0;
+  if (on_device) {
+    int rc;
+    if (!c->mesh_xyz_dev.ptr) {  // first move of a scene that was flattened on the host: the mesh goes up, once
+      if ((rc = alloc_device_mesh(c, static_cast<uint32_t>(c->mesh_xyz.size() / 3), nt, ni))) {
+        drop_device_mesh(c);
+        return rc;
+      }
+      hipError_t e = hipMemcpyAsync(c->mesh_xyz_dev.ptr, mx, c->mesh_xyz.size() * 4, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(c->mesh_idx_dev.ptr, mi, c->mesh_idx.size() * 4, hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) {
+        drop_device_mesh(c);
+        return fail(RTPT_E_DEVICE, std::string("mesh copy: ") + hipGetErrorString(e));
+      }
+      bytes += c->mesh_xyz.size() * 4 + c->mesh_idx.size() * 4;
+    }
+    if ((rc = stage_transforms(c, xf, static_cast<size_t>(ni) * 48))) return rc;
+    bytes += static_cast<uint64_t>(ni) * 48;
+    rt::launch_flatten(flatten_args(c, nt, total, true), c->stream);
+  } else {
+    bytes = static_cast<uint64_t>(total) * 36;  // the posed triangles, copied by the host path below
+  }
+  if (small || !on_device) c->obj_tris.swap(obj);
+  if (!on_device && c->obj_tris_dev.ptr) {
+    // the device's un-posed triangles follow too: rtpt_scene_rebuild can move this scene onto the device-refit path later
+    // (c->obj_tris outlives the copy; the host path below synchronises anyway)
+    const hipError_t e = hipMemcpyAsync(c->obj_tris_dev.ptr, c->obj_tris.data(), static_cast<size_t>(total) * 36, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+      c->obj_tris.swap(obj);
+      return fail(RTPT_E_DEVICE, std::string("un-posed triangle copy: ") + hipGetErrorString(e));
+    }
+    bytes += static_cast<uint64_t>(total) * 36;
+  }
+  const bool paired_before = c->tris_paired;
+  c->tris_paired = paired;
+  const int rc = repose_scene(c, c->model);
+  if (rc) {
+    if (!on_device) {  // nothing reached the device: the scene is the one before the call
+      c->obj_tris.swap(obj);
+      c->tris_paired = paired_before;
+    }
+    return rc;
+  }
+  c->has_xf = true;
+  c->upload_info[0] = bytes;
+  c->upload_info[1] = on_device ? 1 : 0;
+  c->upload_info[2] = 0;  // the pair decision is the upload's: topology is kept
+  if (on_device) c->upload_info[3]++;
+  return RTPT_OK;
+}
 
 int rtpt_scene_build_info(rtpt_ctx* c, struct rtpt_scene_build_info* out) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");

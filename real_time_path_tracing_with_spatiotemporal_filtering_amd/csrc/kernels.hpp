@@ -264,6 +264,18 @@ struct RefitArgs {
 void launch_pose(uint32_t n_verts, const float* src, float* dst, const RefitModel& m, hipStream_t s);
 // level_first[h] .. level_first[h + 1]: the slice of `order` holding the nodes of height h (n_levels + 1 entries)
 void launch_refit(const RefitArgs& a, const uint32_t* level_first, int n_levels, uint32_t n_nodes, float pad_rel, hipStream_t s);
+// device-side flatten + fan-pair test (scene_flatten.hip): mesh x instance transforms -> the un-posed triangles
+struct FlattenArgs {
+  uint32_t n_tris;       // triangles of the mesh
+  uint32_t n_out_verts;  // 3 x n_tris x instances
+  const float* xyz;      // mesh vertices
+  const uint32_t* idx;   // 3 x n_tris vertex indices, each below the vertex count
+  const float* xf;       // instances x 12 floats (3x4 row-major), or NULL: one identity instance, the vertices are copied
+  float* out;            // n_out_verts x 3 floats, triangle id = instance * n_tris + t
+};
+void launch_flatten(const FlattenArgs& a, hipStream_t s);
+// *all_paired (preset to 1 by the caller) is cleared when some (2q, 2q + 1), q < n_pairs, is not a fan pair bit for bit
+void launch_fan_pairs(uint32_t n_pairs, const float* tris, uint32_t* all_paired, hipStream_t s);
 // device-side LBVH build (bvh_build.hip): the topology only — launch_refit + launch_scene_prepare fill boxes, grid and records
 constexpr uint32_t kLbvhMaxLevels = 128;                  // heights the histogram distinguishes (63 + 32 key bits: at most 95)
 constexpr uint32_t kLbvhHeaderWords = 2 + kLbvhMaxLevels;  // [0] depth, [1] nodes, [2 + h] nodes of height h: ONE readback
