@@ -22,6 +22,27 @@ void reuse_invalidate(rtpt_ctx* c, const Buf* b) {
 }
 }  // namespace rtpt_impl
 
+namespace rtpt_impl {
+// k_lut (+ k_pair_weights): the LUT of the current frame and the per-id tables (normals, self weights, areas, id-pair
+// weights) of the posed scene.  The device triangles are already posed, so the kernel's own model is the identity.
+// rtpt_gbuffer calls this when the pose changed; rtpt_temporal_filter when it arrives first (it reads the tables).
+void build_tables(rtpt_ctx* c) {
+  Timer tm(c, RTPT_K_LUT);
+  rt::LutArgs la;
+  la.n_tris = c->n_tris;
+  la.shade = static_cast<const float4*>(c->shade.ptr);
+  for (int i = 0; i < 16; i++) la.model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  la.lut = static_cast<float4*>(c->lut[c->lut_cur].ptr);
+  la.normal_tab = static_cast<float4*>(c->normal_tab.ptr);
+  la.area_tab = la.normal_tab + (c->n_tris + 1);
+  la.pair_tab = static_cast<float*>(c->pair_tab.ptr);
+  la.sigma_n = c->cfg.sigma_n;
+  rt::launch_lut(la, c->stream);
+  c->lut_version[c->lut_cur] = c->model_version;
+  c->tables_valid = true;
+}
+}  // namespace rtpt_impl
+
 namespace {
 
 // the key of the K0 call `a` was built for (api_internal.hpp: K0Key)
@@ -102,23 +123,8 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   }
   // The LUT is a function of the posed scene: the geometry stage's per-frame rewrite (visibility.geom.glsl:57-59)
   // produces the same bytes every frame while the model rests, so only a buffer that does not hold the current
-  // pose yet is rebuilt (after rtpt_scene_upload / a model change / rtpt_set_plane).  The device triangles are
-  // already posed, so the kernel's own model is the identity.
-  if (c->lut_version[c->lut_cur] != c->model_version || !c->tables_valid) {
-    Timer tm(c, RTPT_K_LUT);
-    rt::LutArgs la;
-    la.n_tris = c->n_tris;
-    la.shade = static_cast<const float4*>(c->shade.ptr);
-    for (int i = 0; i < 16; i++) la.model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    la.lut = static_cast<float4*>(c->lut[c->lut_cur].ptr);
-    la.normal_tab = static_cast<float4*>(c->normal_tab.ptr);
-    la.area_tab = la.normal_tab + (c->n_tris + 1);
-    la.pair_tab = static_cast<float*>(c->pair_tab.ptr);
-    la.sigma_n = c->cfg.sigma_n;
-    rt::launch_lut(la, c->stream);
-    c->lut_version[c->lut_cur] = c->model_version;
-    c->tables_valid = true;
-  }
+  // pose yet is rebuilt (after rtpt_scene_upload / a model change / rtpt_set_plane).
+  if (c->lut_version[c->lut_cur] != c->model_version || !c->tables_valid) build_tables(c);
   if ((rc = launch_check("lut"))) return rc;
   if (!c->lut_prev_valid) {
     // D3: visibilityLUTprevious is read during frame 0 before anything wrote it; define it as LUT
@@ -663,6 +669,21 @@ int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_
   if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = filter_validate(c, pc, ubo, y0, y1);
   if (rc) return rc;
+  if (!c->tables_valid) {
+    // no rtpt_gbuffer since the scene was uploaded or posed: the normal / id-pair tables the kernels gather from are
+    // not those of the current pose yet
+    FLUSH_FILTER(c);
+    HIP_TRY(hipSetDevice(c->device));
+    build_tables(c);
+    if ((rc = launch_check("lut"))) return rc;
+    if (!c->lut_prev_valid) {
+      // D3, as in rtpt_gbuffer: a LUTprevious nothing wrote yet is defined as LUT (the final pass reprojects through it)
+      HIP_TRY(hipMemcpyAsync(c->lut[c->lut_cur ^ 1].ptr, c->lut[c->lut_cur].ptr, c->lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
+                             c->stream));
+      c->lut_prev_valid = true;
+      c->lut_version[c->lut_cur ^ 1] = c->model_version;
+    }
+  }
   FilterCall f;
   f.pc = *pc;
   f.has_ubo = ubo != nullptr;

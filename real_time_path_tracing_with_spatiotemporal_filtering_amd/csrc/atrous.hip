@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
       if (i == 1 && j == 1) {
         // centre tap: q == p, so both exponentials are exactly 1 and w = pow(max(0,dot(np,np)),sigma_n)
         cq = cp;
-        w = np4.w;
+        w = centre_weight(np4.w, cp, dp);
       } else {
         const size_t rowq = static_cast<size_t>(qys[j] - a.g.row_base) * W;
         const int qx = qxs[i];
@@ -489,7 +489,7 @@ void k_atrous_comb_sh(AtrousArgs a) {
         f3 cq;
         if (!EXTA && i == 0 && jj == 0) {
           cq = cp;
-          w = wself;  // centre tap: q == p, both exponentials are exactly 1
+          w = centre_weight(wself, cp, dp);  // centre tap: q == p, both exponentials are exactly 1
         } else {
           const int qi = cc + jj * CWp + i * k;
           const float4 cq4 = col[qi];

@@ -241,7 +241,7 @@ __global__ __launch_bounds__(128 * L * G) void k_atrous_chain(AtrousArgs a, Chai
             f3 cq;
             if (i == 0 && jj == 0) {
               cq = cp;
-              w = prow[idp];  // centre tap: q == p, both exponentials are exactly 1
+              w = centre_weight(prow[idp], cp, dp);  // centre tap: q == p, both exponentials are exactly 1
             } else {
               const int qi = rowb[jj + 1] + (i + 1) * st;
               const float4 cq4 = scol[qi];

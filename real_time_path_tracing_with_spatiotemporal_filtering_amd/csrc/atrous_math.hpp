@@ -68,6 +68,14 @@ __device__ __forceinline__ float edge_weight(EdgeStop s, float wn, f3 cp, f3 cq,
   return wn * __builtin_amdgcn_exp2f(e);
 }
 
+// The centre tap (q == p) of the plain 3x3 filter: cp - cp and dp - dp are 0, both exponentials exactly 1 and the weight is the
+// id's self weight — while colour and depth are finite.  A channel or a depth that is Inf or NaN makes Inf - Inf = NaN in the
+// reference's own arithmetic (:67-77, the loop treats the centre like any tap), and the NaN weight turns the whole pixel NaN.
+// x * 0 is +-0 for a finite x and NaN otherwise, so the sum below leaves wself (>= +0) bit for bit or makes it NaN.
+__device__ __forceinline__ float centre_weight(float wself, f3 cp, float dp) {
+  return wself + fmaf_(cp.x, 0.0f, fmaf_(cp.y, 0.0f, fmaf_(cp.z, 0.0f, dp * 0.0f)));
+}
+
 // :146-147, one tap into the sums; hw = h * w with the tap's own h (:145: 1/9, or gauss5 / 273).  The extension family
 // calls this form.
 __device__ __forceinline__ void tap_add_h(f3& num, float& den, float hw, f3 cq) {

@@ -55,7 +55,7 @@ __device__ __forceinline__ f3 sw_filter(EdgeStop es, const float* pairw, int NP,
   tap(B.l);
   tap(C.l);
   tap(A.m);
-  tap_add<EXACT>(num, den, prow[idp], cp);  // centre tap: q == p, both exponentials are exactly 1
+  tap_add<EXACT>(num, den, centre_weight(prow[idp], cp, dp), cp);  // centre tap: q == p, both exponentials are exactly 1
   tap(C.m);
   tap(A.r);
   tap(B.r);
