@@ -271,6 +271,7 @@ bool is_identity(const float* m);
 int launch_check(const char* what);
 int apply_model(rtpt_ctx* c, const float* model);  // api_scene.hip
 void build_tables(rtpt_ctx* c);                      // api_passes.hip: k_lut + k_pair_weights for the posed scene
+int ensure_tables(rtpt_ctx* c);                      // api_passes.hip: build_tables + the D3 LUTprevious, when the tables are stale
 bool refits_on_device(const rtpt_ctx* c);         // api_scene.hip: a changed pose stays on the device and on the stream
 
 // HIP events around a launch on the launch stream, every rtpt_timing_enable(period)-th frame (rtpt_timing_collect)

@@ -41,6 +41,27 @@ void build_tables(rtpt_ctx* c) {
   c->lut_version[c->lut_cur] = c->model_version;
   c->tables_valid = true;
 }
+
+// A pass that reads the per-id tables (normals, areas, id-pair weights) without rtpt_gbuffer in front of it — rtpt_temporal_filter
+// or the stand-alone rtpt_temporal_gradient as the first pass after rtpt_scene_upload or rtpt_scene_set_instances (a changed
+// ubo.model arrives only with rtpt_gbuffer, which rebuilds them in the same call) — builds them here, with the LUT of the
+// current pose; a LUTprevious nothing wrote yet is defined as that LUT (D3, as in rtpt_gbuffer: K1 and the final filter pass
+// read it)
+int ensure_tables(rtpt_ctx* c) {
+  if (c->tables_valid) return RTPT_OK;
+  FLUSH_FILTER(c);
+  HIP_TRY(hipSetDevice(c->device));
+  build_tables(c);
+  int rc = launch_check("lut");
+  if (rc) return rc;
+  if (!c->lut_prev_valid) {
+    HIP_TRY(hipMemcpyAsync(c->lut[c->lut_cur ^ 1].ptr, c->lut[c->lut_cur].ptr, c->lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
+                           c->stream));
+    c->lut_prev_valid = true;
+    c->lut_version[c->lut_cur ^ 1] = c->model_version;
+  }
+  return RTPT_OK;
+}
 }  // namespace rtpt_impl
 
 namespace {
@@ -283,6 +304,7 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
     return gbuffer_flush(c);
   }
   FLUSH_FILTER(c);
+  if ((rc = ensure_tables(c))) return rc;  // K1 first after an upload or moved instances: the tables and LUTs it reads
   rt::GradientArgs a;
   a.g = geom(c, y0, y1);
   for (int i = 0; i < 3; i++) {
@@ -669,21 +691,7 @@ int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_
   if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = filter_validate(c, pc, ubo, y0, y1);
   if (rc) return rc;
-  if (!c->tables_valid) {
-    // no rtpt_gbuffer since the scene was uploaded or posed: the normal / id-pair tables the kernels gather from are
-    // not those of the current pose yet
-    FLUSH_FILTER(c);
-    HIP_TRY(hipSetDevice(c->device));
-    build_tables(c);
-    if ((rc = launch_check("lut"))) return rc;
-    if (!c->lut_prev_valid) {
-      // D3, as in rtpt_gbuffer: a LUTprevious nothing wrote yet is defined as LUT (the final pass reprojects through it)
-      HIP_TRY(hipMemcpyAsync(c->lut[c->lut_cur ^ 1].ptr, c->lut[c->lut_cur].ptr, c->lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
-                             c->stream));
-      c->lut_prev_valid = true;
-      c->lut_version[c->lut_cur ^ 1] = c->model_version;
-    }
-  }
+  if ((rc = ensure_tables(c))) return rc;
   FilterCall f;
   f.pc = *pc;
   f.has_ubo = ubo != nullptr;

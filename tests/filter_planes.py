@@ -356,3 +356,18 @@ def atrous_once_numpy(dtype, img, depth, ids, normals, stride, sigma_n=128, sigm
             num += hw[..., None] * cq
             den += hw
     return num / den[..., None]
+
+
+# ------------------------------------------------------------------------------------------ comparison
+def same_bits(got, want, tag):
+    """NaN positions equal, every other value equal as bits; no pixel left out"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, tag
+    if got.dtype.kind != "f":
+        assert np.array_equal(got, want), (tag, np.argwhere(got != want)[:4].tolist())
+        return
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), (tag, "NaN positions", int(gn.sum()), int(wn.sum()), np.argwhere(gn != wn)[:4].tolist())
+    g, w = np.where(gn, np.float32(0), got).view(np.uint32), np.where(wn, np.float32(0), want).view(np.uint32)
+    bad = np.argwhere(g != w)
+    assert not len(bad), (tag, len(bad), bad[:4].tolist(), [(float(got[tuple(i)]), float(want[tuple(i)])) for i in bad[:4]])

@@ -27,7 +27,7 @@ import numpy as np
 import pytest
 
 import filter_planes as FP
-from conftest import bits
+from filter_planes import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -193,20 +193,6 @@ def gpu_run(abi, p, flags, N, frame, *, gbuffer=True, inject_ids=True, timing=Fa
         return out
     finally:
         ctx.close()
-
-
-def same_bits(got, want, tag):
-    """NaN positions equal, every other value equal as bits; no pixel left out"""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, tag
-    if got.dtype.kind != "f":
-        assert np.array_equal(got, want), (tag, np.argwhere(got != want)[:4].tolist())
-        return
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), (tag, "NaN positions", int(gn.sum()), int(wn.sum()), np.argwhere(gn != wn)[:4].tolist())
-    g, w = bits(np.where(gn, np.float32(0), got)), bits(np.where(wn, np.float32(0), want))
-    bad = np.argwhere(g != w)
-    assert not len(bad), (tag, len(bad), bad[:4].tolist(), [(float(got[tuple(i)]), float(want[tuple(i)])) for i in bad[:4]])
 
 
 def compare_exact(got, ref, tag, N, ext=0):
