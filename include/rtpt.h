@@ -356,6 +356,12 @@ int rtpt_scene_set_instances(rtpt_ctx* ctx, const float* instance_xforms, uint32
  * was taken on the device, [3] rtpt_scene_set_instances calls served without a host synchronisation since rtpt_create. */
 int rtpt_debug_upload_info(rtpt_ctx* ctx, uint64_t out[4]);
 
+/* Device memory the library holds right now, in bytes, over all contexts of the process: every buffer a context owns
+ * (planes, scene, tree, tables, builder scratch, traversal spill area), counted where it is allocated and where it is
+ * freed.  Not counted: pinned host staging, events and streams, and planes bound with rtpt_bind_plane (the caller's).
+ * After rtpt_destroy of every context it is 0; a test compares readings instead of the device-wide hipMemGetInfo. */
+int rtpt_debug_live_device_bytes(uint64_t* out);
+
 /* Frame reuse.  K0 and K1 (rtpt_gbuffer, rtpt_temporal_gradient) read the camera, the light, the posed scene and the LUTs
  * and nothing that changes from frame to frame by itself: no frame number, no random stream.  While all of those rest,
  * both passes would store the bytes their planes already hold, so the context launches neither and rtpt_raytrace runs

@@ -112,6 +112,7 @@ SYMBOLS = [
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
+    "rtpt_debug_live_device_bytes",
 ]
 
 _lib = None
@@ -176,6 +177,7 @@ def load() -> C.CDLL:
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_scene_set_instances": [vp, vp, u32],
         "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
+        "rtpt_debug_live_device_bytes": [C.POINTER(C.c_uint64)],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
     }
     for name, args in sigs.items():
@@ -198,6 +200,13 @@ def _check(rc: int) -> None:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def live_device_bytes() -> int:
+    """device memory the library's contexts own right now (rtpt_debug_live_device_bytes)"""
+    out = C.c_uint64()
+    _check(load().rtpt_debug_live_device_bytes(C.byref(out)))
+    return out.value
 
 
 def config_default(width: int, height: int) -> Config:

@@ -2,6 +2,8 @@
 // helpers shared by the other api_*.hip units (api_internal.hpp).
 #include "api_internal.hpp"
 
+#include <atomic>
+
 namespace rtpt_impl {
 
 thread_local std::string g_err;
@@ -21,8 +23,8 @@ size_t frame_blocks(const rtpt_ctx* c) {
 // the spill area of the BVH traversal stack holds (stack depth - LDS entries) x workgroups x 256 entries: grown (never
 // shrunk) before a launch whose grid is larger than any before it
 int ensure_stack_spill(rtpt_ctx* c, size_t blocks) {
-  if (!c->use_bvh) return RTPT_OK;
-  const size_t depth = static_cast<size_t>(c->bvh_depth + 2 < 8 ? 8 : c->bvh_depth + 2);
+  if (!c->scene.use_bvh) return RTPT_OK;
+  const size_t depth = static_cast<size_t>(c->scene.tree.bvh_depth + 2 < 8 ? 8 : c->scene.tree.bvh_depth + 2);
   const size_t lds = std::min<size_t>(depth, static_cast<size_t>(c->bvh_stack_lds));
   if (depth <= lds || blocks <= c->stack_spill_blocks) return RTPT_OK;
   if (c->stack_spill.ptr) {
@@ -37,9 +39,12 @@ int ensure_stack_spill(rtpt_ctx* c, size_t blocks) {
   return RTPT_OK;
 }
 
+// bytes held by owned Bufs, process-wide (rtpt_debug_live_device_bytes): updated here and in Buf::release, the two places
+// that allocate and free device memory
+static std::atomic<uint64_t> g_live_device_bytes{0};
+
 int alloc_buf(Buf& b, size_t bytes) {
-  if (b.owned && b.ptr) (void)hipFree(b.ptr);
-  b = Buf{};
+  b.release();
   if (bytes == 0) return RTPT_OK;
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, bytes);
@@ -47,13 +52,19 @@ int alloc_buf(Buf& b, size_t bytes) {
   b.ptr = p;
   b.bytes = bytes;
   b.owned = true;
+  g_live_device_bytes += bytes;
   return RTPT_OK;
 }
 
-void free_buf(Buf& b) {
-  if (b.owned && b.ptr) (void)hipFree(b.ptr);
-  b = Buf{};
+void Buf::release() {
+  if (owned && ptr) {
+    (void)hipFree(ptr);
+    g_live_device_bytes -= bytes;
+  }
+  ptr = nullptr, bytes = 0, owned = false;
 }
+
+void free_buf(Buf& b) { b.release(); }
 
 Buf* plane_buf(rtpt_ctx* c, rtpt_plane which) {
   switch (which) {
@@ -65,8 +76,8 @@ Buf* plane_buf(rtpt_ctx* c, rtpt_plane which) {
     case RTPT_PLANE_DEPTH: return &c->depth;
     case RTPT_PLANE_VIS_ID: return &c->vis[c->vis_cur];
     case RTPT_PLANE_PREV_VIS_ID: return &c->vis[c->vis_cur ^ 1];
-    case RTPT_PLANE_LUT: return &c->lut[c->lut_cur];
-    case RTPT_PLANE_LUT_PREV: return &c->lut[c->lut_cur ^ 1];
+    case RTPT_PLANE_LUT: return &c->scene.lut[c->lut_cur];
+    case RTPT_PLANE_LUT_PREV: return &c->scene.lut[c->lut_cur ^ 1];
     case RTPT_PLANE_PREV_PIXEL: return &c->prev_pixel;
     case RTPT_PLANE_RAYCOUNT: return &c->raycount;
     case RTPT_PLANE_HIT_ID: return &c->hit_id;
@@ -94,7 +105,7 @@ size_t plane_size(const rtpt_ctx* c, rtpt_plane which) {
     case RTPT_PLANE_MOMENTS_PREV: return px * 16;
     case RTPT_PLANE_PREV_PIXEL: return px * 8;
     case RTPT_PLANE_LUT:
-    case RTPT_PLANE_LUT_PREV: return (static_cast<size_t>(c->n_tris) + 1) * sizeof(rtpt_visibility_data);
+    case RTPT_PLANE_LUT_PREV: return (static_cast<size_t>(c->scene.n_tris) + 1) * sizeof(rtpt_visibility_data);
     case RTPT_PLANE_RAYCOUNT: return 8;
     default: return 0;
   }
@@ -124,21 +135,21 @@ rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1) {
 
 rt::SceneView scene_view(const rtpt_ctx* c) {
   rt::SceneView s;
-  s.isect_id = static_cast<const float4*>(c->isect_id.ptr);
-  s.isect_leaf = static_cast<const float4*>(c->isect_leaf.ptr);
-  s.leaf_ids = static_cast<const uint32_t*>(c->leaf_order.ptr);
-  s.shade = static_cast<const float4*>(c->shade.ptr);
-  s.nodes = static_cast<const rt::BvhNodeQ*>(c->nodes.ptr);
-  s.bvh_grid = static_cast<const float*>(c->bvh_grid_dev.ptr);
-  s.n_tris = c->n_tris;
-  s.use_bvh = c->use_bvh ? 1u : 0u;
-  s.paired = (c->tris_paired && !c->no_pairing) ? 1u : 0u;
-  s.leaf_pairs = c->leaf_pairs ? 1u : 0u;
-  s.stack_depth = static_cast<uint32_t>(c->bvh_depth + 2 < 8 ? 8 : c->bvh_depth + 2);
+  s.isect_id = static_cast<const float4*>(c->scene.isect_id.ptr);
+  s.isect_leaf = static_cast<const float4*>(c->scene.isect_leaf.ptr);
+  s.leaf_ids = static_cast<const uint32_t*>(c->scene.tree.leaf_order.ptr);
+  s.shade = static_cast<const float4*>(c->scene.shade.ptr);
+  s.nodes = static_cast<const rt::BvhNodeQ*>(c->scene.tree.nodes.ptr);
+  s.bvh_grid = static_cast<const float*>(c->scene.bvh_grid_dev.ptr);
+  s.n_tris = c->scene.n_tris;
+  s.use_bvh = c->scene.use_bvh ? 1u : 0u;
+  s.paired = (c->scene.tris_paired && !c->no_pairing) ? 1u : 0u;
+  s.leaf_pairs = c->scene.tree.leaf_pairs ? 1u : 0u;
+  s.stack_depth = static_cast<uint32_t>(c->scene.tree.bvh_depth + 2 < 8 ? 8 : c->scene.tree.bvh_depth + 2);
   s.stack_lds = std::min<uint32_t>(s.stack_depth, static_cast<uint32_t>(c->bvh_stack_lds));
   s.stack_spill = static_cast<uint32_t*>(c->stack_spill.ptr);
-  s.materials = static_cast<const float4*>(c->materials.ptr);
-  s.n_base_tris = c->n_base_tris ? c->n_base_tris : 1u;
+  s.materials = static_cast<const float4*>(c->scene.materials.ptr);
+  s.n_base_tris = c->scene.n_base_tris ? c->scene.n_base_tris : 1u;
   return s;
 }
 
@@ -150,13 +161,13 @@ rt::SceneView scene_view(const rtpt_ctx* c) {
 // makes the projection unbounded: such a triangle is never culled.
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3],
                    double p00, double p11, double jitter_px, rt::TriBounds* out) {
-  if (c->host_tris.empty() || c->n_tris > static_cast<uint32_t>(rt::kCullMaxTris)) return false;
+  if (c->scene.host_tris.empty() || c->scene.n_tris > static_cast<uint32_t>(rt::kCullMaxTris)) return false;
   const double W = c->cfg.width, H = c->cfg.height;
-  for (uint32_t t = 0; t < c->n_tris; t++) {
+  for (uint32_t t = 0; t < c->scene.n_tris; t++) {
     double xmin = 1e30, xmax = -1e30, ymin = 1e30, ymax = -1e30;
     bool unbounded = false;
     for (int k = 0; k < 3; k++) {
-      const float* P = c->host_tris.data() + 9 * static_cast<size_t>(t) + 3 * k;
+      const float* P = c->scene.host_tris.data() + 9 * static_cast<size_t>(t) + 3 * k;
       const double r[3] = {P[0] - org[0], P[1] - org[1], P[2] - org[2]};
       const double xv = c0[0] * r[0] + c0[1] * r[1] + c0[2] * r[2];
       const double yv = c1[0] * r[0] + c1[1] * r[1] + c1[2] * r[2];
@@ -384,27 +395,12 @@ int rtpt_destroy(rtpt_ctx* c) {
   if (c->handoff_event) (void)hipEventDestroy(c->handoff_event);
   for (hipEvent_t e : c->build_ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto& b : c->color) free_buf(b);
-  for (auto& b : c->vis) free_buf(b);
-  free_buf(c->normals);
-  free_buf(c->path_queue_count);
-  free_buf(c->path_pool);
-  for (auto& b : c->path_queue) free_buf(b);
-  for (auto& b : c->moments) free_buf(b);
-  for (auto& b : c->variance) free_buf(b);
-  free_buf(c->var_scale);
-  for (auto& b : c->lut) free_buf(b);
-  for (Buf* b : {&c->worldpos, &c->gradient, &c->depth, &c->prev_pixel, &c->hit_id, &c->raycount, &c->normal_tab, &c->pair_tab, &c->tris,
-                 &c->leaf_order, &c->isect_id, &c->isect_leaf, &c->shade, &c->nodes, &c->materials, &c->obj_tris_dev, &c->refit_order,
-                 &c->refit_fbox, &c->bvh_grid_dev, &c->ray_tab, &c->bvh_build_scratch, &c->bvh_build_header, &c->mesh_xyz_dev,
-                 &c->mesh_idx_dev, &c->xf_dev, &c->pair_word})
-    free_buf(*b);
   for (auto& st : c->xf_stage) {
     if (st.done) (void)hipEventDestroy(st.done);
     if (st.host) (void)hipHostFree(st.host);
   }
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // every device buffer: the context and its scene own them through Buf members
   return RTPT_OK;
 }
 
@@ -552,6 +548,12 @@ int rtpt_debug_reuse_info(rtpt_ctx* c, uint64_t out[4]) {
   return RTPT_OK;
 }
 
+int rtpt_debug_live_device_bytes(uint64_t* out) {
+  if (!out) return fail(RTPT_E_INVALID, "NULL argument");
+  *out = g_live_device_bytes.load();
+  return RTPT_OK;
+}
+
 int rtpt_debug_upload_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 4; i++) out[i] = c->upload_info[i];
@@ -619,10 +621,10 @@ int rtpt_set_plane(rtpt_ctx* c, rtpt_plane which, const void* src, size_t bytes)
     c->guides_y1 = static_cast<int>(c->cfg.row_end);
   }
   if (which == RTPT_PLANE_LUT_PREV) {
-    c->lut_prev_valid = true;
-    c->lut_version[c->lut_cur ^ 1] = ~0ull;  // injected content: rebuild when it becomes current
+    c->scene.lut_prev_valid = true;
+    c->scene.lut_version[c->lut_cur ^ 1] = ~0ull;  // injected content: rebuild when it becomes current
   }
-  if (which == RTPT_PLANE_LUT) c->lut_version[c->lut_cur] = ~0ull;
+  if (which == RTPT_PLANE_LUT) c->scene.lut_version[c->lut_cur] = ~0ull;
   if (which == RTPT_PLANE_VIS_ID) c->normals_y0 = c->normals_y1 = 0;  // the normal plane no longer matches the ids
   return RTPT_OK;
 }

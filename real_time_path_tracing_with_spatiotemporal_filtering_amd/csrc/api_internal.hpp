@@ -32,10 +32,25 @@ int fail(int code, const std::string& msg);
       return fail(RTPT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
   } while (0)
 
+// A device buffer.  Move-only: an owned allocation (alloc_buf) is released by release(), by the destructor and when another
+// Buf is moved in; a borrowed pointer (rtpt_bind_plane, owned == false) is never freed.  Every release must run with the
+// context's device current: the entry points set it before anything that holds a Buf is replaced or destroyed.
 struct Buf {
   void* ptr = nullptr;
   size_t bytes = 0;
   bool owned = false;
+  Buf() = default;
+  Buf(Buf&& o) noexcept : ptr(o.ptr), bytes(o.bytes), owned(o.owned) { o.ptr = nullptr, o.bytes = 0, o.owned = false; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      release();
+      ptr = o.ptr, bytes = o.bytes, owned = o.owned;
+      o.ptr = nullptr, o.bytes = 0, o.owned = false;
+    }
+    return *this;
+  }
+  ~Buf() { release(); }
+  void release();  // api_context.hip: hipFree of an owned allocation (counted, rtpt_debug_live_device_bytes); leaves *this empty
 };
 
 enum ColorRole { ROLE_IMAGE = 0, ROLE_FILTERED = 1, ROLE_PREVIOUS = 2 };
@@ -81,6 +96,55 @@ struct PlaneTag {  // what a plane the context owns holds: the output of the pas
   bool holds(const K& k) const { return valid && std::memcmp(&key, &k, sizeof k) == 0; }
 };
 
+// The acceleration structure over Scene::tris.  One value: rtpt_scene_rebuild swaps a whole Tree in (api_scene.hip).
+struct Tree {
+  Buf nodes, leaf_order;
+  // device-side refit (refit.hip): nodes sorted by height, scratch boxes, the slice of the order per height (levels + 1)
+  Buf refit_order, refit_fbox;
+  std::vector<uint32_t> refit_level_first;
+  uint32_t n_nodes = 0;
+  int bvh_depth = 0;
+  bool leaf_pairs = false;   // built over fan pairs (bvh.hpp build_bvh(pairs)): every leaf is one pair (2q, 2q + 1)
+  bool device_tree = false;  // built on the device: bvh_host is empty, every refit runs on the device
+  rt::Bvh bvh_host;          // a host-built tree's topology, for the host refit
+  rt::BvhGrid bvh_grid{};    // of the host-built / host-refit node boxes (bvh_grid_dev is what the traversal reads)
+};
+
+// Everything that belongs to the uploaded scene.  rtpt_scene_upload assembles a new one and moves it into the context when
+// it is complete; n_tris == 0 is "no scene" (RTPT_E_NO_SCENE).
+struct Scene {
+  uint32_t n_tris = 0;       // flattened: n_instances * n_base_tris
+  uint32_t n_base_tris = 0;
+  uint32_t n_instances = 0;  // of the upload; 1 with has_xf false: uploaded without transforms
+  bool has_xf = false;
+  Buf tris, isect_id, isect_leaf, shade;  // posed triangles and the records made from them (scene_prepare)
+  Buf obj_tris_dev;                       // the un-posed triangles (instance transforms applied, model not)
+  Buf bvh_grid_dev;                       // the grid of the node boxes, as the traversal reads it (a refit rewrites it)
+  Tree tree;
+  // instances (scene_flatten.hip): the mesh and its instance transforms, resident on the device for RTPT_FLAG_DEVICE_FLATTEN
+  // uploads and from the first rtpt_scene_set_instances on (12 n_verts + 12 n_tris + 48 n_instances bytes); the host keeps
+  // the mesh too (the host path re-flattens from it)
+  struct DeviceMesh {
+    Buf xyz, idx, xf;
+  } mesh_dev;
+  std::vector<float> mesh_xyz;
+  std::vector<uint32_t> mesh_idx;
+  bool use_bvh = false;
+  bool tris_paired = false;  // every (2q, 2q+1) is a fan pair: same v0, v2_A == v1_B bitwise (kernels.hip tri_pair_test)
+  std::vector<float> host_tris;  // flattened world-space triangles, kept for small scenes (screen bounds)
+  // animated model matrix (main.cpp:1469 recomputes ubo.model every frame; it is the identity there): the scene as
+  // uploaded (object space), and the model it is posed with.  obj_tris is kept where the host reads it: scenes small
+  // enough for screen bounds and scenes re-posed on the host
+  std::vector<float> obj_tris;
+  float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  uint64_t model_version = 0;                // bumped whenever the posed geometry changes
+  Buf lut[2], normal_tab, pair_tab;          // rtpt_ctx::lut_cur says which LUT is the current one
+  uint64_t lut_version[2] = {~0ull, ~0ull};  // model_version each LUT buffer was built for
+  bool lut_prev_valid = false;               // D3
+  Buf materials;                             // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
+  struct rtpt_scene_build_info build_info {};
+  bool build_ms_pending = false;  // build_ms is still in rtpt_ctx::build_ev; read lazily by rtpt_scene_build_info
+};
 
 }  // namespace rtpt_impl
 using namespace rtpt_impl;
@@ -97,9 +161,8 @@ struct rtpt_ctx {
   bool alpha_depth[3] = {false, false, false};  // physical buffer carries depth in alpha ("rgbd")
   Buf vis[2];
   int vis_cur = 0;  // vis[vis_cur] = VIS_ID, the other PREV_VIS_ID
-  Buf lut[2];
-  int lut_cur = 0;
-  Buf worldpos, gradient, depth, prev_pixel, hit_id, raycount, normal_tab, pair_tab;
+  int lut_cur = 0;  // scene.lut[lut_cur] = LUT, the other LUT_PREV
+  Buf worldpos, gradient, depth, prev_pixel, hit_id, raycount;
   Buf moments[2], variance[2];  // RTPT_FLAG_EXT_VARIANCE
   Buf var_scale;                // RTPT_FLAG_EXT_SVGF_VARIANCE: the prefiltered variance of the iteration being launched
   Buf path_queue[2], path_queue_count;  // long paths: survivors handed from one k_pathtrace launch to the next
@@ -108,13 +171,6 @@ struct rtpt_ctx {
   uint64_t normals_frame = ~0ull;      // frame (frames_ended) those rows belong to
   int moments_cur = 0;          // moments[moments_cur] is written this frame, the other one is the history
   int variance_last = 0;        // variance[] buffer holding the newest values
-
-  // scene
-  uint32_t n_tris = 0;
-  Buf tris, leaf_order, isect_id, isect_leaf, shade, nodes;
-  // device-side re-pose + refit (refit.hip): the uploaded (un-posed) triangles, the nodes sorted by height, the scratch
-  // boxes and the grid the traversal reads.  BVH scenes only; small brute-force scenes keep host_tris for the screen bounds
-  Buf obj_tris_dev, refit_order, refit_fbox, bvh_grid_dev;
   // rtpt_present_target: the swapchain image rows the NEXT final pass also writes (fused blit); present_fused_* describe
   // what the last final pass actually wrote, so that rtpt_present can skip its own launch
   void* present_dst = nullptr;
@@ -124,17 +180,22 @@ struct rtpt_ctx {
   Buf ray_tab;  // K0: view-space ray direction per column / per row, for the projection and size below
   float ray_tab_p00 = 0.f, ray_tab_p11 = 0.f;
   uint32_t ray_tab_w = 0, ray_tab_h = 0;
-  std::vector<uint32_t> refit_level_first;  // slice of refit_order per height (levels + 1 entries)
-  // instances (scene_flatten.hip): the mesh and its instance transforms, resident on the device for RTPT_FLAG_DEVICE_FLATTEN
-  // uploads and from the first rtpt_scene_set_instances on (12 n_verts + 12 n_tris + 48 n_instances bytes); the host keeps
-  // the mesh too (the host path re-flattens from it).  xf_stage: pinned staging for the transforms of a call, two in turn,
-  // so that the copy needs no synchronisation and the caller's array may die at return
-  Buf mesh_xyz_dev, mesh_idx_dev, xf_dev, pair_word;
-  std::vector<float> mesh_xyz;
-  std::vector<uint32_t> mesh_idx;
-  uint32_t n_instances = 0;  // of the upload; 1 with has_xf false: uploaded without transforms
-  bool has_xf = false;
+
+  // The scene.  The context owns every device buffer through a Buf member, of itself or of the scene: `delete` frees
+  // them all.  What follows the scene here survives an upload: switches, the builder's work area, staging, counters.
+  Scene scene;
+  bool no_pairing = false;   // RTPT_NO_TRI_PAIRS=1: A/B switch
+  bool host_refit = false;   // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
+  // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
+  bool device_bvh = false;      // rtpt_scene_upload builds the tree on the device
+  bool device_bvh_sah = false;  // ... with the SAH builder (bvh_build_sah.hip): RTPT_FLAG_DEVICE_BVH_SAH too, or RTPT_DEVICE_BVH=sah
+  bool lbvh_by_height = false;  // RTPT_LBVH_ORDER=height: the device builder's other node numbering (A/B; same pixels)
   bool device_flatten = false;  // RTPT_FLAG_DEVICE_FLATTEN (with device_bvh)
+  Buf bvh_build_scratch, bvh_build_header;  // the builder's work area (grows, never shrinks) and its readback words
+  hipEvent_t build_ev[2] = {nullptr, nullptr};  // around a device build (Scene::build_ms_pending)
+  Buf pair_word;  // the device's fan-pair decision (scene_flatten.hip), read back by a device-flatten upload
+  // pinned staging for the transforms of a rtpt_scene_set_instances call, two in turn, so that the copy needs no
+  // synchronisation and the caller's array may die at return
   struct XfStage {
     void* host = nullptr;
     size_t bytes = 0;
@@ -143,37 +204,8 @@ struct rtpt_ctx {
   } xf_stage[2];
   int xf_stage_cur = 0;
   uint64_t upload_info[4] = {0, 0, 0, 0};  // rtpt_debug_upload_info
-  uint32_t n_nodes = 0;
-  bool host_refit = false;  // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
-  // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
-  bool device_bvh = false;   // rtpt_scene_upload builds the tree on the device
-  bool device_bvh_sah = false;  // ... with the SAH builder (bvh_build_sah.hip): RTPT_FLAG_DEVICE_BVH_SAH too, or RTPT_DEVICE_BVH=sah
-  bool lbvh_by_height = false;  // RTPT_LBVH_ORDER=height: the device builder's other node numbering (A/B; same pixels)
-  bool device_tree = false;  // the tree on the device now was built there: bvh_host is empty, every refit runs on the device
-  Buf bvh_build_scratch, bvh_build_header;  // the builder's work area (grows, never shrinks) and its readback words
-  struct rtpt_scene_build_info build_info {};
-  hipEvent_t build_ev[2] = {nullptr, nullptr};  // around a device build; read lazily by rtpt_scene_build_info
-  bool build_ms_pending = false;
-  bool use_bvh = false;
-  rt::BvhGrid bvh_grid{};
-  int bvh_depth = 0;
-  bool tris_paired = false;  // every (2q, 2q+1) is a fan pair: same v0, v2_A == v1_B bitwise (kernels.hip tri_pair_test)
-  bool leaf_pairs = false;   // ... and the BVH was built over those pairs (bvh.hpp build_bvh(pairs))
-  bool no_pairing = false;   // RTPT_NO_TRI_PAIRS=1: A/B switch
-  std::vector<float> host_tris;  // flattened world-space triangles, kept for small scenes (screen bounds)
-  // animated model matrix (main.cpp:1469 recomputes ubo.model every frame; it is the identity there): the scene as
-  // uploaded (object space = instance transforms applied, model not), its BVH topology, and the model it is posed with.
-  // obj_tris is kept where the host reads it: scenes small enough for screen bounds and scenes re-posed on the host
-  std::vector<float> obj_tris;
-  rt::Bvh bvh_host;
-  float model[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  uint64_t model_version = 0;          // bumped whenever the posed geometry changes
-  uint64_t lut_version[2] = {~0ull, ~0ull};  // model_version each LUT buffer was built for
-  Buf materials;                       // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
-  uint32_t n_base_tris = 0;
 
   // frame state
-  bool lut_prev_valid = false;   // D3
   bool tables_valid = false;     // normal / id-pair tables match the scene
   bool final_swapped = false;    // the final filter pass already rotated IMAGE <-> FILTERED this frame
   bool image_alias = false;      // between rtpt_end_frame and the next rtpt_raytrace IMAGE reads as PREVIOUS
@@ -272,7 +304,6 @@ int launch_check(const char* what);
 int apply_model(rtpt_ctx* c, const float* model);  // api_scene.hip
 void build_tables(rtpt_ctx* c);                      // api_passes.hip: k_lut + k_pair_weights for the posed scene
 int ensure_tables(rtpt_ctx* c);                      // api_passes.hip: build_tables + the D3 LUTprevious, when the tables are stale
-bool refits_on_device(const rtpt_ctx* c);         // api_scene.hip: a changed pose stays on the device and on the stream
 
 // HIP events around a launch on the launch stream, every rtpt_timing_enable(period)-th frame (rtpt_timing_collect)
 struct Timer {

@@ -18,7 +18,7 @@ void reuse_invalidate(rtpt_ctx* c, const Buf* b) {
   kill(c->tag_normals, &c->normals);
   kill(c->tag_gradient, &c->gradient);
   // K1 reads both LUT buffers, and their version does not see a write through a pointer handed out
-  if (b == &c->lut[0] || b == &c->lut[1]) kill(c->tag_gradient, b);
+  if (b == &c->scene.lut[0] || b == &c->scene.lut[1]) kill(c->tag_gradient, b);
 }
 }  // namespace rtpt_impl
 
@@ -29,16 +29,16 @@ namespace rtpt_impl {
 void build_tables(rtpt_ctx* c) {
   Timer tm(c, RTPT_K_LUT);
   rt::LutArgs la;
-  la.n_tris = c->n_tris;
-  la.shade = static_cast<const float4*>(c->shade.ptr);
+  la.n_tris = c->scene.n_tris;
+  la.shade = static_cast<const float4*>(c->scene.shade.ptr);
   for (int i = 0; i < 16; i++) la.model[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-  la.lut = static_cast<float4*>(c->lut[c->lut_cur].ptr);
-  la.normal_tab = static_cast<float4*>(c->normal_tab.ptr);
-  la.area_tab = la.normal_tab + (c->n_tris + 1);
-  la.pair_tab = static_cast<float*>(c->pair_tab.ptr);
+  la.lut = static_cast<float4*>(c->scene.lut[c->lut_cur].ptr);
+  la.normal_tab = static_cast<float4*>(c->scene.normal_tab.ptr);
+  la.area_tab = la.normal_tab + (c->scene.n_tris + 1);
+  la.pair_tab = static_cast<float*>(c->scene.pair_tab.ptr);
   la.sigma_n = c->cfg.sigma_n;
   rt::launch_lut(la, c->stream);
-  c->lut_version[c->lut_cur] = c->model_version;
+  c->scene.lut_version[c->lut_cur] = c->scene.model_version;
   c->tables_valid = true;
 }
 
@@ -54,11 +54,11 @@ int ensure_tables(rtpt_ctx* c) {
   build_tables(c);
   int rc = launch_check("lut");
   if (rc) return rc;
-  if (!c->lut_prev_valid) {
-    HIP_TRY(hipMemcpyAsync(c->lut[c->lut_cur ^ 1].ptr, c->lut[c->lut_cur].ptr, c->lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
+  if (!c->scene.lut_prev_valid) {
+    HIP_TRY(hipMemcpyAsync(c->scene.lut[c->lut_cur ^ 1].ptr, c->scene.lut[c->lut_cur].ptr, c->scene.lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
                            c->stream));
-    c->lut_prev_valid = true;
-    c->lut_version[c->lut_cur ^ 1] = c->model_version;
+    c->scene.lut_prev_valid = true;
+    c->scene.lut_version[c->lut_cur ^ 1] = c->scene.model_version;
   }
   return RTPT_OK;
 }
@@ -83,7 +83,7 @@ K0Key gbuffer_key(const rtpt_ctx* c, const rt::GbufferArgs& a) {
   k.y0 = a.g.y0;
   k.y1 = a.g.y1;
   k.normals_on = a.normals ? 1 : 0;
-  k.model_version = c->model_version;
+  k.model_version = c->scene.model_version;
   k.scene_gen = c->scene_gen;
   return k;
 }
@@ -125,7 +125,7 @@ extern "C" {
 // ------------------------------------------------------------------------------------------ K0
 int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   if (!c || !ubo) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
   FLUSH_FILTER(c);
@@ -138,21 +138,21 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
     if (!(det != 0.0f) || det != det) return fail(RTPT_E_INVALID, "ubo.model is singular");
   }
   HIP_TRY(hipSetDevice(c->device));
-  if (std::memcmp(ubo->model, c->model, sizeof c->model) != 0) {
+  if (std::memcmp(ubo->model, c->scene.model, sizeof c->scene.model) != 0) {
     int rcm = apply_model(c, ubo->model);
     if (rcm) return rcm;
   }
   // The LUT is a function of the posed scene: the geometry stage's per-frame rewrite (visibility.geom.glsl:57-59)
   // produces the same bytes every frame while the model rests, so only a buffer that does not hold the current
   // pose yet is rebuilt (after rtpt_scene_upload / a model change / rtpt_set_plane).
-  if (c->lut_version[c->lut_cur] != c->model_version || !c->tables_valid) build_tables(c);
+  if (c->scene.lut_version[c->lut_cur] != c->scene.model_version || !c->tables_valid) build_tables(c);
   if ((rc = launch_check("lut"))) return rc;
-  if (!c->lut_prev_valid) {
+  if (!c->scene.lut_prev_valid) {
     // D3: visibilityLUTprevious is read during frame 0 before anything wrote it; define it as LUT
-    HIP_TRY(hipMemcpyAsync(c->lut[c->lut_cur ^ 1].ptr, c->lut[c->lut_cur].ptr, c->lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
+    HIP_TRY(hipMemcpyAsync(c->scene.lut[c->lut_cur ^ 1].ptr, c->scene.lut[c->lut_cur].ptr, c->scene.lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
                            c->stream));
-    c->lut_prev_valid = true;
-    c->lut_version[c->lut_cur ^ 1] = c->model_version;
+    c->scene.lut_prev_valid = true;
+    c->scene.lut_version[c->lut_cur ^ 1] = c->scene.model_version;
   }
   rt::GbufferArgs a;
   a.g = geom(c, y0, y1);
@@ -191,15 +191,15 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
     // view-space axis i of a world vector r is dot(row i of R, r); the columns c0,c1,c2 of the view
     // matrix's rotation hold R^T's rows, i.e. x_view = (c0.x, c1.x, c2.x) . r
     const double rx[3] = {d0[0], d1[0], d2[0]}, ry[3] = {d0[1], d1[1], d2[1]}, rz[3] = {d0[2], d1[2], d2[2]};
-    a.cull = (!c->use_bvh && c->width_fits_i16() && screen_bounds(c, org, rx, ry, rz, a.p00, a.p11, 0.0, a.bounds)) ? 1 : 0;
+    a.cull = (!c->scene.use_bvh && c->width_fits_i16() && screen_bounds(c, org, rx, ry, rz, a.p00, a.p11, 0.0, a.bounds)) ? 1 : 0;
   }
   a.vis = static_cast<uint32_t*>(c->vis[c->vis_cur].ptr);
   a.worldpos = static_cast<float4*>(c->worldpos.ptr);
   a.depth = static_cast<float*>(c->depth.ptr);
   a.normals = nullptr;
-  a.normal_tab = static_cast<const float4*>(c->normal_tab.ptr);
-  a.area_tab = a.normal_tab + (c->n_tris + 1);
-  if (!c->pair_tab.ptr) {  // more than 63 triangles: the filter stages per-pixel normals instead of ids
+  a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
+  a.area_tab = a.normal_tab + (c->scene.n_tris + 1);
+  if (!c->scene.pair_tab.ptr) {  // more than 63 triangles: the filter stages per-pixel normals instead of ids
     if (!c->normals.ptr) {
       int rc2 = alloc_buf(c->normals, c->pixels() * 16);
       if (rc2) return rc2;
@@ -264,7 +264,7 @@ extern "C" {
 // ------------------------------------------------------------------------------------------ K1
 int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint32_t y1) {
   if (!c || !pc) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -281,8 +281,8 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
       g.g_color[i] = pc->currentCameraColor[i];
       g.g_color_prev[i] = pc->previousCameraColor[i];
     }
-    g.lut = static_cast<const float4*>(c->lut[c->lut_cur].ptr);
-    g.lut_prev = static_cast<const float4*>(c->lut[c->lut_cur ^ 1].ptr);
+    g.lut = static_cast<const float4*>(c->scene.lut[c->lut_cur].ptr);
+    g.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
     g.grad = static_cast<float4*>(c->gradient.ptr);
     {
       K1Key& k = c->pending_key;
@@ -293,8 +293,8 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
       std::memcpy(k.color_prev, g.g_color_prev, sizeof k.color_prev);
       k.y0 = g.grad_y0;
       k.y1 = g.grad_y1;
-      k.lut_version[0] = c->lut_version[c->lut_cur];
-      k.lut_version[1] = c->lut_version[c->lut_cur ^ 1];
+      k.lut_version[0] = c->scene.lut_version[c->lut_cur];
+      k.lut_version[1] = c->scene.lut_version[c->lut_cur ^ 1];
     }
     int rcq = filter_flush(c, false);
     if (rcq) return rcq;
@@ -316,10 +316,10 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
   }
   a.vis = static_cast<const uint32_t*>(c->vis[c->vis_cur].ptr);
   a.worldpos = static_cast<const float4*>(c->worldpos.ptr);
-  a.lut = static_cast<const float4*>(c->lut[c->lut_cur].ptr);
-  a.lut_prev = static_cast<const float4*>(c->lut[c->lut_cur ^ 1].ptr);
-  a.normal_tab = static_cast<const float4*>(c->normal_tab.ptr);
-  a.area_tab = a.normal_tab + (c->n_tris + 1);
+  a.lut = static_cast<const float4*>(c->scene.lut[c->lut_cur].ptr);
+  a.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
+  a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
+  a.area_tab = a.normal_tab + (c->scene.n_tris + 1);
   a.grad = static_cast<float4*>(c->gradient.ptr);
   reuse_invalidate(c, &c->gradient);  // launched unrecorded
   {
@@ -332,7 +332,7 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
 // ------------------------------------------------------------------------------------------ K2
 int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint32_t y1) {
   if (!c || !pc) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
@@ -368,12 +368,12 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   a.queue_count = nullptr;
   a.queue_region = 0;
   a.pool_slab = nullptr;
-  if (c->trace_pool && c->use_bvh && c->leaf_pairs && a.compact && a.spp == 1) {
+  if (c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1) {
     const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
     if (need && c->path_pool.bytes < need && (rc = alloc_buf(c->path_pool, need))) return rc;
     a.pool_slab = need ? c->path_pool.ptr : nullptr;
   }
-  const uint32_t window = c->trace_window ? c->trace_window : rt::pt_first_window(c->use_bvh);
+  const uint32_t window = c->trace_window ? c->trace_window : rt::pt_first_window(c->scene.use_bvh);
   a.first_window = window;
   if (a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS)) {
     // a region holds the survivors of ceil(workgroups / kPathQueues) workgroups of 256 paths (kernels.hip); the
@@ -390,7 +390,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
     a.queue_region = static_cast<uint32_t>(region);
   }
   a.cull = 0;
-  if (!c->use_bvh && c->width_fits_i16()) {
+  if (!c->scene.use_bvh && c->width_fits_i16()) {
     // K2 camera (raytrace.comp.glsl:314-320): at cameraPos, looking down -z, d = (slope*ux, slope*uy, -1) with
     // ux = (2cx - W)/H, uy = -(2cy - H)/H.  The Gaussian jitter is 0.375 * sqrt(-2 ln u1) <= 0.375 * 13.3 px
     // (u1 >= 1e-38, :87).
@@ -488,8 +488,8 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
   a.ext = ext;
   a.exact = (c->cfg.flags & RTPT_FLAG_EXACT_FILTER) ? 1 : 0;
   a.direct = (c->cfg.flags & RTPT_FLAG_DIRECT_FILTER) ? 1 : 0;
-  a.n_tris = c->n_tris;
-  a.pair_tab = static_cast<const float*>(c->pair_tab.ptr);
+  a.n_tris = c->scene.n_tris;
+  a.pair_tab = static_cast<const float*>(c->scene.pair_tab.ptr);
   a.rows_stored = static_cast<int32_t>(c->rows());
   a.n_cu = c->n_cu;
   // the last iteration of an even N writes `image` and nothing filters it again: alpha 0 like the reference's
@@ -501,7 +501,7 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
   a.in = static_cast<const float4*>(c->color[in_buf].ptr);
   a.out = static_cast<float4*>(c->color[out_buf].ptr);
   a.vis = static_cast<const uint32_t*>(c->vis[c->vis_cur].ptr);
-  a.normal_tab = static_cast<const float4*>(c->normal_tab.ptr);
+  a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
   {
     const int64_t lo = std::max<int64_t>(0, static_cast<int64_t>(y0) - reach), hi = std::min<int64_t>(c->cfg.height, static_cast<int64_t>(y1) + reach);
     const bool covered = c->normals.ptr && c->normals_frame == c->frames_ended && c->normals_y0 <= lo && c->normals_y1 >= hi;
@@ -519,7 +519,7 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
     a.alpha = c->cfg.alpha;
     a.worldpos = static_cast<const float4*>(c->worldpos.ptr);
     a.history = static_cast<const float4*>(c->color[c->color_of_role[ROLE_PREVIOUS]].ptr);
-    a.lut_prev = static_cast<const float4*>(c->lut[c->lut_cur ^ 1].ptr);
+    a.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
     rt::exact::mat_mul(ubo->projPrev, ubo->viewPrev, a.PVprev);  // temporalFiltering.comp.glsl:180
     a.prev_pixel = (c->debug_mask & RTPT_DEBUG_PREV_PIXEL) ? static_cast<int2*>(c->prev_pixel.ptr) : nullptr;
     a.hist_row_base = static_cast<int32_t>(c->cfg.row_begin);
@@ -553,7 +553,7 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
       m.traced = a.in;
       m.vis = a.vis;
       m.worldpos = static_cast<const float4*>(c->worldpos.ptr);
-      m.lut_prev = static_cast<const float4*>(c->lut[c->lut_cur ^ 1].ptr);
+      m.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
       rt::exact::mat_mul(ubo->projPrev, ubo->viewPrev, m.PVprev);
       m.prev_vis = static_cast<const uint32_t*>(c->vis[c->vis_cur ^ 1].ptr);
       m.moments_prev = static_cast<const float4*>(c->moments[c->moments_cur ^ 1].ptr);
@@ -647,7 +647,7 @@ int filter_flush(rtpt_ctx* c, bool fuse) {
   size_t i = 0;
   while (i < n) {
     int levels = 1;
-    if (fuse && !(c->cfg.flags & (RTPT_FLAG_DIRECT_FILTER | RTPT_FLAG_NO_FILTER_FUSION)) && !(c->cfg.flags & rt::kExtMask) && c->pair_tab.ptr) {
+    if (fuse && !(c->cfg.flags & (RTPT_FLAG_DIRECT_FILTER | RTPT_FLAG_NO_FILTER_FUSION)) && !(c->cfg.flags & rt::kExtMask) && c->scene.pair_tab.ptr) {
       const int k0 = calls[i].pc.waveletIteration, max_it = calls[i].pc.maxWaveletIteration;
       // grow the chain while the next record is the next iteration, its rows are covered and the kernel has the LDS
       while (i + levels < n && levels < c->chain_max) {
@@ -660,7 +660,7 @@ int filter_flush(rtpt_ctx* c, bool fuse) {
         const int need0 = std::max(0, static_cast<int>(nxt.y0) - kn), need1 = std::min(H, static_cast<int>(nxt.y1) + kn);
         if (nxt.y1 <= nxt.y0 || static_cast<int>(cur.y0) > need0 || static_cast<int>(cur.y1) < need1) break;
         if (static_cast<int64_t>(nxt.y1 - nxt.y0) * c->cfg.width < c->chain_min_pixels) break;
-        if (!rt::atrous_chain_supported(k0, levels + 1, c->n_tris)) break;
+        if (!rt::atrous_chain_supported(k0, levels + 1, c->scene.n_tris)) break;
         levels++;
         if (nxt_final) break;
       }
@@ -688,7 +688,7 @@ extern "C" {
 
 int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   if (!c || !pc) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = filter_validate(c, pc, ubo, y0, y1);
   if (rc) return rc;
   if ((rc = ensure_tables(c))) return rc;
@@ -699,7 +699,7 @@ int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_
   f.y0 = y0;
   f.y1 = y1;
   const bool record = !(c->cfg.flags & (RTPT_FLAG_NO_FILTER_FUSION | RTPT_FLAG_DIRECT_FILTER)) && !(c->cfg.flags & rt::kExtMask) &&
-                      c->pair_tab.ptr && c->chain_max > 1;
+                      c->scene.pair_tab.ptr && c->chain_max > 1;
   if (!record) {
     FLUSH_FILTER(c);
     return filter_launch(c, f, 1);
@@ -738,7 +738,7 @@ int rtpt_end_frame(rtpt_ctx* c) {
   c->vis_cur ^= 1;
   c->moments_cur ^= 1;
   c->lut_cur ^= 1;
-  c->lut_prev_valid = c->n_tris != 0;
+  c->scene.lut_prev_valid = c->scene.n_tris != 0;
   c->final_swapped = false;
   c->frames_ended++;
   return RTPT_OK;

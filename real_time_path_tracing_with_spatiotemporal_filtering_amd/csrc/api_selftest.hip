@@ -79,7 +79,7 @@ int rtpt_selftest_div(rtpt_ctx* c, int mode, uint32_t first_pass, uint32_t n_pas
 
 int rtpt_selftest_trace(rtpt_ctx* c, const float* rays, size_t n, uint32_t* out_id, float* out_t) {
   if (!c || !rays || !out_id) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   if (n == 0) return RTPT_OK;
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);  // a recorded G-buffer call holds the scene view, and with it the stack's spill area, which may move below
@@ -145,18 +145,18 @@ void rtpt_util_perspective(float fovy, float aspect, float zn, float zf, float m
 //   [6] child boxes wider than the padded scene (a box that was never rewritten), [7] dangling references
 int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
   if (!c || !stats) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris || !c->nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!c->scene.n_tris || !c->scene.tree.nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
-  const uint32_t n = c->n_tris, nn = c->n_nodes;
+  const uint32_t n = c->scene.n_tris, nn = c->scene.tree.n_nodes;
   std::vector<rt::BvhNodeQ> q(nn);
   std::vector<float> tris(static_cast<size_t>(n) * 9);
   std::vector<uint32_t> leaf(n);
   float g[8];
-  HIP_TRY(hipMemcpyAsync(q.data(), c->nodes.ptr, q.size() * sizeof(rt::BvhNodeQ), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(tris.data(), c->tris.ptr, tris.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(leaf.data(), c->leaf_order.ptr, leaf.size() * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(g, c->bvh_grid_dev.ptr, sizeof g, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(q.data(), c->scene.tree.nodes.ptr, q.size() * sizeof(rt::BvhNodeQ), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(tris.data(), c->scene.tris.ptr, tris.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(leaf.data(), c->scene.tree.leaf_order.ptr, leaf.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(g, c->scene.bvh_grid_dev.ptr, sizeof g, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int i = 0; i < 8; i++) stats[i] = 0;
   stats[0] = nn;
@@ -204,7 +204,7 @@ int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
           stats[7]++;
           continue;
         }
-        if (c->leaf_pairs && !rt::pair_leaf_ok(first, cnt, leaf.data(), n)) stats[7]++;  // read as ONE pair record
+        if (c->scene.tree.leaf_pairs && !rt::pair_leaf_ok(first, cnt, leaf.data(), n)) stats[7]++;  // read as ONE pair record
         for (uint32_t j = 0; j < cnt; j++)
           for (int v = 0; v < 3; v++)
             for (int a = 0; a < 3; a++) {
@@ -252,8 +252,8 @@ int rtpt_debug_bvh_check(rtpt_ctx* c, uint64_t stats[8]) {
 
 int rtpt_debug_bvh_topology(rtpt_ctx* c, uint32_t* child_refs, uint32_t* n_nodes, uint32_t* leaf_order, uint32_t* n_leaf_ids) {
   if (!c || !n_nodes || !n_leaf_ids) return fail(RTPT_E_INVALID, "NULL argument");
-  if (!c->n_tris || !c->nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
-  const uint32_t n = c->n_tris, nn = c->n_nodes;
+  if (!c->scene.n_tris || !c->scene.tree.nodes.ptr) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const uint32_t n = c->scene.n_tris, nn = c->scene.tree.n_nodes;
   if (!child_refs && !leaf_order) {
     *n_nodes = nn;
     *n_leaf_ids = n;
@@ -264,8 +264,8 @@ int rtpt_debug_bvh_topology(rtpt_ctx* c, uint32_t* child_refs, uint32_t* n_nodes
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
   std::vector<rt::BvhNodeQ> q(nn);
-  HIP_TRY(hipMemcpyAsync(q.data(), c->nodes.ptr, q.size() * sizeof(rt::BvhNodeQ), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(leaf_order, c->leaf_order.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(q.data(), c->scene.tree.nodes.ptr, q.size() * sizeof(rt::BvhNodeQ), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(leaf_order, c->scene.tree.leaf_order.ptr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (uint32_t i = 0; i < nn; i++) {
     child_refs[2 * static_cast<size_t>(i)] = q[i].lref;
