@@ -168,6 +168,27 @@ typedef struct rtpt_visibility_data {
                                               same call (host flatten + host SAH, HOST_SAH / FALLBACK_DEPTH).  Same tree, same
                                               pixels; what changes is the cost of an upload.  Additive: the ABI version stays 5 */
 
+#define RTPT_FLAG_EXT_DEMODULATE 0x8000u  /* albedo demodulation (SVGF, Schied et al. 2017; NOT reference behaviour, default off): the
+                                              filter and the history run on ILLUMINATION, colour with the albedo of the primary
+                                              surface divided out, so that a material border between coplanar surfaces (same
+                                              normal, same depth: only the colour term stops there, weakly) stays sharp.
+                                              rtpt_raytrace leaves out the multiply by the first hit's albedo (raytrace.comp.glsl:244
+                                              at segment 0) and stores that albedo in RTPT_PLANE_ALBEDO instead; a path that ends at
+                                              its first query (analytic light, sky, emissive material) stores albedo (1, 1, 1) and the
+                                              colour it has without the flag.  Colour without the flag = demodulated colour x ALBEDO up
+                                              to the order of the multiplies; random stream, ray count and HIT_ID are the same.
+                                              IMAGE, FILTERED, PREVIOUS and the blended history then hold demodulated colour; the
+                                              filter kernels are the ones of the same flags without this bit (it is not an
+                                              extension mode of K3: no wider halo, no other kernel).  rtpt_modulate writes the shaded
+                                              frame to RTPT_PLANE_SHADED and rtpt_present multiplies on the fly.  ALBEDO is valid
+                                              from rtpt_raytrace until the next rtpt_raytrace of the context, for the rows traced.
+                                              samples_per_pixel > 1 with this flag is refused by rtpt_create (RTPT_E_INVALID): the
+                                              mean of products is not the product of means, and the multi-sample accumulators in
+                                              LDS have no room for a second sum.  Known limitation: a pixel on a material border
+                                              takes the albedo this frame's jittered sample met, so it can alternate between the
+                                              two materials from frame to frame (1-spp aliasing that the filter blurs away without
+                                              the flag); ALBEDO is not accumulated over frames.  Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -215,7 +236,11 @@ typedef enum rtpt_plane {
   RTPT_PLANE_MOMENTS = 13,  /* extension RTPT_FLAG_EXT_VARIANCE: (m1, m2, history length, variance) float4 */
   RTPT_PLANE_VARIANCE = 14, /* extension: f32 variance written by the last filter iteration (or by the moments pass) */
   RTPT_PLANE_MOMENTS_PREV = 15, /* extension: the previous frame's moments (what this frame's accumulation reads) */
-  RTPT_PLANE_COUNT = 16
+  RTPT_PLANE_ALBEDO = 16,   /* RTPT_FLAG_EXT_DEMODULATE: RGBA32F like IMAGE, (albedo of the first hit of this frame's jittered
+                               primary ray, 0), (1, 1, 1, 0) where the path ended at its first query; written by rtpt_raytrace */
+  RTPT_PLANE_SHADED = 17,   /* RTPT_FLAG_EXT_DEMODULATE: RGBA32F, (frame.rgb * ALBEDO.rgb, 0), written by rtpt_modulate.  Without
+                               the flag neither plane is allocated: rtpt_plane_ptr returns NULL, rtpt_readback RTPT_E_INVALID */
+  RTPT_PLANE_COUNT = 18
 } rtpt_plane;
 
 typedef struct rtpt_ctx rtpt_ctx;
@@ -428,12 +453,23 @@ int rtpt_end_frame(rtpt_ctx* ctx);
  * buffer is the caller's "swapchain image"; with several ranks each rank converts its own rows and the presenting rank
  * gathers them (4 B/px on the wire instead of 16).  Runs on the context's stream. */
 int rtpt_present(rtpt_ctx* ctx, void* dst_device, uint32_t y0, uint32_t y1);
+/* With RTPT_FLAG_EXT_DEMODULATE the blit multiplies on the fly: every channel of frame.rgb * ALBEDO.rgb is rounded to binary32
+ * and then converted by the rule above, alpha 0 — the bytes are the conversion of RTPT_PLANE_SHADED, which is neither read nor
+ * needed (36 B/px).  The final filter pass never fuses its swapchain store under the flag (it would store demodulated colour):
+ * rtpt_present_target stays callable and rtpt_present does the work. */
 /* Optional, before the frame's rtpt_temporal_filter calls: name the swapchain rows of this frame in advance.  The final
  * filter pass then writes them in swapchain format as it stores the frame (one launch and one 16 B/px read less), and the
  * later rtpt_present of the same rows and image returns at once; where the final pass runs in a kernel that cannot fuse
  * the store (extension modes, direct-load variants), rtpt_present does the work as before — the calling sequence is the
  * same either way.  The registration stays until changed; dst_device == NULL clears it. */
 int rtpt_present_target(rtpt_ctx* ctx, void* dst_device, uint32_t y0, uint32_t y1);
+
+/* RTPT_FLAG_EXT_DEMODULATE (RTPT_E_INVALID without it): multiply the albedo back.  SHADED.rgb = frame.rgb * ALBEDO.rgb for frame
+ * rows [y0,y1) (the row conventions of the passes; 0,0 = all stored rows), one binary32 multiply per channel, alpha 0.  `frame`
+ * is IMAGE until rtpt_end_frame and PREVIOUS after it, like rtpt_present.  Call it after the frame's last rtpt_temporal_filter
+ * or after rtpt_end_frame, before the context's next rtpt_raytrace overwrites ALBEDO.  Per pixel: no halo, no guide, so a strip
+ * context modulates the rows it owns.  Launches what is recorded first, like every entry point; runs on the context's stream. */
+int rtpt_modulate(rtpt_ctx* ctx, uint32_t y0, uint32_t y1);
 
 /* ---- synchronisation / data movement ---------------------------------------------------- */
 int rtpt_sync(rtpt_ctx* ctx);
@@ -470,7 +506,8 @@ typedef enum rtpt_kernel_id {
   RTPT_K_PRESENT = 9,            /* rtpt_present: RGBA32F -> B8G8R8A8_UNORM */
   RTPT_K_GBUFFER_PATHTRACE = 10, /* K0, K1 and K2 in one launch (rtpt_raytrace right behind rtpt_gbuffer + rtpt_temporal_gradient,
                                     the reference's own order, main.cpp:1105-1107): ABI version 4 */
-  RTPT_K_COUNT = 11
+  RTPT_K_MODULATE = 11,          /* rtpt_modulate: SHADED = frame x ALBEDO (RTPT_FLAG_EXT_DEMODULATE) */
+  RTPT_K_COUNT = 12
 } rtpt_kernel_id;
 int rtpt_timing_enable(rtpt_ctx* ctx, int enable);
 int rtpt_timing_collect(rtpt_ctx* ctx, double ms_sum[RTPT_K_COUNT], uint32_t launches[RTPT_K_COUNT]);

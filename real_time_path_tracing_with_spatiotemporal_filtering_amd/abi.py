@@ -28,6 +28,7 @@ FLAG_EXT_SVGF_VARIANCE = 0x800
 FLAG_EXT_MASK = 0x9F0
 FLAG_DEVICE_BVH_BUILD = 0x1000  # rtpt_scene_upload builds the tree on the device (csrc/bvh_build.hip)
 FLAG_DEVICE_BVH_SAH = 0x2000  # with FLAG_DEVICE_BVH_BUILD: the device SAH builder, the host's tree node for node (csrc/bvh_build_sah.hip)
+FLAG_EXT_DEMODULATE = 0x8000  # filter illumination, multiply the first hit's albedo back afterwards (modulate / present); not in FLAG_EXT_MASK
 FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms -> triangles and the fan-pair test on the device (csrc/scene_flatten.hip)
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
@@ -37,12 +38,13 @@ DEBUG_HIT_ID, DEBUG_PREV_PIXEL = 0x1, 0x2
 # rtpt_plane
 (PLANE_IMAGE, PLANE_FILTERED, PLANE_PREVIOUS, PLANE_WORLDPOS, PLANE_GRADIENT, PLANE_DEPTH, PLANE_VIS_ID,
  PLANE_PREV_VIS_ID, PLANE_LUT, PLANE_LUT_PREV, PLANE_PREV_PIXEL, PLANE_RAYCOUNT, PLANE_HIT_ID, PLANE_MOMENTS,
- PLANE_VARIANCE, PLANE_MOMENTS_PREV) = range(16)
+ PLANE_VARIANCE, PLANE_MOMENTS_PREV, PLANE_ALBEDO, PLANE_SHADED) = range(18)
+PLANE_COUNT = 18
 # rtpt_kernel_id
 (K_GBUFFER, K_LUT, K_GRADIENT, K_PATHTRACE, K_ATROUS, K_ATROUS_FINAL, K_ATROUS_CHAIN, K_ATROUS_CHAIN_FINAL,
- K_GBUFFER_GRADIENT, K_PRESENT, K_GBUFFER_PATHTRACE, K_COUNT) = range(12)
+ K_GBUFFER_GRADIENT, K_PRESENT, K_GBUFFER_PATHTRACE, K_MODULATE, K_COUNT) = range(13)
 KERNEL_NAMES = ["k_gbuffer", "k_lut", "k_gradient", "k_pathtrace", "k_atrous", "k_atrous_final", "k_atrous_chain",
-                "k_atrous_chain_final", "k_gbuffer_gradient", "k_present", "k_gbuffer_pathtrace"]
+                "k_atrous_chain_final", "k_gbuffer_gradient", "k_present", "k_gbuffer_pathtrace", "k_modulate"]
 
 
 class RtptLibraryMissing(RuntimeError):
@@ -112,7 +114,7 @@ SYMBOLS = [
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
-    "rtpt_debug_live_device_bytes",
+    "rtpt_debug_live_device_bytes", "rtpt_modulate",
 ]
 
 _lib = None
@@ -153,6 +155,7 @@ def load() -> C.CDLL:
         "rtpt_end_frame": [vp],
         "rtpt_present": [vp, vp, u32, u32],
         "rtpt_present_target": [vp, vp, u32, u32],
+        "rtpt_modulate": [vp, u32, u32],
         "rtpt_sync": [vp],
         "rtpt_readback": [vp, C.c_int, vp, sz],
         "rtpt_set_plane": [vp, C.c_int, vp, sz],
@@ -256,7 +259,7 @@ _PLANE_DTYPE = {
     PLANE_WORLDPOS: (np.float32, 4), PLANE_GRADIENT: (np.float32, 4), PLANE_DEPTH: (np.float32, 1),
     PLANE_VIS_ID: (np.uint32, 1), PLANE_PREV_VIS_ID: (np.uint32, 1), PLANE_PREV_PIXEL: (np.int32, 2),
     PLANE_HIT_ID: (np.uint32, 1), PLANE_MOMENTS: (np.float32, 4), PLANE_VARIANCE: (np.float32, 1),
-    PLANE_MOMENTS_PREV: (np.float32, 4),
+    PLANE_MOMENTS_PREV: (np.float32, 4), PLANE_ALBEDO: (np.float32, 4), PLANE_SHADED: (np.float32, 4),
 }
 
 
@@ -406,6 +409,10 @@ class Context:
     def present(self, dst_device_ptr: int, y0=0, y1=0):
         """main.cpp:1338-1361: rows [y0,y1) of the finished frame -> B8G8R8A8_UNORM at the device address"""
         _check(self._lib.rtpt_present(self._h, C.c_void_p(dst_device_ptr), y0, y1))
+
+    def modulate(self, y0=0, y1=0):
+        """FLAG_EXT_DEMODULATE: SHADED = frame x ALBEDO for rows [y0,y1) of the finished frame (rtpt_modulate)"""
+        _check(self._lib.rtpt_modulate(self._h, y0, y1))
 
     def sync(self):
         _check(self._lib.rtpt_sync(self._h))

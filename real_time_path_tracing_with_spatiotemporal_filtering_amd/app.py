@@ -89,6 +89,14 @@ class HipBackend:
     def end_frame(self):
         self.ctx.end_frame()
 
+    @property
+    def demodulate(self) -> bool:
+        """FLAG_EXT_DEMODULATE: the colour planes hold illumination, the finished frame is the SHADED plane"""
+        return bool(self.ctx.cfg.flags & abi.FLAG_EXT_DEMODULATE)
+
+    def modulate(self, y0, y1):
+        self.ctx.modulate(y0, y1)
+
     def sync(self):
         self.ctx.sync()
 
@@ -158,6 +166,10 @@ class HipBackend:
         base = self.ctx.cfg.row_begin
         return self.ctx.readback(plane)[y0 - base:y1 - base]
 
+    def final_image_rows(self, y0: int, y1: int) -> np.ndarray:
+        """rows of the finished float frame on the host (after end_frame): PREVIOUS, or SHADED with FLAG_EXT_DEMODULATE"""
+        return self.readback_rows(abi.PLANE_SHADED if self.demodulate else abi.PLANE_PREVIOUS, y0, y1)
+
     # presenting the frame (main.cpp:1338-1361) ---------------------------------------------------
     on_device = True
 
@@ -174,7 +186,9 @@ class HipBackend:
         self.ctx.present_target(image8.data_ptr() + y0 * self.width * 4, y0, y1)
 
     def final_rows(self, y0: int, y1: int):
-        """torch view of rows of the finished frame (after end_frame: the PREVIOUS plane)"""
+        """torch view of rows of the finished frame (after end_frame: the PREVIOUS plane; SHADED with FLAG_EXT_DEMODULATE)"""
+        if self.demodulate:
+            return self.guide_rows(abi.PLANE_SHADED, y0, y1)
         return self.color_rows(abi.PLANE_PREVIOUS, y0, y1)
 
     # two frames in flight (PipelinedBackend) ------------------------------------------------
@@ -278,6 +292,13 @@ class PipelinedBackend:
             self.cur.set_history_from(self.prev, o0, o1)
         self.cur.temporal_filter(pc, ubo, y0, y1)
 
+    @property
+    def demodulate(self):
+        return getattr(self.be[0], "demodulate", False)
+
+    def modulate(self, y0, y1):   # called before end_frame: the frame being finished lives in `cur`
+        self.cur.modulate(y0, y1)
+
     def end_frame(self):
         self.cur.end_frame()
         self.frame += 1
@@ -326,7 +347,8 @@ class PipelinedBackend:
 
     def final_image_rows(self, y0, y1):
         """rows of the last finished frame"""
-        return self.prev.readback_rows(abi.PLANE_PREVIOUS, y0, y1)
+        out = getattr(self.prev, "final_image_rows", None)   # HipBackend: SHADED with FLAG_EXT_DEMODULATE
+        return out(y0, y1) if out else self.prev.readback_rows(abi.PLANE_PREVIOUS, y0, y1)
 
     # presenting: called after end_frame, i.e. the finished frame lives in `prev`; no stream-to-stream wait — the
     # caller is still on the finished frame's stream (drawScene's scope)
@@ -537,6 +559,16 @@ class PathTracingApplication:
             if self.plan.world > 1 and k == self.maxWaveletIteration and (k & 1):
                 self._prepare_history()
             self.backend.temporal_filter(pc, self.ubo, *self.plan.filter_rows(k))
+        if getattr(self.backend, "demodulate", False):
+            # FLAG_EXT_DEMODULATE: the filter ran on illumination; the rows this rank owns get their albedo back (SHADED is
+            # what every consumer of the finished float frame takes; history and halo bands stay demodulated)
+            if self.present == "f32" and self._present_done:
+                # a gather of float strips reads SHADED itself, and the one posted for the previous frame may still be
+                # sending (_acquire waits for the one of two frames ago only: enough for the colour buffers, which rotate)
+                import torch
+                for ev in self._present_done.values():
+                    torch.cuda.current_stream().wait_event(ev)
+            self.backend.modulate(*self.plan.own)
 
     def copyImageToSwapChainsCurrentImage(self):
         """main.cpp:1308-1406: the history hand-over (:1364-1372) and, when `present` is set, the blit to the

@@ -84,6 +84,8 @@ Buf* plane_buf(rtpt_ctx* c, rtpt_plane which) {
     case RTPT_PLANE_MOMENTS: return &c->moments[c->moments_cur];
     case RTPT_PLANE_MOMENTS_PREV: return &c->moments[c->moments_cur ^ 1];
     case RTPT_PLANE_VARIANCE: return &c->variance[c->variance_last];
+    case RTPT_PLANE_ALBEDO: return &c->albedo;
+    case RTPT_PLANE_SHADED: return &c->shaded;
     default: return nullptr;
   }
 }
@@ -102,7 +104,9 @@ size_t plane_size(const rtpt_ctx* c, rtpt_plane which) {
     case RTPT_PLANE_HIT_ID:
     case RTPT_PLANE_VARIANCE: return px * 4;
     case RTPT_PLANE_MOMENTS:
-    case RTPT_PLANE_MOMENTS_PREV: return px * 16;
+    case RTPT_PLANE_MOMENTS_PREV:
+    case RTPT_PLANE_ALBEDO:
+    case RTPT_PLANE_SHADED: return px * 16;
     case RTPT_PLANE_PREV_PIXEL: return px * 8;
     case RTPT_PLANE_LUT:
     case RTPT_PLANE_LUT_PREV: return (static_cast<size_t>(c->scene.n_tris) + 1) * sizeof(rtpt_visibility_data);
@@ -264,6 +268,12 @@ static int alloc_planes(rtpt_ctx* c) {
     c->variance_last = 0;
     if (rc == RTPT_OK && (c->cfg.flags & RTPT_FLAG_EXT_SVGF_VARIANCE)) rc = alloc_buf(c->var_scale, px * 4);
   }
+  if (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) {
+    for (Buf* b : {&c->albedo, &c->shaded}) {
+      if (rc == RTPT_OK) rc = alloc_buf(*b, px * 16);
+      if (rc == RTPT_OK) (void)hipMemsetAsync(b->ptr, 0, px * 16, c->stream);
+    }
+  }
   if (rc == RTPT_OK && (c->debug_mask & RTPT_DEBUG_HIT_ID)) rc = alloc_buf(c->hit_id, px * 4);
   if (rc == RTPT_OK && (c->debug_mask & RTPT_DEBUG_PREV_PIXEL)) rc = alloc_buf(c->prev_pixel, px * 8);
   if (rc != RTPT_OK) return rc;
@@ -305,6 +315,8 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
     return fail(RTPT_E_INVALID, "max_segments, samples_per_pixel and sigma_n must be >= 1");
   if ((cfg->flags & RTPT_FLAG_EXT_SVGF_VARIANCE) && !(cfg->flags & RTPT_FLAG_EXT_VARIANCE))
     return fail(RTPT_E_INVALID, "RTPT_FLAG_EXT_SVGF_VARIANCE completes RTPT_FLAG_EXT_VARIANCE: set both");
+  if ((cfg->flags & RTPT_FLAG_EXT_DEMODULATE) && cfg->samples_per_pixel > 1)
+    return fail(RTPT_E_INVALID, "RTPT_FLAG_EXT_DEMODULATE needs samples_per_pixel == 1 (the mean of products is not the product of means)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     (void)hipGetLastError();
@@ -686,6 +698,7 @@ const char* rtpt_kernel_name(rtpt_kernel_id k) {
     case RTPT_K_GBUFFER_GRADIENT: return "k_gbuffer_gradient";
     case RTPT_K_GBUFFER_PATHTRACE: return "k_gbuffer_pathtrace";
     case RTPT_K_PRESENT: return "k_present";
+    case RTPT_K_MODULATE: return "k_modulate";
     default: return "?";
   }
 }

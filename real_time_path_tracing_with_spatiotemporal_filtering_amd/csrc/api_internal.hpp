@@ -165,6 +165,7 @@ struct rtpt_ctx {
   Buf worldpos, gradient, depth, prev_pixel, hit_id, raycount;
   Buf moments[2], variance[2];  // RTPT_FLAG_EXT_VARIANCE
   Buf var_scale;                // RTPT_FLAG_EXT_SVGF_VARIANCE: the prefiltered variance of the iteration being launched
+  Buf albedo, shaded;           // RTPT_FLAG_EXT_DEMODULATE: the first hit's albedo (rtpt_raytrace) and the frame times it (rtpt_modulate)
   Buf path_queue[2], path_queue_count;  // long paths: survivors handed from one k_pathtrace launch to the next
   Buf normals;                  // per-pixel normal plane for the LDS-staged filter of scenes without an id-pair table
   int normals_y0 = 0, normals_y1 = 0;  // rows for which it matches VIS_ID

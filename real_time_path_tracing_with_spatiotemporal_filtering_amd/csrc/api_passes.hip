@@ -359,6 +359,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   a.depth = static_cast<const float*>(c->depth.ptr);
   c->alpha_depth[c->color_of_role[ROLE_IMAGE]] = true;
   a.hit_id = (c->debug_mask & RTPT_DEBUG_HIT_ID) ? static_cast<uint32_t*>(c->hit_id.ptr) : nullptr;
+  a.albedo = (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) ? static_cast<float4*>(c->albedo.ptr) : nullptr;
   a.raycount = static_cast<unsigned long long*>(c->raycount.ptr);
   a.count_y0 = c->count_y0;
   a.count_y1 = c->count_y1;
@@ -368,7 +369,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   a.queue_count = nullptr;
   a.queue_region = 0;
   a.pool_slab = nullptr;
-  if (c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1) {
+  if (c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo) {  // (the pool form stores no albedo)
     const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
     if (need && c->path_pool.bytes < need && (rc = alloc_buf(c->path_pool, need))) return rc;
     a.pool_slab = need ? c->path_pool.ptr : nullptr;
@@ -582,8 +583,9 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
     }
   }
   if (final_pass) c->present_fused_dst = nullptr;  // a new frame's final pass: the previous frame's blit is history
+  // (RTPT_FLAG_EXT_DEMODULATE: the pass stores demodulated colour, the swapchain takes colour x albedo — rtpt_present does the work)
   if (final_pass && levels == 1 && c->present_dst && static_cast<int>(y0) <= c->present_y0 && static_cast<int>(y1) >= c->present_y1 &&
-      rt::atrous_final_fuses_present(a)) {
+      !(c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) && rt::atrous_final_fuses_present(a)) {
     a.present = static_cast<uint32_t*>(c->present_dst);
     a.present_y0 = c->present_y0;
     a.present_y1 = c->present_y1;
@@ -783,9 +785,29 @@ int rtpt_present(rtpt_ctx* c, void* dst_device, uint32_t y0, uint32_t y1) {
   HIP_TRY(hipSetDevice(c->device));
   {
     Timer tm(c, RTPT_K_PRESENT);
-    rt::launch_present(geom(c, y0, y1), static_cast<const float4*>(b->ptr), static_cast<uint32_t*>(dst_device), c->stream);
+    rt::launch_present(geom(c, y0, y1), static_cast<const float4*>(b->ptr),
+                       (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) ? static_cast<const float4*>(c->albedo.ptr) : nullptr, static_cast<uint32_t*>(dst_device),
+                       c->stream);
   }
   return launch_check("present");
+}
+
+// RTPT_FLAG_EXT_DEMODULATE: SHADED = frame x ALBEDO, the frame being what rtpt_present blits
+int rtpt_modulate(rtpt_ctx* c, uint32_t y0, uint32_t y1) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!(c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE)) return fail(RTPT_E_INVALID, "rtpt_modulate needs RTPT_FLAG_EXT_DEMODULATE");
+  FLUSH_FILTER(c);
+  int rc = check_rows(c, y0, y1);
+  if (rc) return rc;
+  Buf* b = plane_buf(c, c->image_alias ? RTPT_PLANE_PREVIOUS : RTPT_PLANE_IMAGE);
+  if (!b || !b->ptr || !c->albedo.ptr || !c->shaded.ptr) return fail(RTPT_E_INVALID, "no image plane");
+  HIP_TRY(hipSetDevice(c->device));
+  {
+    Timer tm(c, RTPT_K_MODULATE);
+    rt::launch_modulate(geom(c, y0, y1), static_cast<const float4*>(b->ptr), static_cast<const float4*>(c->albedo.ptr),
+                        static_cast<float4*>(c->shaded.ptr), c->stream);
+  }
+  return launch_check("modulate");
 }
 
 }  // extern "C"

@@ -565,6 +565,31 @@ __global__ __launch_bounds__(kThreads) void k_present(FrameGeom g, const float4*
   dst[static_cast<size_t>(y - g.y0) * g.W + x] = pack_bgra8(xyz(c), c.w);
 }
 
+// RTPT_FLAG_EXT_DEMODULATE.  The blit of the shaded frame without the shaded frame: the products are rounded to binary32 (the
+// file is compiled -ffp-contract=off) and converted like k_present converts, so the bytes are the conversion of k_modulate's
+// output; 36 B/px
+__global__ __launch_bounds__(kThreads) void k_present_modulated(FrameGeom g, const float4* __restrict__ image, const float4* __restrict__ albedo,
+                                                                uint32_t* __restrict__ dst) {
+  const int x = blockIdx.x * kBlockX + threadIdx.x;
+  const int y = g.y0 + blockIdx.y * kBlockY + threadIdx.y;
+  if (x >= g.W || y >= g.y1) return;
+  const size_t i = static_cast<size_t>(y - g.row_base) * g.W + x;
+  const float4 c = image[i], al = albedo[i];
+  dst[static_cast<size_t>(y - g.y0) * g.W + x] = pack_bgra8(f3{c.x * al.x, c.y * al.y, c.z * al.z}, 0.0f);
+}
+
+// shaded = (image.rgb * albedo.rgb, 0): one pixel per lane, two 16-byte loads and one 16-byte store, a wave covers 1 KiB of
+// each row; the grid is the 64 x 4 tiles of the rows asked for
+__global__ __launch_bounds__(kThreads) void k_modulate(FrameGeom g, const float4* __restrict__ image, const float4* __restrict__ albedo,
+                                                       float4* __restrict__ shaded) {
+  const int x = blockIdx.x * kBlockX + threadIdx.x;
+  const int y = g.y0 + blockIdx.y * kBlockY + threadIdx.y;
+  if (x >= g.W || y >= g.y1) return;
+  const size_t i = static_cast<size_t>(y - g.row_base) * g.W + x;
+  const float4 c = image[i], al = albedo[i];
+  shaded[i] = make_float4(c.x * al.x, c.y * al.y, c.z * al.z, 0.0f);
+}
+
 }  // namespace
 
 #if RTPT_TILE_TIMELINE
@@ -573,9 +598,17 @@ __global__ __launch_bounds__(kThreads) void k_present(FrameGeom g, const float4*
 #undef RTPT_SPAN_HOST
 #endif
 
-void launch_present(const FrameGeom& g, const float4* image, uint32_t* dst, hipStream_t s) {
+void launch_present(const FrameGeom& g, const float4* image, const float4* albedo, uint32_t* dst, hipStream_t s) {
   if (g.y1 <= g.y0) return;
-  hipLaunchKernelGGL(k_present, grid_for(g), dim3(kBlockX, kBlockY), 0, s, g, image, dst);
+  if (albedo)
+    hipLaunchKernelGGL(k_present_modulated, grid_for(g), dim3(kBlockX, kBlockY), 0, s, g, image, albedo, dst);
+  else
+    hipLaunchKernelGGL(k_present, grid_for(g), dim3(kBlockX, kBlockY), 0, s, g, image, dst);
+}
+
+void launch_modulate(const FrameGeom& g, const float4* image, const float4* albedo, float4* shaded, hipStream_t s) {
+  if (g.y1 <= g.y0) return;
+  hipLaunchKernelGGL(k_modulate, grid_for(g), dim3(kBlockX, kBlockY), 0, s, g, image, albedo, shaded);
 }
 
 void launch_var_prefilter(const FrameGeom& g, int rows_stored, const float* var, float* out, hipStream_t s) {

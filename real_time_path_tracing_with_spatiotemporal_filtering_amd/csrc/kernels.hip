@@ -725,14 +725,18 @@ constexpr int kPtRows = 4;
 constexpr int kPtThreads = kBlockX * kPtRows;
 // One path segment after its closest-hit query (raytrace.comp.glsl:226-267): the unoccluded light test, the sky, or a
 // diffuse bounce.  Returns true when the path ended (its colour is then `acc`).
+// alb_px (RTPT_FLAG_EXT_DEMODULATE; non-NULL only at segment 0 of the tile kernel): the pixel of PathtraceArgs::albedo.  The
+// albedo of this hit goes there instead of into the throughput, and a path that ends here stores (1, 1, 1) and keeps its colour.
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
-                                              f3& acc, uint32_t& rng) {
+                                              f3& acc, uint32_t& rng, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
+    if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     return true;
   }
   if (h.id1 == 0) {
     acc = acc * sky_color(d);  // :266
+    if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     return true;
   }
   const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
@@ -749,11 +753,15 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const float4 m0 = m[0], m1 = m[1];
     if (m1.w != 0.0f) {
       acc = acc * f3{m1.x, m1.y, m1.z};
+      if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       return true;
     }
     alb = f3{m0.x, m0.y, m0.z};
   }
-  acc = acc * alb;                                                 // :244
+  if (alb_px)
+    *alb_px = make_float4(alb.x, alb.y, alb.z, 0.0f);  // demodulated: rtpt_modulate / rtpt_present multiply it back
+  else
+    acc = acc * alb;                                               // :244
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
   float st_, ct;
@@ -827,7 +835,9 @@ constexpr int kPtWaves = 8;
 // GB: the launch also holds the workgroups of K0 (+ K1) (k_gbuffer_pathtrace below), which put the G-buffer depth into the
 // traced image's alpha themselves: a path that ends stores the 12 bytes of its colour only.  The launch's grid is then
 // taller than the tile grid (a.tiles_y rows of tiles).
-template <int BVH, bool COMPACT, bool GB>
+// DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
+// test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
+template <int BVH, bool COMPACT, bool GB, bool DEMOD>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -915,7 +925,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
         if (y >= a.count_y0 && y < a.count_y1) rays++;
         const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
-        const bool done = shade_segment(a, h, seg, light_c, o, d, acc, rng);
+        const bool done = shade_segment(a, h, seg, light_c, o, d, acc, rng, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
         if (done) {
           alive = false;
           if (a.spp == 1) {
@@ -1012,17 +1022,17 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
 constexpr int kPtBvhWaves = 8;
-template <int BVH, bool COMPACT>
+template <int BVH, bool COMPACT, bool DEMOD>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a) {
-  pathtrace_tile<BVH, COMPACT, false>(a);
+  pathtrace_tile<BVH, COMPACT, false, DEMOD>(a);
 }
-template <bool COMPACT>
+template <bool COMPACT, bool DEMOD>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a) {
-  pathtrace_tile<false, COMPACT, false>(a);
+  pathtrace_tile<false, COMPACT, false, DEMOD>(a);
 }
 
 // K0 + K1 + K2 in one launch (rtpt_gbuffer / rtpt_temporal_gradient recorded right before rtpt_raytrace: main.cpp:1105-1107
@@ -1032,12 +1042,12 @@ void k_pathtrace_small(PathtraceArgs a) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH>
+template <int BVH, bool DEMOD>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<BVH, true, true>(a);
+    pathtrace_tile<BVH, true, true, DEMOD>(a);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1046,11 +1056,12 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
     gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
+template <bool DEMOD>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<0, true, true>(a);
+    pathtrace_tile<0, true, true, DEMOD>(a);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1338,19 +1349,22 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t
 #endif
   with_scene_mode(a.scene, [&](auto mode) {
     constexpr int M = decltype(mode)::value;
-    if (gb) {
-      if constexpr (M != 0)
-        hipLaunchKernelGGL((k_gbuffer_pathtrace<M>), grid, block, dyn, s, b, *gb);
-      else
-        hipLaunchKernelGGL(k_gbuffer_pathtrace_small, grid, block, dyn, s, b, *gb);
-      return;
-    }
-    with_bool(a.compact != 0, [&](auto compact) {
-      constexpr bool C = decltype(compact)::value;
-      if constexpr (M != 0)
-        hipLaunchKernelGGL((k_pathtrace<M, C>), grid, block, dyn, s, b);
-      else
-        hipLaunchKernelGGL((k_pathtrace_small<C>), grid, block, dyn, s, b);
+    with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
+      constexpr bool D = decltype(demod)::value;
+      if (gb) {
+        if constexpr (M != 0)
+          hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D>), grid, block, dyn, s, b, *gb);
+        else
+          hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D>), grid, block, dyn, s, b, *gb);
+        return;
+      }
+      with_bool(a.compact != 0, [&](auto compact) {
+        constexpr bool C = decltype(compact)::value;
+        if constexpr (M != 0)
+          hipLaunchKernelGGL((k_pathtrace<M, C, D>), grid, block, dyn, s, b);
+        else
+          hipLaunchKernelGGL((k_pathtrace_small<C, D>), grid, block, dyn, s, b);
+      });
     });
   });
   if (!split) return;

@@ -121,6 +121,8 @@ struct PathtraceArgs {
   float4* image;        // written as (rgb, depth): see atrous.hip "rgbd"
   const float* depth;   // G-buffer depth of the same pixels
   uint32_t* hit_id;  // nullable
+  float4* albedo;    // nullable.  RTPT_FLAG_EXT_DEMODULATE: segment 0 stores (albedo of the hit, 0) here — (1, 1, 1, 0) when the path
+                     // ends at that query — instead of multiplying it into the throughput
   unsigned long long* raycount;
   int32_t count_y0, count_y1;  // rows whose queries are counted
   int32_t compact;             // 1: compact surviving paths to the front of the block after every segment
@@ -332,7 +334,11 @@ hipError_t prepare_device_atrous_chain();
 hipError_t prepare_device_atrous();  // per device, from rtpt_create: raises the dynamic-LDS limit of the staged filter kernels
 void launch_stamp_depth(const FrameGeom& g, float4* color, const float* depth, hipStream_t s);
 // swapchain blit (main.cpp:1338-1361): rows [g.y0,g.y1) of `image` -> B8G8R8A8_UNORM at dst (first byte = pixel (0, g.y0))
-void launch_present(const FrameGeom& g, const float4* image, uint32_t* dst, hipStream_t s);
+// albedo != NULL (RTPT_FLAG_EXT_DEMODULATE): the bytes are the conversion of (image.rgb * albedo.rgb, 0), each product rounded to
+// binary32 first
+void launch_present(const FrameGeom& g, const float4* image, const float4* albedo, uint32_t* dst, hipStream_t s);
+// RTPT_FLAG_EXT_DEMODULATE: shaded = (image.rgb * albedo.rgb, 0) over rows [g.y0,g.y1)
+void launch_modulate(const FrameGeom& g, const float4* image, const float4* albedo, float4* shaded, hipStream_t s);
 void launch_selftest_math(int op, const float* in, float* out, size_t n, hipStream_t s);
 void launch_selftest_exhaustive(int op, unsigned long long* out, hipStream_t s);
 void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipStream_t s);

@@ -486,6 +486,17 @@ void PathTracingApplication::applyTemporalFiltering() {
               "applyTemporalFiltering");
       }
     }
+    if (opt_.flags & RTPT_FLAG_EXT_DEMODULATE) {  // the filter ran on illumination: the rows a rank owns get their albedo back
+      // a gather of float strips sends from SHADED itself, and the previous frame's may still be under way (acquirePresent
+      // waits for the one of two frames ago only: enough for the colour buffers, which rotate; SHADED is rewritten every frame)
+      if (opt_.present == 2)
+        for (void* e : presentDone_)
+          if (e) host_stream_wait_event(stream_, e);
+      for (auto& rs : ranks_) {
+        const Rows own = rs.plan.own();
+        check(rtpt_modulate(rs.ctx, static_cast<uint32_t>(own.first), static_cast<uint32_t>(own.second)), "rtpt_modulate");
+      }
+    }
     return;
   }
   for (int k = 1; k <= opt_.maxWaveletIteration; k++) {           // :1259
@@ -509,6 +520,7 @@ void PathTracingApplication::applyTemporalFiltering() {
     // the descriptor swap of :1264-1281 is the ping-pong rule inside rtpt_temporal_filter
     check(rtpt_temporal_filter(ctx_, &pushConstants, &ubo, 0, 0), "applyTemporalFiltering");
   }
+  if (opt_.flags & RTPT_FLAG_EXT_DEMODULATE) check(rtpt_modulate(ctx_, 0, 0), "rtpt_modulate");
 }
 
 void PathTracingApplication::copyImageToSwapChainsCurrentImage() {
@@ -556,8 +568,8 @@ void PathTracingApplication::presentFrame() {
       check(rtpt_present(rs.ctx, dst, static_cast<uint32_t>(own.first), static_cast<uint32_t>(own.second)), "rtpt_present");
       mine[i] = dst;
     } else {
-      void* prev = nullptr;
-      check(rtpt_plane_ptr(rs.ctx, RTPT_PLANE_PREVIOUS, &prev), "rtpt_plane_ptr");
+      void* prev = nullptr;  // the finished float frame: SHADED when the colour planes hold illumination
+      check(rtpt_plane_ptr(rs.ctx, finalPlane(), &prev), "rtpt_plane_ptr");
       mine[i] = static_cast<const char*>(prev) + static_cast<size_t>(own.first - rs.plan.stored().first) * row_bytes;
       if (root)
         host_device_copy(static_cast<char*>(presentImage(&rs, idx)) + static_cast<size_t>(own.first) * row_bytes, mine[i],
@@ -749,14 +761,14 @@ std::vector<float> PathTracingApplication::readImage() {
     for (auto& rs : ranks_) {
       const Rows st = rs.plan.stored(), own = rs.plan.own();
       std::vector<float> strip(static_cast<size_t>(st.second - st.first) * row_floats);
-      check(rtpt_readback(rs.last, RTPT_PLANE_PREVIOUS, strip.data(), strip.size() * sizeof(float)), "rtpt_readback");
+      check(rtpt_readback(rs.last, finalPlane(), strip.data(), strip.size() * sizeof(float)), "rtpt_readback");
       std::memcpy(img.data() + static_cast<size_t>(own.first) * row_floats, strip.data() + static_cast<size_t>(own.first - st.first) * row_floats,
                   static_cast<size_t>(own.second - own.first) * row_floats * sizeof(float));
     }
     return img;
   }
   // after rtpt_end_frame IMAGE and PREVIOUS hold the same pixels (main.cpp:1364)
-  check(rtpt_readback(last_, RTPT_PLANE_PREVIOUS, img.data(), img.size() * sizeof(float)), "rtpt_readback");
+  check(rtpt_readback(last_, finalPlane(), img.data(), img.size() * sizeof(float)), "rtpt_readback");
   return img;
 }
 

@@ -131,6 +131,9 @@ class PathTracingApplication {
   void sceneBounds();
   bool multi() const { return opt_.ranks > 1; }
   bool cameraStatic() const;
+  // the plane that holds the finished float frame after rtpt_end_frame: with RTPT_FLAG_EXT_DEMODULATE PREVIOUS is illumination
+  // (it stays the history) and rtpt_modulate's SHADED is the frame
+  rtpt_plane finalPlane() const { return (opt_.flags & RTPT_FLAG_EXT_DEMODULATE) ? RTPT_PLANE_SHADED : RTPT_PLANE_PREVIOUS; }
   void exchangeHalo(int k);
   void exchangeHaloPlane(int k, rtpt_plane plane, size_t px_bytes);
   void prepareHistory();
