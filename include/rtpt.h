@@ -397,9 +397,27 @@ int rtpt_debug_live_device_bytes(uint64_t* out);
  * rtpt_resize, rtpt_set_stream with another stream and rtpt_enable_debug with another mask make the next frame compute
  * it again, and a plane bound with rtpt_bind_plane is never reused.
  * RTPT_NO_FRAME_REUSE=1 in the environment of rtpt_create turns all of it off.
- * out: [0] frames whose K0 + K1 were not launched, [1] and [2] reserved for a cached reprojection of the final pass (0),
- * [3] plane tags invalidated. */
+ * out: [0] frames whose K0 + K1 were not launched, [1] and [2] reserved and always 0 (the cached reprojection of the final
+ * pass has counters of its own, rtpt_debug_reproj_info), [3] plane tags invalidated. */
 int rtpt_debug_reuse_info(rtpt_ctx* ctx, uint64_t out[4]);
+
+/* Reprojection reuse.  The pixel the final filter pass reprojects to is a function of the world-position plane, the id
+ * plane, LUT_PREV, projPrev * viewPrev and the frame size.  Frame reuse already knows when the first three hold the bytes
+ * of the frame before, so while they and the matrix rest the pass would compute the integers it computed a frame ago.  A
+ * final pass whose inputs equal those of the previous frame's final pass therefore also stores the pair, packed to 4 bytes
+ * per pixel (y << 16 | x, one sentinel for every pixel outside the frame, whose history reads 0 either way), and later
+ * final passes with the same inputs load it instead of reading the world position, gathering the LUT and reprojecting.
+ * The plane (4 bytes per stored pixel) is allocated at the first store; a camera that moves every frame never stores.
+ * Only the single-launch final pass of the LDS-staged kernel takes part (id-pair table or per-pixel normals, 1 <= k <= 16,
+ * frame at most 65535 x 65535); the direct kernel, the extension modes and a chain ending in the final pass reproject as
+ * before.  Everything that makes frame reuse compute a frame again (see above) also drops the stored pairs, as does any
+ * write to a LUT through rtpt_set_plane or a pointer from rtpt_plane_ptr; with RTPT_DEBUG_PREV_PIXEL enabled nothing is
+ * stored or loaded (that plane wants the raw integers).  Every plane, the ray count and the finished frame equal those
+ * of a context that reprojects every frame.  RTPT_NO_REPROJ_REUSE=1 in the environment of rtpt_create turns it off;
+ * RTPT_NO_FRAME_REUSE=1 does too.
+ * out: [0] final passes that stored, [1] final passes that loaded, [2] invalidations of the stored pairs, [3] bytes of
+ * the plane (0 until the first store). */
+int rtpt_debug_reproj_info(rtpt_ctx* ctx, uint64_t out[4]);
 
 /* ---- per-frame passes, one call per reference dispatch ----------------------------------- */
 

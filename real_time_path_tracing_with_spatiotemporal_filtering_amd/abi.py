@@ -114,7 +114,7 @@ SYMBOLS = [
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
-    "rtpt_debug_live_device_bytes", "rtpt_modulate",
+    "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
 ]
 
 _lib = None
@@ -178,6 +178,7 @@ def load() -> C.CDLL:
         "rtpt_scene_rebuild": [vp],
         "rtpt_debug_bvh_topology": [vp, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
+        "rtpt_debug_reproj_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_scene_set_instances": [vp, vp, u32],
         "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_live_device_bytes": [C.POINTER(C.c_uint64)],
@@ -376,6 +377,12 @@ class Context:
         out = (C.c_uint64 * 4)()
         _check(self._lib.rtpt_debug_reuse_info(self._h, C.byref(out)))
         return dict(zip(("frames_skipped", "reproj_stores", "reproj_loads", "tags_invalidated"), (int(v) for v in out)))
+
+    def reproj_info(self) -> dict:
+        """the final pass's cached reprojection as observed so far (rtpt_debug_reproj_info)"""
+        out = (C.c_uint64 * 4)()
+        _check(self._lib.rtpt_debug_reproj_info(self._h, C.byref(out)))
+        return dict(zip(("stores", "loads", "invalidations", "plane_bytes"), (int(v) for v in out)))
 
     def set_materials(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
         """per-triangle material indices + (Kd, Ke) rows; None returns to the reference's normal-keyed colours"""

@@ -255,6 +255,7 @@ static int alloc_planes(rtpt_ctx* c) {
   if (rc == RTPT_OK && !c->raycount.ptr) rc = alloc_buf(c->raycount, 8 * rt::kRayCounters);
   for (auto& b : c->path_queue) free_buf(b);  // sized per frame: re-created by the next rtpt_raytrace
   free_buf(c->normals);  // sized per frame: re-created by the next rtpt_gbuffer
+  free_buf(c->reproj);   // sized per frame: re-created by the next final pass that stores (reuse_invalidate below drops its tag)
   reuse_invalidate(c, nullptr);  // new, cleared planes
   c->normals_y0 = c->normals_y1 = 0;
   if (c->cfg.flags & RTPT_FLAG_EXT_VARIANCE) {
@@ -369,6 +370,7 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   if (const char* v = std::getenv("RTPT_LBVH_ORDER")) c->lbvh_by_height = !std::strcmp(v, "height");
   if (const char* v = std::getenv("RTPT_NO_TRACE_FUSION")) c->fuse_trace = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_NO_FRAME_REUSE")) c->frame_reuse = std::atoi(v) == 0;
+  if (const char* v = std::getenv("RTPT_NO_REPROJ_REUSE")) c->reproj_reuse = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_TRACE_POOL")) c->trace_pool = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_PT_WINDOW")) c->trace_window = static_cast<uint32_t>(std::max(0, std::atoi(v)));
   if (const char* v = std::getenv("RTPT_CHAIN_G1")) c->filter_policy.chain_g_pin = std::atoi(v);
@@ -552,11 +554,20 @@ int rtpt_enable_debug(rtpt_ctx* c, uint32_t mask) {
   return RTPT_OK;
 }
 
-// frame reuse, observed: [0] frames whose K0 + K1 were not launched, [1], [2] reserved (a cached reprojection of the final
-// pass: not built in, 0), [3] plane tags invalidated
+// frame reuse, observed: [0] frames whose K0 + K1 were not launched, [1], [2] reserved and 0 (the cached reprojection of the
+// final pass reports through rtpt_debug_reproj_info), [3] plane tags invalidated
 int rtpt_debug_reuse_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 4; i++) out[i] = c->reuse_info[i];
+  return RTPT_OK;
+}
+
+// reprojection reuse, observed: [0] final passes that stored, [1] final passes that loaded, [2] invalidations of the
+// plane's tag, [3] bytes of the plane
+int rtpt_debug_reproj_info(rtpt_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  for (int i = 0; i < 3; i++) out[i] = c->reproj_info[i];
+  out[3] = c->reproj.bytes;
   return RTPT_OK;
 }
 

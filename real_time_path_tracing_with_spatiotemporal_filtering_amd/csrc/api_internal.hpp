@@ -83,6 +83,15 @@ struct K1Key {
   int32_t y0, y1;
   uint64_t lut_version[2];            // of LUT and LUT_PREV, in that order
 };
+// Reprojection reuse: the pixel pair the final filter pass reprojects to (device_common.hpp: reproject_pixel) is a function
+// of the world-position plane and the id plane (both the output of the K0 call with key k0), the bytes of LUT_PREV, PVprev
+// and the frame size (in k0), over the rows the pass covers.
+struct ReprojKey {
+  K0Key k0;               // carried by tag_worldpos and by the tag of the id plane the pass reads
+  uint64_t lut_version;   // of the buffer that is LUT_PREV; never ~0 (injected content)
+  float PVprev[16];
+  int32_t y0, y1;         // rows of the final pass
+};
 template <class K>
 inline K new_key() {
   K k;
@@ -238,6 +247,16 @@ struct rtpt_ctx {
   PlaneTag<K0Key> tag_vis[2], tag_worldpos, tag_depth, tag_normals;
   PlaneTag<K1Key> tag_gradient;
   uint64_t reuse_info[4] = {0, 0, 0, 0};  // rtpt_debug_reuse_info
+  // Reprojection reuse (api_passes.hip: reproj_policy): a single-launch final pass of the plain comb kernel whose ReprojKey
+  // equals the previous frame's stores its reprojected pixels, packed to 4 bytes, into `reproj`; from then on, while the key
+  // holds, the pass loads them instead of reprojecting.  `reproj` is allocated at the first store.  A moving camera changes
+  // the key every frame and never stores.  RTPT_NO_REPROJ_REUSE=1 (read at rtpt_create) turns it off; so does
+  // RTPT_NO_FRAME_REUSE=1, without which no plane tag is ever valid.
+  bool reproj_reuse = true;
+  Buf reproj;
+  PlaneTag<ReprojKey> tag_reproj;       // what `reproj` holds
+  PlaneTag<ReprojKey> reproj_last;      // the key of the previous frame's final pass (valid: that pass was eligible)
+  uint64_t reproj_info[4] = {0, 0, 0, 0};  // rtpt_debug_reproj_info ([3] is read from `reproj`)
   // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (kernels.hip: k_pathtrace_pool): RTPT_TRACE_POOL
   // (read at rtpt_create); path_pool = the workgroups' slabs, allocated on first use
   bool trace_pool = false;

@@ -18,7 +18,15 @@ void reuse_invalidate(rtpt_ctx* c, const Buf* b) {
   kill(c->tag_normals, &c->normals);
   kill(c->tag_gradient, &c->gradient);
   // K1 reads both LUT buffers, and their version does not see a write through a pointer handed out
-  if (b == &c->scene.lut[0] || b == &c->scene.lut[1]) kill(c->tag_gradient, b);
+  const bool lut = b == &c->scene.lut[0] || b == &c->scene.lut[1];
+  if (lut) kill(c->tag_gradient, b);
+  // the cached reprojection was computed from the world positions, the ids and a LUT: it dies with any of them (its own
+  // counter: rtpt_debug_reproj_info), and the next final pass starts a new run of equal keys
+  if (!b || lut || b == &c->worldpos || b == &c->vis[0] || b == &c->vis[1]) {
+    if (c->tag_reproj.valid) c->reproj_info[2]++;
+    c->tag_reproj.valid = false;
+    c->reproj_last.valid = false;
+  }
 }
 }  // namespace rtpt_impl
 
@@ -460,6 +468,47 @@ int filter_validate(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_ubo* 
   return RTPT_OK;
 }
 
+// Reprojection reuse (api_internal.hpp: ReprojKey), for the single-launch final pass `a` of the plain comb kernel over rows
+// [y0, y1): sets a.reproj_in when the plane holds this pass's reprojected pixels, a.reproj_out when this pass is to store them
+// (its key equals the previous frame's final pass's; the plane is allocated here, at the first store), neither otherwise.
+// *stored: the caller tags the plane with *key once the launch is out.
+int reproj_policy(rtpt_ctx* c, rt::AtrousArgs& a, uint32_t y0, uint32_t y1, ReprojKey* key, bool* stored) {
+  *stored = false;
+  const PlaneTag<K0Key>& wp = c->tag_worldpos;
+  const uint64_t lut_version = c->scene.lut_version[c->lut_cur ^ 1];
+  const bool eligible = c->frame_reuse && c->reproj_reuse && !(c->debug_mask & RTPT_DEBUG_PREV_PIXEL) &&  // (that plane wants the raw integers)
+                        c->cfg.width <= 65535 && c->cfg.height <= 65535 && wp.valid && c->tag_vis[c->vis_cur].holds(wp.key) &&
+                        wp.key.y0 <= static_cast<int32_t>(y0) && wp.key.y1 >= static_cast<int32_t>(y1) && lut_version != ~0ull;
+  if (!eligible) {
+    c->reproj_last.valid = false;
+    return RTPT_OK;
+  }
+  ReprojKey k = new_key<ReprojKey>();
+  k.k0 = wp.key;
+  k.lut_version = lut_version;
+  std::memcpy(k.PVprev, a.PVprev, sizeof k.PVprev);
+  k.y0 = static_cast<int32_t>(y0);
+  k.y1 = static_cast<int32_t>(y1);
+  if (c->tag_reproj.holds(k) && c->reproj.ptr) {
+    a.reproj_in = static_cast<const uint32_t*>(c->reproj.ptr);
+    c->reproj_info[1]++;
+  } else if (c->reproj_last.holds(k)) {
+    if (c->reproj.bytes != c->pixels() * 4) {
+      int rc = alloc_buf(c->reproj, c->pixels() * 4);
+      if (rc) return rc;
+    }
+    if (c->tag_reproj.valid) c->reproj_info[2]++;
+    c->tag_reproj.valid = false;  // until the store is out
+    a.reproj_out = static_cast<uint32_t*>(c->reproj.ptr);
+    *key = k;
+    *stored = true;
+    c->reproj_info[0]++;
+  }
+  c->reproj_last.valid = true;
+  c->reproj_last.key = k;
+  return RTPT_OK;
+}
+
 // launch iteration f.pc.waveletIteration — or, with levels > 1, that iteration and the levels - 1 after it as one chain
 int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
   const rtpt_push_constants* pc = &f.pc;
@@ -593,6 +642,14 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
     c->present_fused_y0 = c->present_y0;
     c->present_fused_y1 = c->present_y1;
   }
+  // the other final-pass routes (direct, extension, chained) neither load nor store and leave the tag alone: it is keyed on
+  // the pass's inputs, not on who ran
+  ReprojKey reproj_key;
+  bool reproj_stored = false;
+  if (final_pass && levels == 1 && rt::atrous_final_plain_comb(a)) {
+    int rcr = reproj_policy(c, a, y0, y1, &reproj_key, &reproj_stored);
+    if (rcr) return rcr;
+  }
   {
     Timer tm(c, levels > 1 ? (final_pass ? RTPT_K_ATROUS_CHAIN_FINAL : RTPT_K_ATROUS_CHAIN) : (final_pass ? RTPT_K_ATROUS_FINAL : RTPT_K_ATROUS));
     if (levels > 1)
@@ -602,6 +659,10 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
   }
   int rc;
   if ((rc = launch_check("temporal_filter"))) return rc;
+  if (reproj_stored) {
+    c->tag_reproj.valid = true;
+    c->tag_reproj.key = reproj_key;
+  }
   if (levels > 1) {
     // point the roles at the buffers the separate passes would have left them in: the result sits in out_buf
     const int res_role = final_pass ? ROLE_IMAGE : ((k_last & 1) ? ROLE_FILTERED : ROLE_IMAGE);

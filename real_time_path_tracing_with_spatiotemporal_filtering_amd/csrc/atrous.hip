@@ -327,12 +327,50 @@ constexpr int kShThreads = 64 * kShWaves;
 // halo columns per segment, and the arithmetic of k_atrous_ext (h kept per tap, correctly-rounded final division), so
 // the two are bit-identical.  25 taps are 25 LDS reads here instead of 75 global loads per pixel.
 constexpr int kFinalWaves = 1;  // id-pair final pass: waves per SIMD to squeeze the registers for (A/B: 4 by itself)
-template <int CWp, bool FINAL, bool EXACT, bool NRM = false, int R = 1, bool EXTA = false, bool VAR = false>
+
+// The reprojected pixel of a final pass as one 4-byte cell (AtrousArgs::reproj_out / reproj_in): the only reader is history_at,
+// which returns 0 for every pixel outside [0, W) x [hist_y0, hist_y1), a subset of the frame — so everything outside the frame
+// (INT_MIN / INT_MAX / NaN landings included) is one sentinel.  W, H <= 65535 (the host's condition): x = 65535 is never inside.
+constexpr uint32_t kReprojOutside = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t reproj_pack(int ppx, int ppy, int W, int H) {
+  return (ppx >= 0 && ppx < W && ppy >= 0 && ppy < H) ? (static_cast<uint32_t>(ppy) << 16 | static_cast<uint32_t>(ppx)) : kReprojOutside;
+}
+__device__ __forceinline__ void reproj_unpack(uint32_t cell, int& ppx, int& ppy) {
+  ppx = static_cast<int>(cell & 0xFFFFu);
+  ppy = static_cast<int>(cell >> 16);
+}
+// Where the RLOAD variants issue their two loads (bits 0-1: id-pair, bits 2-3: per-pixel normals).  0: both behind the taps,
+// where the id-pair compute variant reprojects; 1: the packed cells right behind the publishing barrier and the history fetch
+// ahead of the taps; 2: the packed cells with the staging DMA, ahead of the barrier, and every history fetch of the wave
+// right behind it.
+// Measured at 4K, k = 5, in-process lines of one job (profiles/r12_reproj_reuse_ab.txt); the compute sibling ran 103-107 us
+// (id-pair) and 138 us (per-pixel normals) beside them:
+//   id-pair, compiled like its sibling (waves_per_eu 1: 73 VGPRs, 6 waves)   placement 0: 100.2-100.6   1: 104.6-104.8   2: 93.8-94.4
+//   id-pair, waves_per_eu 8 (62-64 VGPRs, no scratch; LDS admits 7 workgroups)                          1:  83.8-86.8   2: 83.2-86.8
+//   per-pixel normals (69-73 VGPRs; 6 waves either way: LDS admits 6 workgroups) 0: 107.5-107.6         1: 109.7-110.4  2: 108.0-108.2
+// The id-pair pass was never short of bytes: the ones it no longer reads bought 3 us until the registers the reprojection no longer needs
+// were turned into two more resident waves, which bought 20.  With those, where the 4-byte cell is fetched no longer
+// matters, so it stays behind the barrier (placement 1: no load of its own in front of the wait the other workgroups see).
+// The per-pixel-normal taps (x^128 per tap) hide the two dependent loads behind them by themselves: placement 0.
+#ifndef RTPT_REPROJ_LOAD_PLACE
+#define RTPT_REPROJ_LOAD_PLACE 1
+#endif
+#ifndef RTPT_REPROJ_LOAD_WAVES
+#define RTPT_REPROJ_LOAD_WAVES 8  // id-pair RLOAD instances: the waves-per-SIMD pin
+#endif
+
+// RLOAD (FINAL, plain family only): the reprojected pixel comes from a.reproj_in, written by an earlier frame's final pass
+// from the same world-position plane, id plane, LUT_PREV and PVprev (api_passes.hip: ReprojKey) — no world position, no LUT
+// gather, no id read in the NRM variant, none of reproject_pixel's arithmetic.
+template <int CWp, bool FINAL, bool EXACT, bool NRM = false, int R = 1, bool EXTA = false, bool VAR = false, bool RLOAD = false>
 __global__ __launch_bounds__(kShThreads)
 // the per-pixel-normal final pass sits at the edge of six waves per SIMD (79-81 VGPRs as the surrounding code changes;
 // 142-147 us with six waves, 169-176 us with five at 4K): pin it.  Every other instantiation keeps what it gets.
-__attribute__((amdgpu_waves_per_eu(FINAL && NRM && R == 1 && !EXTA && !VAR && !EXACT ? 6 : (FINAL && !NRM && R == 1 && !EXTA && !VAR && !EXACT ? kFinalWaves : 1))))
+__attribute__((amdgpu_waves_per_eu(FINAL && NRM && R == 1 && !EXTA && !VAR && !EXACT ? 6 : (FINAL && !NRM && R == 1 && !EXTA && !VAR && !EXACT ? (RLOAD ? RTPT_REPROJ_LOAD_WAVES : kFinalWaves) : 1))))
 void k_atrous_comb_sh(AtrousArgs a) {
+  static_assert(!RLOAD || (FINAL && R == 1 && !EXTA && !VAR), "the cached reprojection serves the plain final pass only");
+  constexpr int kLoadPlace = RLOAD ? ((RTPT_REPROJ_LOAD_PLACE >> (NRM ? 2 : 0)) & 3) : 0;
+  constexpr bool kLoadEarly = kLoadPlace != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 #if RTPT_TILE_TIMELINE
   SpanScope span_(FINAL ? 1u : 0u, false);
@@ -441,7 +479,7 @@ void k_atrous_comb_sh(AtrousArgs a) {
   // FINAL: the world positions of this wave's output pixels depend on nothing staged — fetch them now, in flight together
   // with the DMA and waited for by the same vmcnt(0)
   f3 wp_pre[kCombM * kShHalves];
-  if (FINAL && NRM) {
+  if (FINAL && NRM && !RLOAD) {
 #pragma unroll
     for (int mh = 0; mh < kCombM * kShHalves; mh++) {
       const int m = mh / kShHalves, hf = mh % kShHalves;
@@ -451,9 +489,34 @@ void k_atrous_comb_sh(AtrousArgs a) {
       if (x < W && y < a.g.y1) wp_pre[mh] = xyz(a.worldpos[static_cast<size_t>(y - a.g.row_base) * W + x]);
     }
   }
+  // RLOAD: the wave's packed cells, 4 bytes per output pixel — in flight with the DMA (placement 2) or issued as soon as
+  // nothing waits on this wave (placement 1)
+  uint32_t cell_pre[kCombM * kShHalves];
+  f3 hc_pre[kCombM * kShHalves];
+  auto load_cells = [&]() {
+#pragma unroll
+    for (int mh = 0; mh < kCombM * kShHalves; mh++) {
+      const int m = mh / kShHalves, hf = mh % kShHalves;
+      const int x = x0 + hf * 64 + lane;
+      const int y = yg + (wave * kCombM + m) * k;
+      cell_pre[mh] = kReprojOutside;
+      if (x < W && y < a.g.y1) cell_pre[mh] = a.reproj_in[static_cast<size_t>(y - a.g.row_base) * W + x];
+    }
+  };
+  if (kLoadPlace == 2) load_cells();
   // own DMA landed, then the barrier publishes every wave's rows to the block
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
+  if (kLoadPlace == 1) load_cells();
+  if (kLoadPlace == 2) {
+#pragma unroll
+    for (int mh = 0; mh < kCombM * kShHalves; mh++) {
+      int qx, qy;
+      reproj_unpack(cell_pre[mh], qx, qy);
+      hc_pre[mh] = f3{0.f, 0.f, 0.f};
+      if (a.frame > 0) hc_pre[mh] = history_at(qx, qy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
+    }
+  }
 
 #pragma unroll
   for (int mh = 0; mh < kCombM * kShHalves; mh++) {
@@ -468,16 +531,21 @@ void k_atrous_comb_sh(AtrousArgs a) {
     const size_t ip = static_cast<size_t>(y - a.g.row_base) * W + x;
     const float4 np4 = NRM ? nrm[cc] : make_float4(0.f, 0.f, 0.f, 0.f);
     const f3 np = xyz(np4);
-    const uint32_t idp = NRM ? (FINAL ? a.vis[ip] : 0u) : ids[cc];  // NRM: the id is only needed for the reprojection
+    const uint32_t idp = NRM ? (FINAL && !RLOAD ? a.vis[ip] : 0u) : ids[cc];  // NRM: the id is only needed for the reprojection
     const float* prow = pairw + idp * NP;
     const float wself = NRM ? np4.w : prow[idp];
     // FINAL: reproject first (:213-239) so that the history fetch is in flight under the taps' arithmetic
     int ppx = x, ppy = y;
     f3 hc{0.f, 0.f, 0.f};
-    if (FINAL && NRM) {
+    if (FINAL && NRM && !RLOAD) {
       reproject_pixel(W, H, a.PVprev, idp, wp_pre[mh], a.lut_prev, x, y, ppx, ppy);
       if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);  // :251,:253
     }
+    if (kLoadPlace == 1) {
+      reproj_unpack(cell_pre[mh], ppx, ppy);
+      if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
+    }
+    if (kLoadPlace == 2) hc = hc_pre[mh];
     f3 num{0.f, 0.f, 0.f};
     float den = 0.f, vsum = 0.f;
     const VarGuide vg = var_guide(a.sigma_l, cp, use_var, use_var ? (a.var_scale ? a.var_scale[ip] : varp[cc]) : 0.0f);
@@ -523,11 +591,18 @@ void k_atrous_comb_sh(AtrousArgs a) {
       __builtin_nontemporal_store(o4, reinterpret_cast<v4f_*>(a.out + ip));
       continue;
     }
-    if (!NRM) {
+    if (!NRM && !RLOAD) {
       reproject_pixel(W, H, a.PVprev, idp, xyz(a.worldpos[ip]), a.lut_prev, x, y, ppx, ppy);  // :213-239
       if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
     }
-    if (a.prev_pixel) a.prev_pixel[ip] = make_int2(ppx, ppy);
+    if (RLOAD && !kLoadEarly) {
+      reproj_unpack(a.reproj_in[ip], ppx, ppy);
+      if (a.frame > 0) hc = history_at(ppx, ppy, W, a.hist_y0, a.hist_y1, a.history, a.hist_row_base);
+    }
+    if (!RLOAD) {  // (the host never asks a loading pass for either: the raw integers are not in the cell)
+      if (a.prev_pixel) a.prev_pixel[ip] = make_int2(ppx, ppy);
+      if (!EXTA && a.reproj_out) a.reproj_out[ip] = reproj_pack(ppx, ppy, W, H);
+    }
     f3 blend = filtered;             // :258
     bool use_history = a.frame > 0;  // :251
     float alpha = a.alpha;
@@ -651,9 +726,11 @@ constexpr int comb_row(type_list<E...>, int need, bool nrm, int r, bool var) {
 }
 static_assert(comb_row(CombInsts{}, kCombW + 2 * 16, false, 1, false) != 0 && comb_row(CombInsts{}, kCombW + 2 * 16, true, 1, false) != 0,
               "launch_atrous() stages every stride up to 16");
-template <class I, class FIN, class EX>
-constexpr auto comb_kernel(I, FIN, EX) {
-  return &k_atrous_comb_sh<I::cw, FIN::value, EX::value, I::nrm, I::r, I::exta, I::var>;
+// RL: the final pass that loads the cached reprojection; only the FINAL instances of the plain family have one (for every
+// other entry RL names the instance without it)
+template <class I, class FIN, class EX, class RL = std::false_type>
+constexpr auto comb_kernel(I, FIN, EX, RL = {}) {
+  return &k_atrous_comb_sh<I::cw, FIN::value, EX::value, I::nrm, I::r, I::exta, I::var, RL::value && FIN::value && !I::exta>;
 }
 
 // Kernels that ask for more than 64 KiB of dynamic LDS need the attribute raised once per DEVICE (it is a
@@ -663,8 +740,8 @@ hipError_t prepare_device_atrous() {
   hipError_t e = hipSuccess;
   auto raise = [&](auto inst) {
     each_final_exact([&](auto fin, auto ex) {
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(comb_kernel(inst, fin, ex)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      for (const void* f : {reinterpret_cast<const void*>(comb_kernel(inst, fin, ex)), reinterpret_cast<const void*>(comb_kernel(inst, fin, ex, std::true_type{}))})
+        if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
   };
   visit_all(CombExtInsts{}, raise);
@@ -678,7 +755,9 @@ static bool launch_comb(List list, int cw, bool nrm, int r, bool var, bool final
     using I = decltype(inst);
     if (I::cw != cw || I::nrm != nrm || I::r != r || I::var != var) return false;
     with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
-      hipLaunchKernelGGL(comb_kernel(inst, fin, ex), grid, dim3(kBlockX, kShWaves), lds, s, a);
+      with_bool(final_pass && !I::exta && a.reproj_in, [&](auto rl) {
+        hipLaunchKernelGGL(comb_kernel(inst, fin, ex, rl), grid, dim3(kBlockX, kShWaves), lds, s, a);
+      });
     });
     return true;
   });
@@ -712,6 +791,13 @@ bool atrous_final_fuses_present(const AtrousArgs& a) {
 static uint32_t comb_blocks_per_xcd(uint32_t nlb, uint32_t slots_per_xcd) {
   const uint32_t items_xcd = (nlb + 7u) / 8u;
   return slots_per_xcd > items_xcd ? (items_xcd ? items_xcd : 1u) : (slots_per_xcd ? slots_per_xcd : 1u);
+}
+
+bool atrous_final_plain_comb(const AtrousArgs& a) {
+  const int np = static_cast<int>(a.n_tris) + 1;
+  const bool pair_mode = a.pair_tab && np <= kPairMax;
+  const bool nrm_mode = !pair_mode && a.normals != nullptr;
+  return !a.ext && !a.direct && (pair_mode || nrm_mode) && a.k >= 1 && a.k <= 16;
 }
 
 void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
@@ -757,7 +843,7 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
   }
   const bool pair_mode = a.pair_tab && np <= kPairMax;
   const bool nrm_mode = !pair_mode && a.normals != nullptr;
-  if (!a.direct && (pair_mode || nrm_mode) && a.k >= 1 && a.k <= 16) {
+  if (atrous_final_plain_comb(a)) {
     a.tiles_x = (a.g.W + kCombW - 1) / kCombW;
     const int nrows = a.g.y1 - a.g.y0;
     const int chunks = (nrows + kCombM * a.k - 1) / (kCombM * a.k);

@@ -193,6 +193,11 @@ struct AtrousArgs {
                                   // the centre pixel (k_var_prefilter of var_in); NULL: var_in's own value
   const float* var_in;            // RTPT_FLAG_EXT_VARIANCE: per-pixel luminance variance read by this iteration
   float* var_out;                 //                         ... and the filtered variance it writes
+  // final pass of the plain comb kernel only (atrous_final_plain_comb): the reprojected pixel of every output pixel, packed
+  // ppy << 16 | ppx, 0xFFFFFFFF when it lies outside the frame (history_at reads 0 there either way); indexed like every plane.
+  // reproj_out: the pass also stores it; reproj_in: the pass reads it INSTEAD of reprojecting (never both)
+  uint32_t* reproj_out;
+  const uint32_t* reproj_in;
 };
 
 // RTPT_FLAG_EXT_VARIANCE: temporal accumulation of the luminance moments before the first filter iteration
@@ -312,6 +317,9 @@ bool pathtrace_uses_pool(const PathtraceArgs& a);
 size_t pathtrace_pool_bytes(int W, int rows);
 void launch_atrous(const AtrousArgs& a, bool final_pass, hipStream_t s);
 bool atrous_final_fuses_present(const AtrousArgs& a);
+// true when a launch of `a` runs in the plain comb kernel (no extension mode, not forced direct, 1 <= k <= 16, id-pair table
+// or per-pixel normals): the only kernel whose final pass takes reproj_out / reproj_in
+bool atrous_final_plain_comb(const AtrousArgs& a);
 // `levels` consecutive iterations k, k+1, .. in one launch, intermediates in LDS (atrous_chain.hip): a.k = the first
 // stride, a.in / a.out = input of the first and output of the last iteration (distinct buffers), final_pass = the last
 // level is the frame's FINAL pass (reprojection + blend)
