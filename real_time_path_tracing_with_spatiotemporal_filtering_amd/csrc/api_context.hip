@@ -68,26 +68,37 @@ void free_buf(Buf& b) { b.release(); }
 
 Buf* plane_buf(rtpt_ctx* c, rtpt_plane which) {
   switch (which) {
-    case RTPT_PLANE_IMAGE: return &c->color[c->color_of_role[ROLE_IMAGE]];
-    case RTPT_PLANE_FILTERED: return &c->color[c->color_of_role[ROLE_FILTERED]];
-    case RTPT_PLANE_PREVIOUS: return &c->color[c->color_of_role[ROLE_PREVIOUS]];
+    case RTPT_PLANE_IMAGE: return &c->color[c->frame.color_of_role[ROLE_IMAGE]];
+    case RTPT_PLANE_FILTERED: return &c->color[c->frame.color_of_role[ROLE_FILTERED]];
+    case RTPT_PLANE_PREVIOUS: return &c->color[c->frame.color_of_role[ROLE_PREVIOUS]];
     case RTPT_PLANE_WORLDPOS: return &c->worldpos;
     case RTPT_PLANE_GRADIENT: return &c->gradient;
     case RTPT_PLANE_DEPTH: return &c->depth;
-    case RTPT_PLANE_VIS_ID: return &c->vis[c->vis_cur];
-    case RTPT_PLANE_PREV_VIS_ID: return &c->vis[c->vis_cur ^ 1];
+    case RTPT_PLANE_VIS_ID: return &c->vis[c->frame.vis_cur];
+    case RTPT_PLANE_PREV_VIS_ID: return &c->vis[c->frame.vis_cur ^ 1];
     case RTPT_PLANE_LUT: return &c->scene.lut[c->lut_cur];
     case RTPT_PLANE_LUT_PREV: return &c->scene.lut[c->lut_cur ^ 1];
     case RTPT_PLANE_PREV_PIXEL: return &c->prev_pixel;
     case RTPT_PLANE_RAYCOUNT: return &c->raycount;
     case RTPT_PLANE_HIT_ID: return &c->hit_id;
-    case RTPT_PLANE_MOMENTS: return &c->moments[c->moments_cur];
-    case RTPT_PLANE_MOMENTS_PREV: return &c->moments[c->moments_cur ^ 1];
-    case RTPT_PLANE_VARIANCE: return &c->variance[c->variance_last];
+    case RTPT_PLANE_MOMENTS: return &c->moments[c->frame.moments_cur];
+    case RTPT_PLANE_MOMENTS_PREV: return &c->moments[c->frame.moments_cur ^ 1];
+    case RTPT_PLANE_VARIANCE: return &c->variance[c->frame.variance_last];
     case RTPT_PLANE_ALBEDO: return &c->albedo;
     case RTPT_PLANE_SHADED: return &c->shaded;
     default: return nullptr;
   }
+}
+
+int color_index(const rtpt_ctx* c, const Buf* b) {
+  for (int i = 0; i < 3; i++)
+    if (b == &c->color[i]) return i;
+  return -1;
+}
+
+FinishedFrame finished_frame(rtpt_ctx* c) {
+  if (c->frame.image_alias) return {plane_buf(c, RTPT_PLANE_PREVIOUS), c->frame.hist};
+  return {plane_buf(c, RTPT_PLANE_IMAGE), c->frame.final};
 }
 
 size_t plane_size(const rtpt_ctx* c, rtpt_plane which) {
@@ -257,7 +268,6 @@ static int alloc_planes(rtpt_ctx* c) {
   free_buf(c->normals);  // sized per frame: re-created by the next rtpt_gbuffer
   free_buf(c->reproj);   // sized per frame: re-created by the next final pass that stores (reuse_invalidate below drops its tag)
   reuse_invalidate(c, nullptr);  // new, cleared planes
-  c->normals_y0 = c->normals_y1 = 0;
   if (c->cfg.flags & RTPT_FLAG_EXT_VARIANCE) {
     for (int i = 0; i < 2 && rc == RTPT_OK; i++) rc = alloc_buf(c->moments[i], px * 16);
     for (int i = 0; i < 2 && rc == RTPT_OK; i++) rc = alloc_buf(c->variance[i], px * 4);
@@ -265,8 +275,6 @@ static int alloc_planes(rtpt_ctx* c) {
       (void)hipMemsetAsync(c->moments[i].ptr, 0, px * 16, c->stream);
       (void)hipMemsetAsync(c->variance[i].ptr, 0, px * 4, c->stream);
     }
-    c->moments_cur = 0;
-    c->variance_last = 0;
     if (rc == RTPT_OK && (c->cfg.flags & RTPT_FLAG_EXT_SVGF_VARIANCE)) rc = alloc_buf(c->var_scale, px * 4);
   }
   if (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) {
@@ -289,20 +297,10 @@ static int alloc_planes(rtpt_ctx* c) {
   if (c->prev_pixel.ptr) (void)hipMemsetAsync(c->prev_pixel.ptr, 0, px * 8, c->stream);
   hipError_t e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("initial clear: ") + hipGetErrorString(e));
-  for (int i = 0; i < 3; i++) {
-    c->color_of_role[i] = i;
-    c->alpha_depth[i] = false;
-  }
-  c->vis_cur = 0;
-  c->final_swapped = false;
-  c->image_alias = false;
-  c->hist_y0 = c->hist_y1 = 0;
-  c->final_y0 = c->final_y1 = 0;
-  c->guides_y0 = c->guides_y1 = 0;
-  c->ext_history = nullptr;
-  c->ext_prev_vis = c->ext_moments = nullptr;
-  c->count_y0 = static_cast<int>(c->cfg.row_begin);
-  c->count_y1 = static_cast<int>(c->cfg.row_end);
+  // (without RTPT_FLAG_EXT_VARIANCE the moment planes were not reallocated above: one a caller bound keeps its place)
+  const int moments_cur = (c->cfg.flags & RTPT_FLAG_EXT_VARIANCE) ? 0 : c->frame.moments_cur;
+  c->frame = FrameState(c->stored_rows());
+  c->frame.moments_cur = moments_cur;
   return RTPT_OK;
 }
 
@@ -334,7 +332,6 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   if (!c) return fail(RTPT_E_NOMEM, "host allocation failed");
   c->cfg = *cfg;
   c->device = dev;
-  for (int i = 0; i < 3; i++) c->color_of_role[i] = i;
   hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete c;
@@ -353,8 +350,6 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
       return fail(RTPT_E_DEVICE, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
     }
   }
-  c->count_y0 = static_cast<int>(cfg->row_begin);
-  c->count_y1 = static_cast<int>(cfg->row_end);
   // tuning knobs for A/B runs on the box (never needed for correctness: every setting computes the same pixels)
   if (const char* v = std::getenv("RTPT_NO_TRI_PAIRS")) c->no_pairing = std::atoi(v) != 0;
   if (const char* v = std::getenv("RTPT_HOST_REFIT")) c->host_refit = std::atoi(v) != 0;
@@ -430,7 +425,7 @@ int rtpt_resize(rtpt_ctx* c, uint32_t width, uint32_t height, uint32_t row_begin
   c->cfg.height = height;
   c->cfg.row_begin = row_begin;
   c->cfg.row_end = row_end;
-  c->present_dst = c->present_fused_dst = nullptr;  // a swapchain image registered for the old size is not this size's
+  c->present_dst = c->frame.present_fused_dst = nullptr;  // a swapchain image registered for the old size is not this size's
   int rc = alloc_planes(c);
   if (rc != RTPT_OK) {  // leave a usable context behind if the old size still fits
     c->cfg = old;
@@ -485,8 +480,7 @@ int rtpt_bind_plane(rtpt_ctx* c, rtpt_plane which, void* device_ptr, size_t byte
   b->ptr = device_ptr;
   b->bytes = bytes;
   b->owned = false;
-  for (int i = 0; i < 3; i++)
-    if (b == &c->color[i]) c->alpha_depth[i] = false;
+  if (const int i = color_index(c, b); i >= 0) c->frame.alpha_depth[i] = false;
   return RTPT_OK;
 }
 
@@ -494,26 +488,24 @@ int rtpt_set_external_history(rtpt_ctx* c, const void* device_ptr, uint32_t row_
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   if (device_ptr && (row_begin >= row_end || row_end > c->cfg.height)) return fail(RTPT_E_INVALID, "bad history row range");
   if (device_ptr && (reinterpret_cast<uintptr_t>(device_ptr) & 15u)) return fail(RTPT_E_INVALID, "history buffer must be 16-byte aligned");
-  c->ext_history = device_ptr;
-  c->ext_hist_y0 = static_cast<int>(row_begin);
-  c->ext_hist_y1 = static_cast<int>(row_end);
+  c->frame.ext_history = device_ptr;
+  c->frame.ext_hist = Rows(row_begin, row_end);
   return RTPT_OK;
 }
 
 int rtpt_set_external_guides(rtpt_ctx* c, const void* prev_vis, const void* moments_prev, uint32_t row_begin, uint32_t row_end) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   if (!prev_vis && !moments_prev) {
-    c->ext_prev_vis = c->ext_moments = nullptr;
+    c->frame.ext_prev_vis = c->frame.ext_moments = nullptr;
     return RTPT_OK;
   }
   if (!prev_vis) return fail(RTPT_E_INVALID, "the previous id plane is needed whenever guides are registered");
   if (row_begin >= row_end || row_end > c->cfg.height) return fail(RTPT_E_INVALID, "bad guide row range");
   if ((reinterpret_cast<uintptr_t>(prev_vis) & 3u) || (reinterpret_cast<uintptr_t>(moments_prev) & 15u))
     return fail(RTPT_E_INVALID, "guide buffers must be 4- / 16-byte aligned");
-  c->ext_prev_vis = prev_vis;
-  c->ext_moments = moments_prev;
-  c->ext_guides_y0 = static_cast<int>(row_begin);
-  c->ext_guides_y1 = static_cast<int>(row_end);
+  c->frame.ext_prev_vis = prev_vis;
+  c->frame.ext_moments = moments_prev;
+  c->frame.ext_guides = Rows(row_begin, row_end);
   return RTPT_OK;
 }
 
@@ -595,7 +587,7 @@ int rtpt_sync(rtpt_ctx* c) {
 int rtpt_readback(rtpt_ctx* c, rtpt_plane which, void* dst, size_t bytes) {
   if (!c || !dst) return fail(RTPT_E_INVALID, "NULL argument");
   FLUSH_FILTER(c);
-  Buf* b = plane_buf(c, (which == RTPT_PLANE_IMAGE && c->image_alias) ? RTPT_PLANE_PREVIOUS : which);
+  Buf* b = which == RTPT_PLANE_IMAGE ? finished_frame(c).buf : plane_buf(c, which);
   if (!b) return fail(RTPT_E_INVALID, "unknown plane");
   if (!b->ptr) return fail(RTPT_E_INVALID, "plane not allocated (scene not uploaded / debug plane not enabled)");
   const size_t need = plane_size(c, which);
@@ -612,12 +604,11 @@ int rtpt_readback(rtpt_ctx* c, rtpt_plane which, void* dst, size_t bytes) {
   }
   HIP_TRY(hipMemcpyAsync(dst, b->ptr, need, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 3; i++)
-    if (b == &c->color[i] && c->alpha_depth[i]) {
-      // the reference's colour images have alpha 0; internally alpha carries depth between passes
-      float* f = static_cast<float*>(dst);
-      for (size_t px = 0, n = need / 16; px < n; px++) f[4 * px + 3] = 0.0f;
-    }
+  if (const int i = color_index(c, b); i >= 0 && c->frame.alpha_depth[i]) {
+    // the reference's colour images have alpha 0; internally alpha carries depth between passes
+    float* f = static_cast<float*>(dst);
+    for (size_t px = 0, n = need / 16; px < n; px++) f[4 * px + 3] = 0.0f;
+  }
   return RTPT_OK;
 }
 
@@ -633,22 +624,15 @@ int rtpt_set_plane(rtpt_ctx* c, rtpt_plane which, const void* src, size_t bytes)
   reuse_invalidate(c, b);
   HIP_TRY(hipMemcpyAsync(b->ptr, src, need, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 3; i++)
-    if (b == &c->color[i]) c->alpha_depth[i] = false;
-  if (which == RTPT_PLANE_PREVIOUS) {
-    c->hist_y0 = static_cast<int>(c->cfg.row_begin);
-    c->hist_y1 = static_cast<int>(c->cfg.row_end);
-  }
-  if (which == RTPT_PLANE_PREV_VIS_ID || which == RTPT_PLANE_MOMENTS_PREV) {
-    c->guides_y0 = static_cast<int>(c->cfg.row_begin);
-    c->guides_y1 = static_cast<int>(c->cfg.row_end);
-  }
+  if (const int i = color_index(c, b); i >= 0) c->frame.alpha_depth[i] = false;
+  if (which == RTPT_PLANE_PREVIOUS) c->frame.hist = c->stored_rows();
+  if (which == RTPT_PLANE_PREV_VIS_ID || which == RTPT_PLANE_MOMENTS_PREV) c->frame.guides = c->stored_rows();
   if (which == RTPT_PLANE_LUT_PREV) {
     c->scene.lut_prev_valid = true;
     c->scene.lut_version[c->lut_cur ^ 1] = ~0ull;  // injected content: rebuild when it becomes current
   }
   if (which == RTPT_PLANE_LUT) c->scene.lut_version[c->lut_cur] = ~0ull;
-  if (which == RTPT_PLANE_VIS_ID) c->normals_y0 = c->normals_y1 = 0;  // the normal plane no longer matches the ids
+  if (which == RTPT_PLANE_VIS_ID) c->frame.normals = Rows();  // the normal plane no longer matches the ids
   return RTPT_OK;
 }
 
@@ -662,8 +646,7 @@ int rtpt_reset_counters(rtpt_ctx* c) {
 int rtpt_set_count_rows(rtpt_ctx* c, uint32_t y0, uint32_t y1) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   if (y0 > y1) return fail(RTPT_E_INVALID, "y0 > y1");
-  c->count_y0 = static_cast<int>(y0);
-  c->count_y1 = static_cast<int>(y1);
+  c->frame.count = Rows(y0, y1);
   return RTPT_OK;
 }
 

@@ -105,6 +105,39 @@ struct PlaneTag {  // what a plane the context owns holds: the output of the pas
   bool holds(const K& k) const { return valid && std::memcmp(&key, &k, sizeof k) == 0; }
 };
 
+struct Rows {  // frame rows [y0, y1)
+  int y0, y1;
+  Rows(int64_t a = 0, int64_t b = 0) : y0(static_cast<int>(a)), y1(static_cast<int>(b)) {}
+  bool covers(int64_t a, int64_t b) const { return y0 <= a && y1 >= b; }
+  void extend(int64_t a, int64_t b) { *this = Rows(std::min<int64_t>(y0, a), std::max<int64_t>(y1, b)); }
+};
+
+// The frames rendered so far at this size: which buffer plays which part and which rows of it mean something.  One value:
+// alloc_planes replaces it whole, so a member added here is reset by rtpt_resize without being listed anywhere.
+struct FrameState {
+  int color_of_role[3] = {0, 1, 2};             // role -> physical index of rtpt_ctx::color
+  bool alpha_depth[3] = {false, false, false};  // physical buffer carries depth in alpha ("rgbd")
+  int vis_cur = 0;        // vis[vis_cur] = VIS_ID, the other PREV_VIS_ID
+  int moments_cur = 0;    // moments[moments_cur] is written this frame, the other one is the history
+  int variance_last = 0;  // variance[] buffer holding the newest values
+  bool final_swapped = false;  // the final filter pass already rotated IMAGE <-> FILTERED this frame
+  bool image_alias = false;    // between rtpt_end_frame and the next rtpt_raytrace IMAGE reads as PREVIOUS
+  Rows final;    // of IMAGE the frame's last filter iteration wrote
+  Rows hist;     // of PREVIOUS holding a valid previous frame
+  Rows guides;   // of the context's own previous id / moment planes that hold a previous frame
+  Rows normals;  // of rtpt_ctx::normals that match VIS_ID ...
+  uint64_t normals_frame = ~0ull;  // ... in this frame (frames_ended)
+  const void* ext_history = nullptr;  // rtpt_set_external_history
+  Rows ext_hist;
+  const void* ext_prev_vis = nullptr;  // rtpt_set_external_guides: previous frame's ids / moments gathered across strips
+  const void* ext_moments = nullptr;
+  Rows ext_guides;
+  void* present_fused_dst = nullptr;  // what the last final pass wrote of rtpt_ctx::present_dst: rtpt_present skips its launch
+  Rows present_fused;
+  Rows count;  // counted into RAYCOUNT: the stored rows until rtpt_set_count_rows
+  explicit FrameState(Rows stored = Rows()) : count(stored) {}
+};
+
 // The acceleration structure over Scene::tris.  One value: rtpt_scene_rebuild swaps a whole Tree in (api_scene.hip).
 struct Tree {
   Buf nodes, leaf_order;
@@ -165,11 +198,8 @@ struct rtpt_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
 
-  Buf color[3];          // physical RGBA32F buffers
-  int color_of_role[3];  // role -> physical index
-  bool alpha_depth[3] = {false, false, false};  // physical buffer carries depth in alpha ("rgbd")
+  Buf color[3];  // physical RGBA32F buffers (FrameState::color_of_role)
   Buf vis[2];
-  int vis_cur = 0;  // vis[vis_cur] = VIS_ID, the other PREV_VIS_ID
   int lut_cur = 0;  // scene.lut[lut_cur] = LUT, the other LUT_PREV
   Buf worldpos, gradient, depth, prev_pixel, hit_id, raycount;
   Buf moments[2], variance[2];  // RTPT_FLAG_EXT_VARIANCE
@@ -177,16 +207,10 @@ struct rtpt_ctx {
   Buf albedo, shaded;           // RTPT_FLAG_EXT_DEMODULATE: the first hit's albedo (rtpt_raytrace) and the frame times it (rtpt_modulate)
   Buf path_queue[2], path_queue_count;  // long paths: survivors handed from one k_pathtrace launch to the next
   Buf normals;                  // per-pixel normal plane for the LDS-staged filter of scenes without an id-pair table
-  int normals_y0 = 0, normals_y1 = 0;  // rows for which it matches VIS_ID
-  uint64_t normals_frame = ~0ull;      // frame (frames_ended) those rows belong to
-  int moments_cur = 0;          // moments[moments_cur] is written this frame, the other one is the history
-  int variance_last = 0;        // variance[] buffer holding the newest values
-  // rtpt_present_target: the swapchain image rows the NEXT final pass also writes (fused blit); present_fused_* describe
-  // what the last final pass actually wrote, so that rtpt_present can skip its own launch
+  FrameState frame;             // reset by alloc_planes (rtpt_create, rtpt_resize); everything else here survives a resize
+  // rtpt_present_target: the swapchain image rows the NEXT final pass also writes (fused blit)
   void* present_dst = nullptr;
-  int present_y0 = 0, present_y1 = 0;
-  void* present_fused_dst = nullptr;
-  int present_fused_y0 = 0, present_fused_y1 = 0;
+  Rows present_rows;
   Buf ray_tab;  // K0: view-space ray direction per column / per row, for the projection and size below
   float ray_tab_p00 = 0.f, ray_tab_p11 = 0.f;
   uint32_t ray_tab_w = 0, ray_tab_h = 0;
@@ -215,21 +239,9 @@ struct rtpt_ctx {
   int xf_stage_cur = 0;
   uint64_t upload_info[4] = {0, 0, 0, 0};  // rtpt_debug_upload_info
 
-  // frame state
-  bool tables_valid = false;     // normal / id-pair tables match the scene
-  bool final_swapped = false;    // the final filter pass already rotated IMAGE <-> FILTERED this frame
-  bool image_alias = false;      // between rtpt_end_frame and the next rtpt_raytrace IMAGE reads as PREVIOUS
-  int hist_y0 = 0, hist_y1 = 0;  // rows of PREVIOUS holding a valid previous frame
-  int final_y0 = 0, final_y1 = 0;
+  bool tables_valid = false;  // normal / id-pair tables match the scene
   uint32_t debug_mask = 0;
-  const void* ext_history = nullptr;  // rtpt_set_external_history
-  const void* ext_prev_vis = nullptr; // rtpt_set_external_guides: previous frame's ids / moments gathered across strips
-  const void* ext_moments = nullptr;
-  int ext_guides_y0 = 0, ext_guides_y1 = 0;
-  int guides_y0 = 0, guides_y1 = 0;   // rows of the context's own previous id / moment planes that hold a previous frame
-  hipEvent_t handoff_event = nullptr; // rtpt_stream_wait(x, this): recorded on this context's stream
-  int ext_hist_y0 = 0, ext_hist_y1 = 0;
-  int count_y0 = 0, count_y1 = 0;  // rows counted into RAYCOUNT
+  hipEvent_t handoff_event = nullptr;  // rtpt_stream_wait(x, this): recorded on this context's stream
 
   // K0 recorded by rtpt_gbuffer: launched together with K1 when rtpt_temporal_gradient follows at once, alone otherwise
   rt::GbufferArgs pending_gb{};
@@ -289,6 +301,7 @@ struct rtpt_ctx {
   std::vector<hipEvent_t> event_pool;
 
   uint32_t rows() const { return cfg.row_end - cfg.row_begin; }
+  Rows stored_rows() const { return Rows(cfg.row_begin, cfg.row_end); }
   bool width_fits_i16() const { return cfg.width < 30000 && cfg.height < 30000; }
   size_t pixels() const { return static_cast<size_t>(rows()) * cfg.width; }
 };
@@ -321,6 +334,14 @@ bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], c
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);
 int launch_check(const char* what);
+int color_index(const rtpt_ctx* c, const Buf* b);  // of c->color, -1 for any other buffer
+// The finished frame: IMAGE until rtpt_end_frame, PREVIOUS after it (the reference blits before it copies, the pixels are the
+// same); only the rows the last final pass wrote hold it
+struct FinishedFrame {
+  Buf* buf;
+  Rows rows;
+};
+FinishedFrame finished_frame(rtpt_ctx* c);
 int apply_model(rtpt_ctx* c, const float* model);  // api_scene.hip
 void build_tables(rtpt_ctx* c);                      // api_passes.hip: k_lut + k_pair_weights for the posed scene
 int ensure_tables(rtpt_ctx* c);                      // api_passes.hip: build_tables + the D3 LUTprevious, when the tables are stale

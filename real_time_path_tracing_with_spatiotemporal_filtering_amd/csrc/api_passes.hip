@@ -50,25 +50,32 @@ void build_tables(rtpt_ctx* c) {
   c->tables_valid = true;
 }
 
+// D3: visibilityLUTprevious is read during frame 0 (K1, the final filter pass) before anything wrote it; define it as LUT
+static int seed_lut_prev(rtpt_ctx* c) {
+  if (c->scene.lut_prev_valid) return RTPT_OK;
+  HIP_TRY(hipMemcpyAsync(c->scene.lut[c->lut_cur ^ 1].ptr, c->scene.lut[c->lut_cur].ptr, c->scene.lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
+                         c->stream));
+  c->scene.lut_prev_valid = true;
+  c->scene.lut_version[c->lut_cur ^ 1] = c->scene.model_version;
+  return RTPT_OK;
+}
+
+// the tables and LUT of the current pose (when `stale`), then the LUTprevious: rtpt_gbuffer's and ensure_tables's common path
+static int refresh_tables(rtpt_ctx* c, bool stale) {
+  if (stale) build_tables(c);
+  int rc = launch_check("lut");
+  return rc ? rc : seed_lut_prev(c);
+}
+
 // A pass that reads the per-id tables (normals, areas, id-pair weights) without rtpt_gbuffer in front of it — rtpt_temporal_filter
 // or the stand-alone rtpt_temporal_gradient as the first pass after rtpt_scene_upload or rtpt_scene_set_instances (a changed
 // ubo.model arrives only with rtpt_gbuffer, which rebuilds them in the same call) — builds them here, with the LUT of the
-// current pose; a LUTprevious nothing wrote yet is defined as that LUT (D3, as in rtpt_gbuffer: K1 and the final filter pass
-// read it)
+// current pose
 int ensure_tables(rtpt_ctx* c) {
   if (c->tables_valid) return RTPT_OK;
   FLUSH_FILTER(c);
   HIP_TRY(hipSetDevice(c->device));
-  build_tables(c);
-  int rc = launch_check("lut");
-  if (rc) return rc;
-  if (!c->scene.lut_prev_valid) {
-    HIP_TRY(hipMemcpyAsync(c->scene.lut[c->lut_cur ^ 1].ptr, c->scene.lut[c->lut_cur].ptr, c->scene.lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
-                           c->stream));
-    c->scene.lut_prev_valid = true;
-    c->scene.lut_version[c->lut_cur ^ 1] = c->scene.model_version;
-  }
-  return RTPT_OK;
+  return refresh_tables(c, true);
 }
 }  // namespace rtpt_impl
 
@@ -126,6 +133,46 @@ bool reuse_covers(const rtpt_ctx* c) {
   return !a.normals || c->tag_normals.holds(k.k0);
 }
 
+// the five push-constant vectors K1 reads, to where GbufferArgs (g_*), GradientArgs or K1Key keep them
+void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, float* light_prev, float* color, float* color_prev) {
+  const float* src[5] = {pc->cameraPos, pc->lightPos, pc->lightPosPrev, pc->currentCameraColor, pc->previousCameraColor};
+  float* dst[5] = {cam, light, light_prev, color, color_prev};
+  for (int i = 0; i < 5; i++) std::memcpy(dst[i], src[i], 3 * sizeof(float));
+}
+
+// K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (rtpt_ctx::trace_pool): the workgroups' slabs
+int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
+  a.pool_slab = nullptr;
+  if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo)) return RTPT_OK;  // (the pool form stores no albedo)
+  const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
+  if (need && c->path_pool.bytes < need)
+    if (int rc = alloc_buf(c->path_pool, need)) return rc;
+  a.pool_slab = need ? c->path_pool.ptr : nullptr;
+  return RTPT_OK;
+}
+
+// the queues that hand the survivors of the first `window` segments to the queue kernels.  A region holds the survivors of
+// ceil(workgroups / kPathQueues) workgroups of 256 paths (kernels.hip); the second buffer is only needed when a third segment
+// window exists
+int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
+  a.queue[0] = a.queue[1] = nullptr;
+  a.queue_count = nullptr;
+  a.queue_region = 0;
+  if (!(a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS))) return RTPT_OK;
+  const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
+  const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
+  const size_t cap = region * rt::kPathQueues;
+  int rc;
+  if (!c->path_queue_count.ptr && (rc = alloc_buf(c->path_queue_count, 2 * rt::kPathQueues * sizeof(uint32_t)))) return rc;
+  if (!c->path_queue[0].ptr && (rc = alloc_buf(c->path_queue[0], cap * 48))) return rc;
+  if (a.max_segments > 2u * window && !c->path_queue[1].ptr && (rc = alloc_buf(c->path_queue[1], cap * 48))) return rc;
+  a.queue[0] = c->path_queue[0].ptr;
+  a.queue[1] = c->path_queue[1].ptr;
+  a.queue_count = static_cast<uint32_t*>(c->path_queue_count.ptr);
+  a.queue_region = static_cast<uint32_t>(region);
+  return RTPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -153,15 +200,7 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   // The LUT is a function of the posed scene: the geometry stage's per-frame rewrite (visibility.geom.glsl:57-59)
   // produces the same bytes every frame while the model rests, so only a buffer that does not hold the current
   // pose yet is rebuilt (after rtpt_scene_upload / a model change / rtpt_set_plane).
-  if (c->scene.lut_version[c->lut_cur] != c->scene.model_version || !c->tables_valid) build_tables(c);
-  if ((rc = launch_check("lut"))) return rc;
-  if (!c->scene.lut_prev_valid) {
-    // D3: visibilityLUTprevious is read during frame 0 before anything wrote it; define it as LUT
-    HIP_TRY(hipMemcpyAsync(c->scene.lut[c->lut_cur ^ 1].ptr, c->scene.lut[c->lut_cur].ptr, c->scene.lut[c->lut_cur].bytes, hipMemcpyDeviceToDevice,
-                           c->stream));
-    c->scene.lut_prev_valid = true;
-    c->scene.lut_version[c->lut_cur ^ 1] = c->scene.model_version;
-  }
+  if ((rc = refresh_tables(c, c->scene.lut_version[c->lut_cur] != c->scene.model_version || !c->tables_valid))) return rc;
   rt::GbufferArgs a;
   a.g = geom(c, y0, y1);
   if ((rc = ensure_stack_spill(c, frame_blocks(c)))) return rc;
@@ -201,7 +240,7 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
     const double rx[3] = {d0[0], d1[0], d2[0]}, ry[3] = {d0[1], d1[1], d2[1]}, rz[3] = {d0[2], d1[2], d2[2]};
     a.cull = (!c->scene.use_bvh && c->width_fits_i16() && screen_bounds(c, org, rx, ry, rz, a.p00, a.p11, 0.0, a.bounds)) ? 1 : 0;
   }
-  a.vis = static_cast<uint32_t*>(c->vis[c->vis_cur].ptr);
+  a.vis = static_cast<uint32_t*>(c->vis[c->frame.vis_cur].ptr);
   a.worldpos = static_cast<float4*>(c->worldpos.ptr);
   a.depth = static_cast<float*>(c->depth.ptr);
   a.normals = nullptr;
@@ -211,18 +250,14 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
     if (!c->normals.ptr) {
       int rc2 = alloc_buf(c->normals, c->pixels() * 16);
       if (rc2) return rc2;
-      c->normals_y0 = c->normals_y1 = 0;
+      c->frame.normals = Rows();
       reuse_invalidate(c, &c->normals);
     }
     a.normals = static_cast<float4*>(c->normals.ptr);
     // rows written so far this frame (strips call the pass once per range; a new frame starts a new range)
-    if (c->normals_y1 == static_cast<int>(y0) && c->normals_frame == c->frames_ended)
-      c->normals_y1 = static_cast<int>(y1);
-    else {
-      c->normals_y0 = static_cast<int>(y0);
-      c->normals_y1 = static_cast<int>(y1);
-    }
-    c->normals_frame = c->frames_ended;
+    const bool continues = c->frame.normals.y1 == static_cast<int>(y0) && c->frame.normals_frame == c->frames_ended;
+    c->frame.normals = Rows(continues ? c->frame.normals.y0 : static_cast<int>(y0), y1);
+    c->frame.normals_frame = c->frames_ended;
   }
   a.grad_on = 0;
   a.grad_y0 = a.grad_y1 = 0;
@@ -282,28 +317,16 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
     g.grad_on = 1;
     g.grad_y0 = static_cast<int32_t>(y0);
     g.grad_y1 = static_cast<int32_t>(y1);
-    for (int i = 0; i < 3; i++) {
-      g.g_cam[i] = pc->cameraPos[i];
-      g.g_light[i] = pc->lightPos[i];
-      g.g_light_prev[i] = pc->lightPosPrev[i];
-      g.g_color[i] = pc->currentCameraColor[i];
-      g.g_color_prev[i] = pc->previousCameraColor[i];
-    }
+    gradient_inputs(pc, g.g_cam, g.g_light, g.g_light_prev, g.g_color, g.g_color_prev);
     g.lut = static_cast<const float4*>(c->scene.lut[c->lut_cur].ptr);
     g.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
     g.grad = static_cast<float4*>(c->gradient.ptr);
-    {
-      K1Key& k = c->pending_key;
-      std::memcpy(k.cam, g.g_cam, sizeof k.cam);
-      std::memcpy(k.light, g.g_light, sizeof k.light);
-      std::memcpy(k.light_prev, g.g_light_prev, sizeof k.light_prev);
-      std::memcpy(k.color, g.g_color, sizeof k.color);
-      std::memcpy(k.color_prev, g.g_color_prev, sizeof k.color_prev);
-      k.y0 = g.grad_y0;
-      k.y1 = g.grad_y1;
-      k.lut_version[0] = c->scene.lut_version[c->lut_cur];
-      k.lut_version[1] = c->scene.lut_version[c->lut_cur ^ 1];
-    }
+    K1Key& k = c->pending_key;
+    gradient_inputs(pc, k.cam, k.light, k.light_prev, k.color, k.color_prev);
+    k.y0 = g.grad_y0;
+    k.y1 = g.grad_y1;
+    k.lut_version[0] = c->scene.lut_version[c->lut_cur];
+    k.lut_version[1] = c->scene.lut_version[c->lut_cur ^ 1];
     int rcq = filter_flush(c, false);
     if (rcq) return rcq;
     // stays recorded: rtpt_raytrace normally follows at once (main.cpp:1107) and takes both passes into its launch; any other
@@ -315,14 +338,8 @@ int rtpt_temporal_gradient(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t 
   if ((rc = ensure_tables(c))) return rc;  // K1 first after an upload or moved instances: the tables and LUTs it reads
   rt::GradientArgs a;
   a.g = geom(c, y0, y1);
-  for (int i = 0; i < 3; i++) {
-    a.cam[i] = pc->cameraPos[i];
-    a.light[i] = pc->lightPos[i];
-    a.light_prev[i] = pc->lightPosPrev[i];
-    a.color[i] = pc->currentCameraColor[i];
-    a.color_prev[i] = pc->previousCameraColor[i];
-  }
-  a.vis = static_cast<const uint32_t*>(c->vis[c->vis_cur].ptr);
+  gradient_inputs(pc, a.cam, a.light, a.light_prev, a.color, a.color_prev);
+  a.vis = static_cast<const uint32_t*>(c->vis[c->frame.vis_cur].ptr);
   a.worldpos = static_cast<const float4*>(c->worldpos.ptr);
   a.lut = static_cast<const float4*>(c->scene.lut[c->lut_cur].ptr);
   a.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
@@ -363,41 +380,19 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   a.jitter = c->cfg.pixel_jitter;
   a.ray_offset = c->cfg.ray_offset;
   a.tmax = c->cfg.ray_tmax;
-  a.image = static_cast<float4*>(c->color[c->color_of_role[ROLE_IMAGE]].ptr);
+  a.image = static_cast<float4*>(c->color[c->frame.color_of_role[ROLE_IMAGE]].ptr);
   a.depth = static_cast<const float*>(c->depth.ptr);
-  c->alpha_depth[c->color_of_role[ROLE_IMAGE]] = true;
+  c->frame.alpha_depth[c->frame.color_of_role[ROLE_IMAGE]] = true;
   a.hit_id = (c->debug_mask & RTPT_DEBUG_HIT_ID) ? static_cast<uint32_t*>(c->hit_id.ptr) : nullptr;
   a.albedo = (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) ? static_cast<float4*>(c->albedo.ptr) : nullptr;
   a.raycount = static_cast<unsigned long long*>(c->raycount.ptr);
-  a.count_y0 = c->count_y0;
-  a.count_y1 = c->count_y1;
+  a.count_y0 = c->frame.count.y0;
+  a.count_y1 = c->frame.count.y1;
   a.compact = (c->cfg.flags & RTPT_FLAG_NO_PATH_COMPACTION) ? 0 : 1;
   a.n_cu = c->n_cu;
-  a.queue[0] = a.queue[1] = nullptr;
-  a.queue_count = nullptr;
-  a.queue_region = 0;
-  a.pool_slab = nullptr;
-  if (c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo) {  // (the pool form stores no albedo)
-    const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
-    if (need && c->path_pool.bytes < need && (rc = alloc_buf(c->path_pool, need))) return rc;
-    a.pool_slab = need ? c->path_pool.ptr : nullptr;
-  }
-  const uint32_t window = c->trace_window ? c->trace_window : rt::pt_first_window(c->scene.use_bvh);
-  a.first_window = window;
-  if (a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS)) {
-    // a region holds the survivors of ceil(workgroups / kPathQueues) workgroups of 256 paths (kernels.hip); the
-    // second buffer is only needed when a third segment window exists
-    const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
-    const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
-    const size_t cap = region * rt::kPathQueues;
-    if (!c->path_queue_count.ptr && (rc = alloc_buf(c->path_queue_count, 2 * rt::kPathQueues * sizeof(uint32_t)))) return rc;
-    if (!c->path_queue[0].ptr && (rc = alloc_buf(c->path_queue[0], cap * 48))) return rc;
-    if (a.max_segments > 2u * window && !c->path_queue[1].ptr && (rc = alloc_buf(c->path_queue[1], cap * 48))) return rc;
-    a.queue[0] = c->path_queue[0].ptr;
-    a.queue[1] = c->path_queue[1].ptr;
-    a.queue_count = static_cast<uint32_t*>(c->path_queue_count.ptr);
-    a.queue_region = static_cast<uint32_t>(region);
-  }
+  if ((rc = ensure_path_pool(c, a))) return rc;
+  a.first_window = c->trace_window ? c->trace_window : rt::pt_first_window(c->scene.use_bvh);
+  if ((rc = ensure_path_queues(c, a, a.first_window))) return rc;
   a.cull = 0;
   if (!c->scene.use_bvh && c->width_fits_i16()) {
     // K2 camera (raytrace.comp.glsl:314-320): at cameraPos, looking down -z, d = (slope*ux, slope*uy, -1) with
@@ -409,8 +404,8 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
     if (slope > 0)
       a.cull = screen_bounds(c, org, ex, ey, ez, H / (W * slope), -1.0 / slope, std::fabs(c->cfg.pixel_jitter) * 13.3, a.bounds) ? 1 : 0;
   }
-  c->final_swapped = false;
-  c->image_alias = false;
+  c->frame.final_swapped = false;
+  c->frame.image_alias = false;
   // K0 (+ K1) recorded right before this call run inside this launch, behind the tracing tiles (kernels.hip: k_gbuffer_pathtrace)
   const bool joined = c->pending_gb_valid && c->fuse_trace && rt::pathtrace_fuses_gbuffer(a, c->pending_gb);
   if (!joined && (rc = gbuffer_flush(c))) return rc;
@@ -447,6 +442,30 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
 
 namespace {
 
+// main.cpp:1264-1281: odd k reads `image`, writes `filteredImageBuffer`; even k the reverse.  An even last iteration blends
+// into a buffer nothing reads (main.cpp:55 "must be an odd number"), so only an odd last iteration is the FINAL pass.
+bool is_final(int k, int max_it) { return k == max_it && (k & 1); }
+
+// the tap spacing of iteration k and how far its taps reach from their centre
+struct Reach {
+  int stride;
+  int64_t reach;
+};
+Reach filter_reach(uint32_t ext, int k) {
+  const int stride = (ext & rt::kExtPow2Stride) ? (1 << (k - 1)) : k;
+  return {stride, static_cast<int64_t>(stride) * ((ext & rt::kExtGauss5) ? 2 : 1)};
+}
+// the rows an iteration over [y0, y1) reads: y +- reach, clamped to the frame (temporalFiltering.comp.glsl:135-136)
+Rows rows_read(const rtpt_ctx* c, uint32_t y0, uint32_t y1, int64_t reach) {
+  return Rows(std::max<int64_t>(0, static_cast<int64_t>(y0) - reach), std::min<int64_t>(c->cfg.height, static_cast<int64_t>(y1) + reach));
+}
+
+// does rtpt_temporal_filter record its calls in this context (to launch consecutive iterations as one chain)?
+bool records_filter_calls(const rtpt_ctx* c) {
+  return !(c->cfg.flags & (RTPT_FLAG_NO_FILTER_FUSION | RTPT_FLAG_DIRECT_FILTER)) && !(c->cfg.flags & rt::kExtMask) && c->scene.pair_tab.ptr &&
+         c->chain_max > 1;
+}
+
 int filter_validate(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_ubo* ubo, uint32_t& y0, uint32_t& y1) {
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
@@ -454,30 +473,46 @@ int filter_validate(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_ubo* 
   if (k < 1 || max_it < 1 || k > max_it) return fail(RTPT_E_INVALID, "need 1 <= waveletIteration <= maxWaveletIteration");
   const uint32_t ext = c->cfg.flags & rt::kExtMask;
   if ((ext & rt::kExtPow2Stride) && k > 24) return fail(RTPT_E_INVALID, "RTPT_FLAG_EXT_POW2_STRIDE supports at most 24 iterations");
-  const int stride = (ext & rt::kExtPow2Stride) ? (1 << (k - 1)) : k;
-  const int64_t reach = static_cast<int64_t>(stride) * ((ext & rt::kExtGauss5) ? 2 : 1);
-  // taps reach rows y +- reach (clamped to the frame, temporalFiltering.comp.glsl:135-136): they must be stored here
-  const int64_t lo = std::max<int64_t>(0, static_cast<int64_t>(y0) - reach);
-  const int64_t hi = std::min<int64_t>(c->cfg.height, static_cast<int64_t>(y1) + reach);
-  if (y1 > y0 && (lo < c->cfg.row_begin || hi > c->cfg.row_end))
+  const int64_t reach = filter_reach(ext, k).reach;
+  const Rows read = rows_read(c, y0, y1, reach);  // they must be stored here
+  if (y1 > y0 && !c->stored_rows().covers(read.y0, read.y1))
     return fail(RTPT_E_INVALID, "filter taps reaching " + std::to_string(reach) + " rows leave the stored rows (missing halo)");
-  const bool final_pass = (k == max_it) && (k & 1);
-  if (final_pass && !ubo) return fail(RTPT_E_INVALID, "the final pass needs the UBO (viewPrev/projPrev)");
+  if (is_final(k, max_it) && !ubo) return fail(RTPT_E_INVALID, "the final pass needs the UBO (viewPrev/projPrev)");
   if ((ext & rt::kExtVariance) && !ubo)
     return fail(RTPT_E_INVALID, "RTPT_FLAG_EXT_VARIANCE needs the UBO (viewPrev/projPrev) on every iteration");
   return RTPT_OK;
 }
 
+// The previous frame as the final pass and the moment accumulation read it: the context's own planes, or the ones gathered
+// across strips that rtpt_set_external_history / rtpt_set_external_guides registered.  `rows` hold a previous frame; the
+// plane stores frame rows from row_base on.
+struct PrevPlane {
+  const void* ptr;
+  const void* moments;  // prev_guides only
+  Rows rows;
+  int row_base;
+};
+PrevPlane prev_history(const rtpt_ctx* c) {
+  const FrameState& fr = c->frame;
+  if (fr.ext_history) return {fr.ext_history, nullptr, fr.ext_hist, fr.ext_hist.y0};
+  return {c->color[fr.color_of_role[ROLE_PREVIOUS]].ptr, nullptr, fr.hist, static_cast<int>(c->cfg.row_begin)};
+}
+// with_moments: the reader needs the moments next to the ids, so registered ids alone do not serve it
+PrevPlane prev_guides(const rtpt_ctx* c, bool with_moments) {
+  const FrameState& fr = c->frame;
+  if (fr.ext_prev_vis && (fr.ext_moments || !with_moments)) return {fr.ext_prev_vis, fr.ext_moments, fr.ext_guides, fr.ext_guides.y0};
+  return {c->vis[fr.vis_cur ^ 1].ptr, c->moments[fr.moments_cur ^ 1].ptr, fr.guides, static_cast<int>(c->cfg.row_begin)};
+}
+
 // Reprojection reuse (api_internal.hpp: ReprojKey), for the single-launch final pass `a` of the plain comb kernel over rows
 // [y0, y1): sets a.reproj_in when the plane holds this pass's reprojected pixels, a.reproj_out when this pass is to store them
 // (its key equals the previous frame's final pass's; the plane is allocated here, at the first store), neither otherwise.
-// *stored: the caller tags the plane with *key once the launch is out.
-int reproj_policy(rtpt_ctx* c, rt::AtrousArgs& a, uint32_t y0, uint32_t y1, ReprojKey* key, bool* stored) {
-  *stored = false;
+// store->valid: the plane carries *store once the launch is out (commit_filter).
+int reproj_policy(rtpt_ctx* c, rt::AtrousArgs& a, uint32_t y0, uint32_t y1, PlaneTag<ReprojKey>* store) {
   const PlaneTag<K0Key>& wp = c->tag_worldpos;
   const uint64_t lut_version = c->scene.lut_version[c->lut_cur ^ 1];
   const bool eligible = c->frame_reuse && c->reproj_reuse && !(c->debug_mask & RTPT_DEBUG_PREV_PIXEL) &&  // (that plane wants the raw integers)
-                        c->cfg.width <= 65535 && c->cfg.height <= 65535 && wp.valid && c->tag_vis[c->vis_cur].holds(wp.key) &&
+                        c->cfg.width <= 65535 && c->cfg.height <= 65535 && wp.valid && c->tag_vis[c->frame.vis_cur].holds(wp.key) &&
                         wp.key.y0 <= static_cast<int32_t>(y0) && wp.key.y1 >= static_cast<int32_t>(y1) && lut_version != ~0ull;
   if (!eligible) {
     c->reproj_last.valid = false;
@@ -500,8 +535,8 @@ int reproj_policy(rtpt_ctx* c, rt::AtrousArgs& a, uint32_t y0, uint32_t y1, Repr
     if (c->tag_reproj.valid) c->reproj_info[2]++;
     c->tag_reproj.valid = false;  // until the store is out
     a.reproj_out = static_cast<uint32_t*>(c->reproj.ptr);
-    *key = k;
-    *stored = true;
+    store->valid = true;
+    store->key = k;
     c->reproj_info[0]++;
   }
   c->reproj_last.valid = true;
@@ -509,192 +544,196 @@ int reproj_policy(rtpt_ctx* c, rt::AtrousArgs& a, uint32_t y0, uint32_t y1, Repr
   return RTPT_OK;
 }
 
-// launch iteration f.pc.waveletIteration — or, with levels > 1, that iteration and the levels - 1 after it as one chain
-int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
-  const rtpt_push_constants* pc = &f.pc;
-  const rtpt_ubo* ubo = f.has_ubo ? &f.ubo : nullptr;
-  const uint32_t y0 = f.y0, y1 = f.y1;  // rows of the LAST iteration of the chain
-  const int k = pc->waveletIteration, max_it = pc->maxWaveletIteration;
-  const int k_last = k + levels - 1;
+// What one launch does: iteration f.pc.waveletIteration — or, with levels > 1, that iteration and the levels - 1 after it as
+// one chain, over the rows of the chain's LAST iteration (f.y0, f.y1).  A function of the context and the call.
+struct FilterPlan {
+  int k, k_last, max_it, levels;
+  Reach tap;
+  bool final_pass;    // k_last is the FINAL pass ...
+  bool second_range;  // ... of a frame that already had one: another row range of the same pass
+  bool alpha_zero;    // the last iteration of an even N writes `image` and nothing filters it again: alpha 0 like the reference's
+                      // vec4(rgb, 0) (temporalFiltering.comp.glsl:152), so a device-side consumer of IMAGE never sees the depth
+  int in_buf, out_buf;  // of rtpt_ctx::color.  A chain reads its first iteration's input and writes the OTHER buffer, whatever
+                        // the parity of its length
+  int result_role;      // the role the separate passes would have left the result in
+  int kernel;           // for the timer
+};
+FilterPlan plan_filter(const rtpt_ctx* c, const FilterCall& f, int levels) {
+  FilterPlan p;
+  p.k = f.pc.waveletIteration;
+  p.max_it = f.pc.maxWaveletIteration;
+  p.levels = levels;
+  p.k_last = p.k + levels - 1;
+  p.tap = filter_reach(c->cfg.flags & rt::kExtMask, p.k);
+  p.final_pass = is_final(p.k_last, p.max_it);
+  p.second_range = levels == 1 && p.final_pass && c->frame.final_swapped;
+  p.alpha_zero = p.k_last == p.max_it && !p.final_pass;
+  const bool from_image = ((p.k & 1) != 0) != p.second_range;  // (the first range swapped the two roles)
+  p.in_buf = c->frame.color_of_role[from_image ? ROLE_IMAGE : ROLE_FILTERED];
+  p.out_buf = c->frame.color_of_role[from_image ? ROLE_FILTERED : ROLE_IMAGE];
+  p.result_role = (p.final_pass || !(p.k_last & 1)) ? ROLE_IMAGE : ROLE_FILTERED;  // D1: the blend becomes `image`
+  p.kernel = levels > 1 ? (p.final_pass ? RTPT_K_ATROUS_CHAIN_FINAL : RTPT_K_ATROUS_CHAIN) : (p.final_pass ? RTPT_K_ATROUS_FINAL : RTPT_K_ATROUS);
+  return p;
+}
+
+// the launches that must precede the pass: the depth channel of an injected input, the moments, the variance prefilter
+void filter_prelaunch(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f) {
+  FrameState& fr = c->frame;
   const uint32_t ext = c->cfg.flags & rt::kExtMask;
-  const int stride = (ext & rt::kExtPow2Stride) ? (1 << (k - 1)) : k;
-  const int64_t reach = static_cast<int64_t>(stride) * ((ext & rt::kExtGauss5) ? 2 : 1);
-  // main.cpp:1264-1281: odd k reads `image`, writes `filteredImageBuffer`; even k the reverse.
-  // An even final pass blends into a buffer nothing reads (main.cpp:55 "must be an odd number"),
-  // so only an odd final pass is a FINAL launch.
-  const bool final_pass = (k_last == max_it) && (k_last & 1);
-  HIP_TRY(hipSetDevice(c->device));
-  int in_role = (k & 1) ? ROLE_IMAGE : ROLE_FILTERED;
-  int out_role = (k & 1) ? ROLE_FILTERED : ROLE_IMAGE;
-  if (levels == 1 && final_pass && c->final_swapped) std::swap(in_role, out_role);  // a second row range of the same final pass
-  // a chain reads the first iteration's input and writes the OTHER buffer, whatever the parity of its length; the roles
-  // are re-pointed below so that afterwards every role names the buffer the separate passes would have left it in
-  const int in_buf = c->color_of_role[in_role], out_buf = c->color_of_role[out_role];
-  rt::AtrousArgs a;
+  if (!fr.alpha_depth[p.in_buf]) {  // rtpt_set_plane / rtpt_bind_plane
+    rt::launch_stamp_depth(geom(c, c->cfg.row_begin, c->cfg.row_end), static_cast<float4*>(c->color[p.in_buf].ptr),
+                           static_cast<const float*>(c->depth.ptr), c->stream);
+    fr.alpha_depth[p.in_buf] = true;
+  }
+  if (!(ext & rt::kExtVariance)) return;
+  if (p.k == 1) {  // temporal accumulation of the luminance moments of the traced image (this iteration's input)
+    const PrevPlane guides = prev_guides(c, true);
+    rt::MomentsArgs m;
+    std::memset(&m, 0, sizeof m);
+    m.g = geom(c, c->cfg.row_begin, c->cfg.row_end);
+    m.frame = f.pc.frameNumber;
+    m.alpha = c->cfg.alpha;
+    m.traced = static_cast<const float4*>(c->color[p.in_buf].ptr);
+    m.vis = static_cast<const uint32_t*>(c->vis[fr.vis_cur].ptr);
+    m.worldpos = static_cast<const float4*>(c->worldpos.ptr);
+    m.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
+    rt::exact::mat_mul(f.ubo.projPrev, f.ubo.viewPrev, m.PVprev);
+    m.prev_vis = static_cast<const uint32_t*>(guides.ptr);
+    m.moments_prev = static_cast<const float4*>(guides.moments);
+    m.hist_row_base = guides.row_base;
+    m.hist_y0 = guides.rows.y0;
+    m.hist_y1 = guides.rows.y1;
+    m.svgf = (ext & rt::kExtSvgfVariance) ? 1 : 0;
+    m.rows_stored = static_cast<int32_t>(c->rows());
+    m.moments_out = static_cast<float4*>(c->moments[fr.moments_cur].ptr);
+    m.var_out = static_cast<float*>(c->variance[0].ptr);
+    rt::launch_moments(m, c->stream);
+    fr.variance_last = 0;
+  }
+  if ((ext & rt::kExtSvgfVariance) && c->var_scale.ptr)  // SVGF's variance prefilter: the centre's scale only
+    rt::launch_var_prefilter(geom(c, f.y0, f.y1), static_cast<int>(c->rows()), static_cast<const float*>(c->variance[fr.variance_last].ptr),
+                             static_cast<float*>(c->var_scale.ptr), c->stream);
+  fr.variance_last ^= 1;  // the buffer the pass writes
+}
+
+// the kernel's arguments.  Besides `a` this writes the reuse counters and FrameState::present_fused; *store as reproj_policy
+int fill_atrous_args(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, rt::AtrousArgs& a, PlaneTag<ReprojKey>* store) {
+  FrameState& fr = c->frame;
   std::memset(&a, 0, sizeof a);
-  a.g = geom(c, y0, y1);
-  a.k = k;
-  a.stride = stride;
-  a.ext = ext;
+  a.g = geom(c, f.y0, f.y1);
+  a.k = p.k;
+  a.stride = p.tap.stride;
+  a.ext = c->cfg.flags & rt::kExtMask;
   a.exact = (c->cfg.flags & RTPT_FLAG_EXACT_FILTER) ? 1 : 0;
   a.direct = (c->cfg.flags & RTPT_FLAG_DIRECT_FILTER) ? 1 : 0;
   a.n_tris = c->scene.n_tris;
   a.pair_tab = static_cast<const float*>(c->scene.pair_tab.ptr);
   a.rows_stored = static_cast<int32_t>(c->rows());
   a.n_cu = c->n_cu;
-  // the last iteration of an even N writes `image` and nothing filters it again: alpha 0 like the reference's
-  // vec4(rgb, 0) (temporalFiltering.comp.glsl:152), so a device-side consumer of IMAGE never sees the depth
-  a.alpha_zero = (k_last == max_it && !final_pass) ? 1 : 0;
+  a.alpha_zero = p.alpha_zero ? 1 : 0;
   a.sigma_n = c->cfg.sigma_n;
   a.sigma_z = c->cfg.sigma_z;
   a.sigma_l = c->cfg.sigma_l;
-  a.in = static_cast<const float4*>(c->color[in_buf].ptr);
-  a.out = static_cast<float4*>(c->color[out_buf].ptr);
-  a.vis = static_cast<const uint32_t*>(c->vis[c->vis_cur].ptr);
+  a.in = static_cast<const float4*>(c->color[p.in_buf].ptr);
+  a.out = static_cast<float4*>(c->color[p.out_buf].ptr);
+  a.vis = static_cast<const uint32_t*>(c->vis[fr.vis_cur].ptr);
   a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
-  {
-    const int64_t lo = std::max<int64_t>(0, static_cast<int64_t>(y0) - reach), hi = std::min<int64_t>(c->cfg.height, static_cast<int64_t>(y1) + reach);
-    const bool covered = c->normals.ptr && c->normals_frame == c->frames_ended && c->normals_y0 <= lo && c->normals_y1 >= hi;
-    a.normals = covered ? static_cast<const float4*>(c->normals.ptr) : nullptr;
+  const Rows read = rows_read(c, f.y0, f.y1, p.tap.reach);
+  if (c->normals.ptr && fr.normals_frame == c->frames_ended && fr.normals.covers(read.y0, read.y1)) a.normals = static_cast<const float4*>(c->normals.ptr);
+  if (a.ext & rt::kExtVariance) {  // (filter_prelaunch left variance_last naming the buffer this pass writes)
+    a.var_in = static_cast<const float*>(c->variance[fr.variance_last ^ 1].ptr);
+    a.var_out = static_cast<float*>(c->variance[fr.variance_last].ptr);
+    if ((a.ext & rt::kExtSvgfVariance) && c->var_scale.ptr) a.var_scale = static_cast<const float*>(c->var_scale.ptr);
   }
-  if (!c->alpha_depth[in_buf]) {
-    // the input plane was injected (rtpt_set_plane / rtpt_bind_plane): give it its depth channel
-    rt::launch_stamp_depth(geom(c, c->cfg.row_begin, c->cfg.row_end), static_cast<float4*>(c->color[in_buf].ptr),
-                           static_cast<const float*>(c->depth.ptr), c->stream);
-    c->alpha_depth[in_buf] = true;
-  }
-  c->alpha_depth[out_buf] = !final_pass && !a.alpha_zero;
-  if (final_pass) {
-    a.frame = pc->frameNumber;
-    a.alpha = c->cfg.alpha;
-    a.worldpos = static_cast<const float4*>(c->worldpos.ptr);
-    a.history = static_cast<const float4*>(c->color[c->color_of_role[ROLE_PREVIOUS]].ptr);
-    a.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
-    rt::exact::mat_mul(ubo->projPrev, ubo->viewPrev, a.PVprev);  // temporalFiltering.comp.glsl:180
-    a.prev_pixel = (c->debug_mask & RTPT_DEBUG_PREV_PIXEL) ? static_cast<int2*>(c->prev_pixel.ptr) : nullptr;
-    a.hist_row_base = static_cast<int32_t>(c->cfg.row_begin);
-    a.hist_y0 = c->hist_y0;
-    a.hist_y1 = c->hist_y1;
-    a.gradient = static_cast<const float4*>(c->gradient.ptr);
-    a.prev_vis = static_cast<const uint32_t*>(c->vis[c->vis_cur ^ 1].ptr);
-    a.pvis_y0 = c->guides_y0;
-    a.pvis_y1 = c->guides_y1;
-    a.pvis_row_base = static_cast<int32_t>(c->cfg.row_begin);
-    if (c->ext_prev_vis) {  // gathered across strips
-      a.prev_vis = static_cast<const uint32_t*>(c->ext_prev_vis);
-      a.pvis_y0 = c->ext_guides_y0;
-      a.pvis_y1 = c->ext_guides_y1;
-      a.pvis_row_base = c->ext_guides_y0;
-    }
-    if (c->ext_history) {  // all-gathered previous frame (multi-GPU strips)
-      a.history = static_cast<const float4*>(c->ext_history);
-      a.hist_row_base = c->ext_hist_y0;
-      a.hist_y0 = c->ext_hist_y0;
-      a.hist_y1 = c->ext_hist_y1;
-    }
-  }
-  if (ext & rt::kExtVariance) {
-    if (k == 1) {  // temporal accumulation of the luminance moments of the traced image (this iteration's input)
-      rt::MomentsArgs m;
-      std::memset(&m, 0, sizeof m);
-      m.g = geom(c, c->cfg.row_begin, c->cfg.row_end);
-      m.frame = pc->frameNumber;
-      m.alpha = c->cfg.alpha;
-      m.traced = a.in;
-      m.vis = a.vis;
-      m.worldpos = static_cast<const float4*>(c->worldpos.ptr);
-      m.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
-      rt::exact::mat_mul(ubo->projPrev, ubo->viewPrev, m.PVprev);
-      m.prev_vis = static_cast<const uint32_t*>(c->vis[c->vis_cur ^ 1].ptr);
-      m.moments_prev = static_cast<const float4*>(c->moments[c->moments_cur ^ 1].ptr);
-      m.hist_row_base = static_cast<int32_t>(c->cfg.row_begin);
-      m.hist_y0 = c->guides_y0;
-      m.hist_y1 = c->guides_y1;
-      if (c->ext_prev_vis && c->ext_moments) {  // gathered across strips (rtpt_set_external_guides)
-        m.prev_vis = static_cast<const uint32_t*>(c->ext_prev_vis);
-        m.moments_prev = static_cast<const float4*>(c->ext_moments);
-        m.hist_row_base = m.hist_y0 = c->ext_guides_y0;
-        m.hist_y1 = c->ext_guides_y1;
-      }
-      m.svgf = (ext & rt::kExtSvgfVariance) ? 1 : 0;
-      m.rows_stored = static_cast<int32_t>(c->rows());
-      m.moments_out = static_cast<float4*>(c->moments[c->moments_cur].ptr);
-      m.var_out = static_cast<float*>(c->variance[0].ptr);
-      rt::launch_moments(m, c->stream);
-      c->variance_last = 0;
-    }
-    a.var_in = static_cast<const float*>(c->variance[c->variance_last].ptr);
-    a.var_out = static_cast<float*>(c->variance[c->variance_last ^ 1].ptr);
-    c->variance_last ^= 1;
-    if ((ext & rt::kExtSvgfVariance) && c->var_scale.ptr) {  // SVGF's variance prefilter: the centre's scale only
-      rt::launch_var_prefilter(geom(c, y0, y1), static_cast<int>(c->rows()), a.var_in, static_cast<float*>(c->var_scale.ptr), c->stream);
-      a.var_scale = static_cast<const float*>(c->var_scale.ptr);
-    }
-  }
-  if (final_pass) c->present_fused_dst = nullptr;  // a new frame's final pass: the previous frame's blit is history
+  if (!p.final_pass) return RTPT_OK;
+  const PrevPlane hist = prev_history(c), guides = prev_guides(c, false);
+  a.frame = f.pc.frameNumber;
+  a.alpha = c->cfg.alpha;
+  a.worldpos = static_cast<const float4*>(c->worldpos.ptr);
+  a.lut_prev = static_cast<const float4*>(c->scene.lut[c->lut_cur ^ 1].ptr);
+  rt::exact::mat_mul(f.ubo.projPrev, f.ubo.viewPrev, a.PVprev);  // temporalFiltering.comp.glsl:180
+  a.prev_pixel = (c->debug_mask & RTPT_DEBUG_PREV_PIXEL) ? static_cast<int2*>(c->prev_pixel.ptr) : nullptr;
+  a.gradient = static_cast<const float4*>(c->gradient.ptr);
+  a.history = static_cast<const float4*>(hist.ptr);
+  a.hist_row_base = hist.row_base;
+  a.hist_y0 = hist.rows.y0;
+  a.hist_y1 = hist.rows.y1;
+  a.prev_vis = static_cast<const uint32_t*>(guides.ptr);
+  a.pvis_row_base = guides.row_base;
+  a.pvis_y0 = guides.rows.y0;
+  a.pvis_y1 = guides.rows.y1;
+  fr.present_fused_dst = nullptr;  // a new frame's final pass: the previous frame's blit is history
+  if (p.levels > 1) return RTPT_OK;
   // (RTPT_FLAG_EXT_DEMODULATE: the pass stores demodulated colour, the swapchain takes colour x albedo — rtpt_present does the work)
-  if (final_pass && levels == 1 && c->present_dst && static_cast<int>(y0) <= c->present_y0 && static_cast<int>(y1) >= c->present_y1 &&
-      !(c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) && rt::atrous_final_fuses_present(a)) {
+  if (c->present_dst && Rows(f.y0, f.y1).covers(c->present_rows.y0, c->present_rows.y1) && !(c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) &&
+      rt::atrous_final_fuses_present(a)) {
     a.present = static_cast<uint32_t*>(c->present_dst);
-    a.present_y0 = c->present_y0;
-    a.present_y1 = c->present_y1;
-    c->present_fused_dst = c->present_dst;
-    c->present_fused_y0 = c->present_y0;
-    c->present_fused_y1 = c->present_y1;
+    a.present_y0 = c->present_rows.y0;
+    a.present_y1 = c->present_rows.y1;
+    fr.present_fused_dst = c->present_dst;
+    fr.present_fused = c->present_rows;
   }
   // the other final-pass routes (direct, extension, chained) neither load nor store and leave the tag alone: it is keyed on
   // the pass's inputs, not on who ran
-  ReprojKey reproj_key;
-  bool reproj_stored = false;
-  if (final_pass && levels == 1 && rt::atrous_final_plain_comb(a)) {
-    int rcr = reproj_policy(c, a, y0, y1, &reproj_key, &reproj_stored);
-    if (rcr) return rcr;
-  }
-  {
-    Timer tm(c, levels > 1 ? (final_pass ? RTPT_K_ATROUS_CHAIN_FINAL : RTPT_K_ATROUS_CHAIN) : (final_pass ? RTPT_K_ATROUS_FINAL : RTPT_K_ATROUS));
-    if (levels > 1)
-      rt::launch_atrous_chain(a, levels, final_pass, c->filter_policy, c->stream);
+  return rt::atrous_final_plain_comb(a) ? reproj_policy(c, a, f.y0, f.y1, store) : RTPT_OK;
+}
+
+// the launch is out: afterwards every role names the buffer the separate passes would have left it in
+void commit_filter(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, const PlaneTag<ReprojKey>& stored) {
+  FrameState& fr = c->frame;
+  if (stored.valid) c->tag_reproj = stored;
+  fr.alpha_depth[p.out_buf] = !p.final_pass && !p.alpha_zero;
+  fr.color_of_role[p.result_role] = p.out_buf;
+  fr.color_of_role[p.result_role == ROLE_IMAGE ? ROLE_FILTERED : ROLE_IMAGE] = p.in_buf;
+  if (p.k_last == p.max_it) {  // the rows of IMAGE that hold the filtered frame
+    if (p.second_range)
+      fr.final.extend(f.y0, f.y1);
     else
-      rt::launch_atrous(a, final_pass, c->stream);
+      fr.final = Rows(f.y0, f.y1);
   }
-  int rc;
+  if (p.final_pass) fr.final_swapped = true;
+}
+
+int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
+  HIP_TRY(hipSetDevice(c->device));
+  const FilterPlan p = plan_filter(c, f, levels);
+  filter_prelaunch(c, p, f);
+  rt::AtrousArgs a;
+  PlaneTag<ReprojKey> stored;
+  int rc = fill_atrous_args(c, p, f, a, &stored);
+  if (rc) return rc;
+  {
+    Timer tm(c, p.kernel);
+    if (levels > 1)
+      rt::launch_atrous_chain(a, levels, p.final_pass, c->filter_policy, c->stream);
+    else
+      rt::launch_atrous(a, p.final_pass, c->stream);
+  }
   if ((rc = launch_check("temporal_filter"))) return rc;
-  if (reproj_stored) {
-    c->tag_reproj.valid = true;
-    c->tag_reproj.key = reproj_key;
-  }
-  if (levels > 1) {
-    // point the roles at the buffers the separate passes would have left them in: the result sits in out_buf
-    const int res_role = final_pass ? ROLE_IMAGE : ((k_last & 1) ? ROLE_FILTERED : ROLE_IMAGE);
-    const int oth_role = res_role == ROLE_IMAGE ? ROLE_FILTERED : ROLE_IMAGE;
-    c->color_of_role[res_role] = out_buf;
-    c->color_of_role[oth_role] = in_buf;
-    if (final_pass) {
-      c->final_swapped = true;
-      c->final_y0 = static_cast<int>(y0);
-      c->final_y1 = static_cast<int>(y1);
-    } else if (k_last == max_it) {
-      c->final_y0 = static_cast<int>(y0);
-      c->final_y1 = static_cast<int>(y1);
-    }
-    return RTPT_OK;
-  }
-  if (final_pass) {
-    if (!c->final_swapped) {
-      // D1: the blend went to a distinct buffer, which now becomes `image`
-      std::swap(c->color_of_role[ROLE_IMAGE], c->color_of_role[ROLE_FILTERED]);
-      c->final_swapped = true;
-      c->final_y0 = static_cast<int>(y0);
-      c->final_y1 = static_cast<int>(y1);
-    } else {
-      c->final_y0 = std::min(c->final_y0, static_cast<int>(y0));
-      c->final_y1 = std::max(c->final_y1, static_cast<int>(y1));
-    }
-  } else if (k == max_it) {
-    c->final_y0 = static_cast<int>(y0);
-    c->final_y1 = static_cast<int>(y1);
-  }
+  commit_filter(c, p, f, stored);
   return RTPT_OK;
+}
+
+// how many of the records from calls[i] on run as one launch: the chain grows while the next record is the next iteration,
+// its rows are covered and the kernel has the LDS.  Greedy from the front.
+int chain_length(const rtpt_ctx* c, const std::vector<FilterCall>& calls, size_t i) {
+  const int k0 = calls[i].pc.waveletIteration, max_it = calls[i].pc.maxWaveletIteration;
+  int levels = 1;
+  while (i + levels < calls.size() && levels < c->chain_max) {
+    const FilterCall &cur = calls[i + levels - 1], &nxt = calls[i + levels];
+    const int kn = nxt.pc.waveletIteration;
+    if (kn != k0 + levels || nxt.pc.maxWaveletIteration != max_it) break;
+    const bool nxt_final = is_final(kn, max_it);
+    if (nxt_final && !c->chain_final) break;
+    if (nxt_final && c->frame.final_swapped) break;
+    const Rows need = rows_read(c, nxt.y0, nxt.y1, filter_reach(c->cfg.flags & rt::kExtMask, kn).reach);
+    if (nxt.y1 <= nxt.y0 || !Rows(cur.y0, cur.y1).covers(need.y0, need.y1)) break;
+    if (static_cast<int64_t>(nxt.y1 - nxt.y0) * c->cfg.width < c->chain_min_pixels) break;
+    if (!rt::atrous_chain_supported(k0, levels + 1, c->scene.n_tris)) break;
+    levels++;
+    if (nxt_final) break;
+  }
+  return levels;
 }
 
 }  // namespace
@@ -705,30 +744,9 @@ int filter_flush(rtpt_ctx* c, bool fuse) {
   if (c->pending.empty()) return RTPT_OK;
   std::vector<FilterCall> calls;
   calls.swap(c->pending);  // filter_launch may fail: the record is dropped either way
-  const size_t n = calls.size();
-  const int H = static_cast<int>(c->cfg.height);
-  size_t i = 0;
-  while (i < n) {
-    int levels = 1;
-    if (fuse && !(c->cfg.flags & (RTPT_FLAG_DIRECT_FILTER | RTPT_FLAG_NO_FILTER_FUSION)) && !(c->cfg.flags & rt::kExtMask) && c->scene.pair_tab.ptr) {
-      const int k0 = calls[i].pc.waveletIteration, max_it = calls[i].pc.maxWaveletIteration;
-      // grow the chain while the next record is the next iteration, its rows are covered and the kernel has the LDS
-      while (i + levels < n && levels < c->chain_max) {
-        const FilterCall &cur = calls[i + levels - 1], &nxt = calls[i + levels];
-        const int kn = nxt.pc.waveletIteration;
-        if (kn != k0 + levels || nxt.pc.maxWaveletIteration != max_it) break;
-        const bool nxt_final = (kn == max_it) && (kn & 1);
-        if (nxt_final && !c->chain_final) break;
-        if (nxt_final && c->final_swapped) break;
-        const int need0 = std::max(0, static_cast<int>(nxt.y0) - kn), need1 = std::min(H, static_cast<int>(nxt.y1) + kn);
-        if (nxt.y1 <= nxt.y0 || static_cast<int>(cur.y0) > need0 || static_cast<int>(cur.y1) < need1) break;
-        if (static_cast<int64_t>(nxt.y1 - nxt.y0) * c->cfg.width < c->chain_min_pixels) break;
-        if (!rt::atrous_chain_supported(k0, levels + 1, c->scene.n_tris)) break;
-        levels++;
-        if (nxt_final) break;
-      }
-      // a chain must not end one short of a FINAL pass it could have included... nothing to do: greedy from the front
-    }
+  fuse = fuse && records_filter_calls(c);
+  for (size_t i = 0; i < calls.size();) {
+    const int levels = fuse ? chain_length(c, calls, i) : 1;
     FilterCall f = calls[i];
     if (levels > 1) {
       const FilterCall& lastc = calls[i + levels - 1];
@@ -761,9 +779,7 @@ int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_
   if (ubo) f.ubo = *ubo;
   f.y0 = y0;
   f.y1 = y1;
-  const bool record = !(c->cfg.flags & (RTPT_FLAG_NO_FILTER_FUSION | RTPT_FLAG_DIRECT_FILTER)) && !(c->cfg.flags & rt::kExtMask) &&
-                      c->scene.pair_tab.ptr && c->chain_max > 1;
-  if (!record) {
+  if (!records_filter_calls(c)) {
     FLUSH_FILTER(c);
     return filter_launch(c, f, 1);
   }
@@ -790,19 +806,18 @@ int rtpt_end_frame(rtpt_ctx* c) {
   // copy both images hold the same pixels; here IMAGE now names the old history buffer (about to be
   // overwritten by the next rtpt_raytrace), so until then rtpt_readback(IMAGE) is served from
   // PREVIOUS (image_alias).
-  std::swap(c->color_of_role[ROLE_IMAGE], c->color_of_role[ROLE_PREVIOUS]);
-  c->image_alias = true;
-  c->hist_y0 = c->final_y0;
-  c->hist_y1 = c->final_y1;
+  FrameState& fr = c->frame;
+  std::swap(fr.color_of_role[ROLE_IMAGE], fr.color_of_role[ROLE_PREVIOUS]);
+  fr.image_alias = true;
+  fr.hist = fr.final;
   // the id plane (and, with RTPT_FLAG_EXT_VARIANCE, the moment plane) of the frame just ended cover the stored rows
-  c->guides_y0 = static_cast<int>(c->cfg.row_begin);
-  c->guides_y1 = static_cast<int>(c->cfg.row_end);
+  fr.guides = c->stored_rows();
   // main.cpp:1367 visibilityBuffer -> previousVisibilityBuffer; main.cpp:1372 LUT -> LUTprev
-  c->vis_cur ^= 1;
-  c->moments_cur ^= 1;
+  fr.vis_cur ^= 1;
+  fr.moments_cur ^= 1;
   c->lut_cur ^= 1;
   c->scene.lut_prev_valid = c->scene.n_tris != 0;
-  c->final_swapped = false;
+  fr.final_swapped = false;
   c->frames_ended++;
   return RTPT_OK;
 }
@@ -819,8 +834,7 @@ int rtpt_present_target(rtpt_ctx* c, void* dst_device, uint32_t y0, uint32_t y1)
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
   c->present_dst = dst_device;
-  c->present_y0 = static_cast<int>(y0);
-  c->present_y1 = static_cast<int>(y1);
+  c->present_rows = Rows(y0, y1);
   return RTPT_OK;
 }
 
@@ -832,17 +846,15 @@ int rtpt_present(rtpt_ctx* c, void* dst_device, uint32_t y0, uint32_t y1) {
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
   // already there: the frame's final pass wrote these rows of this image in swapchain format (rtpt_present_target)
-  if (c->present_fused_dst && static_cast<int>(y0) >= c->present_fused_y0 && static_cast<int>(y1) <= c->present_fused_y1 &&
-      static_cast<char*>(dst_device) == static_cast<char*>(c->present_fused_dst) + static_cast<size_t>(static_cast<int>(y0) - c->present_fused_y0) * c->cfg.width * 4)
+  const FrameState& fr = c->frame;
+  if (fr.present_fused_dst && fr.present_fused.covers(y0, y1) &&
+      static_cast<char*>(dst_device) == static_cast<char*>(fr.present_fused_dst) + static_cast<size_t>(static_cast<int>(y0) - fr.present_fused.y0) * c->cfg.width * 4)
     return RTPT_OK;
-  // the finished frame: IMAGE until rtpt_end_frame, PREVIOUS after it (the reference blits before it copies, the pixels
-  // are the same); only rows the last final pass wrote hold it
-  Buf* b = plane_buf(c, c->image_alias ? RTPT_PLANE_PREVIOUS : RTPT_PLANE_IMAGE);
+  const auto [b, rows] = finished_frame(c);
   if (!b || !b->ptr) return fail(RTPT_E_INVALID, "no image plane");
-  const int f0 = c->image_alias ? c->hist_y0 : c->final_y0, f1 = c->image_alias ? c->hist_y1 : c->final_y1;
-  if (static_cast<int>(y0) < f0 || static_cast<int>(y1) > f1)
+  if (!rows.covers(y0, y1))
     return fail(RTPT_E_INVALID, "rtpt_present: rows [" + std::to_string(y0) + "," + std::to_string(y1) + ") outside the rows of the finished frame [" +
-                                    std::to_string(f0) + "," + std::to_string(f1) + ")");
+                                    std::to_string(rows.y0) + "," + std::to_string(rows.y1) + ")");
   HIP_TRY(hipSetDevice(c->device));
   {
     Timer tm(c, RTPT_K_PRESENT);
@@ -860,7 +872,7 @@ int rtpt_modulate(rtpt_ctx* c, uint32_t y0, uint32_t y1) {
   FLUSH_FILTER(c);
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
-  Buf* b = plane_buf(c, c->image_alias ? RTPT_PLANE_PREVIOUS : RTPT_PLANE_IMAGE);
+  const Buf* b = finished_frame(c).buf;
   if (!b || !b->ptr || !c->albedo.ptr || !c->shaded.ptr) return fail(RTPT_E_INVALID, "no image plane");
   HIP_TRY(hipSetDevice(c->device));
   {

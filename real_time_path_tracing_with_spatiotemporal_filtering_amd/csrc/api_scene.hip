@@ -53,7 +53,7 @@ int check_record_offsets(uint64_t total, uint64_t n_nodes) {
 // spill area (sized by the replaced tree's depth), and what frame reuse and the LUTs compare.  Every replacement calls it.
 void forget_scene(rtpt_ctx* c) {
   c->tables_valid = false;
-  c->normals_y0 = c->normals_y1 = 0;
+  c->frame.normals = Rows();
   free_buf(c->stack_spill);
   c->stack_spill_blocks = 0;
   c->scene.model_version++;
