@@ -324,6 +324,33 @@ typedef struct rtpt_material {
 int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material* materials,
                              uint32_t n_materials);
 
+/* Albedo textures (NOT reference behaviour, off until this call): the albedo of a hit becomes (Kd, or the
+ * normal-keyed colour without materials) x texel.rgb — one binary32 multiply per channel, taken before the throughput
+ * multiply — at EVERY segment of a path, in every kernel that shades (csrc/texture.hpp is the one sampler).  A surface with
+ * Ke != 0 ends the path before any texture is read, as without textures.  With RTPT_FLAG_EXT_DEMODULATE, RTPT_PLANE_ALBEDO
+ * holds that product for the first hit.
+ * tri_uv: 6 floats per triangle of the uploaded MESH (u0 v0 u1 v1 u2 v2, corner order of idx); tri_texture[t]: 0 =
+ * untextured, i + 1 = textures[i]; instances share both (triangle id reads record id % n_tris).  texels: RGBA32F, linear,
+ * row-major, row 0 is v in [0, 1/height); texture i owns texels [first_texel, first_texel + width * height); alpha is
+ * carried and ignored.  Coordinates repeat (s = u - floor(u)); the filter is bilinear unless RTPT_TEX_NEAREST is set; no
+ * mip-mapping.  Everything is copied: the arrays may die at return.
+ * Device memory held, counted by rtpt_debug_live_device_bytes: exactly 32 * n_tris + 16 * n_textures + 16 * n_texels bytes.
+ * Lifetime, like the materials': rtpt_scene_upload drops the textures; rtpt_scene_set_materials, rtpt_scene_set_instances,
+ * rtpt_scene_rebuild, a changed ubo->model and rtpt_resize keep them.  tri_uv, tri_texture, textures or texels NULL, or
+ * n_textures / n_texels 0, drops them (every kernel is then the one of a scene that never had any).
+ * Launches what is recorded first and blocks until the stream is idle, like rtpt_scene_set_materials.  K0, K1 and the filter
+ * read no texture: frame reuse and reprojection reuse go on across the call.
+ * RTPT_E_NO_SCENE before an upload.  RTPT_E_INVALID, with the scene and its textures untouched, for: n_tris other than the
+ * uploaded mesh's; tri_texture[t] > n_textures; a zero width or height, or one above 65536; a rectangle that ends beyond
+ * n_texels (or beyond 2^32 - 1 texels); an unknown flag; a uv that is not finite (or above 2^64 in magnitude).  No kernel
+ * can index outside the atlas: that is decided here, on the host. */
+#define RTPT_TEX_NEAREST 0x1u /* default: bilinear */
+typedef struct rtpt_texture {
+  uint32_t width, height, first_texel, flags;
+} rtpt_texture;
+int rtpt_scene_set_textures(rtpt_ctx* ctx, const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris,
+                            const rtpt_texture* textures, uint32_t n_textures, const float* texels, size_t n_texels);
+
 /* What built the tree that is on the device now.  (A struct tag without a typedef: the entry point below carries the
  * same name, and C keeps tags and functions apart.) */
 enum { RTPT_BVH_BUILDER_HOST_SAH = 0, RTPT_BVH_BUILDER_DEVICE_LBVH = 1 };
@@ -549,6 +576,12 @@ int rtpt_selftest_div(rtpt_ctx* ctx, int mode, uint32_t first_pass, uint32_t n_p
  * force): rays = n x {ox,oy,oz,dx,dy,dz}; out_id[n] = primitive id+1 or 0; out_t[n] may be NULL */
 int rtpt_selftest_trace(rtpt_ctx* ctx, const float* rays, size_t n, uint32_t* out_id, float* out_t);
 
+/* device-side evaluation of the sampler for arbitrary uv (parity with the tests' numpy restatement): rgba_out[4 i .. 4 i + 3]
+ * = what a hit with texture coordinates (uv[2 i], uv[2 i + 1]) reads from textures[texture] (0-based) of the last
+ * rtpt_scene_set_textures, alpha included.  RTPT_E_NO_SCENE without a scene; RTPT_E_INVALID without textures, for an index
+ * >= n_textures or a uv that is not finite. */
+int rtpt_selftest_texture(rtpt_ctx* ctx, uint32_t texture, const float* uv, size_t n, float* rgba_out);
+
 /* ---- host-side helpers shared by the C++ and Python hosts -------------------------------- */
 /* glm::lookAt / glm::perspective as used at main.cpp:482-484,:1470-1472 (right-handed,
  * zero-to-one depth — D6; the caller applies proj[1][1] *= -1 like the reference does). */
@@ -564,6 +597,16 @@ int rtpt_util_load_obj(const char* path, float* xyz, uint32_t* n_verts, uint32_t
  * OBJ names one that does not exist (scenes/CornellBox-Original-Merged.obj:3) — *n_materials comes back 0. */
 int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material* materials,
                                  uint32_t* n_materials);
+/* the texture-coordinate side of the same file: `vt` records and the vt of `f v/vt`, `f v/vt/vn` corners (`f v`, `f v//vn`:
+ * the corner gets (0, 0)); negative vt indices count back from the last `vt` read.  tri_uv: 6 floats per triangle (u0 v0 u1
+ * v1 u2 v2), fanned like rtpt_util_load_obj's triangles, so the two arrays line up.  Two-call pattern (NULL: count). */
+int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris);
+/* the `map_Kd` file name of every material, in rtpt_util_load_obj_materials' numbering (entry 0, the default material, is
+ * always empty; no map: empty): *n_materials NUL-terminated strings, one after the other, in `names`.  Options before the
+ * name are not supported (the last word of the line is taken).  Two-call pattern: names == NULL stores the byte count in
+ * *names_bytes and the count in *n_materials; with names, *names_bytes in = capacity.  *n_materials comes back 0 when the
+ * OBJ names no readable library. */
+int rtpt_util_load_obj_map_kd(const char* path, char* names, size_t* names_bytes, uint32_t* n_materials);
 /* Host-only self check of the acceleration-structure builder that stands in for the driver's BLAS/TLAS build
  * (buildAccelerationStructure, main.cpp:687-742): builds the BVH over `n_tris` world-space triangles (9 floats
  * each), packs the device nodes and verifies the invariants the traversal relies on.  Needs no GPU.
@@ -608,6 +651,7 @@ static_assert(offsetof(rtpt_push_constants, maxWaveletIteration) == 96, "maxWave
 static_assert(sizeof(rtpt_ubo) == 384, "UniformBufferObject is 384 bytes (main.cpp:82-90)");
 static_assert(sizeof(rtpt_visibility_data) == 48, "VisibilityData stride 48 (std430)");
 static_assert(sizeof(struct rtpt_scene_build_info) == 32, "rtpt_scene_build_info is 32 bytes");
+static_assert(sizeof(rtpt_texture) == 16, "rtpt_texture is 16 bytes");
 #endif
 
 #endif /* RTPT_H */

@@ -34,6 +34,7 @@ BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
 DEBUG_HIT_ID, DEBUG_PREV_PIXEL = 0x1, 0x2
+TEX_NEAREST = 0x1  # rtpt_texture.flags: nearest texel instead of bilinear
 
 # rtpt_plane
 (PLANE_IMAGE, PLANE_FILTERED, PLANE_PREVIOUS, PLANE_WORLDPOS, PLANE_GRADIENT, PLANE_DEPTH, PLANE_VIS_ID,
@@ -115,6 +116,7 @@ SYMBOLS = [
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
     "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
+    "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
 ]
 
 _lib = None
@@ -183,6 +185,10 @@ def load() -> C.CDLL:
         "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_live_device_bytes": [C.POINTER(C.c_uint64)],
         "rtpt_util_load_obj_materials": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
+        "rtpt_scene_set_textures": [vp, vp, vp, u32, vp, u32, vp, sz],
+        "rtpt_selftest_texture": [vp, u32, vp, sz, vp],
+        "rtpt_util_load_obj_texcoords": [C.c_char_p, vp, C.POINTER(u32)],
+        "rtpt_util_load_obj_map_kd": [C.c_char_p, vp, C.POINTER(sz), C.POINTER(u32)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -253,6 +259,27 @@ def load_obj_materials(path: str):
     mats = np.zeros((nm.value, 6), np.float32)
     _check(load().rtpt_util_load_obj_materials(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
     return tri, mats
+
+
+def load_obj_texcoords(path: str) -> np.ndarray:
+    """tri_uv[t, 6] f32 (u0 v0 u1 v1 u2 v2), lined up with load_obj's triangles; corners without `vt` are (0, 0)"""
+    nt = C.c_uint32()
+    _check(load().rtpt_util_load_obj_texcoords(path.encode(), None, C.byref(nt)))
+    uv = np.zeros((nt.value, 6), np.float32)
+    _check(load().rtpt_util_load_obj_texcoords(path.encode(), _ptr(uv), C.byref(nt)))
+    return uv
+
+
+def load_obj_map_kd(path: str):
+    """the `map_Kd` file name of every material in load_obj_materials' numbering ('' = none; entry 0 is the default
+    material); None when the OBJ names no readable library"""
+    nb, nm = C.c_size_t(), C.c_uint32()
+    _check(load().rtpt_util_load_obj_map_kd(path.encode(), None, C.byref(nb), C.byref(nm)))
+    if nm.value == 0:
+        return None
+    buf = C.create_string_buffer(max(nb.value, 1))
+    _check(load().rtpt_util_load_obj_map_kd(path.encode(), buf, C.byref(nb), C.byref(nm)))
+    return [n.decode() for n in buf.raw[:nb.value].split(b"\0")[:nm.value]]
 
 
 _PLANE_DTYPE = {
@@ -393,6 +420,20 @@ class Context:
         mats = np.ascontiguousarray(materials, np.float32).reshape(-1, 6)
         _check(self._lib.rtpt_scene_set_materials(self._h, _ptr(tri), len(tri), _ptr(mats), len(mats)))
 
+    def set_textures(self, tri_uv=None, tri_texture=None, textures=None, texels=None):
+        """albedo textures (rtpt_scene_set_textures): tri_uv [t, 6] f32, tri_texture [t] u32 (0 = untextured, i + 1 =
+        textures[i]), textures [n, 4] u32 rows (width, height, first_texel, flags), texels [m, 4] f32 RGBA; None drops them"""
+        if tri_uv is None or tri_texture is None or textures is None or texels is None:
+            _check(self._lib.rtpt_scene_set_textures(self._h, None, None, 0, None, 0, None, 0))
+            return
+        uv = np.ascontiguousarray(tri_uv, np.float32).reshape(-1, 6)
+        tri = np.ascontiguousarray(tri_texture, np.uint32).ravel()
+        if len(uv) != len(tri):
+            raise ValueError("one uv record and one texture index per triangle")
+        desc = np.ascontiguousarray(textures, np.uint32).reshape(-1, 4)
+        tex = np.ascontiguousarray(texels, np.float32).reshape(-1, 4)
+        _check(self._lib.rtpt_scene_set_textures(self._h, _ptr(uv), _ptr(tri), len(tri), _ptr(desc), len(desc), _ptr(tex), len(tex)))
+
     # -- passes
     def gbuffer(self, ubo: Ubo, y0=0, y1=0):
         _check(self._lib.rtpt_gbuffer(self._h, C.byref(ubo), y0, y1))
@@ -497,6 +538,13 @@ class Context:
         first = np.zeros(2, np.uint32)
         _check(self._lib.rtpt_selftest_div(self._h, mode, first_pass, n_passes, C.byref(n), _ptr(first)))
         return int(n.value), first
+
+    def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:
+        """[n, 4] RGBA the device sampler reads from textures[texture] at uv [n, 2] (rtpt_selftest_texture)"""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 4), np.float32)
+        _check(self._lib.rtpt_selftest_texture(self._h, texture, _ptr(uv), len(uv), _ptr(out)))
+        return out
 
     def selftest_trace(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

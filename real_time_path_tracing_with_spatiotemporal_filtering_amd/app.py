@@ -74,6 +74,12 @@ class HipBackend:
     def scene_set_instances(self, xforms):
         self.ctx.scene_set_instances(xforms)
 
+    def set_materials(self, tri_material, materials):
+        self.ctx.set_materials(tri_material, materials)
+
+    def set_textures(self, tri_uv=None, tri_texture=None, textures=None, texels=None):
+        self.ctx.set_textures(tri_uv, tri_texture, textures, texels)
+
     def gbuffer(self, ubo, y0, y1):
         self.ctx.gbuffer(ubo, y0, y1)
 
@@ -263,6 +269,14 @@ class PipelinedBackend:
     def scene_set_instances(self, xforms):
         for b in self.be:   # both contexts trace the scene: each is re-posed on its own stream
             b.scene_set_instances(xforms)
+
+    def set_materials(self, tri_material, materials):
+        for b in self.be:
+            b.set_materials(tri_material, materials)
+
+    def set_textures(self, tri_uv=None, tri_texture=None, textures=None, texels=None):
+        for b in self.be:   # both contexts shade
+            b.set_textures(tri_uv, tri_texture, textures, texels)
 
     def gbuffer(self, ubo, y0, y1):
         self.cur.gbuffer(ubo, y0, y1)
@@ -734,9 +748,12 @@ class PathTracingApplication:
 
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
-             frames_in_flight=1, samples_per_pixel=1, splits=(), **app_kw):
+             frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
-    the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank)."""
+    the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
+    `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
+    material library — Kd / Ke as rtpt_app does, and the `map_Kd` images (P6 / PFM, next to the OBJ) sampled at every hit —
+    to every context of this rank (textures.py; `texture_filter` = "bilinear" or "nearest")."""
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())
     if torch_planes is None:
         torch_planes = world > 1  # halo exchange and the history all-gather move rows of torch-owned planes
@@ -755,4 +772,15 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     else:
         app.loadMesh(scene)
     app.buildAccelerationStructure(instance_xforms)
+    if texture_filter not in ("bilinear", "nearest"):
+        raise ValueError("texture_filter must be 'bilinear' or 'nearest'")
+    if textures:
+        if mesh is not None:
+            raise ValueError("textures=True reads the OBJ's library: it needs `scene`, not `mesh`")
+        from .textures import load_obj_textures
+        t = load_obj_textures(scene, nearest=texture_filter == "nearest")
+        if t.materials is not None:
+            be.set_materials(t.tri_material, t.materials)
+        if t.textures is not None:
+            be.set_textures(t.tri_uv, t.tri_texture, t.textures, t.texels)
     return app

@@ -168,6 +168,14 @@ rt::SceneView scene_view(const rtpt_ctx* c) {
   return s;
 }
 
+rt::TexView tex_view(const rtpt_ctx* c) {
+  rt::TexView t;
+  t.records = static_cast<const float4*>(c->scene.textures.records.ptr);
+  t.desc = static_cast<const rt::TexDesc*>(c->scene.textures.desc.ptr);
+  t.texels = static_cast<const float4*>(c->scene.textures.texels.ptr);
+  return t;
+}
+
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose
 // view-space axes are the columns c0,c1,c2 and whose pixel (x,y) looks along
 // (nx/p00, ny/p11, -1), nx = (2(x+.5)-W)/W, ny = (2(y+.5)-H)/H  (the K0 ray; the K2 camera is the

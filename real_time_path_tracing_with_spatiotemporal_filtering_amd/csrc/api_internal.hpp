@@ -184,6 +184,11 @@ struct Scene {
   uint64_t lut_version[2] = {~0ull, ~0ull};  // model_version each LUT buffer was built for
   bool lut_prev_valid = false;               // D3
   Buf materials;                             // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
+  // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
+  struct Textures {
+    Buf records, desc, texels;
+    uint32_t n_textures = 0;
+  } textures;
   struct rtpt_scene_build_info build_info {};
   bool build_ms_pending = false;  // build_ms is still in rtpt_ctx::build_ev; read lazily by rtpt_scene_build_info
 };
@@ -330,6 +335,7 @@ size_t plane_size(const rtpt_ctx* c, rtpt_plane which);
 int check_rows(const rtpt_ctx* c, uint32_t& y0, uint32_t& y1);
 rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1);
 rt::SceneView scene_view(const rtpt_ctx* c);
+rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3], double p00, double p11,
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);

@@ -2,6 +2,7 @@
 // :687-742; flattened on the host, or on the device: scene_flatten.hip), instances that move between frames
 // (rtpt_scene_set_instances), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
 #include "api_internal.hpp"
+#include "texture_host.hpp"
 
 #include <chrono>
 
@@ -663,6 +664,47 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->scene.materials = std::move(recs);
+  return RTPT_OK;
+}
+
+int rtpt_scene_set_textures(rtpt_ctx* c, const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris, const rtpt_texture* textures,
+                            uint32_t n_textures, const float* texels, size_t n_texels) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const bool drop = !tri_uv || !tri_texture || !textures || !texels || !n_textures || !n_texels;
+  // everything that can refuse the call comes first: a refused call leaves the scene, and the textures it has, untouched
+  if (!drop)
+    if (const char* why = rtpt_tex::check_textures(tri_uv, tri_texture, n_tris, c->scene.n_base_tris, textures, n_textures, n_texels))
+      return fail(RTPT_E_INVALID, why);
+  std::vector<float> rec;
+  if (!drop) {
+    try {
+      rec.resize(static_cast<size_t>(n_tris) * 8);
+    } catch (const std::bad_alloc&) {
+      return fail(RTPT_E_NOMEM, "host allocation failed (texture records)");
+    }
+    rtpt_tex::pack_records(tri_uv, tri_texture, n_tris, rec.data());
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the set being replaced
+  // K0, K1 and the filter read no texture: no plane tag, no scene generation changes — frame reuse goes on
+  if (drop) {
+    c->scene.textures = Scene::Textures{};
+    return RTPT_OK;
+  }
+  static_assert(sizeof(rtpt_texture) == sizeof(rt::TexDesc), "the descriptors are copied as they are");
+  Scene::Textures t;  // joins the scene when it is complete; the set it replaces stays until then
+  int rc;
+  if ((rc = alloc_buf(t.records, rec.size() * sizeof(float))) || (rc = alloc_buf(t.desc, static_cast<size_t>(n_textures) * sizeof(rtpt_texture))) ||
+      (rc = alloc_buf(t.texels, n_texels * 16)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(t.records.ptr, rec.data(), t.records.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(t.desc.ptr, textures, t.desc.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(t.texels.ptr, texels, t.texels.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays and `rec` may die at return
+  t.n_textures = n_textures;
+  c->scene.textures = std::move(t);
   return RTPT_OK;
 }
 

@@ -1,6 +1,7 @@
 // api_selftest.hip — self tests of the device arithmetic and of the acceleration structure, and the host-side stand-ins
 // for glm / tinyobjloader (rtpt_util_*): nothing a frame calls.
 #include "api_internal.hpp"
+#include "texture_host.hpp"
 
 extern "C" {
 
@@ -106,6 +107,31 @@ int rtpt_selftest_trace(rtpt_ctx* c, const float* rays, size_t n, uint32_t* out_
   (void)hipFree(did);
   (void)hipFree(dt);
   if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_trace: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
+int rtpt_selftest_texture(rtpt_ctx* c, uint32_t texture, const float* uv, size_t n, float* rgba_out) {
+  if (!c || !uv || !rgba_out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const Scene::Textures& t = c->scene.textures;
+  if (!t.desc.ptr || texture >= t.n_textures) return fail(RTPT_E_INVALID, "no such texture (rtpt_scene_set_textures)");
+  for (size_t i = 0; i < 2 * n; i++)
+    if (!std::isfinite(uv[i])) return fail(RTPT_E_INVALID, "a uv coordinate is not finite");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  Buf duv, dout;
+  int rc;
+  if ((rc = alloc_buf(duv, n * 8)) || (rc = alloc_buf(dout, n * 16))) return rc;
+  hipError_t e = hipMemcpyAsync(duv.ptr, uv, n * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_texture(static_cast<const rt::TexDesc*>(t.desc.ptr) + texture, static_cast<const float4*>(t.texels.ptr),
+                                static_cast<const float*>(duv.ptr), n, static_cast<float4*>(dout.ptr), c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, dout.ptr, n * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_texture: ") + hipGetErrorString(e));
   return RTPT_OK;
 }
 
@@ -529,6 +555,34 @@ int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint3
     std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material));
   }
   *n_materials = static_cast<uint32_t>(mats.size());
+  return RTPT_OK;
+}
+
+// the texcoord / map_Kd side of the OBJ reader lives in texture_host.hpp (host-only code a plain C++ program can exercise)
+int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris) {
+  if (!path || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
+  std::string err;
+  if (rtpt_tex::load_obj_texcoords(path, tri_uv, n_tris, &err)) return fail(RTPT_E_INVALID, err);
+  return RTPT_OK;
+}
+
+int rtpt_util_load_obj_map_kd(const char* path, char* names, size_t* names_bytes, uint32_t* n_materials) {
+  if (!path || !names_bytes || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
+  std::string err;
+  std::vector<std::string> maps;
+  if (rtpt_tex::load_obj_map_kd(path, &maps, &err)) return fail(RTPT_E_INVALID, err);
+  size_t need = 0;
+  for (const std::string& m : maps) need += m.size() + 1;
+  if (names) {
+    if (*names_bytes < need) return fail(RTPT_E_INVALID, "names array too small");
+    char* o = names;
+    for (const std::string& m : maps) {
+      std::memcpy(o, m.c_str(), m.size() + 1);
+      o += m.size() + 1;
+    }
+  }
+  *names_bytes = need;
+  *n_materials = static_cast<uint32_t>(maps.size());
   return RTPT_OK;
 }
 

@@ -727,8 +727,12 @@ constexpr int kPtThreads = kBlockX * kPtRows;
 // diffuse bounce.  Returns true when the path ended (its colour is then `acc`).
 // alb_px (RTPT_FLAG_EXT_DEMODULATE; non-NULL only at segment 0 of the tile kernel): the pixel of PathtraceArgs::albedo.  The
 // albedo of this hit goes there instead of into the throughput, and a path that ends here stores (1, 1, 1) and keeps its colour.
+// TEX: the scene has albedo textures (rtpt_scene_set_textures): the albedo is (Kd or the normal-keyed colour) x texel.rgb, one
+// multiply per channel, at every segment.  A compile-time switch for DEMOD's reason: the instantiations without it are the
+// kernels of a build that knows no textures, register for register.
+template <bool TEX>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
-                                              f3& acc, uint32_t& rng, float4* alb_px = nullptr) {
+                                              f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
     if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -757,6 +761,16 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       return true;
     }
     alb = f3{m0.x, m0.y, m0.z};
+  }
+  if (TEX) {
+    const float4* tr = tex.records + 2 * static_cast<size_t>((h.id1 - 1) % a.scene.n_base_tris);
+    const float4 t0 = tr[0], t1 = tr[1];
+    const uint32_t ti = __float_as_uint(t1.z);
+    if (ti) {
+      const float tu = tex::interp_uv(b0, b1, b2, t0.x, t0.z, t1.x), tv = tex::interp_uv(b0, b1, b2, t0.y, t0.w, t1.y);
+      const float4 tx = tex::sample(tex.desc[ti - 1], tex.texels, tu, tv);
+      alb = f3{alb.x * tx.x, alb.y * tx.y, alb.z * tx.z};
+    }
   }
   if (alb_px)
     *alb_px = make_float4(alb.x, alb.y, alb.z, 0.0f);  // demodulated: rtpt_modulate / rtpt_present multiply it back
@@ -837,8 +851,9 @@ constexpr int kPtWaves = 8;
 // taller than the tile grid (a.tiles_y rows of tiles).
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
-template <int BVH, bool COMPACT, bool GB, bool DEMOD>
-__device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
+// TEX: shade_segment samples the scene's albedo textures.
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, bool TEX>
+__device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex) {
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
   // Sharing it takes the BVH kernel from 41 to 30 KB per block: 5 instead of 3 resident blocks per CU for a
@@ -925,7 +940,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
         if (y >= a.count_y0 && y < a.count_y1) rays++;
         const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
-        const bool done = shade_segment(a, h, seg, light_c, o, d, acc, rng, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
+        const bool done = shade_segment<TEX>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
         if (done) {
           alive = false;
           if (a.spp == 1) {
@@ -1022,17 +1037,17 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a) {
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
 constexpr int kPtBvhWaves = 8;
-template <int BVH, bool COMPACT, bool DEMOD>
+template <int BVH, bool COMPACT, bool DEMOD, bool TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_pathtrace(PathtraceArgs a) {
-  pathtrace_tile<BVH, COMPACT, false, DEMOD>(a);
+void k_pathtrace(PathtraceArgs a, TexView tex) {
+  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX>(a, tex);
 }
-template <bool COMPACT, bool DEMOD>
+template <bool COMPACT, bool DEMOD, bool TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_pathtrace_small(PathtraceArgs a) {
-  pathtrace_tile<false, COMPACT, false, DEMOD>(a);
+void k_pathtrace_small(PathtraceArgs a, TexView tex) {
+  pathtrace_tile<false, COMPACT, false, DEMOD, TEX>(a, tex);
 }
 
 // K0 + K1 + K2 in one launch (rtpt_gbuffer / rtpt_temporal_gradient recorded right before rtpt_raytrace: main.cpp:1105-1107
@@ -1042,12 +1057,12 @@ void k_pathtrace_small(PathtraceArgs a) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD>
+template <int BVH, bool DEMOD, bool TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
+void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<BVH, true, true, DEMOD>(a);
+    pathtrace_tile<BVH, true, true, DEMOD, TEX>(a, tex);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1056,12 +1071,12 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g) {
     gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
-template <bool DEMOD>
+template <bool DEMOD, bool TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g) {
+void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<0, true, true, DEMOD>(a);
+    pathtrace_tile<0, true, true, DEMOD, TEX>(a, tex);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1071,8 +1086,8 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g) {
   }
 }
 
-template <int BVH>
-__global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a) {
+template <int BVH, bool TEX>
+__global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
   __shared__ uint32_t wave_cnt[kPtRows];
@@ -1107,7 +1122,7 @@ __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a)
         closest_hit<BVH>(a.scene, o, d, h, stack, tid, kPtThreads, 1 + static_cast<int>(seg));  // :208-222
         const int x = static_cast<int>(pix & 0xFFFFu), y = static_cast<int>(pix >> 16);
         if (y >= a.count_y0 && y < a.count_y1) rays++;
-        if (shade_segment(a, h, seg, light_c, o, d, acc, rng)) {
+        if (shade_segment<TEX>(a, h, seg, light_c, o, d, acc, rng, tex)) {
           alive = false;
           const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
           a.image[gi] = make_float4(acc.x, acc.y, acc.z, a.depth[gi]);  // :328,:343 (+ depth in alpha)
@@ -1245,6 +1260,13 @@ __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const
   if (out_t) out_t[i] = h.id1 ? h.t : 0.0f;
 }
 
+// the sampler of texture.hpp at arbitrary uv (rtpt_selftest_texture)
+__global__ void k_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = tex::sample(*desc, texels, uv[2 * i], uv[2 * i + 1]);
+}
+
 }  // namespace
 
 #if RTPT_BVH_COUNT || RTPT_TILE_TIMELINE
@@ -1315,10 +1337,11 @@ uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
   const int tr = pathtrace_uses_pool(a) ? kPoolRows : kPtRows;
   return gx * ((a.g.y1 - a.g.y0 + tr - 1) / tr + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0));
 }
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t s) {
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, hipStream_t s) {
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
-  const bool pool = pathtrace_uses_pool(a);
+  const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
+  const bool textured = tex.records != nullptr;  // rtpt_scene_set_textures: the instantiations that sample the atlas
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
@@ -1347,23 +1370,27 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t
       hipLaunchKernelGGL((k_pathtrace_pool<false>), grid, block, dyn, s, b, GbufferArgs{});
   } else
 #endif
+  // the instantiation list of the family: scene mode x DEMOD x TEX (x COMPACT for the unfused launch), here and nowhere else
   with_scene_mode(a.scene, [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
       constexpr bool D = decltype(demod)::value;
-      if (gb) {
-        if constexpr (M != 0)
-          hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D>), grid, block, dyn, s, b, *gb);
-        else
-          hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D>), grid, block, dyn, s, b, *gb);
-        return;
-      }
-      with_bool(a.compact != 0, [&](auto compact) {
-        constexpr bool C = decltype(compact)::value;
-        if constexpr (M != 0)
-          hipLaunchKernelGGL((k_pathtrace<M, C, D>), grid, block, dyn, s, b);
-        else
-          hipLaunchKernelGGL((k_pathtrace_small<C, D>), grid, block, dyn, s, b);
+      with_bool(textured, [&](auto tex_on) {
+        constexpr bool T = decltype(tex_on)::value;
+        if (gb) {
+          if constexpr (M != 0)
+            hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T>), grid, block, dyn, s, b, *gb, tex);
+          else
+            hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T>), grid, block, dyn, s, b, *gb, tex);
+          return;
+        }
+        with_bool(a.compact != 0, [&](auto compact) {
+          constexpr bool C = decltype(compact)::value;
+          if constexpr (M != 0)
+            hipLaunchKernelGGL((k_pathtrace<M, C, D, T>), grid, block, dyn, s, b, tex);
+          else
+            hipLaunchKernelGGL((k_pathtrace_small<C, D, T>), grid, block, dyn, s, b, tex);
+        });
       });
     });
   });
@@ -1382,7 +1409,11 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t
     c.q_out = more ? a.queue[cur ^ 1] : nullptr;
     c.q_out_count = more ? a.queue_count + (cur ^ 1) * kPathQueues : nullptr;
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
-    with_scene_mode(a.scene, [&](auto mode) { hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value>), qgrid, block, dyn_queue, s, c); });
+    with_scene_mode(a.scene, [&](auto mode) {
+      with_bool(textured, [&](auto tex_on) {
+        hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_on)::value>), qgrid, block, dyn_queue, s, c, tex);
+      });
+    });
     if (end >= a.max_segments) break;
   }
 }
@@ -1395,6 +1426,10 @@ void launch_selftest_exhaustive(int op, unsigned long long* out, hipStream_t s) 
 }
 void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipStream_t s) {
   hipLaunchKernelGGL(k_selftest_div, dim3((1u << 23) / 256u), dim3(256), 0, s, mode, pass, out);
+}
+void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_texture, dim3((n + 255) / 256), dim3(256), 0, s, desc, texels, uv, n, out);
 }
 void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, float tmax, uint32_t* out_id,
                            float* out_t, hipStream_t s) {

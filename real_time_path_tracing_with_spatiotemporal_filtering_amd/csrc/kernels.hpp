@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bvh.hpp"
+#include "texture.hpp"
 
 namespace rt {
 
@@ -38,6 +39,17 @@ struct SceneView {
   //   m0 = (Kd.rgb, 0)  m1 = (Ke.rgb, 1 if emissive else 0).  NULL: the reference's normal-keyed colours
   const float4* materials;
   uint32_t n_base_tris;
+};
+
+// Optional albedo textures of the BASE mesh (rtpt_scene_set_textures; texture.hpp): two float4 per triangle (corner uvs and the
+// texture index), the descriptors, and the RGBA32F atlas they index.  All NULL without textures.  It travels as the LAST
+// parameter of the path-trace kernels, not inside SceneView: as three more pointers there it moved every later field of
+// PathtraceArgs / GbufferArgs by 24 bytes, and the 1,152,000-triangle frame measured 0.1 % slower with textures off.  Behind
+// the other arguments it leaves every existing offset, and so the code of the TEX = false instantiations, as it was.
+struct TexView {
+  const float4* records;
+  const TexDesc* desc;
+  const float4* texels;
 };
 
 // Screen-space bounds of every triangle of a small scene (<= 64), computed on the host per call and
@@ -310,7 +322,7 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
 void launch_gradient(const GradientArgs& a, hipStream_t s);
 // gb != NULL: K0 (+ K1) of gb's rows run inside the tile kernel's launch, behind the tracing tiles (pathtrace_fuses_gbuffer says
 // whether they can; pathtrace_grid_blocks = the workgroups of that launch, what the BVH stack's spill area is sized for)
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, hipStream_t s);
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, hipStream_t s);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
 bool pathtrace_uses_pool(const PathtraceArgs& a);
@@ -352,5 +364,7 @@ void launch_selftest_exhaustive(int op, unsigned long long* out, hipStream_t s);
 void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipStream_t s);
 void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, float tmax, uint32_t* out_id,
                            float* out_t, hipStream_t s);
+// tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
+void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 
 }  // namespace rt

@@ -1,0 +1,197 @@
+// texture_host.hpp — the host side of the albedo textures, free of HIP so that a plain C++ program can exercise it (and a
+// sanitizer build of that program can: csrc/tests/texture_host_check.cpp): the texcoord and map_Kd side of the OBJ / MTL
+// reader, the checks rtpt_scene_set_textures applies before anything reaches the device, and the record packing.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/rtpt.h"
+
+namespace rtpt_tex {
+
+// limits a descriptor must meet so that the sampler's 32-bit index arithmetic (texture.hpp) cannot wrap
+constexpr uint32_t kMaxTexDim = 65536u;
+constexpr float kMaxUv = 18446744073709551616.0f;  // 2^64: interpolated coordinates of such corners stay finite
+
+// Everything rtpt_scene_set_textures refuses, decided on arguments alone.  NULL: the arguments are fine.
+inline const char* check_textures(const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris, uint32_t n_base_tris,
+                                  const rtpt_texture* textures, uint32_t n_textures, size_t n_texels) {
+  if (n_tris != n_base_tris) return "one uv record and one texture index per triangle of the uploaded mesh";
+  for (uint32_t i = 0; i < n_textures; i++) {
+    const rtpt_texture& t = textures[i];
+    if (t.width == 0 || t.height == 0) return "a texture has a zero dimension";
+    if (t.width > kMaxTexDim || t.height > kMaxTexDim) return "a texture is larger than 65536 texels along an axis";
+    if (t.flags & ~static_cast<uint32_t>(RTPT_TEX_NEAREST)) return "unknown texture flag";
+    const uint64_t end = static_cast<uint64_t>(t.first_texel) + static_cast<uint64_t>(t.width) * t.height;
+    if (end > n_texels || end > 0xFFFFFFFFull) return "a texture's rectangle lies beyond the texel array";
+  }
+  for (uint32_t t = 0; t < n_tris; t++) {
+    if (tri_texture[t] > n_textures) return "texture index out of range";
+    for (int k = 0; k < 6; k++) {
+      const float c = tri_uv[6 * static_cast<size_t>(t) + k];
+      if (!(std::fabs(c) <= kMaxUv)) return "a uv coordinate is not finite (or beyond 2^64)";
+    }
+  }
+  return nullptr;
+}
+
+// n_tris records of 8 floats: (u0 v0 u1 v1) (u2 v2, texture index as bits, 0) — TexView::records
+inline void pack_records(const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris, float* out) {
+  for (uint32_t t = 0; t < n_tris; t++) {
+    float* r = out + 8 * static_cast<size_t>(t);
+    std::memcpy(r, tri_uv + 6 * static_cast<size_t>(t), 6 * sizeof(float));
+    std::memcpy(r + 6, tri_texture + t, sizeof(uint32_t));
+    r[7] = 0.0f;
+  }
+}
+
+// bytes of device memory a set of textures holds (the formula include/rtpt.h documents)
+inline size_t device_bytes(uint32_t n_tris, uint32_t n_textures, size_t n_texels) {
+  return 32 * static_cast<size_t>(n_tris) + 16 * static_cast<size_t>(n_textures) + 16 * n_texels;
+}
+
+inline const char* skip_blank(const char* p) {
+  while (*p == ' ' || *p == '\t') p++;
+  return p;
+}
+inline bool at_end(const char* p) { return *p == '\0' || *p == '\n' || *p == '\r'; }
+
+// The texcoord side of an OBJ: `vt u v` records and the vt part of `f v/vt`, `f v/vt/vn` corners (`f v`, `f v//vn`: no
+// texcoord, the corner gets (0, 0)); negative indices count back from the last `vt` read.  Polygons fan exactly like
+// rtpt_util_load_obj (0, k, k + 1), so tri_uv lines up with its index array.  tri_uv may be NULL (count only).
+// Returns 0, or -1 with *err set.
+inline int load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris, std::string* err) {
+  FILE* fp = std::fopen(path, "r");
+  if (!fp) {
+    *err = std::string("cannot open ") + path;
+    return -1;
+  }
+  std::vector<float> vt;
+  std::vector<float> poly;  // u, v per corner
+  uint32_t nt = 0;
+  int rc = 0;
+  char line[2048];
+  while (std::fgets(line, sizeof line, fp)) {
+    const char* p = skip_blank(line);
+    if (p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t')) {
+      char* end = nullptr;
+      const char* q = p + 3;
+      const float u = std::strtof(q, &end);
+      if (end == q) continue;
+      q = end;
+      float v = std::strtof(q, &end);
+      if (end == q) v = 0.0f;  // `vt u` is legal: v defaults to 0
+      vt.push_back(u);
+      vt.push_back(v);
+    } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
+      poly.clear();
+      const char* q = p + 2;
+      while (*q) {
+        q = skip_blank(q);
+        if (at_end(q)) break;
+        char* end = nullptr;
+        (void)std::strtol(q, &end, 10);
+        if (end == q) break;
+        q = end;
+        float u = 0.0f, v = 0.0f;
+        // the vt number follows the slash at once (strtol would skip a blank and take the next corner's vertex number)
+        if (*q == '/' && (q[1] == '-' || q[1] == '+' || (q[1] >= '0' && q[1] <= '9'))) {
+          const long t = std::strtol(q + 1, &end, 10);
+          if (end != q + 1) {
+            const long n = static_cast<long>(vt.size() / 2);
+            const long r = t > 0 ? t - 1 : n + t;
+            if (r < 0 || r >= n) {
+              *err = "OBJ texcoord index out of range";
+              rc = -1;
+            } else {
+              u = vt[2 * static_cast<size_t>(r)];
+              v = vt[2 * static_cast<size_t>(r) + 1];
+            }
+            q = end;
+          }
+        }
+        poly.push_back(u);
+        poly.push_back(v);
+        while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;  // the rest of the corner ("/vn")
+      }
+      const size_t corners = poly.size() / 2;
+      for (size_t k = 1; k + 1 < corners; k++) {
+        if (tri_uv) {
+          float* o = tri_uv + 6 * static_cast<size_t>(nt);
+          o[0] = poly[0], o[1] = poly[1];
+          o[2] = poly[2 * k], o[3] = poly[2 * k + 1];
+          o[4] = poly[2 * k + 2], o[5] = poly[2 * k + 3];
+        }
+        nt++;
+      }
+    }
+  }
+  std::fclose(fp);
+  *n_tris = nt;
+  return rc;
+}
+
+// The `map_Kd` file name of every material of the OBJ's libraries, in rtpt_util_load_obj_materials' numbering: entry 0 is
+// the default material (never textured), entry i the i-th `newmtl` over all `mtllib` files in file order.  Empty string: no
+// map.  Options before the name (`-s 1 1 1 file`) are not supported: the last word of the line is the name.
+// Returns 0 (names empty when the OBJ names no readable library), or -1 with *err set.
+inline int load_obj_map_kd(const char* path, std::vector<std::string>* names, std::string* err) {
+  names->clear();
+  FILE* fp = std::fopen(path, "r");
+  if (!fp) {
+    *err = std::string("cannot open ") + path;
+    return -1;
+  }
+  std::string dir(path);
+  const size_t slash = dir.find_last_of('/');
+  dir = slash == std::string::npos ? std::string() : dir.substr(0, slash + 1);
+  auto word = [](const char* q, std::string& out) {
+    q = skip_blank(q);
+    out.clear();
+    while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') out.push_back(*q++);
+  };
+  bool any_library = false;
+  std::vector<std::string> maps{std::string()};
+  char line[2048];
+  while (std::fgets(line, sizeof line, fp)) {
+    const char* p = skip_blank(line);
+    if (std::strncmp(p, "mtllib", 6) || !(p[6] == ' ' || p[6] == '\t')) continue;
+    std::string file;
+    word(p + 6, file);
+    FILE* mf = std::fopen((dir + file).c_str(), "r");
+    if (!mf) continue;
+    any_library = true;
+    char ln[1024];
+    bool in_material = false;
+    while (std::fgets(ln, sizeof ln, mf)) {
+      const char* m = skip_blank(ln);
+      if (!std::strncmp(m, "newmtl", 6) && (m[6] == ' ' || m[6] == '\t')) {
+        maps.emplace_back();
+        in_material = true;
+      } else if (in_material && !std::strncmp(m, "map_Kd", 6) && (m[6] == ' ' || m[6] == '\t')) {
+        std::string last, w;
+        const char* q = m + 6;
+        for (;;) {
+          q = skip_blank(q);
+          if (at_end(q)) break;
+          word(q, w);
+          q += w.size();
+          last = w;
+        }
+        maps.back() = last;
+      }
+    }
+    std::fclose(mf);
+  }
+  std::fclose(fp);
+  if (any_library) names->swap(maps);
+  return 0;
+}
+
+}  // namespace rtpt_tex

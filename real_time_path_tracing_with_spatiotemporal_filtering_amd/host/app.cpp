@@ -69,6 +69,11 @@ void PathTracingApplication::loadMesh() {
     check(rtpt_util_load_obj_materials(opt_.scene.c_str(), triMaterial.data(), &ntm, objMaterials.data(), &nm), "loadMesh");
   }
   // configs[4]: tessellated quads on a lattice of instances (scene_gen.hpp); camera, light and far plane frame the lattice
+  sceneTextures_ = SceneTextures{};
+  if (opt_.textures) {
+    if (opt_.tessellate > 1) throw std::runtime_error("--tessellate does not carry texture coordinates over");
+    sceneTextures_ = load_scene_textures(opt_.scene, triMaterial, opt_.textures_nearest);
+  }
   if (opt_.tessellate > 1) {
     if (!objMaterials.empty()) throw std::runtime_error("--tessellate does not carry a material library over");
     if (!tessellate_quads(objVertices, objIndices, opt_.tessellate, objVertices, objIndices))
@@ -179,6 +184,11 @@ void PathTracingApplication::buildAccelerationStructure() {
       check(rtpt_scene_set_materials(ctx, triMaterial.data(), static_cast<uint32_t>(triMaterial.size()), objMaterials.data(),
                                      static_cast<uint32_t>(objMaterials.size())),
             "rtpt_scene_set_materials");
+    const SceneTextures& t = sceneTextures_;
+    if (!t.textures.empty())
+      check(rtpt_scene_set_textures(ctx, t.tri_uv.data(), t.tri_texture.data(), static_cast<uint32_t>(t.tri_texture.size()), t.textures.data(),
+                                    static_cast<uint32_t>(t.textures.size()), t.texels.data(), t.texels.size() / 4),
+            "rtpt_scene_set_textures");
   };
   // main.cpp:728-741: the instance list (one identity transform in the reference; the lattice of configs[4] here)
   const float* xf = instanceXforms_.empty() ? nullptr : instanceXforms_.data();

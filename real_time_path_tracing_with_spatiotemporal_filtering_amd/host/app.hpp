@@ -11,6 +11,7 @@
 
 #include "../../include/rtpt.h"
 #include "strips.hpp"
+#include "textures.hpp"
 
 namespace rtpt_host {
 
@@ -25,6 +26,10 @@ struct Options {
   // a lattice of translations (the reference's own instance list is one identity transform, main.cpp:728-741); the camera,
   // the light and the far plane then frame the lattice.  --lattice 10x10x10 --tessellate 6 = 1,152,000 triangles
   int tessellate = 1;
+  // --textures [--texture-filter nearest|bilinear]: the `map_Kd` images of the OBJ's library (P6 / PFM next to the OBJ) sampled at every hit
+  // (rtpt_scene_set_textures).  Off: an OBJ with map_Kd renders as it always did
+  bool textures = false;
+  bool textures_nearest = false;
   int lattice[3] = {0, 0, 0};           // 0: no instancing (one identity instance)
   float pitch = 2.5f;
   std::string instances;                // text file, 12 floats per instance (3x4 row-major transform): a general instance list
@@ -143,6 +148,7 @@ class PathTracingApplication {
   std::vector<uint32_t> objIndices;            // main.cpp:256
   std::vector<rtpt_material> objMaterials;     // tinyobj's `materials` (main.cpp:419), used when the OBJ has a library
   std::vector<uint32_t> triMaterial;           // material index per triangle
+  SceneTextures sceneTextures_;                // --textures: the library's map_Kd images as one atlas (textures.hpp)
   float cameraOrigin[3] = {-0.001f, 1.0f, 6.0f};  // main.cpp:65
   float lightPos[3] = {1.0f, 1.0f, -0.4f};        // main.cpp:70
   float lightColor[3] = {0.5f, 0.5f, 0.5f};       // main.cpp:72

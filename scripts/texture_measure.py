@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""First numbers for the textured path (rtpt_scene_set_textures): the 4K Cornell box with a 1024 x 1024 checker on every
+surface, nearest and bilinear, against the same scene with materials only (Kd = the checker's mean colour).
+
+    python scripts/texture_measure.py [--width 3840 --height 2160 --segments 4 --frames 200 --warmup 30 --repeats 3]
+
+The three variants run in turn, `repeats` times over (alternating, so that a drift of the machine shows as spread and not
+as a difference); every window is `frames` whole frames (K0 + K1 + K2 + 5 filter iterations) between two device
+synchronisations on the host clock, after `warmup` frames of the same variant.  The light moves every frame so that frame
+reuse serves nothing.  k_pathtrace / k_gbuffer_pathtrace times come from the library's own HIP-event timing in a separate
+short window (bracketing costs time: not mixed with the frame figure).  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def planar_uv(xyz, idx, cells_per_unit):
+    """per-triangle uv: the two coordinates of each corner in the plane of the triangle's dominant normal axis"""
+    v = xyz[idx]
+    n = np.abs(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]))
+    axis = n.argmax(1)
+    keep = np.array([[1, 2], [0, 2], [0, 1]])[axis]
+    uv = np.take_along_axis(v, keep[:, None, :].repeat(3, 1), 2)
+    return (uv * cells_per_unit).reshape(-1, 6).astype(np.float32)
+
+
+def checker(n, cells):
+    c = (np.add.outer(np.arange(n) * cells // n, np.arange(n) * cells // n) & 1).astype(np.float32)
+    im = np.ones((n, n, 4), np.float32)
+    im[..., :3] = np.where(c[..., None] == 0, np.float32([0.9, 0.85, 0.8]), np.float32([0.3, 0.35, 0.4]))
+    return im
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--segments", type=int, default=4)
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--texture", type=int, default=1024)
+    a = ap.parse_args()
+    import torch  # noqa: F401  (before the library: one ROCm runtime for both)
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd.app import DEFAULT_SCENE, make_app
+    xyz, idx = abi.load_obj(DEFAULT_SCENE)
+    n = len(idx)
+    im = checker(a.texture, 16)
+    mean = im[..., :3].reshape(-1, 3).mean(0)
+    tri = np.zeros(n, np.uint32)
+    variants = {
+        "materials": (np.array([[*mean, 0, 0, 0]], np.float32), None),
+        "nearest": (np.array([[1, 1, 1, 0, 0, 0]], np.float32), abi.TEX_NEAREST),
+        "bilinear": (np.array([[1, 1, 1, 0, 0, 0]], np.float32), 0),
+    }
+    apps = {}
+    for name, (mats, tflags) in variants.items():
+        app = make_app(a.width, a.height, max_segments=a.segments, iterations=5)
+        app.backend.ctx.set_materials(tri, mats)
+        if tflags is not None:
+            desc = np.array([[a.texture, a.texture, 0, tflags]], np.uint32)
+            app.backend.ctx.set_textures(planar_uv(xyz, idx, 0.5), np.ones(n, np.uint32), desc, im.reshape(-1, 4))
+        apps[name] = app
+
+    def run(app, frames):
+        for f in range(frames):
+            app.drawScene(("J",) if f & 1 else ("L",))     # the light moves: nothing is reused
+        app.backend.sync()
+    ms = {name: [] for name in apps}
+    for _ in range(a.repeats):
+        for name, app in apps.items():
+            run(app, a.warmup)
+            t0 = time.perf_counter()
+            run(app, a.frames)
+            ms[name].append((time.perf_counter() - t0) * 1e3 / a.frames)
+    kernels = {}
+    for name, app in apps.items():
+        ctx = app.backend.ctx
+        ctx.timing_enable(1)
+        run(app, 20)
+        tm = ctx.timing_collect()
+        ctx.timing_enable(0)
+        kernels[name] = {k: round(v[0] / v[1] * 1e3, 1) for k, v in tm.items() if v[1] and "pathtrace" in k}
+        app.backend.close()
+    out = {"size": [a.width, a.height], "segments": a.segments, "texture": a.texture, "frames": a.frames, "repeats": a.repeats,
+           "frame_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+           "frame_ms_median": {k: round(float(np.median(v)), 4) for k, v in ms.items()},
+           "trace_kernel_us": kernels}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
