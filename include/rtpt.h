@@ -333,8 +333,28 @@ int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32
  * untextured, i + 1 = textures[i]; instances share both (triangle id reads record id % n_tris).  texels: RGBA32F, linear,
  * row-major, row 0 is v in [0, 1/height); texture i owns texels [first_texel, first_texel + width * height); alpha is
  * carried and ignored.  Coordinates repeat (s = u - floor(u)); the filter is bilinear unless RTPT_TEX_NEAREST is set; no
- * mip-mapping.  Everything is copied: the arrays may die at return.
- * Device memory held, counted by rtpt_debug_live_device_bytes: exactly 32 * n_tris + 16 * n_textures + 16 * n_texels bytes.
+ * mip-mapping unless RTPT_TEX_MIPMAP is set (below).  Everything is copied: the arrays may die at return.
+ * Device memory held, counted by rtpt_debug_live_device_bytes: exactly 32 * n_tris + 16 * n_textures + 16 * n_texels bytes
+ * when no texture has a mip flag.
+ * Mip-mapping, opt-in per texture (RTPT_TEX_MIPMAP): level l of a W x H texture is max(1, W >> l) x max(1, H >> l) texels and
+ * there are floor(log2(max(W, H))) + 1 levels (rtpt_util_texture_chain).  Texel (x, y) of level l + 1 is the binary32 value
+ * ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, w - 1), 2y) and the same columns of row min(2y + 1, h - 1)
+ * of level l, all four channels: an odd last column or row is dropped, except where the level is one texel wide or high.
+ * The library builds the levels on the device from `texels`, which holds level 0 only, as without the flag; with
+ * RTPT_TEX_MIPS_GIVEN the caller supplies them: level l follows level l - 1 directly, from first_texel on, and the rectangle
+ * checked against n_texels is the whole chain.  A hit reads level lambda = 0.5 * plog2(rho^2), clamped to [0, levels - 1]:
+ * rho^2 = w^2 D / (n.d)^2, w the ray's footprint width at the hit (segment 0: t * 2 * fov_slope / height, the full frame's;
+ * every later segment: t * 1/8, t that segment's length alone), D = |twice the triangle's area in level-0 texels| / |twice
+ * its posed world area|, plog2 the piecewise-linear log2 (exponent + mantissa fraction: exact at powers of two, at most
+ * 0.0861 from log2 elsewhere); a degenerate triangle reads level 0.  Bilinear textures blend the bilinear samples of levels
+ * floor(lambda) and floor(lambda) + 1 (a level of weight 0 is not read); RTPT_TEX_NEAREST reads the nearest texel of level
+ * floor(lambda + 0.5).  csrc/texture.hpp states the arithmetic.  Known bias: a bounce reads pre-filtered albedo, so the
+ * converged image of a mip-mapped scene differs slightly from the un-mipped one (the mean of a product of albedos along a
+ * path is not the product of their means); first hits that magnify the texture are unchanged.
+ * With a mip flag on any texture the device holds exactly
+ *   32 * n_tris + 16 * n_textures + 16 * n_texels + 16 * G + 80 * n_textures bytes,
+ * G = the texels of levels 1.. of every texture with RTPT_TEX_MIPMAP and without RTPT_TEX_MIPS_GIVEN (the generated levels),
+ * 80 bytes per texture the table of level offsets.
  * Lifetime, like the materials': rtpt_scene_upload drops the textures; rtpt_scene_set_materials, rtpt_scene_set_instances,
  * rtpt_scene_rebuild, a changed ubo->model and rtpt_resize keep them.  tri_uv, tri_texture, textures or texels NULL, or
  * n_textures / n_texels 0, drops them (every kernel is then the one of a scene that never had any).
@@ -342,9 +362,12 @@ int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32
  * read no texture: frame reuse and reprojection reuse go on across the call.
  * RTPT_E_NO_SCENE before an upload.  RTPT_E_INVALID, with the scene and its textures untouched, for: n_tris other than the
  * uploaded mesh's; tri_texture[t] > n_textures; a zero width or height, or one above 65536; a rectangle that ends beyond
- * n_texels (or beyond 2^32 - 1 texels); an unknown flag; a uv that is not finite (or above 2^64 in magnitude).  No kernel
- * can index outside the atlas: that is decided here, on the host. */
-#define RTPT_TEX_NEAREST 0x1u /* default: bilinear */
+ * n_texels (or beyond 2^32 - 1 texels; the whole chain with RTPT_TEX_MIPS_GIVEN); generated levels that take the atlas
+ * beyond 2^32 - 1 texels; an unknown flag (0x2, 0x4, 0x8 among them); RTPT_TEX_MIPS_GIVEN without RTPT_TEX_MIPMAP; a uv
+ * that is not finite (or above 2^64 in magnitude).  No kernel can index outside the atlas: that is decided here, on the host. */
+#define RTPT_TEX_NEAREST 0x1u     /* default: bilinear */
+#define RTPT_TEX_MIPMAP 0x10u     /* sampled from a mip chain, the level chosen from the ray's footprint */
+#define RTPT_TEX_MIPS_GIVEN 0x20u /* only with RTPT_TEX_MIPMAP: `texels` holds the whole chain of this texture */
 typedef struct rtpt_texture {
   uint32_t width, height, first_texel, flags;
 } rtpt_texture;
@@ -581,6 +604,16 @@ int rtpt_selftest_trace(rtpt_ctx* ctx, const float* rays, size_t n, uint32_t* ou
  * rtpt_scene_set_textures, alpha included.  RTPT_E_NO_SCENE without a scene; RTPT_E_INVALID without textures, for an index
  * >= n_textures or a uv that is not finite. */
 int rtpt_selftest_texture(rtpt_ctx* ctx, uint32_t texture, const float* uv, size_t n, float* rgba_out);
+/* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
+ * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
+ * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */
+int rtpt_selftest_texture_lod(rtpt_ctx* ctx, uint32_t texture, const float* uv, const float* lod, size_t n, float* rgba_out);
+/* Level selection of the tracing kernels: traces n rays (6 floats each, as rtpt_selftest_trace) through the product's
+ * traversal and returns out_id[i] = hit id + 1 (0: miss) and out_lod[i] = the lambda shade_segment would sample the hit's
+ * texture at — computed by the device function the tracing kernels call.  bounce == 0: the rule of segment 0 with the
+ * context's frame height and fov_slope; bounce == 1: the rule of every later segment.  Misses, untextured hits, textures
+ * without RTPT_TEX_MIPMAP and scenes without textures return 0. */
+int rtpt_selftest_texture_footprint(rtpt_ctx* ctx, const float* rays, size_t n, uint32_t bounce, uint32_t* out_id, float* out_lod);
 
 /* ---- host-side helpers shared by the C++ and Python hosts -------------------------------- */
 /* glm::lookAt / glm::perspective as used at main.cpp:482-484,:1470-1472 (right-handed,
@@ -607,6 +640,10 @@ int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tr
  * *names_bytes and the count in *n_materials; with names, *names_bytes in = capacity.  *n_materials comes back 0 when the
  * OBJ names no readable library. */
 int rtpt_util_load_obj_map_kd(const char* path, char* names, size_t* names_bytes, uint32_t* n_materials);
+/* The mip chain of a width x height texture (RTPT_TEX_MIPMAP): *n_levels = floor(log2(max(width, height))) + 1, *n_texels =
+ * the sum over the levels of max(1, width >> l) * max(1, height >> l) — what RTPT_TEX_MIPS_GIVEN expects from first_texel
+ * on.  Either pointer may be NULL.  Needs no GPU.  RTPT_E_INVALID for a zero dimension or one above 65536. */
+int rtpt_util_texture_chain(uint32_t width, uint32_t height, uint32_t* n_levels, uint64_t* n_texels);
 /* Host-only self check of the acceleration-structure builder that stands in for the driver's BLAS/TLAS build
  * (buildAccelerationStructure, main.cpp:687-742): builds the BVH over `n_tris` world-space triangles (9 floats
  * each), packs the device nodes and verifies the invariants the traversal relies on.  Needs no GPU.

@@ -35,6 +35,8 @@ BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
 DEBUG_HIT_ID, DEBUG_PREV_PIXEL = 0x1, 0x2
 TEX_NEAREST = 0x1  # rtpt_texture.flags: nearest texel instead of bilinear
+TEX_MIPMAP = 0x10  # sampled from a mip chain at the level of the ray's footprint; the library generates the chain
+TEX_MIPS_GIVEN = 0x20  # with TEX_MIPMAP: texels holds the whole chain, level l right behind level l - 1
 
 # rtpt_plane
 (PLANE_IMAGE, PLANE_FILTERED, PLANE_PREVIOUS, PLANE_WORLDPOS, PLANE_GRADIENT, PLANE_DEPTH, PLANE_VIS_ID,
@@ -117,6 +119,7 @@ SYMBOLS = [
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
     "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
+    "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain",
 ]
 
 _lib = None
@@ -189,6 +192,9 @@ def load() -> C.CDLL:
         "rtpt_selftest_texture": [vp, u32, vp, sz, vp],
         "rtpt_util_load_obj_texcoords": [C.c_char_p, vp, C.POINTER(u32)],
         "rtpt_util_load_obj_map_kd": [C.c_char_p, vp, C.POINTER(sz), C.POINTER(u32)],
+        "rtpt_selftest_texture_lod": [vp, u32, vp, vp, sz, vp],
+        "rtpt_selftest_texture_footprint": [vp, vp, sz, u32, vp, vp],
+        "rtpt_util_texture_chain": [u32, u32, C.POINTER(u32), C.POINTER(C.c_uint64)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -546,12 +552,36 @@ class Context:
         _check(self._lib.rtpt_selftest_texture(self._h, texture, _ptr(uv), len(uv), _ptr(out)))
         return out
 
+    def selftest_texture_lod(self, texture: int, uv: np.ndarray, lod: np.ndarray) -> np.ndarray:
+        """[n, 4] RGBA the device sampler reads from textures[texture] at uv [n, 2] and level lod [n] (rtpt_selftest_texture_lod)"""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        lod = np.ascontiguousarray(np.broadcast_to(np.asarray(lod, np.float32), (len(uv),)))
+        out = np.zeros((len(uv), 4), np.float32)
+        _check(self._lib.rtpt_selftest_texture_lod(self._h, texture, _ptr(uv), _ptr(lod), len(uv), _ptr(out)))
+        return out
+
+    def selftest_texture_footprint(self, rays: np.ndarray, bounce: int):
+        """(hit id + 1, the level shade_segment would sample the hit's texture at) of rays [n, 6]; bounce 0: the rule of
+        segment 0, 1: of every later segment (rtpt_selftest_texture_footprint)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        ids = np.zeros(len(rays), np.uint32)
+        lod = np.zeros(len(rays), np.float32)
+        _check(self._lib.rtpt_selftest_texture_footprint(self._h, _ptr(rays), len(rays), bounce, _ptr(ids), _ptr(lod)))
+        return ids, lod
+
     def selftest_trace(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         ids = np.zeros(len(rays), np.uint32)
         ts = np.zeros(len(rays), np.float32)
         _check(self._lib.rtpt_selftest_trace(self._h, _ptr(rays), len(rays), _ptr(ids), _ptr(ts)))
         return ids, ts
+
+
+def texture_chain(width: int, height: int):
+    """(levels, texels) of the mip chain of a width x height texture (rtpt_util_texture_chain; needs no GPU)"""
+    n, t = C.c_uint32(0), C.c_uint64(0)
+    _check(load().rtpt_util_texture_chain(width, height, C.byref(n), C.byref(t)))
+    return int(n.value), int(t.value)
 
 
 def bvh_check(tris: np.ndarray, built_for: np.ndarray | None = None, pairs: bool = False) -> dict:

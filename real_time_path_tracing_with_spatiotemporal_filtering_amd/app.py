@@ -748,12 +748,14 @@ class PathTracingApplication:
 
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
-             frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", **app_kw):
+             frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
+             **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
     material library — Kd / Ke as rtpt_app does, and the `map_Kd` images (P6 / PFM, next to the OBJ) sampled at every hit —
-    to every context of this rank (textures.py; `texture_filter` = "bilinear" or "nearest")."""
+    to every context of this rank (textures.py; `texture_filter` = "bilinear" or "nearest"; `texture_mips`: every image is
+    sampled from a generated mip chain at the level of the ray's footprint, RTPT_TEX_MIPMAP)."""
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())
     if torch_planes is None:
         torch_planes = world > 1  # halo exchange and the history all-gather move rows of torch-owned planes
@@ -778,7 +780,7 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
         if mesh is not None:
             raise ValueError("textures=True reads the OBJ's library: it needs `scene`, not `mesh`")
         from .textures import load_obj_textures
-        t = load_obj_textures(scene, nearest=texture_filter == "nearest")
+        t = load_obj_textures(scene, nearest=texture_filter == "nearest", mips=texture_mips)
         if t.materials is not None:
             be.set_materials(t.tri_material, t.materials)
         if t.textures is not None:

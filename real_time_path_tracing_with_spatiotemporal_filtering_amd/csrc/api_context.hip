@@ -173,6 +173,8 @@ rt::TexView tex_view(const rtpt_ctx* c) {
   t.records = static_cast<const float4*>(c->scene.textures.records.ptr);
   t.desc = static_cast<const rt::TexDesc*>(c->scene.textures.desc.ptr);
   t.texels = static_cast<const float4*>(c->scene.textures.texels.ptr);
+  t.levels = static_cast<const uint32_t*>(c->scene.textures.levels.ptr);
+  t.bounce_spread = c->tex_bounce_spread;
   return t;
 }
 
@@ -375,6 +377,10 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
   if (const char* v = std::getenv("RTPT_NO_FRAME_REUSE")) c->frame_reuse = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_NO_REPROJ_REUSE")) c->reproj_reuse = std::atoi(v) == 0;
   if (const char* v = std::getenv("RTPT_TRACE_POOL")) c->trace_pool = std::atoi(v) != 0;
+  if (const char* v = std::getenv("RTPT_TEX_BOUNCE_SPREAD")) {
+    const float f = std::strtof(v, nullptr);
+    if (f > 0.0f && f <= 64.0f) c->tex_bounce_spread = f;
+  }
   if (const char* v = std::getenv("RTPT_PT_WINDOW")) c->trace_window = static_cast<uint32_t>(std::max(0, std::atoi(v)));
   if (const char* v = std::getenv("RTPT_CHAIN_G1")) c->filter_policy.chain_g_pin = std::atoi(v);
   if (const char* v = std::getenv("RTPT_CHAIN_GENERIC")) c->filter_policy.chain_generic = std::atoi(v);

@@ -187,6 +187,7 @@ struct Scene {
   // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
   struct Textures {
     Buf records, desc, texels;
+    Buf levels;  // the level table, only when some texture has RTPT_TEX_MIPMAP; texels then also holds the generated levels
     uint32_t n_textures = 0;
   } textures;
   struct rtpt_scene_build_info build_info {};
@@ -280,6 +281,7 @@ struct rtpt_ctx {
   // segments of a path the tile kernel runs before the survivors go through the queue kernels (kernels.hpp: pt_first_window is
   // the default); RTPT_PT_WINDOW at rtpt_create, 0 = the default
   uint32_t trace_window = 0;
+  float tex_bounce_spread = rt::kTexBounceSpread;  // RTPT_TEX_BOUNCE_SPREAD, for measurements only (texture.hpp)
   Buf path_pool;
   rt::FilterPolicy filter_policy;  // RTPT_CHAIN_* (read once, here: rtpt_create)
   // K3 iterations recorded by rtpt_temporal_filter and not launched yet (see filter_flush)

@@ -677,13 +677,20 @@ int rtpt_scene_set_textures(rtpt_ctx* c, const float* tri_uv, const uint32_t* tr
     if (const char* why = rtpt_tex::check_textures(tri_uv, tri_texture, n_tris, c->scene.n_base_tris, textures, n_textures, n_texels))
       return fail(RTPT_E_INVALID, why);
   std::vector<float> rec;
+  std::vector<uint32_t> levels;  // the level table, when some texture has RTPT_TEX_MIPMAP
+  size_t generated = 0;          // texels of the levels built here, appended to the atlas
   if (!drop) {
     try {
       rec.resize(static_cast<size_t>(n_tris) * 8);
+      if (rtpt_tex::any_mipmap(textures, n_textures)) levels.resize(static_cast<size_t>(n_textures) * rtpt_tex::kLevelRow);
     } catch (const std::bad_alloc&) {
       return fail(RTPT_E_NOMEM, "host allocation failed (texture records)");
     }
     rtpt_tex::pack_records(tri_uv, tri_texture, n_tris, rec.data());
+    if (!levels.empty()) {
+      rtpt_tex::build_level_table(textures, n_textures, n_texels, levels.data());
+      generated = static_cast<size_t>(rtpt_tex::generated_texels(textures, n_textures));  // check_textures: the atlas stays below 2^32
+    }
   }
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
@@ -697,11 +704,23 @@ int rtpt_scene_set_textures(rtpt_ctx* c, const float* tri_uv, const uint32_t* tr
   Scene::Textures t;  // joins the scene when it is complete; the set it replaces stays until then
   int rc;
   if ((rc = alloc_buf(t.records, rec.size() * sizeof(float))) || (rc = alloc_buf(t.desc, static_cast<size_t>(n_textures) * sizeof(rtpt_texture))) ||
-      (rc = alloc_buf(t.texels, n_texels * 16)))
+      (rc = alloc_buf(t.texels, (n_texels + generated) * 16)) || (!levels.empty() && (rc = alloc_buf(t.levels, levels.size() * sizeof(uint32_t)))))
     return rc;
   HIP_TRY(hipMemcpyAsync(t.records.ptr, rec.data(), t.records.bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(t.desc.ptr, textures, t.desc.bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(t.texels.ptr, texels, t.texels.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(t.texels.ptr, texels, n_texels * 16, hipMemcpyHostToDevice, c->stream));
+  if (!levels.empty()) {
+    HIP_TRY(hipMemcpyAsync(t.levels.ptr, levels.data(), t.levels.bytes, hipMemcpyHostToDevice, c->stream));
+    // the generated chains: level l + 1 from level l, one launch each, at the offsets of the table
+    for (uint32_t i = 0; i < n_textures; i++) {
+      if (!rtpt_tex::generates_chain(textures[i])) continue;
+      const uint32_t* row = levels.data() + static_cast<size_t>(rtpt_tex::kLevelRow) * i;
+      for (uint32_t l = 0; l + 1 < row[rtpt_tex::kLevelRowCount]; l++)
+        rt::launch_mip_downsample(static_cast<float4*>(t.texels.ptr), row[l], rtpt_tex::level_dim(textures[i].width, l),
+                                  rtpt_tex::level_dim(textures[i].height, l), row[l + 1], c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays and `rec` may die at return
   t.n_textures = n_textures;
   c->scene.textures = std::move(t);

@@ -135,6 +135,71 @@ int rtpt_selftest_texture(rtpt_ctx* c, uint32_t texture, const float* uv, size_t
   return RTPT_OK;
 }
 
+int rtpt_selftest_texture_lod(rtpt_ctx* c, uint32_t texture, const float* uv, const float* lod, size_t n, float* rgba_out) {
+  if (!c || !uv || !lod || !rgba_out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const Scene::Textures& t = c->scene.textures;
+  if (!t.desc.ptr || texture >= t.n_textures) return fail(RTPT_E_INVALID, "no such texture (rtpt_scene_set_textures)");
+  for (size_t i = 0; i < 2 * n; i++)
+    if (!std::isfinite(uv[i])) return fail(RTPT_E_INVALID, "a uv coordinate is not finite");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  Buf duv, dlod, dout, drow;
+  int rc;
+  if ((rc = alloc_buf(duv, n * 8)) || (rc = alloc_buf(dlod, n * 4)) || (rc = alloc_buf(dout, n * 16))) return rc;
+  // a scene without any mip chain has no level table: its textures have the one level of their descriptor
+  const uint32_t* row = t.levels.ptr ? static_cast<const uint32_t*>(t.levels.ptr) + static_cast<size_t>(rtpt_tex::kLevelRow) * texture : nullptr;
+  uint32_t one_level[rtpt_tex::kLevelRow] = {};
+  hipError_t e = hipSuccess;
+  if (!row) {
+    rtpt_texture d;
+    if ((rc = alloc_buf(drow, sizeof one_level))) return rc;
+    e = hipMemcpy(&d, static_cast<const rtpt_texture*>(t.desc.ptr) + texture, sizeof d, hipMemcpyDeviceToHost);
+    one_level[0] = d.first_texel;
+    one_level[rtpt_tex::kLevelRowCount] = 1;
+    if (e == hipSuccess) e = hipMemcpyAsync(drow.ptr, one_level, sizeof one_level, hipMemcpyHostToDevice, c->stream);
+    row = static_cast<const uint32_t*>(drow.ptr);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(duv.ptr, uv, n * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dlod.ptr, lod, n * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_texture_lod(static_cast<const rt::TexDesc*>(t.desc.ptr) + texture, row, static_cast<const float4*>(t.texels.ptr),
+                                    static_cast<const float*>(duv.ptr), static_cast<const float*>(dlod.ptr), n, static_cast<float4*>(dout.ptr),
+                                    c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(rgba_out, dout.ptr, n * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // one_level is read by its copy until here
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_texture_lod: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
+int rtpt_selftest_texture_footprint(rtpt_ctx* c, const float* rays, size_t n, uint32_t bounce, uint32_t* out_id, float* out_lod) {
+  if (!c || !rays || !out_id || !out_lod) return fail(RTPT_E_INVALID, "NULL argument");
+  if (bounce > 1) return fail(RTPT_E_INVALID, "bounce is 0 (the rule of segment 0) or 1 (of every later segment)");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);  // as rtpt_selftest_trace
+  Buf drays, did, dlod;
+  int rc;
+  if ((rc = alloc_buf(drays, n * 24)) || (rc = alloc_buf(did, n * 4)) || (rc = alloc_buf(dlod, n * 4))) return rc;
+  if ((rc = ensure_stack_spill(c, std::max(frame_blocks(c), (n + 255) / 256)))) return rc;
+  hipError_t e = hipMemcpyAsync(drays.ptr, rays, n * 24, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_footprint(scene_view(c), tex_view(c), static_cast<const float*>(drays.ptr), n, c->cfg.ray_tmax, bounce == 0,
+                                  c->cfg.fov_slope, static_cast<int>(c->cfg.height), static_cast<uint32_t*>(did.ptr),
+                                  static_cast<float*>(dlod.ptr), c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out_id, did.ptr, n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_lod, dlod.ptr, n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_texture_footprint: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 // ------------------------------------------------------------------------------------------ host helpers
 void rtpt_util_look_at(const float eye[3], const float center[3], const float up[3], float m[16]) {
   // glm::lookAtRH (main.cpp:482, :1470)
@@ -563,6 +628,14 @@ int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tr
   if (!path || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
   std::string err;
   if (rtpt_tex::load_obj_texcoords(path, tri_uv, n_tris, &err)) return fail(RTPT_E_INVALID, err);
+  return RTPT_OK;
+}
+
+int rtpt_util_texture_chain(uint32_t width, uint32_t height, uint32_t* n_levels, uint64_t* n_texels) {
+  if (!width || !height || width > rtpt_tex::kMaxTexDim || height > rtpt_tex::kMaxTexDim)
+    return fail(RTPT_E_INVALID, "a texture dimension is zero or above 65536");
+  if (n_levels) *n_levels = rtpt_tex::chain_levels(width, height);
+  if (n_texels) *n_texels = rtpt_tex::chain_texels(width, height);
   return RTPT_OK;
 }
 

@@ -266,7 +266,7 @@ void k_pathtrace_pool(PathtraceArgs a, GbufferArgs g) {
         if (y >= a.count_y0 && y < a.count_y1) rays++;
         const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
         if (seg == 0 && a.hit_id) a.hit_id[gi] = h.id1;
-        if (shade_segment<false>(a, h, seg, light_c, o, d, acc, rng, TexView{})) {
+        if (shade_segment<0>(a, h, seg, light_c, o, d, acc, rng, TexView{})) {
           if (GB)
             store_rgb(a.image + gi, acc);
           else

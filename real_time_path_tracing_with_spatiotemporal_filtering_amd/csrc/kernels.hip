@@ -729,8 +729,20 @@ constexpr int kPtThreads = kBlockX * kPtRows;
 // albedo of this hit goes there instead of into the throughput, and a path that ends here stores (1, 1, 1) and keeps its colour.
 // TEX: the scene has albedo textures (rtpt_scene_set_textures): the albedo is (Kd or the normal-keyed colour) x texel.rgb, one
 // multiply per channel, at every segment.  A compile-time switch for DEMOD's reason: the instantiations without it are the
-// kernels of a build that knows no textures, register for register.
-template <bool TEX>
+// kernels of a build that knows no textures, register for register.  TEX == 2: some texture of the scene has RTPT_TEX_MIPMAP,
+// and the texel comes from the level of the ray's footprint (hit_texture_lod, tex::sample_lod); 1: level 0, as before mips.
+// The level a hit's texture is sampled at (texture.hpp states the arithmetic): the footprint of segment 0 is the pixel's,
+// t * 2 * slope / H of the FULL frame, so strips agree; every later segment starts over from its own length, t * spread —
+// nothing is carried between segments.  Density and areas come from the hit's own records, so instances, a changed model
+// and moved instances are right without host bookkeeping.  td: the hit's descriptor; s, t0, t1: its shade and uv records.
+__device__ __forceinline__ float hit_texture_lod(const TexDesc td, float4 s0, float4 s1, float4 s2, float4 t0, float4 t1, float t, f3 d,
+                                                 bool primary, float slope, int frame_h, float bounce_spread) {
+  if (!(td.flags & kTexMipmap)) return 0.0f;
+  const float w = t * (primary ? (2.0f * slope) / static_cast<float>(frame_h) : bounce_spread);
+  return tex::footprint_lod(w, exact::dot(f3{s0.w, s1.w, s2.w}, d), s0, s1, s2, t0, t1, td.width, td.height);
+}
+
+template <int TEX>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
@@ -768,7 +780,14 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const uint32_t ti = __float_as_uint(t1.z);
     if (ti) {
       const float tu = tex::interp_uv(b0, b1, b2, t0.x, t0.z, t1.x), tv = tex::interp_uv(b0, b1, b2, t0.y, t0.w, t1.y);
-      const float4 tx = tex::sample(tex.desc[ti - 1], tex.texels, tu, tv);
+      float4 tx;
+      if constexpr (TEX == 2) {
+        const TexDesc td = tex.desc[ti - 1];
+        const float lambda = hit_texture_lod(td, s0, s1, s2, t0, t1, h.t, d, seg == 0, a.slope, a.g.H, tex.bounce_spread);
+        tx = tex::sample_lod(td, tex.levels + kTexLevelRow * static_cast<size_t>(ti - 1), tex.texels, tu, tv, lambda);
+      } else {
+        tx = tex::sample(tex.desc[ti - 1], tex.texels, tu, tv);
+      }
       alb = f3{alb.x * tx.x, alb.y * tx.y, alb.z * tx.z};
     }
   }
@@ -852,7 +871,7 @@ constexpr int kPtWaves = 8;
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
 // TEX: shade_segment samples the scene's albedo textures.
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, bool TEX>
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex) {
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -1037,13 +1056,13 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
 constexpr int kPtBvhWaves = 8;
-template <int BVH, bool COMPACT, bool DEMOD, bool TEX>
+template <int BVH, bool COMPACT, bool DEMOD, int TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex) {
   pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX>(a, tex);
 }
-template <bool COMPACT, bool DEMOD, bool TEX>
+template <bool COMPACT, bool DEMOD, int TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex) {
@@ -1057,7 +1076,7 @@ void k_pathtrace_small(PathtraceArgs a, TexView tex) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD, bool TEX>
+template <int BVH, bool DEMOD, int TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
@@ -1071,7 +1090,7 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
     gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
-template <bool DEMOD, bool TEX>
+template <bool DEMOD, int TEX>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
@@ -1086,7 +1105,7 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   }
 }
 
-template <int BVH, bool TEX>
+template <int BVH, int TEX>
 __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
@@ -1267,6 +1286,45 @@ __global__ void k_selftest_texture(const TexDesc* desc, const float4* texels, co
   out[i] = tex::sample(*desc, texels, uv[2 * i], uv[2 * i + 1]);
 }
 
+// the sampler at an explicit level (rtpt_selftest_texture_lod); lv: the texture's row of the level table
+__global__ void k_selftest_texture_lod(const TexDesc* desc, const uint32_t* lv, const float4* texels, const float* uv, const float* lod,
+                                       size_t n, float4* out) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = tex::sample_lod(*desc, lv, texels, uv[2 * i], uv[2 * i + 1], lod[i]);
+}
+
+// k_selftest_trace, then the level shade_segment would sample the hit's texture at (rtpt_selftest_texture_footprint)
+template <int BVH>
+__global__ __launch_bounds__(kThreads) void k_selftest_footprint(SceneView sc, TexView tex, const float* rays, size_t n, float tmax,
+                                                                 uint32_t primary, float slope, int frame_h, uint32_t* out_id,
+                                                                 float* out_lod) {
+  extern __shared__ uint32_t stack[];
+  size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  f3 o = ld3(rays + 6 * i), d = ld3(rays + 6 * i + 3);
+  HitRec h{tmax, 0u, 0.f, 0.f, 1.f};
+  closest_hit<BVH>(sc, o, d, h, stack, threadIdx.x);
+  out_id[i] = h.id1;
+  float lambda = 0.0f;
+  if (h.id1 && tex.records && tex.levels) {
+    const float4* tr = tex.records + 2 * static_cast<size_t>((h.id1 - 1) % sc.n_base_tris);
+    const float4 t0 = tr[0], t1 = tr[1];
+    const uint32_t ti = __float_as_uint(t1.z);
+    if (ti) {
+      const float4* s = sc.shade + 3 * static_cast<size_t>(h.id1 - 1);
+      const TexDesc td = tex.desc[ti - 1];
+      lambda = hit_texture_lod(td, s[0], s[1], s[2], t0, t1, h.t, d, primary != 0, slope, frame_h, tex.bounce_spread);
+      uint32_t L = tex.levels[kTexLevelRow * static_cast<size_t>(ti - 1) + kTexLevelRowCount];  // the clamp of tex::sample_lod
+      L = L < 1u ? 1u : (L > kTexLevelRowCount ? kTexLevelRowCount : L);
+      const float top = static_cast<float>(L - 1u);
+      lambda = lambda > 0.0f ? lambda : 0.0f;
+      lambda = lambda < top ? lambda : top;
+    }
+  }
+  out_lod[i] = lambda;
+}
+
 }  // namespace
 
 #if RTPT_BVH_COUNT || RTPT_TILE_TIMELINE
@@ -1275,6 +1333,17 @@ __global__ void k_selftest_texture(const TexDesc* desc, const float4* texels, co
 #undef RTPT_INSTR_HOST
 #endif
 
+// f(mode) with the texture mode as a compile-time constant (shade_segment<TEX>): 2 the scene has textures and some of them a
+// mip chain (the level table exists), 1 textures without mips, 0 no textures
+template <class F>
+static void with_tex_mode(const TexView& tex, F&& f) {
+  if (tex.records && tex.levels)
+    f(std::integral_constant<int, 2>{});
+  else if (tex.records)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 0>{});
+}
 // f(mode) with the scene's closest-hit mode as a compile-time constant: 2 BVH over fan pairs, 1 BVH over triangles, 0 brute
 // force (closest_hit<BVH>; the brute-force tile kernels have names of their own, *_small, for their occupancy pin)
 template <class F>
@@ -1341,7 +1410,6 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
   const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
-  const bool textured = tex.records != nullptr;  // rtpt_scene_set_textures: the instantiations that sample the atlas
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
@@ -1375,8 +1443,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     constexpr int M = decltype(mode)::value;
     with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
       constexpr bool D = decltype(demod)::value;
-      with_bool(textured, [&](auto tex_on) {
-        constexpr bool T = decltype(tex_on)::value;
+      with_tex_mode(tex, [&](auto tex_mode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
+        constexpr int T = decltype(tex_mode)::value;
         if (gb) {
           if constexpr (M != 0)
             hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T>), grid, block, dyn, s, b, *gb, tex);
@@ -1410,8 +1478,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     c.q_out_count = more ? a.queue_count + (cur ^ 1) * kPathQueues : nullptr;
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
     with_scene_mode(a.scene, [&](auto mode) {
-      with_bool(textured, [&](auto tex_on) {
-        hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_on)::value>), qgrid, block, dyn_queue, s, c, tex);
+      with_tex_mode(tex, [&](auto tex_mode) {
+        hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_mode)::value>), qgrid, block, dyn_queue, s, c, tex);
       });
     });
     if (end >= a.max_segments) break;
@@ -1430,6 +1498,21 @@ void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipSt
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_texture, dim3((n + 255) / 256), dim3(256), 0, s, desc, texels, uv, n, out);
+}
+void launch_selftest_texture_lod(const TexDesc* desc, const uint32_t* lv, const float4* texels, const float* uv, const float* lod, size_t n,
+                                 float4* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_texture_lod, dim3((n + 255) / 256), dim3(256), 0, s, desc, lv, texels, uv, lod, n, out);
+}
+void launch_selftest_footprint(const SceneView& scene, const TexView& tex, const float* rays, size_t n, float tmax, bool primary, float slope,
+                               int frame_h, uint32_t* out_id, float* out_lod, hipStream_t s) {
+  if (!n) return;
+  dim3 grid((n + kThreads - 1) / kThreads), block(kThreads);
+  with_scene_mode(scene, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    hipLaunchKernelGGL(k_selftest_footprint<M>, grid, block, M ? scene.stack_lds * kThreads * 4 : 0, s, scene, tex, rays, n, tmax,
+                       primary ? 1u : 0u, slope, frame_h, out_id, out_lod);
+  });
 }
 void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, float tmax, uint32_t* out_id,
                            float* out_t, hipStream_t s) {

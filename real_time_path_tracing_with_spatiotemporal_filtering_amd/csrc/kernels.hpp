@@ -46,11 +46,20 @@ struct SceneView {
 // parameter of the path-trace kernels, not inside SceneView: as three more pointers there it moved every later field of
 // PathtraceArgs / GbufferArgs by 24 bytes, and the 1,152,000-triangle frame measured 0.1 % slower with textures off.  Behind
 // the other arguments it leaves every existing offset, and so the code of the TEX = false instantiations, as it was.
+// levels: the per-texture table of level offsets (texture.hpp: kTexLevelRow dwords a texture), non-NULL exactly when some texture
+// has RTPT_TEX_MIPMAP — what selects the mip instantiations; bounce_spread: kTexBounceSpread unless the environment overrides it.
 struct TexView {
   const float4* records;
   const TexDesc* desc;
   const float4* texels;
+  const uint32_t* levels;
+  float bounce_spread;
 };
+
+// Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
+// and the same columns of row min(2y + 1, sh - 1) of level l (texture_mips.hip): one launch per level.  src and dst are texel
+// offsets into `atlas`; dw = max(1, sw >> 1), dh = max(1, sh >> 1).
+void launch_mip_downsample(float4* atlas, uint32_t src, uint32_t sw, uint32_t sh, uint32_t dst, hipStream_t s);
 
 // Screen-space bounds of every triangle of a small scene (<= 64), computed on the host per call and
 // passed in the kernel-argument segment (scalar loads).  A wave covers 64 pixels of one row; a
@@ -366,5 +375,11 @@ void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, 
                            float* out_t, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
+// tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs
+void launch_selftest_texture_lod(const TexDesc* desc, const uint32_t* lv, const float4* texels, const float* uv, const float* lod, size_t n,
+                                 float4* out, hipStream_t s);
+// launch_selftest_trace, returning instead of t the level hit_texture_lod gives the hit, clamped to its chain (0 without one)
+void launch_selftest_footprint(const SceneView& scene, const TexView& tex, const float* rays, size_t n, float tmax, bool primary, float slope,
+                               int frame_h, uint32_t* out_id, float* out_lod, hipStream_t s);
 
 }  // namespace rt

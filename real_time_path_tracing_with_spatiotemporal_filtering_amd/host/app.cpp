@@ -72,7 +72,7 @@ void PathTracingApplication::loadMesh() {
   sceneTextures_ = SceneTextures{};
   if (opt_.textures) {
     if (opt_.tessellate > 1) throw std::runtime_error("--tessellate does not carry texture coordinates over");
-    sceneTextures_ = load_scene_textures(opt_.scene, triMaterial, opt_.textures_nearest);
+    sceneTextures_ = load_scene_textures(opt_.scene, triMaterial, opt_.textures_nearest, opt_.texture_mips);
   }
   if (opt_.tessellate > 1) {
     if (!objMaterials.empty()) throw std::runtime_error("--tessellate does not carry a material library over");

@@ -21,8 +21,9 @@ static void usage(const char* argv0) {
       "          [--tessellate n] [--lattice NXxNYxNZ [--pitch P] | --instances file] [--dump-scene out.bin]\n"
       "          [--frames-in-flight 1|2]\n"
       "          [--demodulate  (filter illumination and multiply the first hit's albedo back, RTPT_FLAG_EXT_DEMODULATE = --flags 0x8000)]\n"
-      "          [--textures [--texture-filter bilinear|nearest]  (sample the map_Kd images of the OBJ's library, binary PPM / PFM next to\n"
-      "           the OBJ, at every hit: rtpt_scene_set_textures; without it an OBJ with map_Kd renders as it always did)]\n"
+      "          [--textures [--texture-filter bilinear|nearest] [--texture-mips]  (sample the map_Kd images of the OBJ's library, binary\n"
+      "           PPM / PFM next to the OBJ, at every hit: rtpt_scene_set_textures; without it an OBJ with map_Kd renders as it always did;\n"
+      "           --texture-mips: from generated mip chains, at the level of the ray's footprint, RTPT_TEX_MIPMAP)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -84,6 +85,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--exact-filter")) opt.flags |= RTPT_FLAG_EXACT_FILTER;
     else if (!std::strcmp(argv[i], "--demodulate")) opt.flags |= RTPT_FLAG_EXT_DEMODULATE;
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
+    else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
     else if (!std::strcmp(argv[i], "--texture-filter")) {
       const char* v = need("--texture-filter");
       if (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear")) { std::fprintf(stderr, "--texture-filter nearest|bilinear\n"); return 2; }

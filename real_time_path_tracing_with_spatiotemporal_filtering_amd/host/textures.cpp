@@ -75,7 +75,7 @@ Image load_image(const std::string& path) {
   return im;
 }
 
-SceneTextures load_scene_textures(const std::string& obj_path, const std::vector<uint32_t>& tri_material, bool nearest) {
+SceneTextures load_scene_textures(const std::string& obj_path, const std::vector<uint32_t>& tri_material, bool nearest, bool mips) {
   SceneTextures out;
   if (tri_material.empty()) return out;
   size_t bytes = 0;
@@ -95,7 +95,8 @@ SceneTextures load_scene_textures(const std::string& obj_path, const std::vector
   const std::string dir = slash == std::string::npos ? std::string() : obj_path.substr(0, slash + 1);
   for (const std::string& file : files) {
     const Image im = load_image(dir + file);
-    out.textures.push_back(rtpt_texture{im.width, im.height, static_cast<uint32_t>(out.texels.size() / 4), nearest ? RTPT_TEX_NEAREST : 0u});
+    out.textures.push_back(rtpt_texture{im.width, im.height, static_cast<uint32_t>(out.texels.size() / 4),
+                                        (nearest ? RTPT_TEX_NEAREST : 0u) | (mips ? RTPT_TEX_MIPMAP : 0u)});
     out.texels.insert(out.texels.end(), im.rgba.begin(), im.rgba.end());
   }
   std::vector<uint32_t> of_material(maps.size(), 0);

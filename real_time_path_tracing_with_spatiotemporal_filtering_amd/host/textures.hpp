@@ -26,6 +26,7 @@ struct SceneTextures {
   std::vector<float> texels;
 };
 // tri_material: rtpt_util_load_obj_materials' per-triangle indices of the same OBJ (empty: no library, no textures)
-SceneTextures load_scene_textures(const std::string& obj_path, const std::vector<uint32_t>& tri_material, bool nearest);
+// mips: every texture gets RTPT_TEX_MIPMAP, with a chain the library generates (--texture-mips)
+SceneTextures load_scene_textures(const std::string& obj_path, const std::vector<uint32_t>& tri_material, bool nearest, bool mips);
 
 }  // namespace rtpt_host

@@ -60,14 +60,15 @@ def load_image(path: str) -> np.ndarray:
     return out
 
 
-def build_atlas(images, nearest=False):
+def build_atlas(images, nearest=False, mips=False):
     """(textures [n, 4] u32, texels [m, 4] f32) for rtpt_scene_set_textures: the images ([H, W, 4] f32, row 0 = v 0) one
-    after the other"""
+    after the other; `mips`: every texture gets RTPT_TEX_MIPMAP (the library generates the chains on the device)"""
     desc, parts, first = [], [], 0
+    flags = (abi.TEX_NEAREST if nearest else 0) | (abi.TEX_MIPMAP if mips else 0)
     for im in images:
         im = np.ascontiguousarray(im, np.float32)
         h, w = im.shape[:2]
-        desc.append((w, h, first, abi.TEX_NEAREST if nearest else 0))
+        desc.append((w, h, first, flags))
         parts.append(im.reshape(-1, 4))
         first += w * h
     return np.array(desc, np.uint32).reshape(-1, 4), np.concatenate(parts) if parts else np.zeros((0, 4), np.float32)
@@ -82,7 +83,7 @@ class ObjTextures(NamedTuple):
     texels: np.ndarray | None
 
 
-def load_obj_textures(path: str, nearest=False) -> ObjTextures:
+def load_obj_textures(path: str, nearest=False, mips=False) -> ObjTextures:
     """the material library of an OBJ with its `map_Kd` images (looked up next to the OBJ) as one atlas"""
     tri_material, materials = abi.load_obj_materials(path)
     maps = abi.load_obj_map_kd(path)
@@ -91,5 +92,5 @@ def load_obj_textures(path: str, nearest=False) -> ObjTextures:
     files = sorted({m for m in maps if m})
     images = [load_image(os.path.join(os.path.dirname(path), f)) for f in files]
     of_material = np.array([files.index(m) + 1 if m else 0 for m in maps], np.uint32)
-    textures, texels = build_atlas(images, nearest)
+    textures, texels = build_atlas(images, nearest, mips)
     return ObjTextures(tri_material, materials, abi.load_obj_texcoords(path), of_material[tri_material], textures, texels)

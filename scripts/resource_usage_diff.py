@@ -6,7 +6,9 @@
 Kernels are matched by demangled name without the argument list (a change may add a kernel parameter; it is the
 instantiation that is matched).  A change that adds a trailing bool template parameter to a kernel family (TEX of the
 path-trace kernels) is compared with `--family NAME=false`: the parent's `NAME<...>` is matched with the change's
-`NAME<..., false>`.  Prints every kernel of the parent with both sets of numbers, marks the rows that differ, then lists the
+`NAME<..., false>`.  A change that turns the last template parameter of a family from bool into int (TEX again, for the mip
+instantiations) is compared with `--retype NAME=false:0` (and `NAME=true:1`): the parent's `NAME<..., false>` is matched with the
+change's `NAME<..., 0>`.  Prints every kernel of the parent with both sets of numbers, marks the rows that differ, then lists the
 kernels only the change has.  `--only REGEX` prints the rows of the kernels whose name matches and counts the other
 unchanged ones in the last line only (the whole report of this library is 0.9 MB).  Exit status 1 when a matched kernel
 differs or is missing."""
@@ -46,15 +48,24 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("change")
     ap.add_argument("--family", action="append", default=[], help="NAME=VALUE: the change appended template argument VALUE to kernel NAME")
+    ap.add_argument("--retype", action="append", default=[], help="NAME=OLD:NEW: the change spells the last template argument OLD of kernel NAME as NEW")
     ap.add_argument("--only", default=None, help="print only the kernels whose demangled name matches this regular expression")
     a = ap.parse_args()
     p, c = parse(a.parent), parse(a.change)
     fam = dict(f.split("=") for f in a.family)
+    retype = {}
+    for r in a.retype:
+        name, pair = r.split("=")
+        retype.setdefault(name, {}).update([pair.split(":")])
 
     def renamed(name):
         m = re.match(r"(void )?(rt::)?(\w+)<(.*)>$", name)
         if m and m.group(3) in fam:
             return f"{m.group(1) or ''}{m.group(2) or ''}{m.group(3)}<{m.group(4)}, {fam[m.group(3)]}>"
+        if m and m.group(3) in retype:
+            args = m.group(4).split(", ")
+            args[-1] = retype[m.group(3)].get(args[-1], args[-1])
+            return f"{m.group(1) or ''}{m.group(2) or ''}{m.group(3)}<{', '.join(args)}>"
         return name
     show = (lambda n: re.search(a.only, n)) if a.only else (lambda n: True)
     bad, matched, hidden = 0, set(), 0

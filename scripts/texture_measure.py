@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
-"""First numbers for the textured path (rtpt_scene_set_textures): the 4K Cornell box with a 1024 x 1024 checker on every
-surface, nearest and bilinear, against the same scene with materials only (Kd = the checker's mean colour).
+"""Numbers for the textured path (rtpt_scene_set_textures): the 4K Cornell box with a 1024 x 1024 checker on every
+surface, nearest and bilinear, without and with a generated mip chain (RTPT_TEX_MIPMAP), against the same scene with
+materials only (Kd = the checker's mean colour); the mip-mapped bilinear variant also with RTPT_TEX_BOUNCE_SPREAD at 1/32 and
+1/2 (the shipped 1/8 is the plain `bilinear_mips`).  Then the set-up time of rtpt_scene_set_textures with and without the
+chain build, and at 64 x 48 the RMS of each spread's converged image against the converged un-mipped image (the bias of
+pre-filtered albedo at bounces), next to the RMS between two un-mipped means of other frame numbers (the noise floor).
 
     python scripts/texture_measure.py [--width 3840 --height 2160 --segments 4 --frames 200 --warmup 30 --repeats 3]
 
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--texture", type=int, default=1024)
+    ap.add_argument("--converge", type=int, default=2048, help="frames averaged for each converged 64 x 48 image")
     a = ap.parse_args()
     import torch  # noqa: F401  (before the library: one ROCm runtime for both)
     from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi
@@ -56,19 +61,31 @@ def main():
     im = checker(a.texture, 16)
     mean = im[..., :3].reshape(-1, 3).mean(0)
     tri = np.zeros(n, np.uint32)
-    variants = {
-        "materials": (np.array([[*mean, 0, 0, 0]], np.float32), None),
-        "nearest": (np.array([[1, 1, 1, 0, 0, 0]], np.float32), abi.TEX_NEAREST),
-        "bilinear": (np.array([[1, 1, 1, 0, 0, 0]], np.float32), 0),
+    white = np.array([[1, 1, 1, 0, 0, 0]], np.float32)
+    variants = {     # name: (materials, texture flags or None, RTPT_TEX_BOUNCE_SPREAD or None)
+        "materials": (np.array([[*mean, 0, 0, 0]], np.float32), None, None),
+        "nearest": (white, abi.TEX_NEAREST, None),
+        "bilinear": (white, 0, None),
+        "nearest_mips": (white, abi.TEX_NEAREST | abi.TEX_MIPMAP, None),
+        "bilinear_mips": (white, abi.TEX_MIPMAP, None),
+        "bilinear_mips_spread_1_32": (white, abi.TEX_MIPMAP, 1 / 32),
+        "bilinear_mips_spread_1_2": (white, abi.TEX_MIPMAP, 1 / 2),
     }
-    apps = {}
-    for name, (mats, tflags) in variants.items():
-        app = make_app(a.width, a.height, max_segments=a.segments, iterations=5)
+    uv = planar_uv(xyz, idx, 0.5)
+
+    def textured_app(width, height, mats, tflags, spread):
+        if spread is None:
+            os.environ.pop("RTPT_TEX_BOUNCE_SPREAD", None)
+        else:
+            os.environ["RTPT_TEX_BOUNCE_SPREAD"] = repr(spread)      # read by rtpt_create
+        app = make_app(width, height, max_segments=a.segments, iterations=5)
+        os.environ.pop("RTPT_TEX_BOUNCE_SPREAD", None)
         app.backend.ctx.set_materials(tri, mats)
         if tflags is not None:
             desc = np.array([[a.texture, a.texture, 0, tflags]], np.uint32)
-            app.backend.ctx.set_textures(planar_uv(xyz, idx, 0.5), np.ones(n, np.uint32), desc, im.reshape(-1, 4))
-        apps[name] = app
+            app.backend.ctx.set_textures(uv, np.ones(n, np.uint32), desc, im.reshape(-1, 4))
+        return app
+    apps = {name: textured_app(a.width, a.height, *v) for name, v in variants.items()}
 
     def run(app, frames):
         for f in range(frames):
@@ -90,10 +107,39 @@ def main():
         ctx.timing_enable(0)
         kernels[name] = {k: round(v[0] / v[1] * 1e3, 1) for k, v in tm.items() if v[1] and "pathtrace" in k}
         app.backend.close()
+    # set-up: rtpt_scene_set_textures (it blocks) on the host clock, best of 5, without and with the chain build
+    setup = {}
+    app = make_app(64, 48, max_segments=a.segments, iterations=5)
+    for name, tflags in (("plain", 0), ("mipmap", abi.TEX_MIPMAP)):
+        desc, best = np.array([[a.texture, a.texture, 0, tflags]], np.uint32), 1e9
+        for _ in range(5):
+            t0 = time.perf_counter()
+            app.backend.ctx.set_textures(uv, np.ones(n, np.uint32), desc, im.reshape(-1, 4))
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        setup[name] = round(best, 3)
+    app.backend.close()
+
+    # bias of the bounce rule: converged traced images at 64 x 48
+    def converged(v, first, count):
+        app = textured_app(64, 48, *v)
+        ctx = app.backend.ctx
+        app.updateScene(())
+        acc = np.zeros((48, 64, 3), np.float64)
+        for f in range(count):
+            app.pushConstants.frameNumber = first + f
+            ctx.raytrace(app.pushConstants)
+            acc += ctx.readback(abi.PLANE_IMAGE)[..., :3]
+        app.backend.close()
+        return acc / count
+    ref = converged(variants["bilinear"], 1000, a.converge)
+    rms = {"noise_floor": round(float(np.sqrt(np.mean((converged(variants["bilinear"], 1000 + a.converge, a.converge) - ref) ** 2))), 6)}
+    for name in ("bilinear_mips_spread_1_32", "bilinear_mips", "bilinear_mips_spread_1_2"):
+        rms[name] = round(float(np.sqrt(np.mean((converged(variants[name], 1000, a.converge) - ref) ** 2))), 6)
     out = {"size": [a.width, a.height], "segments": a.segments, "texture": a.texture, "frames": a.frames, "repeats": a.repeats,
            "frame_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
            "frame_ms_median": {k: round(float(np.median(v)), 4) for k, v in ms.items()},
-           "trace_kernel_us": kernels}
+           "trace_kernel_us": kernels, "set_textures_ms": setup, "rms_64x48_against_converged_unmipped": rms,
+           "converge_frames": a.converge}
     print(json.dumps(out))
 
 
