@@ -241,6 +241,7 @@ class SeqDump(C.Structure):
 
 
 END_LIGHT, END_SKY, END_BOUND = 1, 2, 3
+END_EMISSIVE = 4  # raytrace_seq_mat only
 
 
 def raytrace_seq(cfg, pc: PushConstants, tris):
@@ -258,6 +259,28 @@ def raytrace_seq(cfg, pc: PushConstants, tris):
     d = SeqDump(seq_id.ctypes.data, seq_n.ctypes.data, seq_end.ctypes.data, max_rec, dir0.ctypes.data)
     lib().oracle_raytrace_seq(C.byref(cfg), C.byref(pc), _p(tris), C.c_uint32(len(tris)), C.c_uint32(0), C.c_uint32(H),
                               _p(img), C.byref(rc), _p(hid), C.byref(d))
+    return img, int(rc.value), hid, seq_id, seq_n, seq_end, dir0
+
+
+def raytrace_seq_mat(cfg, pc: PushConstants, tris, tri_mat=None, y0=0, y1=None):
+    """raytrace_seq() of raytrace(tri_mat=...)'s paths, rows [y0, y1): the same tuple; a path that ends on an emissive material
+    has seq_end END_EMISSIVE.  With samples_per_pixel > 1 seq_n is the total over the samples, seq_end the last sample's"""
+    W, H = cfg.width, cfg.height
+    y1 = H if y1 is None else y1
+    max_rec = int(cfg.max_segments) * int(cfg.samples_per_pixel)
+    img = np.zeros((H, W, 4), np.float32)
+    hid = np.zeros((H, W), np.uint32)
+    seq_id = np.zeros((H, W, max_rec), np.uint16)
+    seq_n = np.zeros((H, W), np.int32)
+    seq_end = np.zeros((H, W), np.uint8)
+    rc = C.c_uint64(0)
+    dir0 = np.zeros((H, W, 3), np.float32)
+    d = SeqDump(seq_id.ctypes.data, seq_n.ctypes.data, seq_end.ctypes.data, max_rec, dir0.ctypes.data)
+    if tri_mat is not None:
+        tri_mat = np.ascontiguousarray(tri_mat, np.float32)
+    lib().oracle_raytrace_seq_mat(C.byref(cfg), C.byref(pc), _p(tris), C.c_uint32(len(tris)), _p(tri_mat),
+                                  C.c_uint32(0 if tri_mat is None else len(tri_mat)), C.c_uint32(y0), C.c_uint32(y1),
+                                  _p(img), C.byref(rc), _p(hid), C.byref(d))
     return img, int(rc.value), hid, seq_id, seq_n, seq_end, dir0
 
 

@@ -647,6 +647,7 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
               const float* m = tri_mat + 8 * (uint64_t)((id - 1) % n_base);
               if (m[7] != 0.0f) { /* an emissive surface ends the path like the analytic light (:226-234) */
                 acc = v3_mul(acc, v3(m[4], m[5], m[6]));
+                end_code = ORACLE_END_EMISSIVE; /* dumped by oracle_raytrace_seq_mat only: oracle_raytrace_seq has no materials */
                 break;
               }
               alb = v3(m[0], m[1], m[2]);
@@ -707,6 +708,11 @@ void oracle_raytrace_mat(const oracle_config* cfg, const oracle_push_constants* 
 
 void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
   raytrace_mat_args A = {cfg, pc, tris, n, NULL, 0, image, raycount, hit_id, dump};
+  run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
+}
+
+void oracle_raytrace_seq_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
+  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, dump};
   run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
 }
 

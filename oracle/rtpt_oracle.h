@@ -134,6 +134,7 @@ void oracle_raytrace_mat(const oracle_config* cfg, const oracle_push_constants* 
 #define ORACLE_END_LIGHT 1 /* :226-235 */
 #define ORACLE_END_SKY 2   /* :266-267 */
 #define ORACLE_END_BOUND 3 /* :204 */
+#define ORACLE_END_EMISSIVE 4 /* an emissive material (oracle_raytrace_mat's extension); oracle_raytrace_seq_mat only */
 typedef struct oracle_seq_dump {
   uint16_t* seq_id;
   int32_t* seq_n;
@@ -144,6 +145,11 @@ typedef struct oracle_seq_dump {
 void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                          uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount,
                          uint32_t* hit_id, const oracle_seq_dump* dump);
+/* the same dump of oracle_raytrace_mat's paths: tri_mat as there (NULL: oracle_raytrace_seq).  A path that ends on an emissive
+ * material reports ORACLE_END_EMISSIVE */
+void oracle_raytrace_seq_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
+                             uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image,
+                             uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump);
 /* K3: temporalFiltering.comp.glsl:191-265, one iteration.  `in` is the colorImage snapshot (D1),
  * `out` receives the filtered colour (k < max) or the blend (k == max).  prev_pixel (nullable,
  * 2 ints per pixel) receives previousPixelPos when k == max. */
