@@ -593,6 +593,7 @@ int rtpt_selftest_exhaustive(rtpt_ctx* ctx, int op, uint64_t* mismatches, uint32
  * passes [first_pass, first_pass + n_passes) of the 256-pass enumeration of ALL 2^23 x 2^23 pairs of binary32 significands
  * (~0.15 s per pass; all 256 is the proof that the short sequence is correctly rounded for operands of ordinary magnitude);
  * mode 1: n_passes x 2^33 operand pairs of arbitrary bits, pass numbers seeding the generator (range test + long path).
+ * mode 2: mode 1's operand pairs through exact::quotient_positive(a, b) against a / b > 0.0f (the contract is 0 here too).
  * *mismatches = results that differ in any bit (two NaNs count as equal); first_bad = the bits of one offending (a, b). */
 int rtpt_selftest_div(rtpt_ctx* ctx, int mode, uint32_t first_pass, uint32_t n_passes, uint64_t* mismatches, uint32_t first_bad[2]);
 /* closest-hit of arbitrary rays through the product's traversal (parity vs the oracle's brute

@@ -53,7 +53,8 @@ int rtpt_selftest_exhaustive(rtpt_ctx* c, int op, uint64_t* mismatches, uint32_t
 
 int rtpt_selftest_div(rtpt_ctx* c, int mode, uint32_t first_pass, uint32_t n_passes, uint64_t* mismatches, uint32_t first_bad[2]) {
   if (!c || !mismatches) return fail(RTPT_E_INVALID, "NULL argument");
-  if (mode != 0 && mode != 1) return fail(RTPT_E_INVALID, "rtpt_selftest_div: mode must be 0 (significand pairs) or 1 (arbitrary bits)");
+  if (mode < 0 || mode > 2)
+    return fail(RTPT_E_INVALID, "rtpt_selftest_div: mode must be 0 (significand pairs), 1 (arbitrary bits) or 2 (quotient_positive, arbitrary bits)");
   if (mode == 0 && (first_pass >= 256u || n_passes > 256u - first_pass))
     return fail(RTPT_E_INVALID, "rtpt_selftest_div: the enumeration has 256 passes");
   HIP_TRY(hipSetDevice(c->device));

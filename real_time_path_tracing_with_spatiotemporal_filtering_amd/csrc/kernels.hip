@@ -27,9 +27,22 @@ struct HitRec {
 // The divisions of the tracing kernels are hipcc's correctly rounded ones, not exact::div_ (rtpt_math.hpp): the tracing kernels
 // sit at their 64-VGPR budget (8 waves per SIMD), the short sequence keeps the refined reciprocal live next to the operands
 // of the long path, and what the fewer instructions bring (K2 at 4K 368.7 -> 364.9 us with both) the spills take back on the
-// BVH kernel (3.34 -> 3.41 ms; profiles/r03_div_ab.csv).  Two names so that the two groups stay easy to find.
+// BVH kernel (3.34 -> 3.41 ms; profiles/r03_div_ab.csv).  Two names so that the two groups stay easy to find.  (One exception
+// since: the barycentrics of a hit in the brute-force kernels, hit_barycentrics<SHORT_DIV> below.)
 #define RTPT_DIV_TH(a, b) ((a) / (b))  // hit distances
 #define RTPT_DIV_SH(a, b) ((a) / (b))  // shading (barycentrics, the light test, the pixel's ndc)
+
+// What K2's shading leaves out or shortens, one bit per item so that scripts/build_variant.sh can build each alone
+// (-DRTPT_TRACE_ITEMS=<mask>; profiles/r15_trace_shading_ab.txt):
+//   1  the last segment of a path returns before the bounce nothing follows (shade_segment)
+//   2  the light test takes the sign of its quotient without dividing (exact::quotient_positive)
+//   8  the two barycentric divisions of a hit share one reciprocal (exact::div2_) in the brute-force instantiations that keep
+//      their registers with it (pathtrace_tile, k_pathtrace_queue: SHORT_DIV)
+// (4, the primary ray's two divisions by the frame height through exact::div2_, and 16, exact::div_ for the hit distance of the
+// brute-force triangle tests, were measured with these and brought nothing: they are not kept.)
+#ifndef RTPT_TRACE_ITEMS
+#define RTPT_TRACE_ITEMS 11
+#endif
 
 // Scalar-triple-product form of Moller-Trumbore, plane normal n = e1 x e2 precomputed per triangle,
 // division deferred until a candidate passes the inside tests:
@@ -699,8 +712,14 @@ __device__ __forceinline__ bool ray_hits_light(f3 o, f3 d, f3 c, float r2) {
   // addition and the correctly-rounded division are monotonic, so t1 <= t2 whenever neither is NaN: t1 > 0 implies
   // t2 > 0, and the disjunction IS "t2 > 0" (NaN operands make both comparisons false either way; 2a == 0 gives +-inf /
   // NaN with the same signs).  One division less per path segment.
+#if RTPT_TRACE_ITEMS & 2
+  // ... and of t2 only the sign is asked for: exact::quotient_positive is "num / den > 0.0f" on every pair of operands and
+  // divides only where the sign is not num's (2a is 2 |d|^2, about 2)
+  return exact::quotient_positive(-b + sq, 2.0f * a);
+#else
   float t2 = RTPT_DIV_SH(-b + sq, 2.0f * a);
   return t2 > 0.0f;
+#endif
 }
 
 __device__ __forceinline__ f3 sky_color(f3 d) {  // raytrace.comp.glsl:95-107
@@ -742,7 +761,30 @@ __device__ __forceinline__ float hit_texture_lod(const TexDesc td, float4 s0, fl
   return tex::footprint_lod(w, exact::dot(f3{s0.w, s1.w, s2.w}, d), s0, s1, s2, t0, t1, td.width, td.height);
 }
 
-template <int TEX>
+// b1 = -u / ad, b2 = v / ad, b0 = 1 - b1 - b2 (:134).  SHORT_DIV: exact::div2_, for the wave-uniform brute-force kernels that have
+// the registers; the BVH kernels, pinned at 64 VGPRs, keep hipcc's divisions (RTPT_DIV_SH above)
+template <bool SHORT_DIV>
+__device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, float& b1, float& b2) {
+  if (SHORT_DIV) {
+    exact::div2_(-h.u, h.v, h.ad, b1, b2);
+  } else {
+    b1 = RTPT_DIV_SH(-h.u, h.ad);
+    b2 = RTPT_DIV_SH(h.v, h.ad);
+  }
+  b0 = 1.0f - b1 - b2;
+}
+
+// BVH: the caller's closest-hit structure; SHORT_DIV: see hit_barycentrics (the defaults are the kernels before either).
+// The LAST segment of a path (seg + 1 >= a.max_segments — the path's budget, not the launch's window seg_end: behind a window
+// boundary the queue kernel goes on with o, d and rng) ends after its throughput update: the hit point, the faceforward, the
+// offset origin, the two draws' floats, sincos2pi, the square root and the normalize make an o and a d that nothing reads.  What
+// stays: the barycentrics where the hit samples a texture, and with samples_per_pixel > 1 the two steps of the RNG state, which
+// the pixel's next sample continues from (rng_pix, pathtrace_tile).
+// Two places keep the bounce, for their registers (make resource-usage, profiles/r15_trace_shading_ab.txt): the untextured
+// instantiations over fan pairs (BVH == 2, TEX == 0; pinned at 64 VGPRs with 8 to 14 spilled ones — the early return cost
+// k_gbuffer_pathtrace<2, false, 0>, the kernel of the instanced frame, one more: 36 -> 40 bytes of scratch) and the segment that
+// stores the albedo plane (alb_px; 0 -> 8 bytes in the brute-force DEMOD kernels), which is a path's last only with max_segments 1.
+template <int TEX, int BVH = 1, bool SHORT_DIV = false>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
@@ -757,9 +799,13 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
   float4 s0 = s[0], s1 = s[1], s2 = s[2];
-  float b1 = RTPT_DIV_SH(-h.u, h.ad), b2 = RTPT_DIV_SH(h.v, h.ad);
-  float b0 = 1.0f - b1 - b2;                                       // :134
-  f3 pos = bary_point(xyz(s0), xyz(s1), xyz(s2), b0, b1, b2);      // :137
+  const bool last = (RTPT_TRACE_ITEMS & 1) && !(BVH == 2 && TEX == 0) && !alb_px && seg + 1 >= a.max_segments;  // block-uniform
+  float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+  f3 pos{0.f, 0.f, 0.f};
+  if (!last) {
+    hit_barycentrics<SHORT_DIV>(h, b0, b1, b2);
+    pos = bary_point(xyz(s0), xyz(s1), xyz(s2), b0, b1, b2);      // :137
+  }
   f3 n{s0.w, s1.w, s2.w};                                          // :150 (precomputed per triangle)
   f3 alb = (n.x > 0.99f) ? f3{1.f, 0.f, 0.f} : ((-n.x > 0.99f) ? f3{0.f, 1.f, 0.f} : f3{0.7f, 0.7f, 0.7f});  // :155-163
   if (a.scene.materials) {
@@ -779,6 +825,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const float4 t0 = tr[0], t1 = tr[1];
     const uint32_t ti = __float_as_uint(t1.z);
     if (ti) {
+      if (last) hit_barycentrics<SHORT_DIV>(h, b0, b1, b2);
       const float tu = tex::interp_uv(b0, b1, b2, t0.x, t0.z, t1.x), tv = tex::interp_uv(b0, b1, b2, t0.y, t0.w, t1.y);
       float4 tx;
       if constexpr (TEX == 2) {
@@ -795,6 +842,13 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     *alb_px = make_float4(alb.x, alb.y, alb.z, 0.0f);  // demodulated: rtpt_modulate / rtpt_present multiply it back
   else
     acc = acc * alb;                                               // :244
+  if (last) {  // budget exhausted: the path returns its throughput (:270)
+    if (a.spp > 1) {
+      exact::rng_skip(rng);  // :256
+      exact::rng_skip(rng);  // :257
+    }
+    return true;
+  }
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
   float st_, ct;
@@ -959,7 +1013,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if (y >= a.count_y0 && y < a.count_y1) rays++;
         const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
-        const bool done = shade_segment<TEX>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
+        // the short barycentric divisions where they cost no register: with DEMOD or without compaction they spill one
+        constexpr bool kShortDiv = (RTPT_TRACE_ITEMS & 8) && BVH == 0 && COMPACT && !DEMOD;
+        const bool done = shade_segment<TEX, BVH, kShortDiv>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
         if (done) {
           alive = false;
           if (a.spp == 1) {
@@ -1141,7 +1197,7 @@ __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a,
         closest_hit<BVH>(a.scene, o, d, h, stack, tid, kPtThreads, 1 + static_cast<int>(seg));  // :208-222
         const int x = static_cast<int>(pix & 0xFFFFu), y = static_cast<int>(pix >> 16);
         if (y >= a.count_y0 && y < a.count_y1) rays++;
-        if (shade_segment<TEX>(a, h, seg, light_c, o, d, acc, rng, tex)) {
+        if (shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0>(a, h, seg, light_c, o, d, acc, rng, tex)) {
           alive = false;
           const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
           a.image[gi] = make_float4(acc.x, acc.y, acc.z, a.depth[gi]);  // :328,:343 (+ depth in alpha)
@@ -1233,7 +1289,8 @@ __global__ void k_selftest_exhaustive(int op, unsigned long long* out) {
 
 // exact::div_ against hipcc's division.  mode 0: slice `pass` of 256 of the enumeration of all 2^23 x 2^23 significand pairs
 // (thread = one b, 2^15 values of a); mode 1: 2^33 operand pairs of arbitrary bits (every exponent, sign, zero, infinity,
-// NaN and denormal class gets hit: the long path and the range test) from a counter-based generator
+// NaN and denormal class gets hit: the long path and the range test) from a counter-based generator; mode 2: mode 1's pairs through
+// exact::quotient_positive(a, b) against a / b > 0.0f
 __global__ void k_selftest_div(int mode, uint32_t pass, unsigned long long* out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // 0 .. 2^23-1
   unsigned bad = 0;
@@ -1256,6 +1313,10 @@ __global__ void k_selftest_div(int mode, uint32_t pass, unsigned long long* out)
       ub ^= ub >> 22;
       if (i & 1u) ub = (ub & 0x807fffffu) | (ua & 0x7f800000u);  // every other pair: same exponent (quotients near 1)
       const float a = u2f(ua), b = u2f(ub);
+      if (mode == 2) {
+        if (exact::quotient_positive(a, b) != (a / b > 0.0f)) { bad++; fa = ua; fb = ub; }
+        continue;
+      }
       const uint32_t got = f2u(exact::div_(a, b)), want = f2u(a / b);
       if (got != want && !((got & 0x7fffffffu) > 0x7f800000u && (want & 0x7fffffffu) > 0x7f800000u)) { bad++; fa = ua; fb = ub; }
     }

@@ -93,11 +93,41 @@ __device__ __forceinline__ float div_(float a, float b) {
   if (__builtin_expect(!direct, 0)) q = a / b;
   return q;
 }
+// a0 / b and a1 / b: div_'s sequence with ONE refined reciprocal (6 VALU + v_rcp_f32 for the first quotient, 3 for the second);
+// direct only when all three operands lie in div_'s window, otherwise both quotients are hipcc's
+__device__ __forceinline__ void div2_(float a0, float a1, float b, float& q0, float& q1) {
+  const uint32_t u0 = f2u(a0), u1 = f2u(a1), ub = f2u(b);
+  const bool direct = ((u0 + u0) - 0x41000000u < 0x7c000000u) & ((u1 + u1) - 0x41000000u < 0x7c000000u) & ((ub + ub) - 0x41000000u < 0x7c000000u);
+  float r = __builtin_amdgcn_rcpf(b);
+  r = fmaf_(fmaf_(-b, r, 1.0f), r, r);
+  float x = a0 * r, y = a1 * r;
+  x = fmaf_(fmaf_(-b, x, a0), r, x);
+  y = fmaf_(fmaf_(-b, y, a1), r, y);
+  if (__builtin_expect(!direct, 0)) {
+    x = a0 / b;
+    y = a1 / b;
+  }
+  q0 = x;
+  q1 = y;
+}
 #else
 inline float sqrt_(float x) { return __builtin_sqrtf(x); }  // correctly rounded
 inline float rcp_(float x) { return 1.0f / x; }             // correctly rounded division
 inline float div_(float a, float b) { return a / b; }
+inline void div2_(float a0, float a1, float b, float& q0, float& q1) { q0 = a0 / b; q1 = a1 / b; }
 #endif
+
+// num / den > 0.0f for every pair of binary32 patterns, without the division where its sign is known beforehand.  With
+// 2^-126 <= den < 2^63 (positive, finite, normal) the quotient has num's sign or is a zero, so it is positive iff num > 0 and
+// it does not round to zero.  Round-to-nearest-even takes a quotient to +0 iff it is <= 2^-150 (2^-150 itself ties between 0
+// and 2^-149 and goes to the even one, 0); with num >= 2^-86 the quotient is > 2^-86 / 2^63 = 2^-149, so it stays positive.
+// num <= 0 and NaN num give a quotient that is negative, a zero or NaN — not positive, and "num > 0" says the same; +inf / den
+// is +inf.  What is left — 0 < num < 2^-86, and den that is zero, negative, subnormal, >= 2^63, infinite or NaN — divides.
+RT_HD bool quotient_positive(float num, float den) {
+  const bool direct = (den >= 0x1p-126f) & (den < 0x1p63f) & !((num > 0.0f) & (num < 0x1p-86f));
+  if (__builtin_expect(!direct, 0)) return num / den > 0.0f;
+  return num > 0.0f;
+}
 
 RT_HD float dot(f3 a, f3 b) { return fmaf_(a.z, b.z, fmaf_(a.y, b.y, a.x * b.x)); }
 RT_HD f3 cross(f3 a, f3 b) {
@@ -212,6 +242,7 @@ RT_HD float rng_next(uint32_t& s) {
   w = (w >> 22) ^ w;
   return static_cast<float>(w) * 2.3283064365386963e-10f;
 }
+RT_HD void rng_skip(uint32_t& s) { s = s * 747796405u + 1u; }  // rng_next's step of the state without its output
 RT_HD uint32_t rng_seed(uint32_t px, uint32_t py, uint32_t frame, uint32_t batch) {
   return (px * 3266489917u + py * 668265263u) ^ (frame * 374761393u) ^ (batch * 2654435761u);  // :297
 }
@@ -233,10 +264,12 @@ inline void mat_mul(const float* A, const float* B, float* C) {
 
 }  // namespace exact
 
+#if defined(__HIPCC__)  // device builtins: not for a plain C++ compiler (csrc/tests/quotient_positive_host_check.cpp includes this file)
 namespace fast {
 __device__ __forceinline__ float exp_(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 __device__ __forceinline__ float sqrt_(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float rcp_(float x) { return __builtin_amdgcn_rcpf(x); }
 }  // namespace fast
+#endif
 
 }  // namespace rt
