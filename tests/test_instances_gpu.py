@@ -6,7 +6,8 @@ The tree stays ONE tree over world-space triangles; a move re-flattens, re-poses
 oracle's arithmetic bit for bit, so every check here is bit for bit: against `oracle.flatten` for the triangles, against the
 oracle's frames for moving instances (`OracleApp.tris` is a plain attribute: setting it moves the instances and keeps
 lut_prev from the frame before), against the host-flattened context for trees and build info.  rtpt_debug_upload_info
-tells the device path from a host path that computes the same pixels.
+tells the device path from a host path that computes the same pixels.  The moves here are gentle and seen through a camera;
+test_refit_moves_gpu.py traces adversarial rays after hostile ones (stacked, swapped, flung, collapsed, mirrored instances).
 """
 import ctypes as C
 

@@ -9,6 +9,7 @@ rays aim at vertices, edges and shared edges, lie in planes, start on surfaces, 
 subnormal direction components, and start up to 5 000 scene diagonals away.
 
 Every case counts what it exercised against a floor, so a generator that drifts into missing everything fails.
+Every tree here was just built for its geometry; test_refit_moves_gpu.py holds a tree that was REFIT to a hostile pose to D4.
 RTPT_TRAVERSAL_SEEDS=k runs every case under k seeds instead of one."""
 import os
 
