@@ -594,8 +594,41 @@ int rtpt_selftest_exhaustive(rtpt_ctx* ctx, int op, uint64_t* mismatches, uint32
  * (~0.15 s per pass; all 256 is the proof that the short sequence is correctly rounded for operands of ordinary magnitude);
  * mode 1: n_passes x 2^33 operand pairs of arbitrary bits, pass numbers seeding the generator (range test + long path).
  * mode 2: mode 1's operand pairs through exact::quotient_positive(a, b) against a / b > 0.0f (the contract is 0 here too).
+ * mode 3: mode 1's operand pairs and a third draw through exact::div2_(a0, a1, b) against a0 / b and a1 / b (either quotient
+ * counts as one mismatch; first_bad = the offending numerator and b).
  * *mismatches = results that differ in any bit (two NaNs count as equal); first_bad = the bits of one offending (a, b). */
 int rtpt_selftest_div(rtpt_ctx* ctx, int mode, uint32_t first_pass, uint32_t n_passes, uint64_t* mismatches, uint32_t first_bad[2]);
+/* One function of the numerics contract per call, evaluated on the device item by item (one thread each) by the very
+ * functions the frame kernels call (csrc/rtpt_math.hpp, device_common.hpp, kernels.hip), for comparison with the oracle's
+ * oracle_contract_array operand by operand.  in = n items of `in` words, out = n items of `out` words, host arrays of raw
+ * 32-bit patterns: floats as their bits (NaN payloads and signed zeros pass unchanged), integers as they are.
+ *   fn                          in -> out   words
+ *    0 dot                       6 -> 1     a, b
+ *    1 cross                     6 -> 3     a, b
+ *    2 length                    3 -> 1
+ *    3 normalize                 3 -> 3
+ *    4 powi                      2 -> 1     x, n (int)
+ *    5 f2i                       1 -> 1     out: int
+ *    6 glsl_min, glsl_max        2 -> 2     x, y -> min, max
+ *    7 rng_seed                  4 -> 1     px, py, frame, batch (uint)
+ *    8 rng_next, rng_skip        1 -> 3     state -> state after rng_next, its float, state after rng_skip
+ *    9 sincos2pi                 1 -> 2     u in [0, 1] (the contract's domain) -> sin, cos
+ *   10 log_                      1 -> 1     x > 0, finite
+ *   11 exact::exp_               1 -> 1
+ *   12 mat_row_point            19 -> 4     M[16] column-major, p -> rows 0..3
+ *   13 div_                      2 -> 1     a, b
+ *   14 div2_                     3 -> 2     a0, a1, b -> a0 / b, a1 / b
+ *   15 tri_area                  9 -> 1     a, b, c
+ *   16 bary_coords              12 -> 3     p, a, b, c
+ *   17 bary_coords_at           13 -> 3     p, a, b, c, area
+ *   18 bary_mix                 12 -> 3     bc, a, b, c
+ *   19 reproject_pixel          36 -> 2     W, H (int), PVprev[16], id (0..3), wp, the id's three lut_prev cells (float4 each),
+ *                                           x, y (int) -> previous pixel x, y (int)
+ *   20 ray_hits_light           10 -> 1     o, d, c, radius (r2 = radius * radius as rtpt_raytrace forms it) -> 0 / 1
+ *   21 sky_color                 3 -> 3     d
+ *   22 hit_barycentrics          3 -> 6     u (HitRec::u, negated), v, ad -> b0, b1, b2 of <true>, then of <false>
+ * Operands outside a stated domain are not refused; what the functions do with them is not part of the contract. */
+int rtpt_selftest_contract(rtpt_ctx* ctx, int fn, const uint32_t* in, uint32_t* out, size_t n);
 /* closest-hit of arbitrary rays through the product's traversal (parity vs the oracle's brute
  * force): rays = n x {ox,oy,oz,dx,dy,dz}; out_id[n] = primitive id+1 or 0; out_t[n] may be NULL */
 int rtpt_selftest_trace(rtpt_ctx* ctx, const float* rays, size_t n, uint32_t* out_id, float* out_t);

@@ -57,7 +57,8 @@ static inline vec3 v3_normalize(vec3 a) {
 
 /* sin(2*pi*u), cos(2*pi*u) for u in [0,1]  (theta = 2*k_pi*rng at raytrace.comp.glsl:90,:256).
  * q = floor(4u + 0.5); r = u - q/4 (exact); phi = r * fl(2*pi) in [-pi/4, pi/4];
- * cephes sinf/cosf minimax polynomials, Horner with fma; quadrant select on q & 3. */
+ * cephes sinf/cosf minimax polynomials, Horner with fma; quadrant select on q & 3.
+ * [0,1] is the contract's whole domain: for |u| >= 2^29, an infinity or a NaN the conversion (int)qf is undefined. */
 static inline void dm_sincos2pi(float u, float* s_out, float* c_out) {
   float qf = __builtin_floorf(dm_fma(4.0f, u, 0.5f));
   float r = dm_fma(qf, -0.25f, u);

@@ -122,6 +122,30 @@ def math_array(op: int, x: np.ndarray) -> np.ndarray:
     return out
 
 
+CONTRACT_FNS = ("dot", "cross", "length", "normalize", "powi", "f2i", "minmax", "rng_seed", "rng_next_skip", "sincos2pi", "log",
+                "exp", "mat_row_point", "div", "div2", "tri_area", "bary_coords", "bary_coords_at", "bary_mix", "reproject_pixel",
+                "ray_hits_light", "sky_color", "hit_barycentrics")
+
+
+def contract_words(fn: int):
+    """(input words, output words) per item of contract function fn (the table of include/rtpt.h)"""
+    a, b = C.c_uint32(0), C.c_uint32(0)
+    if lib().oracle_contract_words(C.c_int(fn), C.byref(a), C.byref(b)):
+        raise ValueError(f"no contract function {fn}")
+    return int(a.value), int(b.value)
+
+
+def contract_array(fn: int, words: np.ndarray) -> np.ndarray:
+    """words [n, n_in] uint32 -> [n, n_out] uint32: one numerics-contract function on raw bit patterns (oracle_contract_array)"""
+    n_in, n_out = contract_words(fn)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    assert words.ndim == 2 and words.shape[1] == n_in, (words.shape, n_in)
+    out = np.zeros((len(words), n_out), np.uint32)
+    if lib().oracle_contract_array(C.c_int(fn), _p(words), _p(out), C.c_uint64(len(words))):
+        raise ValueError(f"no contract function {fn}")
+    return out
+
+
 def rng_seed(px, py, frame, batch=0) -> int:
     return int(lib().oracle_rng_seed(px, py, frame, batch))
 

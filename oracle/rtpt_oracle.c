@@ -975,3 +975,92 @@ void oracle_atrous_var(const oracle_config* cfg, const oracle_push_constants* pc
   atrous_var_args A = {cfg, pc, ubo, in, depth, vis, lut, lut_prev, worldpos, history, gradient, prev_vis, var_in, out, prev_pixel, var_out};
   run_ranges((int64_t)y0, (int64_t)y1, 4, atrous_var_range, &A);
 }
+
+/* ---------------------------------------------------------------- the contract, function by function
+ * One numerics-contract function per call on raw 32-bit words (the device side is rtpt_selftest_contract; include/rtpt.h
+ * carries the table of fn and its words per item).  Every case calls the function the passes above call. */
+static const uint32_t contract_words[ORACLE_CONTRACT_FNS][2] = {
+    {6, 1},  {6, 3},  {3, 1},  {3, 3},  {2, 1},  {1, 1},  {2, 2},  {4, 1},  {1, 3},  {1, 2},  {1, 1},  {1, 1},
+    {19, 4}, {2, 1},  {3, 2},  {9, 1},  {12, 3}, {13, 3}, {12, 3}, {36, 2}, {10, 1}, {3, 3},  {3, 6}};
+
+int oracle_contract_words(int fn, uint32_t* n_in, uint32_t* n_out) {
+  if (fn < 0 || fn >= ORACLE_CONTRACT_FNS) return -1;
+  *n_in = contract_words[fn][0];
+  *n_out = contract_words[fn][1];
+  return 0;
+}
+
+static inline vec3 cw_v(const uint32_t* w, int k) { return v3(dm_float(w[k]), dm_float(w[k + 1]), dm_float(w[k + 2])); }
+static inline void cw_put3(uint32_t* r, int k, vec3 v) { r[k] = dm_bits(v.x); r[k + 1] = dm_bits(v.y); r[k + 2] = dm_bits(v.z); }
+
+int oracle_contract_array(int fn, const uint32_t* in, uint32_t* out, uint64_t n) {
+  if (fn < 0 || fn >= ORACLE_CONTRACT_FNS) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t* w = in + i * contract_words[fn][0];
+    uint32_t* r = out + i * contract_words[fn][1];
+#define F(k) dm_float(w[k])
+#define V(k) cw_v(w, k)
+    switch (fn) {
+      case 0: r[0] = dm_bits(v3_dot(V(0), V(3))); break;
+      case 1: cw_put3(r, 0, v3_cross(V(0), V(3))); break;
+      case 2: r[0] = dm_bits(v3_length(V(0))); break;
+      case 3: cw_put3(r, 0, v3_normalize(V(0))); break;
+      case 4: r[0] = dm_bits(dm_powi(F(0), (int)w[1])); break;
+      case 5: r[0] = (uint32_t)dm_f2i(F(0)); break;
+      case 6: r[0] = dm_bits(dm_min(F(0), F(1))); r[1] = dm_bits(dm_max(F(0), F(1))); break;
+      case 7: r[0] = oracle_rng_seed(w[0], w[1], w[2], w[3]); break;
+      case 8: {
+        uint32_t st = w[0], sk = w[0];
+        float f;
+        oracle_rng_step(&st, &f);
+        oracle_rng_step(&sk, NULL); /* a skipped draw is a draw whose float nobody reads */
+        r[0] = st; r[1] = dm_bits(f); r[2] = sk;
+        break;
+      }
+      case 9: { float s, c; dm_sincos2pi(F(0), &s, &c); r[0] = dm_bits(s); r[1] = dm_bits(c); break; }
+      case 10: r[0] = dm_bits(dm_log(F(0))); break;
+      case 11: r[0] = dm_bits(dm_exp(F(0))); break;
+      case 12: {
+        float M[16];
+        for (int k = 0; k < 16; k++) M[k] = F(k);
+        for (int k = 0; k < 4; k++) r[k] = dm_bits(mat4_row_point(M, k, V(16)));
+        break;
+      }
+      case 13: r[0] = dm_bits(F(0) / F(1)); break;
+      case 14: r[0] = dm_bits(F(0) / F(2)); r[1] = dm_bits(F(1) / F(2)); break;
+      case 15: r[0] = dm_bits(tri_area(V(0), V(3), V(6))); break;
+      case 16: cw_put3(r, 0, bary_coords(V(0), V(3), V(6), V(9))); break;
+      case 17: { /* bary_coords with the supplied area */
+        vec3 p = V(0), a = V(3), b = V(6), c = V(9);
+        float at = F(12);
+        cw_put3(r, 0, v3(tri_area(p, b, c) / at, tri_area(a, p, c) / at, tri_area(a, b, p) / at));
+        break;
+      }
+      case 18: cw_put3(r, 0, bary_mix(V(0), V(3), V(6), V(9))); break;
+      case 19: { /* W, H, PVprev[16], id, wp[3], the id's three lut_prev cells, x, y; the cells stand at id & 3 of a table of four */
+        float M[16], wp4[4] = {F(19), F(20), F(21), 0.0f}, lut[48];
+        for (int k = 0; k < 16; k++) M[k] = F(2 + k);
+        uint32_t id = w[18] & 3u;
+        memset(lut, 0, sizeof lut);
+        for (int k = 0; k < 12; k++) lut[12 * id + k] = F(22 + k);
+        int px, py;
+        reproject((int)w[0], (int)w[1], M, id, wp4, lut, (int)w[34], (int)w[35], &px, &py);
+        r[0] = (uint32_t)px; r[1] = (uint32_t)py;
+        break;
+      }
+      case 20: r[0] = (uint32_t)ray_hits_light(V(0), V(3), V(6), F(9)); break;
+      case 21: cw_put3(r, 0, sky_color(V(0))); break;
+      case 22: { /* raytrace.comp.glsl:134 */
+        float u = F(0), v = F(1), ad = F(2);
+        float b1 = -u / ad, b2 = v / ad, b0 = 1.0f - b1 - b2;
+        cw_put3(r, 0, v3(b0, b1, b2));
+        cw_put3(r, 3, v3(b0, b1, b2));
+        break;
+      }
+      default: break;
+    }
+#undef F
+#undef V
+  }
+  return 0;
+}

@@ -86,6 +86,12 @@ float oracle_sqrt(float x);
 float oracle_rcp(float x);
 float oracle_powi(float x, int n);
 void oracle_math_array(int op, const float* in, float* out, uint64_t n);
+/* One contract function, item by item, on raw 32-bit words: fn and its {input, output} words per item are the table of
+ * include/rtpt.h (rtpt_selftest_contract, the device's side of the same comparison); oracle_contract_words reads one
+ * row of it.  Both return -1 for an fn outside the table. */
+#define ORACLE_CONTRACT_FNS 23
+int oracle_contract_words(int fn, uint32_t* n_in, uint32_t* n_out);
+int oracle_contract_array(int fn, const uint32_t* in, uint32_t* out, uint64_t n);
 
 /* --- RNG (raytrace.comp.glsl:71-78, :297) -------------------------------------------------- */
 uint32_t oracle_rng_seed(uint32_t px, uint32_t py, uint32_t frame, uint32_t batch);

@@ -119,8 +119,12 @@ SYMBOLS = [
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
     "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
-    "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain",
+    "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
 ]
+
+# rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
+CONTRACT_WORDS = ((6, 1), (6, 3), (3, 1), (3, 3), (2, 1), (1, 1), (2, 2), (4, 1), (1, 3), (1, 2), (1, 1), (1, 1), (19, 4), (2, 1),
+                  (3, 2), (9, 1), (12, 3), (13, 3), (12, 3), (36, 2), (10, 1), (3, 3), (3, 6))
 
 _lib = None
 
@@ -173,6 +177,7 @@ def load() -> C.CDLL:
         "rtpt_selftest_exhaustive": [vp, C.c_int, vp, vp],
         "rtpt_selftest_div": [vp, C.c_int, C.c_uint32, C.c_uint32, vp, vp],
         "rtpt_selftest_trace": [vp, vp, sz, vp, vp],
+        "rtpt_selftest_contract": [vp, C.c_int, vp, vp, sz],
         "rtpt_util_load_obj": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_util_bvh_check": [vp, u32, C.POINTER(C.c_uint64 * 8)],
         "rtpt_util_bvh_check_pairs": [vp, u32, C.c_int, C.POINTER(C.c_uint64 * 8)],
@@ -544,6 +549,17 @@ class Context:
         first = np.zeros(2, np.uint32)
         _check(self._lib.rtpt_selftest_div(self._h, mode, first_pass, n_passes, C.byref(n), _ptr(first)))
         return int(n.value), first
+
+    def selftest_contract(self, fn: int, words: np.ndarray) -> np.ndarray:
+        """words [n, n_in] uint32 -> [n, n_out] uint32: contract function fn on the device, one thread per item; the table of
+        fn and its words per item is in rtpt.h (rtpt_selftest_contract)"""
+        n_in, n_out = CONTRACT_WORDS[fn]
+        words = np.ascontiguousarray(words, np.uint32)
+        if words.ndim != 2 or words.shape[1] != n_in:
+            raise ValueError(f"contract function {fn} takes {n_in} words per item, got an array of shape {words.shape}")
+        out = np.zeros((len(words), n_out), np.uint32)
+        _check(self._lib.rtpt_selftest_contract(self._h, fn, _ptr(words), _ptr(out), len(words)))
+        return out
 
     def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:
         """[n, 4] RGBA the device sampler reads from textures[texture] at uv [n, 2] (rtpt_selftest_texture)"""

@@ -53,8 +53,8 @@ int rtpt_selftest_exhaustive(rtpt_ctx* c, int op, uint64_t* mismatches, uint32_t
 
 int rtpt_selftest_div(rtpt_ctx* c, int mode, uint32_t first_pass, uint32_t n_passes, uint64_t* mismatches, uint32_t first_bad[2]) {
   if (!c || !mismatches) return fail(RTPT_E_INVALID, "NULL argument");
-  if (mode < 0 || mode > 2)
-    return fail(RTPT_E_INVALID, "rtpt_selftest_div: mode must be 0 (significand pairs), 1 (arbitrary bits) or 2 (quotient_positive, arbitrary bits)");
+  if (mode < 0 || mode > 3)
+    return fail(RTPT_E_INVALID, "rtpt_selftest_div: mode must be 0 (significand pairs), 1 (arbitrary bits), 2 (quotient_positive, arbitrary bits) or 3 (div2_, arbitrary bits)");
   if (mode == 0 && (first_pass >= 256u || n_passes > 256u - first_pass))
     return fail(RTPT_E_INVALID, "rtpt_selftest_div: the enumeration has 256 passes");
   HIP_TRY(hipSetDevice(c->device));
@@ -76,6 +76,26 @@ int rtpt_selftest_div(rtpt_ctx* c, int mode, uint32_t first_pass, uint32_t n_pas
     first_bad[0] = static_cast<uint32_t>(h[1]);
     first_bad[1] = static_cast<uint32_t>(h[2]);
   }
+  return RTPT_OK;
+}
+
+int rtpt_selftest_contract(rtpt_ctx* c, int fn, const uint32_t* in, uint32_t* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (fn < 0 || fn >= rt::kContractFns) return fail(RTPT_E_INVALID, "rtpt_selftest_contract: no such fn (the table of include/rtpt.h)");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * rt::kContractWords[fn][0] * 4, out_bytes = n * rt::kContractWords[fn][1] * 4;
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_contract(fn, static_cast<const uint32_t*>(din.ptr), static_cast<uint32_t*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_contract: ") + hipGetErrorString(e));
   return RTPT_OK;
 }
 

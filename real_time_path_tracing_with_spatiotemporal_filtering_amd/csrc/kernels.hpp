@@ -373,6 +373,12 @@ void launch_selftest_exhaustive(int op, unsigned long long* out, hipStream_t s);
 void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipStream_t s);
 void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, float tmax, uint32_t* out_id,
                            float* out_t, hipStream_t s);
+// rtpt_selftest_contract: {input words, output words} per item of every fn (the table of include/rtpt.h, in its order)
+constexpr int kContractFns = 23;
+constexpr uint32_t kContractWords[kContractFns][2] = {
+    {6, 1},  {6, 3},  {3, 1},  {3, 3},  {2, 1},  {1, 1},  {2, 2},  {4, 1},  {1, 3},  {1, 2},  {1, 1},  {1, 1},
+    {19, 4}, {2, 1},  {3, 2},  {9, 1},  {12, 3}, {13, 3}, {12, 3}, {36, 2}, {10, 1}, {3, 3},  {3, 6}};
+void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 // tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs

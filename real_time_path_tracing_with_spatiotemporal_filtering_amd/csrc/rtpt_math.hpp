@@ -140,6 +140,9 @@ RT_HD f3 normalize(f3 a) {
 }
 
 // sin/cos of 2*pi*u, u in [0,1]; quarter-turn reduction is exact, then degree-7/8 minimax kernels
+// [0, 1] is the contract's whole domain (u is an RNG float): outside it the reduction is no longer exact, and for |u| >= 2^29, an
+// infinity or a NaN the conversion of qf to int is undefined in C++ and differs between the host and the device.  Nothing
+// compares the function there.
 RT_HD void sincos2pi(float u, float& s_out, float& c_out) {
   float qf = __builtin_floorf(fmaf_(4.0f, u, 0.5f));
   float r = fmaf_(qf, -0.25f, u);
