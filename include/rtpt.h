@@ -324,6 +324,35 @@ typedef struct rtpt_material {
 int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material* materials,
                              uint32_t n_materials);
 
+/* Specular materials (NOT reference behaviour, off until this call; additive: RTPT_ABI_VERSION stays 5).  A
+ * material is diffuse (flags 0: `albedo` and `emission` mean what they mean in rtpt_material, `specular` and `roughness` are
+ * only checked) or specular (RTPT_MAT_SPECULAR), never a mixture; no Fresnel term, no refraction.  A hit on a specular
+ * material takes `specular` (.mtl Ks) where a diffuse hit takes Kd — texel multiply, albedo plane, throughput multiply and
+ * mip level apply to it unchanged — and leaves along d' = normalize(reflect(d, n) + roughness * s), s the point of the unit
+ * sphere the diffuse bounce would add to the normal, from the same two draws (csrc/specular.hpp states the arithmetic;
+ * roughness 0 is a perfect mirror).  A d' that does not leave the surface ends the path with colour 0 (absorbed); the last
+ * segment of a path returns its throughput before any bounce, as for a diffuse hit.
+ * The call replaces whatever material set the scene has, and rtpt_scene_set_materials replaces a set given here; NULL / 0
+ * drops the set.  Lifetime and synchronisation are rtpt_scene_set_materials': dropped by rtpt_scene_upload, kept by
+ * rtpt_scene_set_instances, rtpt_scene_rebuild, a changed model and rtpt_resize; no plane tag changes, so frame reuse and
+ * reprojection reuse go on.  Device memory held: 32 bytes per triangle, as after rtpt_scene_set_materials.
+ * RTPT_E_INVALID, the scene and its set untouched: another n_tris than the uploaded mesh's, an index >= n_materials, an
+ * unknown flag, a component of any material that is not finite, a specular material with a roughness outside [0, 1] or with
+ * a non-zero emission.  The kernels that know the specular bounce run exactly when some TRIANGLE's material is specular.
+ * Known limitation: the filter's guides (normal, depth, id, world position, reprojection) are the mirror's own, so a
+ * reflected image is blurred over the filter's reach and reprojected with the mirror's surface. */
+#define RTPT_MAT_SPECULAR 0x1u
+typedef struct rtpt_material_ext {
+  float albedo[3];   /* .mtl Kd */
+  float emission[3]; /* .mtl Ke */
+  float specular[3]; /* .mtl Ks: the colour of a specular hit */
+  float roughness;   /* [0, 1] when specular; 0: mirror */
+  uint32_t flags;    /* RTPT_MAT_* */
+  uint32_t _pad;
+} rtpt_material_ext;
+int rtpt_scene_set_materials_ext(rtpt_ctx* ctx, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material_ext* materials,
+                                 uint32_t n_materials);
+
 /* Albedo textures (NOT reference behaviour, off until this call): the albedo of a hit becomes (Kd, or the
  * normal-keyed colour without materials) x texel.rgb — one binary32 multiply per channel, taken before the throughput
  * multiply — at EVERY segment of a path, in every kernel that shades (csrc/texture.hpp is the one sampler).  A surface with
@@ -638,6 +667,11 @@ int rtpt_selftest_trace(rtpt_ctx* ctx, const float* rays, size_t n, uint32_t* ou
  * rtpt_scene_set_textures, alpha included.  RTPT_E_NO_SCENE without a scene; RTPT_E_INVALID without textures, for an index
  * >= n_textures or a uv that is not finite. */
 int rtpt_selftest_texture(rtpt_ctx* ctx, uint32_t texture, const float* uv, size_t n, float* rgba_out);
+/* device-side evaluation of the specular bounce (csrc/specular.hpp: faceforward, the sphere point of the two draws, the lobe),
+ * one case per thread, by the function the tracing kernels call: in = n x 9 floats (d[3], n[3], u1, u2, g), out = n x 4
+ * floats (d'[3], 1.0f if absorbed else 0.0f).  Operands are not checked: d and n are meant to be unit vectors, u1, u2 in
+ * [0, 1], g in [0, 1]. */
+int rtpt_selftest_bounce(rtpt_ctx* ctx, const float* in, float* out, size_t n);
 /* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
  * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
  * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */
@@ -664,6 +698,13 @@ int rtpt_util_load_obj(const char* path, float* xyz, uint32_t* n_verts, uint32_t
  * OBJ names one that does not exist (scenes/CornellBox-Original-Merged.obj:3) — *n_materials comes back 0. */
 int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material* materials,
                                  uint32_t* n_materials);
+/* The same reader, contract and numbering, plus Ks, Ns and illum of every `newmtl`.  The rule is a definition:
+ *   specular[] = Ks (0 without a Ks line); roughness = min(1, sqrt(2 / (Ns + 2))) in binary32 (1 where that is no number in
+ *   [0, 1]), 0 without an Ns line; flags = RTPT_MAT_SPECULAR exactly when illum >= 3, Ks != 0 and Ke == 0 (an emitter ends
+ *   the path either way and stays diffuse); anything else stays diffuse.  albedo, emission and tri_material are what
+ *   rtpt_util_load_obj_materials returns for the same file. */
+int rtpt_util_load_obj_materials_ext(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
+                                     uint32_t* n_materials);
 /* the texture-coordinate side of the same file: `vt` records and the vt of `f v/vt`, `f v/vt/vn` corners (`f v`, `f v//vn`:
  * the corner gets (0, 0)); negative vt indices count back from the last `vt` read.  tri_uv: 6 floats per triangle (u0 v0 u1
  * v1 u2 v2), fanned like rtpt_util_load_obj's triangles, so the two arrays line up.  Two-call pattern (NULL: count). */

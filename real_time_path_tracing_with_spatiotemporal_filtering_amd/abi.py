@@ -84,6 +84,25 @@ class Material(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("emission", C.c_float * 3)]
 
 
+MAT_SPECULAR = 0x1
+# rtpt_material_ext as a numpy record (48 bytes): Kd, Ke, Ks, roughness, flags (MAT_*)
+MATERIAL_EXT = np.dtype([("albedo", np.float32, 3), ("emission", np.float32, 3), ("specular", np.float32, 3),
+                         ("roughness", np.float32), ("flags", np.uint32), ("_pad", np.uint32)])
+assert MATERIAL_EXT.itemsize == 48
+
+
+def materials_ext(materials, specular=None) -> np.ndarray:
+    """MATERIAL_EXT records of (Kd, Ke) rows [m, 6] (flags 0: the set rtpt_scene_set_materials would take); specular: a dict
+    material index -> (Ks, roughness) of the rows to make specular"""
+    rows = np.ascontiguousarray(materials, np.float32).reshape(-1, 6)
+    out = np.zeros(len(rows), MATERIAL_EXT)
+    out["albedo"], out["emission"] = rows[:, :3], rows[:, 3:]
+    for i, (ks, g) in (specular or {}).items():
+        out["specular"][i], out["roughness"][i], out["flags"][i] = np.float32(ks), np.float32(g), MAT_SPECULAR
+        out["emission"][i] = 0
+    return out
+
+
 class SceneBuildInfo(C.Structure):
     """struct rtpt_scene_build_info (32 bytes)."""
     _fields_ = [
@@ -120,6 +139,7 @@ SYMBOLS = [
     "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
+    "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -200,6 +220,9 @@ def load() -> C.CDLL:
         "rtpt_selftest_texture_lod": [vp, u32, vp, vp, sz, vp],
         "rtpt_selftest_texture_footprint": [vp, vp, sz, u32, vp, vp],
         "rtpt_util_texture_chain": [u32, u32, C.POINTER(u32), C.POINTER(C.c_uint64)],
+        "rtpt_scene_set_materials_ext": [vp, vp, u32, vp, u32],
+        "rtpt_util_load_obj_materials_ext": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
+        "rtpt_selftest_bounce": [vp, vp, vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -269,6 +292,19 @@ def load_obj_materials(path: str):
     tri = np.zeros(nt.value, np.uint32)
     mats = np.zeros((nm.value, 6), np.float32)
     _check(load().rtpt_util_load_obj_materials(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
+    return tri, mats
+
+
+def load_obj_materials_ext(path: str):
+    """load_obj_materials with Ks, Ns and illum: (tri_material[t] u32, materials[m] MATERIAL_EXT) by the rule of rtpt.h
+    (specular exactly when illum >= 3, Ks != 0 and Ke == 0; roughness min(1, sqrt(2 / (Ns + 2))), 0 without Ns)"""
+    nt, nm = C.c_uint32(), C.c_uint32()
+    _check(load().rtpt_util_load_obj_materials_ext(path.encode(), None, C.byref(nt), None, C.byref(nm)))
+    if nm.value == 0:
+        return None, None
+    tri = np.zeros(nt.value, np.uint32)
+    mats = np.zeros(nm.value, MATERIAL_EXT)
+    _check(load().rtpt_util_load_obj_materials_ext(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
     return tri, mats
 
 
@@ -559,6 +595,22 @@ class Context:
             raise ValueError(f"contract function {fn} takes {n_in} words per item, got an array of shape {words.shape}")
         out = np.zeros((len(words), n_out), np.uint32)
         _check(self._lib.rtpt_selftest_contract(self._h, fn, _ptr(words), _ptr(out), len(words)))
+        return out
+
+    def set_materials_ext(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
+        """per-triangle material indices + MATERIAL_EXT records (diffuse or specular); None drops the set"""
+        if tri_material is None or materials is None:
+            _check(self._lib.rtpt_scene_set_materials_ext(self._h, None, 0, None, 0))
+            return
+        tri = np.ascontiguousarray(tri_material, np.uint32)
+        mats = np.ascontiguousarray(materials, MATERIAL_EXT)
+        _check(self._lib.rtpt_scene_set_materials_ext(self._h, _ptr(tri), len(tri), _ptr(mats), len(mats)))
+
+    def selftest_bounce(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 4] (d', absorbed) of the device's specular bounce on cases [n, 9] = d, n, u1, u2, g (rtpt_selftest_bounce)"""
+        cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 9)
+        out = np.zeros((len(cases), 4), np.float32)
+        _check(self._lib.rtpt_selftest_bounce(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
 
     def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:

@@ -184,6 +184,7 @@ struct Scene {
   uint64_t lut_version[2] = {~0ull, ~0ull};  // model_version each LUT buffer was built for
   bool lut_prev_valid = false;               // D3
   Buf materials;                             // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
+  bool materials_specular = false;           // some triangle's record is specular (rtpt_scene_set_materials_ext): the SPEC kernels
   // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
   struct Textures {
     Buf records, desc, texels;

@@ -143,8 +143,9 @@ void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, fl
 // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (rtpt_ctx::trace_pool): the workgroups' slabs
 int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
   a.pool_slab = nullptr;
-  if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo && !c->scene.textures.records.ptr))
-    return RTPT_OK;  // (the pool form stores no albedo and samples no texture: such frames take the tile kernel)
+  if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo && !c->scene.textures.records.ptr &&
+        !c->scene.materials_specular))
+    return RTPT_OK;  // (the pool form stores no albedo, samples no texture and bounces diffusely: such frames take the tile kernel)
   const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
   if (need && c->path_pool.bytes < need)
     if (int rc = alloc_buf(c->path_pool, need)) return rc;
@@ -427,7 +428,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   }
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
-    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->stream);
+    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->scene.materials_specular, c->stream);
   }
   return launch_check(fused ? "gbuffer + temporal_gradient + raytrace" : "raytrace");
 }

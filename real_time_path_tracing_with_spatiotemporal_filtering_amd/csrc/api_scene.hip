@@ -2,6 +2,7 @@
 // :687-742; flattened on the host, or on the device: scene_flatten.hip), instances that move between frames
 // (rtpt_scene_set_instances), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
 #include "api_internal.hpp"
+#include "material_host.hpp"
 #include "texture_host.hpp"
 
 #include <chrono>
@@ -645,6 +646,7 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (!tri_material || !materials || !n_materials) {  // back to the reference's normal-keyed colours
     free_buf(c->scene.materials);
+    c->scene.materials_specular = false;
     return RTPT_OK;
   }
   if (n_tris != c->scene.n_base_tris) return fail(RTPT_E_INVALID, "one material index per triangle of the uploaded mesh");
@@ -658,12 +660,49 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
     r[7] = (m.emission[0] != 0.0f || m.emission[1] != 0.0f || m.emission[2] != 0.0f) ? 1.0f : 0.0f;
   }
   free_buf(c->scene.materials);  // never two sets at once; a failure below leaves the reference's colours
+  c->scene.materials_specular = false;  // (a set of rtpt_scene_set_materials_ext is replaced like any other)
   Buf recs;  // joins the scene when it is complete
   int rc = alloc_buf(recs, rec.size() * sizeof(float));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->scene.materials = std::move(recs);
+  return RTPT_OK;
+}
+
+int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material_ext* materials,
+                                 uint32_t n_materials) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const bool drop = !tri_material || !materials || !n_materials;
+  // everything that can refuse the call comes first: a refused call leaves the scene, and the set it has, untouched
+  if (!drop)
+    if (const char* why = rtpt_mat::check_materials(tri_material, n_tris, c->scene.n_base_tris, materials, n_materials))
+      return fail(RTPT_E_INVALID, why);
+  std::vector<float> rec;
+  bool any_specular = false;
+  if (!drop) {
+    try {
+      rec.resize(static_cast<size_t>(n_tris) * 8);
+    } catch (const std::bad_alloc&) {
+      return fail(RTPT_E_NOMEM, "host allocation failed (material records)");
+    }
+    any_specular = rtpt_mat::pack_records(tri_material, n_tris, materials, rec.data());
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the set being replaced
+  // K0, K1 and the filter read no material: no plane tag, no scene generation changes — frame reuse goes on
+  free_buf(c->scene.materials);  // never two sets at once, as in rtpt_scene_set_materials
+  c->scene.materials_specular = false;
+  if (drop) return RTPT_OK;
+  Buf recs;  // joins the scene when it is complete
+  int rc = alloc_buf(recs, rec.size() * sizeof(float));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->scene.materials = std::move(recs);
+  c->scene.materials_specular = any_specular;
   return RTPT_OK;
 }
 

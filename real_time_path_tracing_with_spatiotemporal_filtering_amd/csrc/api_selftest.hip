@@ -1,6 +1,7 @@
 // api_selftest.hip — self tests of the device arithmetic and of the acceleration structure, and the host-side stand-ins
 // for glm / tinyobjloader (rtpt_util_*): nothing a frame calls.
 #include "api_internal.hpp"
+#include "material_host.hpp"
 #include "texture_host.hpp"
 
 extern "C" {
@@ -96,6 +97,25 @@ int rtpt_selftest_contract(rtpt_ctx* c, int fn, const uint32_t* in, uint32_t* ou
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_contract: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
+int rtpt_selftest_bounce(rtpt_ctx* c, const float* in, float* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * 9 * sizeof(float), out_bytes = n * 4 * sizeof(float);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_bounce(static_cast<const float*>(din.ptr), static_cast<float*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_bounce: ") + hipGetErrorString(e));
   return RTPT_OK;
 }
 
@@ -639,6 +659,26 @@ int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint3
   if (materials) {
     if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
     std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material));
+  }
+  *n_materials = static_cast<uint32_t>(mats.size());
+  return RTPT_OK;
+}
+
+// Kd, Ke, Ks, Ns and illum: the reader and its rule live in material_host.hpp (host-only code a plain C++ program can exercise)
+int rtpt_util_load_obj_materials_ext(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
+                                     uint32_t* n_materials) {
+  if (!path || !n_tris || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
+  std::string err;
+  std::vector<rtpt_material_ext> mats;
+  bool any_library = false;
+  if (rtpt_mat::load_obj_materials(path, tri_material, n_tris, &mats, &any_library, &err)) return fail(RTPT_E_INVALID, err);
+  if (!any_library) {
+    *n_materials = 0;
+    return RTPT_OK;
+  }
+  if (materials) {
+    if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
+    std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material_ext));
   }
   *n_materials = static_cast<uint32_t>(mats.size());
   return RTPT_OK;

@@ -10,6 +10,7 @@
 // No MFMA anywhere: nothing on this path is a dense contraction.  Compile with -ffp-contract=off.
 #include "device_common.hpp"
 #include "select.hpp"
+#include "specular.hpp"
 
 namespace rt {
 namespace {
@@ -784,7 +785,11 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // instantiations over fan pairs (BVH == 2, TEX == 0; pinned at 64 VGPRs with 8 to 14 spilled ones — the early return cost
 // k_gbuffer_pathtrace<2, false, 0>, the kernel of the instanced frame, one more: 36 -> 40 bytes of scratch) and the segment that
 // stores the albedo plane (alb_px; 0 -> 8 bytes in the brute-force DEMOD kernels), which is a path's last only with max_segments 1.
-template <int TEX, int BVH = 1, bool SHORT_DIV = false>
+// SPEC: some triangle's material is specular (rtpt_scene_set_materials_ext; specular.hpp states the bounce): such a hit takes Ks
+// where a diffuse one takes Kd — the record's colour, so everything above happens to it unchanged — and leaves along the lobe
+// around its mirror direction, with the same two draws.  A compile-time switch for DEMOD's and TEX's reason.  These instantiations
+// return early on every last segment (no exception for their registers: they are new), so that no schedule absorbs a path there.
+template <int TEX, int BVH = 1, bool SHORT_DIV = false, bool SPEC = false>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
@@ -799,7 +804,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
   float4 s0 = s[0], s1 = s[1], s2 = s[2];
-  const bool last = (RTPT_TRACE_ITEMS & 1) && !(BVH == 2 && TEX == 0) && !alb_px && seg + 1 >= a.max_segments;  // block-uniform
+  const bool last = (RTPT_TRACE_ITEMS & 1) && (SPEC || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
   float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
   f3 pos{0.f, 0.f, 0.f};
   if (!last) {
@@ -807,6 +812,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     pos = bary_point(xyz(s0), xyz(s1), xyz(s2), b0, b1, b2);      // :137
   }
   f3 n{s0.w, s1.w, s2.w};                                          // :150 (precomputed per triangle)
+  [[maybe_unused]] float spec_w = 0.0f;  // SPEC: the record's spare word, 0 = diffuse (specular.hpp)
   f3 alb = (n.x > 0.99f) ? f3{1.f, 0.f, 0.f} : ((-n.x > 0.99f) ? f3{0.f, 1.f, 0.f} : f3{0.7f, 0.7f, 0.7f});  // :155-163
   if (a.scene.materials) {
     // SURVEY 8(f) rank 4, not reference behaviour: a material library replaces the normal-keyed colours; a surface
@@ -819,6 +825,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       return true;
     }
     alb = f3{m0.x, m0.y, m0.z};
+    if constexpr (SPEC) spec_w = m0.w;
   }
   if (TEX) {
     const float4* tr = tex.records + 2 * static_cast<size_t>((h.id1 - 1) % a.scene.n_base_tris);
@@ -855,6 +862,15 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   exact::sincos2pi(exact::rng_next(rng), st_, ct);                 // :256
   float u = fmaf_(2.0f, exact::rng_next(rng), -1.0f);              // :257
   float r = exact::sqrt_(fmaf_(-u, u, 1.0f));                      // :258
+  if constexpr (SPEC) {
+    if (spec::is_specular(spec_w)) {
+      bool absorbed;
+      d = spec::lobe(n, d, r, ct, st_, u, spec::roughness(spec_w), &absorbed);
+      if (seg + 1 >= a.max_segments) return true;  // (only builds without the early return get here)
+      if (absorbed) acc = f3{0.f, 0.f, 0.f};
+      return absorbed;
+    }
+  }
   d = exact::normalize(f3{fmaf_(r, ct, n.x), fmaf_(r, st_, n.y), n.z + u});  // :259-261
   return seg + 1 >= a.max_segments;  // budget exhausted: the path returns its throughput (:270)
 }
@@ -924,8 +940,8 @@ constexpr int kPtWaves = 8;
 // taller than the tile grid (a.tiles_y rows of tiles).
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
-// TEX: shade_segment samples the scene's albedo textures.
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX>
+// TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (specular.hpp).
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, bool SPEC = false>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex) {
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -1015,7 +1031,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
         // the short barycentric divisions where they cost no register: with DEMOD or without compaction they spill one
         constexpr bool kShortDiv = (RTPT_TRACE_ITEMS & 8) && BVH == 0 && COMPACT && !DEMOD;
-        const bool done = shade_segment<TEX, BVH, kShortDiv>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
+        const bool done = shade_segment<TEX, BVH, kShortDiv, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
         if (done) {
           alive = false;
           if (a.spp == 1) {
@@ -1112,17 +1128,17 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
 constexpr int kPtBvhWaves = 8;
-template <int BVH, bool COMPACT, bool DEMOD, int TEX>
+template <int BVH, bool COMPACT, bool DEMOD, int TEX, bool SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex) {
-  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX>(a, tex);
+  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex);
 }
-template <bool COMPACT, bool DEMOD, int TEX>
+template <bool COMPACT, bool DEMOD, int TEX, bool SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex) {
-  pathtrace_tile<false, COMPACT, false, DEMOD, TEX>(a, tex);
+  pathtrace_tile<false, COMPACT, false, DEMOD, TEX, SPEC>(a, tex);
 }
 
 // K0 + K1 + K2 in one launch (rtpt_gbuffer / rtpt_temporal_gradient recorded right before rtpt_raytrace: main.cpp:1105-1107
@@ -1132,12 +1148,12 @@ void k_pathtrace_small(PathtraceArgs a, TexView tex) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD, int TEX>
+template <int BVH, bool DEMOD, int TEX, bool SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<BVH, true, true, DEMOD, TEX>(a, tex);
+    pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1146,12 +1162,12 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
     gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
-template <bool DEMOD, int TEX>
+template <bool DEMOD, int TEX, bool SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   if (blockIdx.y < a.tiles_y) {
-    pathtrace_tile<0, true, true, DEMOD, TEX>(a, tex);
+    pathtrace_tile<0, true, true, DEMOD, TEX, SPEC>(a, tex);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE
@@ -1161,7 +1177,7 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   }
 }
 
-template <int BVH, int TEX>
+template <int BVH, int TEX, bool SPEC>
 __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
@@ -1197,7 +1213,7 @@ __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a,
         closest_hit<BVH>(a.scene, o, d, h, stack, tid, kPtThreads, 1 + static_cast<int>(seg));  // :208-222
         const int x = static_cast<int>(pix & 0xFFFFu), y = static_cast<int>(pix >> 16);
         if (y >= a.count_y0 && y < a.count_y1) rays++;
-        if (shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0>(a, h, seg, light_c, o, d, acc, rng, tex)) {
+        if (shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex)) {
           alive = false;
           const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
           a.image[gi] = make_float4(acc.x, acc.y, acc.z, a.depth[gi]);  // :328,:343 (+ depth in alpha)
@@ -1431,6 +1447,17 @@ __global__ void k_selftest_contract(int fn, uint32_t n_in, uint32_t n_out, const
   }
 }
 
+// specular.hpp's bounce, one case per thread: in = d, n, u1, u2, g; out = d', 1.0f if absorbed else 0.0f (rtpt_selftest_bounce)
+__global__ void k_selftest_bounce(const float* in, float* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = in + 9 * i;
+  bool absorbed;
+  const f3 dn = spec::bounce(ld3(w + 3), ld3(w), w[6], w[7], w[8], &absorbed);
+  out[4 * i] = dn.x; out[4 * i + 1] = dn.y; out[4 * i + 2] = dn.z;
+  out[4 * i + 3] = absorbed ? 1.0f : 0.0f;
+}
+
 template <int BVH>
 __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const float* rays, size_t n, float tmax,
                                                              uint32_t* out_id, float* out_t) {
@@ -1571,7 +1598,7 @@ uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
   const int tr = pathtrace_uses_pool(a) ? kPoolRows : kPtRows;
   return gx * ((a.g.y1 - a.g.y0 + tr - 1) / tr + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0));
 }
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, hipStream_t s) {
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s) {
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
   const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
@@ -1603,26 +1630,29 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       hipLaunchKernelGGL((k_pathtrace_pool<false>), grid, block, dyn, s, b, GbufferArgs{});
   } else
 #endif
-  // the instantiation list of the family: scene mode x DEMOD x TEX (x COMPACT for the unfused launch), here and nowhere else
+  // the instantiation list of the family: scene mode x DEMOD x TEX x SPEC (x COMPACT for the unfused launch), here and nowhere else
   with_scene_mode(a.scene, [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
       constexpr bool D = decltype(demod)::value;
       with_tex_mode(tex, [&](auto tex_mode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tex_mode)::value;
-        if (gb) {
-          if constexpr (M != 0)
-            hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T>), grid, block, dyn, s, b, *gb, tex);
-          else
-            hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T>), grid, block, dyn, s, b, *gb, tex);
-          return;
-        }
-        with_bool(a.compact != 0, [&](auto compact) {
-          constexpr bool C = decltype(compact)::value;
-          if constexpr (M != 0)
-            hipLaunchKernelGGL((k_pathtrace<M, C, D, T>), grid, block, dyn, s, b, tex);
-          else
-            hipLaunchKernelGGL((k_pathtrace_small<C, D, T>), grid, block, dyn, s, b, tex);
+        with_bool(specular, [&](auto spec) {  // rtpt_scene_set_materials_ext: the instantiations that bounce specular materials
+          constexpr bool S = decltype(spec)::value;
+          if (gb) {
+            if constexpr (M != 0)
+              hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T, S>), grid, block, dyn, s, b, *gb, tex);
+            else
+              hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T, S>), grid, block, dyn, s, b, *gb, tex);
+            return;
+          }
+          with_bool(a.compact != 0, [&](auto compact) {
+            constexpr bool C = decltype(compact)::value;
+            if constexpr (M != 0)
+              hipLaunchKernelGGL((k_pathtrace<M, C, D, T, S>), grid, block, dyn, s, b, tex);
+            else
+              hipLaunchKernelGGL((k_pathtrace_small<C, D, T, S>), grid, block, dyn, s, b, tex);
+          });
         });
       });
     });
@@ -1644,7 +1674,10 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
     with_scene_mode(a.scene, [&](auto mode) {
       with_tex_mode(tex, [&](auto tex_mode) {
-        hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_mode)::value>), qgrid, block, dyn_queue, s, c, tex);
+        with_bool(specular, [&](auto spec) {
+          hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_mode)::value, decltype(spec)::value>), qgrid, block,
+                             dyn_queue, s, c, tex);
+        });
       });
     });
     if (end >= a.max_segments) break;
@@ -1667,6 +1700,10 @@ void launch_selftest_div(int mode, uint32_t pass, unsigned long long* out, hipSt
 void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
   if (!n || fn < 0 || fn >= kContractFns) return;
   hipLaunchKernelGGL(k_selftest_contract, dim3((n + 255) / 256), dim3(256), 0, s, fn, kContractWords[fn][0], kContractWords[fn][1], in, out, n);
+}
+void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_bounce, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
 }
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s) {
   if (!n) return;

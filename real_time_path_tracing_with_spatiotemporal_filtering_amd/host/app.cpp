@@ -68,6 +68,11 @@ void PathTracingApplication::loadMesh() {
     triMaterial.resize(ntm);
     check(rtpt_util_load_obj_materials(opt_.scene.c_str(), triMaterial.data(), &ntm, objMaterials.data(), &nm), "loadMesh");
   }
+  objMaterialsExt.clear();
+  if (opt_.specular && !objMaterials.empty()) {  // the same numbering and Kd / Ke, plus Ks / Ns / illum by the loader's rule
+    objMaterialsExt.resize(nm);
+    check(rtpt_util_load_obj_materials_ext(opt_.scene.c_str(), triMaterial.data(), &ntm, objMaterialsExt.data(), &nm), "loadMesh");
+  }
   // configs[4]: tessellated quads on a lattice of instances (scene_gen.hpp); camera, light and far plane frame the lattice
   sceneTextures_ = SceneTextures{};
   if (opt_.textures) {
@@ -180,7 +185,11 @@ void PathTracingApplication::buildAccelerationStructure() {
   // world-space bounds of the scene: strips bound the reprojection reach with them (strips.hpp)
   sceneBounds();
   auto materials = [&](rtpt_ctx* ctx) {
-    if (!objMaterials.empty())
+    if (!objMaterialsExt.empty())
+      check(rtpt_scene_set_materials_ext(ctx, triMaterial.data(), static_cast<uint32_t>(triMaterial.size()), objMaterialsExt.data(),
+                                         static_cast<uint32_t>(objMaterialsExt.size())),
+            "rtpt_scene_set_materials_ext");
+    else if (!objMaterials.empty())
       check(rtpt_scene_set_materials(ctx, triMaterial.data(), static_cast<uint32_t>(triMaterial.size()), objMaterials.data(),
                                      static_cast<uint32_t>(objMaterials.size())),
             "rtpt_scene_set_materials");

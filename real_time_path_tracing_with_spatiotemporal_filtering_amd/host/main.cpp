@@ -24,6 +24,7 @@ static void usage(const char* argv0) {
       "          [--textures [--texture-filter bilinear|nearest] [--texture-mips]  (sample the map_Kd images of the OBJ's library, binary\n"
       "           PPM / PFM next to the OBJ, at every hit: rtpt_scene_set_textures; without it an OBJ with map_Kd renders as it always did;\n"
       "           --texture-mips: from generated mip chains, at the level of the ray's footprint, RTPT_TEX_MIPMAP)]\n"
+      "          [--specular  (a newmtl with illum >= 3 and Ks != 0 bounces as a mirror, or glossy by its Ns: rtpt_scene_set_materials_ext)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -86,6 +87,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--demodulate")) opt.flags |= RTPT_FLAG_EXT_DEMODULATE;
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
     else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
+    else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
     else if (!std::strcmp(argv[i], "--texture-filter")) {
       const char* v = need("--texture-filter");
       if (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear")) { std::fprintf(stderr, "--texture-filter nearest|bilinear\n"); return 2; }
