@@ -308,6 +308,131 @@ def raytrace_seq_mat(cfg, pc: PushConstants, tris, tri_mat=None, y0=0, y1=None):
     return img, int(rc.value), hid, seq_id, seq_n, seq_end, dir0
 
 
+class ShadeExt(C.Structure):
+    """oracle_shade_ext, rtpt_oracle.h"""
+    _fields_ = [("tri_uv", C.c_void_p), ("tri_texture", C.c_void_p), ("textures", C.c_void_p), ("texels", C.c_void_p),
+                ("levels", C.c_void_p), ("bounce_spread", C.c_float), ("specular", C.c_uint32), ("albedo", C.c_void_p),
+                ("rec_lod", C.c_void_p), ("rec_code", C.c_void_p), ("rec_albedo", C.c_void_p), ("rec_ray", C.c_void_p)]
+
+
+END_ABSORBED = 5  # raytrace_ext only
+TEX_NEAREST, TEX_MIPMAP, TEX_MAX_LEVELS, TEX_LEVEL_ROW = 0x1, 0x10, 17, 18
+REC_HIT, REC_TEXTURED, REC_SPECULAR, REC_ABSORBED = 0x1, 0x2, 0x4, 0x8
+
+
+def level_row(first_texels) -> np.ndarray:
+    """one row of the level table: the first texel of every level, then their number at [17]"""
+    row = np.zeros(TEX_LEVEL_ROW, np.uint32)
+    row[:len(first_texels)] = first_texels
+    row[TEX_MAX_LEVELS] = len(first_texels)
+    return row
+
+
+def material_records_ext(tri_material, materials, specular=None) -> np.ndarray:
+    """material_records with the specular word as the device stores it: specular = {material: (Ks, g)} turns those rows into
+    (Ks, -g, 0, 0, 0, 0) (the mirror is -0.0f); every other row keeps 0 there"""
+    mats = np.array(materials, np.float32).reshape(-1, 6)
+    word = np.zeros(len(mats), np.float32)
+    for m, (ks, g) in (specular or {}).items():
+        mats[m, :3], mats[m, 3:], word[m] = np.float32(ks), 0, -np.float32(g)
+    rec = material_records(tri_material, mats)
+    rec[:, 3] = word[np.asarray(tri_material, np.int64)]
+    return rec
+
+
+def raytrace_ext(cfg, pc: PushConstants, tris, tri_mat=None, n_base=None, y0=0, y1=None, textures=None, levels=None,
+                 bounce_spread=0.125, specular=False, want_albedo=False, records=True, dump=True, null_ext=False):
+    """oracle_raytrace_ext: raytrace_seq_mat with the shading extensions.  textures = (tri_uv [b, 6], tri_texture [b], descriptors
+    [n, 4] u32, texels [m, 4]); levels [n, 18] u32 (level_row) or None: no mips; specular: word 3 of tri_mat is the device's
+    specular word (material_records_ext); want_albedo: segment 0's albedo goes to the ALBEDO plane.  Returns a dict: IMAGE, HIT_ID,
+    rays, seq_id, seq_n, seq_end, dir0, and ALBEDO, rec_lod, rec_code, rec_albedo, rec_ray as asked for (per record, like seq_id);
+    null_ext: the struct itself is NULL"""
+    W, H = cfg.width, cfg.height
+    y1 = H if y1 is None else y1
+    max_rec = int(cfg.max_segments) * int(cfg.samples_per_pixel)
+    out = dict(IMAGE=np.zeros((H, W, 4), np.float32), HIT_ID=np.zeros((H, W), np.uint32))
+    rc = C.c_uint64(0)
+    d = None
+    if dump:
+        out.update(seq_id=np.zeros((H, W, max_rec), np.uint16), seq_n=np.zeros((H, W), np.int32), seq_end=np.zeros((H, W), np.uint8),
+                   dir0=np.zeros((H, W, 3), np.float32))
+        d = SeqDump(out["seq_id"].ctypes.data, out["seq_n"].ctypes.data, out["seq_end"].ctypes.data, max_rec, out["dir0"].ctypes.data)
+    if tri_mat is not None:
+        tri_mat = np.ascontiguousarray(tri_mat, np.float32)
+        n_base = len(tri_mat) if n_base is None else n_base
+    e = ShadeExt()
+    e.bounce_spread, e.specular = bounce_spread, int(bool(specular))
+    keep = []
+    if textures is not None:
+        uv, tt, desc, texels = textures
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 6)
+        tt = np.ascontiguousarray(tt, np.uint32).ravel()
+        desc = np.ascontiguousarray(desc, np.uint32).reshape(-1, 4)
+        texels = np.ascontiguousarray(texels, np.float32).reshape(-1, 4)
+        assert len(uv) == len(tt) and int(tt.max(initial=0)) <= len(desc)
+        n_base = len(tt) if n_base is None else n_base
+        assert n_base == len(tt)
+        keep += [uv, tt, desc, texels]
+        e.tri_uv, e.tri_texture, e.textures, e.texels = (a.ctypes.data for a in (uv, tt, desc, texels))
+        if levels is not None:
+            levels = np.ascontiguousarray(levels, np.uint32).reshape(len(desc), TEX_LEVEL_ROW)
+            keep.append(levels)
+            e.levels = levels.ctypes.data
+    if want_albedo:
+        out["ALBEDO"] = np.zeros((H, W, 4), np.float32)
+        e.albedo = out["ALBEDO"].ctypes.data
+    if dump and records:
+        out.update(rec_lod=np.zeros((H, W, max_rec), np.float32), rec_code=np.zeros((H, W, max_rec), np.uint8),
+                   rec_albedo=np.zeros((H, W, max_rec, 3), np.float32), rec_ray=np.zeros((H, W, max_rec, 6), np.float32))
+        e.rec_lod, e.rec_code, e.rec_albedo, e.rec_ray = (out[k].ctypes.data for k in ("rec_lod", "rec_code", "rec_albedo", "rec_ray"))
+    tris = np.ascontiguousarray(tris, np.float32)
+    lib().oracle_raytrace_ext(C.byref(cfg), C.byref(pc), _p(tris), C.c_uint32(len(tris)), _p(tri_mat), C.c_uint32(n_base or 0),
+                              C.c_uint32(y0), C.c_uint32(y1), _p(out["IMAGE"]), C.byref(rc), _p(out["HIT_ID"]),
+                              C.byref(d) if d is not None else None, None if null_ext else C.byref(e))
+    out["rays"] = int(rc.value)
+    return out
+
+
+def texture_sample(texture, texels, uv) -> np.ndarray:
+    """[n, 4]: the oracle's sampler of one texture (width, height, first texel, flags) at uv [n, 2]"""
+    texture = np.ascontiguousarray(texture, np.uint32).reshape(4)
+    texels = np.ascontiguousarray(texels, np.float32).reshape(-1, 4)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((len(uv), 4), np.float32)
+    lib().oracle_texture_sample_array(_p(texture), _p(texels), _p(uv), C.c_uint64(len(uv)), _p(out))
+    return out
+
+
+def texture_sample_lod(texture, row, texels, uv, lod) -> np.ndarray:
+    """[n, 4]: the same at an explicit level lod [n] (any bit pattern); row: level_row of the texture's chain"""
+    texture = np.ascontiguousarray(texture, np.uint32).reshape(4)
+    row = np.ascontiguousarray(row, np.uint32).reshape(TEX_LEVEL_ROW)
+    texels = np.ascontiguousarray(texels, np.float32).reshape(-1, 4)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    lod = np.ascontiguousarray(np.broadcast_to(np.asarray(lod, np.float32), (len(uv),)))
+    out = np.zeros((len(uv), 4), np.float32)
+    lib().oracle_texture_sample_lod_array(_p(texture), _p(row), _p(texels), _p(uv), _p(lod), C.c_uint64(len(uv)), _p(out))
+    return out
+
+
+def texture_footprint(w, nd, p, uv6, W, H) -> np.ndarray:
+    """[n]: the level before the clamp of footprints w [n] at n . d = nd [n] on triangles p [n, 3, 3] with uv records uv6 [n, 6]"""
+    w, nd = np.asarray(w, np.float32).reshape(-1, 1), np.asarray(nd, np.float32).reshape(-1, 1)
+    items = np.ascontiguousarray(np.concatenate([w, nd, np.asarray(p, np.float32).reshape(len(w), 9),
+                                                 np.asarray(uv6, np.float32).reshape(len(w), 6)], 1), np.float32)
+    out = np.zeros(len(items), np.float32)
+    lib().oracle_texture_footprint_array(_p(items), C.c_uint64(len(items)), C.c_uint32(W), C.c_uint32(H), _p(out))
+    return out
+
+
+def bounce(cases) -> np.ndarray:
+    """[n, 4] (d', 1.0 if absorbed else 0.0) of cases [n, 9] = d, n, u1, u2, g: the oracle's specular bounce"""
+    cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 9)
+    out = np.zeros((len(cases), 4), np.float32)
+    lib().oracle_bounce_array(_p(cases), C.c_uint64(len(cases)), _p(out))
+    return out
+
+
 def moments(cfg, pc: PushConstants, ubo: Ubo, traced, vis, worldpos, lut_prev, prev_vis, moments_prev, y0=0, y1=None):
     """extension EXT_VARIANCE: (moments[H,W,4] = m1, m2, n, var; variance[H,W])"""
     W, H = cfg.width, cfg.height

@@ -568,6 +568,147 @@ static inline int ray_hits_light(vec3 o, vec3 d, vec3 center, float radius) {
   return 0;
 }
 
+/* ---------------------------------------------------------------- K2's shading extensions (not reference behaviour)
+ * Albedo textures, mip levels by ray footprint and the specular bounce, stated from the prose of the library's texture.hpp
+ * (lines 5-33) and specular.hpp (lines 6-21) with the dm_ functions; -ffp-contract=off, so only the dm_fma written here fuse. */
+typedef struct { float r, g, b, a; } rgba;
+
+/* repeat wrap: s = u - floor(u), in [0, 1]; a NaN (an infinite u) takes 0 */
+static inline float tex_wrap(float u) {
+  float s = u - __builtin_floorf(u);
+  return s >= 0.0f ? s : 0.0f;
+}
+static inline float tex_lerp(float a, float b, float f) { return a + f * (b - a); }
+static inline rgba tex_lerp4(rgba a, rgba b, float f) {
+  rgba o = {tex_lerp(a.r, b.r, f), tex_lerp(a.g, b.g, f), tex_lerp(a.b, b.b, f), tex_lerp(a.a, b.a, f)};
+  return o;
+}
+static inline rgba tex_texel(const float* t, uint32_t i) {
+  rgba o = {t[4 * (uint64_t)i], t[4 * (uint64_t)i + 1], t[4 * (uint64_t)i + 2], t[4 * (uint64_t)i + 3]};
+  return o;
+}
+/* bilinear taps of one axis: x = s n - 0.5, x0 = floor(x), f = x - x0; taps x0 and x0 + 1 wrapped into [0, n) */
+static inline void tex_taps(float s, int n, int* i0, int* i1, float* f) {
+  float x = s * (float)n - 0.5f;
+  float x0 = __builtin_floorf(x);
+  *f = x - x0;
+  int k = (x0 >= -1.0f && x0 <= (float)n) ? (int)x0 : 0; /* always in [-1, n - 1]; the test only keeps the cast defined */
+  int a = k % n, b = (k + 1) % n;
+  *i0 = a < 0 ? a + n : a;
+  *i1 = b < 0 ? b + n : b;
+}
+/* one level: a W x H rectangle of the atlas that starts at texel `first` */
+static rgba tex_sample(const float* texels, uint32_t W, uint32_t H, uint32_t first, uint32_t flags, float u, float v) {
+  const float* t = texels + 4 * (uint64_t)first;
+  float su = tex_wrap(u), sv = tex_wrap(v);
+  if (flags & ORACLE_TEX_NEAREST) {
+    float fi = __builtin_floorf(su * (float)W), fj = __builtin_floorf(sv * (float)H);
+    int i = fi < (float)(W - 1) ? (int)fi : (int)W - 1; /* s == 1.0 belongs to the last texel */
+    int j = fj < (float)(H - 1) ? (int)fj : (int)H - 1;
+    if (i < 0) i = 0;
+    if (j < 0) j = 0;
+    return tex_texel(t, (uint32_t)j * W + (uint32_t)i);
+  }
+  int i0, i1, j0, j1;
+  float fx, fy;
+  tex_taps(su, (int)W, &i0, &i1, &fx);
+  tex_taps(sv, (int)H, &j0, &j1, &fy);
+  rgba top = tex_lerp4(tex_texel(t, (uint32_t)j0 * W + (uint32_t)i0), tex_texel(t, (uint32_t)j0 * W + (uint32_t)i1), fx);
+  rgba bot = tex_lerp4(tex_texel(t, (uint32_t)j1 * W + (uint32_t)i0), tex_texel(t, (uint32_t)j1 * W + (uint32_t)i1), fx);
+  return tex_lerp4(top, bot, fy);
+}
+/* the piecewise-linear log2 of a positive finite binary32: exponent + mantissa bits 2^-23 */
+static inline float tex_plog2(float x) {
+  uint32_t b = dm_bits(x);
+  return (float)((int)(b >> 23) - 127) + (float)(b & 0x7FFFFFu) * 0x1p-23f;
+}
+/* the level of a footprint of width w on the triangle p (3 x 3 floats) with uv record uv6, before the clamp */
+static float tex_footprint_lod(float w, float nd, const float* p, const float* uv6, uint32_t W, uint32_t H) {
+  float e1x = p[3] - p[0], e1y = p[4] - p[1], e1z = p[5] - p[2];
+  float e2x = p[6] - p[0], e2y = p[7] - p[1], e2z = p[8] - p[2];
+  float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+  float aw = dm_sqrt((cx * cx + cy * cy) + cz * cz);
+  float u0 = uv6[0], v0 = uv6[1], u1 = uv6[2], v1 = uv6[3], u2 = uv6[4], v2 = uv6[5];
+  float at = fabsf(((u1 - u0) * (v2 - v0) - (u2 - u0) * (v1 - v0)) * ((float)W * (float)H));
+  float D = at / aw;
+  float rho2 = ((w * w) * D) / (nd * nd);
+  if (!(D > 0.0f && D < INFINITY && rho2 > 0.0f && rho2 < INFINITY)) return 0.0f;
+  return 0.5f * tex_plog2(rho2);
+}
+/* lambda > 0 ? lambda : 0 (a NaN too), then lambda < L - 1 ? lambda : L - 1 */
+static inline float tex_clamp_lod(float lambda, uint32_t L) {
+  float top = (float)(L - 1u);
+  lambda = lambda > 0.0f ? lambda : 0.0f;
+  return lambda < top ? lambda : top;
+}
+static inline uint32_t tex_level_count(const uint32_t* row) {
+  uint32_t L = row[ORACLE_TEX_MAX_LEVELS];
+  return L < 1u ? 1u : (L > ORACLE_TEX_MAX_LEVELS ? ORACLE_TEX_MAX_LEVELS : L);
+}
+/* texture d = (width, height, first texel, flags) at level lambda (any bits); row: its row of the level table */
+static rgba tex_sample_lod(const float* texels, const uint32_t* d, const uint32_t* row, float u, float v, float lambda) {
+  uint32_t L = tex_level_count(row);
+  lambda = tex_clamp_lod(lambda, L);
+  int nearest = (d[3] & ORACLE_TEX_NEAREST) != 0;
+  uint32_t l0 = (uint32_t)__builtin_floorf(nearest ? lambda + 0.5f : lambda); /* lambda is in [0, L - 1] here */
+  if (l0 > L - 1u) l0 = L - 1u;
+  uint32_t w0 = d[0] >> l0, h0 = d[1] >> l0;
+  rgba a = tex_sample(texels, w0 ? w0 : 1u, h0 ? h0 : 1u, row[l0], d[3], u, v);
+  if (nearest) return a;
+  float f = lambda - (float)l0;
+  if (f == 0.0f) return a; /* the other level is not read */
+  uint32_t l1 = l0 + 1u > L - 1u ? L - 1u : l0 + 1u;
+  uint32_t w1 = d[0] >> l1, h1 = d[1] >> l1;
+  return tex_lerp4(a, tex_sample(texels, w1 ? w1 : 1u, h1 ? h1 : 1u, row[l1], d[3], u, v), f);
+}
+
+/* the specular bounce of unit ray d at the FACEFORWARDED unit normal n; (sn, cs) = sincos2pi(u1), u = 2 u2 - 1, rho = sqrt(1 - u^2)
+ * as the diffuse bounce draws them (raytrace.comp.glsl:256-258).  Returns d'; *absorbed: d' does not leave the surface */
+static vec3 spec_lobe(vec3 n, vec3 d, float rho, float cs, float sn, float u, float g, int* absorbed) {
+  float c2 = -2.0f * v3_dot(n, d);
+  vec3 r = v3(dm_fma(c2, n.x, d.x), dm_fma(c2, n.y, d.y), dm_fma(c2, n.z, d.z));
+  vec3 s = v3(rho * cs, rho * sn, u);
+  vec3 dn = v3_normalize(v3(dm_fma(g, s.x, r.x), dm_fma(g, s.y, r.y), dm_fma(g, s.z, r.z)));
+  *absorbed = !(v3_dot(n, dn) > 0.0f);
+  return dn;
+}
+static vec3 spec_bounce(vec3 n, vec3 d, float u1, float u2, float g, int* absorbed) {
+  if (!(v3_dot(n, d) < 0.0f)) n = v3_neg(n);
+  float sn, cs;
+  dm_sincos2pi(u1, &sn, &cs);
+  float u = dm_fma(2.0f, u2, -1.0f);
+  float rho = dm_sqrt(dm_fma(-u, u, 1.0f));
+  return spec_lobe(n, d, rho, cs, sn, u, g, absorbed);
+}
+
+void oracle_texture_sample_array(const uint32_t* texture, const float* texels, const float* uv, uint64_t n, float* out) {
+  for (uint64_t i = 0; i < n; i++) {
+    rgba c = tex_sample(texels, texture[0], texture[1], texture[2], texture[3], uv[2 * i], uv[2 * i + 1]);
+    out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = c.a;
+  }
+}
+void oracle_texture_sample_lod_array(const uint32_t* texture, const uint32_t* level_row, const float* texels, const float* uv,
+                                     const float* lod, uint64_t n, float* out) {
+  for (uint64_t i = 0; i < n; i++) {
+    rgba c = tex_sample_lod(texels, texture, level_row, uv[2 * i], uv[2 * i + 1], lod[i]);
+    out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = c.a;
+  }
+}
+void oracle_texture_footprint_array(const float* in, uint64_t n, uint32_t W, uint32_t H, float* out) {
+  for (uint64_t i = 0; i < n; i++) {
+    const float* q = in + 17 * i;
+    out[i] = tex_footprint_lod(q[0], q[1], q + 2, q + 11, W, H);
+  }
+}
+void oracle_bounce_array(const float* cases, uint64_t n, float* out) {
+  for (uint64_t i = 0; i < n; i++) {
+    const float* q = cases + 9 * i;
+    int absorbed;
+    vec3 dn = spec_bounce(v3(q[3], q[4], q[5]), v3(q[0], q[1], q[2]), q[6], q[7], q[8], &absorbed);
+    out[4 * i] = dn.x; out[4 * i + 1] = dn.y; out[4 * i + 2] = dn.z; out[4 * i + 3] = absorbed ? 1.0f : 0.0f;
+  }
+}
+
 void oracle_raytrace(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                      uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount,
                      uint32_t* hit_id) {
@@ -579,7 +720,7 @@ void oracle_raytrace(const oracle_config* cfg, const oracle_push_constants* pc, 
  * normal-keyed colours (raytrace.comp.glsl:155-163) */
 static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                          uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image,
-                         uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
+                         uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump, const oracle_shade_ext* ext) {
   const int W = (int)cfg->width, H = (int)cfg->height;
   vec3 light_c = v3(pc->lightPos[0], pc->lightPos[1], pc->lightPos[2]); /* :279 */
   vec3 light_col = v3(pc->currentCameraColor[0] * cfg->light_intensity, pc->currentCameraColor[1] * cfg->light_intensity,
@@ -618,11 +759,22 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
           uint32_t id = oracle_closest_hit(tris, n, oo, dd, cfg->ray_tmax, &t, &b1, &b2); /* :208-222 */
           rays_total++;
           if (seg == 0 && smp == 0) first_id = id;
+          uint64_t rec = 0; /* this query's slot of the per-record planes */
+          int rec_on = 0;
           if (dump) {
-            if (n_rec < dump->max_rec) dump->seq_id[((uint64_t)y * W + x) * dump->max_rec + n_rec] = (uint16_t)id;
+            rec_on = n_rec < dump->max_rec;
+            rec = ((uint64_t)y * W + x) * dump->max_rec + n_rec;
+            if (rec_on) dump->seq_id[rec] = (uint16_t)id;
             n_rec++;
             end_code = ORACLE_END_BOUND;
           }
+          rec_on = rec_on && ext;
+          if (rec_on && ext->rec_ray) {
+            float* q = ext->rec_ray + 6 * rec;
+            q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = d.x; q[4] = d.y; q[5] = d.z;
+          }
+          float* alb_px = (ext && ext->albedo && seg == 0) ? ext->albedo + 4 * ((uint64_t)y * W + x) : NULL;
+          if (alb_px) { alb_px[0] = alb_px[1] = alb_px[2] = 1.0f; alb_px[3] = 0.0f; } /* (1, 1, 1) unless the path goes on */
           if (ray_hits_light(o, d, light_c, cfg->light_radius)) { /* :226 — not compared with t */
             end_code = ORACLE_END_LIGHT;
             if (seg == 0) {
@@ -640,6 +792,7 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
             vec3 v0 = v3(tri[0], tri[1], tri[2]);
             vec3 nrm = v3_normalize(v3_cross(v3_sub(v3(tri[3], tri[4], tri[5]), v0), v3_sub(v3(tri[6], tri[7], tri[8]), v0))); /* :150 */
             vec3 alb;
+            float spec_w = 0.0f; /* the record's spare word: 0 (all bits) = diffuse, -g = specular */
             if (nrm.x > 0.99f) alb = v3(1.f, 0.f, 0.f);        /* :155 dot(n,(1,0,0)) == n.x exactly */
             else if (-nrm.x > 0.99f) alb = v3(0.f, 1.f, 0.f);  /* :158 */
             else alb = v3(0.7f, 0.7f, 0.7f);                   /* :162 */
@@ -650,16 +803,63 @@ static void raytrace_mat_rows(const oracle_config* cfg, const oracle_push_consta
                 end_code = ORACLE_END_EMISSIVE; /* dumped by oracle_raytrace_seq_mat only: oracle_raytrace_seq has no materials */
                 break;
               }
-              alb = v3(m[0], m[1], m[2]);
+              alb = v3(m[0], m[1], m[2]); /* Kd, or Ks of a specular material */
+              if (ext && ext->specular) spec_w = m[3];
             }
-            acc = v3_mul(acc, alb);                            /* :244 */
+            uint8_t code = 0;
+            if (ext && ext->tri_uv) { /* albedo = colour x texel.rgb, at every segment */
+              uint32_t r = n_base ? (id - 1) % n_base : id - 1; /* instances share the base mesh's records */
+              uint32_t ti = ext->tri_texture[r];
+              if (ti) {
+                const float* uv6 = ext->tri_uv + 6 * (uint64_t)r;
+                const uint32_t* td = ext->textures + 4 * (uint64_t)(ti - 1);
+                float tu = dm_fma(b2, uv6[4], dm_fma(b1, uv6[2], b0 * uv6[0]));
+                float tv = dm_fma(b2, uv6[5], dm_fma(b1, uv6[3], b0 * uv6[1]));
+                rgba tx;
+                float lambda = 0.0f;
+                if (ext->levels) {
+                  const uint32_t* row = ext->levels + ORACLE_TEX_LEVEL_ROW * (uint64_t)(ti - 1);
+                  if (td[3] & ORACLE_TEX_MIPMAP) {
+                    /* the footprint: the pixel's at segment 0 (of the FULL frame's height), t * spread afterwards */
+                    float w = t * (seg == 0 ? (2.0f * slope) / fh : ext->bounce_spread);
+                    lambda = tex_footprint_lod(w, v3_dot(nrm, d), tri, uv6, td[0], td[1]);
+                  }
+                  tx = tex_sample_lod(ext->texels, td, row, tu, tv, lambda);
+                  lambda = tex_clamp_lod(lambda, tex_level_count(row));
+                } else {
+                  tx = tex_sample(ext->texels, td[0], td[1], td[2], td[3], tu, tv);
+                }
+                alb = v3(alb.x * tx.r, alb.y * tx.g, alb.z * tx.b);
+                code |= ORACLE_REC_TEXTURED;
+                if (rec_on && ext->rec_lod) ext->rec_lod[rec] = lambda;
+              }
+            }
+            if (dm_bits(spec_w) != 0u) code |= ORACLE_REC_SPECULAR;
+            if (rec_on && ext->rec_albedo) {
+              float* q = ext->rec_albedo + 3 * rec;
+              q[0] = alb.x; q[1] = alb.y; q[2] = alb.z;
+            }
+            if (alb_px) { alb_px[0] = alb.x; alb_px[1] = alb.y; alb_px[2] = alb.z; } /* demodulated: not into the throughput */
+            else acc = v3_mul(acc, alb);                       /* :244 */
             if (!(v3_dot(nrm, d) < 0.0f)) nrm = v3_neg(nrm);   /* :247 faceforward(N,I,Nref) */
             o = v3(dm_fma(cfg->ray_offset, nrm.x, pos.x), dm_fma(cfg->ray_offset, nrm.y, pos.y), dm_fma(cfg->ray_offset, nrm.z, pos.z)); /* :250 */
             float s, c;
             dm_sincos2pi(rng_float(&rng), &s, &c);        /* :256 */
             float u = dm_fma(2.0f, rng_float(&rng), -1.0f); /* :257 */
             float r = dm_sqrt(dm_fma(-u, u, 1.0f));       /* :258 */
-            d = v3_normalize(v3(dm_fma(r, c, nrm.x), dm_fma(r, s, nrm.y), nrm.z + u)); /* :259-261 */
+            if (code & ORACLE_REC_SPECULAR) { /* the same two draws, around the mirror direction */
+              int absorbed;
+              d = spec_lobe(nrm, d, r, c, s, u, fabsf(spec_w), &absorbed);
+              if (absorbed && seg + 1 < cfg->max_segments) { /* the last segment returned its throughput before any bounce */
+                acc = v3(0.f, 0.f, 0.f);
+                end_code = ORACLE_END_ABSORBED;
+                if (rec_on && ext->rec_code) ext->rec_code[rec] = code | ORACLE_REC_ABSORBED;
+                break;
+              }
+            } else {
+              d = v3_normalize(v3(dm_fma(r, c, nrm.x), dm_fma(r, s, nrm.y), nrm.z + u)); /* :259-261 */
+            }
+            if (rec_on && ext->rec_code) ext->rec_code[rec] = code | ORACLE_REC_HIT;
           } else {
             acc = v3_mul(acc, sky_color(d)); /* :266 */
             end_code = ORACLE_END_SKY;
@@ -694,25 +894,31 @@ typedef struct {
   uint64_t* raycount;
   uint32_t* hit_id;
   const oracle_seq_dump* dump;
+  const oracle_shade_ext* ext;
 } raytrace_mat_args;
 
 static void raytrace_mat_range(void* ctx, int64_t a, int64_t b) {
   const raytrace_mat_args* A = (const raytrace_mat_args*)ctx;
-  raytrace_mat_rows(A->cfg, A->pc, A->tris, A->n, A->tri_mat, A->n_base, (uint32_t)a, (uint32_t)b, A->image, A->raycount, A->hit_id, A->dump);
+  raytrace_mat_rows(A->cfg, A->pc, A->tris, A->n, A->tri_mat, A->n_base, (uint32_t)a, (uint32_t)b, A->image, A->raycount, A->hit_id, A->dump, A->ext);
 }
 
 void oracle_raytrace_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id) {
-  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, NULL};
+  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, NULL, NULL};
   run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
 }
 
 void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
-  raytrace_mat_args A = {cfg, pc, tris, n, NULL, 0, image, raycount, hit_id, dump};
+  raytrace_mat_args A = {cfg, pc, tris, n, NULL, 0, image, raycount, hit_id, dump, NULL};
   run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
 }
 
 void oracle_raytrace_seq_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump) {
-  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, dump};
+  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, dump, NULL};
+  run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
+}
+
+void oracle_raytrace_ext(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump, const oracle_shade_ext* ext) {
+  raytrace_mat_args A = {cfg, pc, tris, n, tri_mat, n_base, image, raycount, hit_id, dump, ext};
   run_ranges((int64_t)y0, (int64_t)y1, 4, raytrace_mat_range, &A);
 }
 

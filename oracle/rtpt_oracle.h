@@ -156,6 +156,62 @@ void oracle_raytrace_seq(const oracle_config* cfg, const oracle_push_constants* 
 void oracle_raytrace_seq_mat(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris,
                              uint32_t n, const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image,
                              uint64_t* raycount, uint32_t* hit_id, const oracle_seq_dump* dump);
+/* K2 with the library's shading extensions (none of them reference behaviour; the reference has no textures, no mip levels and
+ * traces no reflection): oracle_raytrace_seq_mat plus one struct of optional inputs and outputs.  Every pointer may be NULL; with
+ * ext NULL, or all of them NULL, the result is oracle_raytrace_seq_mat's bit for bit.
+ *   albedo textures   a hit on triangle id reads uv record and texture index (id - 1) % n_base (n_base 0: id - 1).  uv =
+ *                     fma(b2, uv2, fma(b1, uv1, b0 uv0)) per component; albedo = (Kd | Ks | the normal-keyed colour) x texel.rgb at
+ *                     every segment.  Repeat wrap s = u - floor(u); ORACLE_TEX_NEAREST: texel min(floor(s W), W - 1); else bilinear:
+ *                     x = s W - 0.5, taps floor(x) and floor(x) + 1 wrapped, lerp(a, b, f) = a + f (b - a) along x, then along y
+ *   mip levels        with a level table: a texture with ORACLE_TEX_MIPMAP is read at lambda = 0.5 plog2(((w w) D) / (nd nd)),
+ *                     w = t (2 slope / H) at segment 0 (H: the FULL frame's height) and t x bounce_spread afterwards, D = texel area /
+ *                     world area of the triangle, nd = n . d, plog2 the piecewise-linear log2; lambda = 0 unless D and the quotient
+ *                     are positive and finite; clamped to [0, L - 1]; bilinear: lerp of levels floor(lambda) and the next by the
+ *                     fraction, one level alone where the fraction is 0; nearest: the level floor(lambda + 0.5)
+ *   specular bounce   specular != 0: word 3 of the 8-float material record is the device's: 0 (all bits) diffuse, else specular with
+ *                     roughness g = |word| (the mirror is -0.0f).  r = fma(-2 (n . d), n, d) at the faceforwarded normal; the same
+ *                     two draws as the diffuse bounce give s = (rho cos, rho sin, u); d' = normalize(fma(g, s, r)); !(n . d' > 0)
+ *                     ends the path with colour 0 (ORACLE_END_ABSORBED) unless the segment is the path's last
+ *   albedo plane      albedo != NULL: segment 0's albedo goes there (4 floats per pixel, alpha 0) instead of into the throughput;
+ *                     (1, 1, 1) where segment 0 ends at the light, the sky or an emitter
+ * Order per segment: light, sky, emitter, albedo, bounce; the RNG takes its two steps on every hit, a mirror's too. */
+#define ORACLE_TEX_NEAREST 0x1u
+#define ORACLE_TEX_MIPMAP 0x10u
+#define ORACLE_TEX_MAX_LEVELS 17u
+#define ORACLE_TEX_LEVEL_ROW 18u /* per texture: [l] the first texel of level l, [17] the number of levels */
+#define ORACLE_END_ABSORBED 5
+/* per closest-hit record (rec_code): 0 = the query ended the path (miss, light, emitter), else ORACLE_REC_HIT with what the hit did */
+#define ORACLE_REC_HIT 0x1
+#define ORACLE_REC_TEXTURED 0x2
+#define ORACLE_REC_SPECULAR 0x4
+#define ORACLE_REC_ABSORBED 0x8
+typedef struct oracle_shade_ext {
+  const float* tri_uv;         /* n_base x 6: (u0, v0, u1, v1, u2, v2); NULL: no textures */
+  const uint32_t* tri_texture; /* n_base: texture index + 1, 0 = untextured */
+  const uint32_t* textures;    /* per texture (width, height, first texel, ORACLE_TEX_* flags) */
+  const float* texels;         /* the RGBA32F atlas */
+  const uint32_t* levels;      /* per texture ORACLE_TEX_LEVEL_ROW words; NULL: no mips (every texture is read at level 0) */
+  float bounce_spread;         /* footprint width per unit length of a bounce segment */
+  uint32_t specular;           /* read word 3 of the material records */
+  float* albedo;               /* out, nullable: the ALBEDO plane */
+  /* out, nullable, with a dump: per record (index pixel * max_rec + k, as seq_id; the caller zeroes them) */
+  float* rec_lod;              /* the level a textured hit sampled, clamped to its chain, before it is split into two levels */
+  uint8_t* rec_code;           /* ORACLE_REC_* */
+  float* rec_albedo;           /* 3 floats: the hit's albedo */
+  float* rec_ray;              /* 6 floats: the query's origin and direction */
+} oracle_shade_ext;
+void oracle_raytrace_ext(const oracle_config* cfg, const oracle_push_constants* pc, const float* tris, uint32_t n,
+                         const float* tri_mat, uint32_t n_base, uint32_t y0, uint32_t y1, float* image, uint64_t* raycount,
+                         uint32_t* hit_id, const oracle_seq_dump* dump, const oracle_shade_ext* ext);
+/* the new functions one by one, item by item (bit-exact comparison with their other statements):
+ * the sampler of one texture (4 words as above) at uv [n, 2]; at uv and an explicit level (any bits; level_row as above);
+ * the level before the clamp of items of 17 floats (w, nd, the triangle's 9, the uv record's 6) on a W x H texture;
+ * the bounce of items (d, n, u1, u2, g) -> (d', 1.0f if absorbed else 0.0f), faceforward included */
+void oracle_texture_sample_array(const uint32_t* texture, const float* texels, const float* uv, uint64_t n, float* out);
+void oracle_texture_sample_lod_array(const uint32_t* texture, const uint32_t* level_row, const float* texels, const float* uv,
+                                     const float* lod, uint64_t n, float* out);
+void oracle_texture_footprint_array(const float* in, uint64_t n, uint32_t W, uint32_t H, float* out);
+void oracle_bounce_array(const float* cases, uint64_t n, float* out);
 /* K3: temporalFiltering.comp.glsl:191-265, one iteration.  `in` is the colorImage snapshot (D1),
  * `out` receives the filtered colour (k < max) or the blend (k == max).  prev_pixel (nullable,
  * 2 ints per pixel) receives previousPixelPos when k == max. */

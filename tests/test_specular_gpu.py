@@ -3,8 +3,9 @@ catch: the bounce function against its numpy restatement, diffuse scenes that mu
 mirrors, the reflected direction end to end, schedule independence where paths are absorbed at different segments, absorption
 itself, demodulation / textures / lifetime / refusals, and the two hosts.
 
-No oracle frame is involved (the oracle knows no specular bounce): every expectation is a closed form, a float64 restatement,
-the numpy float32 restatement of tests/specular_scenes.py, or another schedule of the same frame."""
+No oracle frame is involved here: every expectation is a closed form, a float64 restatement, the numpy float32 restatement of
+tests/specular_scenes.py, or another schedule of the same frame.  The oracle's statement of the specular bounce
+(oracle_raytrace_ext) is compared frame by frame in tests/test_shading_ext_gpu.py."""
 import gc
 import json
 import os

@@ -10,9 +10,10 @@ quotient from exact::quotient_positive, the primary ray's two divisions share a 
   * the light sphere around the camera, through the camera (c == 0 in the quadratic: the numerator of t2 is exactly 0 or 2 |b|),
     across the frame (its silhouette: discriminants near 0) and behind the camera.
 
-The oracle knows no textures.  A textured frame is compared with it through an atlas of constants (texture p = the colour Kd_p
-over white materials is the material table, test_textures_gpu.py), and the barycentrics of the last hit — which only a texture
-reads there — through distinct texels: the image of a 1-segment frame is the first hit's albedo, which a 2-segment demodulated
+The oracle's plain path loop (oracle_raytrace_seq_mat, the reference of this file) samples no texture; its statement of the
+textured path, oracle_raytrace_ext, is compared frame by frame in tests/test_shading_ext_gpu.py.  Here a textured frame is compared
+with the plain loop through an atlas of constants (texture p = the colour Kd_p over white materials is the material table,
+test_textures_gpu.py), and the barycentrics of the last hit — which only a texture reads there — through distinct texels: the image of a 1-segment frame is the first hit's albedo, which a 2-segment demodulated
 frame stores in ALBEDO from a hit that is NOT its last."""
 import numpy as np
 import pytest
