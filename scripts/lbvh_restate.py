@@ -1,7 +1,10 @@
 """numpy restatement of the device LBVH builder (csrc/bvh_build.hip): primitive centres, 63-bit Morton keys, the stable
 sort, the radix tree over the augmented keys (ties split by sorted position) and its pre-order numbering.  Needs no GPU.
-Used to predict depths (which scenes fall back to the host builder) and to explain a traversal result: `path_to` gives
-the nodes above a triangle, `first_missed` the first of them whose padded box a ray does not pass through.
+Top-down splits where the device runs Karras' per-node searches: an independent statement, and the reference the device's
+tree is held to array for array (tests/test_device_tree_gpu.py; tests/test_device_tree_cpu.py holds this file to the
+definition of the radix tree).  Also used to predict depths (which scenes fall back to the host builder) and to explain
+a traversal result: `path_to` gives the nodes above a triangle, `first_missed` the first of them whose padded box a ray
+does not pass through.
 
     python scripts/lbvh_restate.py scene.bin        # n x 9 float32 world-space triangles: prints nodes, depth
 """
@@ -10,6 +13,7 @@ import sys
 import numpy as np
 
 F32 = np.float32
+LEAF, EMPTY = 0x80000000, 0xFFFFFFFF
 
 
 def pair_ok(tris):
@@ -42,13 +46,16 @@ def morton_keys(tris, w):
 
 
 class Tree:
-    """nodes in pre-order: left / right = ("leaf", sorted position) or ("node", index); first / last = range of sorted positions"""
+    """nodes in pre-order: left / right = ("leaf", sorted position) or ("node", index); first / last = range of sorted positions.
+    `child_refs()` and `leaf_order()` are the arrays rtpt_debug_bvh_topology reads back from a device-built tree, `depth` is
+    the depth of rtpt_scene_build_info: the level of the deepest leaf, the root pair's children at 1 (0 for one primitive)"""
 
-    def __init__(self, tris, pairs=None):
+    def __init__(self, tris, pairs=None, keys=None):
+        """`keys`: one 64-bit key per primitive instead of morton_keys' — the tree a builder with other keys would make"""
         tris = np.ascontiguousarray(tris, F32).reshape(-1, 9)
         self.tris = tris
         self.w = 2 if (pair_ok(tris) if pairs is None else pairs) else 1
-        keys = morton_keys(tris, self.w)
+        keys = morton_keys(tris, self.w) if keys is None else np.asarray(keys, np.uint64)
         self.order = np.argsort(keys, kind="stable")  # sorted position -> primitive
         k = [int(x) for x in keys[self.order]]
         n = len(k)
@@ -87,6 +94,19 @@ class Tree:
 
     def n_nodes(self):
         return len(self.left)
+
+    def child_refs(self):
+        """[n_nodes, 2] uint32: an internal child is its pre-order index, a leaf bit 31 | (sorted position * w) << 2 | (w - 1);
+        the absent right child of a one-primitive scene is 0xFFFFFFFF"""
+        def ref(ch):
+            if ch is None:
+                return EMPTY
+            return ch[1] if ch[0] == "node" else LEAF | ((ch[1] * self.w) << 2) | (self.w - 1)
+        return np.array([[ref(l), ref(r)] for l, r in zip(self.left, self.right)], np.uint32).reshape(-1, 2)
+
+    def leaf_order(self):
+        """[n_triangles] uint32: slot sorted position * w + k holds triangle order[sorted position] * w + k"""
+        return (self.order[:, None] * self.w + np.arange(self.w)[None, :]).reshape(-1).astype(np.uint32)
 
     def box(self, a, b):
         """unpadded binary32 box of sorted positions a..b"""

@@ -43,7 +43,8 @@ def bin_of(c, mn, scale):
 
 class Tree:
     """nodes in pre-order (the order in which the host allocates them): child_refs[i] = (left, right) reference of node i,
-    leaf_order = triangle ids in leaf-slot order, depth = level of the deepest leaf (the root pair's children at 1)"""
+    leaf_order = triangle ids in leaf-slot order, depth = level of the deepest leaf (the root pair's children at 1),
+    median_at = (depth, primitives) of every range that was split at the object median"""
 
     def __init__(self, tris, pairs=None):
         tris = np.ascontiguousarray(tris, F32).reshape(-1, 9)
@@ -56,6 +57,7 @@ class Tree:
         self.refs, self.first, self.last = [], [], []
         self.depth = 0
         self.median_splits = 0
+        self.median_at = []  # (depth, primitives) of every range split at the object median, in pre-order
         if n <= MAX_LEAF:
             self.refs.append([LEAF | (n - 1), EMPTY])
             self.first.append(0), self.last.append(n // w - 1)
@@ -130,6 +132,7 @@ class Tree:
             self.perm[lo:hi] = p[np.lexsort((p, key))]
             mid = lo + (hi - lo) // 2
             self.median_splits += 1
+            self.median_at.append((depth, hi - lo))
         me = len(self.refs)
         self.refs.append([None, None])
         self.first.append(lo), self.last.append(hi - 1)
