@@ -66,10 +66,11 @@ def _ubo(cls, W, H, fin):
     return u
 
 
-def planes(oracle, T, W, H, kind, cls, finite=False):
+def planes(oracle, T, W, H, kind, cls, finite=False, roll=0):
     """everything a run injects, once per key.  kind 'gbuffer': the ids (world positions, depth) are the G-buffer's own
-    (oracle.gbuffer), for the route that must not inject VIS_ID.  finite: ids without the all-identical-vertex triangle."""
-    key = (T, W, H, kind, cls, finite)
+    (oracle.gbuffer), for the route that must not inject VIS_ID.  finite: ids without the all-identical-vertex triangle.
+    roll: the id plane moved down by that many rows (a pair plane then starts at a strip's first stored row)."""
+    key = (T, W, H, kind, cls, finite) + ((roll,) if roll else ())
     if key in _planes_cache:
         return _planes_cache[key]
     tris = _scene(T)
@@ -80,7 +81,7 @@ def planes(oracle, T, W, H, kind, cls, finite=False):
         cfg = oracle.config_default(W, H)
         ids, wp, gdepth = oracle.gbuffer(cfg, tris, _ubo(oracle.Ubo, W, H, fin0))
     else:
-        ids = np.array(FP.id_plane(kind, nt, W, H))
+        ids = np.roll(np.array(FP.id_plane(kind, nt, W, H)), roll, axis=0)
     if finite:
         ids = FP.without_point(ids)
     FP.check_ids(ids, nt)
@@ -98,12 +99,15 @@ def planes(oracle, T, W, H, kind, cls, finite=False):
     _, pp = oracle.atrous(cfg, pc, _ubo(oracle.Ubo, W, H, fin), p["img"], p["depth"], ids, p["lut"], p["lut_prev"], p["worldpos"],
                           p["history"], want_prev_pixel=True)
     p["prev_vis"] = FP.prev_ids(ids, nt, pp)
+    p["landing"] = pp                      # [H, W, 2] the reprojected pixels (tests/strip_planes.py counts where they land)
     _planes_cache[key] = p
     return p
 
 
 # ------------------------------------------------------------------------------------------ the two sides
 def oracle_run(oracle, p, ext, N, frame):
+    """the whole-frame reference.  out["iters"][k - 1]: (image, variance) after iteration k (what a strip's neighbour sends
+    before iteration k + 1); p["prev_vis_moments"]: previous ids for the moment accumulation alone, where they differ"""
     key = (p["key"], ext, N, frame)
     if key in _oracle_cache:
         return _oracle_cache[key]
@@ -113,11 +117,12 @@ def oracle_run(oracle, p, ext, N, frame):
     pc = oracle.PushConstants()
     pc.frameNumber, pc.maxWaveletIteration = frame, N
     ubo = _ubo(oracle.Ubo, W, H, p)
-    out = dict(moments=None, variance=None, prev_pixel=None)
+    out = dict(moments=None, variance=None, prev_pixel=None, iters=[])
     var = None
     if ext & 0x100:
         pc.waveletIteration = 1
-        out["moments"], var = oracle.moments(cfg, pc, ubo, p["img"], p["ids"], p["worldpos"], p["lut_prev"], p["prev_vis"], p["moments_prev"])
+        out["moments"], var = oracle.moments(cfg, pc, ubo, p["img"], p["ids"], p["worldpos"], p["lut_prev"],
+                                             p.get("prev_vis_moments", p["prev_vis"]), p["moments_prev"])
     cur = p["img"]
     for k in range(1, N + 1):
         pc.waveletIteration = k
@@ -126,6 +131,7 @@ def oracle_run(oracle, p, ext, N, frame):
         if var is not None:
             var, res = res[-1], res[:-1]
         cur = res[0] if isinstance(res, tuple) else res
+        out["iters"].append((cur, var))
         if k == N:
             out["prev_pixel"] = res[1]
     out["image"], out["variance"] = cur, var
@@ -431,10 +437,10 @@ def test_fast_direct_kernel_non_finite_positions(hip_lib, oracle, ext):
 
 
 # ------------------------------------------------------------------------------------------ present
-def _present_planes(oracle, T, W, H):
+def _present_planes(oracle, T, W, H, finite=False):
     """colours that end up < 0, > 1, NaN, +-Inf and within an ulp of the rounding boundaries (n + 0.5) / 255 of unorm8: depths
     1000 apart give every tap but the pixel's own the weight exp(-1000) = 0, so a pixel keeps its colour up to rounding"""
-    p = dict(planes(oracle, T, W, H, "random", "bounded"))
+    p = dict(planes(oracle, T, W, H, "random", "bounded", finite=finite))
     p["key"] = p["key"] + ("present",)
     ids = p["ids"]
     rng = np.random.default_rng(5)
