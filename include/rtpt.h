@@ -498,6 +498,27 @@ int rtpt_debug_reuse_info(rtpt_ctx* ctx, uint64_t out[4]);
  * the plane (0 until the first store). */
 int rtpt_debug_reproj_info(rtpt_ctx* ctx, uint64_t out[4]);
 
+/* The deferred final pass.  On a frame at rest the tracing launch is bound by instruction issue and touches next to no
+ * memory, the final filter pass by memory bandwidth, and as launches of their own they never run together.  The final pass
+ * of frame n and rtpt_raytrace of frame n + 1 read and write disjoint planes, so a final pass that qualifies is prepared
+ * where it is recorded and launched inside the next rtpt_raytrace's launch, as workgroups in front of and behind the
+ * tracing tiles.  It qualifies when it is the frame's last recorded iteration, a single launch of the LDS-staged id-pair
+ * kernel that loads its reprojected pixels (see above), with k <= 5, no extension flag, no RTPT_DEBUG_PREV_PIXEL, no
+ * rtpt_present_target and no bound or external plane in the context.  rtpt_raytrace takes it when it runs the brute-force
+ * tile kernel alone (K0 and K1 reused or not recorded) with one sample per pixel over all stored rows, without
+ * demodulation, textures or specular materials; it then traces into a fourth colour buffer, allocated at the first such
+ * call (16 bytes per stored pixel), because the pass still reads the buffer IMAGE named.  Every other entry point that
+ * launches, exposes or changes a plane, a stream, the scene or the context launches the pass first, by itself, and what it
+ * returns or leaves is what it would have been; rtpt_gbuffer, rtpt_temporal_gradient and rtpt_end_frame in their usual
+ * order do not.  A pointer obtained from rtpt_plane_ptr, or one bound or registered as an external plane, is therefore
+ * complete only after a call that flushes: ask rtpt_plane_ptr again (or call rtpt_sync) after rtpt_end_frame before
+ * reading it on the device.  Every plane, the ray count and the finished frame equal those of a context that launches
+ * the pass where it is recorded.  RTPT_NO_FINAL_DEFER=1 in the environment of rtpt_create turns it off;
+ * RTPT_FINAL_FRONT=<workgroups per CU>[,<percent of the pass's work>] sets how much of the pass runs in front of the tiles.
+ * out: [0] passes recorded instead of launched, [1] of those launched inside a tracing launch, [2] launched alone,
+ * [3] bytes of the fourth colour buffer (0 until the first such launch). */
+int rtpt_debug_defer_info(rtpt_ctx* ctx, uint64_t out[4]);
+
 /* ---- per-frame passes, one call per reference dispatch ----------------------------------- */
 
 /* drawVisbilityBuffer (main.cpp:1187-1199; visibility.{vert,geom,frag}.glsl): id, world

@@ -136,7 +136,7 @@ SYMBOLS = [
     "rtpt_scene_set_materials", "rtpt_util_load_obj_materials", "rtpt_util_bvh_refit_check", "rtpt_set_external_guides",
     "rtpt_present", "rtpt_debug_bvh_check", "rtpt_present_target", "rtpt_scene_build_info", "rtpt_scene_rebuild",
     "rtpt_debug_reuse_info", "rtpt_debug_bvh_topology", "rtpt_scene_set_instances", "rtpt_debug_upload_info",
-    "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info",
+    "rtpt_debug_live_device_bytes", "rtpt_modulate", "rtpt_debug_reproj_info", "rtpt_debug_defer_info",
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
@@ -209,6 +209,7 @@ def load() -> C.CDLL:
         "rtpt_debug_bvh_topology": [vp, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_reproj_info": [vp, C.POINTER(C.c_uint64 * 4)],
+        "rtpt_debug_defer_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_scene_set_instances": [vp, vp, u32],
         "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_live_device_bytes": [C.POINTER(C.c_uint64)],
@@ -457,6 +458,12 @@ class Context:
         out = (C.c_uint64 * 4)()
         _check(self._lib.rtpt_debug_reproj_info(self._h, C.byref(out)))
         return dict(zip(("stores", "loads", "invalidations", "plane_bytes"), (int(v) for v in out)))
+
+    def defer_info(self) -> dict:
+        """the deferred final pass as observed so far (rtpt_debug_defer_info)"""
+        out = (C.c_uint64 * 4)()
+        _check(self._lib.rtpt_debug_defer_info(self._h, C.byref(out)))
+        return dict(zip(("recorded", "launched_in_trace", "launched_alone", "spare_bytes"), (int(v) for v in out)))
 
     def set_materials(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
         """per-triangle material indices + (Kd, Ke) rows; None returns to the reference's normal-keyed colours"""

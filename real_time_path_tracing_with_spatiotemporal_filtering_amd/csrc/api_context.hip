@@ -91,7 +91,7 @@ Buf* plane_buf(rtpt_ctx* c, rtpt_plane which) {
 }
 
 int color_index(const rtpt_ctx* c, const Buf* b) {
-  for (int i = 0; i < 3; i++)
+  for (int i = 0; i < 4; i++)
     if (b == &c->color[i]) return i;
   return -1;
 }
@@ -269,6 +269,7 @@ static int alloc_planes(rtpt_ctx* c) {
   const size_t px = c->pixels();
   int rc = RTPT_OK;
   for (int i = 0; i < 3 && rc == RTPT_OK; i++) rc = alloc_buf(c->color[i], px * 16);
+  free_buf(c->color[3]);  // sized per frame: re-created by the next trace that carries a deferred final pass
   for (int i = 0; i < 2 && rc == RTPT_OK; i++) rc = alloc_buf(c->vis[i], px * 4);
   if (rc == RTPT_OK) rc = alloc_buf(c->worldpos, px * 16);
   if (rc == RTPT_OK) rc = alloc_buf(c->gradient, px * 16);
@@ -390,6 +391,11 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
     if (const char* comma = std::strchr(v, ',')) c->filter_policy.chain_skew2 = std::atoi(comma + 1);
   }
   if (const char* v = std::getenv("RTPT_CHAIN_BW")) c->filter_policy.chain_bw = std::atoi(v);
+  if (const char* v = std::getenv("RTPT_NO_FINAL_DEFER")) c->final_defer = std::atoi(v) == 0;
+  if (const char* v = std::getenv("RTPT_FINAL_FRONT")) {
+    c->filter_policy.final_front = std::atoi(v);
+    if (const char* comma = std::strchr(v, ',')) c->filter_policy.final_front_share = std::atoi(comma + 1);
+  }
   if (const char* v = std::getenv("RTPT_CHAIN_SW")) c->filter_policy.chain_sw = std::atoi(v);
   if (const char* v = std::getenv("RTPT_CHAIN_SW_G1")) c->filter_policy.chain_sw_g1 = std::atoi(v);
   if (const char* v = std::getenv("RTPT_CHAIN_SW_G3")) c->filter_policy.chain_sw_g3 = std::atoi(v);
@@ -409,6 +415,7 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
 int rtpt_destroy(rtpt_ctx* c) {
   if (!c) return RTPT_OK;
   (void)hipSetDevice(c->device);
+  (void)final_flush(c);  // (the caller may own the buffer it writes and expect the frame there)
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (auto& t : c->timed) {
     (void)hipEventDestroy(t.start);
@@ -502,6 +509,7 @@ int rtpt_set_external_history(rtpt_ctx* c, const void* device_ptr, uint32_t row_
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   if (device_ptr && (row_begin >= row_end || row_end > c->cfg.height)) return fail(RTPT_E_INVALID, "bad history row range");
   if (device_ptr && (reinterpret_cast<uintptr_t>(device_ptr) & 15u)) return fail(RTPT_E_INVALID, "history buffer must be 16-byte aligned");
+  if (int rc = final_flush(c)) return rc;  // (recorded iterations stay recorded: the registration is for the pass still to come)
   c->frame.ext_history = device_ptr;
   c->frame.ext_hist = Rows(row_begin, row_end);
   return RTPT_OK;
@@ -509,6 +517,7 @@ int rtpt_set_external_history(rtpt_ctx* c, const void* device_ptr, uint32_t row_
 
 int rtpt_set_external_guides(rtpt_ctx* c, const void* prev_vis, const void* moments_prev, uint32_t row_begin, uint32_t row_end) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (int rc = final_flush(c)) return rc;
   if (!prev_vis && !moments_prev) {
     c->frame.ext_prev_vis = c->frame.ext_moments = nullptr;
     return RTPT_OK;
@@ -531,6 +540,10 @@ int rtpt_stream_wait(rtpt_ctx* c, rtpt_ctx* other) {
   if (rcw == RTPT_OK) rcw = gbuffer_flush(c);
   if (rcw == RTPT_OK) rcw = filter_flush(other, true);
   if (rcw == RTPT_OK) rcw = filter_flush(c, true);
+  // (a final pass those two deferred included: the wait orders everything submitted so far, and the pass of `c` must not end
+  // up behind a wait it was recorded in front of)
+  if (rcw == RTPT_OK) rcw = final_flush(other);
+  if (rcw == RTPT_OK) rcw = final_flush(c);
   if (rcw) return rcw;
   if (c == other || c->stream == other->stream) return RTPT_OK;  // one stream is already in order
   if (c->device != other->device) return fail(RTPT_E_INVALID, "rtpt_stream_wait: the contexts are on different devices");
@@ -545,6 +558,7 @@ int rtpt_stream_wait(rtpt_ctx* c, rtpt_ctx* other) {
 int rtpt_enable_debug(rtpt_ctx* c, uint32_t mask) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
   HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
   if ((mask & RTPT_DEBUG_HIT_ID) && !c->hit_id.ptr) {
     int rc = alloc_buf(c->hit_id, c->pixels() * 4);
     if (rc) return rc;
@@ -574,6 +588,15 @@ int rtpt_debug_reproj_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 3; i++) out[i] = c->reproj_info[i];
   out[3] = c->reproj.bytes;
+  return RTPT_OK;
+}
+
+// the deferred final pass, observed: [0] passes recorded instead of launched, [1] of those launched inside a tracing launch,
+// [2] launched alone, [3] bytes of the fourth colour buffer
+int rtpt_debug_defer_info(rtpt_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  for (int i = 0; i < 3; i++) out[i] = c->defer_info[i];
+  out[3] = c->color[3].bytes;
   return RTPT_OK;
 }
 

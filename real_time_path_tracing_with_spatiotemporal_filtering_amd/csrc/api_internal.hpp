@@ -62,6 +62,14 @@ struct FilterCall {  // one recorded rtpt_temporal_filter call
   uint32_t y0, y1;
 };
 
+// A final filter pass that was prepared and not launched (api_passes.hip: filter_launch): the next rtpt_raytrace takes it into
+// its launch when it can, every other entry point that launches, exposes or changes anything launches it first, alone
+// (final_flush).  Roles, tags and FrameState already say what they say after the launch.
+struct DeferredFinal {
+  rt::AtrousArgs args;  // finished: what launch_atrous or launch_pathtrace takes
+  int kernel;           // for the timer of a launch of its own
+};
+
 struct TimedLaunch {
   int kernel;
   hipEvent_t start, stop;
@@ -116,7 +124,8 @@ struct Rows {  // frame rows [y0, y1)
 // alloc_planes replaces it whole, so a member added here is reset by rtpt_resize without being listed anywhere.
 struct FrameState {
   int color_of_role[3] = {0, 1, 2};             // role -> physical index of rtpt_ctx::color
-  bool alpha_depth[3] = {false, false, false};  // physical buffer carries depth in alpha ("rgbd")
+  int color_spare = 3;    // the buffer no role names: the trace that carries a deferred final pass writes it (rtpt_ctx::deferred)
+  bool alpha_depth[4] = {false, false, false, false};  // physical buffer carries depth in alpha ("rgbd")
   int vis_cur = 0;        // vis[vis_cur] = VIS_ID, the other PREV_VIS_ID
   int moments_cur = 0;    // moments[moments_cur] is written this frame, the other one is the history
   int variance_last = 0;  // variance[] buffer holding the newest values
@@ -205,7 +214,8 @@ struct rtpt_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
 
-  Buf color[3];  // physical RGBA32F buffers (FrameState::color_of_role)
+  Buf color[4];  // physical RGBA32F buffers (FrameState::color_of_role, color_spare); [3] is allocated by the first trace that
+                 // carries a deferred final pass
   Buf vis[2];
   int lut_cur = 0;  // scene.lut[lut_cur] = LUT, the other LUT_PREV
   Buf worldpos, gradient, depth, prev_pixel, hit_id, raycount;
@@ -284,7 +294,13 @@ struct rtpt_ctx {
   uint32_t trace_window = 0;
   float tex_bounce_spread = rt::kTexBounceSpread;  // RTPT_TEX_BOUNCE_SPREAD, for measurements only (texture.hpp)
   Buf path_pool;
-  rt::FilterPolicy filter_policy;  // RTPT_CHAIN_* (read once, here: rtpt_create)
+  rt::FilterPolicy filter_policy;  // RTPT_CHAIN_*, RTPT_FINAL_FRONT (read once, here: rtpt_create)
+  // The last final pass, deferred (DeferredFinal): RTPT_NO_FINAL_DEFER=1 (read at rtpt_create) launches every pass where it is
+  // recorded, as before
+  bool final_defer = true;
+  bool deferred_valid = false;
+  DeferredFinal deferred;
+  uint64_t defer_info[4] = {0, 0, 0, 0};  // rtpt_debug_defer_info
   // K3 iterations recorded by rtpt_temporal_filter and not launched yet (see filter_flush)
   std::vector<FilterCall> pending;
   int chain_max = 2;        // iterations per chained launch (1 = never chain)
@@ -319,11 +335,13 @@ namespace rtpt_impl {
 // K3 iterations recorded by rtpt_temporal_filter are launched before anything else looks at or changes the planes
 int filter_flush(rtpt_ctx* c, bool fuse);
 int gbuffer_flush(rtpt_ctx* c);
+int final_flush(rtpt_ctx* c);  // a deferred final pass goes out, alone (no-op without one)
 // frame reuse: something other than K0 / K1 may write plane b (NULL: any plane) — its tag no longer describes it
 void reuse_invalidate(rtpt_ctx* c, const Buf* b);
 #define FLUSH_FILTER(c)                              \
   do {                                               \
-    int rcf_ = gbuffer_flush(c);                     \
+    int rcf_ = final_flush(c);                       \
+    if (rcf_ == RTPT_OK) rcf_ = gbuffer_flush(c);    \
     if (rcf_ == RTPT_OK) rcf_ = filter_flush((c), false); \
     if (rcf_) return rcf_;                           \
   } while (0)

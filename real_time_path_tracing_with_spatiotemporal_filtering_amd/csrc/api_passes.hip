@@ -185,7 +185,16 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
   int rc = check_rows(c, y0, y1);
   if (rc) return rc;
-  FLUSH_FILTER(c);
+  if ((rc = gbuffer_flush(c)) || (rc = filter_flush(c, false))) return rc;
+  // A deferred final pass stays deferred through a call that only records (the next rtpt_raytrace may take it): one that
+  // launches or allocates anything, or changes what the pass reads (the pose and its LUTs), sends it out first
+  if (c->deferred_valid &&
+      ((c->cfg.flags & RTPT_FLAG_NO_FILTER_FUSION) || std::memcmp(ubo->model, c->scene.model, sizeof c->scene.model) != 0 ||
+       c->scene.lut_version[c->lut_cur] != c->scene.model_version || !c->tables_valid || !c->scene.lut_prev_valid || !c->ray_tab.ptr ||
+       c->ray_tab_p00 != ubo->proj[0] || c->ray_tab_p11 != ubo->proj[5] || c->ray_tab_w != c->cfg.width || c->ray_tab_h != c->cfg.height ||
+       (!c->scene.pair_tab.ptr && !c->normals.ptr)) &&
+      (rc = final_flush(c)))
+    return rc;
   {
     // an affine model only (last row 0 0 0 1): the posed vertex is the xyz of model * (v, 1), visibility.vert.glsl:24
     const float* m = ubo->model;
@@ -286,6 +295,19 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
 }  // extern "C"
 
 namespace rtpt_impl {
+int final_flush(rtpt_ctx* c) {
+  if (!c->deferred_valid) return RTPT_OK;
+  c->deferred_valid = false;
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  {
+    Timer tm(c, c->deferred.kernel);
+    rt::launch_atrous(c->deferred.args, true, c->stream);
+  }
+  c->defer_info[2]++;
+  return launch_check("temporal_filter");
+}
+
 int gbuffer_flush(rtpt_ctx* c) {
   if (!c->pending_gb_valid) return RTPT_OK;
   c->pending_gb_valid = false;
@@ -295,6 +317,7 @@ int gbuffer_flush(rtpt_ctx* c) {
     c->reuse_info[0]++;
     return RTPT_OK;
   }
+  if (int rc = final_flush(c)) return rc;  // (it reads the planes this launch rewrites)
   tag_outputs(c, c->pending_gb, &c->pending_key);
   {
     Timer tm(c, c->pending_gb.grad_on ? RTPT_K_GBUFFER_GRADIENT : RTPT_K_GBUFFER);
@@ -382,9 +405,8 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   a.jitter = c->cfg.pixel_jitter;
   a.ray_offset = c->cfg.ray_offset;
   a.tmax = c->cfg.ray_tmax;
-  a.image = static_cast<float4*>(c->color[c->frame.color_of_role[ROLE_IMAGE]].ptr);
+  a.image = nullptr;  // (below: a launch that carries a deferred final pass traces into the spare buffer)
   a.depth = static_cast<const float*>(c->depth.ptr);
-  c->frame.alpha_depth[c->frame.color_of_role[ROLE_IMAGE]] = true;
   a.hit_id = (c->debug_mask & RTPT_DEBUG_HIT_ID) ? static_cast<uint32_t*>(c->hit_id.ptr) : nullptr;
   a.albedo = (c->cfg.flags & RTPT_FLAG_EXT_DEMODULATE) ? static_cast<float4*>(c->albedo.ptr) : nullptr;
   a.raycount = static_cast<unsigned long long*>(c->raycount.ptr);
@@ -416,6 +438,23 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   // that serves K0 + K1 + K2
   const bool reused = joined && reuse_covers(c);
   const bool fused = joined && !reused;
+  // The deferred final pass of the frame before joins this launch when only tracing tiles are in it, the tile kernel can carry
+  // it and the trace covers every stored row (so that the spare buffer it writes then holds what IMAGE would).  The pass reads
+  // the buffer IMAGE names now (the old history), so the trace goes to the buffer no role names and the two change places.
+  // Every other call sends the pass out first.
+  const bool take = c->deferred_valid && !fused && rt::pathtrace_takes_final(a, tex_view(c), c->scene.materials_specular) &&
+                    a.g.y0 == static_cast<int32_t>(c->cfg.row_begin) && a.g.y1 == static_cast<int32_t>(c->cfg.row_end);
+  if (!take && (rc = final_flush(c))) return rc;
+  if (take) {
+    FrameState& fr = c->frame;
+    if (!c->color[fr.color_spare].ptr) {
+      if ((rc = alloc_buf(c->color[fr.color_spare], c->pixels() * 16))) return rc;
+      HIP_TRY(hipMemsetAsync(c->color[fr.color_spare].ptr, 0, c->pixels() * 16, c->stream));
+    }
+    std::swap(fr.color_of_role[ROLE_IMAGE], fr.color_spare);
+  }
+  a.image = static_cast<float4*>(c->color[c->frame.color_of_role[ROLE_IMAGE]].ptr);
+  c->frame.alpha_depth[c->frame.color_of_role[ROLE_IMAGE]] = true;
   if ((rc = ensure_stack_spill(c, std::max<size_t>(frame_blocks(c), rt::pathtrace_grid_blocks(a, fused ? &c->pending_gb : nullptr))))) return rc;
   a.scene = scene_view(c);
   if (joined) {
@@ -428,7 +467,12 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   }
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
-    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->scene.materials_specular, c->stream);
+    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->scene.materials_specular, c->stream,
+                         take ? &c->deferred.args : nullptr, &c->filter_policy);
+  }
+  if (take) {
+    c->deferred_valid = false;
+    c->defer_info[1]++;
   }
   return launch_check(fused ? "gbuffer + temporal_gradient + raytrace" : "raytrace");
 }
@@ -696,7 +740,19 @@ void commit_filter(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, const 
   if (p.final_pass) fr.final_swapped = true;
 }
 
-int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
+// may the prepared final pass `a` wait for the next rtpt_raytrace (DeferredFinal)?  A single launch of the plain comb kernel that
+// a tracing launch can carry (rt::atrous_final_role: no extension, no prev_pixel store, no fused present, LDS within that
+// launch's), reading and writing nothing but planes the context owns
+bool defers(const rtpt_ctx* c, const FilterPlan& p, rt::AtrousArgs& a) {
+  if (!c->final_defer || !p.final_pass || p.levels != 1 || p.second_range || c->frame.ext_history || c->frame.ext_prev_vis) return false;
+  for (int i = 0; i < 3; i++)
+    if (!c->color[i].owned) return false;
+  if (!c->vis[c->frame.vis_cur].owned || !c->depth.owned) return false;
+  return rt::atrous_final_role(a);
+}
+
+// defer: the call is the last record of a frame's run (filter_flush)
+int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels, bool defer = false) {
   HIP_TRY(hipSetDevice(c->device));
   const FilterPlan p = plan_filter(c, f, levels);
   filter_prelaunch(c, p, f);
@@ -704,6 +760,14 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels) {
   PlaneTag<ReprojKey> stored;
   int rc = fill_atrous_args(c, p, f, a, &stored);
   if (rc) return rc;
+  if (defer && defers(c, p, a)) {
+    c->deferred.args = a;
+    c->deferred.kernel = p.kernel;
+    c->deferred_valid = true;
+    c->defer_info[0]++;
+    commit_filter(c, p, f, stored);
+    return RTPT_OK;
+  }
   {
     Timer tm(c, p.kernel);
     if (levels > 1)
@@ -744,6 +808,7 @@ namespace rtpt_impl {
 // run the recorded iterations.  fuse = false: one launch per iteration (an observer is about to look at the planes)
 int filter_flush(rtpt_ctx* c, bool fuse) {
   if (c->pending.empty()) return RTPT_OK;
+  if (int rc = final_flush(c)) return rc;  // an earlier frame's deferred pass goes ahead of these
   std::vector<FilterCall> calls;
   calls.swap(c->pending);  // filter_launch may fail: the record is dropped either way
   fuse = fuse && records_filter_calls(c);
@@ -758,7 +823,7 @@ int filter_flush(rtpt_ctx* c, bool fuse) {
       f.ubo = lastc.ubo;
       f.pc.frameNumber = lastc.pc.frameNumber;
     }
-    int rc = filter_launch(c, f, levels);
+    int rc = filter_launch(c, f, levels, fuse && i + static_cast<size_t>(levels) == calls.size());
     if (rc) return rc;
     i += static_cast<size_t>(levels);
   }
@@ -803,7 +868,11 @@ int rtpt_temporal_filter(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_
 // ------------------------------------------------------------------------------------------ K4
 int rtpt_end_frame(rtpt_ctx* c) {
   if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
-  FLUSH_FILTER(c);
+  {  // (a deferred final pass stays deferred: the roles rotate on top of what it will have written)
+    int rcf = gbuffer_flush(c);
+    if (rcf == RTPT_OK) rcf = filter_flush(c, false);
+    if (rcf) return rcf;
+  }
   // main.cpp:1364 image -> previousImage: rotate roles instead of blitting.  After the reference's
   // copy both images hold the same pixels; here IMAGE now names the old history buffer (about to be
   // overwritten by the next rtpt_raytrace), so until then rtpt_readback(IMAGE) is served from

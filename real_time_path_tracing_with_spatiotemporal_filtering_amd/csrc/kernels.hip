@@ -8,6 +8,9 @@
 //                                 reprojection + blend (:213-263)
 //
 // No MFMA anywhere: nothing on this path is a dense contraction.  Compile with -ffp-contract=off.
+#include <cstdlib>
+
+#include "atrous_comb.hpp"
 #include "device_common.hpp"
 #include "select.hpp"
 #include "specular.hpp"
@@ -941,8 +944,25 @@ constexpr int kPtWaves = 8;
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
 // TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (specular.hpp).
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, bool SPEC = false>
-__device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex) {
+// the tile grid's width / a tile's linear index, where pathtrace_tile used to read gridDim.x / compute the index (every use keeps
+// its place, so that the ROLE = 0 instantiations compile to what they were)
+template <int ROLE>
+__device__ __forceinline__ uint32_t tile_gx(uint32_t role_gx) {
+  if constexpr (ROLE != 0) return role_gx;
+  else return gridDim.x;
+}
+template <int ROLE>
+__device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
+  if constexpr (ROLE != 0) return role_lin;
+  else return blockIdx.y * gridDim.x + blockIdx.x;
+}
+// ROLE: 1 in the launch that also holds filter workgroups (k_pathtrace_final).  An instantiation of its own, so that its three
+// static LDS words are that kernel's alone: shared between two kernels they would move into the module-wide LDS block and
+// shift the dynamic LDS of every kernel of this file.
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, bool SPEC = false, int ROLE = 0>
+__device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
+                                               const uint32_t role_gy = 0) {
+  // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
   // Sharing it takes the BVH kernel from 41 to 30 KB per block: 5 instead of 3 resident blocks per CU for a
@@ -966,18 +986,18 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   // workgroups are dispatched in the order of their linear index; tiles are taken column by column from the middle of
   // the frame outwards, so the last ones dispatched — the tail of the launch — are the outermost columns, where (camera
   // facing the scene) the paths are short.  A frame of a few thousand tiles is only ~2 generations of workgroups.
-  const uint32_t tiles_y_ = GB ? a.tiles_y : gridDim.y;
-  const uint32_t lin_ = blockIdx.y * gridDim.x + blockIdx.x, col_ = lin_ / tiles_y_;
-  uint32_t bx_ = (col_ & 1u) ? (gridDim.x - 1u) / 2u + (col_ + 1u) / 2u : (gridDim.x - 1u) / 2u - col_ / 2u, by_ = lin_ % tiles_y_;
+  const uint32_t tiles_y_ = GB ? a.tiles_y : (ROLE ? role_gy : gridDim.y);
+  const uint32_t lin_ = tile_lin<ROLE>(role_lin), col_ = lin_ / tiles_y_;
+  uint32_t bx_ = (col_ & 1u) ? (tile_gx<ROLE>(role_gx) - 1u) / 2u + (col_ + 1u) / 2u : (tile_gx<ROLE>(role_gx) - 1u) / 2u - col_ / 2u, by_ = lin_ % tiles_y_;
 #if RTPT_TILE_TIMELINE
-  if (g_tile_order_n == gridDim.x * gridDim.y) {
+  if (g_tile_order_n == tile_gx<ROLE>(role_gx) * (ROLE ? role_gy : gridDim.y)) {
     const uint32_t t_ = g_tile_order[lin_];
-    bx_ = t_ % gridDim.x;
-    by_ = t_ / gridDim.x;
+    bx_ = t_ % tile_gx<ROLE>(role_gx);
+    by_ = t_ / tile_gx<ROLE>(role_gx);
   }
 #endif
 #if RTPT_TILE_TIMELINE
-  TimelineScope tl_(1, by_ * gridDim.x + bx_);  // indexed by tile
+  TimelineScope tl_(1, by_ * tile_gx<ROLE>(role_gx) + bx_);  // indexed by tile
 #endif
   const int tile_x0 = static_cast<int>(bx_) * kBlockX, tile_y0 = a.g.y0 + static_cast<int>(by_) * kPtRows;
   const float fw = static_cast<float>(a.g.W), fh = static_cast<float>(a.g.H);
@@ -1095,7 +1115,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
     if (a.seg_end < a.max_segments) {  // only with spp == 1: the unfinished paths continue in a queue kernel
       const uint32_t pixg = (static_cast<uint32_t>(tile_y0 + static_cast<int>(pix >> 6)) << 16) |
                             static_cast<uint32_t>(tile_x0 + static_cast<int>(pix & 63u));
-      const uint32_t blk = blockIdx.y * gridDim.x + blockIdx.x;
+      const uint32_t blk = tile_lin<ROLE>(role_lin);
       enqueue_paths(a, blk % kPathQueues, wave_cnt, &q_base, alive, wave, lane, pixg, rng, o, d, acc);
     }
   }
@@ -1118,7 +1138,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   // spread over kRayCounters slots: 32 400 same-address atomics per 4K launch serialise in the memory system and kept
   // the workgroups' slots occupied until acknowledged (a 1-segment launch took 397 us, of which the arithmetic is ~110)
   if (tid == 0 && block_rays)
-    atomicAdd(a.raycount + ((blockIdx.y * gridDim.x + blockIdx.x) & (kRayCounters - 1u)), static_cast<unsigned long long>(block_rays));
+    atomicAdd(a.raycount + (tile_lin<ROLE>(role_lin) & (kRayCounters - 1u)), static_cast<unsigned long long>(block_rays));
 }
 
 // the two kernels of the tile body: the wave-uniform brute-force one is pinned at 8 waves per SIMD (above), the BVH one
@@ -1174,6 +1194,40 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
     TimelineScope tl_(0, (blockIdx.y - a.tiles_y) * gridDim.x + blockIdx.x);
 #endif
     gbuffer_tile<0>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
+  }
+}
+
+// K2 of frame n + 1 and the final filter pass of frame n in one launch (api_passes.hip: DeferredFinal).  The trace is bound by VALU
+// issue and touches next to no memory, the final pass by HBM; neither reads what the other writes (DESIGN §4 has the table), and
+// as launches of their own they never share the machine.  One grid, three runs of workgroups in dispatch order: sp.n_front filter
+// workgroups, which run beside the body of the trace; the tracing tiles; sp.n_tail filter workgroups, which start as the last
+// tiles drain.  The filter workgroups are the comb kernel's (atrous_comb.hpp: comb_items); the front group owns the first
+// sp.front_items items of the list and the tail group the rest, so every item has one owner and no workgroup waits for another.
+// The launch's dynamic LDS is the larger of the two bodies': a staged row of kFinalRoleCw cells keeps it at 8 workgroups per CU.
+// Only the pass that loads its reprojected pixels (RLOAD) is instantiated: at this kernel's 64 VGPRs it needs no scratch, the
+// reprojecting pass would spill 48 registers per lane — it runs as the launch of its own (atrous_final_role).
+struct FinalSplit {
+  uint32_t n_front, n_tail;      // workgroups, multiples of 8 (0: the group owns no item)
+  uint32_t front_items, items;   // of the final pass's work list
+  uint32_t tiles_x;              // the tile grid is tiles_x x PathtraceArgs::tiles_y
+};
+// (CW, the staged row: a template like every other user of the dynamic LDS array `stack`, so that the array is still first
+// emitted through k_gbuffer's declaration — a plain kernel here comes first and hands its 16-byte alignment to the one symbol
+// all of them share, which moves the dynamic LDS of every kernel of this file from byte 24 to 32)
+template <int CW>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
+void k_pathtrace_final(PathtraceArgs a, TexView tex, AtrousArgs f, FinalSplit sp) {
+  static_assert(kPtThreads == kShThreads && kPtRows == kShWaves, "the two bodies share the workgroup shape");
+  const uint32_t n_tiles = sp.tiles_x * a.tiles_y, t = blockIdx.x - sp.n_front;
+  if (t < n_tiles) {  // (unsigned: a front workgroup wraps past it)
+    pathtrace_tile<0, true, false, false, 0, false, 1>(a, tex, t, sp.tiles_x, a.tiles_y);
+  } else {
+    extern __shared__ __attribute__((aligned(16))) unsigned char final_lds[];
+    const bool front = blockIdx.x < sp.n_front;
+    comb_items<CW, true, false, false, 1, false, false, true, true>(f, final_lds, front ? blockIdx.x : t - n_tiles,
+                                                                       front ? sp.n_front : sp.n_tail, front ? 0u : sp.front_items,
+                                                                       front ? sp.front_items : sp.items);
   }
 }
 
@@ -1593,12 +1647,36 @@ constexpr int kPoolRows = kPtRows;
 bool pathtrace_uses_pool(const PathtraceArgs&) { return false; }
 size_t pathtrace_pool_bytes(int, int) { return 0; }
 #endif
+bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, bool specular) {
+  return !a.scene.use_bvh && a.compact && a.spp == 1 && !a.albedo && !tex.records && !specular && !pathtrace_uses_pool(a) && a.g.y1 > a.g.y0;
+}
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
   const uint32_t gx = (a.g.W + kBlockX - 1) / kBlockX;
   const int tr = pathtrace_uses_pool(a) ? kPoolRows : kPtRows;
   return gx * ((a.g.y1 - a.g.y0 + tr - 1) / tr + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0));
 }
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s) {
+// the filter workgroups of a launch that carries the final pass `f` (atrous_final_role finished it): how many in front of and
+// behind the tiles, and where the work list is cut between them
+static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const FilterPolicy& pol, uint32_t tiles_x) {
+  const uint32_t n_cu = a.n_cu > 0 ? static_cast<uint32_t>(a.n_cu) : 256u, cu8 = (n_cu + 7u) / 8u;
+  const uint32_t per_cu = static_cast<uint32_t>(kPtWaves * 4 / kShWaves);  // resident workgroups of either kind
+  FinalSplit sp;
+  sp.tiles_x = tiles_x;
+  sp.items = static_cast<uint32_t>(f.tiles_x) * static_cast<uint32_t>(f.tiles_y) * static_cast<uint32_t>(f.stride);
+  auto clamp = [](int v, int hi) { return static_cast<uint32_t>(v < 0 ? 0 : (v > hi ? hi : v)); };
+  const uint32_t front_wg = clamp(pol.final_front, static_cast<int>(per_cu) - 1), share = clamp(pol.final_front_share, 100);
+  sp.front_items = front_wg ? static_cast<uint32_t>(static_cast<uint64_t>(sp.items) * share / 100u) : 0u;
+  // a group takes every slot it may hold, but no more workgroups than an XCD's eighth of its range has items
+  auto group = [&](uint32_t items, uint32_t slots_per_xcd) {
+    const uint32_t per_xcd = (items + 7u) / 8u;
+    return items ? 8u * (per_xcd < slots_per_xcd ? per_xcd : slots_per_xcd) : 0u;
+  };
+  sp.n_front = group(sp.front_items, cu8 * front_wg);
+  sp.n_tail = group(sp.items - sp.front_items, cu8 * (per_cu - front_wg));
+  return sp;
+}
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s, const AtrousArgs* fin,
+                      const FilterPolicy* pol) {
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
   const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
@@ -1607,6 +1685,10 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
   const size_t stack_bytes = a.scene.use_bvh ? static_cast<size_t>(a.scene.stack_lds) * kPtThreads * 4 : 0;
   size_t dyn = stack_bytes > sizeof(PathState) ? stack_bytes : sizeof(PathState);  // shared by both tenants
+  if (fin) {  // (api_passes.hip asked pathtrace_takes_final and atrous_final_role: no G-buffer workgroups, one sample, no BVH)
+    if (gb || !pol || !fin->reproj_in || !pathtrace_takes_final(a, tex, specular)) std::abort();
+    dyn = dyn > final_role_lds(*fin) ? dyn : final_role_lds(*fin);
+  }
   PathtraceArgs b = a;
   b.tiles_y = tiles_y;
   b.multi_off = static_cast<uint32_t>(dyn / 4);
@@ -1622,6 +1704,11 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   b.q_out = split ? a.queue[0] : nullptr;
   b.q_out_count = split ? a.queue_count : nullptr;
   if (split) (void)hipMemsetAsync(a.queue_count, 0, 2 * kPathQueues * sizeof(uint32_t), s);
+  if (fin) {
+    const FinalSplit sp = final_split(a, *fin, *pol, grid.x);
+    const dim3 grid1(sp.n_front + grid.x * tiles_y + sp.n_tail);
+    hipLaunchKernelGGL(k_pathtrace_final<kFinalRoleCw>, grid1, block, dyn, s, b, tex, *fin, sp);
+  } else
 #if RTPT_AB_VARIANTS
   if (pool) {
     if (gb)

@@ -334,7 +334,14 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // whether they can; pathtrace_grid_blocks = the workgroups of that launch, what the BVH stack's spill area is sized for)
 // specular: some triangle's material is specular (Scene::materials_specular) — what selects the SPEC instantiations; it travels
 // beside the kernel arguments, not in them, so that every existing argument offset stays
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s);
+// fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
+// atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
+// pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
+// textures, no specular bounce
+struct FilterPolicy;
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s, const AtrousArgs* fin = nullptr,
+                      const FilterPolicy* pol = nullptr);
+bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, bool specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
 bool pathtrace_uses_pool(const PathtraceArgs& a);
@@ -344,6 +351,11 @@ bool atrous_final_fuses_present(const AtrousArgs& a);
 // true when a launch of `a` runs in the plain comb kernel (no extension mode, not forced direct, 1 <= k <= 16, id-pair table
 // or per-pixel normals): the only kernel whose final pass takes reproj_out / reproj_in
 bool atrous_final_plain_comb(const AtrousArgs& a);
+// The final pass `a` as workgroups of a tracing launch (launch_pathtrace's fin): true when the comb body is instantiated for it
+// there — id-pair table, the fast weights, a stride whose halo fits that launch's LDS (atrous_comb.hpp: kFinalRoleMaxK), the
+// reprojected pixels loaded (reproj_in), neither prev_pixel nor present — and then the members a launch sets (cz, cl, tiles)
+// are filled in
+bool atrous_final_role(AtrousArgs& a);
 // `levels` consecutive iterations k, k+1, .. in one launch, intermediates in LDS (atrous_chain.hip): a.k = the first
 // stride, a.in / a.out = input of the first and output of the last iteration (distinct buffers), final_pass = the last
 // level is the frame's FINAL pass (reprojection + blend)
@@ -359,6 +371,11 @@ struct FilterPolicy {
   // (atrous_chain.hip: chain_segments), "a" or "a,b": a for four workgroups per CU, b for two or three; -1 = the built-in values
   int chain_skew = -1, chain_skew2 = -1;
   int chain_bw = 0;         // RTPT_CHAIN_BW: columns a strip of the pair (1,2) stores (A/B; 0 = the widest, 124)
+  // RTPT_FINAL_FRONT=<workgroups per CU>[,<percent of the work list>]: the filter workgroups of a tracing launch that carries the
+  // previous frame's final pass (kernels.hip: k_pathtrace_final) dispatched in FRONT of the tiles, and the share of the list they
+  // own; the rest runs behind the tiles.  0 = behind only.  4K frame at rest, one job (profiles/r17_final_defer_ab.txt): parent
+  // 0.620-0.624 ms; 0: 0.620; 1 per CU owning 25 / 50 / 75 %: 0.609 / 0.601 / 0.592; 2 per CU: 0.611 / 0.606 / 0.594
+  int final_front = 1, final_front_share = 75;
 };
 void launch_atrous_chain(const AtrousArgs& a, int levels, bool final_pass, const FilterPolicy& pol, hipStream_t s);
 bool atrous_chain_supported(int k0, int levels, uint32_t n_tris);
