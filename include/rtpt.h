@@ -326,7 +326,8 @@ int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32
 
 /* Specular materials (NOT reference behaviour, off until this call; additive: RTPT_ABI_VERSION stays 5).  A
  * material is diffuse (flags 0: `albedo` and `emission` mean what they mean in rtpt_material, `specular` and `roughness` are
- * only checked) or specular (RTPT_MAT_SPECULAR), never a mixture; no Fresnel term, no refraction.  A hit on a specular
+ * only checked), specular (RTPT_MAT_SPECULAR) or a dielectric (RTPT_MAT_DIELECTRIC, below), never a mixture; a specular
+ * material has no Fresnel term and does not refract.  A hit on a specular
  * material takes `specular` (.mtl Ks) where a diffuse hit takes Kd — texel multiply, albedo plane, throughput multiply and
  * mip level apply to it unchanged — and leaves along d' = normalize(reflect(d, n) + roughness * s), s the point of the unit
  * sphere the diffuse bounce would add to the normal, from the same two draws (csrc/specular.hpp states the arithmetic;
@@ -340,15 +341,31 @@ int rtpt_scene_set_materials(rtpt_ctx* ctx, const uint32_t* tri_material, uint32
  * unknown flag, a component of any material that is not finite, a specular material with a roughness outside [0, 1] or with
  * a non-zero emission.  The kernels that know the specular bounce run exactly when some TRIANGLE's material is specular.
  * Known limitation: the filter's guides (normal, depth, id, world position, reprojection) are the mirror's own, so a
- * reflected image is blurred over the filter's reach and reprojected with the mirror's surface. */
+ * reflected image is blurred over the filter's reach and reprojected with the mirror's surface.
+ *
+ * Dielectrics (RTPT_MAT_DIELECTRIC; additive as well): a perfectly smooth interface between the outside (index 1) and a medium
+ * of index `ior` >= 1, whose triangles' normals point out of the medium.  A hit takes `specular` as its colour exactly as a
+ * specular hit does, takes the segment's two draws, and is reflected with the probability of Schlick's Fresnel term F = R0 +
+ * (1 - R0)(1 - cos)^5 — R0 = ((ior - 1) / (ior + 1))^2, the cosine taken on the rarer side — exactly when its first draw is
+ * below F or the angle is beyond the critical one; otherwise it is refracted by Snell's law and goes on from the far side of
+ * the surface (csrc/dielectric.hpp states the arithmetic).  Never absorbed; the second draw is unused.  The word after `flags`
+ * carries `ior` when the flag is set and is ignored without it (the struct keeps its size and layout; `_pad` still names the
+ * word).  RTPT_E_INVALID as above, too, for: both flags on one material; a dielectric with a roughness other than 0, with a
+ * non-zero emission, or with an ior that is not finite or is < 1.  The kernels that know the interface run exactly when some
+ * TRIANGLE's material is a dielectric.  Known limitation: the filter's guides are the pane's own, so what is seen through glass
+ * is blurred and reprojected with the pane, as in a mirror. */
 #define RTPT_MAT_SPECULAR 0x1u
+#define RTPT_MAT_DIELECTRIC 0x2u
 typedef struct rtpt_material_ext {
   float albedo[3];   /* .mtl Kd */
   float emission[3]; /* .mtl Ke */
-  float specular[3]; /* .mtl Ks: the colour of a specular hit */
-  float roughness;   /* [0, 1] when specular; 0: mirror */
+  float specular[3]; /* .mtl Ks: the colour of a specular or dielectric hit */
+  float roughness;   /* [0, 1] when specular; 0: mirror.  0 when dielectric */
   uint32_t flags;    /* RTPT_MAT_* */
-  uint32_t _pad;
+  union {
+    uint32_t _pad; /* without RTPT_MAT_DIELECTRIC: ignored */
+    float ior;     /* with it: the index of refraction, finite and >= 1 (.mtl Ni) */
+  };
 } rtpt_material_ext;
 int rtpt_scene_set_materials_ext(rtpt_ctx* ctx, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material_ext* materials,
                                  uint32_t n_materials);
@@ -693,6 +710,11 @@ int rtpt_selftest_texture(rtpt_ctx* ctx, uint32_t texture, const float* uv, size
  * floats (d'[3], 1.0f if absorbed else 0.0f).  Operands are not checked: d and n are meant to be unit vectors, u1, u2 in
  * [0, 1], g in [0, 1]. */
 int rtpt_selftest_bounce(rtpt_ctx* ctx, const float* in, float* out, size_t n);
+/* the same for the dielectric interface (csrc/dielectric.hpp: the side, Snell's law, Schlick's term, the choice, the direction):
+ * in = n x 9 floats (d[3], n[3], u1, u2, ior), out = n x 5 floats (d'[3], 1.0f if transmitted else 0.0f, F).  Operands are not
+ * checked: d and n are meant to be unit vectors, u1, u2 in [0, 1], ior >= 1; 1 / ior and R0 are computed as the host computes
+ * them for the record. */
+int rtpt_selftest_refract(rtpt_ctx* ctx, const float* in, float* out, size_t n);
 /* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
  * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
  * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */
@@ -726,6 +748,12 @@ int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint3
  *   rtpt_util_load_obj_materials returns for the same file. */
 int rtpt_util_load_obj_materials_ext(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
                                      uint32_t* n_materials);
+/* rtpt_util_load_obj_materials_ext plus Ni and Tf.  A material is a dielectric instead of what the rule above makes it exactly
+ * when illum is 4, 6, 7 or 9, it has an `Ni` line with a finite value >= 1, Ke == 0 and its colour is not 0, the colour being Tf
+ * where a complete `Tf r g b` line exists and Ks otherwise: then specular[] = colour, ior = Ni, roughness = 0 and flags =
+ * RTPT_MAT_DIELECTRIC.  Every other material is what rtpt_util_load_obj_materials_ext returns for it, `_pad` 0 included. */
+int rtpt_util_load_obj_materials_ni(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
+                                    uint32_t* n_materials);
 /* the texture-coordinate side of the same file: `vt` records and the vt of `f v/vt`, `f v/vt/vn` corners (`f v`, `f v//vn`:
  * the corner gets (0, 0)); negative vt indices count back from the last `vt` read.  tri_uv: 6 floats per triangle (u0 v0 u1
  * v1 u2 v2), fanned like rtpt_util_load_obj's triangles, so the two arrays line up.  Two-call pattern (NULL: count). */

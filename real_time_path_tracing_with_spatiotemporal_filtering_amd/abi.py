@@ -85,20 +85,27 @@ class Material(C.Structure):
 
 
 MAT_SPECULAR = 0x1
-# rtpt_material_ext as a numpy record (48 bytes): Kd, Ke, Ks, roughness, flags (MAT_*)
-MATERIAL_EXT = np.dtype([("albedo", np.float32, 3), ("emission", np.float32, 3), ("specular", np.float32, 3),
-                         ("roughness", np.float32), ("flags", np.uint32), ("_pad", np.uint32)])
+MAT_DIELECTRIC = 0x2
+# rtpt_material_ext as a numpy record (48 bytes): Kd, Ke, Ks, roughness, flags (MAT_*), and the last word under its two names:
+# `_pad` (uint32) and `ior` (float32, read when MAT_DIELECTRIC is set) overlap, as the union of rtpt.h does
+MATERIAL_EXT = np.dtype({"names": ["albedo", "emission", "specular", "roughness", "flags", "_pad", "ior"],
+                         "formats": [(np.float32, 3), (np.float32, 3), (np.float32, 3), np.float32, np.uint32, np.uint32, np.float32],
+                         "offsets": [0, 12, 24, 36, 40, 44, 44], "itemsize": 48})
 assert MATERIAL_EXT.itemsize == 48
 
 
-def materials_ext(materials, specular=None) -> np.ndarray:
+def materials_ext(materials, specular=None, dielectric=None) -> np.ndarray:
     """MATERIAL_EXT records of (Kd, Ke) rows [m, 6] (flags 0: the set rtpt_scene_set_materials would take); specular: a dict
-    material index -> (Ks, roughness) of the rows to make specular"""
+    material index -> (Ks, roughness) of the rows to make specular; dielectric: a dict material index -> (colour, ior) of the
+    rows to make dielectric"""
     rows = np.ascontiguousarray(materials, np.float32).reshape(-1, 6)
     out = np.zeros(len(rows), MATERIAL_EXT)
     out["albedo"], out["emission"] = rows[:, :3], rows[:, 3:]
     for i, (ks, g) in (specular or {}).items():
         out["specular"][i], out["roughness"][i], out["flags"][i] = np.float32(ks), np.float32(g), MAT_SPECULAR
+        out["emission"][i] = 0
+    for i, (colour, ior) in (dielectric or {}).items():
+        out["specular"][i], out["roughness"][i], out["flags"][i], out["ior"][i] = np.float32(colour), 0, MAT_DIELECTRIC, np.float32(ior)
         out["emission"][i] = 0
     return out
 
@@ -140,6 +147,7 @@ SYMBOLS = [
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
+    "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -224,6 +232,8 @@ def load() -> C.CDLL:
         "rtpt_scene_set_materials_ext": [vp, vp, u32, vp, u32],
         "rtpt_util_load_obj_materials_ext": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_selftest_bounce": [vp, vp, vp, sz],
+        "rtpt_util_load_obj_materials_ni": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
+        "rtpt_selftest_refract": [vp, vp, vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -306,6 +316,20 @@ def load_obj_materials_ext(path: str):
     tri = np.zeros(nt.value, np.uint32)
     mats = np.zeros(nm.value, MATERIAL_EXT)
     _check(load().rtpt_util_load_obj_materials_ext(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
+    return tri, mats
+
+
+def load_obj_materials_ni(path: str):
+    """load_obj_materials_ext with Ni and Tf: a material with illum 4 / 6 / 7 / 9, an `Ni` >= 1, Ke == 0 and a colour (Tf, else
+    Ks) that is not 0 is a dielectric (flags MAT_DIELECTRIC, specular = colour, ior = Ni, roughness 0); every other one is
+    load_obj_materials_ext's (rtpt_util_load_obj_materials_ni)"""
+    nt, nm = C.c_uint32(), C.c_uint32()
+    _check(load().rtpt_util_load_obj_materials_ni(path.encode(), None, C.byref(nt), None, C.byref(nm)))
+    if nm.value == 0:
+        return None, None
+    tri = np.zeros(nt.value, np.uint32)
+    mats = np.zeros(nm.value, MATERIAL_EXT)
+    _check(load().rtpt_util_load_obj_materials_ni(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
     return tri, mats
 
 
@@ -618,6 +642,13 @@ class Context:
         cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 9)
         out = np.zeros((len(cases), 4), np.float32)
         _check(self._lib.rtpt_selftest_bounce(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def selftest_refract(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 5] (d', transmitted, F) of the device's dielectric interface on cases [n, 9] = d, n, u1, u2, ior (rtpt_selftest_refract)"""
+        cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 9)
+        out = np.zeros((len(cases), 5), np.float32)
+        _check(self._lib.rtpt_selftest_refract(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
 
     def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:

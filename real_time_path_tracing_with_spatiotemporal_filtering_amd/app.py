@@ -756,7 +756,7 @@ class PathTracingApplication:
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
-             specular=False, **app_kw):
+             specular=False, dielectric=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -765,7 +765,9 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     sampled from a generated mip chain at the level of the ray's footprint, RTPT_TEX_MIPMAP).
     `specular` (off by default): apply the library's Kd / Ke / Ks / Ns / illum by the rule of abi.load_obj_materials_ext — a
     `newmtl` with illum >= 3 and Ks != 0 bounces as a mirror or glossy surface (rtpt_scene_set_materials_ext) — to every context
-    of this rank; with `textures` the maps multiply Ks as they multiply Kd."""
+    of this rank; with `textures` the maps multiply Ks as they multiply Kd.
+    `dielectric` (off by default): the same with Ni and Tf too, by the rule of abi.load_obj_materials_ni — a `newmtl` with illum
+    4 / 6 / 7 / 9 and an `Ni` >= 1 is glass: Fresnel reflection or refraction at every hit (RTPT_MAT_DIELECTRIC)."""
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())
     if torch_planes is None:
         torch_planes = world > 1  # halo exchange and the history all-gather move rows of torch-owned planes
@@ -795,10 +797,10 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
             be.set_materials(t.tri_material, t.materials)
         if t.textures is not None:
             be.set_textures(t.tri_uv, t.tri_texture, t.textures, t.texels)
-    if specular:
+    if specular or dielectric:
         if mesh is not None:
-            raise ValueError("specular=True reads the OBJ's library: it needs `scene`, not `mesh`")
-        tri_material, materials = abi.load_obj_materials_ext(scene)
+            raise ValueError("specular=True / dielectric=True read the OBJ's library: they need `scene`, not `mesh`")
+        tri_material, materials = (abi.load_obj_materials_ni if dielectric else abi.load_obj_materials_ext)(scene)
         if materials is not None:
             be.set_materials_ext(tri_material, materials)      # (replaces the Kd / Ke set of textures=True: the same Kd / Ke)
     return app

@@ -193,7 +193,8 @@ struct Scene {
   uint64_t lut_version[2] = {~0ull, ~0ull};  // model_version each LUT buffer was built for
   bool lut_prev_valid = false;               // D3
   Buf materials;                             // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
-  bool materials_specular = false;           // some triangle's record is specular (rtpt_scene_set_materials_ext): the SPEC kernels
+  int materials_specular = 0;                // 1: some triangle's record is specular (rtpt_scene_set_materials_ext), 2: some
+                                             // triangle's is a dielectric — the SPEC kernels; 0: every record is diffuse
   // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
   struct Textures {
     Buf records, desc, texels;

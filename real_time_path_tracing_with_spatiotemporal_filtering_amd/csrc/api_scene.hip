@@ -680,14 +680,14 @@ int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint
     if (const char* why = rtpt_mat::check_materials(tri_material, n_tris, c->scene.n_base_tris, materials, n_materials))
       return fail(RTPT_E_INVALID, why);
   std::vector<float> rec;
-  bool any_specular = false;
+  int any_specular = 0;  // rtpt_mat::kMode*
   if (!drop) {
     try {
       rec.resize(static_cast<size_t>(n_tris) * 8);
     } catch (const std::bad_alloc&) {
       return fail(RTPT_E_NOMEM, "host allocation failed (material records)");
     }
-    any_specular = rtpt_mat::pack_records(tri_material, n_tris, materials, rec.data());
+    any_specular = rtpt_mat::pack_records_mode(tri_material, n_tris, materials, rec.data());
   }
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);

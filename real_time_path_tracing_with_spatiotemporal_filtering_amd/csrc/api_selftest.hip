@@ -119,6 +119,25 @@ int rtpt_selftest_bounce(rtpt_ctx* c, const float* in, float* out, size_t n) {
   return RTPT_OK;
 }
 
+int rtpt_selftest_refract(rtpt_ctx* c, const float* in, float* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * 9 * sizeof(float), out_bytes = n * 5 * sizeof(float);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_refract(static_cast<const float*>(din.ptr), static_cast<float*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_refract: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_trace(rtpt_ctx* c, const float* rays, size_t n, uint32_t* out_id, float* out_t) {
   if (!c || !rays || !out_id) return fail(RTPT_E_INVALID, "NULL argument");
   if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
@@ -672,6 +691,26 @@ int rtpt_util_load_obj_materials_ext(const char* path, uint32_t* tri_material, u
   std::vector<rtpt_material_ext> mats;
   bool any_library = false;
   if (rtpt_mat::load_obj_materials(path, tri_material, n_tris, &mats, &any_library, &err)) return fail(RTPT_E_INVALID, err);
+  if (!any_library) {
+    *n_materials = 0;
+    return RTPT_OK;
+  }
+  if (materials) {
+    if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
+    std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material_ext));
+  }
+  *n_materials = static_cast<uint32_t>(mats.size());
+  return RTPT_OK;
+}
+
+// ... plus Ni and Tf: a smooth dielectric by the rule of material_host.hpp
+int rtpt_util_load_obj_materials_ni(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
+                                    uint32_t* n_materials) {
+  if (!path || !n_tris || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
+  std::string err;
+  std::vector<rtpt_material_ext> mats;
+  bool any_library = false;
+  if (rtpt_mat::load_obj_materials_ni(path, tri_material, n_tris, &mats, &any_library, &err)) return fail(RTPT_E_INVALID, err);
   if (!any_library) {
     *n_materials = 0;
     return RTPT_OK;

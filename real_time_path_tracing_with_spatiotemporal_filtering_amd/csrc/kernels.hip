@@ -14,6 +14,7 @@
 #include "device_common.hpp"
 #include "select.hpp"
 #include "specular.hpp"
+#include "dielectric.hpp"
 
 namespace rt {
 namespace {
@@ -792,7 +793,11 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // where a diffuse one takes Kd — the record's colour, so everything above happens to it unchanged — and leaves along the lobe
 // around its mirror direction, with the same two draws.  A compile-time switch for DEMOD's and TEX's reason.  These instantiations
 // return early on every last segment (no exception for their registers: they are new), so that no schedule absorbs a path there.
-template <int TEX, int BVH = 1, bool SHORT_DIV = false, bool SPEC = false>
+// SPEC == 2: some triangle's material is a dielectric too (RTPT_MAT_DIELECTRIC; dielectric.hpp states the interface): such a hit
+// takes the record's colour the same way, takes both draws, and leaves reflected or refracted by its first draw against the
+// Fresnel term.  The origin is formed after the choice, its offset's sign selected once, so that the hit point is live once (the
+// BVH variants are pinned at 64 VGPRs).  0 and 1 are the instantiations before it, statement for statement.
+template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
@@ -815,7 +820,8 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     pos = bary_point(xyz(s0), xyz(s1), xyz(s2), b0, b1, b2);      // :137
   }
   f3 n{s0.w, s1.w, s2.w};                                          // :150 (precomputed per triangle)
-  [[maybe_unused]] float spec_w = 0.0f;  // SPEC: the record's spare word, 0 = diffuse (specular.hpp)
+  [[maybe_unused]] float spec_w = 0.0f;  // SPEC: the record's spare word, 0 = diffuse (specular.hpp), > 0 = the ior (dielectric.hpp)
+  [[maybe_unused]] float diel_inv = 0.0f, diel_r0 = 0.0f;  // SPEC == 2: 1 / ior and R0 of a dielectric's record
   f3 alb = (n.x > 0.99f) ? f3{1.f, 0.f, 0.f} : ((-n.x > 0.99f) ? f3{0.f, 1.f, 0.f} : f3{0.7f, 0.7f, 0.7f});  // :155-163
   if (a.scene.materials) {
     // SURVEY 8(f) rank 4, not reference behaviour: a material library replaces the normal-keyed colours; a surface
@@ -828,7 +834,11 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       return true;
     }
     alb = f3{m0.x, m0.y, m0.z};
-    if constexpr (SPEC) spec_w = m0.w;
+    if constexpr (SPEC != 0) spec_w = m0.w;
+    if constexpr (SPEC == 2) {
+      diel_inv = m1.x;
+      diel_r0 = m1.y;
+    }
   }
   if (TEX) {
     const float4* tr = tex.records + 2 * static_cast<size_t>((h.id1 - 1) % a.scene.n_base_tris);
@@ -859,13 +869,27 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     }
     return true;
   }
+  if constexpr (SPEC == 2) {
+    if (diel::is_dielectric(spec_w)) {
+      const bool entering = exact::dot(n, d) < 0.0f;
+      if (!entering) n = -n;
+      const float u1 = exact::rng_next(rng);                       // :256
+      exact::rng_skip(rng);                                        // :257 (drawn, unused)
+      bool transmitted;
+      float fresnel;
+      d = diel::interface(n, entering, d, u1, spec_w, diel_inv, diel_r0, &transmitted, &fresnel);
+      const float off = transmitted ? -a.ray_offset : a.ray_offset;
+      o = f3{fmaf_(off, n.x, pos.x), fmaf_(off, n.y, pos.y), fmaf_(off, n.z, pos.z)};
+      return seg + 1 >= a.max_segments;  // never absorbed (only builds without the early return get here on a last segment)
+    }
+  }
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
   float st_, ct;
   exact::sincos2pi(exact::rng_next(rng), st_, ct);                 // :256
   float u = fmaf_(2.0f, exact::rng_next(rng), -1.0f);              // :257
   float r = exact::sqrt_(fmaf_(-u, u, 1.0f));                      // :258
-  if constexpr (SPEC) {
+  if constexpr (SPEC != 0) {
     if (spec::is_specular(spec_w)) {
       bool absorbed;
       d = spec::lobe(n, d, r, ct, st_, u, spec::roughness(spec_w), &absorbed);
@@ -943,7 +967,8 @@ constexpr int kPtWaves = 8;
 // taller than the tile grid (a.tiles_y rows of tiles).
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
-// TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (specular.hpp).
+// TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (1, specular.hpp) and dielectric
+// ones too (2, dielectric.hpp).
 // the tile grid's width / a tile's linear index, where pathtrace_tile used to read gridDim.x / compute the index (every use keeps
 // its place, so that the ROLE = 0 instantiations compile to what they were)
 template <int ROLE>
@@ -959,7 +984,7 @@ __device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
 // ROLE: 1 in the launch that also holds filter workgroups (k_pathtrace_final).  An instantiation of its own, so that its three
 // static LDS words are that kernel's alone: shared between two kernels they would move into the module-wide LDS block and
 // shift the dynamic LDS of every kernel of this file.
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, bool SPEC = false, int ROLE = 0>
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
                                                const uint32_t role_gy = 0) {
   // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
@@ -1148,13 +1173,13 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
 // 5 waves per SIMD (the compiler's 79 VGPRs and the old 30 KB stack) 3.69 ms; pinned at 6 / 7 / 8: 3.93 / 3.55 / 3.36 ms
 // (at 8: 64 VGPRs and 8 dwords of scratch per lane).
 constexpr int kPtBvhWaves = 8;
-template <int BVH, bool COMPACT, bool DEMOD, int TEX, bool SPEC>
+template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex) {
   pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex);
 }
-template <bool COMPACT, bool DEMOD, int TEX, bool SPEC>
+template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex) {
@@ -1168,7 +1193,7 @@ void k_pathtrace_small(PathtraceArgs a, TexView tex) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD, int TEX, bool SPEC>
+template <int BVH, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
@@ -1182,7 +1207,7 @@ void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
     gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
-template <bool DEMOD, int TEX, bool SPEC>
+template <bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
@@ -1231,7 +1256,7 @@ void k_pathtrace_final(PathtraceArgs a, TexView tex, AtrousArgs f, FinalSplit sp
   }
 }
 
-template <int BVH, int TEX, bool SPEC>
+template <int BVH, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex) {
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
@@ -1512,6 +1537,20 @@ __global__ void k_selftest_bounce(const float* in, float* out, size_t n) {
   out[4 * i + 3] = absorbed ? 1.0f : 0.0f;
 }
 
+// dielectric.hpp's interface, one case per thread: in = d, n, u1, u2, ior; out = d', 1.0f if transmitted else 0.0f, F
+// (rtpt_selftest_refract)
+__global__ void k_selftest_refract(const float* in, float* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = in + 9 * i;
+  bool transmitted;
+  float fresnel;
+  const f3 dn = diel::refract(ld3(w + 3), ld3(w), w[6], w[8], &transmitted, &fresnel);
+  out[5 * i] = dn.x; out[5 * i + 1] = dn.y; out[5 * i + 2] = dn.z;
+  out[5 * i + 3] = transmitted ? 1.0f : 0.0f;
+  out[5 * i + 4] = fresnel;
+}
+
 template <int BVH>
 __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const float* rays, size_t n, float tmax,
                                                              uint32_t* out_id, float* out_t) {
@@ -1590,6 +1629,17 @@ static void with_tex_mode(const TexView& tex, F&& f) {
   else
     f(std::integral_constant<int, 0>{});
 }
+// f(mode) with the material mode as a compile-time constant (shade_segment<SPEC>): 2 some triangle's material is a dielectric, 1
+// some triangle's is specular and none a dielectric, 0 every material is diffuse
+template <class F>
+static void with_spec_mode(int specular, F&& f) {
+  if (specular >= 2)
+    f(std::integral_constant<int, 2>{});
+  else if (specular == 1)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 0>{});
+}
 // f(mode) with the scene's closest-hit mode as a compile-time constant: 2 BVH over fan pairs, 1 BVH over triangles, 0 brute
 // force (closest_hit<BVH>; the brute-force tile kernels have names of their own, *_small, for their occupancy pin)
 template <class F>
@@ -1647,7 +1697,7 @@ constexpr int kPoolRows = kPtRows;
 bool pathtrace_uses_pool(const PathtraceArgs&) { return false; }
 size_t pathtrace_pool_bytes(int, int) { return 0; }
 #endif
-bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, bool specular) {
+bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular) {
   return !a.scene.use_bvh && a.compact && a.spp == 1 && !a.albedo && !tex.records && !specular && !pathtrace_uses_pool(a) && a.g.y1 > a.g.y0;
 }
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
@@ -1675,7 +1725,7 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
   sp.n_tail = group(sp.items - sp.front_items, cu8 * (per_cu - front_wg));
   return sp;
 }
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s, const AtrousArgs* fin,
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
                       const FilterPolicy* pol) {
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
@@ -1724,8 +1774,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       constexpr bool D = decltype(demod)::value;
       with_tex_mode(tex, [&](auto tex_mode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tex_mode)::value;
-        with_bool(specular, [&](auto spec) {  // rtpt_scene_set_materials_ext: the instantiations that bounce specular materials
-          constexpr bool S = decltype(spec)::value;
+        with_spec_mode(specular, [&](auto spec) {  // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials
+          constexpr int S = decltype(spec)::value;
           if (gb) {
             if constexpr (M != 0)
               hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T, S>), grid, block, dyn, s, b, *gb, tex);
@@ -1761,7 +1811,7 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
     with_scene_mode(a.scene, [&](auto mode) {
       with_tex_mode(tex, [&](auto tex_mode) {
-        with_bool(specular, [&](auto spec) {
+        with_spec_mode(specular, [&](auto spec) {
           hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tex_mode)::value, decltype(spec)::value>), qgrid, block,
                              dyn_queue, s, c, tex);
         });
@@ -1791,6 +1841,10 @@ void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t 
 void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_bounce, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_refract, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
 }
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s) {
   if (!n) return;

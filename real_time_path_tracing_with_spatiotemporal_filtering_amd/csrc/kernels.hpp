@@ -38,6 +38,7 @@ struct SceneView {
   // optional per-triangle materials of the BASE mesh (.mtl Kd / Ke; instance i, triangle t reads record t):
   //   m0 = (Kd.rgb, 0)  m1 = (Ke.rgb, 1 if emissive else 0).  NULL: the reference's normal-keyed colours
   //   a specular material (rtpt_scene_set_materials_ext): m0 = (Ks.rgb, -roughness), -0.0f for the mirror (specular.hpp)
+  //   a dielectric one: m0 = (colour, ior), m1 = (1 / ior, R0, 0, 0) (dielectric.hpp)
   const float4* materials;
   uint32_t n_base_tris;
 };
@@ -332,16 +333,17 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
 void launch_gradient(const GradientArgs& a, hipStream_t s);
 // gb != NULL: K0 (+ K1) of gb's rows run inside the tile kernel's launch, behind the tracing tiles (pathtrace_fuses_gbuffer says
 // whether they can; pathtrace_grid_blocks = the workgroups of that launch, what the BVH stack's spill area is sized for)
-// specular: some triangle's material is specular (Scene::materials_specular) — what selects the SPEC instantiations; it travels
+// specular: 1 some triangle's material is specular, 2 some triangle's is a dielectric, 0 neither (Scene::materials_specular) — what
+// selects the SPEC instantiations; it travels
 // beside the kernel arguments, not in them, so that every existing argument offset stays
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
 // textures, no specular bounce
 struct FilterPolicy;
-void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, bool specular, hipStream_t s, const AtrousArgs* fin = nullptr,
+void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
                       const FilterPolicy* pol = nullptr);
-bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, bool specular);
+bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
 bool pathtrace_uses_pool(const PathtraceArgs& a);
@@ -401,6 +403,8 @@ constexpr uint32_t kContractWords[kContractFns][2] = {
 void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // spec::bounce (specular.hpp) on n cases of 9 floats (d, n, u1, u2, g): out = n x (d', absorbed as 1.0f / 0.0f)
 void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s);
+// diel::refract (dielectric.hpp) on n cases of 9 floats (d, n, u1, u2, ior): out = n x (d', transmitted as 1.0f / 0.0f, F)
+void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 // tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs

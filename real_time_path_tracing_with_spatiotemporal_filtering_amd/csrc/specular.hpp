@@ -1,7 +1,8 @@
 // specular.hpp — the specular bounce (rtpt_scene_set_materials_ext, RTPT_MAT_SPECULAR).  ONE definition, used by every kernel that
 // shades a hit (kernels.hip: shade_segment<..., SPEC = true>) and by the self test (rtpt_selftest_bounce).  Not reference
 // behaviour: the reference traces no reflection (its only reflect() is a highlight of the gradient shader).  A material is
-// diffuse or specular, never a mixture; no Fresnel term, no refraction.
+// diffuse or specular, never a mixture; no Fresnel term, no refraction here — a smooth dielectric is a third kind of material,
+// dielectric.hpp.
 //
 // The arithmetic, contract functions only (rtpt_math.hpp), stated so that numpy float32 reproduces it bit for bit (the build
 // has -ffp-contract=off: only the fmas written here fuse; tests/specular_scenes.py restates it).  n: the triangle's unit normal,

@@ -69,9 +69,11 @@ void PathTracingApplication::loadMesh() {
     check(rtpt_util_load_obj_materials(opt_.scene.c_str(), triMaterial.data(), &ntm, objMaterials.data(), &nm), "loadMesh");
   }
   objMaterialsExt.clear();
-  if (opt_.specular && !objMaterials.empty()) {  // the same numbering and Kd / Ke, plus Ks / Ns / illum by the loader's rule
-    objMaterialsExt.resize(nm);
-    check(rtpt_util_load_obj_materials_ext(opt_.scene.c_str(), triMaterial.data(), &ntm, objMaterialsExt.data(), &nm), "loadMesh");
+  if ((opt_.specular || opt_.dielectric) && !objMaterials.empty()) {  // the same numbering and Kd / Ke, plus Ks / Ns / illum by the loader's rule
+    objMaterialsExt.resize(nm);                                       // (--dielectric: Ni and Tf too)
+    check((opt_.dielectric ? rtpt_util_load_obj_materials_ni : rtpt_util_load_obj_materials_ext)(opt_.scene.c_str(), triMaterial.data(), &ntm,
+                                                                                                 objMaterialsExt.data(), &nm),
+          "loadMesh");
   }
   // configs[4]: tessellated quads on a lattice of instances (scene_gen.hpp); camera, light and far plane frame the lattice
   sceneTextures_ = SceneTextures{};

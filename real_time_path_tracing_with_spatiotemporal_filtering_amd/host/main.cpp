@@ -25,6 +25,7 @@ static void usage(const char* argv0) {
       "           PPM / PFM next to the OBJ, at every hit: rtpt_scene_set_textures; without it an OBJ with map_Kd renders as it always did;\n"
       "           --texture-mips: from generated mip chains, at the level of the ray's footprint, RTPT_TEX_MIPMAP)]\n"
       "          [--specular  (a newmtl with illum >= 3 and Ks != 0 bounces as a mirror, or glossy by its Ns: rtpt_scene_set_materials_ext)]\n"
+      "          [--dielectric  (--specular's rule, and a newmtl with illum 4 / 6 / 7 / 9 and an Ni >= 1 is glass: Fresnel reflection or refraction)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -88,6 +89,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
     else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
+    else if (!std::strcmp(argv[i], "--dielectric")) opt.dielectric = true;
     else if (!std::strcmp(argv[i], "--texture-filter")) {
       const char* v = need("--texture-filter");
       if (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear")) { std::fprintf(stderr, "--texture-filter nearest|bilinear\n"); return 2; }
