@@ -666,7 +666,7 @@ int rtpt_selftest_exhaustive(rtpt_ctx* ctx, int op, uint64_t* mismatches, uint32
  * *mismatches = results that differ in any bit (two NaNs count as equal); first_bad = the bits of one offending (a, b). */
 int rtpt_selftest_div(rtpt_ctx* ctx, int mode, uint32_t first_pass, uint32_t n_passes, uint64_t* mismatches, uint32_t first_bad[2]);
 /* One function of the numerics contract per call, evaluated on the device item by item (one thread each) by the very
- * functions the frame kernels call (csrc/rtpt_math.hpp, device_common.hpp, kernels.hip), for comparison with the oracle's
+ * functions the frame kernels call (csrc/rtpt_math.hpp, device_common.hpp, shade_segment.hpp), for comparison with the oracle's
  * oracle_contract_array operand by operand.  in = n items of `in` words, out = n items of `out` words, host arrays of raw
  * 32-bit patterns: floats as their bits (NaN payloads and signed zeros pass unchanged), integers as they are.
  *   fn                          in -> out   words

@@ -181,7 +181,7 @@ struct Scene {
   std::vector<float> mesh_xyz;
   std::vector<uint32_t> mesh_idx;
   bool use_bvh = false;
-  bool tris_paired = false;  // every (2q, 2q+1) is a fan pair: same v0, v2_A == v1_B bitwise (kernels.hip tri_pair_test)
+  bool tris_paired = false;  // every (2q, 2q+1) is a fan pair: same v0, v2_A == v1_B bitwise (closest_hit.hpp tri_pair_test)
   std::vector<float> host_tris;  // flattened world-space triangles, kept for small scenes (screen bounds)
   // animated model matrix (main.cpp:1469 recomputes ubo.model every frame; it is the identity there): the scene as
   // uploaded (object space), and the model it is posed with.  obj_tris is kept where the host reads it: scenes small

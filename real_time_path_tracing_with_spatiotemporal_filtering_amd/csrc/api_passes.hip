@@ -154,7 +154,7 @@ int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
 }
 
 // the queues that hand the survivors of the first `window` segments to the queue kernels.  A region holds the survivors of
-// ceil(workgroups / kPathQueues) workgroups of 256 paths (kernels.hip); the second buffer is only needed when a third segment
+// ceil(workgroups / kPathQueues) workgroups of 256 paths (pathtrace_tile.hpp: enqueue_paths); the second buffer is only needed when a third segment
 // window exists
 int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
   a.queue[0] = a.queue[1] = nullptr;

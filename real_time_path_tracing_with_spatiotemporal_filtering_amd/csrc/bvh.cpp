@@ -336,7 +336,7 @@ BvhGrid pack_quantised_nodes(const Bvh& bvh, std::vector<BvhNodeQ>& out) {
   // of (origin - o) / d is ~2^-24 |origin - o| / |d|, and the triangle test's own rounding of o - v0 is of the same size,
   // while the padding (1e-5 x the scene's size) plus the grid's outward rounding (< one cell) is fixed.  The padding
   // absorbs the gap for an origin within a few scene diagonals; beyond ~100 of them it would not, so the traversal adds a
-  // per-ray margin proportional to |origin - o| (kernels.hip, closest_hit_bvh).
+  // per-ray margin proportional to |origin - o| (closest_hit.hpp, closest_hit_bvh).
   auto decode = [&](double q, int a) { return std::fmaf(static_cast<float>(q), g.cell[a], g.origin[a]); };
   auto qdown = [&](float x, int a) -> uint16_t {
     double q = std::floor((static_cast<double>(x) - static_cast<double>(g.origin[a])) / cell[a]);

@@ -49,7 +49,7 @@ struct Bvh {
 // inflate the leaves of the 1.15M-triangle lattice by ~30 % and the trace ran 3x SLOWER; the grid is 32x finer.)
 struct alignas(16) BvhNodeQ {
   // per child and axis one dword (min | max << 16): left x, y, z, right x, y, z.  The traversal rotates a dword by 16 where
-  // the ray runs against the axis, so that its low half is always the plane the ray meets first (kernels.hip: node_step)
+  // the ray runs against the axis, so that its low half is always the plane the ray meets first (closest_hit.hpp: node_step)
   uint16_t box[12];
   uint32_t lref, rref;
 };
@@ -73,7 +73,7 @@ BvhGrid pack_quantised_nodes(const Bvh& bvh, std::vector<BvhNodeQ>& out);
 void build_bvh(const float* tris, uint32_t n, Bvh& out, float pad_rel = 1e-5f, bool pairs = false);
 
 // The leaf layout a tree built with pairs = true must have, because the traversal's pairs-mode leaf test reads exactly ONE
-// 80-byte pair record per leaf, at slot first / 2, whatever the leaf's count (kernels.hip: closest_hit_bvh<true>): the leaf
+// 80-byte pair record per leaf, at slot first / 2, whatever the leaf's count (closest_hit.hpp: closest_hit_bvh<true>): the leaf
 // is the two triangles 2q, 2q + 1 of one fan pair, in this order, from an even slot.
 inline bool pair_leaf_ok(uint32_t first, uint32_t cnt, const uint32_t* leaf_order, size_t n_slots) {
   return cnt == 2 && !(first & 1u) && static_cast<size_t>(first) + 1 < n_slots && !(leaf_order[first] & 1u) &&

@@ -1,5 +1,5 @@
 // dielectric.hpp — the dielectric interface (rtpt_scene_set_materials_ext, RTPT_MAT_DIELECTRIC): Fresnel reflection or refraction
-// at a perfectly smooth surface.  ONE definition, used by every kernel that shades a hit (kernels.hip: shade_segment<..., SPEC = 2>)
+// at a perfectly smooth surface.  ONE definition, used by every kernel that shades a hit (shade_segment.hpp: shade_segment<..., SPEC = 2>)
 // and by the self test (rtpt_selftest_refract).  Not reference behaviour: the reference traces neither.
 //
 // The arithmetic, contract functions only (rtpt_math.hpp: exact::dot, exact::sqrt_, exact::normalize, fmaf_) and plain binary32

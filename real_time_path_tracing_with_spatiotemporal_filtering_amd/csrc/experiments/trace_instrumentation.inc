@@ -1,7 +1,9 @@
 // experiments/trace_instrumentation.inc — the COUNTING (-DRTPT_BVH_COUNT=1) and TIMELINE (-DRTPT_TILE_TIMELINE=1) builds of
-// kernels.hip: device-side counters / timestamps and the exported readers scripts/bvh_count.py and scripts/tile_timeline.py
-// call.  Never part of the shipped library; kernels.hip keeps only the hooks (RTPT_COUNT_*, TimelineScope at the top of a kernel).
-// Included twice: inside kernels.hip's anonymous namespace (RTPT_INSTR_DEVICE) and behind it (RTPT_INSTR_HOST).
+// the tracing kernels: device-side counters / timestamps and the exported readers scripts/bvh_count.py and scripts/tile_timeline.py
+// call.  Never part of the shipped library; the kernels keep only the hooks (RTPT_COUNT_* in closest_hit.hpp, TimelineScope at the
+// top of a workgroup's body).  Included twice: inside closest_hit.hpp's anonymous namespace (RTPT_INSTR_DEVICE; every unit that
+// traces gets the globals, the readers see those of kernels.hip, whose kernels the frame runs) and behind kernels.hip's
+// (RTPT_INSTR_HOST).
 #if defined(RTPT_INSTR_DEVICE)
 // Counting build (-DRTPT_BVH_COUNT=1, scripts/bvh_count.py; never the shipped library): where the traversal's idle lanes are.
 // Per call of closest_hit_bvh and wave: trips of the node loop / of the leaf loop, the lanes active in each trip, and the

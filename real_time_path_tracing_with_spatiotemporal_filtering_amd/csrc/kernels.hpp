@@ -1,5 +1,5 @@
 // kernels.hpp — launch interface between the C-ABI layer (api_*.hip) and the gfx950 kernels
-// (kernels.hip).  Plain structs passed by value as kernel arguments.
+// (kernels.hip, selftest_kernels.hip).  Plain structs passed by value as kernel arguments.
 #pragma once
 
 #include <hip/hip_runtime.h>

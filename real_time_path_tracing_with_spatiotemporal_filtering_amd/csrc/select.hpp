@@ -1,6 +1,6 @@
 // select.hpp — from a run-time value to a template argument.  A kernel family lists its instantiations ONCE, as a
 // type_list of tag types; the prepare function visits every entry, the launch function the first entry that matches, and
-// a run-time bool reaches a generic lambda as std::true_type / std::false_type.
+// a run-time bool reaches a generic lambda as std::true_type / std::false_type, a three-valued mode as an integral_constant.
 #pragma once
 
 #include <type_traits>
@@ -29,6 +29,17 @@ inline void with_bool(bool b, F&& f) {
     f(std::true_type{});
   else
     f(std::false_type{});
+}
+// f(std::integral_constant<int, mode>{}) for a mode of 0, 1 or 2 (anything else is 0): the three-valued template axes of the
+// tracing kernels, whose modes scene_mode (closest_hit.hpp), tex_mode and spec_mode (shade_segment.hpp) compute
+template <class F>
+inline void with_mode3(int mode, F&& f) {
+  if (mode == 2)
+    f(std::integral_constant<int, 2>{});
+  else if (mode == 1)
+    f(std::integral_constant<int, 1>{});
+  else
+    f(std::integral_constant<int, 0>{});
 }
 // f(FINAL, EXACT): the two bools every filter kernel is instantiated over
 template <class F>

@@ -1,0 +1,218 @@
+// shade_segment.hpp — one path segment after its closest-hit query (raytrace.comp.glsl:226-267), stated once for the tile
+// kernels and the queue kernel (pathtrace_tile.hpp, kernels.hip): the light test, the sky, the albedo with its textures, and the
+// diffuse, specular or dielectric bounce.  The self-test kernels (selftest_kernels.hip) call its pieces.  Everything here is
+// force-inlined.
+#pragma once
+
+#include "closest_hit.hpp"
+#include "dielectric.hpp"
+#include "specular.hpp"
+
+namespace rt {
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// K2 path trace
+// ------------------------------------------------------------------------------------------
+// raytrace.comp.glsl:168-198 — only the boolean is consumed (:226), and the sphere is tested
+// regardless of the triangle hit distance (the light is never occluded)
+__device__ __forceinline__ bool ray_hits_light(f3 o, f3 d, f3 c, float r2) {
+  f3 oc = o - c;
+  float a = exact::dot(d, d);
+  float b = 2.0f * exact::dot(oc, d);
+  float cc = exact::dot(oc, oc) - r2;
+  float disc = fmaf_(b, b, -((4.0f * a) * cc));
+  if (disc < 0.0f) return false;
+  float sq = exact::sqrt_(disc);
+  // :190-197 "t1 > 0 || t2 > 0" with t1 = (-b - sq) / 2a, t2 = (-b + sq) / 2a.  sq >= 0 and 2a >= 0, and both the
+  // addition and the correctly-rounded division are monotonic, so t1 <= t2 whenever neither is NaN: t1 > 0 implies
+  // t2 > 0, and the disjunction IS "t2 > 0" (NaN operands make both comparisons false either way; 2a == 0 gives +-inf /
+  // NaN with the same signs).  One division less per path segment.
+#if RTPT_TRACE_ITEMS & 2
+  // ... and of t2 only the sign is asked for: exact::quotient_positive is "num / den > 0.0f" on every pair of operands and
+  // divides only where the sign is not num's (2a is 2 |d|^2, about 2)
+  return exact::quotient_positive(-b + sq, 2.0f * a);
+#else
+  float t2 = RTPT_DIV_SH(-b + sq, 2.0f * a);
+  return t2 > 0.0f;
+#endif
+}
+
+__device__ __forceinline__ f3 sky_color(f3 d) {  // raytrace.comp.glsl:95-107
+  if (d.y > 0.0f) {
+    float t = d.y, it = 1.0f - t;
+    return f3{fmaf_(0.25f, t, it), fmaf_(0.5f, t, it), fmaf_(1.0f, t, it)};
+  }
+  return f3{0.03f, 0.03f, 0.03f};
+}
+
+// the colour of a pixel of an "rgbd" image without touching its alpha (one global_store_dwordx3)
+__device__ __forceinline__ void store_rgb(float4* px, f3 c) {
+  typedef float v3f_ __attribute__((ext_vector_type(3)));
+  *reinterpret_cast<v3f_*>(px) = v3f_{c.x, c.y, c.z};
+}
+
+// The level a hit's texture is sampled at (texture.hpp states the arithmetic): the footprint of segment 0 is the pixel's,
+// t * 2 * slope / H of the FULL frame, so strips agree; every later segment starts over from its own length, t * spread —
+// nothing is carried between segments.  Density and areas come from the hit's own records, so instances, a changed model
+// and moved instances are right without host bookkeeping.  td: the hit's descriptor; s, t0, t1: its shade and uv records.
+__device__ __forceinline__ float hit_texture_lod(const TexDesc td, float4 s0, float4 s1, float4 s2, float4 t0, float4 t1, float t, f3 d,
+                                                 bool primary, float slope, int frame_h, float bounce_spread) {
+  if (!(td.flags & kTexMipmap)) return 0.0f;
+  const float w = t * (primary ? (2.0f * slope) / static_cast<float>(frame_h) : bounce_spread);
+  return tex::footprint_lod(w, exact::dot(f3{s0.w, s1.w, s2.w}, d), s0, s1, s2, t0, t1, td.width, td.height);
+}
+
+// b1 = -u / ad, b2 = v / ad, b0 = 1 - b1 - b2 (:134).  SHORT_DIV: exact::div2_, for the wave-uniform brute-force kernels that have
+// the registers; the BVH kernels, pinned at 64 VGPRs, keep hipcc's divisions (RTPT_DIV_SH, closest_hit.hpp)
+template <bool SHORT_DIV>
+__device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, float& b1, float& b2) {
+  if (SHORT_DIV) {
+    exact::div2_(-h.u, h.v, h.ad, b1, b2);
+  } else {
+    b1 = RTPT_DIV_SH(-h.u, h.ad);
+    b2 = RTPT_DIV_SH(h.v, h.ad);
+  }
+  b0 = 1.0f - b1 - b2;
+}
+
+// One path segment after its closest-hit query (raytrace.comp.glsl:226-267): the unoccluded light test, the sky, or a
+// diffuse bounce.  Returns true when the path ended (its colour is then `acc`).
+// alb_px (RTPT_FLAG_EXT_DEMODULATE; non-NULL only at segment 0 of the tile kernel): the pixel of PathtraceArgs::albedo.  The
+// albedo of this hit goes there instead of into the throughput, and a path that ends here stores (1, 1, 1) and keeps its colour.
+// TEX: the scene has albedo textures (rtpt_scene_set_textures): the albedo is (Kd or the normal-keyed colour) x texel.rgb, one
+// multiply per channel, at every segment.  A compile-time switch for DEMOD's reason: the instantiations without it are the
+// kernels of a build that knows no textures, register for register.  TEX == 2: some texture of the scene has RTPT_TEX_MIPMAP,
+// and the texel comes from the level of the ray's footprint (hit_texture_lod, tex::sample_lod); 1: level 0, as before mips.
+// BVH: the caller's closest-hit structure; SHORT_DIV: see hit_barycentrics (the defaults are the kernels before either).
+// The LAST segment of a path (seg + 1 >= a.max_segments — the path's budget, not the launch's window seg_end: behind a window
+// boundary the queue kernel goes on with o, d and rng) ends after its throughput update: the hit point, the faceforward, the
+// offset origin, the two draws' floats, sincos2pi, the square root and the normalize make an o and a d that nothing reads.  What
+// stays: the barycentrics where the hit samples a texture, and with samples_per_pixel > 1 the two steps of the RNG state, which
+// the pixel's next sample continues from (rng_pix, pathtrace_tile).
+// Two places keep the bounce, for their registers (make resource-usage, profiles/r15_trace_shading_ab.txt): the untextured
+// instantiations over fan pairs (BVH == 2, TEX == 0; pinned at 64 VGPRs with 8 to 14 spilled ones — the early return cost
+// k_gbuffer_pathtrace<2, false, 0>, the kernel of the instanced frame, one more: 36 -> 40 bytes of scratch) and the segment that
+// stores the albedo plane (alb_px; 0 -> 8 bytes in the brute-force DEMOD kernels), which is a path's last only with max_segments 1.
+// SPEC: some triangle's material is specular (rtpt_scene_set_materials_ext; specular.hpp states the bounce): such a hit takes Ks
+// where a diffuse one takes Kd — the record's colour, so everything above happens to it unchanged — and leaves along the lobe
+// around its mirror direction, with the same two draws.  A compile-time switch for DEMOD's and TEX's reason.  These instantiations
+// return early on every last segment (no exception for their registers: they are new), so that no schedule absorbs a path there.
+// SPEC == 2: some triangle's material is a dielectric too (RTPT_MAT_DIELECTRIC; dielectric.hpp states the interface): such a hit
+// takes the record's colour the same way, takes both draws, and leaves reflected or refracted by its first draw against the
+// Fresnel term.  The origin is formed after the choice, its offset's sign selected once, so that the hit point is live once (the
+// BVH variants are pinned at 64 VGPRs).  0 and 1 are the instantiations before it, statement for statement.
+template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0>
+__device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
+                                              f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr) {
+  if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
+    acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
+    if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    return true;
+  }
+  if (h.id1 == 0) {
+    acc = acc * sky_color(d);  // :266
+    if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    return true;
+  }
+  const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
+  float4 s0 = s[0], s1 = s[1], s2 = s[2];
+  const bool last = (RTPT_TRACE_ITEMS & 1) && (SPEC || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
+  float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+  f3 pos{0.f, 0.f, 0.f};
+  if (!last) {
+    hit_barycentrics<SHORT_DIV>(h, b0, b1, b2);
+    pos = bary_point(xyz(s0), xyz(s1), xyz(s2), b0, b1, b2);      // :137
+  }
+  f3 n{s0.w, s1.w, s2.w};                                          // :150 (precomputed per triangle)
+  [[maybe_unused]] float spec_w = 0.0f;  // SPEC: the record's spare word, 0 = diffuse (specular.hpp), > 0 = the ior (dielectric.hpp)
+  [[maybe_unused]] float diel_inv = 0.0f, diel_r0 = 0.0f;  // SPEC == 2: 1 / ior and R0 of a dielectric's record
+  f3 alb = (n.x > 0.99f) ? f3{1.f, 0.f, 0.f} : ((-n.x > 0.99f) ? f3{0.f, 1.f, 0.f} : f3{0.7f, 0.7f, 0.7f});  // :155-163
+  if (a.scene.materials) {
+    // SURVEY 8(f) rank 4, not reference behaviour: a material library replaces the normal-keyed colours; a surface
+    // with emission ends the path like the analytic light does (:226-234), throughput *= Ke
+    const float4* m = a.scene.materials + 2 * static_cast<size_t>((h.id1 - 1) % a.scene.n_base_tris);
+    const float4 m0 = m[0], m1 = m[1];
+    if (m1.w != 0.0f) {
+      acc = acc * f3{m1.x, m1.y, m1.z};
+      if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      return true;
+    }
+    alb = f3{m0.x, m0.y, m0.z};
+    if constexpr (SPEC != 0) spec_w = m0.w;
+    if constexpr (SPEC == 2) {
+      diel_inv = m1.x;
+      diel_r0 = m1.y;
+    }
+  }
+  if (TEX) {
+    const float4* tr = tex.records + 2 * static_cast<size_t>((h.id1 - 1) % a.scene.n_base_tris);
+    const float4 t0 = tr[0], t1 = tr[1];
+    const uint32_t ti = __float_as_uint(t1.z);
+    if (ti) {
+      if (last) hit_barycentrics<SHORT_DIV>(h, b0, b1, b2);
+      const float tu = tex::interp_uv(b0, b1, b2, t0.x, t0.z, t1.x), tv = tex::interp_uv(b0, b1, b2, t0.y, t0.w, t1.y);
+      float4 tx;
+      if constexpr (TEX == 2) {
+        const TexDesc td = tex.desc[ti - 1];
+        const float lambda = hit_texture_lod(td, s0, s1, s2, t0, t1, h.t, d, seg == 0, a.slope, a.g.H, tex.bounce_spread);
+        tx = tex::sample_lod(td, tex.levels + kTexLevelRow * static_cast<size_t>(ti - 1), tex.texels, tu, tv, lambda);
+      } else {
+        tx = tex::sample(tex.desc[ti - 1], tex.texels, tu, tv);
+      }
+      alb = f3{alb.x * tx.x, alb.y * tx.y, alb.z * tx.z};
+    }
+  }
+  if (alb_px)
+    *alb_px = make_float4(alb.x, alb.y, alb.z, 0.0f);  // demodulated: rtpt_modulate / rtpt_present multiply it back
+  else
+    acc = acc * alb;                                               // :244
+  if (last) {  // budget exhausted: the path returns its throughput (:270)
+    if (a.spp > 1) {
+      exact::rng_skip(rng);  // :256
+      exact::rng_skip(rng);  // :257
+    }
+    return true;
+  }
+  if constexpr (SPEC == 2) {
+    if (diel::is_dielectric(spec_w)) {
+      const bool entering = exact::dot(n, d) < 0.0f;
+      if (!entering) n = -n;
+      const float u1 = exact::rng_next(rng);                       // :256
+      exact::rng_skip(rng);                                        // :257 (drawn, unused)
+      bool transmitted;
+      float fresnel;
+      d = diel::interface(n, entering, d, u1, spec_w, diel_inv, diel_r0, &transmitted, &fresnel);
+      const float off = transmitted ? -a.ray_offset : a.ray_offset;
+      o = f3{fmaf_(off, n.x, pos.x), fmaf_(off, n.y, pos.y), fmaf_(off, n.z, pos.z)};
+      return seg + 1 >= a.max_segments;  // never absorbed (only builds without the early return get here on a last segment)
+    }
+  }
+  if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
+  o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
+  float st_, ct;
+  exact::sincos2pi(exact::rng_next(rng), st_, ct);                 // :256
+  float u = fmaf_(2.0f, exact::rng_next(rng), -1.0f);              // :257
+  float r = exact::sqrt_(fmaf_(-u, u, 1.0f));                      // :258
+  if constexpr (SPEC != 0) {
+    if (spec::is_specular(spec_w)) {
+      bool absorbed;
+      d = spec::lobe(n, d, r, ct, st_, u, spec::roughness(spec_w), &absorbed);
+      if (seg + 1 >= a.max_segments) return true;  // (only builds without the early return get here)
+      if (absorbed) acc = f3{0.f, 0.f, 0.f};
+      return absorbed;
+    }
+  }
+  d = exact::normalize(f3{fmaf_(r, ct, n.x), fmaf_(r, st_, n.y), n.z + u});  // :259-261
+  return seg + 1 >= a.max_segments;  // budget exhausted: the path returns its throughput (:270)
+}
+
+// shade_segment's TEX for with_mode3 (select.hpp): 2 the scene has textures and some of them a mip chain (the level table
+// exists), 1 textures without mips, 0 no textures
+inline int tex_mode(const TexView& tex) { return tex.records ? (tex.levels ? 2 : 1) : 0; }
+// shade_segment's SPEC: 2 some triangle's material is a dielectric, 1 some triangle's is specular and none a dielectric, 0 every
+// material is diffuse
+inline int spec_mode(int specular) { return specular >= 2 ? 2 : (specular == 1 ? 1 : 0); }
+
+}  // namespace
+}  // namespace rt

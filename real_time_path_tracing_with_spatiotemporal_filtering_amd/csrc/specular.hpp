@@ -1,5 +1,5 @@
 // specular.hpp — the specular bounce (rtpt_scene_set_materials_ext, RTPT_MAT_SPECULAR).  ONE definition, used by every kernel that
-// shades a hit (kernels.hip: shade_segment<..., SPEC = true>) and by the self test (rtpt_selftest_bounce).  Not reference
+// shades a hit (shade_segment.hpp: shade_segment<..., SPEC = 1>) and by the self test (rtpt_selftest_bounce).  Not reference
 // behaviour: the reference traces no reflection (its only reflect() is a highlight of the gradient shader).  A material is
 // diffuse or specular, never a mixture; no Fresnel term, no refraction here — a smooth dielectric is a third kind of material,
 // dielectric.hpp.

@@ -1,5 +1,5 @@
 // texture.hpp — the albedo-texture sampler (rtpt_scene_set_textures).  ONE definition, used by every kernel that shades a hit
-// (kernels.hip: shade_segment) and by the sampler self test (rtpt_selftest_texture).  Not reference behaviour: the reference
+// (shade_segment.hpp: shade_segment) and by the sampler self test (rtpt_selftest_texture).  Not reference behaviour: the reference
 // has no textures.  No image instructions, no LDS: plain 16-byte global loads of RGBA32F texels.
 //
 // The arithmetic, stated so that numpy float32 reproduces it bit for bit (the build has -ffp-contract=off: only the fmas

@@ -7,7 +7,7 @@ the lane utilisation of the node loop and of the leaf loop and what bounds it.
         python scripts/bvh_count.py [--frames 2] [--width 3840 --height 2160] [--out profiles/xyz.json]
 
 Per call of closest_hit_bvh and wave the kernel counts the trips of the node loop and of the leaf loop, the lanes active in
-each trip and the longest lane's trips (kernels.hip, RTPT_BVH_COUNT).  From the sums:
+each trip and the longest lane's trips (closest_hit.hpp, RTPT_BVH_COUNT).  From the sums:
     util        = lane-trips / (64 x trips)                    what SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU) sees
     length_cap  = lane-trips / (64 x sum of the longest lane)  the bound set by unequal work inside a wave
                                                                 (and by partly filled waves): no reordering of one

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two copies of csrc/, kernel by kernel.
 
-    scripts/device_asm_diff.py <parent csrc> <new csrc> [-o summary.txt] [-j jobs] [-D macro ...]
+    scripts/device_asm_diff.py <parent csrc> <new csrc> [--by-kernel] [-o summary.txt] [-j jobs] [-D macro ...]
 
 For a refactor that must not change what the GPU executes.  Every .hip file of the new directory is compiled in both
 directories with the Makefile's own HIPCC / CXXFLAGS plus `--cuda-device-only -S` (no GPU needed), and the two assembly
@@ -12,6 +12,13 @@ by kernel name.  Three things are normalised, nothing else:
   * the numbering of `.LBB<n>_<m>` and `.Lfunc_begin<n>` / `.Lfunc_end<n>` (n = order of instantiation in the file),
   * comments (`;` to the end of the line) and column padding.
 Prints one line per file (kernels compared, kernels equal) and exits 1 if any set of symbols or any text differs.
+
+--by-kernel: for a refactor that moves kernels between files.  Every .hip file of EITHER directory is compiled where it lies,
+the kernels, the other device functions and the metadata entries of a side are pooled over its files, and the two pools are
+compared by name, with the same normalisations.  A name that two files of one side define cannot be pooled (the pool would hold
+one of them): it is compared as `name [file]`, file by file as without the option, and counted in the side's line — a library's
+template kernels that two files instantiate (rocprim's, in the two tree builders).  Such a kernel that also moved between files
+therefore shows as "only in".  Prints one line per side (files, kernels) and one for the comparison.
 """
 import argparse
 import concurrent.futures
@@ -112,6 +119,46 @@ def compare(what, old, new, report):
     return equal
 
 
+def pooled(asms):
+    """(kernels, other device functions, metadata entries, names in two files) of one side, name -> text, over all of its files"""
+    where = {}
+    per_file = {f: (functions(asms[f]), metadata(asms[f])) for f in sorted(asms)}
+    for f, (fns, _) in per_file.items():
+        for n in fns:
+            where.setdefault(n, []).append(f)
+    twice = {n for n, fs in where.items() if len(fs) > 1}
+    key = lambda n, f: f"{n} [{f}]" if n in twice else n
+    kern, plain, meta = {}, {}, {}
+    for f, (fns, md) in per_file.items():
+        for n, (t, k) in fns.items():
+            (kern if k else plain)[key(n, f)] = t
+        for n, t in md.items():
+            meta[key(n, f)] = t
+    return kern, plain, meta, len(twice)
+
+
+def by_kernel(a):
+    sides = {"parent": a.parent, "new": a.new}
+    with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
+        jobs = {side: {f: pool.submit(device_asm, d, f, a.defines, tmp, side) for f in sorted(os.listdir(d)) if f.endswith(".hip")}
+                for side, d in sides.items()}
+        asms = {side: {f: j.result() for f, j in fs.items()} for side, fs in jobs.items()}
+    report, summary = [], []
+    (ko, po, mo, to), (kn, pn, mn, tn) = (pooled(asms[side]) for side in ("parent", "new"))
+    for side, k, twice in (("parent", ko, to), ("new", kn, tn)):
+        summary.append(f"{side}: {len(asms[side])} files, {len(k)} kernels" + (f" ({twice} names in two files, compared per file)" if twice else ""))
+    k_eq = compare("kernel", ko, kn, report)
+    p_eq = compare("device function", po, pn, report)
+    m_eq = compare("metadata entry", mo, mn, report)
+    line = f"by kernel: kernels compared {len(set(ko) | set(kn))}, equal {k_eq}; metadata entries {len(set(mo) | set(mn))}, equal {m_eq}"
+    if po or pn:
+        line += f"; other device functions {len(set(po) | set(pn))}, equal {p_eq}"
+    summary.append(line)
+    if report:
+        print("\n".join(report))
+    return summary, not report
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("parent")
@@ -119,7 +166,15 @@ def main():
     ap.add_argument("-o", "--out", help="also write the summary lines to this file")
     ap.add_argument("-j", "--jobs", type=int, default=4)
     ap.add_argument("-D", dest="defines", action="append", default=[], help="macro for both sides (e.g. RTPT_AB_VARIANTS=1)")
+    ap.add_argument("--by-kernel", action="store_true", help="pool the kernels of each side over its files and compare by kernel name")
     a = ap.parse_args()
+    if a.by_kernel:
+        summary, ok = by_kernel(a)
+        text = "\n".join(summary) + "\n" + ("all equal\n" if ok else "DIFFERENCES\n")
+        print(text, end="")
+        if a.out:
+            open(a.out, "w").write(text)
+        return 0 if ok else 1
     names = sorted(f for f in os.listdir(a.new) if f.endswith(".hip"))
     missing = [f for f in sorted(os.listdir(a.parent)) if f.endswith(".hip") and f not in names]
     summary, ok = [], not missing

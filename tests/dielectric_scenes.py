@@ -7,7 +7,7 @@ dot as well (fma below: exact, where texture_scenes.fma32 rounds twice), the squ
 two divisions of the record in numpy float32 (all correctly rounded, like the device's).  refract64 is the same interface in
 float64 libm from the float32 operands as they are.
 
-walk() restates K2 for one sample per pixel, materials and no textures: primary-ray generation and shade_segment (csrc/kernels.hip)
+walk() restates K2 for one sample per pixel, materials and no textures: primary-ray generation and shade_segment (csrc/pathtrace_tile.hpp, csrc/shade_segment.hpp)
 in numpy float32 over the contract functions, with oracle_closest_hit through ctypes for t, b1 and b2 of every ray.  The oracle
 knows no dielectric, so walk() is the reference of the dielectric frames — after tests/test_dielectric_cpu.py has held it to
 oracle.raytrace_ext on scenes without one, IMAGE and HIT_ID bit for bit."""

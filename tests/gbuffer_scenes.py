@@ -1,7 +1,7 @@
 """Seeded generators of adversarial inputs for what runs between closest hit and the filter (numpy only; no fixture, no GPU):
 
   cull scenes   at most 64 triangles, the scenes whose primary rays go through the padded 16-bit screen rectangles of
-                screen_bounds() (csrc/api_context.hip) and span_candidates() / closest_hit_brute_set() (csrc/kernels.hip):
+                screen_bounds() (csrc/api_context.hip) and span_candidates() / closest_hit_brute_set() (csrc/closest_hit.hpp):
                 many SMALL triangles in a slab, so that a 16 x 4 pixel block meets a few rectangles out of dozens, a backdrop
                 that makes every pixel hit (a dropped candidate changes an id, it does not turn into background), and named
                 members placed against the rules of screen_bounds for the camera at EYE0 looking down -z;
@@ -26,7 +26,7 @@ FOVY = 0.4                                                            # the refe
 EYE0 = (0.1, -0.05, 6.0)      # the camera the named members are placed for: looks down -z, its plane is z = 6
 SLAB = ((-4.5, 4.5), (-1.1, 1.1), (-1.0, 1.0))                        # where the small triangles are scattered
 EXTENT = 9.0                                                          # the slab's longest side
-BLOCK = (16, 4)                                                       # the pixels a wave starts on (kernels.hip: kWaveW x kWaveH)
+BLOCK = (16, 4)                                                       # the pixels a wave starts on (closest_hit.hpp: kWaveW x kWaveH)
 
 # ids (triangle index + 1) of the named members of a cull scene with T >= 40
 (ID_BACKDROP_A, ID_BACKDROP_B, ID_STRADDLE, ID_BEHIND, ID_NEAR_BOUNDED, ID_NEAR_UNBOUNDED, ID_SLIVER, ID_CLOSE, ID_BOUNDARY,

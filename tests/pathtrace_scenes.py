@@ -1,6 +1,6 @@
 """Seeded generators of adversarial scenes for everything the path-trace kernels (K2) do after the first hit (numpy only; no
 fixture, no GPU): shade_segment, the per-segment compaction, the hand-over queue between the tile kernel and k_pathtrace_queue,
-the accumulators of samples_per_pixel > 1 and the ray counter (csrc/kernels.hip).  Every scene carries its K2 camera, its
+the accumulators of samples_per_pixel > 1 and the ray counter (csrc/pathtrace_tile.hpp, csrc/kernels.hip).  Every scene carries its K2 camera, its
 light and an optional material table, and exists in up to three forms:
 
   small   at most 64 triangles: the wave-uniform brute-force kernels (k_pathtrace_small / k_gbuffer_pathtrace_small);
@@ -36,7 +36,7 @@ F32 = np.float32
 SEGMENTS = 9                                  # the GPU test's max_segments outside its window cases
 EDGE_SHAPES = ((65, 7), (1, 1))
 RESIZED_SHAPE = (197, 45)                     # the larger frame of the GPU test's resize
-TILE = (64, 4)                                # pathtrace_tile's pixels; a wave owns 16 x 4 of them (tile_pixel, kernels.hip)
+TILE = (64, 4)                                # pathtrace_tile's pixels; a wave owns 16 x 4 of them (tile_pixel, closest_hit.hpp)
 WAVE_W = 16
 FORMS = ("small", "pairs", "odd")
 LIGHT_FAR = (300.0, 5000.0, -400.0)           # the "closed" scenes' light

@@ -4,7 +4,7 @@ passes the Cornell box, one heightfield and one soup from cameras that look at t
 
   cull scenes    at most 64 triangles: the primary rays of K0 and K2 test only the triangles whose padded 16-bit screen rectangle
                  (screen_bounds, csrc/api_context.hip) meets the 16 x 4 pixel block of their wave (span_candidates,
-                 closest_hit_brute_set, csrc/kernels.hip).  rtpt_selftest_trace never takes that path.  A rectangle one pixel too
+                 closest_hit_brute_set, csrc/closest_hit.hpp).  rtpt_selftest_trace never takes that path.  A rectangle one pixel too
                  tight changes an id (the backdrop is behind every pixel), RTPT_FLAG_FORCE_BVH runs the same frames without it.
   K1             alone on injected ids / world positions / previous LUTs (k_gradient), as the first pass after an upload, a
                  re-upload or moved instances (it has to build the per-id tables it reads), and inside the K0 + K1 and the

@@ -1,4 +1,4 @@
-"""What K2's shading leaves out (csrc/kernels.hip: shade_segment, ray_hits_light, the primary ray of pathtrace_tile)
+"""What K2's shading leaves out (csrc/shade_segment.hpp: shade_segment, ray_hits_light; csrc/pathtrace_tile.hpp: the primary ray of pathtrace_tile)
 must not show in any stored value: the last segment of a path returns before its bounce, the light test takes the sign of its
 quotient from exact::quotient_positive, the primary ray's two divisions share a reciprocal.
 

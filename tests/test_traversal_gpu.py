@@ -1,7 +1,7 @@
 """Closest hit on adversarial geometry: the device traversal (brute force, BVH over triangles, BVH over fan pairs, a stack
 that spills) against the oracle's brute force, bit for bit.
 
-D4 (kernels.hip, bvh.hpp): the winner is the minimum over (t, id) of ONE ray-triangle routine, so no structure that
+D4 (closest_hit.hpp, bvh.hpp): the winner is the minimum over (t, id) of ONE ray-triangle routine, so no structure that
 enumerates the candidates may change it.  The other GPU tests of that rule all use axis-aligned box walls near the
 origin; the scenes here are soups in every orientation, degenerate and flat triangles, coordinates far from the origin,
 scales whose triple products go subnormal or overflow, slivers, duplicates at other ids, and non-planar fan pairs.  The
