@@ -531,7 +531,8 @@ int rtpt_debug_reproj_info(rtpt_ctx* ctx, uint64_t out[4]);
  * complete only after a call that flushes: ask rtpt_plane_ptr again (or call rtpt_sync) after rtpt_end_frame before
  * reading it on the device.  Every plane, the ray count and the finished frame equal those of a context that launches
  * the pass where it is recorded.  RTPT_NO_FINAL_DEFER=1 in the environment of rtpt_create turns it off;
- * RTPT_FINAL_FRONT=<workgroups per CU>[,<percent of the pass's work>] sets how much of the pass runs in front of the tiles.
+ * RTPT_FINAL_FRONT=<workgroups per CU, or from 8 on workgroups in all>[,<percent of the pass's work>] sets how much of the
+ * pass runs in front of the tiles (built in: one workgroup per CU; all of the pass on a frame as large as 4K, 75 % on a small one).
  * out: [0] passes recorded instead of launched, [1] of those launched inside a tracing launch, [2] launched alone,
  * [3] bytes of the fourth colour buffer (0 until the first such launch). */
 int rtpt_debug_defer_info(rtpt_ctx* ctx, uint64_t out[4]);

@@ -58,7 +58,7 @@ __device__ unsigned long long g_bvh_octant[8][3];
 // workgroup of the last launch of a kernel on the 100 MHz wall clock, and where it ran (HW_ID, XCC_ID).
 #if RTPT_TILE_TIMELINE
 constexpr uint32_t kTimelineMax = 1u << 16;
-__device__ unsigned long long g_timeline[2][kTimelineMax][3];  // [kernel: 0 K0, 1 K2][workgroup]{start, end, hw}
+__device__ unsigned long long g_timeline[3][kTimelineMax][3];  // [kernel: 0 K0, 1 K2, 2 filter workgroups of k_pathtrace_final][workgroup]{start, end, hw}
 __device__ uint32_t g_tile_order[kTimelineMax];  // experiment: K2 workgroup b takes tile g_tile_order[b] (by * gx + bx); see rtpt_debug_tile_order
 __device__ uint32_t g_tile_order_n;              // 0: the built-in order
 struct TimelineScope {
@@ -75,14 +75,33 @@ struct TimelineScope {
     }
   }
 };
+// a filter workgroup of the launch that carries a final pass (k_pathtrace_final): record `block` of kernel 2 (the front group's
+// workgroups first, then the tail group's), its role (final_split.hpp: kFinalRole*) in bits 48.. of the hw word.  A plain
+// store per workgroup and no barrier, as experiments/span_instrumentation.inc does for the filter's own launches; a start of 0
+// is a record no launch has written.
+struct FilterTimelineScope {
+  unsigned long long t0;
+  uint32_t role, b;
+  __device__ FilterTimelineScope(uint32_t role_, uint32_t block) : t0(wall_clock64()), role(role_), b(block) {}
+  __device__ ~FilterTimelineScope() {
+    if (threadIdx.x == 0 && threadIdx.y == 0 && b < kTimelineMax) {
+      g_timeline[2][b][0] = t0;
+      g_timeline[2][b][1] = wall_clock64();
+      g_timeline[2][b][2] = (static_cast<unsigned long long>(role) << 48) |
+                            (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11))) << 32) |
+                            __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
+    }
+  }
+};
 #endif
 
 #endif  // RTPT_INSTR_DEVICE
 #if defined(RTPT_INSTR_HOST)
 #if RTPT_TILE_TIMELINE
-// timeline build only: {start, end, hw} of the first n workgroups of the last K0 (kernel 0) / K2 (kernel 1) launch
+// timeline build only: {start, end, hw} of the first n workgroups of the last K0 (kernel 0) / K2 (kernel 1) launch, or of the
+// filter workgroups of the last tracing launch that carried a final pass (kernel 2)
 extern "C" __attribute__((visibility("default"))) int rtpt_debug_timeline(int kernel, unsigned long long* out, uint32_t n) {
-  if (kernel < 0 || kernel > 1 || n > kTimelineMax) return -1;
+  if (kernel < 0 || kernel > 2 || n > kTimelineMax) return -1;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_timeline), sizeof(unsigned long long) * 3 * n,
                              sizeof(unsigned long long) * 3 * kTimelineMax * kernel) == hipSuccess ? 0 : -1;
 }

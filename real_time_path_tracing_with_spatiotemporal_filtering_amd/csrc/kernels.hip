@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "atrous_comb.hpp"
+#include "final_split.hpp"
 #include "pathtrace_tile.hpp"
 #include "select.hpp"
 
@@ -180,18 +181,14 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
 
 // K2 of frame n + 1 and the final filter pass of frame n in one launch (api_passes.hip: DeferredFinal).  The trace is bound by VALU
 // issue and touches next to no memory, the final pass by HBM; neither reads what the other writes (DESIGN §4 has the table), and
-// as launches of their own they never share the machine.  One grid, three runs of workgroups in dispatch order: sp.n_front filter
-// workgroups, which run beside the body of the trace; the tracing tiles; sp.n_tail filter workgroups, which start as the last
-// tiles drain.  The filter workgroups are the comb kernel's (atrous_comb.hpp: comb_items); the front group owns the first
+// as launches of their own they never share the machine.  One grid, three runs of workgroups in dispatch order (final_split.hpp
+// states the layout and the role of a workgroup, once): sp.n_front filter workgroups, which run beside the body of the trace; the
+// tracing tiles; sp.n_tail filter workgroups, which start as the last tiles drain (none by default: the front group owns the
+// whole list).  The filter workgroups are the comb kernel's (atrous_comb.hpp: comb_items); the front group owns the first
 // sp.front_items items of the list and the tail group the rest, so every item has one owner and no workgroup waits for another.
 // The launch's dynamic LDS is the larger of the two bodies': a staged row of kFinalRoleCw cells keeps it at 8 workgroups per CU.
 // Only the pass that loads its reprojected pixels (RLOAD) is instantiated: at this kernel's 64 VGPRs it needs no scratch, the
 // reprojecting pass would spill 48 registers per lane — it runs as the launch of its own (atrous_final_role).
-struct FinalSplit {
-  uint32_t n_front, n_tail;      // workgroups, multiples of 8 (0: the group owns no item)
-  uint32_t front_items, items;   // of the final pass's work list
-  uint32_t tiles_x;              // the tile grid is tiles_x x PathtraceArgs::tiles_y
-};
 // (CW, the staged row: a template like every other user of the dynamic LDS array `stack`, so that the array is still first
 // emitted through k_gbuffer's declaration — a plain kernel here comes first and hands its 16-byte alignment to the one symbol
 // all of them share, which moves the dynamic LDS of every kernel of this file from byte 24 to 32)
@@ -200,15 +197,17 @@ __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_final(PathtraceArgs a, TexView tex, AtrousArgs f, FinalSplit sp) {
   static_assert(kPtThreads == kShThreads && kPtRows == kShWaves, "the two bodies share the workgroup shape");
-  const uint32_t n_tiles = sp.tiles_x * a.tiles_y, t = blockIdx.x - sp.n_front;
-  if (t < n_tiles) {  // (unsigned: a front workgroup wraps past it)
-    pathtrace_tile<0, true, false, false, 0, 0, 1>(a, tex, t, sp.tiles_x, a.tiles_y);
+  const FinalRole r = final_role(sp, blockIdx.x);
+  if (r.role == kFinalRoleTile) {
+    pathtrace_tile<0, true, false, false, 0, 0, 1>(a, tex, r.index, sp.tiles_x, a.tiles_y);
   } else {
     extern __shared__ __attribute__((aligned(16))) unsigned char final_lds[];
-    const bool front = blockIdx.x < sp.n_front;
-    comb_items<CW, true, false, false, 1, false, false, true, true>(f, final_lds, front ? blockIdx.x : t - n_tiles,
-                                                                       front ? sp.n_front : sp.n_tail, front ? 0u : sp.front_items,
-                                                                       front ? sp.front_items : sp.items);
+    const bool front = r.role == kFinalRoleFront;
+#if RTPT_TILE_TIMELINE
+    FilterTimelineScope tl_(r.role, front ? r.index : sp.n_front + r.index);
+#endif
+    comb_items<CW, true, false, false, 1, false, false, true, true>(f, final_lds, r.index, front ? sp.n_front : sp.n_tail,
+                                                                       front ? 0u : sp.front_items, front ? sp.front_items : sp.items);
   }
 }
 
@@ -362,24 +361,12 @@ uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
   return gx * ((a.g.y1 - a.g.y0 + tr - 1) / tr + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0));
 }
 // the filter workgroups of a launch that carries the final pass `f` (atrous_final_role finished it): how many in front of and
-// behind the tiles, and where the work list is cut between them
-static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const FilterPolicy& pol, uint32_t tiles_x) {
-  const uint32_t n_cu = a.n_cu > 0 ? static_cast<uint32_t>(a.n_cu) : 256u, cu8 = (n_cu + 7u) / 8u;
+// behind the tiles, and where the work list is cut between them (final_split.hpp)
+static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const FilterPolicy& pol, uint32_t tiles_x, uint32_t tiles_y) {
+  const uint32_t n_cu = a.n_cu > 0 ? static_cast<uint32_t>(a.n_cu) : 256u;
   const uint32_t per_cu = static_cast<uint32_t>(kPtWaves * 4 / kShWaves);  // resident workgroups of either kind
-  FinalSplit sp;
-  sp.tiles_x = tiles_x;
-  sp.items = static_cast<uint32_t>(f.tiles_x) * static_cast<uint32_t>(f.tiles_y) * static_cast<uint32_t>(f.stride);
-  auto clamp = [](int v, int hi) { return static_cast<uint32_t>(v < 0 ? 0 : (v > hi ? hi : v)); };
-  const uint32_t front_wg = clamp(pol.final_front, static_cast<int>(per_cu) - 1), share = clamp(pol.final_front_share, 100);
-  sp.front_items = front_wg ? static_cast<uint32_t>(static_cast<uint64_t>(sp.items) * share / 100u) : 0u;
-  // a group takes every slot it may hold, but no more workgroups than an XCD's eighth of its range has items
-  auto group = [&](uint32_t items, uint32_t slots_per_xcd) {
-    const uint32_t per_xcd = (items + 7u) / 8u;
-    return items ? 8u * (per_xcd < slots_per_xcd ? per_xcd : slots_per_xcd) : 0u;
-  };
-  sp.n_front = group(sp.front_items, cu8 * front_wg);
-  sp.n_tail = group(sp.items - sp.front_items, cu8 * (per_cu - front_wg));
-  return sp;
+  const uint32_t items = static_cast<uint32_t>(f.tiles_x) * static_cast<uint32_t>(f.tiles_y) * static_cast<uint32_t>(f.stride);
+  return final_split_plan(items, tiles_x, tiles_y, n_cu, per_cu, pol.final_front, pol.final_front_share);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
                       const FilterPolicy* pol) {
@@ -411,8 +398,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   b.q_out_count = split ? a.queue_count : nullptr;
   if (split) (void)hipMemsetAsync(a.queue_count, 0, 2 * kPathQueues * sizeof(uint32_t), s);
   if (fin) {
-    const FinalSplit sp = final_split(a, *fin, *pol, grid.x);
-    const dim3 grid1(sp.n_front + grid.x * tiles_y + sp.n_tail);
+    const FinalSplit sp = final_split(a, *fin, *pol, grid.x, tiles_y);
+    const dim3 grid1(final_grid(sp));
     hipLaunchKernelGGL(k_pathtrace_final<kFinalRoleCw>, grid1, block, dyn, s, b, tex, *fin, sp);
   } else
 #if RTPT_AB_VARIANTS

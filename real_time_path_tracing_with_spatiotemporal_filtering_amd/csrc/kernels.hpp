@@ -373,11 +373,19 @@ struct FilterPolicy {
   // (atrous_chain.hip: chain_segments), "a" or "a,b": a for four workgroups per CU, b for two or three; -1 = the built-in values
   int chain_skew = -1, chain_skew2 = -1;
   int chain_bw = 0;         // RTPT_CHAIN_BW: columns a strip of the pair (1,2) stores (A/B; 0 = the widest, 124)
-  // RTPT_FINAL_FRONT=<workgroups per CU>[,<percent of the work list>]: the filter workgroups of a tracing launch that carries the
-  // previous frame's final pass (kernels.hip: k_pathtrace_final) dispatched in FRONT of the tiles, and the share of the list they
-  // own; the rest runs behind the tiles.  0 = behind only.  4K frame at rest, one job (profiles/r17_final_defer_ab.txt): parent
-  // 0.620-0.624 ms; 0: 0.620; 1 per CU owning 25 / 50 / 75 %: 0.609 / 0.601 / 0.592; 2 per CU: 0.611 / 0.606 / 0.594
-  int final_front = 1, final_front_share = 75;
+  // RTPT_FINAL_FRONT=<front>[,<percent of the work list>]: the filter workgroups of a tracing launch
+  // that carries the previous frame's final pass (kernels.hip: k_pathtrace_final; final_split.hpp has the layout).  <front>: the
+  // group dispatched in FRONT of the tiles, 1 .. 7 workgroups per CU or, from 8 on, a total number of workgroups (a multiple of
+  // 8); 0 = none.  The second field is the percent of the list the front group owns; the rest runs behind the tiles, where its
+  // workgroups start when the launch is all but over.  Left out (-1): the whole list on a frame as large as 4K, 75 % on one
+  // as small as 1080p (final_split.hpp: kFinalWholeListItems).  Built-in: 1 per CU.  4K frame at rest, one job
+  // (profiles/r19_final_place_ab.txt): parent (1 per CU, 75 %) 0.5935-0.5945 ms; whole list with 128 / 192 / 256 / 512
+  // workgroups in front 0.678 / 0.586 / 0.587 / 0.587 (128 workgroups outlast the tiles; 192 and 256 differ by less than the
+  // spread of a setting, and 256 leaves the group 160 us of the launch to spare where 192 leaves 85); 90 / 80 / 70 % in front
+  // of 256 with the rest behind the tiles 0.590 / 0.595 / 0.600.  1080p: parent 0.1705-0.1712; 100 / 90 / 80 / 75 % 0.1728 /
+  // 0.1722 / 0.1711 / 0.1712.  A third group in front of the sky tiles (the last three eighths dispatched) recovered 3-5 us of
+  // what the tail loses at 4K and stayed behind the whole list in front; it was removed.
+  int final_front = 1, final_front_share = -1;
 };
 void launch_atrous_chain(const AtrousArgs& a, int levels, bool final_pass, const FilterPolicy& pol, hipStream_t s);
 bool atrous_chain_supported(int k0, int levels, uint32_t n_tris);

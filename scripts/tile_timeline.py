@@ -4,6 +4,9 @@ scripts/build_variant.sh timeline -DRTPT_TILE_TIMELINE=1): how many workgroups a
 workgroup lives by the time it starts, where the launch's tail is.
 
     RTPT_LIB_PATH=.../variants/librtpt_timeline.so python scripts/tile_timeline.py [--strip 3/8] [--workload 4k] [--out f.json]
+
+--fused-final: the tracing launch of a frame at rest, which carries the final filter pass of the frame before it
+(k_pathtrace_final) — tiles and filter workgroups on one clock, by kind; RTPT_FINAL_FRONT sizes the filter groups.
 """
 import argparse
 import ctypes as C
@@ -17,8 +20,78 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def fused_final_report(fn, W, rows, bucket_us, res):
+    """The tracing launch that carries the previous frame's final pass (k_pathtrace_final), tiles and filter workgroups on one
+    clock: resident workgroups per bucket by kind, when each filter group's last workgroup ends, where the sky phase starts (the
+    first dispatch-order eighth of the tiles whose mean lifetime is below a quarter of the first eighth's), the launch span."""
+    gx, gy = (W + 63) // 64, (rows + 3) // 4
+    nb = gx * gy
+    buf = (C.c_ulonglong * (3 * nb))()
+    assert fn(1, buf, nb) == 0
+    t = np.frombuffer(buf, dtype=np.uint64).reshape(nb, 3).astype(np.int64)
+    nf = 1 << 16
+    fbuf = (C.c_ulonglong * (3 * nf))()
+    assert fn(2, fbuf, nf) == 0
+    f = np.frombuffer(fbuf, dtype=np.uint64).reshape(nf, 3)
+    role = (f[:, 2] >> np.uint64(48)).astype(np.int64)
+    f = f.astype(np.int64)
+    # records of the launch the tiles belong to (a record keeps what an earlier launch with more filter workgroups left there)
+    lo, hi = t[:, 0].min() - 100000, t[:, 1].max() + 100000
+    live = (f[:, 0] != 0) & (f[:, 0] >= lo) & (f[:, 0] <= hi)
+    if not live.any():
+        print("fused launch: the last tracing launch carried no final pass")
+        return
+    base = min(t[:, 0].min(), f[live, 0].min())
+    end = max(t[:, 1].max(), f[live, 1].max())
+    span = (end - base) / 100.0
+    kinds = [("tiles", t[:, 0], t[:, 1])]
+    for r, name in ((1, "front"), (2, "tail")):
+        m = live & (role == r)
+        if m.any():
+            kinds.append((name, f[m, 0], f[m, 1]))
+    print(f"fused launch (tracing tiles of frame n + 1, final pass of frame n): span {span:.1f} us; " +
+          ", ".join(f"{len(s)} {name}" for name, s, _ in kinds))
+    nbk = int(span / bucket_us) + 1
+    print(f"   resident per {bucket_us:.0f} us (" + " + ".join(name for name, _, _ in kinds) + "):")
+    rows_out = []
+    for b in range(nbk):
+        m = base + (b + 0.5) * bucket_us * 100.0
+        rows_out.append([int(np.count_nonzero((s <= m) & (e > m))) for _, s, e in kinds])
+    print("   " + " ".join("+".join(str(v) for v in r) for r in rows_out))
+    out = {"span_us": float(span), "kinds": [k[0] for k in kinds], "resident": rows_out, "bucket_us": bucket_us}
+    for name, s, e in kinds[1:]:
+        lt = (e - s) / 100.0
+        print(f"   {name} group: first start {(s.min() - base) / 100.0:.1f} us, last start {(s.max() - base) / 100.0:.1f} us, first end "
+              f"{(e.min() - base) / 100.0:.1f} us, last end {(e.max() - base) / 100.0:.1f} us; lifetime min {lt.min():.1f} median {np.median(lt):.1f} max {lt.max():.1f} us")
+        out[name] = {"workgroups": int(len(s)), "first_start_us": float((s.min() - base) / 100.0), "last_end_us": float((e.max() - base) / 100.0)}
+    print(f"   tiles: first start {(t[:, 0].min() - base) / 100.0:.1f} us, last start {(t[:, 0].max() - base) / 100.0:.1f} us, last end {(t[:, 1].max() - base) / 100.0:.1f} us")
+    # the tiles in dispatch order: column by column from the middle outwards (csrc/pathtrace_tile.hpp); the
+    # records are indexed by tile (by * gx + bx)
+    order = []
+    for col in range(gx):
+        bx = (gx - 1) // 2 + (col + 1) // 2 if col & 1 else (gx - 1) // 2 - col // 2
+        order.extend(by * gx + bx for by in range(gy))
+    order = np.array(order)
+    s_us, dur = (t[order, 0] - base) / 100.0, (t[order, 1] - t[order, 0]) / 100.0
+    eighths = np.array_split(np.arange(nb), 8)
+    means = [dur[q].mean() for q in eighths]
+    print("   tiles by dispatch order (eighths): first start us / mean lifetime us: " + " ".join(f"{s_us[q].min():.0f}/{m:.1f}" for q, m in zip(eighths, means)))
+    sky = next((i for i, m in enumerate(means) if m < means[0] / 4), None)
+    if sky is None:
+        print("   sky phase: no eighth's mean lifetime is below a quarter of the first eighth's")
+    else:
+        q = eighths[sky]
+        print(f"   sky phase: from eighth {sky} (tile {q[0]} of {nb} in dispatch order, {100.0 * q[0] / nb:.1f} % of the list), first start {s_us[q].min():.1f} us; "
+              f"from there {nb - q[0]} tiles, mean lifetime {dur[q[0]:].mean():.1f} us, the launch has {span - s_us[q].min():.1f} us left")
+        out["sky"] = {"eighth": sky, "tile": int(q[0]), "start_us": float(s_us[q].min())}
+    res["fused_final"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fused-final", action="store_true",
+                    help="report the last tracing launch as the one that carries the previous frame's final pass (frames at rest; "
+                         "RTPT_FINAL_FRONT places the filter workgroups) instead of the frame's separate launches")
     ap.add_argument("--strip", default=None, metavar="R/N")
     ap.add_argument("--workload", default="4k")
     ap.add_argument("--splits", default=None, metavar="0,A,...,H", help="with --strip R/N: unequal strips (strips.StripPlan.splits)")
@@ -50,6 +123,14 @@ def main():
     for _ in range(args.frames):
         app.drawScene(())
     app.backend.ctx.sync()
+    if args.fused_final:   # the last frame's tracing launch carried the final pass of the frame before it; nothing has run since
+        res = {"workload": args.workload, "final_front": os.environ.get("RTPT_FINAL_FRONT")}
+        rows_of = app.plan.raytrace_rows()
+        print(f"RTPT_FINAL_FRONT={res['final_front']}")
+        fused_final_report(fn, wl["width"], rows_of[1] - rows_of[0], args.bucket_us, res)
+        if args.out:
+            json.dump(res, open(args.out, "w"))
+        return
     # the filter's launches (atrous_chain.hip / atrous.hip, experiments/span_instrumentation.inc) fold every workgroup of every
     # launch since the last clear: re-arm them, draw ONE frame, and every launch of that frame sits on one clock
     spans, reader_names = [], {}
