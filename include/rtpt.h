@@ -537,6 +537,17 @@ int rtpt_debug_reproj_info(rtpt_ctx* ctx, uint64_t out[4]);
  * [3] bytes of the fourth colour buffer (0 until the first such launch). */
 int rtpt_debug_defer_info(rtpt_ctx* ctx, uint64_t out[4]);
 
+/* Empty tile columns (additive: RTPT_ABI_VERSION stays 5).  rtpt_raytrace dispatches its 64 x 4 tiles column by column from
+ * the middle of the frame outwards, and for a scene of at most 64 triangles it has every triangle's padded screen bounds.  In a
+ * launch that carries a deferred final pass (above), the columns at the end of that order which no triangle's bounds reach within
+ * the traced rows are not one workgroup per tile: a workgroup takes a run of R vertically consecutive tiles of one column and
+ * traces their primary rays only, which end on the light or in the sky.  A column without triangles in front of a reached one
+ * stays a column of tiles.  Every plane and the ray count equal those of a context without runs.  RTPT_EMPTY_RUN=<R> in the
+ * environment of rtpt_create sets R; 0 turns the runs off.
+ * out, for the last rtpt_raytrace launch: [0] tile columns served one workgroup per tile (every column of a launch without
+ * runs), [1] run workgroups, [2] tiles served in runs, [3] R. */
+int rtpt_debug_empty_run_info(rtpt_ctx* ctx, uint64_t out[4]);
+
 /* ---- per-frame passes, one call per reference dispatch ----------------------------------- */
 
 /* drawVisbilityBuffer (main.cpp:1187-1199; visibility.{vert,geom,frag}.glsl): id, world

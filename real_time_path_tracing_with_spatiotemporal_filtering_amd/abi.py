@@ -147,7 +147,7 @@ SYMBOLS = [
     "rtpt_scene_set_textures", "rtpt_selftest_texture", "rtpt_util_load_obj_texcoords", "rtpt_util_load_obj_map_kd",
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
-    "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract",
+    "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -218,6 +218,7 @@ def load() -> C.CDLL:
         "rtpt_debug_reuse_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_reproj_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_defer_info": [vp, C.POINTER(C.c_uint64 * 4)],
+        "rtpt_debug_empty_run_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_scene_set_instances": [vp, vp, u32],
         "rtpt_debug_upload_info": [vp, C.POINTER(C.c_uint64 * 4)],
         "rtpt_debug_live_device_bytes": [C.POINTER(C.c_uint64)],
@@ -488,6 +489,12 @@ class Context:
         out = (C.c_uint64 * 4)()
         _check(self._lib.rtpt_debug_defer_info(self._h, C.byref(out)))
         return dict(zip(("recorded", "launched_in_trace", "launched_alone", "spare_bytes"), (int(v) for v in out)))
+
+    def empty_run_info(self) -> dict:
+        """the last tracing launch's tile columns that no triangle reaches, served in runs (rtpt_debug_empty_run_info)"""
+        out = (C.c_uint64 * 4)()
+        _check(self._lib.rtpt_debug_empty_run_info(self._h, C.byref(out)))
+        return dict(zip(("full_columns", "run_workgroups", "run_tiles", "run_len"), (int(v) for v in out)))
 
     def set_materials(self, tri_material: np.ndarray | None, materials: np.ndarray | None):
         """per-triangle material indices + (Kd, Ke) rows; None returns to the reference's normal-keyed colours"""

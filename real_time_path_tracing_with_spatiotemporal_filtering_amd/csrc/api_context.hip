@@ -396,6 +396,7 @@ int rtpt_create(const rtpt_config* cfg, rtpt_ctx** out) {
     c->filter_policy.final_front = std::atoi(v);
     if (const char* comma = std::strchr(v, ',')) c->filter_policy.final_front_share = std::atoi(comma + 1);
   }
+  if (const char* v = std::getenv("RTPT_EMPTY_RUN")) c->filter_policy.empty_run = std::max(0, std::atoi(v));
   if (const char* v = std::getenv("RTPT_CHAIN_SW")) c->filter_policy.chain_sw = std::atoi(v);
   if (const char* v = std::getenv("RTPT_CHAIN_SW_G1")) c->filter_policy.chain_sw_g1 = std::atoi(v);
   if (const char* v = std::getenv("RTPT_CHAIN_SW_G3")) c->filter_policy.chain_sw_g3 = std::atoi(v);
@@ -597,6 +598,15 @@ int rtpt_debug_defer_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 3; i++) out[i] = c->defer_info[i];
   out[3] = c->color[3].bytes;
+  return RTPT_OK;
+}
+
+// the last rtpt_raytrace launch, observed: [0] tile columns served one workgroup per tile, [1] run workgroups, [2] tiles served in
+// runs, [3] the tiles a run workgroup takes at most (RTPT_EMPTY_RUN)
+int rtpt_debug_empty_run_info(rtpt_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  for (int i = 0; i < 3; i++) out[i] = c->empty_run_info[i];
+  out[3] = static_cast<uint64_t>(c->filter_policy.empty_run);
   return RTPT_OK;
 }
 

@@ -302,6 +302,7 @@ struct rtpt_ctx {
   bool deferred_valid = false;
   DeferredFinal deferred;
   uint64_t defer_info[4] = {0, 0, 0, 0};  // rtpt_debug_defer_info
+  uint32_t empty_run_info[3] = {0, 0, 0};  // rtpt_debug_empty_run_info: the last tracing launch
   // K3 iterations recorded by rtpt_temporal_filter and not launched yet (see filter_flush)
   std::vector<FilterCall> pending;
   int chain_max = 2;        // iterations per chained launch (1 = never chain)

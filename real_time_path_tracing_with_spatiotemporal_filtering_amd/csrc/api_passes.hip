@@ -468,7 +468,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->scene.materials_specular, c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy);
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info);
   }
   if (take) {
     c->deferred_valid = false;

@@ -186,6 +186,8 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
 // tracing tiles; sp.n_tail filter workgroups, which start as the last tiles drain (none by default: the front group owns the
 // whole list).  The filter workgroups are the comb kernel's (atrous_comb.hpp: comb_items); the front group owns the first
 // sp.front_items items of the list and the tail group the rest, so every item has one owner and no workgroup waits for another.
+// Between the tiles and the tail group: the run workgroups (sp.n_runs), which serve the tile columns at the end of the dispatch
+// order that no triangle's bounds reach, sp.run_len tiles each (pathtrace_tile.hpp: pathtrace_empty_run).
 // The launch's dynamic LDS is the larger of the two bodies': a staged row of kFinalRoleCw cells keeps it at 8 workgroups per CU.
 // Only the pass that loads its reprojected pixels (RLOAD) is instantiated: at this kernel's 64 VGPRs it needs no scratch, the
 // reprojecting pass would spill 48 registers per lane — it runs as the launch of its own (atrous_final_role).
@@ -200,6 +202,14 @@ void k_pathtrace_final(PathtraceArgs a, TexView tex, AtrousArgs f, FinalSplit sp
   const FinalRole r = final_role(sp, blockIdx.x);
   if (r.role == kFinalRoleTile) {
     pathtrace_tile<0, true, false, false, 0, 0, 1>(a, tex, r.index, sp.tiles_x, a.tiles_y);
+  } else if (r.role == kFinalRoleRun) {
+    // the columns behind the last one a triangle's bounds reach, a run of tiles per workgroup (final_split.hpp, pathtrace_tile.hpp)
+    extern __shared__ __attribute__((aligned(16))) unsigned char final_lds[];
+#if RTPT_TILE_TIMELINE
+    FilterTimelineScope tl_(r.role, sp.n_front + sp.n_tail + r.index);
+#endif
+    const FinalRun run = final_run(sp, r.index);
+    pathtrace_empty_run(a, run.column, run.row0, run.rows, sp.n_tiles + r.index, reinterpret_cast<unsigned int*>(final_lds));
   } else {
     extern __shared__ __attribute__((aligned(16))) unsigned char final_lds[];
     const bool front = r.role == kFinalRoleFront;
@@ -362,14 +372,24 @@ uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb) {
 }
 // the filter workgroups of a launch that carries the final pass `f` (atrous_final_role finished it): how many in front of and
 // behind the tiles, and where the work list is cut between them (final_split.hpp)
+// ... and which columns of the tile order are served in runs: those behind the last one that a triangle's bounds reach, when the
+// launch has bounds (a.cull) and traces at least the primary segment
 static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const FilterPolicy& pol, uint32_t tiles_x, uint32_t tiles_y) {
   const uint32_t n_cu = a.n_cu > 0 ? static_cast<uint32_t>(a.n_cu) : 256u;
   const uint32_t per_cu = static_cast<uint32_t>(kPtWaves * 4 / kShWaves);  // resident workgroups of either kind
   const uint32_t items = static_cast<uint32_t>(f.tiles_x) * static_cast<uint32_t>(f.tiles_y) * static_cast<uint32_t>(f.stride);
-  return final_split_plan(items, tiles_x, tiles_y, n_cu, per_cu, pol.final_front, pol.final_front_share);
+  static_assert(kTileColumnPixels == kBlockX, "final_full_columns and the tile kernel agree on a column");
+  const bool runs = pol.empty_run > 0 && a.cull && a.max_segments > 0;
+  const uint32_t full_cols = runs ? final_full_columns(a.bounds, a.scene.n_tris, a.g.W, a.g.y0, a.g.y1, tiles_x) : tiles_x;
+  return final_split_plan(items, tiles_x, tiles_y, n_cu, per_cu, pol.final_front, pol.final_front_share, full_cols,
+                          runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol) {
+                      const FilterPolicy* pol, uint32_t* run_info) {
+  if (run_info) {
+    run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
+    run_info[1] = run_info[2] = 0u;
+  }
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
   const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
@@ -400,6 +420,11 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   if (fin) {
     const FinalSplit sp = final_split(a, *fin, *pol, grid.x, tiles_y);
     const dim3 grid1(final_grid(sp));
+    if (run_info) {
+      run_info[0] = sp.n_runs ? sp.n_tiles / tiles_y : grid.x;
+      run_info[1] = sp.n_runs;
+      run_info[2] = sp.n_runs ? grid.x * tiles_y - sp.n_tiles : 0u;
+    }
     hipLaunchKernelGGL(k_pathtrace_final<kFinalRoleCw>, grid1, block, dyn, s, b, tex, *fin, sp);
   } else
 #if RTPT_AB_VARIANTS

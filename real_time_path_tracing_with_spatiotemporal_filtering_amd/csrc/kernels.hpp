@@ -340,9 +340,11 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
 // textures, no specular bounce
+// run_info (optional, 3 words): the tile columns the launch serves as ordinary tiles, its run workgroups and the tiles those serve
+// (final_split.hpp; a launch without runs: every column, 0, 0)
 struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
-                      const FilterPolicy* pol = nullptr);
+                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr);
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
@@ -363,6 +365,11 @@ bool atrous_final_role(AtrousArgs& a);
 // level is the frame's FINAL pass (reprojection + blend)
 // launch policy switches of the filter kernels, read from the environment ONCE per context (rtpt_create) — A/B runs and the
 // tests that pin a variant set them before creating the context; 0 = the shipped choice
+// FilterPolicy::empty_run, the built-in R.  4K frame at rest, one job, ms per frame / us of the tracing launch
+// (profiles/r20_empty_runs_ab.txt): parent 0.5876, 0.5895 / 409.2, 411.2; R = 0 0.5874 / 409.5; 2 0.5717 / 393.5; 4 0.5709,
+// 0.5726 / 392.7, 393.7; 8 0.5713, 0.5722 / 392.7, 393.7; 16 0.5731, 0.5743 / 394.6, 395.9; 32 0.5806 / 401.9.  4 and 8 do not
+// differ; 8 has half the workgroups, and on a frame of nothing but sky 8 tiles per workgroup run 2.9 times as fast as one.
+constexpr int kEmptyRunTiles = 8;
 struct FilterPolicy {
   int chain_g_pin = 0;      // RTPT_CHAIN_G1: rows per level and step of a chained pair (2, 3, 4)
   int chain_generic = 0;    // RTPT_CHAIN_GENERIC: the instantiation that reads its strides instead of having them compiled in
@@ -386,6 +393,10 @@ struct FilterPolicy {
   // 0.1722 / 0.1711 / 0.1712.  A third group in front of the sky tiles (the last three eighths dispatched) recovered 3-5 us of
   // what the tail loses at 4K and stayed behind the whole list in front; it was removed.
   int final_front = 1, final_front_share = -1;
+  // RTPT_EMPTY_RUN=<R>: in that launch, the tile columns at the end of the dispatch order that no triangle's screen bounds reach
+  // are served R vertically consecutive tiles per workgroup (final_split.hpp, pathtrace_tile.hpp: pathtrace_empty_run); 0 = one
+  // workgroup per tile, as every other column.  kEmptyRunTiles has the sweep.
+  int empty_run = kEmptyRunTiles;
 };
 void launch_atrous_chain(const AtrousArgs& a, int levels, bool final_pass, const FilterPolicy& pol, hipStream_t s);
 bool atrous_chain_supported(int k0, int levels, uint32_t n_tris);

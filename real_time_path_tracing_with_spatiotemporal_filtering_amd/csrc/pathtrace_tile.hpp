@@ -1,6 +1,7 @@
 // pathtrace_tile.hpp — the body of the K2 tile kernels (k_pathtrace*, k_gbuffer_pathtrace*, k_pathtrace_final) and the steps it
 // shares with the queue kernel (k_pathtrace_queue), all in kernels.hip: the exchange buffer of the compaction, the hand-over of
-// unfinished paths to the next launch and the ray count.  Everything here is force-inlined; the caller (a kernel, or
+// unfinished paths to the next launch and the ray count; and the body of k_pathtrace_final's run workgroups, which serve the tile
+// columns no triangle reaches (pathtrace_empty_run).  Everything here is force-inlined; the caller (a kernel, or
 // pathtrace_tile for the tile kernels) owns the LDS.
 #pragma once
 
@@ -286,6 +287,57 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
     }
   }
   add_block_rays(a, rays, &block_rays, tid, tile_lin<ROLE>(role_lin));
+}
+
+// A run of `rows` vertically consecutive tiles, from tile row `row0` on, of tile column `bx` that no triangle's screen bounds
+// reach (final_split.hpp: final_full_columns; a.cull holds, one sample per pixel): the workgroup of k_pathtrace_final that serves
+// them all.  Every path of such a tile ends at its first query, on the light or in the sky, so of pathtrace_tile only the
+// primary segment is left: no candidate set, no closest hit (it would find id 0), no compaction, no path state in LDS, no
+// hand-over to a queue (nothing survives), and the loop has no barrier.  The ray count goes out once per workgroup.  A wave
+// takes a row of a tile, lane = column: the image does not depend on which lane traces a pixel.
+// The primary ray restates pathtrace_tile's, statement for statement, as compact_paths is restated in k_pathtrace_queue: as a
+// function of both it compiled the other tracing kernels to other code.  tests/test_empty_runs_gpu.py asks for the bits of a
+// context without runs.
+// block_rays: an LDS word of the caller's, nothing else of the workgroup's LDS is touched.
+__device__ __forceinline__ void pathtrace_empty_run(const PathtraceArgs& a, uint32_t bx, uint32_t row0, uint32_t rows, uint32_t slot,
+                                                    unsigned int* block_rays) {
+  const int tid = threadIdx.y * kBlockX + threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.y));
+  if (tid == 0) *block_rays = 0;
+  const float fw = static_cast<float>(a.g.W), fh = static_cast<float>(a.g.H);
+  const f3 light_c = ld3(a.light_c);
+  const int px0 = static_cast<int>(bx) * kBlockX + static_cast<int>(threadIdx.x);
+  unsigned int rays = 0;
+  if (px0 < a.g.W && a.seg_end > 0) {
+    for (uint32_t r = 0; r < rows; r++) {
+      const int py0 = a.g.y0 + static_cast<int>(row0 + r) * kPtRows + wave;
+      if (py0 >= a.g.y1) break;  // (wave-uniform: the frame's last tile row)
+      const size_t gi = static_cast<size_t>(py0 - a.g.row_base) * a.g.W + px0;
+      const float depth = a.depth[gi];
+      uint32_t rng = exact::rng_seed(static_cast<uint32_t>(px0), static_cast<uint32_t>(py0), a.frame, a.batch);  // :297
+      float u1 = glsl_max(1e-38f, exact::rng_next(rng));  // :87 Box-Muller
+      float u2 = exact::rng_next(rng);
+      float rad = exact::sqrt_(-2.0f * exact::log_(u1));
+      float sn, cs;
+      exact::sincos2pi(u2, sn, cs);
+      float cx = fmaf_(a.jitter, rad * cs, static_cast<float>(px0) + 0.5f);  // :314
+      float cy = fmaf_(a.jitter, rad * sn, static_cast<float>(py0) + 0.5f);
+      float ux = RTPT_DIV_SH(fmaf_(2.0f, cx, -fw), fh);     // :315
+      float uy = -RTPT_DIV_SH(fmaf_(2.0f, cy, -fh), fh);  // :316
+      const f3 d = exact::normalize(f3{a.slope * ux, a.slope * uy, -1.0f});  // :319-320
+      const f3 o = ld3(a.cam);
+      f3 acc{1.f, 1.f, 1.f};  // :201
+      if (py0 >= a.count_y0 && py0 < a.count_y1) rays++;
+      if (a.hit_id) a.hit_id[gi] = 0u;
+      if (ray_hits_light(o, d, light_c, a.light_r2))  // :226
+        acc = acc * ld3(a.light_col_first);            // :229
+      else
+        acc = acc * sky_color(d);                      // :266
+      a.image[gi] = make_float4(acc.x, acc.y, acc.z, depth);  // :328,:343
+    }
+  }
+  __syncthreads();  // block_rays is zero before the first wave adds to it
+  add_block_rays(a, rays, block_rays, tid, slot);
 }
 
 // K0 + K1 + K2 in one launch, the body of k_gbuffer_pathtrace and k_gbuffer_pathtrace_small (kernels.hip has the reasons): rows

@@ -6,7 +6,8 @@ workgroup lives by the time it starts, where the launch's tail is.
     RTPT_LIB_PATH=.../variants/librtpt_timeline.so python scripts/tile_timeline.py [--strip 3/8] [--workload 4k] [--out f.json]
 
 --fused-final: the tracing launch of a frame at rest, which carries the final filter pass of the frame before it
-(k_pathtrace_final) — tiles and filter workgroups on one clock, by kind; RTPT_FINAL_FRONT sizes the filter groups.
+(k_pathtrace_final) — tiles, run workgroups and filter workgroups on one clock, by kind; RTPT_FINAL_FRONT sizes the filter groups,
+RTPT_EMPTY_RUN the runs of tiles in the columns no triangle reaches.  --camera 30,1,6: a frame of nothing but such columns.
 """
 import argparse
 import ctypes as C
@@ -20,15 +21,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def fused_final_report(fn, W, rows, bucket_us, res):
+def fused_final_report(fn, W, rows, bucket_us, res, runs=None):
     """The tracing launch that carries the previous frame's final pass (k_pathtrace_final), tiles and filter workgroups on one
     clock: resident workgroups per bucket by kind, when each filter group's last workgroup ends, where the sky phase starts (the
-    first dispatch-order eighth of the tiles whose mean lifetime is below a quarter of the first eighth's), the launch span."""
+    first dispatch-order eighth of the tiles whose mean lifetime is below a quarter of the first eighth's), the launch span.
+    runs: rtpt_debug_empty_run_info of that launch, or None (a library without it).  The tiles its run workgroups serve have no
+    record of their own (theirs is an earlier launch's): only the columns served as tiles are read, and the run workgroups are a
+    kind of their own, recorded with the filter workgroups (role 3)."""
     gx, gy = (W + 63) // 64, (rows + 3) // 4
     nb = gx * gy
     buf = (C.c_ulonglong * (3 * nb))()
     assert fn(1, buf, nb) == 0
-    t = np.frombuffer(buf, dtype=np.uint64).reshape(nb, 3).astype(np.int64)
+    t_all = np.frombuffer(buf, dtype=np.uint64).reshape(nb, 3).astype(np.int64)
+    # the tiles in dispatch order: column by column from the middle outwards (csrc/final_split.hpp: tile_order_column); the
+    # records are indexed by tile (by * gx + bx)
+    order = []
+    for col in range(gx):
+        bx = (gx - 1) // 2 + (col + 1) // 2 if col & 1 else (gx - 1) // 2 - col // 2
+        order.extend(by * gx + bx for by in range(gy))
+    order = np.array(order)
+    if runs and runs["run_workgroups"]:
+        print(f"runs: {runs['full_columns']} of {gx} columns as tiles, {runs['run_workgroups']} run workgroups of at most {runs['run_len']} tiles "
+              f"serve {runs['run_tiles']} tiles")
+        order = order[:runs["full_columns"] * gy]
+        res["runs"] = runs
+    nb = len(order)
+    if nb == 0:   # no column is reached: the clock starts with the filter workgroups
+        t = np.zeros((0, 3), np.int64)
+    else:
+        t = t_all[order]
     nf = 1 << 16
     fbuf = (C.c_ulonglong * (3 * nf))()
     assert fn(2, fbuf, nf) == 0
@@ -36,16 +57,19 @@ def fused_final_report(fn, W, rows, bucket_us, res):
     role = (f[:, 2] >> np.uint64(48)).astype(np.int64)
     f = f.astype(np.int64)
     # records of the launch the tiles belong to (a record keeps what an earlier launch with more filter workgroups left there)
-    lo, hi = t[:, 0].min() - 100000, t[:, 1].max() + 100000
+    if nb:
+        lo, hi = t[:, 0].min() - 100000, t[:, 1].max() + 100000
+    else:
+        lo, hi = f[:, 0].max() - 100000, f[:, 0].max() + 100000
     live = (f[:, 0] != 0) & (f[:, 0] >= lo) & (f[:, 0] <= hi)
     if not live.any():
         print("fused launch: the last tracing launch carried no final pass")
         return
-    base = min(t[:, 0].min(), f[live, 0].min())
-    end = max(t[:, 1].max(), f[live, 1].max())
+    base = min(t[:, 0].min() if nb else f[live, 0].min(), f[live, 0].min())
+    end = max(t[:, 1].max() if nb else 0, f[live, 1].max())
     span = (end - base) / 100.0
     kinds = [("tiles", t[:, 0], t[:, 1])]
-    for r, name in ((1, "front"), (2, "tail")):
+    for r, name in ((1, "front"), (3, "runs"), (2, "tail")):
         m = live & (role == r)
         if m.any():
             kinds.append((name, f[m, 0], f[m, 1]))
@@ -64,15 +88,11 @@ def fused_final_report(fn, W, rows, bucket_us, res):
         print(f"   {name} group: first start {(s.min() - base) / 100.0:.1f} us, last start {(s.max() - base) / 100.0:.1f} us, first end "
               f"{(e.min() - base) / 100.0:.1f} us, last end {(e.max() - base) / 100.0:.1f} us; lifetime min {lt.min():.1f} median {np.median(lt):.1f} max {lt.max():.1f} us")
         out[name] = {"workgroups": int(len(s)), "first_start_us": float((s.min() - base) / 100.0), "last_end_us": float((e.max() - base) / 100.0)}
+    res["fused_final"] = out
+    if nb == 0:
+        return
     print(f"   tiles: first start {(t[:, 0].min() - base) / 100.0:.1f} us, last start {(t[:, 0].max() - base) / 100.0:.1f} us, last end {(t[:, 1].max() - base) / 100.0:.1f} us")
-    # the tiles in dispatch order: column by column from the middle outwards (csrc/pathtrace_tile.hpp); the
-    # records are indexed by tile (by * gx + bx)
-    order = []
-    for col in range(gx):
-        bx = (gx - 1) // 2 + (col + 1) // 2 if col & 1 else (gx - 1) // 2 - col // 2
-        order.extend(by * gx + bx for by in range(gy))
-    order = np.array(order)
-    s_us, dur = (t[order, 0] - base) / 100.0, (t[order, 1] - t[order, 0]) / 100.0
+    s_us, dur = (t[:, 0] - base) / 100.0, (t[:, 1] - t[:, 0]) / 100.0
     eighths = np.array_split(np.arange(nb), 8)
     means = [dur[q].mean() for q in eighths]
     print("   tiles by dispatch order (eighths): first start us / mean lifetime us: " + " ".join(f"{s_us[q].min():.0f}/{m:.1f}" for q, m in zip(eighths, means)))
@@ -92,6 +112,8 @@ def main():
     ap.add_argument("--fused-final", action="store_true",
                     help="report the last tracing launch as the one that carries the previous frame's final pass (frames at rest; "
                          "RTPT_FINAL_FRONT places the filter workgroups) instead of the frame's separate launches")
+    ap.add_argument("--camera", default=None, metavar="X,Y,Z",
+                    help="cameraOrigin (default -0.001,1,6; 30,1,6 looks past the box: every tile column sees only sky)")
     ap.add_argument("--strip", default=None, metavar="R/N")
     ap.add_argument("--workload", default="4k")
     ap.add_argument("--splits", default=None, metavar="0,A,...,H", help="with --strip R/N: unequal strips (strips.StripPlan.splits)")
@@ -118,6 +140,8 @@ def main():
         xyz, idx = abi.load_obj(DEFAULT_SCENE)
         vx, ti, xf, cam, zfar = scenes.instanced_cornell(xyz, idx)
         extra = dict(mesh=(vx, ti), instance_xforms=xf, cameraOrigin=cam, z_far=zfar, lightPos=(1.0, float(cam[1]), float(cam[2]) - 8.0))
+    if args.camera:
+        extra["cameraOrigin"] = tuple(float(v) for v in args.camera.split(","))
     app = make_app(wl["width"], wl["height"], max_segments=wl["max_segments"], iterations=wl["iterations"], rank=r, world=n,
                    mode="redundant", torch_planes=False, splits=tuple(int(v) for v in args.splits.split(",")) if args.splits else (), **extra)
     for _ in range(args.frames):
@@ -126,8 +150,9 @@ def main():
     if args.fused_final:   # the last frame's tracing launch carried the final pass of the frame before it; nothing has run since
         res = {"workload": args.workload, "final_front": os.environ.get("RTPT_FINAL_FRONT")}
         rows_of = app.plan.raytrace_rows()
-        print(f"RTPT_FINAL_FRONT={res['final_front']}")
-        fused_final_report(fn, wl["width"], rows_of[1] - rows_of[0], args.bucket_us, res)
+        print(f"RTPT_FINAL_FRONT={res['final_front']} RTPT_EMPTY_RUN={os.environ.get('RTPT_EMPTY_RUN')} camera={args.camera}")
+        info = getattr(app.backend.ctx, "empty_run_info", None)   # (absent in a library older than the runs)
+        fused_final_report(fn, wl["width"], rows_of[1] - rows_of[0], args.bucket_us, res, info() if info else None)
         if args.out:
             json.dump(res, open(args.out, "w"))
         return
