@@ -294,44 +294,34 @@ def load_obj(path: str):
     return xyz, idx
 
 
+def _load_obj_materials(fn, path: str, new_materials):
+    """count, then fill: (tri_material, new_materials(m) filled), or (None, None) when *n_materials comes back 0"""
+    nt, nm = C.c_uint32(), C.c_uint32()
+    _check(fn(path.encode(), None, C.byref(nt), None, C.byref(nm)))
+    if nm.value == 0:
+        return None, None
+    tri, mats = np.zeros(nt.value, np.uint32), new_materials(nm.value)
+    _check(fn(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
+    return tri, mats
+
+
 def load_obj_materials(path: str):
     """(tri_material[t] u32, materials[m, 6] f32 = Kd, Ke) of an OBJ's `mtllib`/`usemtl`; (None, None) when the OBJ names
     no readable library (the reference's Cornell box: its .mtl is missing upstream)"""
-    nt, nm = C.c_uint32(), C.c_uint32()
-    _check(load().rtpt_util_load_obj_materials(path.encode(), None, C.byref(nt), None, C.byref(nm)))
-    if nm.value == 0:
-        return None, None
-    tri = np.zeros(nt.value, np.uint32)
-    mats = np.zeros((nm.value, 6), np.float32)
-    _check(load().rtpt_util_load_obj_materials(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
-    return tri, mats
+    return _load_obj_materials(load().rtpt_util_load_obj_materials, path, lambda m: np.zeros((m, 6), np.float32))
 
 
 def load_obj_materials_ext(path: str):
     """load_obj_materials with Ks, Ns and illum: (tri_material[t] u32, materials[m] MATERIAL_EXT) by the rule of rtpt.h
     (specular exactly when illum >= 3, Ks != 0 and Ke == 0; roughness min(1, sqrt(2 / (Ns + 2))), 0 without Ns)"""
-    nt, nm = C.c_uint32(), C.c_uint32()
-    _check(load().rtpt_util_load_obj_materials_ext(path.encode(), None, C.byref(nt), None, C.byref(nm)))
-    if nm.value == 0:
-        return None, None
-    tri = np.zeros(nt.value, np.uint32)
-    mats = np.zeros(nm.value, MATERIAL_EXT)
-    _check(load().rtpt_util_load_obj_materials_ext(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
-    return tri, mats
+    return _load_obj_materials(load().rtpt_util_load_obj_materials_ext, path, lambda m: np.zeros(m, MATERIAL_EXT))
 
 
 def load_obj_materials_ni(path: str):
     """load_obj_materials_ext with Ni and Tf: a material with illum 4 / 6 / 7 / 9, an `Ni` >= 1, Ke == 0 and a colour (Tf, else
     Ks) that is not 0 is a dielectric (flags MAT_DIELECTRIC, specular = colour, ior = Ni, roughness 0); every other one is
     load_obj_materials_ext's (rtpt_util_load_obj_materials_ni)"""
-    nt, nm = C.c_uint32(), C.c_uint32()
-    _check(load().rtpt_util_load_obj_materials_ni(path.encode(), None, C.byref(nt), None, C.byref(nm)))
-    if nm.value == 0:
-        return None, None
-    tri = np.zeros(nt.value, np.uint32)
-    mats = np.zeros(nm.value, MATERIAL_EXT)
-    _check(load().rtpt_util_load_obj_materials_ni(path.encode(), _ptr(tri), C.byref(nt), _ptr(mats), C.byref(nm)))
-    return tri, mats
+    return _load_obj_materials(load().rtpt_util_load_obj_materials_ni, path, lambda m: np.zeros(m, MATERIAL_EXT))
 
 
 def load_obj_texcoords(path: str) -> np.ndarray:

@@ -1,7 +1,7 @@
-// api_selftest.hip — self tests of the device arithmetic and of the acceleration structure, and the host-side stand-ins
-// for glm / tinyobjloader (rtpt_util_*): nothing a frame calls.
+// api_selftest.hip — what needs a context and is nothing a frame calls: the self tests of the device arithmetic, of the traversal
+// and of the sampler (rtpt_selftest_*), and the checks of the acceleration structure as it stands on the device
+// (rtpt_debug_bvh_*).  The context-free helpers (rtpt_util_*) are api_util.hip's.
 #include "api_internal.hpp"
-#include "material_host.hpp"
 #include "texture_host.hpp"
 
 extern "C" {
@@ -260,35 +260,7 @@ int rtpt_selftest_texture_footprint(rtpt_ctx* c, const float* rays, size_t n, ui
   return RTPT_OK;
 }
 
-// ------------------------------------------------------------------------------------------ host helpers
-void rtpt_util_look_at(const float eye[3], const float center[3], const float up[3], float m[16]) {
-  // glm::lookAtRH (main.cpp:482, :1470)
-  using namespace rt;
-  f3 e{eye[0], eye[1], eye[2]};
-  f3 f = exact::normalize(f3{center[0], center[1], center[2]} - e);
-  f3 s = exact::normalize(exact::cross(f, f3{up[0], up[1], up[2]}));
-  f3 u = exact::cross(s, f);
-  std::memset(m, 0, 16 * sizeof(float));
-  m[0] = s.x; m[4] = s.y; m[8] = s.z;
-  m[1] = u.x; m[5] = u.y; m[9] = u.z;
-  m[2] = -f.x; m[6] = -f.y; m[10] = -f.z;
-  m[12] = -exact::dot(s, e);
-  m[13] = -exact::dot(u, e);
-  m[14] = exact::dot(f, e);
-  m[15] = 1.0f;
-}
-
-void rtpt_util_perspective(float fovy, float aspect, float zn, float zf, float m[16]) {
-  // glm::perspectiveRH_ZO (D6; main.cpp:483, :1471)
-  const float t = static_cast<float>(std::tan(static_cast<double>(fovy) * 0.5));
-  std::memset(m, 0, 16 * sizeof(float));
-  m[0] = 1.0f / (aspect * t);
-  m[5] = 1.0f / t;
-  m[10] = zf / (zn - zf);
-  m[11] = -1.0f;
-  m[14] = -(zf * zn) / (zf - zn);
-}
-
+// ------------------------------------------------------------------------------------------ the tree on the device
 // The acceleration structure AS IT STANDS ON THE DEVICE (after rtpt_scene_upload, or after a model matrix re-posed and
 // refit it inside rtpt_gbuffer): nodes, grid, posed triangles and leaf order are read back and checked on the host.
 //   stats[0] nodes, [1] leaves, [2] deepest level, [3] largest leaf, [4] triangles not referenced exactly once,
@@ -424,338 +396,6 @@ int rtpt_debug_bvh_topology(rtpt_ctx* c, uint32_t* child_refs, uint32_t* n_nodes
   }
   *n_nodes = nn;
   *n_leaf_ids = n;
-  return RTPT_OK;
-}
-
-static int bvh_check_impl(const float* build_tris, const float* tris, uint32_t n, bool pairs, uint64_t stats[8]) {
-  if (!tris || !stats || n == 0) return fail(RTPT_E_INVALID, "NULL argument / empty scene");
-  if (pairs && n % 2) return fail(RTPT_E_INVALID, "pairs mode needs an even triangle count (fan pairs 2q, 2q + 1)");
-  rt::Bvh bvh;
-  rt::build_bvh(build_tris ? build_tris : tris, n, bvh, 1e-5f, pairs);
-  if (build_tris) rt::refit_bvh(tris, n, bvh);  // same topology, boxes recomputed for the moved triangles
-  std::vector<rt::BvhNodeQ> q;
-  const rt::BvhGrid g = rt::pack_quantised_nodes(bvh, q);
-  for (int i = 0; i < 8; i++) stats[i] = 0;
-  stats[0] = bvh.nodes.size();
-  stats[2] = static_cast<uint64_t>(bvh.max_depth);
-  std::vector<uint32_t> seen(n, 0);
-  if (bvh.leaf_order.size() != n) stats[4] += 1;
-  for (uint32_t id : bvh.leaf_order) {
-    if (id >= n) {
-      stats[4]++;
-      continue;
-    }
-    seen[id]++;
-  }
-  for (uint32_t i = 0; i < n; i++)
-    if (seen[i] != 1) stats[4]++;
-  struct Item { uint32_t node; };
-  // bounds of a subtree = union of the triangles below it: computed bottom-up by recursion with an explicit stack
-  struct Bounds { float mn[3], mx[3]; };
-  auto tri_bounds = [&](uint32_t first, uint32_t cnt) {
-    Bounds b{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-    for (uint32_t j = 0; j < cnt; j++) {
-      const uint32_t id = bvh.leaf_order[first + j];
-      for (int v = 0; v < 3; v++)
-        for (int a = 0; a < 3; a++) {
-          const float x = tris[9 * static_cast<size_t>(id) + 3 * v + a];
-          b.mn[a] = std::min(b.mn[a], x);
-          b.mx[a] = std::max(b.mx[a], x);
-        }
-    }
-    return b;
-  };
-  std::vector<Bounds> sub(bvh.nodes.size());
-  std::vector<uint8_t> done(bvh.nodes.size(), 0);
-  std::vector<uint32_t> st{0};
-  while (!st.empty()) {
-    const uint32_t ni = st.back();
-    const rt::BvhNode& nd = bvh.nodes[ni];
-    bool ready = true;
-    for (int side = 0; side < 2; side++) {
-      const uint32_t idx = side ? nd.ridx : nd.lidx, cnt = side ? nd.rcnt : nd.lcnt;
-      if (idx == rt::kBvhEmpty || cnt) continue;
-      if (idx >= bvh.nodes.size()) {
-        stats[7]++;
-        continue;
-      }
-      if (!done[idx]) {
-        st.push_back(idx);
-        ready = false;
-      }
-    }
-    if (!ready) continue;
-    st.pop_back();
-    Bounds me{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-    for (int side = 0; side < 2; side++) {
-      const uint32_t idx = side ? nd.ridx : nd.lidx, cnt = side ? nd.rcnt : nd.lcnt;
-      const float* bmn = side ? nd.rmin : nd.lmin;
-      const float* bmx = side ? nd.rmax : nd.lmax;
-      if (idx == rt::kBvhEmpty) continue;
-      Bounds cb;
-      if (cnt) {
-        stats[1]++;
-        stats[3] = std::max<uint64_t>(stats[3], cnt);
-        if (cnt > static_cast<uint32_t>(rt::kBvhMaxLeaf) || static_cast<uint64_t>(idx) + cnt > n) {
-          stats[7]++;
-          continue;
-        }
-        if (pairs && !rt::pair_leaf_ok(idx, cnt, bvh.leaf_order.data(), bvh.leaf_order.size())) stats[7]++;
-        cb = tri_bounds(idx, cnt);
-      } else {
-        if (idx >= bvh.nodes.size()) continue;
-        cb = sub[idx];
-      }
-      for (int a = 0; a < 3; a++) {
-        if (!(bmn[a] <= cb.mn[a] && bmx[a] >= cb.mx[a])) stats[5]++;
-        // the device box: origin + q * cell, evaluated as the traversal's arithmetic implies (binary32)
-        const float qlo = std::fmaf(static_cast<float>(q[ni].box[rt::bvh_box_lo(side, a)]), g.cell[a], g.origin[a]);
-        const float qhi = std::fmaf(static_cast<float>(q[ni].box[rt::bvh_box_hi(side, a)]), g.cell[a], g.origin[a]);
-        if (!(qlo <= bmn[a] && qhi >= bmx[a])) stats[6]++;
-        me.mn[a] = std::min(me.mn[a], cb.mn[a]);
-        me.mx[a] = std::max(me.mx[a], cb.mx[a]);
-      }
-      const uint32_t want = cnt ? (0x80000000u | (idx << 2) | (cnt - 1u)) : idx;
-      if ((side ? q[ni].rref : q[ni].lref) != want) stats[7]++;
-    }
-    sub[ni] = me;
-    done[ni] = 1;
-  }
-  return RTPT_OK;
-}
-
-int rtpt_util_bvh_check(const float* tris, uint32_t n, uint64_t stats[8]) { return bvh_check_impl(nullptr, tris, n, false, stats); }
-int rtpt_util_bvh_check_pairs(const float* tris, uint32_t n, int pairs, uint64_t stats[8]) {
-  return bvh_check_impl(nullptr, tris, n, pairs != 0, stats);
-}
-int rtpt_util_bvh_refit_check(const float* built_for, const float* moved, uint32_t n, uint64_t stats[8]) {
-  if (!built_for) return fail(RTPT_E_INVALID, "NULL argument");
-  return bvh_check_impl(built_for, moved, n, false, stats);
-}
-
-int rtpt_util_load_obj(const char* path, float* xyz, uint32_t* n_verts, uint32_t* idx, uint32_t* n_tris) {
-  if (!path || !n_verts || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
-  FILE* fp = std::fopen(path, "r");
-  if (!fp) return fail(RTPT_E_INVALID, std::string("cannot open ") + path);
-  std::vector<long> poly;
-  uint32_t nv = 0, nt = 0;
-  char line[2048];
-  int rc = RTPT_OK;
-  while (std::fgets(line, sizeof line, fp)) {
-    const char* p = line;
-    while (*p == ' ' || *p == '\t') p++;
-    if (p[0] == 'v' && (p[1] == ' ' || p[1] == '\t')) {
-      char* end = nullptr;
-      float v[3];
-      const char* q = p + 2;
-      bool ok = true;
-      for (int k = 0; k < 3; k++) {
-        v[k] = std::strtof(q, &end);
-        if (end == q) ok = false;
-        q = end;
-      }
-      if (!ok) continue;
-      if (xyz) std::memcpy(xyz + 3 * static_cast<size_t>(nv), v, sizeof v);
-      nv++;
-    } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
-      poly.clear();
-      const char* q = p + 2;
-      while (*q) {
-        while (*q == ' ' || *q == '\t') q++;
-        if (*q == '\0' || *q == '\n' || *q == '\r') break;
-        char* end = nullptr;
-        long v = std::strtol(q, &end, 10);
-        if (end == q) break;
-        long resolved = v > 0 ? v - 1 : static_cast<long>(nv) + v;  // OBJ indices are 1-based; negative = relative
-        if (resolved < 0 || resolved >= static_cast<long>(nv)) rc = fail(RTPT_E_INVALID, "OBJ face index out of range");
-        poly.push_back(resolved);
-        q = end;
-        while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;  // skip "/vt/vn"
-      }
-      for (size_t k = 1; k + 1 < poly.size(); k++) {  // D5: fan triangulation in file order
-        if (idx) {
-          idx[3 * static_cast<size_t>(nt)] = static_cast<uint32_t>(poly[0]);
-          idx[3 * static_cast<size_t>(nt) + 1] = static_cast<uint32_t>(poly[k]);
-          idx[3 * static_cast<size_t>(nt) + 2] = static_cast<uint32_t>(poly[k + 1]);
-        }
-        nt++;
-      }
-    }
-  }
-  std::fclose(fp);
-  *n_verts = nv;
-  *n_tris = nt;
-  return rc;
-}
-
-
-// Materials of an OBJ (tinyobjloader hands main.cpp:416-428 the same information, which the
-// reference ignores — its colours are keyed on the normal, raytrace.comp.glsl:155-163, and the .mtl its OBJ names is
-// missing upstream).  `mtllib` files are looked up next to the OBJ; `usemtl` selects the material of the faces that
-// follow; a face fan-triangulates into poly - 2 triangles exactly like rtpt_util_load_obj (D5), so tri_material lines
-// up with its index array.  Material 0 is the default (Kd 0.7, the reference's grey; Ke 0) for faces without a usable
-// `usemtl`.  A missing library is not an error: *n_materials comes back 0 and the caller keeps the normal-keyed colours.
-int rtpt_util_load_obj_materials(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material* materials,
-                                 uint32_t* n_materials) {
-  if (!path || !n_tris || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
-  FILE* fp = std::fopen(path, "r");
-  if (!fp) return fail(RTPT_E_INVALID, std::string("cannot open ") + path);
-  std::string dir(path);
-  const size_t slash = dir.find_last_of('/');
-  dir = slash == std::string::npos ? std::string() : dir.substr(0, slash + 1);
-  std::vector<std::string> names{"<default>"};
-  std::vector<rtpt_material> mats(1);
-  mats[0] = rtpt_material{{0.7f, 0.7f, 0.7f}, {0.f, 0.f, 0.f}};
-  bool any_library = false;
-  auto word = [](const char* q, std::string& out) {
-    while (*q == ' ' || *q == '\t') q++;
-    out.clear();
-    while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') out.push_back(*q++);
-  };
-  auto load_mtl = [&](const std::string& file) {
-    FILE* mf = std::fopen((dir + file).c_str(), "r");
-    if (!mf) return;
-    any_library = true;
-    char ln[1024];
-    int cur = -1;
-    while (std::fgets(ln, sizeof ln, mf)) {
-      const char* p = ln;
-      while (*p == ' ' || *p == '\t') p++;
-      if (!std::strncmp(p, "newmtl", 6) && (p[6] == ' ' || p[6] == '\t')) {
-        std::string nm;
-        word(p + 6, nm);
-        names.push_back(nm);
-        mats.push_back(rtpt_material{{0.7f, 0.7f, 0.7f}, {0.f, 0.f, 0.f}});
-        cur = static_cast<int>(mats.size()) - 1;
-      } else if (cur >= 0 && (p[0] == 'K') && (p[1] == 'd' || p[1] == 'e') && (p[2] == ' ' || p[2] == '\t')) {
-        float v[3];
-        if (std::sscanf(p + 2, "%f %f %f", &v[0], &v[1], &v[2]) == 3)
-          std::memcpy(p[1] == 'd' ? mats[static_cast<size_t>(cur)].albedo : mats[static_cast<size_t>(cur)].emission, v, sizeof v);
-      }
-    }
-    std::fclose(mf);
-  };
-  uint32_t nt = 0, cur_mat = 0;
-  char line[2048];
-  while (std::fgets(line, sizeof line, fp)) {
-    const char* p = line;
-    while (*p == ' ' || *p == '\t') p++;
-    if (!std::strncmp(p, "mtllib", 6) && (p[6] == ' ' || p[6] == '\t')) {
-      std::string file;
-      word(p + 6, file);
-      load_mtl(file);
-    } else if (!std::strncmp(p, "usemtl", 6) && (p[6] == ' ' || p[6] == '\t')) {
-      std::string nm;
-      word(p + 6, nm);
-      cur_mat = 0;
-      for (size_t i = 1; i < names.size(); i++)
-        if (names[i] == nm) cur_mat = static_cast<uint32_t>(i);
-    } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
-      size_t corners = 0;
-      const char* q = p + 2;
-      while (*q) {
-        while (*q == ' ' || *q == '\t') q++;
-        if (*q == '\0' || *q == '\n' || *q == '\r') break;
-        char* end = nullptr;
-        (void)std::strtol(q, &end, 10);
-        if (end == q) break;
-        corners++;
-        q = end;
-        while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;
-      }
-      for (size_t k = 1; k + 1 < corners; k++) {
-        if (tri_material) tri_material[nt] = cur_mat;
-        nt++;
-      }
-    }
-  }
-  std::fclose(fp);
-  *n_tris = nt;
-  if (!any_library) {
-    *n_materials = 0;
-    return RTPT_OK;
-  }
-  if (materials) {
-    if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
-    std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material));
-  }
-  *n_materials = static_cast<uint32_t>(mats.size());
-  return RTPT_OK;
-}
-
-// Kd, Ke, Ks, Ns and illum: the reader and its rule live in material_host.hpp (host-only code a plain C++ program can exercise)
-int rtpt_util_load_obj_materials_ext(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
-                                     uint32_t* n_materials) {
-  if (!path || !n_tris || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
-  std::string err;
-  std::vector<rtpt_material_ext> mats;
-  bool any_library = false;
-  if (rtpt_mat::load_obj_materials(path, tri_material, n_tris, &mats, &any_library, &err)) return fail(RTPT_E_INVALID, err);
-  if (!any_library) {
-    *n_materials = 0;
-    return RTPT_OK;
-  }
-  if (materials) {
-    if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
-    std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material_ext));
-  }
-  *n_materials = static_cast<uint32_t>(mats.size());
-  return RTPT_OK;
-}
-
-// ... plus Ni and Tf: a smooth dielectric by the rule of material_host.hpp
-int rtpt_util_load_obj_materials_ni(const char* path, uint32_t* tri_material, uint32_t* n_tris, rtpt_material_ext* materials,
-                                    uint32_t* n_materials) {
-  if (!path || !n_tris || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
-  std::string err;
-  std::vector<rtpt_material_ext> mats;
-  bool any_library = false;
-  if (rtpt_mat::load_obj_materials_ni(path, tri_material, n_tris, &mats, &any_library, &err)) return fail(RTPT_E_INVALID, err);
-  if (!any_library) {
-    *n_materials = 0;
-    return RTPT_OK;
-  }
-  if (materials) {
-    if (*n_materials < mats.size()) return fail(RTPT_E_INVALID, "materials array too small");
-    std::memcpy(materials, mats.data(), mats.size() * sizeof(rtpt_material_ext));
-  }
-  *n_materials = static_cast<uint32_t>(mats.size());
-  return RTPT_OK;
-}
-
-// the texcoord / map_Kd side of the OBJ reader lives in texture_host.hpp (host-only code a plain C++ program can exercise)
-int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris) {
-  if (!path || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
-  std::string err;
-  if (rtpt_tex::load_obj_texcoords(path, tri_uv, n_tris, &err)) return fail(RTPT_E_INVALID, err);
-  return RTPT_OK;
-}
-
-int rtpt_util_texture_chain(uint32_t width, uint32_t height, uint32_t* n_levels, uint64_t* n_texels) {
-  if (!width || !height || width > rtpt_tex::kMaxTexDim || height > rtpt_tex::kMaxTexDim)
-    return fail(RTPT_E_INVALID, "a texture dimension is zero or above 65536");
-  if (n_levels) *n_levels = rtpt_tex::chain_levels(width, height);
-  if (n_texels) *n_texels = rtpt_tex::chain_texels(width, height);
-  return RTPT_OK;
-}
-
-int rtpt_util_load_obj_map_kd(const char* path, char* names, size_t* names_bytes, uint32_t* n_materials) {
-  if (!path || !names_bytes || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");
-  std::string err;
-  std::vector<std::string> maps;
-  if (rtpt_tex::load_obj_map_kd(path, &maps, &err)) return fail(RTPT_E_INVALID, err);
-  size_t need = 0;
-  for (const std::string& m : maps) need += m.size() + 1;
-  if (names) {
-    if (*names_bytes < need) return fail(RTPT_E_INVALID, "names array too small");
-    char* o = names;
-    for (const std::string& m : maps) {
-      std::memcpy(o, m.c_str(), m.size() + 1);
-      o += m.size() + 1;
-    }
-  }
-  *names_bytes = need;
-  *n_materials = static_cast<uint32_t>(maps.size());
   return RTPT_OK;
 }
 

@@ -331,7 +331,7 @@ BvhGrid pack_quantised_nodes(const Bvh& bvh, std::vector<BvhNodeQ>& out) {
     cell[a] = g.cell[a];
   }
   // the decoded face is ONE binary32 fma, fma(q, cell, origin) — the same expression in the device refit (refit.hip) and in
-  // the checkers (api_selftest.hip): step until THAT value is on the outer side.  The traversal computes
+  // the checkers (api_util.hip, api_selftest.hip): step until THAT value is on the outer side.  The traversal computes
   // q * (cell / d) + (origin - o) / d instead.  What lies between the two is NOT bounded by the coordinate: the rounding
   // of (origin - o) / d is ~2^-24 |origin - o| / |d|, and the triangle test's own rounding of o - v0 is of the same size,
   // while the padding (1e-5 x the scene's size) plus the grid's outward rounding (< one cell) is fixed.  The padding

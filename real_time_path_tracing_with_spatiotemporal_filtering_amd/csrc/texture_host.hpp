@@ -1,7 +1,7 @@
 // texture_host.hpp — the host side of the albedo textures, free of HIP so that a plain C++ program can exercise it (and a
-// sanitizer build of that program can: csrc/tests/texture_host_check.cpp): the texcoord and map_Kd side of the OBJ / MTL
-// reader, the checks rtpt_scene_set_textures applies before anything reaches the device, the record packing, and the layout
-// of the mip chains (csrc/tests/texture_mips_host_check.cpp exercises that part).
+// sanitizer build of that program can: csrc/tests/texture_host_check.cpp): the checks rtpt_scene_set_textures applies before
+// anything reaches the device, the record packing, and the layout of the mip chains (csrc/tests/texture_mips_host_check.cpp
+// exercises that part).  The OBJ / MTL reader is obj_host.hpp's; the texcoord and map_Kd loaders at the end of this file call it.
 #pragma once
 
 #include <cmath>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rtpt.h"
+#include "obj_host.hpp"
 
 namespace rtpt_tex {
 
@@ -131,141 +132,27 @@ inline size_t device_bytes(uint32_t n_tris, const rtpt_texture* textures, uint32
          (any_mipmap(textures, n_textures) ? 4 * static_cast<size_t>(kLevelRow) * n_textures : 0);
 }
 
-inline const char* skip_blank(const char* p) {
-  while (*p == ' ' || *p == '\t') p++;
-  return p;
-}
-inline bool at_end(const char* p) { return *p == '\0' || *p == '\n' || *p == '\r'; }
-
-// The texcoord side of an OBJ: `vt u v` records and the vt part of `f v/vt`, `f v/vt/vn` corners (`f v`, `f v//vn`: no
-// texcoord, the corner gets (0, 0)); negative indices count back from the last `vt` read.  Polygons fan exactly like
-// rtpt_util_load_obj (0, k, k + 1), so tri_uv lines up with its index array.  tri_uv may be NULL (count only).
-// Returns 0, or -1 with *err set.
+// The texcoord side of the OBJ reader (obj_host.hpp): 6 floats per triangle, lined up with rtpt_util_load_obj's index array;
+// a corner without a vt (`f v`, `f v//vn`) is (0, 0).  tri_uv may be NULL (count only).  Returns 0, or -1 with *err set; after
+// a texcoord index out of range the count and the array are written all the same.
 inline int load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris, std::string* err) {
-  FILE* fp = std::fopen(path, "r");
-  if (!fp) {
-    *err = std::string("cannot open ") + path;
-    return -1;
-  }
-  std::vector<float> vt;
-  std::vector<float> poly;  // u, v per corner
-  uint32_t nt = 0;
-  int rc = 0;
-  char line[2048];
-  while (std::fgets(line, sizeof line, fp)) {
-    const char* p = skip_blank(line);
-    if (p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t')) {
-      char* end = nullptr;
-      const char* q = p + 3;
-      const float u = std::strtof(q, &end);
-      if (end == q) continue;
-      q = end;
-      float v = std::strtof(q, &end);
-      if (end == q) v = 0.0f;  // `vt u` is legal: v defaults to 0
-      vt.push_back(u);
-      vt.push_back(v);
-    } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
-      poly.clear();
-      const char* q = p + 2;
-      while (*q) {
-        q = skip_blank(q);
-        if (at_end(q)) break;
-        char* end = nullptr;
-        (void)std::strtol(q, &end, 10);
-        if (end == q) break;
-        q = end;
-        float u = 0.0f, v = 0.0f;
-        // the vt number follows the slash at once (strtol would skip a blank and take the next corner's vertex number)
-        if (*q == '/' && (q[1] == '-' || q[1] == '+' || (q[1] >= '0' && q[1] <= '9'))) {
-          const long t = std::strtol(q + 1, &end, 10);
-          if (end != q + 1) {
-            const long n = static_cast<long>(vt.size() / 2);
-            const long r = t > 0 ? t - 1 : n + t;
-            if (r < 0 || r >= n) {
-              *err = "OBJ texcoord index out of range";
-              rc = -1;
-            } else {
-              u = vt[2 * static_cast<size_t>(r)];
-              v = vt[2 * static_cast<size_t>(r) + 1];
-            }
-            q = end;
-          }
-        }
-        poly.push_back(u);
-        poly.push_back(v);
-        while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') q++;  // the rest of the corner ("/vn")
-      }
-      const size_t corners = poly.size() / 2;
-      for (size_t k = 1; k + 1 < corners; k++) {
-        if (tri_uv) {
-          float* o = tri_uv + 6 * static_cast<size_t>(nt);
-          o[0] = poly[0], o[1] = poly[1];
-          o[2] = poly[2 * k], o[3] = poly[2 * k + 1];
-          o[4] = poly[2 * k + 2], o[5] = poly[2 * k + 3];
-        }
-        nt++;
-      }
-    }
-  }
-  std::fclose(fp);
-  *n_tris = nt;
-  return rc;
+  rtpt_obj::Obj o;
+  if (rtpt_obj::parse(path, &o, err)) return -1;
+  if (tri_uv) rtpt_obj::copy_tri_uv(o, tri_uv);
+  *n_tris = rtpt_obj::n_tris(o);
+  if (o.bad_texcoord_index) *err = rtpt_obj::kBadTexcoordIndex;
+  return o.bad_texcoord_index ? -1 : 0;
 }
 
 // The `map_Kd` file name of every material of the OBJ's libraries, in rtpt_util_load_obj_materials' numbering: entry 0 is
 // the default material (never textured), entry i the i-th `newmtl` over all `mtllib` files in file order.  Empty string: no
-// map.  Options before the name (`-s 1 1 1 file`) are not supported: the last word of the line is the name.
-// Returns 0 (names empty when the OBJ names no readable library), or -1 with *err set.
+// map.  Returns 0 (names empty when the OBJ names no readable library), or -1 with *err set.
 inline int load_obj_map_kd(const char* path, std::vector<std::string>* names, std::string* err) {
   names->clear();
-  FILE* fp = std::fopen(path, "r");
-  if (!fp) {
-    *err = std::string("cannot open ") + path;
-    return -1;
-  }
-  std::string dir(path);
-  const size_t slash = dir.find_last_of('/');
-  dir = slash == std::string::npos ? std::string() : dir.substr(0, slash + 1);
-  auto word = [](const char* q, std::string& out) {
-    q = skip_blank(q);
-    out.clear();
-    while (*q && *q != ' ' && *q != '\t' && *q != '\n' && *q != '\r') out.push_back(*q++);
-  };
-  bool any_library = false;
-  std::vector<std::string> maps{std::string()};
-  char line[2048];
-  while (std::fgets(line, sizeof line, fp)) {
-    const char* p = skip_blank(line);
-    if (std::strncmp(p, "mtllib", 6) || !(p[6] == ' ' || p[6] == '\t')) continue;
-    std::string file;
-    word(p + 6, file);
-    FILE* mf = std::fopen((dir + file).c_str(), "r");
-    if (!mf) continue;
-    any_library = true;
-    char ln[1024];
-    bool in_material = false;
-    while (std::fgets(ln, sizeof ln, mf)) {
-      const char* m = skip_blank(ln);
-      if (!std::strncmp(m, "newmtl", 6) && (m[6] == ' ' || m[6] == '\t')) {
-        maps.emplace_back();
-        in_material = true;
-      } else if (in_material && !std::strncmp(m, "map_Kd", 6) && (m[6] == ' ' || m[6] == '\t')) {
-        std::string last, w;
-        const char* q = m + 6;
-        for (;;) {
-          q = skip_blank(q);
-          if (at_end(q)) break;
-          word(q, w);
-          q += w.size();
-          last = w;
-        }
-        maps.back() = last;
-      }
-    }
-    std::fclose(mf);
-  }
-  std::fclose(fp);
-  if (any_library) names->swap(maps);
+  rtpt_obj::Obj o;
+  if (rtpt_obj::parse(path, &o, err)) return -1;
+  if (o.any_library)
+    for (const rtpt_obj::Material& m : o.materials) names->push_back(m.map_kd);
   return 0;
 }
 
