@@ -727,6 +727,13 @@ int rtpt_selftest_bounce(rtpt_ctx* ctx, const float* in, float* out, size_t n);
  * checked: d and n are meant to be unit vectors, u1, u2 in [0, 1], ior >= 1; 1 / ior and R0 are computed as the host computes
  * them for the record. */
 int rtpt_selftest_refract(rtpt_ctx* ctx, const float* in, float* out, size_t n);
+/* Next-event estimation, the piece that exists (additive: RTPT_ABI_VERSION stays 5; DESIGN.md 8 says what is still missing: no
+ * kernel samples a light yet).  The light sample (csrc/light_sample.hpp: the pick, the point, the direction, the weight), one
+ * case per thread: in = n x 19 words (v0[3], v1[3], v2[3] of the light, x[3] the bounce origin, nf[3] the faced normal, u_l,
+ * u_a, u_b as floats, L as a uint32), out = n x 9 words (y[3], wd[3], g, 1.0f if valid else 0.0f as floats, the picked entry
+ * min(uint(u_l * L), L - 1) as a uint32).  The light's unit normal is computed as for its shade record.  Operands are not
+ * checked; L is meant to be in [1, 2^24]. */
+int rtpt_selftest_light_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
 /* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
  * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
  * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */

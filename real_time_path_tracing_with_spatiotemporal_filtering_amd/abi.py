@@ -148,6 +148,7 @@ SYMBOLS = [
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
     "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
+    "rtpt_selftest_light_sample",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -235,6 +236,7 @@ def load() -> C.CDLL:
         "rtpt_selftest_bounce": [vp, vp, vp, sz],
         "rtpt_util_load_obj_materials_ni": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_selftest_refract": [vp, vp, vp, sz],
+        "rtpt_selftest_light_sample": [vp, vp, vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -646,6 +648,14 @@ class Context:
         cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 9)
         out = np.zeros((len(cases), 5), np.float32)
         _check(self._lib.rtpt_selftest_refract(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def selftest_light_sample(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 9] uint32 words (y, wd, g, valid as floats, the picked entry) of the device's light sample on cases [n, 19] words =
+        v0, v1, v2, x, nf, u_l, u_a, u_b as floats, L as uint32 (rtpt_selftest_light_sample)"""
+        cases = np.ascontiguousarray(cases, np.uint32).reshape(-1, 19)
+        out = np.zeros((len(cases), 9), np.uint32)
+        _check(self._lib.rtpt_selftest_light_sample(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
 
     def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:

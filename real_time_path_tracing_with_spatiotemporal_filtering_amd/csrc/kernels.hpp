@@ -424,6 +424,9 @@ void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t 
 void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s);
 // diel::refract (dielectric.hpp) on n cases of 9 floats (d, n, u1, u2, ior): out = n x (d', transmitted as 1.0f / 0.0f, F)
 void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s);
+// light::pick and light::sample (light_sample.hpp) on n cases of 19 words (v0, v1, v2, x, nf, u_l, u_a, u_b, L): out = n x (y, wd,
+// g, valid as 1.0f / 0.0f, the picked entry)
+void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 // tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs

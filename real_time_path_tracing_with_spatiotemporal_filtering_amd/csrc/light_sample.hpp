@@ -1,0 +1,55 @@
+// light_sample.hpp — the light sample of next-event estimation: one point on one emissive triangle per diffuse hit, stated once.
+// Today only the self test calls it (rtpt_selftest_light_sample, k_selftest_light_sample): no tracing kernel samples a light yet
+// (DESIGN.md 8).  Not reference behaviour: the reference collects light only by hitting it.  Contract functions only
+// (rtpt_math.hpp), no new transcendental; tests/nee_scenes.py restates every step in numpy float32 and walks whole paths with it.
+//
+// The estimator at a diffuse hit x with shading normal nf (faced against the ray) and albedo alb already in the throughput T:
+//   light i uniform among the L entries of the scene's light list, y uniform on it by area (pdf 1 / (L * area)),
+//   contribution T * Ke * (alb / pi is in T but for the 1 / pi) * cos(x) * cos(y) / r^2 / pdf = (T * Ke) * g with
+//   g = ((cs * cl) * (a2 * L)) / (2 pi * r2),   a2 = |cross(v1 - v0, v2 - v0)| = twice the area,
+// counted when the closest hit from x towards y is that triangle.
+#pragma once
+
+#include "closest_hit.hpp"
+
+namespace rt {
+namespace light {
+
+constexpr float k2Pi = 6.28318548202514648f;  // the binary32 nearest 2 pi
+constexpr uint32_t kMaxLights = 1u << 24;     // u_l has 24 bits: a longer list would have entries the pick never reaches (the
+                                              // bound a light list has to keep; the self test is told L)
+
+// entry of a list of L > 0 lights that draw u_l in [0, 1) picks
+__device__ __forceinline__ uint32_t pick(float u_l, uint32_t L) {
+  const uint32_t i = static_cast<uint32_t>(u_l * static_cast<float>(L));
+  return i < L - 1u ? i : L - 1u;
+}
+
+struct Sample {
+  f3 y;       // the point on the light
+  f3 wd;      // unit direction from x to it
+  float g;    // the weight of (T * Ke)
+  bool valid; // x faces the light's plane from a distance and the light has an area: only then is the shadow query sent
+};
+
+// v0, v1, v2, nl: the light's vertices and unit normal (its shade record); x: the bounce origin; nf: the hit's normal, faced
+// against the arriving ray; u_a, u_b: the draws behind u_l; L: entries of the list
+__device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf, float u_a, float u_b, uint32_t L) {
+  Sample s;
+  const float su = exact::sqrt_(u_a);
+  const float b0 = 1.0f - su, b1 = su * (1.0f - u_b), b2 = su * u_b;
+  s.y = bary_point(v0, v1, v2, b0, b1, b2);
+  const f3 w = s.y - x;
+  const float r2 = exact::dot(w, w);
+  s.wd = exact::normalize(w);
+  const float cs = exact::dot(nf, s.wd);
+  const float cl = __builtin_fabsf(exact::dot(nl, s.wd));  // emitters shine from both sides, as they do when a path hits them
+  const f3 c = exact::cross(v1 - v0, v2 - v0);
+  const float a2 = exact::sqrt_(exact::dot(c, c));
+  s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
+  s.g = exact::div_((cs * cl) * (a2 * static_cast<float>(L)), k2Pi * r2);
+  return s;
+}
+
+}  // namespace light
+}  // namespace rt

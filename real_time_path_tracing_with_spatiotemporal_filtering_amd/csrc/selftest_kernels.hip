@@ -3,6 +3,7 @@
 // an edit here does not recompile the frame kernels (kernels.hip).
 #include "closest_hit.hpp"
 #include "dielectric.hpp"
+#include "light_sample.hpp"
 #include "select.hpp"
 #include "shade_segment.hpp"
 #include "specular.hpp"
@@ -214,6 +215,24 @@ __global__ void k_selftest_refract(const float* in, float* out, size_t n) {
   out[5 * i + 4] = fresnel;
 }
 
+// light_sample.hpp's pick and sample, one case per thread: in = v0, v1, v2, x, nf, u_l, u_a, u_b, L (19 words); out = y, wd, g,
+// 1.0f if valid else 0.0f, the picked entry (9 words).  The light's normal as k_scene_prepare stores it (rtpt_selftest_light_sample)
+__global__ void k_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = reinterpret_cast<const float*>(in + 19 * i);
+  const f3 v0 = ld3(w), v1 = ld3(w + 3), v2 = ld3(w + 6);
+  const uint32_t L = in[19 * i + 18];
+  const f3 nl = exact::normalize(exact::cross(v1 - v0, v2 - v0));  // raytrace.comp.glsl:150
+  const light::Sample s = light::sample(v0, v1, v2, nl, ld3(w + 9), ld3(w + 12), w[16], w[17], L);
+  uint32_t* r = out + 9 * i;
+  r[0] = f2u(s.y.x); r[1] = f2u(s.y.y); r[2] = f2u(s.y.z);
+  r[3] = f2u(s.wd.x); r[4] = f2u(s.wd.y); r[5] = f2u(s.wd.z);
+  r[6] = f2u(s.g);
+  r[7] = f2u(s.valid ? 1.0f : 0.0f);
+  r[8] = light::pick(w[15], L);
+}
+
 template <int BVH>
 __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const float* rays, size_t n, float tmax,
                                                              uint32_t* out_id, float* out_t) {
@@ -296,6 +315,10 @@ void launch_selftest_contract(int fn, const uint32_t* in, uint32_t* out, size_t 
 void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_bounce, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_light_sample, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
 }
 void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;
