@@ -189,6 +189,34 @@ typedef struct rtpt_visibility_data {
                                               two materials from frame to frame (1-spp aliasing that the filter blurs away without
                                               the flag); ALBEDO is not accumulated over frames.  Additive: the ABI version stays 5 */
 
+#define RTPT_FLAG_EXT_NEE 0x10000u /* next-event estimation (NOT reference behaviour, default off; DESIGN.md 8, csrc/light_sample.hpp states
+                                      the rules): rtpt_raytrace samples the scene's emissive triangles.  rtpt_scene_set_materials and
+                                      rtpt_scene_set_materials_ext build the LIGHT LIST beside the material records — id + 1 of every
+                                      posed triangle whose material has Ke != 0, ascending; more than 2^24 of them are refused with
+                                      the scene untouched (RTPT_E_INVALID).  Everything below holds only while the list has L > 0
+                                      entries; without an emitter, without materials and without the flag the frames, the ray counts
+                                      and the kernels are those of a context without it, bit for bit.
+                                      At a DIFFUSE hit that is not the path's last segment (seg + 1 < max_segments), after the albedo
+                                      went into the throughput T (or, at segment 0 with RTPT_FLAG_EXT_DEMODULATE, into ALBEDO), after
+                                      the faceforward and the offset origin x, and before the bounce's two draws, three draws u_l,
+                                      u_a, u_b pick entry min(uint(u_l * L), L - 1) and a point y uniform on that triangle; if x
+                                      faces y and y's plane from a distance and the triangle has an area, ONE closest-hit query goes
+                                      from x towards y (the path's own query: same tmax, same tie rule; counted in RAYCOUNT), and if
+                                      it returns that triangle the pixel's radiance R gains (T * Ke) * g per channel, g = cos(x)
+                                      cos(y) 2 area L / (2 pi r^2).  The hit sets the path's sampled bit, valid sample or not; a
+                                      specular or dielectric hit takes no light draw and clears it; the primary ray starts with it
+                                      clear.  A path that meets an emissive triangle with the bit set ends with colour 0 (its light
+                                      was collected at the hit before), with the bit clear with T * Ke as without the flag.  The
+                                      analytic sphere light, the sky and the end of the segment budget end a path as without the
+                                      flag; none of them is sampled.  The pixel stores R + the path's terminal colour; with
+                                      samples_per_pixel > 1 that sum goes into the sample mean and R restarts at 0 per sample.  With
+                                      RTPT_FLAG_EXT_DEMODULATE the gain of segment 0 is illumination (T lacks the first albedo), so
+                                      IMAGE x ALBEDO is the frame without that flag up to the order of the multiplies.
+                                      Such a launch runs every segment in the tile kernel (as RTPT_FLAG_SINGLE_LAUNCH_PATHS) and
+                                      carries no deferred final filter pass.  Instances moved, a rebuilt tree, a changed model and
+                                      rtpt_resize keep the list; rtpt_scene_upload drops it with the materials.  Additive: the ABI
+                                      version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -727,13 +755,16 @@ int rtpt_selftest_bounce(rtpt_ctx* ctx, const float* in, float* out, size_t n);
  * checked: d and n are meant to be unit vectors, u1, u2 in [0, 1], ior >= 1; 1 / ior and R0 are computed as the host computes
  * them for the record. */
 int rtpt_selftest_refract(rtpt_ctx* ctx, const float* in, float* out, size_t n);
-/* Next-event estimation, the piece that exists (additive: RTPT_ABI_VERSION stays 5; DESIGN.md 8 says what is still missing: no
- * kernel samples a light yet).  The light sample (csrc/light_sample.hpp: the pick, the point, the direction, the weight), one
+/* Next-event estimation (RTPT_FLAG_EXT_NEE; additive: RTPT_ABI_VERSION stays 5).  The light sample (csrc/light_sample.hpp: the pick, the point, the direction, the weight), one
  * case per thread: in = n x 19 words (v0[3], v1[3], v2[3] of the light, x[3] the bounce origin, nf[3] the faced normal, u_l,
  * u_a, u_b as floats, L as a uint32), out = n x 9 words (y[3], wd[3], g, 1.0f if valid else 0.0f as floats, the picked entry
  * min(uint(u_l * L), L - 1) as a uint32).  The light's unit normal is computed as for its shade record.  Operands are not
  * checked; L is meant to be in [1, 2^24]. */
 int rtpt_selftest_light_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
+/* The light list of RTPT_FLAG_EXT_NEE as it stands on the device: *n = its entries (0 without the flag, without materials or
+ * without an emitter), of which the first min(*n, cap) are copied to ids — id + 1 of every posed triangle inst * n_tris + t whose
+ * material has Ke != 0, ascending.  ids may be NULL when cap is 0 (count only). */
+int rtpt_debug_light_list(rtpt_ctx* ctx, uint32_t* ids, uint32_t cap, uint32_t* n);
 /* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
  * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
  * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */

@@ -30,6 +30,7 @@ FLAG_DEVICE_BVH_BUILD = 0x1000  # rtpt_scene_upload builds the tree on the devic
 FLAG_DEVICE_BVH_SAH = 0x2000  # with FLAG_DEVICE_BVH_BUILD: the device SAH builder, the host's tree node for node (csrc/bvh_build_sah.hip)
 FLAG_EXT_DEMODULATE = 0x8000  # filter illumination, multiply the first hit's albedo back afterwards (modulate / present); not in FLAG_EXT_MASK
 FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms -> triangles and the fan-pair test on the device (csrc/scene_flatten.hip)
+FLAG_EXT_NEE = 0x10000  # next-event estimation: rtpt_raytrace samples the scene's emissive triangles (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -148,7 +149,7 @@ SYMBOLS = [
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
     "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
-    "rtpt_selftest_light_sample",
+    "rtpt_selftest_light_sample", "rtpt_debug_light_list",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -237,6 +238,7 @@ def load() -> C.CDLL:
         "rtpt_util_load_obj_materials_ni": [C.c_char_p, vp, C.POINTER(u32), vp, C.POINTER(u32)],
         "rtpt_selftest_refract": [vp, vp, vp, sz],
         "rtpt_selftest_light_sample": [vp, vp, vp, sz],
+        "rtpt_debug_light_list": [vp, vp, u32, C.POINTER(u32)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -453,6 +455,16 @@ class Context:
         out = (C.c_uint64 * 4)()
         _check(self._lib.rtpt_debug_upload_info(self._h, C.byref(out)))
         return dict(zip(("h2d_bytes", "device_flatten", "device_pairs", "moves_without_sync"), (int(v) for v in out)))
+
+    def debug_light_list(self) -> np.ndarray:
+        """the light list of FLAG_EXT_NEE as it stands on the device (rtpt_debug_light_list): uint32 [L], id + 1 of every posed
+        emissive triangle, ascending; empty without the flag, without materials or without an emitter"""
+        n = C.c_uint32()
+        _check(self._lib.rtpt_debug_light_list(self._h, None, 0, C.byref(n)))
+        ids = np.zeros(n.value, np.uint32)
+        if n.value:
+            _check(self._lib.rtpt_debug_light_list(self._h, _ptr(ids), n.value, C.byref(n)))
+        return ids
 
     def scene_build_info(self) -> dict:
         """what built the tree that is on the device now (rtpt_scene_build_info): builder, fallback, counts, milliseconds"""

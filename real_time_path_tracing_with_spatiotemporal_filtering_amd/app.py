@@ -756,7 +756,7 @@ class PathTracingApplication:
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
-             specular=False, dielectric=False, **app_kw):
+             specular=False, dielectric=False, nee=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -767,7 +767,13 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     `newmtl` with illum >= 3 and Ks != 0 bounces as a mirror or glossy surface (rtpt_scene_set_materials_ext) — to every context
     of this rank; with `textures` the maps multiply Ks as they multiply Kd.
     `dielectric` (off by default): the same with Ni and Tf too, by the rule of abi.load_obj_materials_ni — a `newmtl` with illum
-    4 / 6 / 7 / 9 and an `Ni` >= 1 is glass: Fresnel reflection or refraction at every hit (RTPT_MAT_DIELECTRIC)."""
+    4 / 6 / 7 / 9 and an `Ni` >= 1 is glass: Fresnel reflection or refraction at every hit (RTPT_MAT_DIELECTRIC).
+    `nee` (off by default): next-event estimation, abi.FLAG_EXT_NEE on every context of this rank — every diffuse hit samples one of
+    the triangles whose material has a Ke.  It is `flags=abi.FLAG_EXT_NEE` by another name: the lamps come from the material
+    table, which `textures`, `specular`, `dielectric` or the caller's own set_materials / set_materials_ext call provides;
+    without a table no frame changes."""
+    if nee:
+        flags |= abi.FLAG_EXT_NEE
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())
     if torch_planes is None:
         torch_planes = world > 1  # halo exchange and the history all-gather move rows of torch-owned planes

@@ -178,6 +178,10 @@ rt::TexView tex_view(const rtpt_ctx* c) {
   return t;
 }
 
+rt::LightView light_view(const rtpt_ctx* c) {
+  return rt::LightView{static_cast<const uint32_t*>(c->scene.lights.ptr), c->scene.n_lights};
+}
+
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose
 // view-space axes are the columns c0,c1,c2 and whose pixel (x,y) looks along
 // (nx/p00, ny/p11, -1), nx = (2(x+.5)-W)/W, ny = (2(y+.5)-H)/H  (the K0 ray; the K2 camera is the
@@ -613,6 +617,20 @@ int rtpt_debug_empty_run_info(rtpt_ctx* c, uint64_t out[4]) {
 int rtpt_debug_live_device_bytes(uint64_t* out) {
   if (!out) return fail(RTPT_E_INVALID, "NULL argument");
   *out = g_live_device_bytes.load();
+  return RTPT_OK;
+}
+
+// the light list as it stands on the device: *n = its entries, of which the first min(*n, cap) are copied to ids
+int rtpt_debug_light_list(rtpt_ctx* c, uint32_t* ids, uint32_t cap, uint32_t* n) {
+  if (!c || !n || (cap && !ids)) return fail(RTPT_E_INVALID, "NULL argument");
+  const uint32_t have = c->scene.lights.ptr ? c->scene.n_lights : 0u;
+  *n = have;
+  const uint32_t take = have < cap ? have : cap;
+  if (!take) return RTPT_OK;  // no zero-byte copy
+  if (static_cast<size_t>(have) * 4 > c->scene.lights.bytes) return fail(RTPT_E_INVALID, "internal: the light list is shorter than its count");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(ids, c->scene.lights.ptr, static_cast<size_t>(take) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return RTPT_OK;
 }
 

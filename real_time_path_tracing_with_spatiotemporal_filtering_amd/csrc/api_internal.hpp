@@ -195,6 +195,11 @@ struct Scene {
   Buf materials;                             // optional per-base-triangle (Kd, Ke) records, rtpt_scene_set_materials
   int materials_specular = 0;                // 1: some triangle's record is specular (rtpt_scene_set_materials_ext), 2: some
                                              // triangle's is a dielectric — the SPEC kernels; 0: every record is diffuse
+  // RTPT_FLAG_EXT_NEE: the light list (light_list_host.hpp), id + 1 of every posed emissive triangle, built beside the material
+  // records on a context with the flag and dropped with them; empty (no allocation) without the flag or without an emitter.  An
+  // upload drops it with the scene; moved instances, a rebuilt tree, a changed model and a resize keep it: ids do not change
+  Buf lights;
+  uint32_t n_lights = 0;
   // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
   struct Textures {
     Buf records, desc, texels;
@@ -359,6 +364,7 @@ int check_rows(const rtpt_ctx* c, uint32_t& y0, uint32_t& y1);
 rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1);
 rt::SceneView scene_view(const rtpt_ctx* c);
 rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
+rt::LightView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights)
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3], double p00, double p11,
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);

@@ -140,11 +140,19 @@ void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, fl
   for (int i = 0; i < 5; i++) std::memcpy(dst[i], src[i], 3 * sizeof(float));
 }
 
+// launch_pathtrace's `specular`: rt::kSpecNee when the launch samples lights — the context has RTPT_FLAG_EXT_NEE and the scene's
+// light list has entries (then it has material records too: the list is built beside them and dropped with them) — else what
+// the materials ask for.  Without the flag, or with an empty list, every choice below is the one of a context without the flag
+int trace_material_mode(const rtpt_ctx* c) {
+  const bool nee = (c->cfg.flags & RTPT_FLAG_EXT_NEE) && c->scene.n_lights > 0 && c->scene.lights.ptr && c->scene.materials.ptr;
+  return nee ? rt::kSpecNee : c->scene.materials_specular;
+}
+
 // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (rtpt_ctx::trace_pool): the workgroups' slabs
 int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
   a.pool_slab = nullptr;
   if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo && !c->scene.textures.records.ptr &&
-        !c->scene.materials_specular))
+        !trace_material_mode(c)))
     return RTPT_OK;  // (the pool form stores no albedo, samples no texture and bounces diffusely: such frames take the tile kernel)
   const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
   if (need && c->path_pool.bytes < need)
@@ -161,6 +169,7 @@ int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
   a.queue_count = nullptr;
   a.queue_region = 0;
   if (!(a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS))) return RTPT_OK;
+  if (trace_material_mode(c) == rt::kSpecNee) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
   const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
   const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
   const size_t cap = region * rt::kPathQueues;
@@ -442,7 +451,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   // it and the trace covers every stored row (so that the spare buffer it writes then holds what IMAGE would).  The pass reads
   // the buffer IMAGE names now (the old history), so the trace goes to the buffer no role names and the two change places.
   // Every other call sends the pass out first.
-  const bool take = c->deferred_valid && !fused && rt::pathtrace_takes_final(a, tex_view(c), c->scene.materials_specular) &&
+  const bool take = c->deferred_valid && !fused && rt::pathtrace_takes_final(a, tex_view(c), trace_material_mode(c)) &&
                     a.g.y0 == static_cast<int32_t>(c->cfg.row_begin) && a.g.y1 == static_cast<int32_t>(c->cfg.row_end);
   if (!take && (rc = final_flush(c))) return rc;
   if (take) {
@@ -467,8 +476,8 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   }
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
-    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), c->scene.materials_specular, c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info);
+    rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), trace_material_mode(c), c->stream,
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c));
   }
   if (take) {
     c->deferred_valid = false;

@@ -2,6 +2,7 @@
 // :687-742; flattened on the host, or on the device: scene_flatten.hip), instances that move between frames
 // (rtpt_scene_set_instances), the posed scene of a changed ubo.model (device-side refit, refit.hip), materials.
 #include "api_internal.hpp"
+#include "light_list_host.hpp"
 #include "material_host.hpp"
 #include "texture_host.hpp"
 
@@ -236,6 +237,42 @@ int device_build_tree(rtpt_ctx* c, Scene& s, bool leaf_pairs, bool* too_deep) {
   s.build_ms_pending = true;
   set_build_info(s, sah ? static_cast<uint32_t>(RTPT_BUILDER_DEVICE_SAH) : static_cast<uint32_t>(RTPT_BVH_BUILDER_DEVICE_LBVH), RTPT_BVH_FALLBACK_NONE, 0.f);
   return RTPT_OK;
+}
+
+// RTPT_FLAG_EXT_NEE: the light list of a material call (light_list_host.hpp), built on the host before anything of the scene is
+// touched.  Without the flag the list stays empty and nothing else happens
+template <class M>
+int host_light_list(const rtpt_ctx* c, const uint32_t* tri_material, const M* materials, std::vector<uint32_t>* list) {
+  list->clear();
+  if (!(c->cfg.flags & RTPT_FLAG_EXT_NEE)) return RTPT_OK;
+  const int r = rtpt_light::build_light_list(tri_material, materials, c->scene.n_base_tris, c->scene.n_instances ? c->scene.n_instances : 1u, list);
+  if (r == rtpt_light::kListTooLong) return fail(RTPT_E_INVALID, "more than 2^24 emissive triangles: the light list of RTPT_FLAG_EXT_NEE has no room for them");
+  if (r != rtpt_light::kListOk) return fail(RTPT_E_NOMEM, "host allocation failed (light list)");
+  return RTPT_OK;
+}
+
+// ... to the device, in the manner of the material records: `list` outlives the caller's synchronise, and `ids` is the caller's
+// local, which joins the scene together with the records once both copies are complete (join_materials): a failure here or
+// there leaves the scene without either.  An empty list allocates and copies nothing
+int upload_light_list(rtpt_ctx* c, const std::vector<uint32_t>& list, Buf& ids) {
+  if (list.empty()) return RTPT_OK;
+  const size_t bytes = list.size() * sizeof(uint32_t);
+  int rc = alloc_buf(ids, bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ids.ptr, list.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  return RTPT_OK;
+}
+void join_materials(rtpt_ctx* c, Buf& recs, Buf& ids, size_t n_lights) {
+  c->scene.materials = std::move(recs);
+  if (ids.ptr) {
+    c->scene.lights = std::move(ids);
+    c->scene.n_lights = static_cast<uint32_t>(n_lights);
+  }
+}
+
+void drop_lights(rtpt_ctx* c) {
+  free_buf(c->scene.lights);
+  c->scene.n_lights = 0;
 }
 
 // the mesh and the instance transforms of one rtpt_scene_upload call
@@ -647,6 +684,7 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
   if (!tri_material || !materials || !n_materials) {  // back to the reference's normal-keyed colours
     free_buf(c->scene.materials);
     c->scene.materials_specular = false;
+    drop_lights(c);
     return RTPT_OK;
   }
   if (n_tris != c->scene.n_base_tris) return fail(RTPT_E_INVALID, "one material index per triangle of the uploaded mesh");
@@ -659,14 +697,19 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
     r[4] = m.emission[0]; r[5] = m.emission[1]; r[6] = m.emission[2];
     r[7] = (m.emission[0] != 0.0f || m.emission[1] != 0.0f || m.emission[2] != 0.0f) ? 1.0f : 0.0f;
   }
+  std::vector<uint32_t> lights;  // RTPT_FLAG_EXT_NEE (empty without): refused, like everything above, before anything is freed
+  int rc = host_light_list(c, tri_material, materials, &lights);
+  if (rc) return rc;
   free_buf(c->scene.materials);  // never two sets at once; a failure below leaves the reference's colours
   c->scene.materials_specular = false;  // (a set of rtpt_scene_set_materials_ext is replaced like any other)
-  Buf recs;  // joins the scene when it is complete
-  int rc = alloc_buf(recs, rec.size() * sizeof(float));
+  drop_lights(c);
+  Buf recs, ids;  // join the scene when both are complete
+  rc = alloc_buf(recs, rec.size() * sizeof(float));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if ((rc = upload_light_list(c, lights, ids))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->scene.materials = std::move(recs);
+  join_materials(c, recs, ids, lights.size());
   return RTPT_OK;
 }
 
@@ -689,19 +732,24 @@ int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint
     }
     any_specular = rtpt_mat::pack_records_mode(tri_material, n_tris, materials, rec.data());
   }
+  std::vector<uint32_t> lights;  // RTPT_FLAG_EXT_NEE (empty without, and for a dropped set)
+  if (!drop)
+    if (int rcl = host_light_list(c, tri_material, materials, &lights)) return rcl;
   HIP_TRY(hipSetDevice(c->device));
   FLUSH_FILTER(c);
   HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the set being replaced
   // K0, K1 and the filter read no material: no plane tag, no scene generation changes — frame reuse goes on
   free_buf(c->scene.materials);  // never two sets at once, as in rtpt_scene_set_materials
   c->scene.materials_specular = false;
+  drop_lights(c);
   if (drop) return RTPT_OK;
-  Buf recs;  // joins the scene when it is complete
+  Buf recs, ids;  // join the scene when both are complete
   int rc = alloc_buf(recs, rec.size() * sizeof(float));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if ((rc = upload_light_list(c, lights, ids))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->scene.materials = std::move(recs);
+  join_materials(c, recs, ids, lights.size());
   c->scene.materials_specular = any_specular;
   return RTPT_OK;
 }

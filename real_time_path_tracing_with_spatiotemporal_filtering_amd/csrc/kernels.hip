@@ -179,6 +179,38 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex);
 }
 
+// The same four kernels for launches that sample lights (SPEC = 3, RTPT_FLAG_EXT_NEE on a scene with a light list): overloads
+// that take the list as a parameter of their own behind TexView (kernels.hpp: LightView), so that the argument segments of the
+// kernels above stay what they were.
+template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
+void k_pathtrace(PathtraceArgs a, TexView tex, LightView lights) {
+  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
+}
+template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
+void k_pathtrace_small(PathtraceArgs a, TexView tex, LightView lights) {
+  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
+}
+template <int BVH, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
+void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
+  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
+}
+template <bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
+void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
+  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
+}
+
 // K2 of frame n + 1 and the final filter pass of frame n in one launch (api_passes.hip: DeferredFinal).  The trace is bound by VALU
 // issue and touches next to no memory, the final pass by HBM; neither reads what the other writes (DESIGN §4 has the table), and
 // as launches of their own they never share the machine.  One grid, three runs of workgroups in dispatch order (final_split.hpp
@@ -351,7 +383,7 @@ bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g) {
 // the path-pool form of the tile kernel (experiments/pathtrace_pool.inc, -DRTPT_AB_VARIANTS=1 builds only) serves scenes whose
 // BVH is built over fan pairs, one sample per pixel
 #if RTPT_AB_VARIANTS
-bool pathtrace_uses_pool(const PathtraceArgs& a) {
+bool pathtrace_uses_pool(const PathtraceArgs& a) {  // (a launch that samples lights gets no slab: ensure_path_pool)
   return a.pool_slab && a.scene.use_bvh && a.scene.leaf_pairs && a.compact && a.spp == 1;
 }
 size_t pathtrace_pool_bytes(int W, int rows) {  // slabs of the tracing workgroups of a launch over `rows` rows
@@ -385,14 +417,16 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
                           runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol, uint32_t* run_info) {
+                      const FilterPolicy* pol, uint32_t* run_info, const LightView& lights) {
   if (run_info) {
     run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
     run_info[1] = run_info[2] = 0u;
   }
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
-  const bool pool = pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
+  const bool nee = spec_mode(specular) == 3;  // the launch samples lights: the SPEC = 3 tile kernels, all segments in them
+  if (nee && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();  // (api_passes.hip: trace_material_mode)
+  const bool pool = !nee && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
@@ -406,10 +440,11 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   b.tiles_y = tiles_y;
   b.multi_off = static_cast<uint32_t>(dyn / 4);
   const size_t dyn_queue = dyn;
+  if (nee) dyn += 3 * kPtThreads * 4;        // rad_r, rad_g, rad_b (pathtrace_tile), in front of the sums
   if (a.spp > 1) dyn += 4 * kPtThreads * 4;  // sum_r, sum_g, sum_b, rng_pix
   const uint32_t phase0 = a.first_window ? a.first_window : pt_first_window(a.scene.use_bvh != 0);
-  const bool split = a.spp == 1 && a.compact && a.queue[0] && a.queue_count && a.max_segments > phase0 &&
-                     (a.max_segments <= 2 * phase0 || a.queue[1]);
+  const bool split = !nee && a.spp == 1 && a.compact && a.queue[0] && a.queue_count && a.max_segments > phase0 &&
+                     (a.max_segments <= 2 * phase0 || a.queue[1]);  // (the queue kernels sample no light)
   b.seg_begin = 0;
   b.seg_end = split ? phase0 : a.max_segments;
   b.q_in = nullptr;
@@ -442,22 +477,43 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       constexpr bool D = decltype(demod)::value;
       with_mode3(tex_mode(tex), [&](auto tmode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tmode)::value;
-        with_mode3(spec_mode(specular), [&](auto spec) {  // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials
+        // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE: those that
+        // sample lights too (3), which take the light list as one more argument
+        with_mode4(spec_mode(specular), [&](auto spec) {
           constexpr int S = decltype(spec)::value;
-          if (gb) {
-            if constexpr (M != 0)
-              hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T, S>), grid, block, dyn, s, b, *gb, tex);
-            else
-              hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T, S>), grid, block, dyn, s, b, *gb, tex);
-            return;
+          if constexpr (S == 3) {
+            // (the launch syntax, because these kernels are OVERLOADS of the names below: an overload set is no argument for
+            // hipLaunchKernelGGL's deduced kernel type, a call resolves it by its arguments)
+            if (gb) {
+              if constexpr (M != 0)
+                k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, lights);
+              else
+                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, lights);
+              return;
+            }
+            with_bool(a.compact != 0, [&](auto compact) {
+              constexpr bool C = decltype(compact)::value;
+              if constexpr (M != 0)
+                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, lights);
+              else
+                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, lights);
+            });
+          } else {
+            if (gb) {
+              if constexpr (M != 0)
+                hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T, S>), grid, block, dyn, s, b, *gb, tex);
+              else
+                hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T, S>), grid, block, dyn, s, b, *gb, tex);
+              return;
+            }
+            with_bool(a.compact != 0, [&](auto compact) {
+              constexpr bool C = decltype(compact)::value;
+              if constexpr (M != 0)
+                hipLaunchKernelGGL((k_pathtrace<M, C, D, T, S>), grid, block, dyn, s, b, tex);
+              else
+                hipLaunchKernelGGL((k_pathtrace_small<C, D, T, S>), grid, block, dyn, s, b, tex);
+            });
           }
-          with_bool(a.compact != 0, [&](auto compact) {
-            constexpr bool C = decltype(compact)::value;
-            if constexpr (M != 0)
-              hipLaunchKernelGGL((k_pathtrace<M, C, D, T, S>), grid, block, dyn, s, b, tex);
-            else
-              hipLaunchKernelGGL((k_pathtrace_small<C, D, T, S>), grid, block, dyn, s, b, tex);
-          });
         });
       });
     });

@@ -58,6 +58,18 @@ struct TexView {
   float bounce_spread;
 };
 
+// The light list of next-event estimation (RTPT_FLAG_EXT_NEE; light_sample.hpp, light_list_host.hpp): ids[i] = id + 1 of a posed
+// emissive triangle, ascending; n in [1, 2^24] where a kernel reads it.  It travels as a parameter of its own behind TexView, and
+// only of the kernels that sample lights (kernels.hip: the overloads of the four tile kernels that take a LightView), for TexView's reason: inside SceneView the pointer would move
+// every later field of PathtraceArgs / GbufferArgs, and behind TexView it would change the argument segment of every tracing kernel.
+struct LightView {
+  const uint32_t* ids;
+  uint32_t n;
+};
+// launch_pathtrace's `specular` for a launch that samples lights: the SPEC = 3 instantiations, which include the specular and
+// dielectric bounces (Scene::materials_specular is 0, 1 or 2)
+constexpr int kSpecNee = 3;
+
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
 // and the same columns of row min(2y + 1, sh - 1) of level l (texture_mips.hip): one launch per level.  src and dst are texel
 // offsets into `atlas`; dw = max(1, sw >> 1), dh = max(1, sh >> 1).
@@ -335,7 +347,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // whether they can; pathtrace_grid_blocks = the workgroups of that launch, what the BVH stack's spill area is sized for)
 // specular: 1 some triangle's material is specular, 2 some triangle's is a dielectric, 0 neither (Scene::materials_specular) — what
 // selects the SPEC instantiations; it travels
-// beside the kernel arguments, not in them, so that every existing argument offset stays
+// beside the kernel arguments, not in them, so that every existing argument offset stays.  kSpecNee (then `lights` has entries):
+// the launch samples lights, every segment runs in the tile kernel (no queue kernels) and it carries no final pass
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -344,7 +357,7 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // (final_split.hpp; a launch without runs: every column, 0, 0)
 struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
-                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr);
+                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr, const LightView& lights = LightView{nullptr, 0u});
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);

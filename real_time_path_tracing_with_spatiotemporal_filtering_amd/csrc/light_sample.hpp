@@ -1,7 +1,30 @@
 // light_sample.hpp — the light sample of next-event estimation: one point on one emissive triangle per diffuse hit, stated once.
-// Today only the self test calls it (rtpt_selftest_light_sample, k_selftest_light_sample): no tracing kernel samples a light yet
-// (DESIGN.md 8).  Not reference behaviour: the reference collects light only by hitting it.  Contract functions only
-// (rtpt_math.hpp), no new transcendental; tests/nee_scenes.py restates every step in numpy float32 and walks whole paths with it.
+// The SPEC = 3 instantiations of the tile kernels call it (shade_segment.hpp, pathtrace_tile.hpp), and the self test
+// (rtpt_selftest_light_sample, k_selftest_light_sample).  Not reference behaviour: the reference collects light only by hitting
+// it.  Contract functions only (rtpt_math.hpp), no new transcendental; tests/nee_scenes.py restates every step in numpy float32,
+// tests/nee_paths.py walks whole paths with it.
+//
+// THE RULES (RTPT_FLAG_EXT_NEE on a scene whose light list has L > 0 entries; in every other case frames, ray counts and the
+// kernels chosen are those of a context without the flag, bit for bit):
+//   * A sample is taken at a DIFFUSE hit that is not the path's last segment (seg + 1 < max_segments): after the albedo went into
+//     the throughput T (into the albedo plane at segment 0 with RTPT_FLAG_EXT_DEMODULATE), after the faceforward and the offset
+//     origin x = o, before the bounce's two draws.
+//   * Three draws u_l, u_a, u_b in that order; entry i = pick(u_l, L) names posed triangle id = lights[i] (id + 1, as
+//     HitRec::id1); its vertices and unit normal come from its shade record, its Ke from the material record of
+//     (id - 1) % n_base_tris; s = sample(v0, v1, v2, nl, x, nf, u_a, u_b, L).
+//   * If s.valid, ONE closest-hit query goes from x along s.wd, with the launch's tmax and the path's own closest_hit<BVH>, tie
+//     rule included; if it returns id, the pixel's radiance R gains ((T.c * Ke.c) * s.g) per channel c: two multiplies in that
+//     order, one addition into R, a rounding each.  The query counts as a ray for pixels inside the count rows.
+//   * The path's SAMPLED BIT is set by such a hit whether or not the sample was valid; a specular or dielectric hit takes no light
+//     draw (its random stream is unchanged) and clears it; the primary ray starts with it clear.  The bounce then takes its two
+//     draws as before.  A path's last segment takes no light draw and sends no query (with samples_per_pixel > 1 its two rng_skip
+//     stay two).
+//   * A path that meets an emissive triangle with the bit set ends with terminal colour 0, with the bit clear with T * Ke as
+//     without the flag.  The analytic sphere light, the sky and the end of the segment budget end a path as without the flag: none
+//     of them is sampled.
+//   * The pixel stores R + terminal, one addition per channel; with samples_per_pixel > 1 that value goes into the sample sum and
+//     R restarts at 0 for every sample.  With demodulation T at segment 0 lacks the first albedo, so the gain of segment 0 is
+//     illumination, like the terminal colour; an emitter seen directly stores albedo (1, 1, 1).
 //
 // The estimator at a diffuse hit x with shading normal nf (faced against the ray) and albedo alb already in the throughput T:
 //   light i uniform among the L entries of the scene's light list, y uniform on it by area (pdf 1 / (L * area)),
@@ -11,6 +34,7 @@
 #pragma once
 
 #include "closest_hit.hpp"
+#include "light_list_host.hpp"
 
 namespace rt {
 namespace light {
@@ -18,6 +42,7 @@ namespace light {
 constexpr float k2Pi = 6.28318548202514648f;  // the binary32 nearest 2 pi
 constexpr uint32_t kMaxLights = 1u << 24;     // u_l has 24 bits: a longer list would have entries the pick never reaches (the
                                               // bound a light list has to keep; the self test is told L)
+static_assert(kMaxLights == rtpt_light::kMaxLights, "the host refuses the lists the pick cannot reach");
 
 // entry of a list of L > 0 lights that draw u_l in [0, 1) picks
 __device__ __forceinline__ uint32_t pick(float u_l, uint32_t L) {

@@ -41,6 +41,14 @@ inline void with_mode3(int mode, F&& f) {
   else
     f(std::integral_constant<int, 0>{});
 }
+// ... and for a mode of 0 to 3: shade_segment's material axis in the tile kernels, whose fourth value samples lights (spec_mode)
+template <class F>
+inline void with_mode4(int mode, F&& f) {
+  if (mode == 3)
+    f(std::integral_constant<int, 3>{});
+  else
+    with_mode3(mode, f);
+}
 // f(FINAL, EXACT): the two bools every filter kernel is instantiated over
 template <class F>
 inline void with_final_exact(bool final_pass, bool exact, F&& f) {

@@ -1,0 +1,134 @@
+"""Next-event estimation without a device (RTPT_FLAG_EXT_NEE; csrc/light_sample.hpp states the rules): the numpy path walker of
+tests/nee_paths.py, which tests/test_nee_paths_gpu.py holds the tile kernels to bit for bit, is first held to
+dielectric_scenes.walk where no light is sampled, then to the estimator it replaces — the mean of its frames against the mean of
+the flag-off walker's, the integral both estimate; the light list's rule on hand-made cases and in a program of its own under
+the sanitizers (csrc/tests/light_list_host_check.cpp); and every entry point of the binding has its ctypes signature."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import dielectric_scenes as DS
+import nee_paths as NP
+import nee_scenes as N
+import pathtrace_scenes as P
+from conftest import ROOT, bits
+
+from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi
+
+F32, U32 = np.float32, np.uint32
+CSRC = os.path.join(ROOT, "real_time_path_tracing_with_spatiotemporal_filtering_amd", "csrc")
+W1, H1 = N.SIZES[1]
+ESTIMATOR_FRAMES = 8192
+
+
+# ------------------------------------------------------------------------------------------ the walker is gated first
+@pytest.mark.parametrize("segments", [9, 33])
+@pytest.mark.parametrize("form", ["small", "pairs"])
+def test_walker_without_lights_is_the_dielectric_walker(oracle, form, segments):
+    """the glass room (diffuse, mirror-free, dielectric and emissive hits) at 70 x 10: with an empty list — NEE off, or L = 0 —
+    walk_nee takes no light draw and is dielectric_scenes.walk bit for bit, IMAGE, HIT_ID and rays; and a room whose lamp is dark has
+    an empty list of its own"""
+    scene, glass = DS.glass_room(form)
+    rec = DS.records(scene, None, glass)
+    want = DS.walk(oracle, scene, W1, H1, segments, rec)
+    got = NP.walk_nee(oracle, scene, W1, H1, segments, rec, np.zeros(0, U32))
+    assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and np.array_equal(got["HIT_ID"], want["HIT_ID"])
+    assert got["rays"] == want["rays"] and got["samples"] == 0
+    dark = scene._replace(materials=P._frozen(np.where(np.arange(6)[None, :] >= 3, 0, np.asarray(scene.materials))))
+    rec_dark = DS.records(dark, None, glass)
+    assert len(NP.light_list(dark, 1, rec_dark)) == 0 and len(NP.light_list(scene, 1, rec)) == (2 if form == "small" else 18)
+    if segments == 9:
+        want = DS.walk(oracle, dark, W1, H1, segments, rec_dark, spp=2)
+        got = NP.walk_nee(oracle, dark, W1, H1, segments, rec_dark, NP.light_list(dark, 1, rec_dark), spp=2)
+        assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and got["rays"] == want["rays"]
+
+
+# ------------------------------------------------------------------------------------------ the estimator is right
+def test_nee_estimates_what_the_path_tracer_estimates(oracle):
+    """nee_scenes.receiver() at 70 x 10, two segments, pixel_jitter 0, frames 0 .. N - 1: the per-pixel mean of walk_nee's frames
+    against the mean of the flag-off walker's (dielectric_scenes.walk, the code the oracle pins) — the same integral, the lamp seen
+    by a sample from the first hit on one side and by running into it on the other — within 5 standard errors of the difference
+    at every pixel and channel, none left out; and the summed per-pixel variance of the NEE frames is below the flag-off frames'.
+    At 70 x 10 the frame is seven times wider than tall: 160 pixels meet the receiver, the other 540 see the sky along their
+    unjittered primary ray in every frame, where both walkers store the same bits and the standard error is 0 — there the
+    difference has to be exactly 0 (z = 0), and anything else counts as beyond every bar.
+    N = 8192: Lambert's form factor of the lamp is at least 0.00165 at every hit point (asserted below; the receiver's far
+    corner), so the flag-off side expects at least 13.5 lamp hits at every pixel and 44 at the median one; with 1,024 frames the
+    far pixels would expect 1.7, and a pixel without a single hit misses the lamp's term altogether.
+    Measured: max |z| 3.21 over 2100 values (none above 4); summed variance NEE / flag-off 0.234."""
+    scene = N.receiver()
+    rec = DS.records(scene)
+    lights = NP.light_list(scene)
+    assert list(lights) == [3, 4]
+    n = ESTIMATOR_FRAMES
+    on = np.zeros((n, H1 * W1 * 3), F32)
+    off = np.zeros_like(on)
+    for f in range(n):
+        on[f] = NP.walk_nee(oracle, scene, W1, H1, 2, rec, lights, frame=f)["IMAGE"][..., :3].ravel()
+        off[f] = DS.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
+    a, b = on.astype(np.float64), off.astype(np.float64)
+    se = np.sqrt(a.var(0, ddof=1) / n + b.var(0, ddof=1) / n)
+    diff = a.mean(0) - b.mean(0)
+    with np.errstate(all="ignore"):
+        z = np.where(se > 0, diff / se, np.where(diff == 0, 0.0, np.inf))      # no pixel is left out
+    assert (se > 0).sum() == 3 * 160 and ((se > 0) | (bits(on[0]) == bits(off[0]))).all()
+    ratio = a.var(0, ddof=1).sum() / b.var(0, ddof=1).sum()
+    print(f"NEE vs flag-off, {W1} x {H1} x {n} frames: max |z| {np.abs(z).max():.2f} over {z.size} values (above 4: {(np.abs(z) > 4).sum()}), "
+          f"variance ratio {ratio:.3f}")
+    assert np.abs(z).max() <= 5.0
+    assert ratio < 1.0
+
+
+def test_receiver_form_factor_bounds_the_frame_count(oracle):
+    """the reasoning behind ESTIMATOR_FRAMES: the lamp's form factor at the receiver's hit points"""
+    hit = DS.walk(oracle, N.receiver(), W1, H1, 1, DS.records(N.receiver()))["HIT_ID"]
+    ys, xs = np.nonzero(hit)
+    assert len(ys) == 160 and set(hit[ys, xs]) == {1, 2}
+    ux, uy = (2 * (xs + 0.5) - W1) / H1, -(2 * (ys + 0.5) - H1) / H1       # raytrace.comp.glsl:315-316, pixel_jitter 0
+    x = np.stack([N.RECEIVER_CAM[2] * N.RECEIVER_SLOPE * ux, N.RECEIVER_CAM[2] * N.RECEIVER_SLOPE * uy, np.zeros(len(xs))], 1)
+    ff = N.form_factor(N.RECEIVER_LAMP, x, np.broadcast_to([0.0, 0.0, 1.0], x.shape))
+    assert ff.min() >= 0.00165 and ff.min() * ESTIMATOR_FRAMES >= 13.5 and np.median(ff) * ESTIMATOR_FRAMES >= 44
+
+
+# ------------------------------------------------------------------------------------------ the light list
+def test_light_list_cases():
+    """light_list on hand-made tables: no emitter, every triangle, 1 to 3 instances, the last triangle of the last instance, and a
+    specular or dielectric record, which carries no Ke"""
+    mk = lambda tri_material, ke: P.Scene("t", "small", None, None, None, None, None, None, np.asarray(tri_material, np.uint32),
+                                          P._frozen(np.concatenate([np.full((len(ke), 3), 0.5), np.asarray(ke, np.float64).reshape(-1, 3)], 1)))
+    dark, lamp, blue = (0, 0, 0), (4, 3, 2), (0, 0, 1e-30)
+    for ni in (1, 2, 3):
+        assert len(NP.light_list(mk([0, 0, 0], [dark]), ni)) == 0
+        assert list(NP.light_list(mk([1, 2, 1], [dark, lamp, blue]), ni)) == list(range(1, 3 * ni + 1))
+        got = NP.light_list(mk([0, 0, 0, 0, 2], [dark, lamp, blue]), ni)
+        assert list(got) == [5 * i + 5 for i in range(ni)] and got.dtype == U32
+        got = NP.light_list(mk([0, 1, 0, 2, 0, 0, 1], [dark, lamp, blue]), ni)
+        assert list(got) == sorted(7 * i + t + 1 for i in range(ni) for t in (1, 3, 6))
+    sc = mk([0, 1, 2, 1], [lamp, lamp, lamp])
+    rec = DS.records(sc, {1: ((0.9, 0.9, 0.9), 0.0)}, {2: ((1, 1, 1), 1.5)})
+    assert list(NP.light_list(sc, 2, rec)) == [1, 5]
+
+
+def test_light_list_host_check(tmp_path):
+    """`make -C csrc light-list-host-check`: csrc/light_list_host.hpp on both material struct types, 1 to 3 instances and the bound of
+    2^24 entries from either side, under the address and undefined-behaviour sanitizers"""
+    out = subprocess.run(["make", "-C", CSRC, "light-list-host-check", f"OBJDIR={tmp_path}"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "light_list_host_check: ok" in out.stdout.splitlines()
+
+
+# ------------------------------------------------------------------------------------------ the binding
+def test_every_exported_symbol_has_a_signature(hip_lib):
+    """every name of abi.SYMBOLS that the library exports has argtypes: a pointer passed through ctypes without them is truncated
+    to an int.  And the new entry point is in the header, the list and the library, the flag in both"""
+    lib = hip_lib.load()
+    missing = [s for s in abi.SYMBOLS if hasattr(lib, s) and getattr(lib, s).argtypes is None]
+    assert not missing, missing
+    header = open(os.path.join(ROOT, "include", "rtpt.h")).read()
+    assert "rtpt_debug_light_list" in abi.SYMBOLS and hasattr(lib, "rtpt_debug_light_list")
+    assert "int rtpt_debug_light_list(rtpt_ctx* ctx, uint32_t* ids, uint32_t cap, uint32_t* n);" in header
+    assert "#define RTPT_FLAG_EXT_NEE 0x10000u" in header and abi.FLAG_EXT_NEE == 0x10000
+    assert "#define RTPT_ABI_VERSION 5" in header
+    assert lib.rtpt_debug_light_list(None, None, 0, None) == abi.RTPT_E_INVALID
