@@ -217,6 +217,33 @@ typedef struct rtpt_visibility_data {
                                       rtpt_resize keep the list; rtpt_scene_upload drops it with the materials.  Additive: the ABI
                                       version stays 5 */
 
+#define RTPT_FLAG_EXT_NEE_SPHERE 0x20000u /* next-event estimation of the ANALYTIC SPHERE LIGHT (NOT reference behaviour, default off;
+                                      DESIGN.md 8, csrc/light_sample.hpp states the rules and the arithmetic): independent of
+                                      RTPT_FLAG_EXT_NEE and combinable with it; without it every frame, ray count and kernel is
+                                      that of a context without it, bit for bit.
+                                      At a DIFFUSE hit that is not the path's last segment (seg + 1 < max_segments), where the
+                                      triangle sample sits — after the albedo, the faceforward and the offset origin x, before the
+                                      bounce's two draws — two draws u_c, u_p (behind the triangle sample's three where that one is
+                                      taken; drawn whether or not the sample is valid; a specular or dielectric hit and a last
+                                      segment take none) pick a direction in the cone the light subtends from x:
+                                      dc = c - x, d2 = dot(dc, dc), w = normalize(dc), q = r2 / d2, cm = sqrt(1 - q),
+                                      k = q / (1 + cm), ct = fma(-u_c, k, 1), st = sqrt(max(0, fma(-ct, ct, 1))),
+                                      (sp, cp) = sincos2pi(u_p), (t, b) the branch-free orthonormal pair around w that
+                                      light_sample.hpp states, wd = normalize((st cp) t + (st sp) b + ct w), cs = dot(nf, wd).
+                                      TAKEN when d2 > r2 (NaN fails, x inside or on the sphere fails); VALID when taken and cs > 0.
+                                      A valid sample adds ((T.c * light_col.c) * g) per channel to the pixel's radiance R,
+                                      g = (2 cs) k, light_col never light_col_first; no query is sent and no ray is counted (the
+                                      reference's light is never occluded).  Where a hit takes both samples the sphere's gain goes
+                                      into R first, the triangle's after its shadow query.  The path's SPHERE BIT is set by a
+                                      diffuse non-last hit whose sample was taken, valid or not, cleared by one whose sample was not
+                                      taken and by a specular or dielectric hit, and clear on the primary ray; a segment that meets
+                                      the sphere light with the bit set ends the path with terminal colour 0, with the bit clear as
+                                      without the flag.  The bit does not touch emissive triangles, RTPT_FLAG_EXT_NEE's sampled bit
+                                      not the sphere.  With RTPT_FLAG_EXT_DEMODULATE the gain of segment 0 is illumination.
+                                      Such a launch has the limits of a RTPT_FLAG_EXT_NEE launch, whatever the scene's materials:
+                                      every segment in the tile kernel, no queue kernels, no deferred final filter pass.
+                                      Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -761,6 +788,11 @@ int rtpt_selftest_refract(rtpt_ctx* ctx, const float* in, float* out, size_t n);
  * min(uint(u_l * L), L - 1) as a uint32).  The light's unit normal is computed as for its shade record.  Operands are not
  * checked; L is meant to be in [1, 2^24]. */
 int rtpt_selftest_light_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
+/* The sphere sample of RTPT_FLAG_EXT_NEE_SPHERE (csrc/light_sample.hpp: sphere_sample), one case per thread: in = n x 12 words
+ * (x[3] the bounce origin, nf[3] the faced normal, c[3] the light's centre, r2 its squared radius, u_c, u_p as floats), out = n x
+ * 6 words (wd[3], g, 1.0f if taken else 0.0f, 1.0f if valid else 0.0f as floats; wd and g are written as 0 where the sample is
+ * not taken).  Operands are not checked.  Additive: RTPT_ABI_VERSION stays 5. */
+int rtpt_selftest_sphere_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
 /* The light list of RTPT_FLAG_EXT_NEE as it stands on the device: *n = its entries (0 without the flag, without materials or
  * without an emitter), of which the first min(*n, cap) are copied to ids — id + 1 of every posed triangle inst * n_tris + t whose
  * material has Ke != 0, ascending.  ids may be NULL when cap is 0 (count only). */

@@ -31,6 +31,7 @@ FLAG_DEVICE_BVH_SAH = 0x2000  # with FLAG_DEVICE_BVH_BUILD: the device SAH build
 FLAG_EXT_DEMODULATE = 0x8000  # filter illumination, multiply the first hit's albedo back afterwards (modulate / present); not in FLAG_EXT_MASK
 FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms -> triangles and the fan-pair test on the device (csrc/scene_flatten.hip)
 FLAG_EXT_NEE = 0x10000  # next-event estimation: rtpt_raytrace samples the scene's emissive triangles (csrc/light_sample.hpp); not in FLAG_EXT_MASK
+FLAG_EXT_NEE_SPHERE = 0x20000  # next-event estimation of the analytic sphere light: every diffuse hit samples its cone, no shadow ray (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -149,7 +150,7 @@ SYMBOLS = [
     "rtpt_selftest_texture_lod", "rtpt_selftest_texture_footprint", "rtpt_util_texture_chain", "rtpt_selftest_contract",
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
     "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
-    "rtpt_selftest_light_sample", "rtpt_debug_light_list",
+    "rtpt_selftest_light_sample", "rtpt_debug_light_list", "rtpt_selftest_sphere_sample",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -239,6 +240,7 @@ def load() -> C.CDLL:
         "rtpt_selftest_refract": [vp, vp, vp, sz],
         "rtpt_selftest_light_sample": [vp, vp, vp, sz],
         "rtpt_debug_light_list": [vp, vp, u32, C.POINTER(u32)],
+        "rtpt_selftest_sphere_sample": [vp, vp, vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -668,6 +670,14 @@ class Context:
         cases = np.ascontiguousarray(cases, np.uint32).reshape(-1, 19)
         out = np.zeros((len(cases), 9), np.uint32)
         _check(self._lib.rtpt_selftest_light_sample(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def selftest_sphere_sample(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 6] uint32 words (wd, g, taken, valid as floats; wd and g 0 where not taken) of the device's sphere sample on cases
+        [n, 12] words = x, nf, c, r2, u_c, u_p as floats (rtpt_selftest_sphere_sample)"""
+        cases = np.ascontiguousarray(cases, np.uint32).reshape(-1, 12)
+        out = np.zeros((len(cases), 6), np.uint32)
+        _check(self._lib.rtpt_selftest_sphere_sample(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
 
     def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:

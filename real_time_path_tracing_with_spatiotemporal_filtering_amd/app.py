@@ -756,7 +756,7 @@ class PathTracingApplication:
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
-             specular=False, dielectric=False, nee=False, **app_kw):
+             specular=False, dielectric=False, nee=False, nee_sphere=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -771,9 +771,14 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     `nee` (off by default): next-event estimation, abi.FLAG_EXT_NEE on every context of this rank — every diffuse hit samples one of
     the triangles whose material has a Ke.  It is `flags=abi.FLAG_EXT_NEE` by another name: the lamps come from the material
     table, which `textures`, `specular`, `dielectric` or the caller's own set_materials / set_materials_ext call provides;
-    without a table no frame changes."""
+    without a table no frame changes.
+    `nee_sphere` (off by default): next-event estimation of the analytic sphere light, abi.FLAG_EXT_NEE_SPHERE on every context of
+    this rank — every diffuse hit samples the cone the light subtends, without a shadow ray.  It is
+    `flags=abi.FLAG_EXT_NEE_SPHERE` by another name, needs no material table and may be combined with `nee`."""
     if nee:
         flags |= abi.FLAG_EXT_NEE
+    if nee_sphere:
+        flags |= abi.FLAG_EXT_NEE_SPHERE
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())
     if torch_planes is None:
         torch_planes = world > 1  # halo exchange and the history all-gather move rows of torch-owned planes

@@ -179,7 +179,8 @@ rt::TexView tex_view(const rtpt_ctx* c) {
 }
 
 rt::LightView light_view(const rtpt_ctx* c) {
-  return rt::LightView{static_cast<const uint32_t*>(c->scene.lights.ptr), c->scene.n_lights};
+  const bool list = c->scene.lights.ptr && c->scene.materials.ptr;  // (the list is built beside the records and dropped with them)
+  return rt::LightView{list ? static_cast<const uint32_t*>(c->scene.lights.ptr) : nullptr, list ? c->scene.n_lights : 0u};
 }
 
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose

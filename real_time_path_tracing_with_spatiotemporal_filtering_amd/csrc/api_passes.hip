@@ -142,8 +142,12 @@ void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, fl
 
 // launch_pathtrace's `specular`: rt::kSpecNee when the launch samples lights — the context has RTPT_FLAG_EXT_NEE and the scene's
 // light list has entries (then it has material records too: the list is built beside them and dropped with them) — else what
-// the materials ask for.  Without the flag, or with an empty list, every choice below is the one of a context without the flag
+// the materials ask for.  Without the flag, or with an empty list, every choice below is the one of a context without the flag.
+// A context with RTPT_FLAG_EXT_NEE_SPHERE samples the analytic sphere light, whatever the scene's materials or light list:
+// rt::kSpecNeeSphere, the kernels that sample both kinds (the triangles where the list has entries).  Such a launch has a
+// sampling launch's limits (every segment in the tile kernel, no queue kernels, no path pool, no deferred final pass)
 int trace_material_mode(const rtpt_ctx* c) {
+  if (c->cfg.flags & RTPT_FLAG_EXT_NEE_SPHERE) return rt::kSpecNeeSphere;
   const bool nee = (c->cfg.flags & RTPT_FLAG_EXT_NEE) && c->scene.n_lights > 0 && c->scene.lights.ptr && c->scene.materials.ptr;
   return nee ? rt::kSpecNee : c->scene.materials_specular;
 }
@@ -169,7 +173,7 @@ int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
   a.queue_count = nullptr;
   a.queue_region = 0;
   if (!(a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS))) return RTPT_OK;
-  if (trace_material_mode(c) == rt::kSpecNee) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
+  if (trace_material_mode(c) >= rt::kSpecNee) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
   const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
   const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
   const size_t cap = region * rt::kPathQueues;

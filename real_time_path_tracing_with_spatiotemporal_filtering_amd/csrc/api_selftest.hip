@@ -157,6 +157,25 @@ int rtpt_selftest_light_sample(rtpt_ctx* c, const uint32_t* in, uint32_t* out, s
   return RTPT_OK;
 }
 
+int rtpt_selftest_sphere_sample(rtpt_ctx* c, const uint32_t* in, uint32_t* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * 12 * sizeof(uint32_t), out_bytes = n * 6 * sizeof(uint32_t);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_sphere_sample(static_cast<const uint32_t*>(din.ptr), static_cast<uint32_t*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_sphere_sample: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_trace(rtpt_ctx* c, const float* rays, size_t n, uint32_t* out_id, float* out_t) {
   if (!c || !rays || !out_id) return fail(RTPT_E_INVALID, "NULL argument");
   if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");

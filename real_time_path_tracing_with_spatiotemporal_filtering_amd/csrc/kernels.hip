@@ -179,35 +179,36 @@ void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
   gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex);
 }
 
-// The same four kernels for launches that sample lights (SPEC = 3, RTPT_FLAG_EXT_NEE on a scene with a light list): overloads
+// The same four kernels for launches that sample lights (SPEC = 3, RTPT_FLAG_EXT_NEE on a scene with a light list; SPEC = 4,
+// RTPT_FLAG_EXT_NEE_SPHERE: the sphere light too, and the list may be empty): overloads
 // that take the list as a parameter of their own behind TexView (kernels.hpp: LightView), so that the argument segments of the
 // kernels above stay what they were.
 template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
   pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
 }
 template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
   pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
 }
 template <int BVH, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
   gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
 }
 template <bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC == 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
   gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
 }
 
@@ -424,8 +425,11 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   }
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
-  const bool nee = spec_mode(specular) == 3;  // the launch samples lights: the SPEC = 3 tile kernels, all segments in them
-  if (nee && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();  // (api_passes.hip: trace_material_mode)
+  const bool nee = spec_mode(specular) >= 3;  // the launch samples lights: the SPEC = 3 / 4 tile kernels, all segments in them
+  // (api_passes.hip: trace_material_mode) SPEC = 3 samples the triangles of a list that has entries; 4 the sphere light, and the
+  // triangles where the list has entries
+  if (spec_mode(specular) == 3 && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
+  if (spec_mode(specular) == 4 && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
   const bool pool = !nee && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
@@ -478,10 +482,10 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       with_mode3(tex_mode(tex), [&](auto tmode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tmode)::value;
         // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE: those that
-        // sample lights too (3), which take the light list as one more argument
-        with_mode4(spec_mode(specular), [&](auto spec) {
+        // sample lights too (3), RTPT_FLAG_EXT_NEE_SPHERE: and the sphere light (4), which take the light list as one more argument
+        with_mode5(spec_mode(specular), [&](auto spec) {
           constexpr int S = decltype(spec)::value;
-          if constexpr (S == 3) {
+          if constexpr (S >= 3) {
             // (the launch syntax, because these kernels are OVERLOADS of the names below: an overload set is no argument for
             // hipLaunchKernelGGL's deduced kernel type, a call resolves it by its arguments)
             if (gb) {

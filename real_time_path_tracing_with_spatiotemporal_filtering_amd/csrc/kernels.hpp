@@ -62,6 +62,8 @@ struct TexView {
 // emissive triangle, ascending; n in [1, 2^24] where a kernel reads it.  It travels as a parameter of its own behind TexView, and
 // only of the kernels that sample lights (kernels.hip: the overloads of the four tile kernels that take a LightView), for TexView's reason: inside SceneView the pointer would move
 // every later field of PathtraceArgs / GbufferArgs, and behind TexView it would change the argument segment of every tracing kernel.
+// The kernels that sample the sphere light too (RTPT_FLAG_EXT_NEE_SPHERE, SPEC = 4) take it the same way; there ids may be NULL
+// and n 0: no triangle is sampled.
 struct LightView {
   const uint32_t* ids;
   uint32_t n;
@@ -69,6 +71,9 @@ struct LightView {
 // launch_pathtrace's `specular` for a launch that samples lights: the SPEC = 3 instantiations, which include the specular and
 // dielectric bounces (Scene::materials_specular is 0, 1 or 2)
 constexpr int kSpecNee = 3;
+// ... and for a launch of a context with RTPT_FLAG_EXT_NEE_SPHERE: the SPEC = 4 instantiations, SPEC = 3 plus the sample of the
+// analytic sphere light, whatever the scene's materials or light list
+constexpr int kSpecNeeSphere = 4;
 
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
 // and the same columns of row min(2y + 1, sh - 1) of level l (texture_mips.hip): one launch per level.  src and dst are texel
@@ -348,7 +353,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // specular: 1 some triangle's material is specular, 2 some triangle's is a dielectric, 0 neither (Scene::materials_specular) — what
 // selects the SPEC instantiations; it travels
 // beside the kernel arguments, not in them, so that every existing argument offset stays.  kSpecNee (then `lights` has entries):
-// the launch samples lights, every segment runs in the tile kernel (no queue kernels) and it carries no final pass
+// the launch samples lights, every segment runs in the tile kernel (no queue kernels) and it carries no final pass; the same for
+// kSpecNeeSphere, whose `lights` may be empty
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -440,6 +446,8 @@ void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t 
 // light::pick and light::sample (light_sample.hpp) on n cases of 19 words (v0, v1, v2, x, nf, u_l, u_a, u_b, L): out = n x (y, wd,
 // g, valid as 1.0f / 0.0f, the picked entry)
 void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
+// light::sphere_sample on n cases of 12 words (x, nf, c, r2, u_c, u_p): out = n x (wd, g, taken, valid), 6 words
+void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 // tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs

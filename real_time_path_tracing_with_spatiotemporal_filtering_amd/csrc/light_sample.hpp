@@ -1,6 +1,7 @@
 // light_sample.hpp — the light sample of next-event estimation: one point on one emissive triangle per diffuse hit, stated once.
 // The SPEC = 3 instantiations of the tile kernels call it (shade_segment.hpp, pathtrace_tile.hpp), and the self test
-// (rtpt_selftest_light_sample, k_selftest_light_sample).  Not reference behaviour: the reference collects light only by hitting
+// (rtpt_selftest_light_sample, k_selftest_light_sample).  Below it, the sample of the analytic sphere light (sphere_sample,
+// RTPT_FLAG_EXT_NEE_SPHERE), which the SPEC = 4 instantiations call besides.  Not reference behaviour: the reference collects light only by hitting
 // it.  Contract functions only (rtpt_math.hpp), no new transcendental; tests/nee_scenes.py restates every step in numpy float32,
 // tests/nee_paths.py walks whole paths with it.
 //
@@ -73,6 +74,69 @@ __device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf
   const float a2 = exact::sqrt_(exact::dot(c, c));
   s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
   s.g = exact::div_((cs * cl) * (a2 * static_cast<float>(L)), k2Pi * r2);
+  return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// THE SPHERE SAMPLE (RTPT_FLAG_EXT_NEE_SPHERE, independent of RTPT_FLAG_EXT_NEE and combinable with it; without the flag frames,
+// ray counts and the kernels chosen are those of a context without it, bit for bit): one direction inside the cone the analytic
+// sphere light (centre c = lightPos, squared radius r2 = PathtraceArgs::light_r2) subtends from x.  ray_hits_light tests the
+// sphere whatever the triangle hit distance — the light is never occluded — so the sample needs no shadow query: no query is sent
+// and no ray is counted.  tests/nee_sphere.py restates every step in numpy float32 and walks whole paths with it.
+//   * Where: at a DIFFUSE hit that is not the path's last segment (seg + 1 < max_segments), the triangle sample's place: after the
+//     albedo, the faceforward and the offset origin x = o, before the bounce's two draws.
+//   * Draws: two, u_c then u_p, behind the triangle sample's three where that one is taken and in front of the bounce's two; taken
+//     whether or not the sample turns out valid.  A specular or dielectric hit takes none, nor does a last segment (with
+//     samples_per_pixel > 1 its two rng_skip stay two).
+//   * The sample: sphere_sample below, step by step.  TAKEN when d2 > r2 (NaN fails; x inside or on the sphere fails: every bounce
+//     from there hits the light anyway).  VALID when taken and cs = dot(nf, wd) > 0.
+//   * Weight g = (2 cs) k with k = 1 - cos(theta_max): the bounce's pdf is cs / pi and the cone's 1 / (2 pi k), so a bounce that
+//     returns T * light_col on a hit has the expectation of (T * light_col) * g.  The colour is PathtraceArgs::light_col, never
+//     light_col_first: the sample stands for a hit at segment >= 1.  A valid sample adds ((T.c * light_col.c) * g) per channel c to
+//     the pixel's radiance R: two multiplies in this order, one addition, a rounding each.
+//   * Where a hit takes both samples the sphere's gain goes into R first, the triangle's after its shadow query.
+//   * The path's SPHERE BIT (0x200 of the pix word through the compaction, beside the sampled bit 0x100): set by a diffuse non-last
+//     hit whose sample was taken, valid or not; cleared by a diffuse hit whose sample was not taken and by a specular or dielectric
+//     hit; clear on the primary ray.  A segment whose ray_hits_light is true with the bit set ends the path with terminal colour
+//     0, with the bit clear as without the flag.  The bit does not touch emissive triangles, the sampled bit not the sphere.
+//   * With demodulation T at segment 0 lacks the first albedo, so the gain of segment 0 is illumination, as the triangle's.
+struct SphereSample {
+  f3 wd;       // unit direction from x into the cone
+  float g;     // the weight of (T * light_col)
+  bool taken;  // d2 > r2
+  bool valid;  // taken and the direction leaves the surface
+};
+
+// x: the bounce origin; nf: the hit's normal, faced against the arriving ray; c, r2: the light; u_c, u_p: the two draws
+__device__ __forceinline__ SphereSample sphere_sample(f3 x, f3 nf, f3 c, float r2, float u_c, float u_p) {
+  SphereSample s;
+  const f3 dc = c - x;
+  const float d2 = exact::dot(dc, dc);
+  const f3 w = exact::normalize(dc);
+  const float q = exact::div_(r2, d2);                  // sin^2(theta_max)
+  const float cm = exact::sqrt_(1.0f - q);              // cos(theta_max); NaN where q > 1: not taken
+  const float k = exact::div_(q, 1.0f + cm);            // 1 - cm without the cancellation of a far light (LIGHT_FAR: q = 1.6e-9)
+  const float ct = fmaf_(-u_c, k, 1.0f);                // uniform in [cm, 1]
+  const float st = exact::sqrt_(glsl_max(0.0f, fmaf_(-ct, ct, 1.0f)));  // glsl_max: 0 where the operand is NaN
+  float sp, cp;
+  exact::sincos2pi(u_p, sp, cp);
+  // an orthonormal pair (t, b) around w, branch-free and without a singular direction (Duff et al. 2017, the copysign form):
+  //   sg = copysign(1, w.z);  a = -1 / (sg + w.z);  b_ = (w.x * w.y) * a;  sx = sg * w.x
+  //   t = (fma(sx, w.x * a, 1), sg * b_, -sx),  b = (b_, fma(w.y, w.y * a, sg), -w.y)
+  const float sg = __builtin_copysignf(1.0f, w.z);
+  const float a = exact::div_(-1.0f, sg + w.z);
+  const float b_ = (w.x * w.y) * a;
+  const float sx = sg * w.x;
+  const f3 t{fmaf_(sx, w.x * a, 1.0f), sg * b_, -sx};
+  const f3 b{b_, fmaf_(w.y, w.y * a, sg), -w.y};
+  // v = (st cp) t + (st sp) b + ct w, per channel fma(ct, w, fma(st sp, b, (st cp) * t))
+  const float ac = st * cp, as = st * sp;
+  s.wd = exact::normalize(f3{fmaf_(ct, w.x, fmaf_(as, b.x, ac * t.x)), fmaf_(ct, w.y, fmaf_(as, b.y, ac * t.y)),
+                             fmaf_(ct, w.z, fmaf_(as, b.z, ac * t.z))});
+  const float cs = exact::dot(nf, s.wd);
+  s.taken = d2 > r2;  // NaN fails
+  s.valid = s.taken && (cs > 0.0f);
+  s.g = (2.0f * cs) * k;
   return s;
 }
 

@@ -96,7 +96,8 @@ constexpr int kPtWaves = 8;
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
 // TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (1, specular.hpp) and dielectric
-// ones too (2, dielectric.hpp), and samples the scene's lights besides (3, light_sample.hpp; `lights` then has entries).
+// ones too (2, dielectric.hpp), and samples the scene's lights besides (3, light_sample.hpp; `lights` then has entries), and the
+// analytic sphere light too (4; `lights` may then be empty).
 // the tile grid's width / a tile's linear index, where pathtrace_tile used to read gridDim.x / compute the index (every use keeps
 // its place, so that the ROLE = 0 instantiations compile to what they were)
 template <int ROLE>
@@ -125,12 +126,12 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   // per-pixel sample accumulators and RNG state between samples: behind the shared region, allocated (by
   // launch_pathtrace) only when spp > 1 — the reference runs 1 spp (raytrace.comp.glsl:306); spp > 1 is an EXTENSION, see
   // the note at the rng_pix store below
-  // SPEC == 3: the pixel's radiance R, what its light samples collected so far (light_sample.hpp), sits where the sums sit
+  // SPEC >= 3: the pixel's radiance R, what its light samples collected so far (light_sample.hpp), sits where the sums sit
   // otherwise and the sums move behind it; allocated by launch_pathtrace for these instantiations only.  Indexed by the local
   // pixel `pix`, like the sums, because the compaction moves paths between threads; one path per pixel is live at a time, so a
   // plain read-modify-write has no race.  Zeroed at the start of every sample by the thread that starts on the pixel, read where
   // the path ends.
-  constexpr uint32_t kRadWords = SPEC == 3 ? 3u * kPtThreads : 0u;
+  constexpr uint32_t kRadWords = SPEC >= 3 ? 3u * kPtThreads : 0u;
   [[maybe_unused]] float* const rad_r = reinterpret_cast<float*>(stack + a.multi_off);
   [[maybe_unused]] float* const rad_g = rad_r + kPtThreads;
   [[maybe_unused]] float* const rad_b = rad_g + kPtThreads;
@@ -172,7 +173,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   const uint32_t pix0 = tile_pixel(wave, lane);  // the pixel this thread starts on
   uint32_t pix = pix0, rng = 0;
   f3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, -1.f}, acc{1.f, 1.f, 1.f};
-  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false};  // SPEC == 3
+  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false, f3{0.f, 0.f, 0.f}, false, false};  // SPEC >= 3
   {
     const int x = tile_x0 + static_cast<int>(pix0 & 63u), y = tile_y0 + static_cast<int>(pix0 >> 6);
     rng = exact::rng_seed(static_cast<uint32_t>(x), static_cast<uint32_t>(y), a.frame, a.batch);  // :297
@@ -185,10 +186,11 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       pix = pix0;
       rng = rng_pix[pix0];  // the pixel's RNG state after its previous sample (stored at path end)
     }
-    if constexpr (SPEC == 3) {
+    if constexpr (SPEC >= 3) {
       // (smp > 0: behind the barrier above, so the thread that ended this pixel's previous path has read its R)
       rad_r[pix0] = rad_g[pix0] = rad_b[pix0] = 0.0f;
       nee.sampled = false;  // the primary ray
+      if constexpr (SPEC == 4) nee.sphere = false;
     }
     const int px0 = tile_x0 + static_cast<int>(pix0 & 63u), py0 = tile_y0 + static_cast<int>(pix0 >> 6);
     bool alive = (px0 < a.g.W) && (py0 < a.g.y1);
@@ -219,14 +221,24 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
         // the short barycentric divisions where they cost no register: with DEMOD or without compaction they spill one
         constexpr bool kShortDiv = (RTPT_TRACE_ITEMS & 8) && BVH == 0 && COMPACT && !DEMOD;
-        if constexpr (SPEC == 3) nee.valid = false;
+        if constexpr (SPEC >= 3) nee.valid = false;
+        if constexpr (SPEC == 4) nee.sphere_valid = false;
         bool done;
-        if constexpr (SPEC == 3)
+        if constexpr (SPEC >= 3)
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
                                                                    NeeArgs{lights, &nee});
         else
           done = shade_segment<TEX, BVH, kShortDiv, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
-        if constexpr (SPEC == 3) {
+        if constexpr (SPEC >= 3) {
+          // The sphere sample's gain (RTPT_FLAG_EXT_NEE_SPHERE) goes into R first: it needs no query, the order of the two additions
+          // is fixed this way, and the gain is dead before the traversal below starts.
+          if constexpr (SPEC == 4) {
+            if (nee.sphere_valid) {
+              rad_r[pix] += nee.sphere_c.x;
+              rad_g[pix] += nee.sphere_c.y;
+              rad_b[pix] += nee.sphere_c.z;
+            }
+          }
           // The shadow query of the light sample, from the new origin towards the sampled point: the path's own closest hit, so
           // "unoccluded" is "the nearest triangle along the ray is the sampled one", ties resolved as the path resolves them.
           // No new barrier: in the BVH variants the node stack aliases the exchange buffer, which is written and read only
@@ -286,7 +298,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       if (alive) {
         const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(live >> 32),
                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(live), 0u));
-        if constexpr (SPEC == 3)
+        if constexpr (SPEC == 4)
+          st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u) | (nee.sphere ? 0x200u : 0u);  // ... and the sphere bit beside it
+        else if constexpr (SPEC == 3)
           st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u);  // pix has 8 bits: the sampled bit travels with the path
         else
           st.pix[slot] = pix;
@@ -299,8 +313,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       alive = static_cast<uint32_t>(tid) < total;
       if (alive) {
         pix = st.pix[tid];
-        if constexpr (SPEC == 3) {
+        if constexpr (SPEC >= 3) {
           nee.sampled = (pix & 0x100u) != 0u;
+          if constexpr (SPEC == 4) nee.sphere = (pix & 0x200u) != 0u;
           pix &= 0xFFu;
         }
         rng = st.rng[tid];
@@ -393,7 +408,7 @@ template <int BVH, bool DEMOD, int TEX, int SPEC>
 __device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, const GbufferArgs& g, const TexView& tex,
                                                        [[maybe_unused]] const LightView& lights = LightView{nullptr, 0u}) {
   if (blockIdx.y < a.tiles_y) {
-    if constexpr (SPEC == 3)
+    if constexpr (SPEC >= 3)
       pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
     else
       pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex);

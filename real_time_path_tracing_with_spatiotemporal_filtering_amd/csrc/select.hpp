@@ -49,6 +49,14 @@ inline void with_mode4(int mode, F&& f) {
   else
     with_mode3(mode, f);
 }
+// ... and of 0 to 4: the fifth value samples the analytic sphere light as well
+template <class F>
+inline void with_mode5(int mode, F&& f) {
+  if (mode == 4)
+    f(std::integral_constant<int, 4>{});
+  else
+    with_mode4(mode, f);
+}
 // f(FINAL, EXACT): the two bools every filter kernel is instantiated over
 template <class F>
 inline void with_final_exact(bool final_pass, bool exact, F&& f) {

@@ -233,6 +233,20 @@ __global__ void k_selftest_light_sample(const uint32_t* in, uint32_t* out, size_
   r[8] = light::pick(w[15], L);
 }
 
+// light_sample.hpp's sphere_sample, one case per thread: in = x, nf, c, r2, u_c, u_p (12 words); out = wd, g, 1.0f if taken else
+// 0.0f, 1.0f if valid else 0.0f (6 words); wd and g as 0 where the sample is not taken (rtpt_selftest_sphere_sample)
+__global__ void k_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = reinterpret_cast<const float*>(in + 12 * i);
+  const light::SphereSample s = light::sphere_sample(ld3(w), ld3(w + 3), ld3(w + 6), w[9], w[10], w[11]);
+  uint32_t* r = out + 6 * i;
+  r[0] = s.taken ? f2u(s.wd.x) : 0u; r[1] = s.taken ? f2u(s.wd.y) : 0u; r[2] = s.taken ? f2u(s.wd.z) : 0u;
+  r[3] = s.taken ? f2u(s.g) : 0u;
+  r[4] = f2u(s.taken ? 1.0f : 0.0f);
+  r[5] = f2u(s.valid ? 1.0f : 0.0f);
+}
+
 template <int BVH>
 __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const float* rays, size_t n, float tmax,
                                                              uint32_t* out_id, float* out_t) {
@@ -319,6 +333,10 @@ void launch_selftest_bounce(const float* in, float* out, size_t n, hipStream_t s
 void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_light_sample, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_sphere_sample, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
 }
 void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;

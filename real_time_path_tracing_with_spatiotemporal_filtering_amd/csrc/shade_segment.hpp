@@ -112,14 +112,24 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // gains if it does, (T * Ke) * g per channel; the caller sends the query (pathtrace_tile).  nee.sampled is the path's sampled bit:
 // set by such a hit whether or not the sample was valid, cleared by a specular or dielectric one, and an emissive triangle met
 // with the bit set ends the path with colour 0 — its light was already collected at the hit before.
+// SPEC == 4: SPEC == 3 plus the sample of the analytic sphere light (RTPT_FLAG_EXT_NEE_SPHERE; light_sample.hpp states the rules):
+// two more draws (u_c, u_p) behind the triangle sample's three, no query; the gain (T * light_col) * g is left in `nee` (sphere_c,
+// sphere_valid) for the caller to add to R before it sends the triangle's shadow query, and nee.sphere is the path's sphere bit,
+// with which a segment that meets the light ends with colour 0.  Here the triangle sample is taken only where the list has
+// entries (wave-uniform): with the sphere flag alone these instantiations run without a list and without a material table.
+// A compile-time switch because a run-time one cost the SPEC == 3 kernels 3.5 % of a frame with the switch off
+// (profiles/r23_nee_sphere_measure.txt); 3 is the instantiation before it, statement for statement.
 struct NeeState {
   f3 wd;          // the shadow ray's direction, from the path's new origin
   f3 c;           // (T * Ke) * g
   uint32_t id1;   // the sampled triangle, id + 1
   bool valid;     // this segment took a sample whose shadow query is to be sent
   bool sampled;   // the path's sampled bit
+  f3 sphere_c;        // SPEC == 4: (T * light_col) * g of the sphere sample
+  bool sphere_valid;  // ... this segment took a sphere sample that adds sphere_c to R
+  bool sphere;        // ... the path's sphere bit
 };
-// what the SPEC == 3 instantiations take behind alb_px, and what every other one takes there: nothing.  (As two more parameters
+// what the SPEC >= 3 instantiations take behind alb_px, and what every other one takes there: nothing.  (As two more parameters
 // with defaults, a list and a pointer nobody read, the untextured queue kernels came out with their registers renamed.)
 struct NeeArgs {
   LightView lights;
@@ -130,9 +140,12 @@ template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE 
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr,
                                               [[maybe_unused]] NEE nee_args = NEE{}) {
-  static_assert(std::is_same<NEE, NeeArgs>::value == (SPEC == 3), "the instantiations that sample lights, and only they, take NeeArgs");
+  static_assert(std::is_same<NEE, NeeArgs>::value == (SPEC >= 3), "the instantiations that sample lights, and only they, take NeeArgs");
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
+    if constexpr (SPEC == 4) {
+      if (nee_args.st->sphere) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the sphere: this hit's light is counted there
+    }
     if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     return true;
   }
@@ -161,7 +174,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const float4 m0 = m[0], m1 = m[1];
     if (m1.w != 0.0f) {
       acc = acc * f3{m1.x, m1.y, m1.z};
-      if constexpr (SPEC == 3) {
+      if constexpr (SPEC >= 3) {
         if (nee_args.st->sampled) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the lights: this one's emission is counted there
       }
       if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -205,7 +218,8 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   if constexpr (SPEC >= 2) {
     if (diel::is_dielectric(spec_w)) {
-      if constexpr (SPEC == 3) nee_args.st->sampled = false;
+      if constexpr (SPEC >= 3) nee_args.st->sampled = false;
+      if constexpr (SPEC == 4) nee_args.st->sphere = false;
       const bool entering = exact::dot(n, d) < 0.0f;
       if (!entering) n = -n;
       const float u1 = exact::rng_next(rng);                       // :256
@@ -220,27 +234,39 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
-  if constexpr (SPEC == 3) {
+  if constexpr (SPEC >= 3) {
     // next-event estimation (light_sample.hpp): o is the sample's x, n its nf, acc its T
     const LightView lights = nee_args.lights;
     NeeState* const nee = nee_args.st;
     const bool diffuse = !spec::is_specular(spec_w);
     if (diffuse && seg + 1 < a.max_segments) {
-      const float u_l = exact::rng_next(rng);
-      const float u_a = exact::rng_next(rng);
-      const float u_b = exact::rng_next(rng);
-      const uint32_t id1 = lights.ids[light::pick(u_l, lights.n)];
-      const float4* ls = a.scene.shade + 3 * static_cast<size_t>(id1 - 1);
-      const float4 l0 = ls[0], l1 = ls[1], l2 = ls[2];
-      const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
-      const light::Sample sm = light::sample(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, lights.n);
-      nee->wd = sm.wd;
-      nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
-      nee->id1 = id1;
-      nee->valid = sm.valid;
-      nee->sampled = true;
+      if (SPEC == 3 || lights.n > 0) {  // (SPEC == 3: the list has entries; 4: it may be empty — wave-uniform)
+        const float u_l = exact::rng_next(rng);
+        const float u_a = exact::rng_next(rng);
+        const float u_b = exact::rng_next(rng);
+        const uint32_t id1 = lights.ids[light::pick(u_l, lights.n)];
+        const float4* ls = a.scene.shade + 3 * static_cast<size_t>(id1 - 1);
+        const float4 l0 = ls[0], l1 = ls[1], l2 = ls[2];
+        const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
+        const light::Sample sm = light::sample(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, lights.n);
+        nee->wd = sm.wd;
+        nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
+        nee->id1 = id1;
+        nee->valid = sm.valid;
+        nee->sampled = true;
+      }
+      if constexpr (SPEC == 4) {  // the sphere sample: light_c, a.light_r2 and a.light_col are ray_hits_light's light
+        const float u_c = exact::rng_next(rng);
+        const float u_p = exact::rng_next(rng);
+        const light::SphereSample ss = light::sphere_sample(o, n, light_c, a.light_r2, u_c, u_p);
+        const f3 lc = ld3(a.light_col);
+        nee->sphere_c = f3{(acc.x * lc.x) * ss.g, (acc.y * lc.y) * ss.g, (acc.z * lc.z) * ss.g};
+        nee->sphere_valid = ss.valid;
+        nee->sphere = ss.taken;
+      }
     } else if (!diffuse) {
       nee->sampled = false;
+      if constexpr (SPEC == 4) nee->sphere = false;
     }
   }
   float st_, ct;
@@ -263,10 +289,11 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
 // shade_segment's TEX for with_mode3 (select.hpp): 2 the scene has textures and some of them a mip chain (the level table
 // exists), 1 textures without mips, 0 no textures
 inline int tex_mode(const TexView& tex) { return tex.records ? (tex.levels ? 2 : 1) : 0; }
-// shade_segment's SPEC: 3 the launch samples lights (kSpecNee: RTPT_FLAG_EXT_NEE and a light list with entries, whatever the
+// shade_segment's SPEC: 4 the launch samples the analytic sphere light, and the triangles of the light list where it has entries
+// (kSpecNeeSphere: RTPT_FLAG_EXT_NEE_SPHERE), 3 the launch samples lights (kSpecNee: RTPT_FLAG_EXT_NEE and a light list with entries, whatever the
 // materials), 2 some triangle's material is a dielectric, 1 some triangle's is specular and none a dielectric, 0 every material is
 // diffuse
-inline int spec_mode(int specular) { return specular >= kSpecNee ? 3 : (specular == 2 ? 2 : (specular == 1 ? 1 : 0)); }
+inline int spec_mode(int specular) { return specular >= kSpecNeeSphere ? 4 : specular == kSpecNee ? 3 :(specular == 2 ? 2 : (specular == 1 ? 1 : 0)); }
 
 }  // namespace
 }  // namespace rt

@@ -28,6 +28,8 @@ static void usage(const char* argv0) {
       "          [--dielectric  (--specular's rule, and a newmtl with illum 4 / 6 / 7 / 9 and an Ni >= 1 is glass: Fresnel reflection or refraction)]\n"
       "          [--nee  (next-event estimation: every diffuse hit samples one of the triangles whose material has a Ke, one shadow ray each,\n"
       "           RTPT_FLAG_EXT_NEE = --flags 0x10000; on every context of a rank; without an emissive material the frames are unchanged)]\n"
+      "          [--nee-sphere  (next-event estimation of the analytic sphere light: every diffuse hit samples the cone the light subtends,\n"
+      "           no shadow ray, RTPT_FLAG_EXT_NEE_SPHERE = --flags 0x20000; on every context of a rank; needs no materials, combines with --nee)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -89,6 +91,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--exact-filter")) opt.flags |= RTPT_FLAG_EXACT_FILTER;
     else if (!std::strcmp(argv[i], "--demodulate")) opt.flags |= RTPT_FLAG_EXT_DEMODULATE;
     else if (!std::strcmp(argv[i], "--nee")) opt.flags |= RTPT_FLAG_EXT_NEE;
+    else if (!std::strcmp(argv[i], "--nee-sphere")) opt.flags |= RTPT_FLAG_EXT_NEE_SPHERE;
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
     else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
