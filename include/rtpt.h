@@ -244,6 +244,35 @@ typedef struct rtpt_visibility_data {
                                       every segment in the tile kernel, no queue kernels, no deferred final filter pass.
                                       Additive: the ABI version stays 5 */
 
+#define RTPT_FLAG_EXT_NEE_POWER 0x40000u /* next-event estimation picks its emissive triangle BY POWER, not uniformly (NOT reference
+                                      behaviour, default off; DESIGN.md 8, csrc/light_sample.hpp states the rules and the
+                                      arithmetic).  It works together with RTPT_FLAG_EXT_NEE on a scene whose light list has
+                                      entries; alone, or with only RTPT_FLAG_EXT_NEE_SPHERE, it is ignored (as the SAH bit is
+                                      without the build bit), and without it every frame, ray count, kernel and allocation is that
+                                      of a context without it, bit for bit.  It combines with RTPT_FLAG_EXT_NEE_SPHERE, with
+                                      demodulation, textures, samples_per_pixel > 1, strips and two frames in flight exactly where
+                                      RTPT_FLAG_EXT_NEE does.  Every rule of RTPT_FLAG_EXT_NEE holds unchanged — the place of the
+                                      sample, the three draws and their order, the sampled bit, the shadow query and its tie rule,
+                                      R — except two: which entry the draw u_l names, and that float(L) in g becomes inv_p, the
+                                      inverse of the pick's probability.
+                                      Entry i (posed id, vertices from its shade record, Ke from material record (id - 1) %
+                                      n_base_tris) weighs w_i = a2_i * k_i, a2_i the sample's a2 (twice the area), k_i =
+                                      max(|Ke.r|, |Ke.g|, |Ke.b|); a w_i that is NaN, infinite or not > 0 counts as 0: a degenerate
+                                      emitter is never picked.  w_max = max w_i.  q_i = 1 for every entry if w_max == 0 (the uniform
+                                      pick), else max(1, uint32((w_i / w_max) * 65536.0f)) where w_i > 0 and 0 elsewhere.
+                                      C_i = sum_{j <= i} q_j as uint64, S = C_{L-1} <= 2^40; 8 bytes an entry, on a context with both
+                                      bits and L > 0 only, beside the builder's scratch.  Pick: m = uint32(u_l * 2^24),
+                                      t = (uint64(m) * S) >> 24, the entry is the smallest i with C_i > t (binary search),
+                                      inv_p = float(S) / float(q_i) (uint64 -> binary32 to nearest even, a correctly rounded
+                                      division), g = ((cs * cl) * (a2 * inv_p)) / (2 pi * r2).
+                                      The table is built on the device, on the context's stream, when the list joins the scene and
+                                      after every re-pose (rtpt_scene_set_instances, a changed ubo.model, rtpt_scene_rebuild), so
+                                      that it belongs to the posed triangles a trace reads; it is dropped with the list.
+                                      Known limit: an entry with q_i * 2^24 < S can be skipped by every value of the draw (needs
+                                      S > 2^24: hundreds of full-weight lights beside a tiny one); its share of the light is lost.
+                                      Such a launch has the limits of a RTPT_FLAG_EXT_NEE launch.
+                                      Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -793,10 +822,21 @@ int rtpt_selftest_light_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out,
  * 6 words (wd[3], g, 1.0f if taken else 0.0f, 1.0f if valid else 0.0f as floats; wd and g are written as 0 where the sample is
  * not taken).  Operands are not checked.  Additive: RTPT_ABI_VERSION stays 5. */
 int rtpt_selftest_sphere_sample(rtpt_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
+/* The cumulative table of RTPT_FLAG_EXT_NEE_POWER (csrc/light_table.hip) from n given weights, 1 <= n <= 2^24: the maximum, the
+ * quantisation and the scan as the context's builder runs them; cdf_out = n x uint64.  Needs neither a scene nor the flag.
+ * Additive: RTPT_ABI_VERSION stays 5. */
+int rtpt_selftest_light_table(rtpt_ctx* ctx, const float* w, size_t n, uint64_t* cdf_out);
+/* The weighted pick (csrc/light_sample.hpp: pick_power) of k draws u_l on the table cdf[0, n), 1 <= n <= 2^24: index_out[j] the
+ * entry, inv_p_out[j] = float(S) / float(q).  Operands are not checked beyond n; every index the search reads lies in [0, n). */
+int rtpt_selftest_light_pick(rtpt_ctx* ctx, const uint64_t* cdf, size_t n, const float* u_l, size_t k, uint32_t* index_out, float* inv_p_out);
 /* The light list of RTPT_FLAG_EXT_NEE as it stands on the device: *n = its entries (0 without the flag, without materials or
  * without an emitter), of which the first min(*n, cap) are copied to ids — id + 1 of every posed triangle inst * n_tris + t whose
  * material has Ke != 0, ascending.  ids may be NULL when cap is 0 (count only). */
 int rtpt_debug_light_list(rtpt_ctx* ctx, uint32_t* ids, uint32_t cap, uint32_t* n);
+/* The cumulative table of RTPT_FLAG_EXT_NEE_POWER as it stands on the device, in the manner of rtpt_debug_light_list: *n = its
+ * entries (0 without both bits, without materials or without an emitter), of which the first min(*n, cap) are copied to cdf.
+ * cdf may be NULL when cap is 0 (count only). */
+int rtpt_debug_light_table(rtpt_ctx* ctx, uint64_t* cdf, uint32_t cap, uint32_t* n);
 /* The same at an explicit level: lod[i] is the lambda a hit would have computed (any bit pattern: it is clamped to
  * [0, levels - 1], a NaN reads level 0).  A texture without RTPT_TEX_MIPMAP has one level.  rtpt_selftest_texture keeps
  * reading level 0.  Refusals as rtpt_selftest_texture (lod is not checked). */

@@ -32,6 +32,7 @@ FLAG_EXT_DEMODULATE = 0x8000  # filter illumination, multiply the first hit's al
 FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms -> triangles and the fan-pair test on the device (csrc/scene_flatten.hip)
 FLAG_EXT_NEE = 0x10000  # next-event estimation: rtpt_raytrace samples the scene's emissive triangles (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 FLAG_EXT_NEE_SPHERE = 0x20000  # next-event estimation of the analytic sphere light: every diffuse hit samples its cone, no shadow ray (csrc/light_sample.hpp); not in FLAG_EXT_MASK
+FLAG_EXT_NEE_POWER = 0x40000  # with FLAG_EXT_NEE: the emissive triangle is picked by area x emission from a cumulative table built on the device (csrc/light_table.hip); ignored alone; not in FLAG_EXT_MASK
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -151,6 +152,7 @@ SYMBOLS = [
     "rtpt_scene_set_materials_ext", "rtpt_util_load_obj_materials_ext", "rtpt_selftest_bounce",
     "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
     "rtpt_selftest_light_sample", "rtpt_debug_light_list", "rtpt_selftest_sphere_sample",
+    "rtpt_selftest_light_table", "rtpt_selftest_light_pick", "rtpt_debug_light_table",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -240,6 +242,9 @@ def load() -> C.CDLL:
         "rtpt_selftest_refract": [vp, vp, vp, sz],
         "rtpt_selftest_light_sample": [vp, vp, vp, sz],
         "rtpt_debug_light_list": [vp, vp, u32, C.POINTER(u32)],
+        "rtpt_selftest_light_table": [vp, vp, sz, vp],
+        "rtpt_selftest_light_pick": [vp, vp, sz, vp, sz, vp, vp],
+        "rtpt_debug_light_table": [vp, vp, u32, C.POINTER(u32)],
         "rtpt_selftest_sphere_sample": [vp, vp, vp, sz],
     }
     for name, args in sigs.items():
@@ -451,6 +456,16 @@ class Context:
         flattened, posed and refit again, on the device where a changed model matrix is (rtpt_scene_set_instances)"""
         xf = np.ascontiguousarray(instance_xforms, np.float32).reshape(-1, 12)
         _check(self._lib.rtpt_scene_set_instances(self._h, _ptr(xf), len(xf)))
+
+    def debug_light_table(self) -> np.ndarray:
+        """the cumulative table of FLAG_EXT_NEE_POWER as it stands on the device (rtpt_debug_light_table): uint64 [L]; empty without
+        both bits, without materials or without an emitter"""
+        n = C.c_uint32()
+        _check(self._lib.rtpt_debug_light_table(self._h, None, 0, C.byref(n)))
+        cdf = np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(self._lib.rtpt_debug_light_table(self._h, _ptr(cdf), n.value, C.byref(n)))
+        return cdf
 
     def debug_upload_info(self) -> dict:
         """how the last scene_upload / scene_set_instances moved the geometry (rtpt_debug_upload_info)"""
@@ -671,6 +686,24 @@ class Context:
         out = np.zeros((len(cases), 9), np.uint32)
         _check(self._lib.rtpt_selftest_light_sample(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
+
+    def selftest_light_table(self, w: np.ndarray) -> np.ndarray:
+        """uint64 [n]: the cumulative table of FLAG_EXT_NEE_POWER the device builds from the weights w [n] float32
+        (rtpt_selftest_light_table; needs neither a scene nor the flag)"""
+        w = np.ascontiguousarray(w, np.float32).ravel()
+        out = np.zeros(len(w), np.uint64)
+        _check(self._lib.rtpt_selftest_light_table(self._h, _ptr(w), len(w), _ptr(out)))
+        return out
+
+    def selftest_light_pick(self, cdf: np.ndarray, u_l: np.ndarray):
+        """(entry uint32 [k], inv_p float32 [k]) of the device's weighted pick of draws u_l [k] on the table cdf [n] uint64
+        (rtpt_selftest_light_pick)"""
+        cdf = np.ascontiguousarray(cdf, np.uint64).ravel()
+        u_l = np.ascontiguousarray(u_l, np.float32).ravel()
+        idx = np.zeros(len(u_l), np.uint32)
+        inv_p = np.zeros(len(u_l), np.float32)
+        _check(self._lib.rtpt_selftest_light_pick(self._h, _ptr(cdf), len(cdf), _ptr(u_l), len(u_l), _ptr(idx), _ptr(inv_p)))
+        return idx, inv_p
 
     def selftest_sphere_sample(self, cases: np.ndarray) -> np.ndarray:
         """[n, 6] uint32 words (wd, g, taken, valid as floats; wd and g 0 where not taken) of the device's sphere sample on cases

@@ -635,6 +635,20 @@ int rtpt_debug_light_list(rtpt_ctx* c, uint32_t* ids, uint32_t cap, uint32_t* n)
   return RTPT_OK;
 }
 
+// ... and the cumulative table of RTPT_FLAG_EXT_NEE_POWER beside it, the same way
+int rtpt_debug_light_table(rtpt_ctx* c, uint64_t* cdf, uint32_t cap, uint32_t* n) {
+  if (!c || !n || (cap && !cdf)) return fail(RTPT_E_INVALID, "NULL argument");
+  const uint32_t have = (c->scene.light_table.cdf.ptr && c->scene.lights.ptr) ? c->scene.n_lights : 0u;
+  *n = have;
+  const uint32_t take = have < cap ? have : cap;
+  if (!take) return RTPT_OK;  // no zero-byte copy
+  if (static_cast<size_t>(have) * 8 > c->scene.light_table.cdf.bytes) return fail(RTPT_E_INVALID, "internal: the light table is shorter than its list");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(cdf, c->scene.light_table.cdf.ptr, static_cast<size_t>(take) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RTPT_OK;
+}
+
 int rtpt_debug_upload_info(rtpt_ctx* c, uint64_t out[4]) {
   if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
   for (int i = 0; i < 4; i++) out[i] = c->upload_info[i];

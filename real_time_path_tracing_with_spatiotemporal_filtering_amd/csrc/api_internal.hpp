@@ -200,6 +200,13 @@ struct Scene {
   // upload drops it with the scene; moved instances, a rebuilt tree, a changed model and a resize keep it: ids do not change
   Buf lights;
   uint32_t n_lights = 0;
+  // RTPT_FLAG_EXT_NEE_POWER (with RTPT_FLAG_EXT_NEE, and a list with entries; no allocation otherwise): the cumulative table of
+  // the weighted pick, 8 bytes an entry, and the builder's work area (rt::light_table_scratch_bytes).  Joined and dropped with
+  // the list; rebuilt on the context's stream behind every launch_scene_prepare, so that it belongs to the shade records a trace
+  // reads (api_scene.hip: rebuild_light_table)
+  struct LightTable {
+    Buf cdf, scratch;
+  } light_table;
   // optional albedo textures, rtpt_scene_set_textures: per-base-triangle uv records, descriptors, the RGBA32F atlas
   struct Textures {
     Buf records, desc, texels;

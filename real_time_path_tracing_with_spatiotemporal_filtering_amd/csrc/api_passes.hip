@@ -146,10 +146,14 @@ void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, fl
 // A context with RTPT_FLAG_EXT_NEE_SPHERE samples the analytic sphere light, whatever the scene's materials or light list:
 // rt::kSpecNeeSphere, the kernels that sample both kinds (the triangles where the list has entries).  Such a launch has a
 // sampling launch's limits (every segment in the tile kernel, no queue kernels, no path pool, no deferred final pass)
+// RTPT_FLAG_EXT_NEE_POWER on top of a launch that samples the triangles of a list (both bits, entries, and the cumulative table
+// that join_materials built beside the list): rt::kSpecNeePower / rt::kSpecNeeSpherePower, the kernels that pick by weight.
+// Alone, with only RTPT_FLAG_EXT_NEE_SPHERE, or with an empty list the bit changes nothing
 int trace_material_mode(const rtpt_ctx* c) {
-  if (c->cfg.flags & RTPT_FLAG_EXT_NEE_SPHERE) return rt::kSpecNeeSphere;
   const bool nee = (c->cfg.flags & RTPT_FLAG_EXT_NEE) && c->scene.n_lights > 0 && c->scene.lights.ptr && c->scene.materials.ptr;
-  return nee ? rt::kSpecNee : c->scene.materials_specular;
+  const bool power = nee && (c->cfg.flags & RTPT_FLAG_EXT_NEE_POWER) && c->scene.light_table.cdf.ptr;
+  if (c->cfg.flags & RTPT_FLAG_EXT_NEE_SPHERE) return power ? rt::kSpecNeeSpherePower : rt::kSpecNeeSphere;
+  return nee ? (power ? rt::kSpecNeePower : rt::kSpecNee) : c->scene.materials_specular;
 }
 
 // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (rtpt_ctx::trace_pool): the workgroups' slabs
@@ -481,7 +485,8 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), trace_material_mode(c), c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c));
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c),
+                         static_cast<const uint64_t*>(c->scene.light_table.cdf.ptr));
   }
   if (take) {
     c->deferred_valid = false;

@@ -25,6 +25,9 @@ rt::ScenePrepArgs scene_prep_args(const Scene& s) {
   sp.leaf_pairs = s.tree.leaf_pairs ? 1u : 0u;
   return sp;
 }
+// what follows every launch_scene_prepare: the cumulative light table of RTPT_FLAG_EXT_NEE_POWER, where the scene has one
+// (defined beside the light list below)
+void rebuild_light_table(rtpt_ctx* c, Scene& s);
 
 rt::RefitArgs refit_args(const Scene& s) {
   rt::RefitArgs ra;
@@ -230,6 +233,7 @@ int device_build_tree(rtpt_ctx* c, Scene& s, bool leaf_pairs, bool* too_deep) {
   std::swap(s.tree, t);
   rt::launch_refit(refit_args(s), s.tree.refit_level_first.data(), static_cast<int>(levels), n_nodes, 1e-5f, c->stream);
   rt::launch_scene_prepare(scene_prep_args(s), c->stream);
+  rebuild_light_table(c, s);
   const int rcl = launch_check("device BVH build");
   const hipError_t ee = hipEventRecord(c->build_ev[1], c->stream);
   if (rcl) return rcl;
@@ -262,17 +266,48 @@ int upload_light_list(rtpt_ctx* c, const std::vector<uint32_t>& list, Buf& ids) 
   HIP_TRY(hipMemcpyAsync(ids.ptr, list.data(), bytes, hipMemcpyHostToDevice, c->stream));
   return RTPT_OK;
 }
-void join_materials(rtpt_ctx* c, Buf& recs, Buf& ids, size_t n_lights) {
+// RTPT_FLAG_EXT_NEE_POWER: room for the cumulative table of a list of n_lights entries and for its builder, the caller's local
+// like `ids`.  Without both bits, or for an empty list, nothing is allocated
+int alloc_light_table(const rtpt_ctx* c, size_t n_lights, Scene::LightTable& tab) {
+  const uint32_t both = RTPT_FLAG_EXT_NEE | RTPT_FLAG_EXT_NEE_POWER;
+  if ((c->cfg.flags & both) != both || !n_lights) return RTPT_OK;
+  int rc;
+  if ((rc = alloc_buf(tab.cdf, n_lights * sizeof(uint64_t))) || (rc = alloc_buf(tab.scratch, rt::light_table_scratch_bytes(n_lights)))) return rc;
+  return RTPT_OK;
+}
+// The table of scene s from its light list, shade records and material records as they stand on the stream: behind every
+// launch_scene_prepare, and where the list joins the scene.  No synchronisation, no readback; nothing without a table
+void rebuild_light_table(rtpt_ctx* c, Scene& s) {
+  if (!s.light_table.cdf.ptr || !s.lights.ptr || !s.n_lights || !s.materials.ptr || !s.shade.ptr) return;
+  rt::LightTableArgs la;
+  la.ids = static_cast<const uint32_t*>(s.lights.ptr);
+  la.n = s.n_lights;
+  la.shade = static_cast<const float4*>(s.shade.ptr);
+  la.materials = static_cast<const float4*>(s.materials.ptr);
+  la.n_base_tris = s.n_base_tris;
+  la.cdf = static_cast<uint64_t*>(s.light_table.cdf.ptr);
+  la.scratch = s.light_table.scratch.ptr;
+  rt::launch_light_table(la, c->stream);
+}
+int join_materials(rtpt_ctx* c, Buf& recs, Buf& ids, size_t n_lights, Scene::LightTable& tab) {
   c->scene.materials = std::move(recs);
   if (ids.ptr) {
     c->scene.lights = std::move(ids);
     c->scene.n_lights = static_cast<uint32_t>(n_lights);
+    if (tab.cdf.ptr) {
+      c->scene.light_table = std::move(tab);
+      rebuild_light_table(c, c->scene);
+      return launch_check("light table");
+    }
   }
+  return RTPT_OK;
 }
 
 void drop_lights(rtpt_ctx* c) {
   free_buf(c->scene.lights);
   c->scene.n_lights = 0;
+  free_buf(c->scene.light_table.cdf);
+  free_buf(c->scene.light_table.scratch);
 }
 
 // the mesh and the instance transforms of one rtpt_scene_upload call
@@ -373,6 +408,7 @@ int upload_host_tree(rtpt_ctx* c, Scene& s, const std::vector<float>& tris, bool
   float grid_h[8];
   if ((rc = upload_grid(c, s, grid_h))) return rc;
   rt::launch_scene_prepare(scene_prep_args(s), c->stream);
+  rebuild_light_table(c, s);
   if ((rc = launch_check("scene_prepare"))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
   s.tree.bvh_host = std::move(bvh);
@@ -514,6 +550,7 @@ int repose_scene(rtpt_ctx* c, const float* model) {
     rt::launch_pose(total * 3, static_cast<const float*>(s.obj_tris_dev.ptr), static_cast<float*>(s.tris.ptr), rm, c->stream);
     rt::launch_refit(refit_args(s), s.tree.refit_level_first.data(), static_cast<int>(s.tree.refit_level_first.size()) - 1, s.tree.n_nodes, 1e-5f, c->stream);
     rt::launch_scene_prepare(scene_prep_args(s), c->stream);
+    rebuild_light_table(c, s);
     if ((rc = launch_check("device refit"))) return rc;
   } else {
     rt::refit_bvh(posed.data(), total, s.tree.bvh_host);
@@ -525,6 +562,7 @@ int repose_scene(rtpt_ctx* c, const float* model) {
     float grid_h[8];
   if ((rc = upload_grid(c, s, grid_h))) return rc;
     rt::launch_scene_prepare(scene_prep_args(s), c->stream);
+    rebuild_light_table(c, s);
     if ((rc = launch_check("scene_prepare"))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
   }
@@ -708,9 +746,10 @@ int rtpt_scene_set_materials(rtpt_ctx* c, const uint32_t* tri_material, uint32_t
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   if ((rc = upload_light_list(c, lights, ids))) return rc;
+  Scene::LightTable tab;  // RTPT_FLAG_EXT_NEE_POWER (empty without)
+  if ((rc = alloc_light_table(c, lights.size(), tab))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  join_materials(c, recs, ids, lights.size());
-  return RTPT_OK;
+  return join_materials(c, recs, ids, lights.size(), tab);
 }
 
 int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint32_t n_tris, const rtpt_material_ext* materials,
@@ -748,10 +787,12 @@ int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(recs.ptr, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   if ((rc = upload_light_list(c, lights, ids))) return rc;
+  Scene::LightTable tab;  // RTPT_FLAG_EXT_NEE_POWER (empty without)
+  if ((rc = alloc_light_table(c, lights.size(), tab))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  join_materials(c, recs, ids, lights.size());
+  rc = join_materials(c, recs, ids, lights.size(), tab);
   c->scene.materials_specular = any_specular;
-  return RTPT_OK;
+  return rc;
 }
 
 int rtpt_scene_set_textures(rtpt_ctx* c, const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris, const rtpt_texture* textures,

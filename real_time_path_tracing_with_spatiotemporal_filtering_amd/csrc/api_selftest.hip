@@ -176,6 +176,51 @@ int rtpt_selftest_sphere_sample(rtpt_ctx* c, const uint32_t* in, uint32_t* out, 
   return RTPT_OK;
 }
 
+int rtpt_selftest_light_table(rtpt_ctx* c, const float* w, size_t n, uint64_t* cdf_out) {
+  if (!c || !w || !cdf_out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  if (n > (static_cast<size_t>(1) << 24)) return fail(RTPT_E_INVALID, "a light table has at most 2^24 entries");
+  HIP_TRY(hipSetDevice(c->device));
+  Buf dw, dcdf, scratch;
+  int rc;
+  if ((rc = alloc_buf(dw, n * sizeof(float))) || (rc = alloc_buf(dcdf, n * sizeof(uint64_t))) ||
+      (rc = alloc_buf(scratch, rt::light_table_scratch_bytes(n))))
+    return rc;
+  hipError_t e = hipMemcpyAsync(dw.ptr, w, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_light_table_weights(static_cast<const float*>(dw.ptr), n, static_cast<uint64_t*>(dcdf.ptr), scratch.ptr, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(cdf_out, dcdf.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_light_table: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
+int rtpt_selftest_light_pick(rtpt_ctx* c, const uint64_t* cdf, size_t n, const float* u_l, size_t k, uint32_t* index_out, float* inv_p_out) {
+  if (!c || !cdf || !u_l || !index_out || !inv_p_out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0 || n > (static_cast<size_t>(1) << 24)) return fail(RTPT_E_INVALID, "a light table has 1 to 2^24 entries");
+  if (k == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  Buf dcdf, du, di, dp;
+  int rc;
+  if ((rc = alloc_buf(dcdf, n * sizeof(uint64_t))) || (rc = alloc_buf(du, k * sizeof(float))) || (rc = alloc_buf(di, k * sizeof(uint32_t))) ||
+      (rc = alloc_buf(dp, k * sizeof(float))))
+    return rc;
+  hipError_t e = hipMemcpyAsync(dcdf.ptr, cdf, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(du.ptr, u_l, k * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_light_pick(static_cast<const uint64_t*>(dcdf.ptr), static_cast<uint32_t>(n), static_cast<const float*>(du.ptr), k,
+                                   static_cast<uint32_t*>(di.ptr), static_cast<float*>(dp.ptr), c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(index_out, di.ptr, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(inv_p_out, dp.ptr, k * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_light_pick: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_trace(rtpt_ctx* c, const float* rays, size_t n, uint32_t* out_id, float* out_t) {
   if (!c || !rays || !out_id) return fail(RTPT_E_INVALID, "NULL argument");
   if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");

@@ -187,28 +187,60 @@ template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
   pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
 }
 template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
   pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
 }
 template <int BVH, bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
   gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
 }
 template <bool DEMOD, int TEX, int SPEC>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC >= 3, "only the instantiations that sample lights take the list");
+  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
+  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
+}
+
+// ... and for launches that pick their light by weight (SPEC = 5 / 6, RTPT_FLAG_EXT_NEE_POWER: 3 / 4 with the cumulative table):
+// overloads once more, on the list's sibling that carries the table (kernels.hpp: LightTableView), so that the kernels above keep
+// their argument segments and their code.
+template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
+void k_pathtrace(PathtraceArgs a, TexView tex, LightTableView lights) {
+  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
+  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
+}
+template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
+void k_pathtrace_small(PathtraceArgs a, TexView tex, LightTableView lights) {
+  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
+  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
+}
+template <int BVH, bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
+void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightTableView lights) {
+  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
+  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
+}
+template <bool DEMOD, int TEX, int SPEC>
+__global__ __launch_bounds__(kPtThreads)
+__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
+void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightTableView lights) {
+  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
   gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
 }
 
@@ -418,7 +450,7 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
                           runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol, uint32_t* run_info, const LightView& lights) {
+                      const FilterPolicy* pol, uint32_t* run_info, const LightView& lights, const uint64_t* light_cdf) {
   if (run_info) {
     run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
     run_info[1] = run_info[2] = 0u;
@@ -430,6 +462,9 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   // triangles where the list has entries
   if (spec_mode(specular) == 3 && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
   if (spec_mode(specular) == 4 && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
+  // 5 / 6: 3 / 4 with the weighted pick, on a list that has entries and a table
+  if (spec_mode(specular) >= 5 && (!lights.ids || !lights.n || !a.scene.materials || !light_cdf)) std::abort();
+  [[maybe_unused]] const LightTableView table{lights.ids, lights.n, light_cdf};
   const bool pool = !nee && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
@@ -483,9 +518,25 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
         constexpr int T = decltype(tmode)::value;
         // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE: those that
         // sample lights too (3), RTPT_FLAG_EXT_NEE_SPHERE: and the sphere light (4), which take the light list as one more argument
-        with_mode5(spec_mode(specular), [&](auto spec) {
+        // RTPT_FLAG_EXT_NEE_POWER: 3 / 4 with the weighted pick (5 / 6), which take the list with its table
+        with_mode7(spec_mode(specular), [&](auto spec) {
           constexpr int S = decltype(spec)::value;
-          if constexpr (S >= 3) {
+          if constexpr (S >= 5) {
+            if (gb) {
+              if constexpr (M != 0)
+                k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, table);
+              else
+                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, table);
+              return;
+            }
+            with_bool(a.compact != 0, [&](auto compact) {
+              constexpr bool C = decltype(compact)::value;
+              if constexpr (M != 0)
+                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, table);
+              else
+                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, table);
+            });
+          } else if constexpr (S >= 3) {
             // (the launch syntax, because these kernels are OVERLOADS of the names below: an overload set is no argument for
             // hipLaunchKernelGGL's deduced kernel type, a call resolves it by its arguments)
             if (gb) {

@@ -74,6 +74,19 @@ constexpr int kSpecNee = 3;
 // ... and for a launch of a context with RTPT_FLAG_EXT_NEE_SPHERE: the SPEC = 4 instantiations, SPEC = 3 plus the sample of the
 // analytic sphere light, whatever the scene's materials or light list
 constexpr int kSpecNeeSphere = 4;
+// The light list with the cumulative table of RTPT_FLAG_EXT_NEE_POWER behind it (light_sample.hpp: pick_power; light_table.hip
+// builds it): cdf[i] = the sum of the quantised weights of entries 0..i, cdf[n - 1] = S.  A sibling of LightView, not a field of
+// it, and the parameter of overloads of their own (SPEC = 5 / 6), so that the argument segments and the code of the SPEC = 3 / 4
+// kernels stay what they were; ids, cdf non-NULL and n in [1, 2^24] wherever a kernel takes it.
+struct LightTableView {
+  const uint32_t* ids;
+  uint32_t n;
+  const uint64_t* cdf;
+};
+// ... for a launch of a context with RTPT_FLAG_EXT_NEE and RTPT_FLAG_EXT_NEE_POWER on a scene whose light list has entries: SPEC = 3
+// with the weighted pick (5), and SPEC = 4 with it (6, RTPT_FLAG_EXT_NEE_SPHERE besides).  With an empty list 0x60000 launches 4
+constexpr int kSpecNeePower = 5;
+constexpr int kSpecNeeSpherePower = 6;
 
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
 // and the same columns of row min(2y + 1, sh - 1) of level l (texture_mips.hip): one launch per level.  src and dst are texel
@@ -354,7 +367,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // selects the SPEC instantiations; it travels
 // beside the kernel arguments, not in them, so that every existing argument offset stays.  kSpecNee (then `lights` has entries):
 // the launch samples lights, every segment runs in the tile kernel (no queue kernels) and it carries no final pass; the same for
-// kSpecNeeSphere, whose `lights` may be empty
+// kSpecNeeSphere, whose `lights` may be empty; kSpecNeePower / kSpecNeeSpherePower: `lights` has entries and light_cdf is its
+// cumulative table (LightTableView)
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -363,7 +377,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // (final_split.hpp; a launch without runs: every column, 0, 0)
 struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
-                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr, const LightView& lights = LightView{nullptr, 0u});
+                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr, const LightView& lights = LightView{nullptr, 0u},
+                      const uint64_t* light_cdf = nullptr);
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
@@ -448,6 +463,28 @@ void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t 
 void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // light::sphere_sample on n cases of 12 words (x, nf, c, r2, u_c, u_p): out = n x (wd, g, taken, valid), 6 words
 void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
+
+// The cumulative table of RTPT_FLAG_EXT_NEE_POWER (light_table.hip; light_sample.hpp states the arithmetic): everything on stream
+// s, no synchronisation, no readback.  kLightTableBlock entries per workgroup; light_table_scratch_bytes(n) = what the builder
+// needs beside the table for n entries: the maximum's word (8 bytes), the sums of the workgroups of every level of the scan
+// (8 bytes each: ceil(n / 1024), ceil(that / 1024), ... down to one workgroup) and the weights (4 n).
+constexpr uint32_t kLightTableBlock = 1024;
+size_t light_table_scratch_bytes(size_t n);
+// ... of the light list ids[0, n) of a scene: the weights come from the shade records and the material records
+struct LightTableArgs {
+  const uint32_t* ids;
+  uint32_t n;
+  const float4* shade;
+  const float4* materials;
+  uint32_t n_base_tris;
+  uint64_t* cdf;  // n entries
+  void* scratch;  // light_table_scratch_bytes(n)
+};
+void launch_light_table(const LightTableArgs& a, hipStream_t s);
+// ... of n given weights w (a device pointer): rtpt_selftest_light_table
+void launch_light_table_weights(const float* w, size_t n, uint64_t* cdf, void* scratch, hipStream_t s);
+// light::pick_power on k draws u_l of the table cdf[0, n): index_out[j], inv_p_out[j] (rtpt_selftest_light_pick)
+void launch_selftest_light_pick(const uint64_t* cdf, uint32_t n, const float* u_l, size_t k, uint32_t* index_out, float* inv_p_out, hipStream_t s);
 // tex::sample of descriptor `desc` (a device pointer) at n uv pairs: out[i] = the RGBA the kernels would read
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s);
 // tex::sample_lod of descriptor `desc` and its level-table row `lv` (device pointers) at n (uv, lod) pairs

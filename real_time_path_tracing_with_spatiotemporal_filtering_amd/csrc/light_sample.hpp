@@ -42,7 +42,11 @@ namespace light {
 
 constexpr float k2Pi = 6.28318548202514648f;  // the binary32 nearest 2 pi
 constexpr uint32_t kMaxLights = 1u << 24;     // u_l has 24 bits: a longer list would have entries the pick never reaches (the
-                                              // bound a light list has to keep; the self test is told L)
+                                              // bound a light list has to keep; the self test is told L).  The weighted
+                                              // pick (RTPT_FLAG_EXT_NEE_POWER, below) has a limit of the same kind: an entry
+                                              // whose quantised weight q_i has q_i * 2^24 < S can be skipped by all 2^24 values
+                                              // of the draw, and its share of the light is lost; that needs S > 2^24, hundreds of
+                                              // full-weight lights beside one of the smallest weight
 static_assert(kMaxLights == rtpt_light::kMaxLights, "the host refuses the lists the pick cannot reach");
 
 // entry of a list of L > 0 lights that draw u_l in [0, 1) picks
@@ -74,6 +78,91 @@ __device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf
   const float a2 = exact::sqrt_(exact::dot(c, c));
   s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
   s.g = exact::div_((cs * cl) * (a2 * static_cast<float>(L)), k2Pi * r2);
+  return s;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// THE WEIGHTED PICK (RTPT_FLAG_EXT_NEE_POWER together with RTPT_FLAG_EXT_NEE on a scene whose light list has L > 0 entries; alone,
+// or with only RTPT_FLAG_EXT_NEE_SPHERE, the bit is ignored, and without it every frame, ray count, kernel and allocation is that of
+// a context without it, bit for bit).  Every rule above holds unchanged — the place of the sample, the three draws and their
+// order, the sampled bit, the shadow query and its tie rule, R — except two: WHICH ENTRY the draw u_l names, and that float(L) in
+// g becomes inv_p, the inverse of the pick's probability.  Entries are picked in proportion to area times emission, from a
+// cumulative table of integers that light_table.hip builds on the device; all of its arithmetic is fixed so that a parallel build
+// gives the same bits in any order.  tests/nee_power.py restates weights, table and pick, and walks whole paths with them.
+//   * Weight of entry i (posed id, vertices from its shade record, Ke from material record (id - 1) % n_base_tris): w_i = a2_i * k_i,
+//     a2_i = sample()'s a2 (exact::cross, exact::dot, exact::sqrt_), k_i = max(|Ke.r|, |Ke.g|, |Ke.b|) as k = |r|; if (|g| > k)
+//     k = |g|; if (|b| > k) k = |b|.  A w_i that is NaN, infinite or not > 0 counts as 0: a degenerate emitter is never picked.
+//   * w_max = max_i w_i: of non-negative finite floats, so the unsigned maximum of their bit patterns, in any order.
+//   * Quantised weight q_i: 1 for every entry where w_max == 0 (the uniform pick); else max(1, uint32(exact::div_(w_i, w_max) *
+//     65536.0f)) where w_i > 0 and 0 elsewhere.  q_i <= 2^16.
+//   * C_i = sum_{j <= i} q_j as uint64, S = C_{L-1} <= 2^40: integer sums, any scan order.  8 bytes an entry.
+//   * Pick: m = uint32(u_l * 2^24), exact since a draw is a multiple of 2^-24; t = (uint64(m) * S) >> 24 (the product is below
+//     2^64); the entry is the smallest i with C_i > t, by binary search; inv_p = exact::div_(float(S), float(q_i)), the
+//     uint64 -> binary32 conversion rounding to nearest even.
+//   * g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2): sample_inv_p below, sample() with inv_p where it takes L.
+// KNOWN LIMIT, of the kind of kMaxLights: an entry with q_i * 2^24 < S can be skipped by all 2^24 values of the draw, and its
+// share of the light is then lost.  That needs S > 2^24: hundreds of full-weight lights beside one of the smallest weight.
+constexpr float kPickScale = 16777216.0f;    // 2^24
+constexpr float kWeightScale = 65536.0f;     // 2^16: the quantised weight of the heaviest entry
+
+// w_i of the rules above from the light's vertices and its Ke, before "counts as 0"
+__device__ __forceinline__ float weight(f3 v0, f3 v1, f3 v2, f3 ke) {
+  const f3 c = exact::cross(v1 - v0, v2 - v0);
+  const float a2 = exact::sqrt_(exact::dot(c, c));
+  const float r = __builtin_fabsf(ke.x), g = __builtin_fabsf(ke.y), b = __builtin_fabsf(ke.z);
+  float k = r;
+  if (g > k) k = g;
+  if (b > k) k = b;
+  return a2 * k;
+}
+// ... and "counts as 0": the bits of w where it is finite and > 0, else 0
+__device__ __forceinline__ uint32_t weight_bits(float w) {
+  return (w > 0.0f && w < __builtin_inff()) ? f2u(w) : 0u;
+}
+// q_i of a weight that went through weight_bits, given the maximum's bits
+__device__ __forceinline__ uint32_t quantise(uint32_t w_bits, uint32_t w_max_bits) {
+  if (w_max_bits == 0u) return 1u;
+  if (w_bits == 0u) return 0u;
+  const uint32_t q = static_cast<uint32_t>(exact::div_(u2f(w_bits), u2f(w_max_bits)) * kWeightScale);
+  return q > 1u ? q : 1u;
+}
+
+struct Pick {
+  uint32_t i;    // the entry
+  float inv_p;   // S / q_i
+};
+// entry of the table C[0, L), L > 0, that draw u_l in [0, 1) picks.  Every index read lies in [0, L) whatever u_l and C hold.
+__device__ __forceinline__ Pick pick_power(float u_l, const uint64_t* C, uint32_t L) {
+  const uint64_t S = C[L - 1u];
+  const uint32_t m = static_cast<uint32_t>(u_l * kPickScale);
+  const uint64_t t = (static_cast<uint64_t>(m) * S) >> 24;
+  uint32_t lo = 0u, hi = L - 1u;  // t < S = C[L - 1]: the answer lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (C[mid] > t)
+      hi = mid;
+    else
+      lo = mid + 1u;
+  }
+  const uint64_t q = C[lo] - (lo ? C[lo - 1u] : 0ull);
+  return Pick{lo, exact::div_(static_cast<float>(S), static_cast<float>(q))};
+}
+
+// sample() with the inverse of the pick's probability where it takes L
+__device__ __forceinline__ Sample sample_inv_p(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf, float u_a, float u_b, float inv_p) {
+  Sample s;
+  const float su = exact::sqrt_(u_a);
+  const float b0 = 1.0f - su, b1 = su * (1.0f - u_b), b2 = su * u_b;
+  s.y = bary_point(v0, v1, v2, b0, b1, b2);
+  const f3 w = s.y - x;
+  const float r2 = exact::dot(w, w);
+  s.wd = exact::normalize(w);
+  const float cs = exact::dot(nf, s.wd);
+  const float cl = __builtin_fabsf(exact::dot(nl, s.wd));
+  const f3 c = exact::cross(v1 - v0, v2 - v0);
+  const float a2 = exact::sqrt_(exact::dot(c, c));
+  s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
+  s.g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2);
   return s;
 }
 

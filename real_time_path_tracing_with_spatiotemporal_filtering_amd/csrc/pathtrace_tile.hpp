@@ -113,9 +113,11 @@ __device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
 // ROLE: 1 in the launch that also holds filter workgroups (k_pathtrace_final).  An instantiation of its own, so that its three
 // static LDS words are that kernel's alone: shared between two kernels they would move into the module-wide LDS block and
 // shift the dynamic LDS of every kernel of kernels.hip.
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0>
+// LV: what `lights` is — LightView, or LightTableView for the instantiations that pick by weight (SPEC = 5 / 6)
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0, class LV = LightView>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
-                                               const uint32_t role_gy = 0, [[maybe_unused]] const LightView& lights = LightView{nullptr, 0u}) {
+                                               const uint32_t role_gy = 0, [[maybe_unused]] const LV& lights = LV{}) {
+  static_assert(std::is_same<LV, LightTableView>::value == spec_power(SPEC), "the instantiations that pick by weight take the table");
   // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -190,7 +192,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       // (smp > 0: behind the barrier above, so the thread that ended this pixel's previous path has read its R)
       rad_r[pix0] = rad_g[pix0] = rad_b[pix0] = 0.0f;
       nee.sampled = false;  // the primary ray
-      if constexpr (SPEC == 4) nee.sphere = false;
+      if constexpr (spec_sphere(SPEC)) nee.sphere = false;
     }
     const int px0 = tile_x0 + static_cast<int>(pix0 & 63u), py0 = tile_y0 + static_cast<int>(pix0 >> 6);
     bool alive = (px0 < a.g.W) && (py0 < a.g.y1);
@@ -222,9 +224,12 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         // the short barycentric divisions where they cost no register: with DEMOD or without compaction they spill one
         constexpr bool kShortDiv = (RTPT_TRACE_ITEMS & 8) && BVH == 0 && COMPACT && !DEMOD;
         if constexpr (SPEC >= 3) nee.valid = false;
-        if constexpr (SPEC == 4) nee.sphere_valid = false;
+        if constexpr (spec_sphere(SPEC)) nee.sphere_valid = false;
         bool done;
-        if constexpr (SPEC >= 3)
+        if constexpr (spec_power(SPEC))
+          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgsPower>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
+                                                                        NeeArgsPower{lights, &nee});
+        else if constexpr (SPEC >= 3)
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
                                                                    NeeArgs{lights, &nee});
         else
@@ -232,7 +237,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if constexpr (SPEC >= 3) {
           // The sphere sample's gain (RTPT_FLAG_EXT_NEE_SPHERE) goes into R first: it needs no query, the order of the two additions
           // is fixed this way, and the gain is dead before the traversal below starts.
-          if constexpr (SPEC == 4) {
+          if constexpr (spec_sphere(SPEC)) {
             if (nee.sphere_valid) {
               rad_r[pix] += nee.sphere_c.x;
               rad_g[pix] += nee.sphere_c.y;
@@ -298,9 +303,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       if (alive) {
         const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(live >> 32),
                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(live), 0u));
-        if constexpr (SPEC == 4)
+        if constexpr (spec_sphere(SPEC))
           st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u) | (nee.sphere ? 0x200u : 0u);  // ... and the sphere bit beside it
-        else if constexpr (SPEC == 3)
+        else if constexpr (SPEC >= 3)
           st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u);  // pix has 8 bits: the sampled bit travels with the path
         else
           st.pix[slot] = pix;
@@ -315,7 +320,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         pix = st.pix[tid];
         if constexpr (SPEC >= 3) {
           nee.sampled = (pix & 0x100u) != 0u;
-          if constexpr (SPEC == 4) nee.sphere = (pix & 0x200u) != 0u;
+          if constexpr (spec_sphere(SPEC)) nee.sphere = (pix & 0x200u) != 0u;
           pix &= 0xFFu;
         }
         rng = st.rng[tid];
@@ -404,12 +409,12 @@ __device__ __forceinline__ void pathtrace_empty_run(const PathtraceArgs& a, uint
 // K0 + K1 + K2 in one launch, the body of k_gbuffer_pathtrace and k_gbuffer_pathtrace_small (kernels.hip has the reasons): rows
 // [0, a.tiles_y) of the grid are the tracing tiles, the rows behind them the G-buffer's 64 x 4 tiles, which put their depth into
 // the alpha of the traced image's pixels
-template <int BVH, bool DEMOD, int TEX, int SPEC>
+template <int BVH, bool DEMOD, int TEX, int SPEC, class LV = LightView>
 __device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, const GbufferArgs& g, const TexView& tex,
-                                                       [[maybe_unused]] const LightView& lights = LightView{nullptr, 0u}) {
+                                                       [[maybe_unused]] const LV& lights = LV{}) {
   if (blockIdx.y < a.tiles_y) {
     if constexpr (SPEC >= 3)
-      pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
+      pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC, 0, LV>(a, tex, 0, 0, 0, lights);
     else
       pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex);
   } else {

@@ -57,6 +57,16 @@ inline void with_mode5(int mode, F&& f) {
   else
     with_mode4(mode, f);
 }
+// ... and of 0 to 6: 5 and 6 are 3 and 4 with the weighted light pick
+template <class F>
+inline void with_mode7(int mode, F&& f) {
+  if (mode == 5)
+    f(std::integral_constant<int, 5>{});
+  else if (mode == 6)
+    f(std::integral_constant<int, 6>{});
+  else
+    with_mode5(mode, f);
+}
 // f(FINAL, EXACT): the two bools every filter kernel is instantiated over
 template <class F>
 inline void with_final_exact(bool final_pass, bool exact, F&& f) {

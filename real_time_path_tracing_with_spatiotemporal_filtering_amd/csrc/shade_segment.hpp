@@ -119,6 +119,12 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // entries (wave-uniform): with the sphere flag alone these instantiations run without a list and without a material table.
 // A compile-time switch because a run-time one cost the SPEC == 3 kernels 3.5 % of a frame with the switch off
 // (profiles/r23_nee_sphere_measure.txt); 3 is the instantiation before it, statement for statement.
+// SPEC == 5 / 6: SPEC == 3 / 4 with the weighted pick of RTPT_FLAG_EXT_NEE_POWER (light_sample.hpp: pick_power, sample_inv_p): the
+// draw u_l names an entry through the cumulative table that travels with the list (NeeArgsPower: LightTableView), and the
+// sample's weight takes the inverse of the pick's probability where it takes L.  Everything else is 3 / 4, and those two are the
+// instantiations before it, statement for statement.  The list has entries wherever 5 or 6 is launched.
+constexpr bool spec_sphere(int spec) { return spec == 4 || spec == 6; }  // the instantiations that sample the sphere light
+constexpr bool spec_power(int spec) { return spec >= 5; }                // ... that pick by weight
 struct NeeState {
   f3 wd;          // the shadow ray's direction, from the path's new origin
   f3 c;           // (T * Ke) * g
@@ -135,15 +141,20 @@ struct NeeArgs {
   LightView lights;
   NeeState* st;
 };
+struct NeeArgsPower {  // SPEC == 5 / 6
+  LightTableView lights;
+  NeeState* st;
+};
 struct NoNee {};
 template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE = NoNee>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr,
                                               [[maybe_unused]] NEE nee_args = NEE{}) {
-  static_assert(std::is_same<NEE, NeeArgs>::value == (SPEC >= 3), "the instantiations that sample lights, and only they, take NeeArgs");
+  static_assert(std::is_same<NEE, NeeArgs>::value == (SPEC == 3 || SPEC == 4), "the instantiations that sample lights, and only they, take NeeArgs");
+  static_assert(std::is_same<NEE, NeeArgsPower>::value == spec_power(SPEC), "... and those that pick by weight NeeArgsPower");
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
-    if constexpr (SPEC == 4) {
+    if constexpr (spec_sphere(SPEC)) {
       if (nee_args.st->sphere) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the sphere: this hit's light is counted there
     }
     if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -219,7 +230,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   if constexpr (SPEC >= 2) {
     if (diel::is_dielectric(spec_w)) {
       if constexpr (SPEC >= 3) nee_args.st->sampled = false;
-      if constexpr (SPEC == 4) nee_args.st->sphere = false;
+      if constexpr (spec_sphere(SPEC)) nee_args.st->sphere = false;
       const bool entering = exact::dot(n, d) < 0.0f;
       if (!entering) n = -n;
       const float u1 = exact::rng_next(rng);                       // :256
@@ -236,11 +247,26 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
   if constexpr (SPEC >= 3) {
     // next-event estimation (light_sample.hpp): o is the sample's x, n its nf, acc its T
-    const LightView lights = nee_args.lights;
+    const auto lights = nee_args.lights;  // LightView, or LightTableView where SPEC picks by weight
     NeeState* const nee = nee_args.st;
     const bool diffuse = !spec::is_specular(spec_w);
     if (diffuse && seg + 1 < a.max_segments) {
-      if (SPEC == 3 || lights.n > 0) {  // (SPEC == 3: the list has entries; 4: it may be empty — wave-uniform)
+      if constexpr (spec_power(SPEC)) {  // the weighted pick; the list has entries
+        const float u_l = exact::rng_next(rng);
+        const float u_a = exact::rng_next(rng);
+        const float u_b = exact::rng_next(rng);
+        const light::Pick pk = light::pick_power(u_l, lights.cdf, lights.n);
+        const uint32_t id1 = lights.ids[pk.i];
+        const float4* ls = a.scene.shade + 3 * static_cast<size_t>(id1 - 1);
+        const float4 l0 = ls[0], l1 = ls[1], l2 = ls[2];
+        const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
+        const light::Sample sm = light::sample_inv_p(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, pk.inv_p);
+        nee->wd = sm.wd;
+        nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
+        nee->id1 = id1;
+        nee->valid = sm.valid;
+        nee->sampled = true;
+      } else if (SPEC == 3 || lights.n > 0) {  // (SPEC == 3: the list has entries; 4: it may be empty — wave-uniform)
         const float u_l = exact::rng_next(rng);
         const float u_a = exact::rng_next(rng);
         const float u_b = exact::rng_next(rng);
@@ -255,7 +281,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
         nee->valid = sm.valid;
         nee->sampled = true;
       }
-      if constexpr (SPEC == 4) {  // the sphere sample: light_c, a.light_r2 and a.light_col are ray_hits_light's light
+      if constexpr (spec_sphere(SPEC)) {  // the sphere sample: light_c, a.light_r2 and a.light_col are ray_hits_light's light
         const float u_c = exact::rng_next(rng);
         const float u_p = exact::rng_next(rng);
         const light::SphereSample ss = light::sphere_sample(o, n, light_c, a.light_r2, u_c, u_p);
@@ -266,7 +292,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       }
     } else if (!diffuse) {
       nee->sampled = false;
-      if constexpr (SPEC == 4) nee->sphere = false;
+      if constexpr (spec_sphere(SPEC)) nee->sphere = false;
     }
   }
   float st_, ct;
@@ -289,11 +315,15 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
 // shade_segment's TEX for with_mode3 (select.hpp): 2 the scene has textures and some of them a mip chain (the level table
 // exists), 1 textures without mips, 0 no textures
 inline int tex_mode(const TexView& tex) { return tex.records ? (tex.levels ? 2 : 1) : 0; }
-// shade_segment's SPEC: 4 the launch samples the analytic sphere light, and the triangles of the light list where it has entries
+// shade_segment's SPEC: 6 / 5 are 4 / 3 with the weighted pick (kSpecNeeSpherePower, kSpecNeePower: RTPT_FLAG_EXT_NEE_POWER on a
+// scene whose light list has entries), 4 the launch samples the analytic sphere light, and the triangles of the light list where it has entries
 // (kSpecNeeSphere: RTPT_FLAG_EXT_NEE_SPHERE), 3 the launch samples lights (kSpecNee: RTPT_FLAG_EXT_NEE and a light list with entries, whatever the
 // materials), 2 some triangle's material is a dielectric, 1 some triangle's is specular and none a dielectric, 0 every material is
 // diffuse
-inline int spec_mode(int specular) { return specular >= kSpecNeeSphere ? 4 : specular == kSpecNee ? 3 :(specular == 2 ? 2 : (specular == 1 ? 1 : 0)); }
+inline int spec_mode(int specular) {
+  if (specular == kSpecNeePower || specular == kSpecNeeSpherePower) return specular;
+  return specular >= kSpecNeeSphere ? 4 : specular == kSpecNee ? 3 :(specular == 2 ? 2 : (specular == 1 ? 1 : 0));
+}
 
 }  // namespace
 }  // namespace rt

@@ -30,6 +30,8 @@ static void usage(const char* argv0) {
       "           RTPT_FLAG_EXT_NEE = --flags 0x10000; on every context of a rank; without an emissive material the frames are unchanged)]\n"
       "          [--nee-sphere  (next-event estimation of the analytic sphere light: every diffuse hit samples the cone the light subtends,\n"
       "           no shadow ray, RTPT_FLAG_EXT_NEE_SPHERE = --flags 0x20000; on every context of a rank; needs no materials, combines with --nee)]\n"
+      "          [--nee-power  (--nee with the emissive triangle picked by area times emission, not uniformly: RTPT_FLAG_EXT_NEE_POWER too,\n"
+      "           --flags 0x50000; implies --nee; the cumulative table is built on the device)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -92,6 +94,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--demodulate")) opt.flags |= RTPT_FLAG_EXT_DEMODULATE;
     else if (!std::strcmp(argv[i], "--nee")) opt.flags |= RTPT_FLAG_EXT_NEE;
     else if (!std::strcmp(argv[i], "--nee-sphere")) opt.flags |= RTPT_FLAG_EXT_NEE_SPHERE;
+    else if (!std::strcmp(argv[i], "--nee-power")) opt.flags |= RTPT_FLAG_EXT_NEE | RTPT_FLAG_EXT_NEE_POWER;
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
     else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;

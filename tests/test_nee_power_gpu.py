@@ -1,0 +1,476 @@
+"""The weighted light pick of next-event estimation on the device (RTPT_FLAG_EXT_NEE_POWER; csrc/light_sample.hpp states the
+rules, csrc/light_table.hip builds the table): the table builder and the pick against their numpy restatement bit for bit, whole
+frames against the walker of tests/nee_power.py (held on the CPU by tests/test_nee_power_cpu.py) — IMAGE, HIT_ID and the ray
+count bit for bit — the table's lifetime on the posed scene, the identities, and the hosts.  Every test but the flag-off
+identities fails on a library without the feature: the symbols and the flag do not exist there."""
+import gc
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import dielectric_scenes as DS
+import filter_planes as FP
+import nee_paths as NP
+import nee_power as PW
+import nee_scenes as N
+import pathtrace_scenes as P
+import refit_moves as RM
+import test_demodulate_gpu as D
+import test_nee_paths_gpu as TN
+import test_pathtrace_scenes_gpu as T
+from conftest import bits
+from filter_planes import same_bits
+
+pytestmark = pytest.mark.gpu
+
+F32, U32, U64 = np.float32, np.uint32, np.uint64
+W0, H0 = N.SIZES[0]
+W1, H1 = N.SIZES[1]
+FORCE_BVH, NO_COMPACTION, UNFUSED, DEMODULATE, NEE, SPHERE, POWER = 0x2, 0x8, 0x400, 0x8000, 0x10000, 0x20000, 0x40000
+STRIP_ROWS = (5, 21)
+
+# The builder scans kLightTableBlock = 1024 entries a workgroup (16 waves of 64), so the issue's sizes sit where it asks: 63 / 64 / 65
+# a wave, 1023 / 1024 / 1025 a workgroup, 65,537 past 64 workgroups, 2^20 + 1,025 past 1,024 workgroups — the sums of the
+# workgroups no longer fit one workgroup and the scan takes a third level.  255 / 256 / 257 is the workgroup of the weight kernel.
+TABLE_SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 65537, (1 << 20) + 1025]
+
+_walked = {}
+
+
+# ------------------------------------------------------------------------------------------ one frame, both sides
+def context(abi, scene, W, H, segments, flags=NEE | POWER, spp=1, rows=None):
+    ctx = abi.Context(T._config(abi, scene, W, H, segments, spp, flags, rows))
+    ctx.enable_debug(abi.DEBUG_HIT_ID)
+    return ctx
+
+
+def frame(abi, oracle, ctx, scene, W, H, planes=(), frame_no=0):
+    out = T.frame_on_gpu(abi, oracle, ctx, scene, W, H, frame_no)
+    for p in planes:
+        out[p] = ctx.readback(getattr(abi, "PLANE_" + p))
+    return out
+
+
+def walked(oracle, key, scene, W, H, segments, rec, lights, sphere=False, power=True, spp=1, texture=None):
+    """the walker's frame, computed once and left unchanged"""
+    key = (key, W, H, segments, spp, len(lights), sphere, power, texture is not None)
+    if key not in _walked:
+        r = PW.walk_nee_power(oracle, scene, W, H, segments, rec, lights, sphere=sphere, power=power, spp=spp, texture=texture)
+        for a in r.values():
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _walked[key] = r
+    return _walked[key]
+
+
+def same_frame(got, want, tag, rows=None):
+    y0, y1 = rows or (0, len(want["IMAGE"]))
+    same_bits(got["HIT_ID"], want["HIT_ID"][y0:y1], tag + ("HIT_ID",))
+    same_bits(got["IMAGE"], want["IMAGE"][y0:y1], tag + ("IMAGE",))
+
+
+def scenes():
+    """name -> (scene, glass, records, light list): two_lamps (its degenerate emitter has weight 0), the occluder scene, the
+    receiver under two lamps of unequal Ke, the glass room with a second, smaller lamp"""
+    out = {}
+    for sc in (NP.two_lamps(), NP.occluder(), PW.unequal_lamps()):
+        rec = DS.records(sc)
+        out[sc.name] = (sc, None, rec, NP.light_list(sc))
+    room, glass, rec = PW.glass_room_two_lamps()
+    out[room.name] = (room, glass, rec, NP.light_list(room, 1, rec))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ 1. the table
+@pytest.mark.parametrize("n", TABLE_SIZES)
+def test_table_equals_the_restatement(hip_lib, n):
+    """rtpt_selftest_light_table against nee_power.table bit for bit, with seeded skewed weights and with every hostile set: zeros
+    between positives, all zeros, one weight of 1e30 beside ones, subnormals, NaN and the infinities, equal weights, a ratio just
+    below and just at 2^-16"""
+    abi = hip_lib
+    with abi.Context(T._config(abi, N.receiver(), 64, 12, 1, 1, 0)) as ctx:
+        for kind in ("skewed",) + PW.HOSTILE:
+            w = PW.skewed_weights(n) if kind == "skewed" else PW.hostile_weights(n, kind)
+            got = ctx.selftest_light_table(w)
+            want = PW.table(w)
+            assert got.dtype == U64 and np.array_equal(got, want), (n, kind, np.flatnonzero(got != want)[:4])
+            assert int(want[-1]) >= 1
+
+
+# ------------------------------------------------------------------------------------------ 2. the pick
+def _draws(cdf, seed):
+    """4,096 seeded draws, both ends of u_l, and for 512 entries the first draw whose t reaches C_i and the one before it (where
+    S <= 2^24 that t is C_i itself and C_i - 1 or less)"""
+    g = np.random.default_rng(seed)
+    S = int(cdf[-1])
+    m = [g.integers(0, 1 << 24, 4096), [0, (1 << 24) - 1]]
+    pick = g.integers(0, len(cdf), 512)
+    edge = np.array([min((int(c) * (1 << 24) + S - 1) // S, (1 << 24) - 1) for c in cdf[pick]], np.int64)
+    m += [edge, np.maximum(edge - 1, 0)]
+    m = np.concatenate([np.asarray(a, np.int64) for a in m])
+    return (m.astype(F32) * F32(2.0 ** -24)).astype(F32)
+
+
+@pytest.mark.parametrize("name", ["zero_runs", "single", "skewed_1000", "all_zero", "deepest"])
+def test_pick_equals_the_restatement(hip_lib, name):
+    """rtpt_selftest_light_pick against nee_power.pick_power, entry and inv_p bit for bit: tables with runs of zero-weight entries,
+    n = 1, 1,000 skewed weights, the uniform table of weights that are all 0, and n = 2^20 + 1,025, the deepest search"""
+    abi = hip_lib
+    if name == "zero_runs":
+        w = np.ones(300, F32)
+        w[:9] = 0
+        w[40:120] = 0
+        w[290:] = 0
+        w[150] = 77.0
+    elif name == "single":
+        w = F32([0.25])
+    elif name == "skewed_1000":
+        w = PW.skewed_weights(1000)
+    elif name == "all_zero":
+        w = np.zeros(65, F32)
+    else:
+        w = PW.skewed_weights((1 << 20) + 1025)
+    cdf = PW.table(w)
+    u = _draws(cdf, 61)
+    with abi.Context(T._config(abi, N.receiver(), 64, 12, 1, 1, 0)) as ctx:
+        got_i, got_p = ctx.selftest_light_pick(cdf, u)
+    want_i, want_p = PW.pick_power(cdf, u)
+    assert np.array_equal(got_i, want_i), (name, np.flatnonzero(got_i != want_i)[:4])
+    same_bits(got_p, want_p, (name, "inv_p"))
+    q = np.diff(np.concatenate([[0], cdf.astype(np.int64)]))
+    assert (q[want_i] > 0).all(), "a zero-weight entry is never picked"
+    positive = np.flatnonzero(q > 0)
+    assert want_i[4096] == positive[0] and want_i[4097] == positive[-1], "both ends of u_l"
+    if int(cdf[-1]) <= 1 << 24 and len(cdf) > 1:
+        t = ((u[4098:4610] * F32(1 << 24)).astype(U64) * cdf[-1]) >> U64(24)
+        assert np.isin(t, cdf).mean() > 0.9, "these draws land exactly on a C_i"
+
+
+# ------------------------------------------------------------------------------------------ 3. whole frames against the walker
+@pytest.mark.parametrize("flags", [NEE | POWER, NEE | POWER | SPHERE], ids=["0x50000", "0x70000"])
+@pytest.mark.parametrize("vflags", [0, FORCE_BVH], ids=["brute", "bvh"])
+@pytest.mark.parametrize("name", ["nee_two_lamps", "nee_occluder", "nee_unequal_lamps", "glass_room_two_lamps"])
+def test_frames_equal_the_walker(hip_lib, oracle, name, vflags, flags):
+    """IMAGE, HIT_ID and the ray count against walk_nee_power, at 2 segments and at 5 (the glass room: 9), by brute force and with
+    RTPT_FLAG_FORCE_BVH, with flags 0x50000 and 0x70000; and the frame is not the uniform pick's"""
+    abi = hip_lib
+    scene, glass, rec, lights = scenes()[name]
+    sphere = bool(flags & SPHERE)
+    for segments in (2, 9 if glass else 5):
+        want = walked(oracle, name, scene, W0, H0, segments, rec, lights, sphere)
+        uniform = walked(oracle, name, scene, W0, H0, segments, rec, lights, sphere, power=False)
+        assert want["lit"] > 0 and not np.array_equal(bits(want["IMAGE"]), bits(uniform["IMAGE"]))
+        if name == "nee_two_lamps":
+            assert want["picks"][4] == 0 and uniform["picks"][4] > 0, "the degenerate emitter weighs 0"
+        with context(abi, scene, W0, H0, segments, flags | vflags) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            got = frame(abi, oracle, ctx, scene, W0, H0)
+        same_frame(got, want, (name, segments, vflags, flags))
+        assert got["rays"] == want["rays"], (name, segments, vflags, flags)
+
+
+def test_other_schedules_shapes_and_samples(hip_lib, oracle):
+    """the glass room with its second lamp: RTPT_FLAG_NO_PATH_COMPACTION, the unfused launch, a strip context with row_begin 5,
+    and one, two and three samples per pixel at 70 x 10 (partial tiles in x and y; R restarts with every sample)"""
+    abi = hip_lib
+    scene, glass, rec, lights = scenes()["glass_room_two_lamps"]
+    want = walked(oracle, scene.name, scene, W0, H0, 9, rec, lights)
+    for sid, flags in (("no_compaction", NO_COMPACTION), ("unfused", UNFUSED), ("unfused_bvh", UNFUSED | FORCE_BVH)):
+        with context(abi, scene, W0, H0, 9, NEE | POWER | flags) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            got = frame(abi, oracle, ctx, scene, W0, H0)
+        same_frame(got, want, (sid,))
+        assert got["rays"] == want["rays"], sid
+    with context(abi, scene, W0, H0, 9, NEE | POWER, rows=STRIP_ROWS) as ctx:
+        TN.upload(abi, ctx, scene, glass)
+        strip = frame(abi, oracle, ctx, scene, W0, H0)
+    same_frame(strip, want, ("strip",), STRIP_ROWS)
+    for segments, spp, extra in ((9, 1, 0), (2, 2, SPHERE), (5, 3, FORCE_BVH)):
+        want = walked(oracle, scene.name, scene, W1, H1, segments, rec, lights, bool(extra & SPHERE), spp=spp)
+        with context(abi, scene, W1, H1, segments, NEE | POWER | extra, spp) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            got = frame(abi, oracle, ctx, scene, W1, H1)
+        same_frame(got, want, (segments, spp, extra))
+        assert got["rays"] == want["rays"], (segments, spp, extra)
+
+
+def test_demodulated_and_textured(hip_lib, oracle):
+    """RTPT_FLAG_EXT_DEMODULATE with the weighted pick on the glass room, 4 segments: same HIT_ID and ray count, and IMAGE x ALBEDO
+    against the undemodulated frame within test_demodulate_gpu's bar (segments + 2) 2^-23 |value|; and the room with albedo
+    textures (TEX = 1, and TEX = 2 under RTPT_FLAG_FORCE_BVH) against the walker that samples them.
+    Measured on an MI355X: max err / bound 0.183."""
+    abi = hip_lib
+    scene, glass, rec, lights = scenes()["glass_room_two_lamps"]
+    seg = 4
+    out = {}
+    for on in (True, False):
+        with context(abi, scene, W0, H0, seg, NEE | POWER | (DEMODULATE if on else 0)) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            out[on] = frame(abi, oracle, ctx, scene, W0, H0, ("ALBEDO",) if on else ())
+    a, b = out[True], out[False]
+    same_bits(a["HIT_ID"], b["HIT_ID"], ("HIT_ID",))
+    same_frame(b, walked(oracle, scene.name, scene, W0, H0, seg, rec, lights), ("the plain trace is the walker's",))
+    assert a["rays"] == b["rays"]
+    alb, on_img, off_img = a["ALBEDO"][..., :3], a["IMAGE"][..., :3], b["IMAGE"][..., :3]
+    ended = (alb == 1).all(-1)
+    same_bits(on_img[ended], off_img[ended], ("ended at the first query",))
+    went_on = ~ended
+    err = np.abs((on_img * alb).astype(F32).astype(np.float64) - off_img.astype(np.float64))
+    bound = (seg + 2) * 2.0 ** -23 * np.abs(off_img.astype(np.float64))
+    print(f"weighted NEE demodulated: max err / bound = {np.max(err[went_on] / np.maximum(bound[went_on], 1e-300)):.3f}")
+    assert went_on.sum() > 1000 and (err[went_on] <= bound[went_on]).all()
+    for mips, base in ((False, 0), (True, FORCE_BVH)):
+        tex = TN.texture_setup(len(scene.tris), mips)
+        want = walked(oracle, f"textured_{mips}", scene, W0, H0, 5, rec, lights, texture=tex)
+        assert not np.array_equal(bits(want["IMAGE"]), bits(walked(oracle, scene.name, scene, W0, H0, 5, rec, lights)["IMAGE"]))
+        with context(abi, scene, W0, H0, 5, NEE | POWER | base) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            ctx.set_textures(*tex)
+            got = frame(abi, oracle, ctx, scene, W0, H0)
+        same_frame(got, want, ("textured", mips))
+        assert got["rays"] == want["rays"], ("textured", mips)
+
+
+# ------------------------------------------------------------------------------------------ 4. lifetime
+def _table_of(oracle, tris, rec, lights):
+    return PW.table(PW.weights(oracle, tris, rec, lights))
+
+
+@pytest.mark.parametrize("vflags", [0, FORCE_BVH], ids=["host_repose", "device_refit"])
+def test_lifetime_of_the_table(hip_lib, oracle, vflags):
+    """rtpt_debug_light_table against the restatement on the POSED scene — three instances of the unequal-lamps mesh: after
+    rtpt_scene_set_materials (with the live-bytes delta: 8 bytes an entry plus the builder's scratch beside the list's 4); after
+    rtpt_scene_set_instances with one instance scaled non-uniformly (by powers of two, so the flatten's products are exact and its
+    one rounding is numpy's), where the weights change; after a sheared ubo.model through rtpt_gbuffer, re-posed on the host (a
+    small scene) and refit on the device (RTPT_FLAG_FORCE_BVH); after rtpt_scene_rebuild and rtpt_resize, which keep it; after
+    other materials, which rebuild it; after dropped materials and after an upload, which drop it.  A frame on the moved scene
+    is the walker's"""
+    abi = hip_lib
+    gc.collect()
+    base = PW.unequal_lamps()
+    rec = DS.records(base)
+    lights = NP.light_list(base, 3)
+    xf, posed = NP.translated(base, TN.OFFSETS3)
+    with context(abi, base, W0, H0, 5, NEE | POWER | vflags) as ctx:
+        assert len(ctx.debug_light_table()) == 0, "no scene, no table"
+        ctx.scene_upload(*FP.mesh_of(base.tris), instance_xforms=xf)
+        held = abi.live_device_bytes()
+        ctx.set_materials(base.tri_material, base.materials)
+        L = len(lights)
+        assert abi.live_device_bytes() - held == 32 * len(base.tris) + 4 * L + 8 * L + PW.scratch_bytes(L)
+        want = _table_of(oracle, posed.tris, rec, lights)
+        got = ctx.debug_light_table()
+        assert got.dtype == U64 and np.array_equal(got, want), "after set_materials"
+        # one instance scaled non-uniformly, one moved
+        scale = F32([[1, 1, 1], [2, 0.5, 1], [1, 1, 1]])
+        move = F32([(0.0, 0.0, 0.0), (0.5, -0.25, -1.5), (-0.25, 0.5, -2.5)])
+        xf2 = np.zeros((3, 3, 4), F32)
+        for i in range(3):
+            xf2[i, :, :3] = np.diag(scale[i])
+            xf2[i, :, 3] = move[i]
+        b = np.asarray(base.tris, F32).reshape(-1, 3, 3)
+        moved_tris = np.concatenate([((b * scale[i][None, None, :]).astype(F32) + move[i][None, None, :]).astype(F32) for i in range(3)]).reshape(-1, 9)
+        moved = base._replace(name="unequal_scaled3", tris=P._frozen(moved_tris))
+        ctx.scene_set_instances(xf2.reshape(-1, 12))
+        want_moved = _table_of(oracle, moved.tris, rec, lights)
+        assert not np.array_equal(want_moved, want), "the weights change with the scale"
+        assert np.array_equal(ctx.debug_light_table(), want_moved), "after set_instances"
+        w = walked(oracle, "scaled3", moved, W0, H0, 5, rec, lights)
+        got = frame(abi, oracle, ctx, moved, W0, H0)
+        same_frame(got, w, ("moved",))
+        assert got["rays"] == w["rays"]
+        # a sheared model through rtpt_gbuffer
+        model = RM.model("general")
+        sheared = RM.posed(oracle, np.ascontiguousarray(moved.tris, F32), "general")
+        want_sheared = _table_of(oracle, sheared, rec, lights)
+        assert not np.array_equal(want_sheared, want_moved)
+        ubo = T._ubo(abi, oracle, moved, W0, H0)
+        ubo.model[:] = model
+        ctx.gbuffer(ubo)
+        assert np.array_equal(ctx.debug_light_table(), want_sheared), "after a sheared ubo.model"
+        ubo.model[:] = np.eye(4, dtype=F32).ravel()
+        ctx.gbuffer(ubo)
+        assert np.array_equal(ctx.debug_light_table(), want_moved), "the identity again"
+        ctx.scene_rebuild()
+        assert np.array_equal(ctx.debug_light_table(), want_moved), "rtpt_scene_rebuild keeps the table"
+        ctx.resize(W1, H1)
+        assert np.array_equal(ctx.debug_light_table(), want_moved), "rtpt_resize keeps the table"
+        ctx.resize(W0, H0)
+        ctx.enable_debug(abi.DEBUG_HIT_ID)
+        same_frame(frame(abi, oracle, ctx, moved, W0, H0), w, ("rebuilt and resized",))
+        # other materials rebuild it
+        brighter = base.materials.copy()
+        brighter[1, 3:] *= 16
+        rec2 = DS.records(base._replace(materials=P._frozen(brighter)))
+        ctx.set_materials(base.tri_material, brighter)
+        want_bright = _table_of(oracle, moved.tris, rec2, lights)
+        assert not np.array_equal(want_bright, want_moved) and np.array_equal(ctx.debug_light_table(), want_bright), "replaced materials"
+        with_table = abi.live_device_bytes()     # (not `held`: moved instances and frames allocated since)
+        ctx.set_materials(None, None)
+        assert len(ctx.debug_light_table()) == 0, "dropping the materials drops the table"
+        assert with_table - abi.live_device_bytes() == 32 * len(base.tris) + 4 * L + 8 * L + PW.scratch_bytes(L), "... and frees it"
+        ctx.set_materials(base.tri_material, base.materials)
+        assert np.array_equal(ctx.debug_light_table(), want_moved) and abi.live_device_bytes() == with_table
+        ctx.scene_upload(*FP.mesh_of(base.tris))
+        assert len(ctx.debug_light_table()) == 0, "rtpt_scene_upload drops the table with the list"
+    for flags in (NEE, POWER, POWER | SPHERE):
+        with context(abi, base, W0, H0, 5, flags | vflags) as ctx:
+            before = abi.live_device_bytes()
+            ctx.scene_upload(*FP.mesh_of(base.tris))
+            held = abi.live_device_bytes()
+            ctx.set_materials(base.tri_material, base.materials)
+            assert len(ctx.debug_light_table()) == 0, "without both bits no table is built"
+            assert abi.live_device_bytes() - held == 32 * len(base.tris) + (4 * 4 if flags & NEE else 0), hex(flags)
+            assert before <= held
+
+
+# ------------------------------------------------------------------------------------------ 5. identities
+def test_the_bit_alone_is_ignored(hip_lib, oracle):
+    """0x40000 and 0x60000 are 0 and 0x20000 bit for bit, rays included, by brute force and on the BVH; 0x50000 on a scene without an
+    emitter, or without materials, is flag off; 0x60000 on the same is 0x20000"""
+    abi = hip_lib
+    scene, glass, rec, lights = scenes()["glass_room_two_lamps"]
+    dark = scene.materials.copy()
+    dark[:, 3:] = 0
+
+    def render(flags, materials, seg=9):
+        with context(abi, scene, W0, H0, seg, flags) as ctx:
+            ctx.scene_upload(*FP.mesh_of(scene.tris))
+            if materials is not None:
+                ctx.set_materials_ext(scene.tri_material, abi.materials_ext(materials, None, glass))
+            assert len(ctx.debug_light_table()) == 0
+            return frame(abi, oracle, ctx, scene, W0, H0)
+
+    for base in (0, FORCE_BVH):
+        for a, b, materials in ((POWER, 0, scene.materials), (POWER | SPHERE, SPHERE, scene.materials), (NEE | POWER, 0, dark), (NEE | POWER, 0, None),
+                                (NEE | POWER | SPHERE, SPHERE, dark), (NEE | POWER | SPHERE, SPHERE, None)):
+            got, want = render(a | base, materials), render(b | base, materials)
+            same_frame(got, want, (hex(a), hex(b), base))
+            assert got["rays"] == want["rays"], (hex(a), hex(b), base)
+
+
+@pytest.mark.parametrize("vflags", [0, FORCE_BVH], ids=["brute", "bvh"])
+def test_equal_weights_are_the_uniform_pick(hip_lib, oracle, vflags):
+    """nee_power.equal_lamps(): every emitter weighs the same, bit for bit, and L = 4 — the condition used is "L is a power of two
+    (so it divides 2^16, and u_l * float(L) is exact) and all weights are equal": then the table is 65536 (i + 1), the weighted
+    pick names floor(m L / 2^24), the uniform pick's entry, inv_p is float(L), and 0x50000 renders 0x10000's frame"""
+    abi = hip_lib
+    scene = PW.equal_lamps()
+    out = {}
+    for flags in (NEE, NEE | POWER):
+        with context(abi, scene, W0, H0, 5, flags | vflags) as ctx:
+            TN.upload(abi, ctx, scene)
+            if flags & POWER:
+                assert ctx.debug_light_table().tolist() == [65536, 131072, 196608, 262144]
+            out[flags] = frame(abi, oracle, ctx, scene, W0, H0)
+    same_frame(out[NEE | POWER], out[NEE], ("equal weights", vflags))
+    assert out[NEE | POWER]["rays"] == out[NEE]["rays"]
+    want = walked(oracle, scene.name, scene, W0, H0, 5, DS.records(scene), NP.light_list(scene))
+    same_frame(out[NEE | POWER], want, ("the walker", vflags))
+
+
+def test_a_weighted_launch_takes_neither_queues_nor_the_final_pass(hip_lib, oracle):
+    """9 segments on the glass room: a context without the flags allocates the hand-over queues of the split launch, one with
+    0x50000 does not (rtpt_debug_live_device_bytes); and a host loop with 0x50000 never takes a deferred final pass into its tracing
+    launch (rtpt_debug_defer_info), where the same loop without the flags does"""
+    abi = hip_lib
+    gc.collect()
+    scene, glass, rec, lights = scenes()["glass_room_two_lamps"]
+    held = {}
+    for flags in (0, NEE | POWER):
+        before = abi.live_device_bytes()
+        with context(abi, scene, W0, H0, 9, flags) as ctx:
+            TN.upload(abi, ctx, scene, glass)
+            frame(abi, oracle, ctx, scene, W0, H0)
+            held[flags] = abi.live_device_bytes() - before
+    queue_bytes = ((W0 + 63) // 64) * ((H0 + 3) // 4) * 256 * 48
+    assert held[0] - held[NEE | POWER] >= queue_bytes - 12 * len(lights) - PW.scratch_bytes(len(lights)), held
+    mesh = abi.load_obj(D.SCENE)                     # test_final_defer_gpu's resting frames: the Cornell box, one fan pair a lamp
+    table = D.material_table(len(mesh[1]))
+    taken = {}
+    for flags in (0, NEE | POWER):
+        app = D.make(abi, (200, 83), flags, 4, mesh, table)
+        for _ in range(8):
+            app.drawScene(())
+        info = app.backend.ctx.defer_info()
+        taken[flags] = info["launched_in_trace"]
+        assert info["recorded"] >= 4 and info["recorded"] - info["launched_in_trace"] - info["launched_alone"] <= 1, info
+        assert len(app.backend.ctx.debug_light_table()) == (2 if flags else 0)
+        app.backend.close()
+    assert taken[NEE | POWER] == 0 and taken[0] >= 2, taken
+
+
+# ------------------------------------------------------------------------------------------ 6. hosts
+KEYS = ["", "E", "J"]
+
+
+@pytest.fixture(scope="module")
+def lamps_file(tmp_path_factory):
+    """nee_paths.two_lamps() as lamps.obj + lamps.mtl: one `f` per triangle, one newmtl per material row"""
+    scene = NP.two_lamps()
+    d = str(tmp_path_factory.mktemp("nee_power_lamps"))
+    with open(os.path.join(d, "lamps.mtl"), "w") as f:
+        for i, m in enumerate(np.asarray(scene.materials, np.float64)):
+            f.write("newmtl m%d\nKd %r %r %r\nKe %r %r %r\n" % ((i,) + tuple(float(x) for x in m)))
+    with open(os.path.join(d, "lamps.obj"), "w") as f:
+        f.write("mtllib lamps.mtl\n")
+        for v in np.asarray(scene.tris, np.float64).reshape(-1, 3):
+            f.write("v %r %r %r\n" % tuple(float(x) for x in v))
+        for t, m in enumerate(np.asarray(scene.tri_material)):
+            f.write("usemtl m%d\nf %d %d %d\n" % (m, 3 * t + 1, 3 * t + 2, 3 * t + 3))
+    return os.path.join(d, "lamps.obj")
+
+
+def host_frames(path, size, in_flight=1, **kw):
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd.app import make_app
+    app = make_app(size[0], size[1], max_segments=5, iterations=5, scene=path, frames_in_flight=in_flight, specular=True, **kw)
+    frames = []
+    for k in KEYS:
+        app.drawScene(tuple(k))
+        frames.append(app.backend.final_image_rows(0, size[1]).copy())
+    backends = getattr(app.backend, "be", [app.backend])
+    rays = sum(b.ctx.raycount() for b in backends)
+    tables = [b.ctx.debug_light_table().tolist() for b in backends]
+    app.backend.close()
+    return frames, rays, tables
+
+
+def test_hosts_pick_by_power(hip_lib, oracle, lamps_file, tmp_path):
+    """make_app(nee_power=True) on two_lamps as an OBJ file: every context holds the restatement's table, the frames differ from
+    make_app(nee=True)'s, two frames in flight render the same frames, flags=0x50000 is the same switch, and rtpt_app --nee-power
+    (which implies --nee) dumps the last frame bit for bit with the same ray count, as one context and as two strips"""
+    abi = hip_lib
+    from real_time_path_tracing_with_spatiotemporal_filtering_amd.output import read_pfm
+    size = N.SIZES[0]
+    scene = NP.two_lamps()
+    want = _table_of(oracle, scene.tris, DS.records(scene), NP.light_list(scene)).tolist()
+    on, rays_on, tables = host_frames(lamps_file, size, nee_power=True)
+    uniform, rays_uniform, no_tables = host_frames(lamps_file, size, nee=True)
+    assert tables == [want] and no_tables == [[]]
+    assert rays_on > 0 and rays_uniform > 0 and not np.array_equal(bits(on[-1]), bits(uniform[-1]))
+    two, rays_two, tables_two = host_frames(lamps_file, size, in_flight=2, nee_power=True)
+    assert tables_two == [want, want] and rays_two == rays_on
+    for f in range(len(KEYS)):
+        assert np.array_equal(bits(two[f]), bits(on[f])), f
+    flag, rays_flag, _ = host_frames(lamps_file, size, flags=NEE | POWER)
+    assert rays_flag == rays_on and np.array_equal(bits(flag[-1]), bits(on[-1]))
+    app_binary = os.path.join(D.PKG, "rtpt_app")
+    assert os.path.exists(app_binary), "build() leaves rtpt_app next to the package"
+    dumps = {}
+    for extra in (["--nee-power"], ["--nee-power", "--ranks", "2"], ["--nee"]):
+        pfm = tmp_path / "out.pfm"
+        cmd = [app_binary, "--width", str(size[0]), "--height", str(size[1]), "--segments", "5", "--iterations", "5", "--frames", str(len(KEYS)),
+               "--script", ",".join(KEYS), "--dump", str(pfm), "--scene", lamps_file, "--specular"] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True)
+        assert out.returncode == 0, out.stderr
+        dumps[tuple(extra)] = (read_pfm(str(pfm)), json.loads(out.stdout.strip().splitlines()[-1])["rays"])
+    for extra in (("--nee-power",), ("--nee-power", "--ranks", "2")):
+        assert np.array_equal(bits(dumps[extra][0]), bits(np.ascontiguousarray(on[-1][..., :3]))), extra
+        assert dumps[extra][1] == rays_on, extra
+    assert np.array_equal(bits(dumps[("--nee",)][0]), bits(np.ascontiguousarray(uniform[-1][..., :3])))
+    assert not np.array_equal(bits(dumps[("--nee",)][0]), bits(dumps[("--nee-power",)][0]))
+    help_text = subprocess.run([app_binary, "--help"], capture_output=True, text=True)
+    assert "--nee-power" in help_text.stdout + help_text.stderr
