@@ -178,9 +178,10 @@ rt::TexView tex_view(const rtpt_ctx* c) {
   return t;
 }
 
-rt::LightView light_view(const rtpt_ctx* c) {
+rt::LightTableView light_view(const rtpt_ctx* c) {
   const bool list = c->scene.lights.ptr && c->scene.materials.ptr;  // (the list is built beside the records and dropped with them)
-  return rt::LightView{list ? static_cast<const uint32_t*>(c->scene.lights.ptr) : nullptr, list ? c->scene.n_lights : 0u};
+  return rt::LightTableView{list ? static_cast<const uint32_t*>(c->scene.lights.ptr) : nullptr, list ? c->scene.n_lights : 0u,
+                            static_cast<const uint64_t*>(c->scene.light_table.cdf.ptr)};
 }
 
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose

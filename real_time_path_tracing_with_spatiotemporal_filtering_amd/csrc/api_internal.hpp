@@ -371,7 +371,7 @@ int check_rows(const rtpt_ctx* c, uint32_t& y0, uint32_t& y1);
 rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1);
 rt::SceneView scene_view(const rtpt_ctx* c);
 rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
-rt::LightView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights)
+rt::LightTableView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights), and its table or NULL
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3], double p00, double p11,
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);

@@ -177,7 +177,7 @@ int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
   a.queue_count = nullptr;
   a.queue_region = 0;
   if (!(a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS))) return RTPT_OK;
-  if (trace_material_mode(c) >= rt::kSpecNee) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
+  if (rt::spec_lights(trace_material_mode(c))) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
   const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
   const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
   const size_t cap = region * rt::kPathQueues;
@@ -485,8 +485,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), trace_material_mode(c), c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c),
-                         static_cast<const uint64_t*>(c->scene.light_table.cdf.ptr));
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c));
   }
   if (take) {
     c->deferred_valid = false;

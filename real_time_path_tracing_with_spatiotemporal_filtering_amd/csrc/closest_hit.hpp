@@ -465,7 +465,7 @@ __device__ __forceinline__ f3 bary_point(f3 v0, f3 v1, f3 v2, float b0, float b1
             fmaf_(v2.z, b2, fmaf_(v1.z, b1, v0.z * b0))};
 }
 
-// the scene's closest-hit mode, closest_hit's BVH, for with_mode3 (select.hpp): 2 BVH over fan pairs, 1 BVH over triangles, 0
+// the scene's closest-hit mode, closest_hit's BVH, for with_mode<3> (select.hpp): 2 BVH over fan pairs, 1 BVH over triangles, 0
 // brute force (the brute-force tile kernels have names of their own, *_small, for their occupancy pin)
 inline int scene_mode(const SceneView& sc) { return sc.use_bvh ? (sc.leaf_pairs ? 2 : 1) : 0; }
 

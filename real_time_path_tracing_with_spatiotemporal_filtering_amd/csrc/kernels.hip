@@ -146,17 +146,23 @@ __global__ __launch_bounds__(kThreads) void k_gradient(GradientArgs a) {
                                             ld3(a.color_prev)));
 }
 
-template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
+// The four tile kernels.  LV: the light list of an instantiation that samples lights, as a trailing parameter pack that is empty
+// for every other one or holds spec_lights_t<SPEC> (kernels.hpp): a LightView, or a LightTableView where the pick is weighted.
+// The list travels as a parameter of its own, and of those instantiations only, so that the argument segments of the kernels
+// that take none — the kernels of a build that samples no light — stay what they were.
+template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_pathtrace(PathtraceArgs a, TexView tex) {
-  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex);
+void k_pathtrace(PathtraceArgs a, TexView tex, LV... lights) {
+  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
 }
-template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
+template <bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_pathtrace_small(PathtraceArgs a, TexView tex) {
-  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex);
+void k_pathtrace_small(PathtraceArgs a, TexView tex, LV... lights) {
+  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
 }
 
 // K0 + K1 + K2 in one launch (rtpt_gbuffer / rtpt_temporal_gradient recorded right before rtpt_raytrace: main.cpp:1105-1107
@@ -166,82 +172,19 @@ void k_pathtrace_small(PathtraceArgs a, TexView tex) {
 // G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
 // trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
 // store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD, int TEX, int SPEC>
+template <int BVH, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex) {
-  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex);
+void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
+  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights...);
 }
-template <bool DEMOD, int TEX, int SPEC>
+template <bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex) {
-  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex);
-}
-
-// The same four kernels for launches that sample lights (SPEC = 3, RTPT_FLAG_EXT_NEE on a scene with a light list; SPEC = 4,
-// RTPT_FLAG_EXT_NEE_SPHERE: the sphere light too, and the list may be empty): overloads
-// that take the list as a parameter of their own behind TexView (kernels.hpp: LightView), so that the argument segments of the
-// kernels above stay what they were.
-template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_pathtrace(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
-  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
-}
-template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_pathtrace_small(PathtraceArgs a, TexView tex, LightView lights) {
-  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
-  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
-}
-template <int BVH, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
-  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
-}
-template <bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightView lights) {
-  static_assert(SPEC == 3 || SPEC == 4, "only the instantiations that sample lights take the list");
-  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
-}
-
-// ... and for launches that pick their light by weight (SPEC = 5 / 6, RTPT_FLAG_EXT_NEE_POWER: 3 / 4 with the cumulative table):
-// overloads once more, on the list's sibling that carries the table (kernels.hpp: LightTableView), so that the kernels above keep
-// their argument segments and their code.
-template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_pathtrace(PathtraceArgs a, TexView tex, LightTableView lights) {
-  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
-  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
-}
-template <bool COMPACT, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_pathtrace_small(PathtraceArgs a, TexView tex, LightTableView lights) {
-  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
-  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights);
-}
-template <int BVH, bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LightTableView lights) {
-  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
-  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights);
-}
-template <bool DEMOD, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LightTableView lights) {
-  static_assert(SPEC >= 5, "only the instantiations that pick by weight take the table");
-  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights);
+void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
+  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights...);
 }
 
 // K2 of frame n + 1 and the final filter pass of frame n in one launch (api_passes.hip: DeferredFinal).  The trace is bound by VALU
@@ -399,7 +342,7 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
 }
 void launch_gbuffer(const GbufferArgs& a, hipStream_t s) {
   if (a.g.y1 <= a.g.y0) return;
-  with_mode3(scene_mode(a.scene), [&](auto mode) {
+  with_mode<3>(scene_mode(a.scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     hipLaunchKernelGGL(k_gbuffer<M>, grid_for(a.g), dim3(kBlockX, kBlockY), M ? a.scene.stack_lds * kThreads * 4 : 0, s, a);
   });
@@ -450,21 +393,21 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
                           runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol, uint32_t* run_info, const LightView& lights, const uint64_t* light_cdf) {
+                      const FilterPolicy* pol, uint32_t* run_info, const LightTableView& lights) {
   if (run_info) {
     run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
     run_info[1] = run_info[2] = 0u;
   }
   if (a.g.y1 <= a.g.y0) return;
   dim3 block(kBlockX, kPtRows);
-  const bool nee = spec_mode(specular) >= 3;  // the launch samples lights: the SPEC = 3 / 4 tile kernels, all segments in them
-  // (api_passes.hip: trace_material_mode) SPEC = 3 samples the triangles of a list that has entries; 4 the sphere light, and the
-  // triangles where the list has entries
-  if (spec_mode(specular) == 3 && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
-  if (spec_mode(specular) == 4 && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
-  // 5 / 6: 3 / 4 with the weighted pick, on a list that has entries and a table
-  if (spec_mode(specular) >= 5 && (!lights.ids || !lights.n || !a.scene.materials || !light_cdf)) std::abort();
-  [[maybe_unused]] const LightTableView table{lights.ids, lights.n, light_cdf};
+  const int spec = spec_mode(specular);
+  const bool nee = spec_lights(spec);  // the launch samples lights: every segment runs in the tile kernels
+  // (api_passes.hip: trace_material_mode) the triangles of a list are sampled from a list with entries, on a scene with materials:
+  // where the sphere light is sampled without the weighted pick the list may be empty, everywhere else it is not
+  const bool may_be_empty = spec_sphere(spec) && !spec_power(spec);
+  if (nee && !may_be_empty && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
+  if (nee && may_be_empty && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
+  if (spec_power(spec) && !lights.cdf) std::abort();  // the weighted pick reads the list's table
   const bool pool = !nee && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
@@ -510,65 +453,40 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   } else
 #endif
   // the instantiation list of the family: scene mode x DEMOD x TEX x SPEC (x COMPACT for the unfused launch), here and nowhere else
-  with_mode3(scene_mode(a.scene), [&](auto mode) {
+  with_mode<3>(scene_mode(a.scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
       constexpr bool D = decltype(demod)::value;
-      with_mode3(tex_mode(tex), [&](auto tmode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
+      with_mode<3>(tex_mode(tex), [&](auto tmode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tmode)::value;
-        // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE: those that
-        // sample lights too (3), RTPT_FLAG_EXT_NEE_SPHERE: and the sphere light (4), which take the light list as one more argument
-        // RTPT_FLAG_EXT_NEE_POWER: 3 / 4 with the weighted pick (5 / 6), which take the list with its table
-        with_mode7(spec_mode(specular), [&](auto spec) {
-          constexpr int S = decltype(spec)::value;
-          if constexpr (S >= 5) {
+        // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE,
+        // RTPT_FLAG_EXT_NEE_SPHERE, RTPT_FLAG_EXT_NEE_POWER: those that sample lights (kernels.hpp: the SPEC axis)
+        with_mode<kSpecModes>(spec, [&](auto smode) {
+          constexpr int S = decltype(smode)::value;
+          // l: the light argument S asks for, spec_lights_t<S>.  (The launch syntax, because a kernel template with a parameter pack
+          // left to deduction is no argument for hipLaunchKernelGGL's deduced kernel type: a call deduces it from its arguments.)
+          const auto go = [&](auto... l) {
             if (gb) {
               if constexpr (M != 0)
-                k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, table);
+                k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
               else
-                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, table);
+                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
               return;
             }
             with_bool(a.compact != 0, [&](auto compact) {
               constexpr bool C = decltype(compact)::value;
               if constexpr (M != 0)
-                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, table);
+                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
               else
-                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, table);
+                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
             });
-          } else if constexpr (S >= 3) {
-            // (the launch syntax, because these kernels are OVERLOADS of the names below: an overload set is no argument for
-            // hipLaunchKernelGGL's deduced kernel type, a call resolves it by its arguments)
-            if (gb) {
-              if constexpr (M != 0)
-                k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, lights);
-              else
-                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, lights);
-              return;
-            }
-            with_bool(a.compact != 0, [&](auto compact) {
-              constexpr bool C = decltype(compact)::value;
-              if constexpr (M != 0)
-                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, lights);
-              else
-                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, lights);
-            });
-          } else {
-            if (gb) {
-              if constexpr (M != 0)
-                hipLaunchKernelGGL((k_gbuffer_pathtrace<M, D, T, S>), grid, block, dyn, s, b, *gb, tex);
-              else
-                hipLaunchKernelGGL((k_gbuffer_pathtrace_small<D, T, S>), grid, block, dyn, s, b, *gb, tex);
-              return;
-            }
-            with_bool(a.compact != 0, [&](auto compact) {
-              constexpr bool C = decltype(compact)::value;
-              if constexpr (M != 0)
-                hipLaunchKernelGGL((k_pathtrace<M, C, D, T, S>), grid, block, dyn, s, b, tex);
-              else
-                hipLaunchKernelGGL((k_pathtrace_small<C, D, T, S>), grid, block, dyn, s, b, tex);
-            });
-          }
+          };
+          if constexpr (spec_power(S))
+            go(lights);
+          else if constexpr (spec_lights(S))
+            go(LightView{lights.ids, lights.n});
+          else
+            go();
         });
       });
     });
@@ -588,9 +506,9 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     c.q_out = more ? a.queue[cur ^ 1] : nullptr;
     c.q_out_count = more ? a.queue_count + (cur ^ 1) * kPathQueues : nullptr;
     if (more) (void)hipMemsetAsync(a.queue_count + (cur ^ 1) * kPathQueues, 0, kPathQueues * sizeof(uint32_t), s);
-    with_mode3(scene_mode(a.scene), [&](auto mode) {
-      with_mode3(tex_mode(tex), [&](auto tmode) {
-        with_mode3(spec_mode(specular), [&](auto spec) {
+    with_mode<3>(scene_mode(a.scene), [&](auto mode) {
+      with_mode<3>(tex_mode(tex), [&](auto tmode) {
+        with_mode<3>(spec_mode(specular), [&](auto spec) {
           hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tmode)::value, decltype(spec)::value>), qgrid, block,
                              dyn_queue, s, c, tex);
         });

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "bvh.hpp"
 #include "texture.hpp"
 
@@ -60,33 +62,52 @@ struct TexView {
 
 // The light list of next-event estimation (RTPT_FLAG_EXT_NEE; light_sample.hpp, light_list_host.hpp): ids[i] = id + 1 of a posed
 // emissive triangle, ascending; n in [1, 2^24] where a kernel reads it.  It travels as a parameter of its own behind TexView, and
-// only of the kernels that sample lights (kernels.hip: the overloads of the four tile kernels that take a LightView), for TexView's reason: inside SceneView the pointer would move
-// every later field of PathtraceArgs / GbufferArgs, and behind TexView it would change the argument segment of every tracing kernel.
-// The kernels that sample the sphere light too (RTPT_FLAG_EXT_NEE_SPHERE, SPEC = 4) take it the same way; there ids may be NULL
-// and n 0: no triangle is sampled.
+// only of the instantiations that sample lights (kernels.hip: the tile kernels' trailing parameter pack), for TexView's reason:
+// inside SceneView the pointer would move every later field of PathtraceArgs / GbufferArgs, and as a field of TexView it would
+// change the argument segment of every tracing kernel.  The instantiations that sample the sphere light too
+// (RTPT_FLAG_EXT_NEE_SPHERE) take it the same way; there ids may be NULL and n 0: no triangle is sampled.
 struct LightView {
   const uint32_t* ids;
   uint32_t n;
 };
-// launch_pathtrace's `specular` for a launch that samples lights: the SPEC = 3 instantiations, which include the specular and
-// dielectric bounces (Scene::materials_specular is 0, 1 or 2)
-constexpr int kSpecNee = 3;
-// ... and for a launch of a context with RTPT_FLAG_EXT_NEE_SPHERE: the SPEC = 4 instantiations, SPEC = 3 plus the sample of the
-// analytic sphere light, whatever the scene's materials or light list
-constexpr int kSpecNeeSphere = 4;
 // The light list with the cumulative table of RTPT_FLAG_EXT_NEE_POWER behind it (light_sample.hpp: pick_power; light_table.hip
 // builds it): cdf[i] = the sum of the quantised weights of entries 0..i, cdf[n - 1] = S.  A sibling of LightView, not a field of
-// it, and the parameter of overloads of their own (SPEC = 5 / 6), so that the argument segments and the code of the SPEC = 3 / 4
-// kernels stay what they were; ids, cdf non-NULL and n in [1, 2^24] wherever a kernel takes it.
+// it: the instantiations that pick by weight take this one, the others that sample lights a LightView — its first two fields —
+// so that their argument segments and their code are those of a build without the table.  ids, cdf non-NULL and n in [1, 2^24]
+// wherever a kernel takes it.  The host carries the list in this form (launch_pathtrace), cdf NULL where there is no table.
 struct LightTableView {
   const uint32_t* ids;
   uint32_t n;
   const uint64_t* cdf;
 };
-// ... for a launch of a context with RTPT_FLAG_EXT_NEE and RTPT_FLAG_EXT_NEE_POWER on a scene whose light list has entries: SPEC = 3
-// with the weighted pick (5), and SPEC = 4 with it (6, RTPT_FLAG_EXT_NEE_SPHERE besides).  With an empty list 0x60000 launches 4
+
+// THE SPEC AXIS of shade_segment and the tile kernels, and launch_pathtrace's `specular`.  0, 1, 2 are the material modes
+// (Scene::materials_specular): every material diffuse, some specular, some dielectric.  The values above them sample lights and
+// include the specular and dielectric bounces:
+//   kSpecNee             RTPT_FLAG_EXT_NEE on a scene whose light list has entries: the triangles of the list, picked uniformly
+//   kSpecNeeSphere       a context with RTPT_FLAG_EXT_NEE_SPHERE, whatever the scene's materials or light list: the analytic
+//                        sphere light, and the triangles where the list has entries
+//   kSpecNeePower        RTPT_FLAG_EXT_NEE and RTPT_FLAG_EXT_NEE_POWER on a list with entries: kSpecNee with the weighted pick
+//   kSpecNeeSpherePower  ... and RTPT_FLAG_EXT_NEE_SPHERE besides: kSpecNeeSphere with it (with an empty list 0x60000 launches
+//                        kSpecNeeSphere)
+// Nothing outside this block compares a SPEC with a number: it asks the predicates.
+constexpr int kSpecNee = 3;
+constexpr int kSpecNeeSphere = 4;
 constexpr int kSpecNeePower = 5;
 constexpr int kSpecNeeSpherePower = 6;
+constexpr int kSpecModes = 7;  // SPEC lies in [0, kSpecModes)
+constexpr bool spec_lights(int spec) { return spec >= kSpecNee; }                                        // samples lights
+constexpr bool spec_sphere(int spec) { return spec == kSpecNeeSphere || spec == kSpecNeeSpherePower; }   // ... the sphere light
+constexpr bool spec_power(int spec) { return spec == kSpecNeePower || spec == kSpecNeeSpherePower; }     // ... picks by weight
+constexpr int spec_material(int spec) { return spec_lights(spec) ? 2 : spec; }                           // its material mode
+// what an instantiation takes behind TexView: nothing (void), the list, or the list with its table
+template <int SPEC>
+using spec_lights_t = std::conditional_t<spec_power(SPEC), LightTableView, std::conditional_t<spec_lights(SPEC), LightView, void>>;
+// ... as a trailing parameter pack LV: empty, or that one type
+template <int SPEC, class... LV>
+constexpr bool spec_takes() {
+  return sizeof...(LV) == (spec_lights(SPEC) ? 1u : 0u) && (std::is_same<LV, spec_lights_t<SPEC>>::value && ...);
+}
 
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
 // and the same columns of row min(2y + 1, sh - 1) of level l (texture_mips.hip): one launch per level.  src and dst are texel
@@ -363,12 +384,12 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
 void launch_gradient(const GradientArgs& a, hipStream_t s);
 // gb != NULL: K0 (+ K1) of gb's rows run inside the tile kernel's launch, behind the tracing tiles (pathtrace_fuses_gbuffer says
 // whether they can; pathtrace_grid_blocks = the workgroups of that launch, what the BVH stack's spill area is sized for)
-// specular: 1 some triangle's material is specular, 2 some triangle's is a dielectric, 0 neither (Scene::materials_specular) — what
-// selects the SPEC instantiations; it travels
-// beside the kernel arguments, not in them, so that every existing argument offset stays.  kSpecNee (then `lights` has entries):
-// the launch samples lights, every segment runs in the tile kernel (no queue kernels) and it carries no final pass; the same for
-// kSpecNeeSphere, whose `lights` may be empty; kSpecNeePower / kSpecNeeSpherePower: `lights` has entries and light_cdf is its
-// cumulative table (LightTableView)
+// specular: the launch's SPEC (the block of kSpecNee above) — what selects the SPEC instantiations; it travels beside the kernel
+// arguments, not in them, so that every existing argument offset stays.  A launch that samples lights (spec_lights) runs every
+// segment in the tile kernel (no queue kernels) and carries no final pass.
+// lights: the light list in its host form, handed to a kernel as spec_lights_t<SPEC> says: not at all, as a LightView (its first
+// two fields) or whole.  It has entries where the launch samples the list's triangles (with spec_sphere alone it may be empty),
+// and a table (cdf) where it picks by weight (spec_power).
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -377,8 +398,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // (final_split.hpp; a launch without runs: every column, 0, 0)
 struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
-                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr, const LightView& lights = LightView{nullptr, 0u},
-                      const uint64_t* light_cdf = nullptr);
+                      const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr,
+                      const LightTableView& lights = LightTableView{nullptr, 0u, nullptr});
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);

@@ -1,7 +1,7 @@
 // light_sample.hpp — the light sample of next-event estimation: one point on one emissive triangle per diffuse hit, stated once.
-// The SPEC = 3 instantiations of the tile kernels call it (shade_segment.hpp, pathtrace_tile.hpp), and the self test
-// (rtpt_selftest_light_sample, k_selftest_light_sample).  Below it, the sample of the analytic sphere light (sphere_sample,
-// RTPT_FLAG_EXT_NEE_SPHERE), which the SPEC = 4 instantiations call besides.  Not reference behaviour: the reference collects light only by hitting
+// The instantiations of the tile kernels that sample lights call it (spec_lights(SPEC): shade_segment.hpp, pathtrace_tile.hpp), and
+// the self test (rtpt_selftest_light_sample, k_selftest_light_sample).  Below it, the sample of the analytic sphere light
+// (sphere_sample, RTPT_FLAG_EXT_NEE_SPHERE), which the spec_sphere(SPEC) instantiations call besides.  Not reference behaviour: the reference collects light only by hitting
 // it.  Contract functions only (rtpt_math.hpp), no new transcendental; tests/nee_scenes.py restates every step in numpy float32,
 // tests/nee_paths.py walks whole paths with it.
 //
@@ -12,7 +12,7 @@
 //     origin x = o, before the bounce's two draws.
 //   * Three draws u_l, u_a, u_b in that order; entry i = pick(u_l, L) names posed triangle id = lights[i] (id + 1, as
 //     HitRec::id1); its vertices and unit normal come from its shade record, its Ke from the material record of
-//     (id - 1) % n_base_tris; s = sample(v0, v1, v2, nl, x, nf, u_a, u_b, L).
+//     (id - 1) % n_base_tris; s = sample(v0, v1, v2, nl, x, nf, u_a, u_b, float(L)).
 //   * If s.valid, ONE closest-hit query goes from x along s.wd, with the launch's tmax and the path's own closest_hit<BVH>, tie
 //     rule included; if it returns id, the pixel's radiance R gains ((T.c * Ke.c) * s.g) per channel c: two multiplies in that
 //     order, one addition into R, a rounding each.  The query counts as a ray for pixels inside the count rows.
@@ -63,8 +63,9 @@ struct Sample {
 };
 
 // v0, v1, v2, nl: the light's vertices and unit normal (its shade record); x: the bounce origin; nf: the hit's normal, faced
-// against the arriving ray; u_a, u_b: the draws behind u_l; L: entries of the list
-__device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf, float u_a, float u_b, uint32_t L) {
+// against the arriving ray; u_a, u_b: the draws behind u_l; inv_p: the inverse of the pick's probability — float(L) for the
+// uniform pick among L entries, Pick::inv_p for the weighted one
+__device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf, float u_a, float u_b, float inv_p) {
   Sample s;
   const float su = exact::sqrt_(u_a);
   const float b0 = 1.0f - su, b1 = su * (1.0f - u_b), b2 = su * u_b;
@@ -77,7 +78,7 @@ __device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf
   const f3 c = exact::cross(v1 - v0, v2 - v0);
   const float a2 = exact::sqrt_(exact::dot(c, c));
   s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
-  s.g = exact::div_((cs * cl) * (a2 * static_cast<float>(L)), k2Pi * r2);
+  s.g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2);
   return s;
 }
 
@@ -99,7 +100,7 @@ __device__ __forceinline__ Sample sample(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf
 //   * Pick: m = uint32(u_l * 2^24), exact since a draw is a multiple of 2^-24; t = (uint64(m) * S) >> 24 (the product is below
 //     2^64); the entry is the smallest i with C_i > t, by binary search; inv_p = exact::div_(float(S), float(q_i)), the
 //     uint64 -> binary32 conversion rounding to nearest even.
-//   * g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2): sample_inv_p below, sample() with inv_p where it takes L.
+//   * g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2): sample() above, with this inv_p where the uniform pick passes float(L).
 // KNOWN LIMIT, of the kind of kMaxLights: an entry with q_i * 2^24 < S can be skipped by all 2^24 values of the draw, and its
 // share of the light is then lost.  That needs S > 2^24: hundreds of full-weight lights beside one of the smallest weight.
 constexpr float kPickScale = 16777216.0f;    // 2^24
@@ -146,24 +147,6 @@ __device__ __forceinline__ Pick pick_power(float u_l, const uint64_t* C, uint32_
   }
   const uint64_t q = C[lo] - (lo ? C[lo - 1u] : 0ull);
   return Pick{lo, exact::div_(static_cast<float>(S), static_cast<float>(q))};
-}
-
-// sample() with the inverse of the pick's probability where it takes L
-__device__ __forceinline__ Sample sample_inv_p(f3 v0, f3 v1, f3 v2, f3 nl, f3 x, f3 nf, float u_a, float u_b, float inv_p) {
-  Sample s;
-  const float su = exact::sqrt_(u_a);
-  const float b0 = 1.0f - su, b1 = su * (1.0f - u_b), b2 = su * u_b;
-  s.y = bary_point(v0, v1, v2, b0, b1, b2);
-  const f3 w = s.y - x;
-  const float r2 = exact::dot(w, w);
-  s.wd = exact::normalize(w);
-  const float cs = exact::dot(nf, s.wd);
-  const float cl = __builtin_fabsf(exact::dot(nl, s.wd));
-  const f3 c = exact::cross(v1 - v0, v2 - v0);
-  const float a2 = exact::sqrt_(exact::dot(c, c));
-  s.valid = (cs > 0.0f) && (cl > 0.0f) && (r2 > 0.0f) && (a2 > 0.0f);  // NaN fails every comparison
-  s.g = exact::div_((cs * cl) * (a2 * inv_p), k2Pi * r2);
-  return s;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -95,9 +95,8 @@ constexpr int kPtWaves = 8;
 // taller than the tile grid (a.tiles_y rows of tiles).
 // DEMOD: RTPT_FLAG_EXT_DEMODULATE, the albedo store of segment 0 (PathtraceArgs::albedo).  A compile-time switch: as a run-time
 // test the extra pointer cost the BVH variants, pinned at 64 VGPRs, 2 to 15 more spilled registers per lane, also with the flag off.
-// TEX: shade_segment samples the scene's albedo textures.  SPEC: it bounces specular materials (1, specular.hpp) and dielectric
-// ones too (2, dielectric.hpp), and samples the scene's lights besides (3, light_sample.hpp; `lights` then has entries), and the
-// analytic sphere light too (4; `lights` may then be empty).
+// TEX: shade_segment samples the scene's albedo textures.  SPEC: the materials it bounces and the lights it samples (kernels.hpp
+// names the axis, shade_segment.hpp says what each value does).
 // the tile grid's width / a tile's linear index, where pathtrace_tile used to read gridDim.x / compute the index (every use keeps
 // its place, so that the ROLE = 0 instantiations compile to what they were)
 template <int ROLE>
@@ -113,11 +112,12 @@ __device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
 // ROLE: 1 in the launch that also holds filter workgroups (k_pathtrace_final).  An instantiation of its own, so that its three
 // static LDS words are that kernel's alone: shared between two kernels they would move into the module-wide LDS block and
 // shift the dynamic LDS of every kernel of kernels.hip.
-// LV: what `lights` is — LightView, or LightTableView for the instantiations that pick by weight (SPEC = 5 / 6)
-template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0, class LV = LightView>
+// lights: the light list as SPEC takes it (spec_lights_t<SPEC>), the tile kernels' trailing parameter pack: nothing where no light is
+// sampled
+template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0, class... LV>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
-                                               const uint32_t role_gy = 0, [[maybe_unused]] const LV& lights = LV{}) {
-  static_assert(std::is_same<LV, LightTableView>::value == spec_power(SPEC), "the instantiations that pick by weight take the table");
+                                               const uint32_t role_gy = 0, const LV&... lights) {
+  static_assert(spec_takes<SPEC, LV...>(), "an instantiation takes the light argument of its SPEC, spec_lights_t<SPEC>");
   // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -128,12 +128,12 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   // per-pixel sample accumulators and RNG state between samples: behind the shared region, allocated (by
   // launch_pathtrace) only when spp > 1 — the reference runs 1 spp (raytrace.comp.glsl:306); spp > 1 is an EXTENSION, see
   // the note at the rng_pix store below
-  // SPEC >= 3: the pixel's radiance R, what its light samples collected so far (light_sample.hpp), sits where the sums sit
+  // spec_lights(SPEC): the pixel's radiance R, what its light samples collected so far (light_sample.hpp), sits where the sums sit
   // otherwise and the sums move behind it; allocated by launch_pathtrace for these instantiations only.  Indexed by the local
   // pixel `pix`, like the sums, because the compaction moves paths between threads; one path per pixel is live at a time, so a
   // plain read-modify-write has no race.  Zeroed at the start of every sample by the thread that starts on the pixel, read where
   // the path ends.
-  constexpr uint32_t kRadWords = SPEC >= 3 ? 3u * kPtThreads : 0u;
+  constexpr uint32_t kRadWords = spec_lights(SPEC) ? 3u * kPtThreads : 0u;
   [[maybe_unused]] float* const rad_r = reinterpret_cast<float*>(stack + a.multi_off);
   [[maybe_unused]] float* const rad_g = rad_r + kPtThreads;
   [[maybe_unused]] float* const rad_b = rad_g + kPtThreads;
@@ -175,7 +175,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   const uint32_t pix0 = tile_pixel(wave, lane);  // the pixel this thread starts on
   uint32_t pix = pix0, rng = 0;
   f3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, -1.f}, acc{1.f, 1.f, 1.f};
-  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false, f3{0.f, 0.f, 0.f}, false, false};  // SPEC >= 3
+  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false, f3{0.f, 0.f, 0.f}, false, false};  // spec_lights(SPEC)
   {
     const int x = tile_x0 + static_cast<int>(pix0 & 63u), y = tile_y0 + static_cast<int>(pix0 >> 6);
     rng = exact::rng_seed(static_cast<uint32_t>(x), static_cast<uint32_t>(y), a.frame, a.batch);  // :297
@@ -188,7 +188,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       pix = pix0;
       rng = rng_pix[pix0];  // the pixel's RNG state after its previous sample (stored at path end)
     }
-    if constexpr (SPEC >= 3) {
+    if constexpr (spec_lights(SPEC)) {
       // (smp > 0: behind the barrier above, so the thread that ended this pixel's previous path has read its R)
       rad_r[pix0] = rad_g[pix0] = rad_b[pix0] = 0.0f;
       nee.sampled = false;  // the primary ray
@@ -223,18 +223,16 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if (seg == 0 && smp == 0 && a.hit_id) a.hit_id[gi] = h.id1;
         // the short barycentric divisions where they cost no register: with DEMOD or without compaction they spill one
         constexpr bool kShortDiv = (RTPT_TRACE_ITEMS & 8) && BVH == 0 && COMPACT && !DEMOD;
-        if constexpr (SPEC >= 3) nee.valid = false;
+        if constexpr (spec_lights(SPEC)) nee.valid = false;
         if constexpr (spec_sphere(SPEC)) nee.sphere_valid = false;
         bool done;
-        if constexpr (spec_power(SPEC))
-          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgsPower>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
-                                                                        NeeArgsPower{lights, &nee});
-        else if constexpr (SPEC >= 3)
-          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
-                                                                   NeeArgs{lights, &nee});
+        if constexpr (spec_lights(SPEC))
+          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs<spec_lights_t<SPEC>>>(a, h, seg, light_c, o, d, acc, rng, tex,
+                                                                                        (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
+                                                                                        NeeArgs<spec_lights_t<SPEC>>{lights..., &nee});
         else
           done = shade_segment<TEX, BVH, kShortDiv, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr);
-        if constexpr (SPEC >= 3) {
+        if constexpr (spec_lights(SPEC)) {
           // The sphere sample's gain (RTPT_FLAG_EXT_NEE_SPHERE) goes into R first: it needs no query, the order of the two additions
           // is fixed this way, and the gain is dead before the traversal below starts.
           if constexpr (spec_sphere(SPEC)) {
@@ -303,12 +301,10 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       if (alive) {
         const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(live >> 32),
                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(live), 0u));
-        if constexpr (spec_sphere(SPEC))
-          st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u) | (nee.sphere ? 0x200u : 0u);  // ... and the sphere bit beside it
-        else if constexpr (SPEC >= 3)
-          st.pix[slot] = pix | (nee.sampled ? 0x100u : 0u);  // pix has 8 bits: the sampled bit travels with the path
-        else
-          st.pix[slot] = pix;
+        uint32_t word = pix;  // pix has 8 bits: the path's sampled bit travels with it, and the sphere bit beside that
+        if constexpr (spec_lights(SPEC)) word |= nee.sampled ? 0x100u : 0u;
+        if constexpr (spec_sphere(SPEC)) word |= nee.sphere ? 0x200u : 0u;
+        st.pix[slot] = word;
         st.rng[slot] = rng;
         st.ox[slot] = o.x; st.oy[slot] = o.y; st.oz[slot] = o.z;
         st.dx[slot] = d.x; st.dy[slot] = d.y; st.dz[slot] = d.z;
@@ -318,7 +314,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
       alive = static_cast<uint32_t>(tid) < total;
       if (alive) {
         pix = st.pix[tid];
-        if constexpr (SPEC >= 3) {
+        if constexpr (spec_lights(SPEC)) {
           nee.sampled = (pix & 0x100u) != 0u;
           if constexpr (spec_sphere(SPEC)) nee.sphere = (pix & 0x200u) != 0u;
           pix &= 0xFFu;
@@ -409,14 +405,10 @@ __device__ __forceinline__ void pathtrace_empty_run(const PathtraceArgs& a, uint
 // K0 + K1 + K2 in one launch, the body of k_gbuffer_pathtrace and k_gbuffer_pathtrace_small (kernels.hip has the reasons): rows
 // [0, a.tiles_y) of the grid are the tracing tiles, the rows behind them the G-buffer's 64 x 4 tiles, which put their depth into
 // the alpha of the traced image's pixels
-template <int BVH, bool DEMOD, int TEX, int SPEC, class LV = LightView>
-__device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, const GbufferArgs& g, const TexView& tex,
-                                                       [[maybe_unused]] const LV& lights = LV{}) {
+template <int BVH, bool DEMOD, int TEX, int SPEC, class... LV>
+__device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, const GbufferArgs& g, const TexView& tex, const LV&... lights) {
   if (blockIdx.y < a.tiles_y) {
-    if constexpr (SPEC >= 3)
-      pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC, 0, LV>(a, tex, 0, 0, 0, lights);
-    else
-      pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex);
+    pathtrace_tile<BVH, true, true, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
   } else {
     extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
 #if RTPT_TILE_TIMELINE

@@ -1,6 +1,6 @@
 // select.hpp — from a run-time value to a template argument.  A kernel family lists its instantiations ONCE, as a
 // type_list of tag types; the prepare function visits every entry, the launch function the first entry that matches, and
-// a run-time bool reaches a generic lambda as std::true_type / std::false_type, a three-valued mode as an integral_constant.
+// a run-time bool reaches a generic lambda as std::true_type / std::false_type, a mode of N values as an integral_constant (with_mode<N>).
 #pragma once
 
 #include <type_traits>
@@ -30,42 +30,19 @@ inline void with_bool(bool b, F&& f) {
   else
     f(std::false_type{});
 }
-// f(std::integral_constant<int, mode>{}) for a mode of 0, 1 or 2 (anything else is 0): the three-valued template axes of the
-// tracing kernels, whose modes scene_mode (closest_hit.hpp), tex_mode and spec_mode (shade_segment.hpp) compute
-template <class F>
-inline void with_mode3(int mode, F&& f) {
-  if (mode == 2)
-    f(std::integral_constant<int, 2>{});
-  else if (mode == 1)
-    f(std::integral_constant<int, 1>{});
-  else
+// f(std::integral_constant<int, mode>{}) for a mode in [0, N) (anything else is 0): the many-valued template axes of the tracing
+// kernels — with_mode<3> for scene_mode (closest_hit.hpp), tex_mode and the queue kernels' spec_mode (shade_segment.hpp),
+// with_mode<kSpecModes> for the tile kernels' SPEC (kernels.hpp)
+template <int N, class F>
+inline void with_mode(int mode, F&& f) {
+  if constexpr (N > 1) {
+    if (mode == N - 1)
+      f(std::integral_constant<int, N - 1>{});
+    else
+      with_mode<N - 1>(mode, f);
+  } else {
     f(std::integral_constant<int, 0>{});
-}
-// ... and for a mode of 0 to 3: shade_segment's material axis in the tile kernels, whose fourth value samples lights (spec_mode)
-template <class F>
-inline void with_mode4(int mode, F&& f) {
-  if (mode == 3)
-    f(std::integral_constant<int, 3>{});
-  else
-    with_mode3(mode, f);
-}
-// ... and of 0 to 4: the fifth value samples the analytic sphere light as well
-template <class F>
-inline void with_mode5(int mode, F&& f) {
-  if (mode == 4)
-    f(std::integral_constant<int, 4>{});
-  else
-    with_mode4(mode, f);
-}
-// ... and of 0 to 6: 5 and 6 are 3 and 4 with the weighted light pick
-template <class F>
-inline void with_mode7(int mode, F&& f) {
-  if (mode == 5)
-    f(std::integral_constant<int, 5>{});
-  else if (mode == 6)
-    f(std::integral_constant<int, 6>{});
-  else
-    with_mode5(mode, f);
+  }
 }
 // f(FINAL, EXACT): the two bools every filter kernel is instantiated over
 template <class F>

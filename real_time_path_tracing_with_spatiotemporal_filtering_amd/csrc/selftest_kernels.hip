@@ -224,7 +224,7 @@ __global__ void k_selftest_light_sample(const uint32_t* in, uint32_t* out, size_
   const f3 v0 = ld3(w), v1 = ld3(w + 3), v2 = ld3(w + 6);
   const uint32_t L = in[19 * i + 18];
   const f3 nl = exact::normalize(exact::cross(v1 - v0, v2 - v0));  // raytrace.comp.glsl:150
-  const light::Sample s = light::sample(v0, v1, v2, nl, ld3(w + 9), ld3(w + 12), w[16], w[17], L);
+  const light::Sample s = light::sample(v0, v1, v2, nl, ld3(w + 9), ld3(w + 12), w[16], w[17], static_cast<float>(L));
   uint32_t* r = out + 9 * i;
   r[0] = f2u(s.y.x); r[1] = f2u(s.y.y); r[2] = f2u(s.y.z);
   r[3] = f2u(s.wd.x); r[4] = f2u(s.wd.y); r[5] = f2u(s.wd.z);
@@ -355,7 +355,7 @@ void launch_selftest_footprint(const SceneView& scene, const TexView& tex, const
                                int frame_h, uint32_t* out_id, float* out_lod, hipStream_t s) {
   if (!n) return;
   dim3 grid((n + kThreads - 1) / kThreads), block(kThreads);
-  with_mode3(scene_mode(scene), [&](auto mode) {
+  with_mode<3>(scene_mode(scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     hipLaunchKernelGGL(k_selftest_footprint<M>, grid, block, M ? scene.stack_lds * kThreads * 4 : 0, s, scene, tex, rays, n, tmax,
                        primary ? 1u : 0u, slope, frame_h, out_id, out_lod);
@@ -365,7 +365,7 @@ void launch_selftest_trace(const SceneView& scene, const float* rays, size_t n, 
                            float* out_t, hipStream_t s) {
   if (!n) return;
   dim3 grid((n + kThreads - 1) / kThreads), block(kThreads);
-  with_mode3(scene_mode(scene), [&](auto mode) {
+  with_mode<3>(scene_mode(scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     hipLaunchKernelGGL(k_selftest_trace<M>, grid, block, M ? scene.stack_lds * kThreads * 4 : 0, s, scene, rays, n, tmax, out_id, out_t);
   });

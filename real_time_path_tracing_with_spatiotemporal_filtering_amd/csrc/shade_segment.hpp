@@ -97,52 +97,49 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // instantiations over fan pairs (BVH == 2, TEX == 0; pinned at 64 VGPRs with 8 to 14 spilled ones — the early return cost
 // k_gbuffer_pathtrace<2, false, 0>, the kernel of the instanced frame, one more: 36 -> 40 bytes of scratch) and the segment that
 // stores the albedo plane (alb_px; 0 -> 8 bytes in the brute-force DEMOD kernels), which is a path's last only with max_segments 1.
-// SPEC: some triangle's material is specular (rtpt_scene_set_materials_ext; specular.hpp states the bounce): such a hit takes Ks
-// where a diffuse one takes Kd — the record's colour, so everything above happens to it unchanged — and leaves along the lobe
-// around its mirror direction, with the same two draws.  A compile-time switch for DEMOD's and TEX's reason.  These instantiations
-// return early on every last segment (no exception for their registers: they are new), so that no schedule absorbs a path there.
-// SPEC == 2: some triangle's material is a dielectric too (RTPT_MAT_DIELECTRIC; dielectric.hpp states the interface): such a hit
-// takes the record's colour the same way, takes both draws, and leaves reflected or refracted by its first draw against the
-// Fresnel term.  The origin is formed after the choice, its offset's sign selected once, so that the hit point is live once (the
-// BVH variants are pinned at 64 VGPRs).  0 and 1 are the instantiations before it, statement for statement.
-// SPEC == 3: SPEC == 2 plus the light sample of next-event estimation (RTPT_FLAG_EXT_NEE on a scene whose light list has entries;
+// SPEC (kernels.hpp names the axis and its predicates; every value is a compile-time switch for DEMOD's and TEX's reason, and each is
+// the instantiation before it, statement for statement, where its predicate is false):
+// spec_material(SPEC) >= 1: some triangle's material is specular (rtpt_scene_set_materials_ext; specular.hpp states the bounce): such
+// a hit takes Ks where a diffuse one takes Kd — the record's colour, so everything above happens to it unchanged — and leaves along
+// the lobe around its mirror direction, with the same two draws.  These instantiations return early on every last segment (no
+// exception for their registers: they are new), so that no schedule absorbs a path there.
+// spec_material(SPEC) == 2: some triangle's material is a dielectric too (RTPT_MAT_DIELECTRIC; dielectric.hpp states the interface):
+// such a hit takes the record's colour the same way, takes both draws, and leaves reflected or refracted by its first draw against
+// the Fresnel term.  The origin is formed after the choice, its offset's sign selected once, so that the hit point is live once (the
+// BVH variants are pinned at 64 VGPRs).
+// spec_lights(SPEC): the light sample of next-event estimation besides (RTPT_FLAG_EXT_NEE on a scene whose light list has entries;
 // light_sample.hpp states the rules, the estimator and the order of the draws).  A DIFFUSE hit that is not the path's last segment
 // takes three more draws (u_l, u_a, u_b) behind its offset origin and in front of the bounce's two, samples one point of one
 // entry of the list and leaves in `nee` the shadow ray's direction, the triangle it must reach and the colour the pixel's radiance
 // gains if it does, (T * Ke) * g per channel; the caller sends the query (pathtrace_tile).  nee.sampled is the path's sampled bit:
 // set by such a hit whether or not the sample was valid, cleared by a specular or dielectric one, and an emissive triangle met
 // with the bit set ends the path with colour 0 — its light was already collected at the hit before.
-// SPEC == 4: SPEC == 3 plus the sample of the analytic sphere light (RTPT_FLAG_EXT_NEE_SPHERE; light_sample.hpp states the rules):
+// spec_sphere(SPEC): the sample of the analytic sphere light too (RTPT_FLAG_EXT_NEE_SPHERE; light_sample.hpp states the rules):
 // two more draws (u_c, u_p) behind the triangle sample's three, no query; the gain (T * light_col) * g is left in `nee` (sphere_c,
 // sphere_valid) for the caller to add to R before it sends the triangle's shadow query, and nee.sphere is the path's sphere bit,
-// with which a segment that meets the light ends with colour 0.  Here the triangle sample is taken only where the list has
-// entries (wave-uniform): with the sphere flag alone these instantiations run without a list and without a material table.
-// A compile-time switch because a run-time one cost the SPEC == 3 kernels 3.5 % of a frame with the switch off
-// (profiles/r23_nee_sphere_measure.txt); 3 is the instantiation before it, statement for statement.
-// SPEC == 5 / 6: SPEC == 3 / 4 with the weighted pick of RTPT_FLAG_EXT_NEE_POWER (light_sample.hpp: pick_power, sample_inv_p): the
-// draw u_l names an entry through the cumulative table that travels with the list (NeeArgsPower: LightTableView), and the
-// sample's weight takes the inverse of the pick's probability where it takes L.  Everything else is 3 / 4, and those two are the
-// instantiations before it, statement for statement.  The list has entries wherever 5 or 6 is launched.
-constexpr bool spec_sphere(int spec) { return spec == 4 || spec == 6; }  // the instantiations that sample the sphere light
-constexpr bool spec_power(int spec) { return spec >= 5; }                // ... that pick by weight
+// with which a segment that meets the light ends with colour 0.  Without the weighted pick the triangle sample is taken only where
+// the list has entries (wave-uniform): with the sphere flag alone these instantiations run without a list and without a material
+// table.  A compile-time switch because a run-time one cost the kernels that sample triangles only 3.5 % of a frame with the switch
+// off (profiles/r23_nee_sphere_measure.txt).
+// spec_power(SPEC): the weighted pick of RTPT_FLAG_EXT_NEE_POWER (light_sample.hpp: pick_power): the draw u_l names an entry through
+// the cumulative table that travels with the list (spec_lights_t<SPEC> is then LightTableView), and the sample's weight takes the
+// inverse of the pick's probability where the uniform pick's takes L.  The list has entries wherever these are launched.
 struct NeeState {
   f3 wd;          // the shadow ray's direction, from the path's new origin
   f3 c;           // (T * Ke) * g
   uint32_t id1;   // the sampled triangle, id + 1
   bool valid;     // this segment took a sample whose shadow query is to be sent
   bool sampled;   // the path's sampled bit
-  f3 sphere_c;        // SPEC == 4: (T * light_col) * g of the sphere sample
+  f3 sphere_c;        // spec_sphere(SPEC): (T * light_col) * g of the sphere sample
   bool sphere_valid;  // ... this segment took a sphere sample that adds sphere_c to R
   bool sphere;        // ... the path's sphere bit
 };
-// what the SPEC >= 3 instantiations take behind alb_px, and what every other one takes there: nothing.  (As two more parameters
-// with defaults, a list and a pointer nobody read, the untextured queue kernels came out with their registers renamed.)
+// what the instantiations that sample lights take behind alb_px (LV: their spec_lights_t<SPEC>), and what every other one takes
+// there: nothing.  (As two more parameters with defaults, a list and a pointer nobody read, the untextured queue kernels came out
+// with their registers renamed.)
+template <class LV>
 struct NeeArgs {
-  LightView lights;
-  NeeState* st;
-};
-struct NeeArgsPower {  // SPEC == 5 / 6
-  LightTableView lights;
+  LV lights;
   NeeState* st;
 };
 struct NoNee {};
@@ -150,8 +147,8 @@ template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE 
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr,
                                               [[maybe_unused]] NEE nee_args = NEE{}) {
-  static_assert(std::is_same<NEE, NeeArgs>::value == (SPEC == 3 || SPEC == 4), "the instantiations that sample lights, and only they, take NeeArgs");
-  static_assert(std::is_same<NEE, NeeArgsPower>::value == spec_power(SPEC), "... and those that pick by weight NeeArgsPower");
+  static_assert(std::is_same<NEE, std::conditional_t<spec_lights(SPEC), NeeArgs<spec_lights_t<SPEC>>, NoNee>>::value,
+                "the instantiations that sample lights, and only they, take NeeArgs, with the list their SPEC asks for");
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
     if constexpr (spec_sphere(SPEC)) {
@@ -167,7 +164,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
   float4 s0 = s[0], s1 = s[1], s2 = s[2];
-  const bool last = (RTPT_TRACE_ITEMS & 1) && (SPEC || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
+  const bool last = (RTPT_TRACE_ITEMS & 1) && (spec_material(SPEC) != 0 || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
   float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
   f3 pos{0.f, 0.f, 0.f};
   if (!last) {
@@ -176,7 +173,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   f3 n{s0.w, s1.w, s2.w};                                          // :150 (precomputed per triangle)
   [[maybe_unused]] float spec_w = 0.0f;  // SPEC: the record's spare word, 0 = diffuse (specular.hpp), > 0 = the ior (dielectric.hpp)
-  [[maybe_unused]] float diel_inv = 0.0f, diel_r0 = 0.0f;  // SPEC == 2: 1 / ior and R0 of a dielectric's record
+  [[maybe_unused]] float diel_inv = 0.0f, diel_r0 = 0.0f;  // spec_material(SPEC) == 2: 1 / ior and R0 of a dielectric's record
   f3 alb = (n.x > 0.99f) ? f3{1.f, 0.f, 0.f} : ((-n.x > 0.99f) ? f3{0.f, 1.f, 0.f} : f3{0.7f, 0.7f, 0.7f});  // :155-163
   if (a.scene.materials) {
     // SURVEY 8(f) rank 4, not reference behaviour: a material library replaces the normal-keyed colours; a surface
@@ -185,15 +182,15 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const float4 m0 = m[0], m1 = m[1];
     if (m1.w != 0.0f) {
       acc = acc * f3{m1.x, m1.y, m1.z};
-      if constexpr (SPEC >= 3) {
+      if constexpr (spec_lights(SPEC)) {
         if (nee_args.st->sampled) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the lights: this one's emission is counted there
       }
       if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       return true;
     }
     alb = f3{m0.x, m0.y, m0.z};
-    if constexpr (SPEC != 0) spec_w = m0.w;
-    if constexpr (SPEC >= 2) {
+    if constexpr (spec_material(SPEC) != 0) spec_w = m0.w;
+    if constexpr (spec_material(SPEC) == 2) {
       diel_inv = m1.x;
       diel_r0 = m1.y;
     }
@@ -227,9 +224,9 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     }
     return true;
   }
-  if constexpr (SPEC >= 2) {
+  if constexpr (spec_material(SPEC) == 2) {
     if (diel::is_dielectric(spec_w)) {
-      if constexpr (SPEC >= 3) nee_args.st->sampled = false;
+      if constexpr (spec_lights(SPEC)) nee_args.st->sampled = false;
       if constexpr (spec_sphere(SPEC)) nee_args.st->sphere = false;
       const bool entering = exact::dot(n, d) < 0.0f;
       if (!entering) n = -n;
@@ -245,36 +242,33 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
-  if constexpr (SPEC >= 3) {
+  if constexpr (spec_lights(SPEC)) {
     // next-event estimation (light_sample.hpp): o is the sample's x, n its nf, acc its T
-    const auto lights = nee_args.lights;  // LightView, or LightTableView where SPEC picks by weight
+    const spec_lights_t<SPEC> lights = nee_args.lights;
     NeeState* const nee = nee_args.st;
     const bool diffuse = !spec::is_specular(spec_w);
     if (diffuse && seg + 1 < a.max_segments) {
-      if constexpr (spec_power(SPEC)) {  // the weighted pick; the list has entries
+      // the list has entries, except where the sphere light is sampled without the weighted pick: there it may be empty (wave-uniform)
+      constexpr bool kMayBeEmpty = spec_sphere(SPEC) && !spec_power(SPEC);
+      if (!kMayBeEmpty || lights.n > 0) {
         const float u_l = exact::rng_next(rng);
         const float u_a = exact::rng_next(rng);
         const float u_b = exact::rng_next(rng);
-        const light::Pick pk = light::pick_power(u_l, lights.cdf, lights.n);
-        const uint32_t id1 = lights.ids[pk.i];
+        uint32_t entry;
+        float inv_p;  // of the pick's probability
+        if constexpr (spec_power(SPEC)) {
+          const light::Pick pk = light::pick_power(u_l, lights.cdf, lights.n);
+          entry = pk.i;
+          inv_p = pk.inv_p;
+        } else {
+          entry = light::pick(u_l, lights.n);
+          inv_p = static_cast<float>(lights.n);
+        }
+        const uint32_t id1 = lights.ids[entry];
         const float4* ls = a.scene.shade + 3 * static_cast<size_t>(id1 - 1);
         const float4 l0 = ls[0], l1 = ls[1], l2 = ls[2];
         const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
-        const light::Sample sm = light::sample_inv_p(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, pk.inv_p);
-        nee->wd = sm.wd;
-        nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
-        nee->id1 = id1;
-        nee->valid = sm.valid;
-        nee->sampled = true;
-      } else if (SPEC == 3 || lights.n > 0) {  // (SPEC == 3: the list has entries; 4: it may be empty — wave-uniform)
-        const float u_l = exact::rng_next(rng);
-        const float u_a = exact::rng_next(rng);
-        const float u_b = exact::rng_next(rng);
-        const uint32_t id1 = lights.ids[light::pick(u_l, lights.n)];
-        const float4* ls = a.scene.shade + 3 * static_cast<size_t>(id1 - 1);
-        const float4 l0 = ls[0], l1 = ls[1], l2 = ls[2];
-        const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
-        const light::Sample sm = light::sample(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, lights.n);
+        const light::Sample sm = light::sample(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, inv_p);
         nee->wd = sm.wd;
         nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
         nee->id1 = id1;
@@ -299,7 +293,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   exact::sincos2pi(exact::rng_next(rng), st_, ct);                 // :256
   float u = fmaf_(2.0f, exact::rng_next(rng), -1.0f);              // :257
   float r = exact::sqrt_(fmaf_(-u, u, 1.0f));                      // :258
-  if constexpr (SPEC != 0) {
+  if constexpr (spec_material(SPEC) != 0) {
     if (spec::is_specular(spec_w)) {
       bool absorbed;
       d = spec::lobe(n, d, r, ct, st_, u, spec::roughness(spec_w), &absorbed);
@@ -312,17 +306,14 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   return seg + 1 >= a.max_segments;  // budget exhausted: the path returns its throughput (:270)
 }
 
-// shade_segment's TEX for with_mode3 (select.hpp): 2 the scene has textures and some of them a mip chain (the level table
+// shade_segment's TEX for with_mode<3> (select.hpp): 2 the scene has textures and some of them a mip chain (the level table
 // exists), 1 textures without mips, 0 no textures
 inline int tex_mode(const TexView& tex) { return tex.records ? (tex.levels ? 2 : 1) : 0; }
-// shade_segment's SPEC: 6 / 5 are 4 / 3 with the weighted pick (kSpecNeeSpherePower, kSpecNeePower: RTPT_FLAG_EXT_NEE_POWER on a
-// scene whose light list has entries), 4 the launch samples the analytic sphere light, and the triangles of the light list where it has entries
-// (kSpecNeeSphere: RTPT_FLAG_EXT_NEE_SPHERE), 3 the launch samples lights (kSpecNee: RTPT_FLAG_EXT_NEE and a light list with entries, whatever the
-// materials), 2 some triangle's material is a dielectric, 1 some triangle's is specular and none a dielectric, 0 every material is
-// diffuse
+// shade_segment's SPEC of a launch's `specular` (kernels.hpp: the SPEC axis): the value itself where it lies on the axis, else 0;
+// an unnamed value above kSpecNeeSphere samples the sphere light
 inline int spec_mode(int specular) {
-  if (specular == kSpecNeePower || specular == kSpecNeeSpherePower) return specular;
-  return specular >= kSpecNeeSphere ? 4 : specular == kSpecNee ? 3 :(specular == 2 ? 2 : (specular == 1 ? 1 : 0));
+  if (specular < 0) return 0;
+  return specular < kSpecModes ? specular : kSpecNeeSphere;
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two copies of csrc/, kernel by kernel.
 
-    scripts/device_asm_diff.py <parent csrc> <new csrc> [--by-kernel] [-o summary.txt] [-j jobs] [-D macro ...]
+    scripts/device_asm_diff.py <parent csrc> <new csrc> [--by-kernel] [--pair-renamed] [-o summary.txt] [-j jobs] [-D macro ...]
 
 For a refactor that must not change what the GPU executes.  Every .hip file of the new directory is compiled in both
 directories with the Makefile's own HIPCC / CXXFLAGS plus `--cuda-device-only -S` (no GPU needed), and the two assembly
@@ -19,6 +19,13 @@ compared by name, with the same normalisations.  A name that two files of one si
 one of them): it is compared as `name [file]`, file by file as without the option, and counted in the side's line — a library's
 template kernels that two files instantiate (rocprim's, in the two tree builders).  Such a kernel that also moved between files
 therefore shows as "only in".  Prints one line per side (files, kernels) and one for the comparison.
+
+--pair-renamed: for a refactor that changes a kernel's signature or template parameters, and with them its mangled name.  Only
+names found on ONE side are treated: in such an entry's text its own symbol (the .kd symbol carries it too) is replaced by a
+placeholder, and a parent-only name pairs with a new-only name when the two placeholder texts are equal and the qualified function
+name agrees — the length-prefixed components of the mangled name in front of its template arguments; no demangler is needed.
+Names pair as a multiset, a pair counts as compared once and as equal, and the comparison's line gains `renamed N, paired N`.
+Whatever finds no partner is reported as "only in", as without the option.
 """
 import argparse
 import concurrent.futures
@@ -102,13 +109,49 @@ def metadata(asm):
     return out
 
 
-def compare(what, old, new, report):
-    """number of names whose text is equal; differences go to report"""
-    for n in sorted(set(old) - set(new)):
+def qualified_name(symbol):
+    """_ZN2rt12_GLOBAL__N_111k_pathtraceILi1E... -> ("rt", "_GLOBAL__N_1", "k_pathtrace"); a name that is not mangled is itself"""
+    m = re.match(r"_ZN?(?=\d)", symbol)
+    if not m:
+        return (symbol,)
+    rest, parts = symbol[m.end():], []
+    while m := re.match(r"\d+", rest):
+        end = m.end() + int(m.group())
+        parts.append(rest[m.end():end])
+        rest = rest[end:]
+    return tuple(parts)
+
+
+def pair_renamed(old, new):
+    """--pair-renamed: (parent-only names, new-only names, how many of each found a partner), the partners taken out of both lists"""
+    def by_text(d, names):
+        out = {}
+        for n in names:
+            symbol = n.split(" [")[0]
+            out.setdefault((qualified_name(symbol), d[n].replace(symbol, "@renamed")), []).append(n)
+        return out
+
+    only_old, only_new = by_text(old, sorted(set(old) - set(new))), by_text(new, sorted(set(new) - set(old)))
+    paired = 0
+    for k in only_old.keys() & only_new.keys():
+        c = min(len(only_old[k]), len(only_new[k]))
+        paired += c
+        del only_old[k][:c], only_new[k][:c]
+    return sorted(sum(only_old.values(), [])), sorted(sum(only_new.values(), [])), paired
+
+
+def compare(what, old, new, report, pair=False):
+    """"<names compared>, equal <names whose text is equal>" for the summary line; differences go to report"""
+    only_old, only_new, paired, note = sorted(set(old) - set(new)), sorted(set(new) - set(old)), 0, ""
+    if pair:
+        renamed = len(only_old)
+        only_old, only_new, paired = pair_renamed(old, new)
+        note = f", renamed {renamed}, paired {paired}"
+    equal = paired
+    for n in only_old:
         report.append(f"  {what} only in the parent: {n}")
-    for n in sorted(set(new) - set(old)):
+    for n in only_new:
         report.append(f"  {what} only in the new code: {n}")
-    equal = 0
     for n in sorted(set(old) & set(new)):
         if old[n] == new[n]:
             equal += 1
@@ -116,7 +159,7 @@ def compare(what, old, new, report):
         d = list(difflib.unified_diff(old[n].splitlines(), new[n].splitlines(), "parent", "new", lineterm="", n=1))
         report.append(f"  {what} differs: {n} ({sum(l[0] in '+-' for l in d) - 2} changed lines)")
         report.extend("    " + l for l in d[:12])
-    return equal
+    return f"{len(set(old) | set(new)) - paired}, equal {equal}{note}"
 
 
 def pooled(asms):
@@ -147,12 +190,12 @@ def by_kernel(a):
     (ko, po, mo, to), (kn, pn, mn, tn) = (pooled(asms[side]) for side in ("parent", "new"))
     for side, k, twice in (("parent", ko, to), ("new", kn, tn)):
         summary.append(f"{side}: {len(asms[side])} files, {len(k)} kernels" + (f" ({twice} names in two files, compared per file)" if twice else ""))
-    k_eq = compare("kernel", ko, kn, report)
+    k_eq = compare("kernel", ko, kn, report, a.pair_renamed)
     p_eq = compare("device function", po, pn, report)
-    m_eq = compare("metadata entry", mo, mn, report)
-    line = f"by kernel: kernels compared {len(set(ko) | set(kn))}, equal {k_eq}; metadata entries {len(set(mo) | set(mn))}, equal {m_eq}"
+    m_eq = compare("metadata entry", mo, mn, report, a.pair_renamed)
+    line = f"by kernel: kernels compared {k_eq}; metadata entries {m_eq}"
     if po or pn:
-        line += f"; other device functions {len(set(po) | set(pn))}, equal {p_eq}"
+        line += f"; other device functions {p_eq}"
     summary.append(line)
     if report:
         print("\n".join(report))
@@ -167,6 +210,7 @@ def main():
     ap.add_argument("-j", "--jobs", type=int, default=4)
     ap.add_argument("-D", dest="defines", action="append", default=[], help="macro for both sides (e.g. RTPT_AB_VARIANTS=1)")
     ap.add_argument("--by-kernel", action="store_true", help="pool the kernels of each side over its files and compare by kernel name")
+    ap.add_argument("--pair-renamed", action="store_true", help="pair kernels found on one side only by their text and qualified function name")
     a = ap.parse_args()
     if a.by_kernel:
         summary, ok = by_kernel(a)
@@ -194,12 +238,12 @@ def main():
             ko, kn = ({n: t for n, (t, k) in d.items() if k} for d in (fo, fn))
             po, pn = ({n: t for n, (t, k) in d.items() if not k} for d in (fo, fn))
             mo, mn = metadata(old), metadata(new)
-            k_eq = compare("kernel", ko, kn, report)
+            k_eq = compare("kernel", ko, kn, report, a.pair_renamed)
             p_eq = compare("device function", po, pn, report)
-            m_eq = compare("metadata entry", mo, mn, report)
-            line = f"{f}: kernels compared {len(set(ko) | set(kn))}, equal {k_eq}; metadata entries {len(set(mo) | set(mn))}, equal {m_eq}"
+            m_eq = compare("metadata entry", mo, mn, report, a.pair_renamed)
+            line = f"{f}: kernels compared {k_eq}; metadata entries {m_eq}"
             if po or pn:
-                line += f"; other device functions {len(set(po) | set(pn))}, equal {p_eq}"
+                line += f"; other device functions {p_eq}"
             summary.append(line)
             if report:
                 ok = False
