@@ -273,6 +273,40 @@ typedef struct rtpt_visibility_data {
                                       Such a launch has the limits of a RTPT_FLAG_EXT_NEE launch.
                                       Additive: the ABI version stays 5 */
 
+#define RTPT_FLAG_EXT_NEE_MIS 0x80000u /* next-event estimation WEIGHS its light sample against the bounce that meets the same emitter
+                                      (multiple importance sampling with the POWER HEURISTIC, beta = 2; NOT reference behaviour,
+                                      default off; DESIGN.md 8, csrc/light_sample.hpp states the rules and the arithmetic).  It works
+                                      together with RTPT_FLAG_EXT_NEE on a scene whose light list has L > 0 entries, with the uniform
+                                      or the weighted pick, and combines with RTPT_FLAG_EXT_NEE_SPHERE; alone, with only the sphere
+                                      flag, or on an empty list it is ignored (as the POWER bit is without the NEE bit), and in every
+                                      ignored case and without it every frame, ray count, kernel and allocation is that of a context
+                                      without it, bit for bit.  Everything not named here is as RTPT_FLAG_EXT_NEE / _POWER state it:
+                                      the place of the sample, the three draws and their order, the sampled bit, the shadow query and
+                                      its tie rule, R, the order of the sphere's and the triangle's additions, demodulation.  THE
+                                      SPHERE SAMPLE AND THE SPHERE BIT ARE UNCHANGED: the cone sample of a sphere is already close to
+                                      the bounce's own density, and its weighing is left for later.
+                                      With g2 = g * g: the light side weighs m(g) = 1 / (1 + g2), the bounce side wb(g) = g2 / (1 +
+                                      g2) where g2 < +inf and 1 elsewhere (a NaN takes 1); g is the ratio of the bounce's density
+                                      cos(x) / pi to the light sample's density in solid angle, so these are p_l^2 / (p_l^2 + p_b^2)
+                                      and p_b^2 / (p_l^2 + p_b^2).
+                                      1. The light sample's g becomes gm = g * m(g), one multiply behind the division; the gain is
+                                      ((T.c * Ke.c) * gm) per channel; gm <= 0.5.  Validity, the query and the ray count are unchanged.
+                                      2. A diffuse hit that is not the path's last segment and took the triangle draw records cb =
+                                      dot(nf, d') of its normalised diffuse direction d'.  cb travels with the path like the sampled
+                                      bit and is read only while that bit is set.
+                                      3. An emissive triangle met with the sampled bit set ends the path with (T * Ke) * wb(g_hit) —
+                                      the multiply by Ke as before, then one multiply by wb per channel — no longer with 0; with the
+                                      bit clear with T * Ke as before.  g_hit = ((cb * cl) * (a2 * inv_p)) / (2 pi * r2) at the point
+                                      the ray hit: y from the hit's barycentrics on its shade record, r2 = |y - o|^2, cl = |dot(nl,
+                                      d)| with the ray's own d, a2 as the sample computes it; inv_p = float(L) for the uniform pick,
+                                      for the weighted pick float(S) / float(q_i) of the hit triangle's entry i, found by binary
+                                      search in the ascending list (every index read in [0, L)).  Where q_i == 0 (the pick never
+                                      reaches that emitter) or the id is not in the list (which no frame can produce) wb = 1.
+                                      Known limits, inherited: an entry the weighted pick's 24-bit draw can skip (q_i * 2^24 < S)
+                                      still loses that share; such a launch has the limits of a RTPT_FLAG_EXT_NEE launch (every
+                                      segment in the tile kernel, no queues, no deferred final filter pass).
+                                      Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -829,6 +863,16 @@ int rtpt_selftest_light_table(rtpt_ctx* ctx, const float* w, size_t n, uint64_t*
 /* The weighted pick (csrc/light_sample.hpp: pick_power) of k draws u_l on the table cdf[0, n), 1 <= n <= 2^24: index_out[j] the
  * entry, inv_p_out[j] = float(S) / float(q).  Operands are not checked beyond n; every index the search reads lies in [0, n). */
 int rtpt_selftest_light_pick(rtpt_ctx* ctx, const uint64_t* cdf, size_t n, const float* u_l, size_t k, uint32_t* index_out, float* inv_p_out);
+/* The weights of RTPT_FLAG_EXT_NEE_MIS (csrc/light_sample.hpp: hit_weight, mis_bounce, mis_light), one case per thread, by the
+ * functions the tracing kernels call: in = n x 20 words (v0[3], v1[3], v2[3] of the hit emitter, o[3] and d[3] of the ray that hit
+ * it, the hit's b1, b2, cb, inv_p as floats; word 19 is not read), out = n x 3 floats (g_hit, wb(g_hit), g_hit * m(g_hit)).  The
+ * emitter's unit normal is computed as for its shade record, b0 = 1 - b1 - b2.  Operands are not checked.  Additive:
+ * RTPT_ABI_VERSION stays 5. */
+int rtpt_selftest_mis_weight(rtpt_ctx* ctx, const float* in, float* out, size_t n);
+/* The search of RTPT_FLAG_EXT_NEE_MIS (csrc/light_list_host.hpp: find) of k queries on the ascending list ids[0, n), n <= 2^24:
+ * index_out[j] = the index of queries[j] in the list, n for an id that is not in it.  ids is not checked beyond n; every index the
+ * search reads lies in [0, n). */
+int rtpt_selftest_light_find(rtpt_ctx* ctx, const uint32_t* ids, size_t n, const uint32_t* queries, size_t k, uint32_t* index_out);
 /* The light list of RTPT_FLAG_EXT_NEE as it stands on the device: *n = its entries (0 without the flag, without materials or
  * without an emitter), of which the first min(*n, cap) are copied to ids — id + 1 of every posed triangle inst * n_tris + t whose
  * material has Ke != 0, ascending.  ids may be NULL when cap is 0 (count only). */

@@ -33,6 +33,7 @@ FLAG_DEVICE_FLATTEN = 0x4000  # with FLAG_DEVICE_BVH_BUILD: mesh x transforms ->
 FLAG_EXT_NEE = 0x10000  # next-event estimation: rtpt_raytrace samples the scene's emissive triangles (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 FLAG_EXT_NEE_SPHERE = 0x20000  # next-event estimation of the analytic sphere light: every diffuse hit samples its cone, no shadow ray (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 FLAG_EXT_NEE_POWER = 0x40000  # with FLAG_EXT_NEE: the emissive triangle is picked by area x emission from a cumulative table built on the device (csrc/light_table.hip); ignored alone; not in FLAG_EXT_MASK
+FLAG_EXT_NEE_MIS = 0x80000  # with FLAG_EXT_NEE: the light sample and the bounce that meets the same emitter are weighed by the power heuristic (csrc/light_sample.hpp); the sphere sample is not; ignored alone; not in FLAG_EXT_MASK
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -153,6 +154,7 @@ SYMBOLS = [
     "rtpt_util_load_obj_materials_ni", "rtpt_selftest_refract", "rtpt_debug_empty_run_info",
     "rtpt_selftest_light_sample", "rtpt_debug_light_list", "rtpt_selftest_sphere_sample",
     "rtpt_selftest_light_table", "rtpt_selftest_light_pick", "rtpt_debug_light_table",
+    "rtpt_selftest_mis_weight", "rtpt_selftest_light_find",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -246,6 +248,8 @@ def load() -> C.CDLL:
         "rtpt_selftest_light_pick": [vp, vp, sz, vp, sz, vp, vp],
         "rtpt_debug_light_table": [vp, vp, u32, C.POINTER(u32)],
         "rtpt_selftest_sphere_sample": [vp, vp, vp, sz],
+        "rtpt_selftest_mis_weight": [vp, vp, vp, sz],
+        "rtpt_selftest_light_find": [vp, vp, sz, vp, sz, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -704,6 +708,23 @@ class Context:
         inv_p = np.zeros(len(u_l), np.float32)
         _check(self._lib.rtpt_selftest_light_pick(self._h, _ptr(cdf), len(cdf), _ptr(u_l), len(u_l), _ptr(idx), _ptr(inv_p)))
         return idx, inv_p
+
+    def selftest_mis_weight(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 3] float32 (g_hit, wb(g_hit), g_hit * m(g_hit)) of the device's weights of FLAG_EXT_NEE_MIS on cases [n, 20] floats =
+        v0, v1, v2 of the hit emitter, o, d, b1, b2, cb, inv_p, one word that is not read (rtpt_selftest_mis_weight)"""
+        cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 20)
+        out = np.zeros((len(cases), 3), np.float32)
+        _check(self._lib.rtpt_selftest_mis_weight(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def selftest_light_find(self, ids: np.ndarray, queries: np.ndarray) -> np.ndarray:
+        """uint32 [k]: the index of every query in the ascending list ids [n] uint32, n for an id that is not in it
+        (rtpt_selftest_light_find: the search of FLAG_EXT_NEE_MIS)"""
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        queries = np.ascontiguousarray(queries, np.uint32).ravel()
+        out = np.zeros(len(queries), np.uint32)
+        _check(self._lib.rtpt_selftest_light_find(self._h, _ptr(ids) if len(ids) else None, len(ids), _ptr(queries), len(queries), _ptr(out)))
+        return out
 
     def selftest_sphere_sample(self, cases: np.ndarray) -> np.ndarray:
         """[n, 6] uint32 words (wd, g, taken, valid as floats; wd and g 0 where not taken) of the device's sphere sample on cases

@@ -756,7 +756,7 @@ class PathTracingApplication:
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
-             specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, **app_kw):
+             specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, nee_mis=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -777,11 +777,16 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     `flags=abi.FLAG_EXT_NEE_SPHERE` by another name, needs no material table and may be combined with `nee`.
     `nee_power` (off by default): `nee` with the emissive triangle picked by area times emission instead of uniformly,
     abi.FLAG_EXT_NEE | abi.FLAG_EXT_NEE_POWER on every context of this rank (it implies `nee`); the cumulative table is built on
-    the device and follows moved instances and a changed model."""
-    if nee or nee_power:
+    the device and follows moved instances and a changed model.
+    `nee_mis` (off by default): `nee` with the light sample and the bounce that meets the same emitter weighed against each other
+    by the power heuristic, abi.FLAG_EXT_NEE | abi.FLAG_EXT_NEE_MIS on every context of this rank (it implies `nee`); it combines
+    with `nee_power` and `nee_sphere`, whose sphere sample it leaves unweighed."""
+    if nee or nee_power or nee_mis:
         flags |= abi.FLAG_EXT_NEE
     if nee_power:
         flags |= abi.FLAG_EXT_NEE_POWER
+    if nee_mis:
+        flags |= abi.FLAG_EXT_NEE_MIS
     if nee_sphere:
         flags |= abi.FLAG_EXT_NEE_SPHERE
     plan = StripPlan(height, world, rank, iterations, mode, flags & abi.FLAG_EXT_MASK, tuple(splits) if world > 1 else ())

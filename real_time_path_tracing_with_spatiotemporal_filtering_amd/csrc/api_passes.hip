@@ -149,11 +149,17 @@ void gradient_inputs(const rtpt_push_constants* pc, float* cam, float* light, fl
 // RTPT_FLAG_EXT_NEE_POWER on top of a launch that samples the triangles of a list (both bits, entries, and the cumulative table
 // that join_materials built beside the list): rt::kSpecNeePower / rt::kSpecNeeSpherePower, the kernels that pick by weight.
 // Alone, with only RTPT_FLAG_EXT_NEE_SPHERE, or with an empty list the bit changes nothing
+// RTPT_FLAG_EXT_NEE_MIS on top of a launch that samples the triangles of a list (the NEE bit, the MIS bit and entries): the MIS
+// form of whichever of the four values the other bits choose.  Alone, with only RTPT_FLAG_EXT_NEE_SPHERE, or with an empty list
+// the bit changes nothing: 0xA0000 on an empty list launches rt::kSpecNeeSphere
 int trace_material_mode(const rtpt_ctx* c) {
   const bool nee = (c->cfg.flags & RTPT_FLAG_EXT_NEE) && c->scene.n_lights > 0 && c->scene.lights.ptr && c->scene.materials.ptr;
   const bool power = nee && (c->cfg.flags & RTPT_FLAG_EXT_NEE_POWER) && c->scene.light_table.cdf.ptr;
-  if (c->cfg.flags & RTPT_FLAG_EXT_NEE_SPHERE) return power ? rt::kSpecNeeSpherePower : rt::kSpecNeeSphere;
-  return nee ? (power ? rt::kSpecNeePower : rt::kSpecNee) : c->scene.materials_specular;
+  const bool mis = nee && (c->cfg.flags & RTPT_FLAG_EXT_NEE_MIS);
+  if (c->cfg.flags & RTPT_FLAG_EXT_NEE_SPHERE)
+    return power ? (mis ? rt::kSpecNeeSpherePowerMis : rt::kSpecNeeSpherePower) : (mis ? rt::kSpecNeeSphereMis : rt::kSpecNeeSphere);
+  if (!nee) return c->scene.materials_specular;
+  return power ? (mis ? rt::kSpecNeePowerMis : rt::kSpecNeePower) : (mis ? rt::kSpecNeeMis : rt::kSpecNee);
 }
 
 // K2 of scenes whose BVH is built over fan pairs as the path-pool kernel (rtpt_ctx::trace_pool): the workgroups' slabs

@@ -176,6 +176,47 @@ int rtpt_selftest_sphere_sample(rtpt_ctx* c, const uint32_t* in, uint32_t* out, 
   return RTPT_OK;
 }
 
+int rtpt_selftest_mis_weight(rtpt_ctx* c, const float* in, float* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * 20 * sizeof(float), out_bytes = n * 3 * sizeof(float);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_mis_weight(static_cast<const float*>(din.ptr), static_cast<float*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_mis_weight: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
+int rtpt_selftest_light_find(rtpt_ctx* c, const uint32_t* ids, size_t n, const uint32_t* queries, size_t k, uint32_t* index_out) {
+  if (!c || !queries || !index_out || (n && !ids)) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n > (static_cast<size_t>(1) << 24)) return fail(RTPT_E_INVALID, "a light list has at most 2^24 entries");
+  if (k == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  Buf dids, dq, di;
+  int rc;
+  if ((n && (rc = alloc_buf(dids, n * sizeof(uint32_t)))) || (rc = alloc_buf(dq, k * sizeof(uint32_t))) || (rc = alloc_buf(di, k * sizeof(uint32_t))))
+    return rc;
+  hipError_t e = n ? hipMemcpyAsync(dids.ptr, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) : hipSuccess;
+  if (e == hipSuccess) e = hipMemcpyAsync(dq.ptr, queries, k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_light_find(static_cast<const uint32_t*>(dids.ptr), static_cast<uint32_t>(n), static_cast<const uint32_t*>(dq.ptr), k,
+                                   static_cast<uint32_t*>(di.ptr), c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(index_out, di.ptr, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_light_find: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_light_table(rtpt_ctx* c, const float* w, size_t n, uint64_t* cdf_out) {
   if (!c || !w || !cdf_out) return fail(RTPT_E_INVALID, "NULL argument");
   if (n == 0) return RTPT_OK;

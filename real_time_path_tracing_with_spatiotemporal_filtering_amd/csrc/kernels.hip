@@ -404,7 +404,7 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   const bool nee = spec_lights(spec);  // the launch samples lights: every segment runs in the tile kernels
   // (api_passes.hip: trace_material_mode) the triangles of a list are sampled from a list with entries, on a scene with materials:
   // where the sphere light is sampled without the weighted pick the list may be empty, everywhere else it is not
-  const bool may_be_empty = spec_sphere(spec) && !spec_power(spec);
+  const bool may_be_empty = spec_may_be_empty(spec);  // (never a launch that weighs its samples: spec_mis)
   if (nee && !may_be_empty && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
   if (nee && may_be_empty && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
   if (spec_power(spec) && !lights.cdf) std::abort();  // the weighted pick reads the list's table
@@ -423,6 +423,7 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   b.multi_off = static_cast<uint32_t>(dyn / 4);
   const size_t dyn_queue = dyn;
   if (nee) dyn += 3 * kPtThreads * 4;        // rad_r, rad_g, rad_b (pathtrace_tile), in front of the sums
+  if (spec_mis(spec)) dyn += kPtThreads * 4;  // cb_pix behind them, for the instantiations of RTPT_FLAG_EXT_NEE_MIS only
   if (a.spp > 1) dyn += 4 * kPtThreads * 4;  // sum_r, sum_g, sum_b, rng_pix
   const uint32_t phase0 = a.first_window ? a.first_window : pt_first_window(a.scene.use_bvh != 0);
   const bool split = !nee && a.spp == 1 && a.compact && a.queue[0] && a.queue_count && a.max_segments > phase0 &&
@@ -460,7 +461,7 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       with_mode<3>(tex_mode(tex), [&](auto tmode) {  // rtpt_scene_set_textures: the instantiations that sample the atlas, with mips or without
         constexpr int T = decltype(tmode)::value;
         // rtpt_scene_set_materials_ext: the instantiations that bounce specular / dielectric materials; RTPT_FLAG_EXT_NEE,
-        // RTPT_FLAG_EXT_NEE_SPHERE, RTPT_FLAG_EXT_NEE_POWER: those that sample lights (kernels.hpp: the SPEC axis)
+        // RTPT_FLAG_EXT_NEE_SPHERE, RTPT_FLAG_EXT_NEE_POWER, RTPT_FLAG_EXT_NEE_MIS: those that sample lights (kernels.hpp: the SPEC axis)
         with_mode<kSpecModes>(spec, [&](auto smode) {
           constexpr int S = decltype(smode)::value;
           // l: the light argument S asks for, spec_lights_t<S>.  (The launch syntax, because a kernel template with a parameter pack

@@ -90,15 +90,31 @@ struct LightTableView {
 //   kSpecNeePower        RTPT_FLAG_EXT_NEE and RTPT_FLAG_EXT_NEE_POWER on a list with entries: kSpecNee with the weighted pick
 //   kSpecNeeSpherePower  ... and RTPT_FLAG_EXT_NEE_SPHERE besides: kSpecNeeSphere with it (with an empty list 0x60000 launches
 //                        kSpecNeeSphere)
+//   kSpecNeeMis, kSpecNeeSphereMis, kSpecNeePowerMis, kSpecNeeSpherePowerMis
+//                        RTPT_FLAG_EXT_NEE_MIS on top of RTPT_FLAG_EXT_NEE on a list with entries: the four above with the light
+//                        sample and the bounce that meets an emitter weighed against each other (light_sample.hpp: MULTIPLE
+//                        IMPORTANCE SAMPLING).  Such an instantiation always has a list with entries: with the sphere flag on an
+//                        empty list 0xA0000 launches kSpecNeeSphere.  The sphere sample is not weighed.
 // Nothing outside this block compares a SPEC with a number: it asks the predicates.
 constexpr int kSpecNee = 3;
 constexpr int kSpecNeeSphere = 4;
 constexpr int kSpecNeePower = 5;
 constexpr int kSpecNeeSpherePower = 6;
-constexpr int kSpecModes = 7;  // SPEC lies in [0, kSpecModes)
+constexpr int kSpecNeeMis = 7;
+constexpr int kSpecNeeSphereMis = 8;
+constexpr int kSpecNeePowerMis = 9;
+constexpr int kSpecNeeSpherePowerMis = 10;
+constexpr int kSpecModes = 11;  // SPEC lies in [0, kSpecModes)
 constexpr bool spec_lights(int spec) { return spec >= kSpecNee; }                                        // samples lights
-constexpr bool spec_sphere(int spec) { return spec == kSpecNeeSphere || spec == kSpecNeeSpherePower; }   // ... the sphere light
-constexpr bool spec_power(int spec) { return spec == kSpecNeePower || spec == kSpecNeeSpherePower; }     // ... picks by weight
+constexpr bool spec_mis(int spec) { return spec >= kSpecNeeMis; }                                        // ... and weighs them (MIS)
+constexpr int spec_unweighed(int spec) { return spec_mis(spec) ? spec - (kSpecNeeMis - kSpecNee) : spec; }  // the value without MIS
+constexpr bool spec_sphere(int spec) {                                                                   // ... the sphere light
+  return spec_unweighed(spec) == kSpecNeeSphere || spec_unweighed(spec) == kSpecNeeSpherePower;
+}
+constexpr bool spec_power(int spec) {                                                                    // ... picks by weight
+  return spec_unweighed(spec) == kSpecNeePower || spec_unweighed(spec) == kSpecNeeSpherePower;
+}
+constexpr bool spec_may_be_empty(int spec) { return spec_sphere(spec) && !spec_power(spec) && !spec_mis(spec); }  // ... maybe from no list
 constexpr int spec_material(int spec) { return spec_lights(spec) ? 2 : spec; }                           // its material mode
 // what an instantiation takes behind TexView: nothing (void), the list, or the list with its table
 template <int SPEC>
@@ -484,6 +500,11 @@ void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t 
 void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 // light::sphere_sample on n cases of 12 words (x, nf, c, r2, u_c, u_p): out = n x (wd, g, taken, valid), 6 words
 void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
+// light::hit_weight, light::mis_bounce and light::mis_light (light_sample.hpp: RTPT_FLAG_EXT_NEE_MIS) on n cases of 20 words (v0, v1,
+// v2, o, d, b1, b2, cb, inv_p, one word not read): out = n x (g_hit, wb(g_hit), g_hit * m(g_hit))
+void launch_selftest_mis_weight(const float* in, float* out, size_t n, hipStream_t s);
+// rtpt_light::find (light_list_host.hpp) of k queries on the ascending list ids[0, n): index_out[j], n where the id is not in it
+void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out, hipStream_t s);
 
 // The cumulative table of RTPT_FLAG_EXT_NEE_POWER (light_table.hip; light_sample.hpp states the arithmetic): everything on stream
 // s, no synchronisation, no readback.  kLightTableBlock entries per workgroup; light_table_scratch_bytes(n) = what the builder

@@ -51,4 +51,26 @@ inline int build_light_list(const uint32_t* tri_material, const M* materials, ui
   return kListOk;
 }
 
+// THE SEARCH (RTPT_FLAG_EXT_NEE_MIS; light_sample.hpp: the bounce's weight at an emitter it hit): the index of id1 in the ascending
+// list ids[0, n), or n where the list does not hold it.  Stated once, here, for the device (the tracing kernels, through
+// light_sample.hpp, and rtpt_selftest_light_find) and for a plain C++ program under a sanitizer (csrc/tests/
+// light_find_host_check.cpp).  Every index read lies in [0, n) whatever ids and id1 hold: lo <= mid < hi <= n inside the loop, and
+// the read behind it is guarded by lo < n.  On a list that is not ascending the answer is some index whose entry is id1, or n.
+#if defined(__HIPCC__)
+#define RTPT_LIGHT_HD __host__ __device__
+#else
+#define RTPT_LIGHT_HD
+#endif
+RTPT_LIGHT_HD inline uint32_t find(const uint32_t* ids, uint32_t n, uint32_t id1) {
+  uint32_t lo = 0u, hi = n;  // the first entry >= id1 lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (ids[mid] < id1)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  return (lo < n && ids[lo] == id1) ? lo : n;
+}
+
 }  // namespace rtpt_light

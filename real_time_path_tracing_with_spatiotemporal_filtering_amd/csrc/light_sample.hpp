@@ -150,6 +150,69 @@ __device__ __forceinline__ Pick pick_power(float u_l, const uint64_t* C, uint32_
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// MULTIPLE IMPORTANCE SAMPLING (RTPT_FLAG_EXT_NEE_MIS together with RTPT_FLAG_EXT_NEE on a scene whose light list has L > 0 entries,
+// with the uniform or the weighted pick, with or without RTPT_FLAG_EXT_NEE_SPHERE; alone, with only the sphere flag, or on an empty
+// list the bit is ignored, and in every ignored case and without it every frame, ray count, kernel and allocation is that of a
+// context without it, bit for bit).  The light sample and the bounce that meets the same emitter are two estimators of one
+// integral; each is weighed by the POWER HEURISTIC (beta = 2).  Everything not named here is as the rules above state it: the place
+// of the sample, the three draws and their order, the sampled bit, the shadow query and its tie rule, R, the order of the sphere's
+// and the triangle's additions, demodulation.  THE SPHERE SAMPLE AND THE SPHERE BIT ARE UNCHANGED: the cone sample of a sphere is
+// already close to the bounce's own density; its weighing is left for later.  tests/nee_mis.py restates every step in numpy float32
+// and walks whole paths with it.
+//   With g2 = g * g:   light side   m(g)  = exact::div_(1.0f, 1.0f + g2)
+//                      bounce side  wb(g) = (g2 < +inf) ? exact::div_(g2, 1.0f + g2) : 1.0f        (a NaN fails the comparison)
+//   g is the ratio of the bounce's density cs / pi to the light sample's density in solid angle, so these are p_l^2 / (p_l^2 +
+//   p_b^2) and p_b^2 / (p_l^2 + p_b^2).
+//   1. THE LIGHT SAMPLE: sample()'s g becomes gm = g * m(g), one multiply behind the division; the gain is ((T.c * Ke.c) * gm) per
+//      channel.  gm <= 0.5 wherever it is a number (g = +inf gives inf * 0, a NaN, as g = NaN does).  Validity, the query and the
+//      ray count are unchanged.
+//   2. THE BOUNCE'S COSINE: a diffuse hit that is not the path's last segment and that took the triangle draw records cb =
+//      exact::dot(nf, d') behind the normalize of the diffuse direction d'.  cb travels with the path like the sampled bit, is read
+//      only while that bit is set, and nothing resets it: the primary ray starts with the bit clear.
+//   3. AN EMISSIVE TRIANGLE MET WITH THE SAMPLED BIT SET ends the path with (T * Ke) * wb(g_hit): the multiply by Ke as before,
+//      then one multiply by wb per channel — no longer 0.  With the bit clear: T * Ke, as before.  g_hit is the light sample's
+//      weight function at the point the ray hit (hit_weight below): y = bary_point of the hit's barycentrics on the hit triangle's
+//      shade record, as shade_segment forms a bounce's hit point; w = y - o; r2 = exact::dot(w, w); cl = |exact::dot(nl, d)| with
+//      the ray's own unit d and the record's normal; a2 as sample() computes it; g_hit = exact::div_((cb * cl) * (a2 * inv_p),
+//      k2Pi * r2).  inv_p is float(L) for the uniform pick; for the weighted pick it is the hit triangle's: i = the index of the
+//      hit's id1 in the ascending list (rtpt_light::find, light_list_host.hpp: a binary search, every index read in [0, L)),
+//      q_i = C_i - C_{i-1}, inv_p = exact::div_(float(S), float(q_i)) as pick_power forms it.  Where q_i == 0 the pick never
+//      reaches that emitter, so the hit before collected nothing for it: wb = 1; likewise for an id the list does not hold, which
+//      no frame can produce.
+// KNOWN LIMITS, inherited: an entry the weighted pick's 24-bit draw can skip (q_i * 2^24 < S) still loses that share; a launch
+// with the flag has a sampling launch's limits (every segment in the tile kernel, no queues, no deferred final pass).
+__device__ __forceinline__ float mis_light(float g) {
+  const float g2 = g * g;
+  return exact::div_(1.0f, 1.0f + g2);
+}
+__device__ __forceinline__ float mis_bounce(float g) {
+  const float g2 = g * g;
+  return (g2 < __builtin_inff()) ? exact::div_(g2, 1.0f + g2) : 1.0f;
+}
+// g_hit of rule 3.  v0, v1, v2, nl: the hit emitter's vertices and unit normal (its shade record); o, d: the ray that hit it;
+// b0, b1, b2: the hit's barycentrics (hit_barycentrics); cb: the cosine the bounce left with; inv_p: of the pick that would name
+// this emitter
+__device__ __forceinline__ float hit_weight(f3 v0, f3 v1, f3 v2, f3 nl, f3 o, f3 d, float b0, float b1, float b2, float cb, float inv_p) {
+  const f3 y = bary_point(v0, v1, v2, b0, b1, b2);
+  const f3 w = y - o;
+  const float r2 = exact::dot(w, w);
+  const float cl = __builtin_fabsf(exact::dot(nl, d));
+  const f3 c = exact::cross(v1 - v0, v2 - v0);
+  const float a2 = exact::sqrt_(exact::dot(c, c));
+  return exact::div_((cb * cl) * (a2 * inv_p), k2Pi * r2);
+}
+// inv_p of the weighted pick for the emitter id1 of the list ids[0, L) with the table C[0, L), L > 0; false where the pick never
+// names it (q_i == 0, or the list does not hold it): the bounce's weight is then 1
+__device__ __forceinline__ bool hit_inv_p_power(const uint32_t* ids, const uint64_t* C, uint32_t L, uint32_t id1, float* inv_p) {
+  const uint32_t i = rtpt_light::find(ids, L, id1);
+  if (i >= L) return false;
+  const uint64_t q = C[i] - (i ? C[i - 1u] : 0ull);
+  if (q == 0ull) return false;
+  *inv_p = exact::div_(static_cast<float>(C[L - 1u]), static_cast<float>(q));
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // THE SPHERE SAMPLE (RTPT_FLAG_EXT_NEE_SPHERE, independent of RTPT_FLAG_EXT_NEE and combinable with it; without the flag frames,
 // ray counts and the kernels chosen are those of a context without it, bit for bit): one direction inside the cone the analytic
 // sphere light (centre c = lightPos, squared radius r2 = PathtraceArgs::light_r2) subtends from x.  ray_hits_light tests the

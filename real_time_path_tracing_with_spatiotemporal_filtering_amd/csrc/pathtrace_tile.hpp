@@ -133,10 +133,15 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   // pixel `pix`, like the sums, because the compaction moves paths between threads; one path per pixel is live at a time, so a
   // plain read-modify-write has no race.  Zeroed at the start of every sample by the thread that starts on the pixel, read where
   // the path ends.
-  constexpr uint32_t kRadWords = spec_lights(SPEC) ? 3u * kPtThreads : 0u;
+  // spec_mis(SPEC): a fourth array behind R, the cosine the pixel's path left its last diffuse hit with (NeeState::cb), so that it
+  // follows the path through the compaction without a field in PathState, which every tracing kernel shares: written in front of
+  // the compaction's first barrier by the thread that holds the path, read behind its second by the thread that takes it over,
+  // and only while the sampled bit is set.  Without compaction the value stays in its register.  1 KB more per workgroup.
+  constexpr uint32_t kRadWords = spec_mis(SPEC) ? 4u * kPtThreads : (spec_lights(SPEC) ? 3u * kPtThreads : 0u);
   [[maybe_unused]] float* const rad_r = reinterpret_cast<float*>(stack + a.multi_off);
   [[maybe_unused]] float* const rad_g = rad_r + kPtThreads;
   [[maybe_unused]] float* const rad_b = rad_g + kPtThreads;
+  [[maybe_unused]] float* const cb_pix = rad_b + kPtThreads;  // spec_mis(SPEC)
   float* const sum_r = reinterpret_cast<float*>(stack + a.multi_off + kRadWords);
   float* const sum_g = sum_r + kPtThreads;
   float* const sum_b = sum_g + kPtThreads;
@@ -175,7 +180,7 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
   const uint32_t pix0 = tile_pixel(wave, lane);  // the pixel this thread starts on
   uint32_t pix = pix0, rng = 0;
   f3 o{0.f, 0.f, 0.f}, d{0.f, 0.f, -1.f}, acc{1.f, 1.f, 1.f};
-  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false, f3{0.f, 0.f, 0.f}, false, false};  // spec_lights(SPEC)
+  [[maybe_unused]] NeeState nee{f3{0.f, 0.f, 0.f}, f3{0.f, 0.f, 0.f}, 0u, false, false, f3{0.f, 0.f, 0.f}, false, false, 0.0f};  // spec_lights(SPEC)
   {
     const int x = tile_x0 + static_cast<int>(pix0 & 63u), y = tile_y0 + static_cast<int>(pix0 >> 6);
     rng = exact::rng_seed(static_cast<uint32_t>(x), static_cast<uint32_t>(y), a.frame, a.batch);  // :297
@@ -304,6 +309,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         uint32_t word = pix;  // pix has 8 bits: the path's sampled bit travels with it, and the sphere bit beside that
         if constexpr (spec_lights(SPEC)) word |= nee.sampled ? 0x100u : 0u;
         if constexpr (spec_sphere(SPEC)) word |= nee.sphere ? 0x200u : 0u;
+        if constexpr (spec_mis(SPEC)) {
+          if (nee.sampled) cb_pix[pix] = nee.cb;  // by pixel: one path per pixel is live
+        }
         st.pix[slot] = word;
         st.rng[slot] = rng;
         st.ox[slot] = o.x; st.oy[slot] = o.y; st.oz[slot] = o.z;
@@ -318,6 +326,9 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
           nee.sampled = (pix & 0x100u) != 0u;
           if constexpr (spec_sphere(SPEC)) nee.sphere = (pix & 0x200u) != 0u;
           pix &= 0xFFu;
+          if constexpr (spec_mis(SPEC)) {
+            if (nee.sampled) nee.cb = cb_pix[pix];
+          }
         }
         rng = st.rng[tid];
         o = f3{st.ox[tid], st.oy[tid], st.oz[tid]};

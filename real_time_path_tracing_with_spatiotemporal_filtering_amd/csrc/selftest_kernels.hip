@@ -247,6 +247,32 @@ __global__ void k_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size
   r[5] = f2u(s.valid ? 1.0f : 0.0f);
 }
 
+// light_sample.hpp's weights of RTPT_FLAG_EXT_NEE_MIS, one case per thread, by the functions the tracing kernels call: in = v0, v1, v2
+// of the hit emitter, o, d, the hit's b1, b2, cb, inv_p (19 floats of a 20-word case; word 19 is not read); out = g_hit,
+// wb(g_hit), g_hit * m(g_hit).  The emitter's normal as k_scene_prepare stores it; b0 as hit_barycentrics forms it
+// (rtpt_selftest_mis_weight)
+__global__ void k_selftest_mis_weight(const float* in, float* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = in + 20 * i;
+  const f3 v0 = ld3(w), v1 = ld3(w + 3), v2 = ld3(w + 6);
+  const f3 nl = exact::normalize(exact::cross(v1 - v0, v2 - v0));  // raytrace.comp.glsl:150
+  const float b1 = w[15], b2 = w[16];
+  const float b0 = 1.0f - b1 - b2;
+  const float g = light::hit_weight(v0, v1, v2, nl, ld3(w + 9), ld3(w + 12), b0, b1, b2, w[17], w[18]);
+  out[3 * i] = g;
+  out[3 * i + 1] = light::mis_bounce(g);
+  out[3 * i + 2] = g * light::mis_light(g);
+}
+
+// rtpt_light::find (light_list_host.hpp) of k queries on the ascending list ids[0, n): the entry's index, n where the list does not
+// hold the id (rtpt_selftest_light_find)
+__global__ void k_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  index_out[i] = rtpt_light::find(ids, n, queries[i]);
+}
+
 template <int BVH>
 __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const float* rays, size_t n, float tmax,
                                                              uint32_t* out_id, float* out_t) {
@@ -337,6 +363,14 @@ void launch_selftest_light_sample(const uint32_t* in, uint32_t* out, size_t n, h
 void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_sphere_sample, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_mis_weight(const float* in, float* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_mis_weight, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out, hipStream_t s) {
+  if (!k) return;
+  hipLaunchKernelGGL(k_selftest_light_find, dim3(static_cast<uint32_t>((k + 255) / 256)), dim3(256), 0, s, ids, n, queries, k, index_out);
 }
 void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;

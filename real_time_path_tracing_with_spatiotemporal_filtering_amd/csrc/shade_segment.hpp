@@ -124,6 +124,10 @@ __device__ __forceinline__ void hit_barycentrics(const HitRec& h, float& b0, flo
 // spec_power(SPEC): the weighted pick of RTPT_FLAG_EXT_NEE_POWER (light_sample.hpp: pick_power): the draw u_l names an entry through
 // the cumulative table that travels with the list (spec_lights_t<SPEC> is then LightTableView), and the sample's weight takes the
 // inverse of the pick's probability where the uniform pick's takes L.  The list has entries wherever these are launched.
+// spec_mis(SPEC): RTPT_FLAG_EXT_NEE_MIS (light_sample.hpp: MULTIPLE IMPORTANCE SAMPLING): the sample's weight g becomes g * m(g); a
+// diffuse hit that goes on leaves the cosine of its new direction in nee.cb; and an emissive triangle met with the sampled bit set
+// ends the path with (T * Ke) * wb(g_hit) where the others end it with 0 — that return needs the hit's barycentrics, also on a
+// path's last segment.  The list has entries wherever these are launched.  The sphere sample is as without the bit.
 struct NeeState {
   f3 wd;          // the shadow ray's direction, from the path's new origin
   f3 c;           // (T * Ke) * g
@@ -133,6 +137,7 @@ struct NeeState {
   f3 sphere_c;        // spec_sphere(SPEC): (T * light_col) * g of the sphere sample
   bool sphere_valid;  // ... this segment took a sphere sample that adds sphere_c to R
   bool sphere;        // ... the path's sphere bit
+  float cb;           // spec_mis(SPEC): the cosine the path's last diffuse bounce left with; read only while `sampled` is set
 };
 // what the instantiations that sample lights take behind alb_px (LV: their spec_lights_t<SPEC>), and what every other one takes
 // there: nothing.  (As two more parameters with defaults, a list and a pointer nobody read, the untextured queue kernels came out
@@ -183,7 +188,23 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     if (m1.w != 0.0f) {
       acc = acc * f3{m1.x, m1.y, m1.z};
       if constexpr (spec_lights(SPEC)) {
-        if (nee_args.st->sampled) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the lights: this one's emission is counted there
+        if constexpr (spec_mis(SPEC)) {
+          // the hit before sampled the lights: this emission is one of two estimators, weighed by the power heuristic
+          if (nee_args.st->sampled) {
+            const spec_lights_t<SPEC> lights = nee_args.lights;
+            float e0, e1, e2;
+            hit_barycentrics<SHORT_DIV>(h, e0, e1, e2);
+            float inv_p = static_cast<float>(lights.n);
+            bool reached = true;  // the pick can name this emitter
+            if constexpr (spec_power(SPEC)) reached = light::hit_inv_p_power(lights.ids, lights.cdf, lights.n, h.id1, &inv_p);
+            float wb = 1.0f;
+            if (reached)
+              wb = light::mis_bounce(light::hit_weight(xyz(s0), xyz(s1), xyz(s2), f3{s0.w, s1.w, s2.w}, o, d, e0, e1, e2, nee_args.st->cb, inv_p));
+            acc = f3{acc.x * wb, acc.y * wb, acc.z * wb};
+          }
+        } else {
+          if (nee_args.st->sampled) acc = f3{0.f, 0.f, 0.f};  // the hit before sampled the lights: this one's emission is counted there
+        }
       }
       if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       return true;
@@ -249,7 +270,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     const bool diffuse = !spec::is_specular(spec_w);
     if (diffuse && seg + 1 < a.max_segments) {
       // the list has entries, except where the sphere light is sampled without the weighted pick: there it may be empty (wave-uniform)
-      constexpr bool kMayBeEmpty = spec_sphere(SPEC) && !spec_power(SPEC);
+      constexpr bool kMayBeEmpty = spec_may_be_empty(SPEC);
       if (!kMayBeEmpty || lights.n > 0) {
         const float u_l = exact::rng_next(rng);
         const float u_a = exact::rng_next(rng);
@@ -270,7 +291,9 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
         const float4 ke = a.scene.materials[2 * static_cast<size_t>((id1 - 1) % a.scene.n_base_tris) + 1];
         const light::Sample sm = light::sample(xyz(l0), xyz(l1), xyz(l2), f3{l0.w, l1.w, l2.w}, o, n, u_a, u_b, inv_p);
         nee->wd = sm.wd;
-        nee->c = f3{(acc.x * ke.x) * sm.g, (acc.y * ke.y) * sm.g, (acc.z * ke.z) * sm.g};  // two roundings a channel, in this order
+        float g = sm.g;
+        if constexpr (spec_mis(SPEC)) g = sm.g * light::mis_light(sm.g);  // gm: one multiply behind the division
+        nee->c = f3{(acc.x * ke.x) * g, (acc.y * ke.y) * g, (acc.z * ke.z) * g};  // two roundings a channel, in this order
         nee->id1 = id1;
         nee->valid = sm.valid;
         nee->sampled = true;
@@ -303,6 +326,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     }
   }
   d = exact::normalize(f3{fmaf_(r, ct, n.x), fmaf_(r, st_, n.y), n.z + u});  // :259-261
+  if constexpr (spec_mis(SPEC)) nee_args.st->cb = exact::dot(n, d);  // (a last segment returned above: this hit took the triangle draw)
   return seg + 1 >= a.max_segments;  // budget exhausted: the path returns its throughput (:270)
 }
 

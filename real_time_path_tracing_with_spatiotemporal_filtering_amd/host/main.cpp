@@ -32,6 +32,9 @@ static void usage(const char* argv0) {
       "           no shadow ray, RTPT_FLAG_EXT_NEE_SPHERE = --flags 0x20000; on every context of a rank; needs no materials, combines with --nee)]\n"
       "          [--nee-power  (--nee with the emissive triangle picked by area times emission, not uniformly: RTPT_FLAG_EXT_NEE_POWER too,\n"
       "           --flags 0x50000; implies --nee; the cumulative table is built on the device)]\n"
+      "          [--nee-mis  (--nee with the light sample and the bounce that meets the same emitter weighed by the power heuristic:\n"
+      "           RTPT_FLAG_EXT_NEE_MIS too, --flags 0x90000; implies --nee; combines with --nee-power and --nee-sphere, whose sphere sample\n"
+      "           stays unweighed)]\n"
       "          [--device-bvh  (build the acceleration structure on the device, RTPT_FLAG_DEVICE_BVH_BUILD; same pixels)]\n"
       "          [--device-bvh-sah  (... with the device SAH builder: the host builder's tree, RTPT_FLAG_DEVICE_BVH_SAH too)]\n"
       "          [--ranks R [--rank r --rccl-id-file F [--rccl-nonce N] [--rccl-timeout S]] [--halo redundant|exchange] [--splits 0,a,b,..,H] [--device D]]\n"
@@ -95,6 +98,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--nee")) opt.flags |= RTPT_FLAG_EXT_NEE;
     else if (!std::strcmp(argv[i], "--nee-sphere")) opt.flags |= RTPT_FLAG_EXT_NEE_SPHERE;
     else if (!std::strcmp(argv[i], "--nee-power")) opt.flags |= RTPT_FLAG_EXT_NEE | RTPT_FLAG_EXT_NEE_POWER;
+    else if (!std::strcmp(argv[i], "--nee-mis")) opt.flags |= RTPT_FLAG_EXT_NEE | RTPT_FLAG_EXT_NEE_MIS;
     else if (!std::strcmp(argv[i], "--textures")) opt.textures = true;
     else if (!std::strcmp(argv[i], "--texture-mips")) opt.texture_mips = true;
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
