@@ -538,6 +538,22 @@ typedef struct rtpt_texture {
 int rtpt_scene_set_textures(rtpt_ctx* ctx, const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris,
                             const rtpt_texture* textures, uint32_t n_textures, const float* texels, size_t n_texels);
 
+/* Smooth shading: interpolated vertex normals (NOT reference behaviour, off until this call; additive:
+ * RTPT_ABI_VERSION stays 5).  tri_normals: n_tris x 9 floats, the corners' normals of triangle t of the mesh given to
+ * rtpt_scene_upload, in the mesh's own space and in that call's corner order (instance i, triangle t reads record t; the kernels
+ * carry them through model x instance transform with the pose's cofactor matrix, mirrors included).  tri_smooth: n_tris words, 0 =
+ * the triangle keeps its geometric normal; NULL = all smooth.  Normals need not be unit length and may hold anything, NaN and zero
+ * included: a hit whose interpolated normal does not normalise to finite numbers shades with the geometric normal
+ * (csrc/shading_normal.hpp states the rules: which normal each step of a bounce uses, and the side tests that keep rays off the
+ * wrong side of the real surface).  The diffuse, specular and dielectric bounces and the light samples use the interpolated
+ * normal; the offset origin, the normal-keyed colours, the texture footprint, K0, K1, the LUT and the filter keep the
+ * triangle's.  A scene that holds normals is traced through its BVH, as under RTPT_FLAG_FORCE_BVH, however small it is.
+ * tri_normals == NULL with n_tris == 0 removes them; rtpt_scene_upload drops them with the materials; moved instances, a changed
+ * ubo.model, rtpt_scene_rebuild and rtpt_resize keep them.  RTPT_E_NO_SCENE before an upload.  RTPT_E_INVALID, with the scene
+ * untouched, for: n_tris other than the uploaded mesh's; tri_normals == NULL with n_tris != 0; a context created with
+ * RTPT_FLAG_NO_PATH_COMPACTION (that A/B form of the tracing kernels has no smooth instantiation). */
+int rtpt_scene_set_normals(rtpt_ctx* ctx, const float* tri_normals, const uint32_t* tri_smooth, uint32_t n_tris);
+
 /* What built the tree that is on the device now.  (A struct tag without a typedef: the entry point below carries the
  * same name, and C keeps tags and functions apart.) */
 enum { RTPT_BVH_BUILDER_HOST_SAH = 0, RTPT_BVH_BUILDER_DEVICE_LBVH = 1 };
@@ -869,6 +885,13 @@ int rtpt_selftest_light_pick(rtpt_ctx* ctx, const uint64_t* cdf, size_t n, const
  * emitter's unit normal is computed as for its shade record, b0 = 1 - b1 - b2.  Operands are not checked.  Additive:
  * RTPT_ABI_VERSION stays 5. */
 int rtpt_selftest_mis_weight(rtpt_ctx* ctx, const float* in, float* out, size_t n);
+/* The rules of smooth shading (csrc/shading_normal.hpp: rules 1 to 7 and the three side tests), one case per thread, by the
+ * functions the tracing kernels call: in = n x 36 words (n0[3], n1[3], n2[3] the corners' normals, the hit's b1, b2, the three rows
+ * of the pose's cofactor matrix [9], ng[3] the faced geometric normal, d[3] the incoming direction, d'[3] a new direction, wd[3] a
+ * light sample's direction, ray_offset; words 33 to 35 are not read), out = n x 8 floats (1.0f if the hit is smooth else 0.0f,
+ * ns[3] — ng where it is not —, 1.0f if d' is absorbed, 1.0f if wd stays valid, the dielectric's signed offset for d', 0).
+ * b0 = 1 - b1 - b2.  Operands are not checked.  Additive: RTPT_ABI_VERSION stays 5. */
+int rtpt_selftest_shading_normal(rtpt_ctx* ctx, const float* in, float* out, size_t n);
 /* The search of RTPT_FLAG_EXT_NEE_MIS (csrc/light_list_host.hpp: find) of k queries on the ascending list ids[0, n), n <= 2^24:
  * index_out[j] = the index of queries[j] in the list, n for an id that is not in it.  ids is not checked beyond n; every index the
  * search reads lies in [0, n). */
@@ -924,6 +947,12 @@ int rtpt_util_load_obj_materials_ni(const char* path, uint32_t* tri_material, ui
  * the corner gets (0, 0)); negative vt indices count back from the last `vt` read.  tri_uv: 6 floats per triangle (u0 v0 u1
  * v1 u2 v2), fanned like rtpt_util_load_obj's triangles, so the two arrays line up.  Two-call pattern (NULL: count). */
 int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tris);
+/* the vertex-normal side of the same file, for rtpt_scene_set_normals: `vn` records and the vn of `f v//vn`, `f v/vt/vn` corners;
+ * negative vn indices count back from the last `vn` read.  tri_normals: 9 floats per triangle (the three corners' normals),
+ * tri_smooth: one word per triangle, both fanned like rtpt_util_load_obj's triangles, so the arrays line up.  A face with a
+ * corner that has no vn, or whose vn index is 0 or out of range, gives triangles with tri_smooth 0 and normals (0, 0, 0); every
+ * other triangle has tri_smooth 1.  Two-call pattern (tri_normals == NULL: count; tri_smooth may be NULL). */
+int rtpt_util_load_obj_normals(const char* path, float* tri_normals, uint32_t* tri_smooth, uint32_t* n_tris);
 /* the `map_Kd` file name of every material, in rtpt_util_load_obj_materials' numbering (entry 0, the default material, is
  * always empty; no map: empty): *n_materials NUL-terminated strings, one after the other, in `names`.  Options before the
  * name are not supported (the last word of the line is taken).  Two-call pattern: names == NULL stores the byte count in

@@ -155,6 +155,7 @@ SYMBOLS = [
     "rtpt_selftest_light_sample", "rtpt_debug_light_list", "rtpt_selftest_sphere_sample",
     "rtpt_selftest_light_table", "rtpt_selftest_light_pick", "rtpt_debug_light_table",
     "rtpt_selftest_mis_weight", "rtpt_selftest_light_find",
+    "rtpt_scene_set_normals", "rtpt_selftest_shading_normal", "rtpt_util_load_obj_normals",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -250,6 +251,9 @@ def load() -> C.CDLL:
         "rtpt_selftest_sphere_sample": [vp, vp, vp, sz],
         "rtpt_selftest_mis_weight": [vp, vp, vp, sz],
         "rtpt_selftest_light_find": [vp, vp, sz, vp, sz, vp],
+        "rtpt_scene_set_normals": [vp, vp, vp, u32],
+        "rtpt_selftest_shading_normal": [vp, vp, vp, sz],
+        "rtpt_util_load_obj_normals": [C.c_char_p, vp, vp, C.POINTER(u32)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -346,6 +350,16 @@ def load_obj_texcoords(path: str) -> np.ndarray:
     uv = np.zeros((nt.value, 6), np.float32)
     _check(load().rtpt_util_load_obj_texcoords(path.encode(), _ptr(uv), C.byref(nt)))
     return uv
+
+
+def load_obj_normals(path: str):
+    """(tri_normals [t, 9] f32 — the corners' `vn` records —, tri_smooth [t] u32), lined up with load_obj's triangles; a face
+    with a corner that has no usable vn gives triangles with tri_smooth 0 and normals 0 (rtpt_util_load_obj_normals)"""
+    nt = C.c_uint32()
+    _check(load().rtpt_util_load_obj_normals(path.encode(), None, None, C.byref(nt)))
+    nrm, smooth = np.zeros((nt.value, 9), np.float32), np.zeros(nt.value, np.uint32)
+    _check(load().rtpt_util_load_obj_normals(path.encode(), _ptr(nrm), _ptr(smooth), C.byref(nt)))
+    return nrm, smooth
 
 
 def load_obj_map_kd(path: str):
@@ -544,6 +558,19 @@ class Context:
         tex = np.ascontiguousarray(texels, np.float32).reshape(-1, 4)
         _check(self._lib.rtpt_scene_set_textures(self._h, _ptr(uv), _ptr(tri), len(tri), _ptr(desc), len(desc), _ptr(tex), len(tex)))
 
+    def set_normals(self, tri_normals=None, tri_smooth=None):
+        """smooth shading (rtpt_scene_set_normals): tri_normals [t, 9] f32, the corners' normals of every triangle of the
+        uploaded mesh in its own space; tri_smooth [t] u32 (0: the triangle keeps its geometric normal) or None: all smooth.
+        tri_normals None removes them"""
+        if tri_normals is None:
+            _check(self._lib.rtpt_scene_set_normals(self._h, None, None, 0))
+            return
+        nrm = np.ascontiguousarray(tri_normals, np.float32).reshape(-1, 9)
+        sm = None if tri_smooth is None else np.ascontiguousarray(tri_smooth, np.uint32).ravel()
+        if sm is not None and len(sm) != len(nrm):
+            raise ValueError("one smooth word per triangle")
+        _check(self._lib.rtpt_scene_set_normals(self._h, _ptr(nrm), _ptr(sm), len(nrm)))
+
     # -- passes
     def gbuffer(self, ubo: Ubo, y0=0, y1=0):
         _check(self._lib.rtpt_gbuffer(self._h, C.byref(ubo), y0, y1))
@@ -715,6 +742,15 @@ class Context:
         cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 20)
         out = np.zeros((len(cases), 3), np.float32)
         _check(self._lib.rtpt_selftest_mis_weight(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def selftest_shading_normal(self, cases: np.ndarray) -> np.ndarray:
+        """[n, 8] float32 (smooth, ns[3], absorbed, sample_side, the dielectric's offset, 0) of the device's smooth-shading rules
+        on cases [n, 36] floats = n0, n1, n2, b1, b2, the cofactor rows [9], ng, d, d', wd, ray_offset, three words that are
+        not read (rtpt_selftest_shading_normal)"""
+        cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 36)
+        out = np.zeros((len(cases), 8), np.float32)
+        _check(self._lib.rtpt_selftest_shading_normal(self._h, _ptr(cases), _ptr(out), len(cases)))
         return out
 
     def selftest_light_find(self, ids: np.ndarray, queries: np.ndarray) -> np.ndarray:

@@ -83,6 +83,9 @@ class HipBackend:
     def set_textures(self, tri_uv=None, tri_texture=None, textures=None, texels=None):
         self.ctx.set_textures(tri_uv, tri_texture, textures, texels)
 
+    def set_normals(self, tri_normals=None, tri_smooth=None):
+        self.ctx.set_normals(tri_normals, tri_smooth)
+
     def gbuffer(self, ubo, y0, y1):
         self.ctx.gbuffer(ubo, y0, y1)
 
@@ -284,6 +287,10 @@ class PipelinedBackend:
     def set_textures(self, tri_uv=None, tri_texture=None, textures=None, texels=None):
         for b in self.be:   # both contexts shade
             b.set_textures(tri_uv, tri_texture, textures, texels)
+
+    def set_normals(self, tri_normals=None, tri_smooth=None):
+        for b in self.be:
+            b.set_normals(tri_normals, tri_smooth)
 
     def gbuffer(self, ubo, y0, y1):
         self.cur.gbuffer(ubo, y0, y1)
@@ -756,7 +763,8 @@ class PathTracingApplication:
 def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode="exchange", flags=0,
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
-             specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, nee_mis=False, **app_kw):
+             specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, nee_mis=False, smooth_normals=False,
+             **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -780,7 +788,13 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     the device and follows moved instances and a changed model.
     `nee_mis` (off by default): `nee` with the light sample and the bounce that meets the same emitter weighed against each other
     by the power heuristic, abi.FLAG_EXT_NEE | abi.FLAG_EXT_NEE_MIS on every context of this rank (it implies `nee`); it combines
-    with `nee_power` and `nee_sphere`, whose sphere sample it leaves unweighed."""
+    with `nee_power` and `nee_sphere`, whose sphere sample it leaves unweighed.
+    `smooth_normals` (off by default): shade with the OBJ's interpolated `vn` records (abi.load_obj_normals,
+    rtpt_scene_set_normals) on every context of this rank: bounces, refraction and light samples use the interpolated normal, a
+    face without normals keeps its own.  An OBJ without any `vn` is left as it is.  With `mesh`, pass the normals yourself:
+    app.backend.set_normals(tri_normals, tri_smooth)."""
+    if smooth_normals and mesh is not None:
+        raise ValueError("smooth_normals=True reads the OBJ's vn records: it needs `scene`, not `mesh`")
     if nee or nee_power or nee_mis:
         flags |= abi.FLAG_EXT_NEE
     if nee_power:
@@ -824,4 +838,8 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
         tri_material, materials = (abi.load_obj_materials_ni if dielectric else abi.load_obj_materials_ext)(scene)
         if materials is not None:
             be.set_materials_ext(tri_material, materials)      # (replaces the Kd / Ke set of textures=True: the same Kd / Ke)
+    if smooth_normals:
+        tri_normals, tri_smooth = abi.load_obj_normals(scene)
+        if tri_smooth.any():
+            be.set_normals(tri_normals, tri_smooth)
     return app

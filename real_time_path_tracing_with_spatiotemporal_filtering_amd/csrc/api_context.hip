@@ -184,6 +184,12 @@ rt::LightTableView light_view(const rtpt_ctx* c) {
                             static_cast<const uint64_t*>(c->scene.light_table.cdf.ptr)};
 }
 
+rt::NormalView normal_view(const rtpt_ctx* c) {
+  const bool has = c->scene.normals.records.ptr && c->scene.normals.cof.ptr;
+  return rt::NormalView{has ? static_cast<const float4*>(c->scene.normals.records.ptr) : nullptr,
+                        has ? static_cast<const float4*>(c->scene.normals.cof.ptr) : nullptr};
+}
+
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose
 // view-space axes are the columns c0,c1,c2 and whose pixel (x,y) looks along
 // (nx/p00, ny/p11, -1), nx = (2(x+.5)-W)/W, ny = (2(y+.5)-H)/H  (the K0 ray; the K2 camera is the

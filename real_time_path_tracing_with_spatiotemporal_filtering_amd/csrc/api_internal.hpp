@@ -213,6 +213,21 @@ struct Scene {
     Buf levels;  // the level table, only when some texture has RTPT_TEX_MIPMAP; texels then also holds the generated levels
     uint32_t n_textures = 0;
   } textures;
+  // optional vertex normals, rtpt_scene_set_normals (shading_normal.hpp): the per-base-triangle corner normals and the cofactor
+  // matrix of every instance's pose, 48 bytes each.  The table follows the pose: repose_scene rebuilds it (api_scene.hip:
+  // rebuild_normal_cof) on the context's stream from the model and the instance transforms — on the device route from the
+  // transforms as they stand on the device (mesh_dev.xf where it holds them, xf_dev_current; else `xf`, this struct's own
+  // copy), on the host route from inst_xf.  While the records exist the scene traces through its tree (use_bvh).
+  struct Normals {
+    Buf records, cof;
+    Buf xf;  // the instance transforms, where mesh_dev.xf does not hold them
+    bool xf_current = false;  // ... and it holds inst_xf
+    std::vector<float> cof_host;  // the host route's staging for `cof`
+  } normals;
+  // the instance transforms as last given (12 floats each), kept where the device mesh does not hold them (a host-flattened
+  // upload, the host route's moves) and while the scene has normals; a scene with transforms has them here, there, or both
+  std::vector<float> inst_xf;
+  bool xf_dev_current = false;  // mesh_dev.xf holds the transforms as last given
   struct rtpt_scene_build_info build_info {};
   bool build_ms_pending = false;  // build_ms is still in rtpt_ctx::build_ev; read lazily by rtpt_scene_build_info
 };
@@ -372,6 +387,7 @@ rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1);
 rt::SceneView scene_view(const rtpt_ctx* c);
 rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
 rt::LightTableView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights), and its table or NULL
+rt::NormalView normal_view(const rtpt_ctx* c);     // the vertex normals, both NULL without (rtpt_scene_set_normals)
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3], double p00, double p11,
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);

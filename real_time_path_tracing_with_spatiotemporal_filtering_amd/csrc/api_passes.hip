@@ -166,8 +166,8 @@ int trace_material_mode(const rtpt_ctx* c) {
 int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
   a.pool_slab = nullptr;
   if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo && !c->scene.textures.records.ptr &&
-        !trace_material_mode(c)))
-    return RTPT_OK;  // (the pool form stores no albedo, samples no texture and bounces diffusely: such frames take the tile kernel)
+        !trace_material_mode(c) && !c->scene.normals.records.ptr))
+    return RTPT_OK;  // (the pool form stores no albedo, samples no texture, bounces diffusely about the triangle's normal: such frames take the tile kernel)
   const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
   if (need && c->path_pool.bytes < need)
     if (int rc = alloc_buf(c->path_pool, need)) return rc;
@@ -491,7 +491,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), trace_material_mode(c), c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c));
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c), normal_view(c));
   }
   if (take) {
     c->deferred_valid = false;

@@ -4,6 +4,8 @@
 #include "api_internal.hpp"
 #include "light_list_host.hpp"
 #include "material_host.hpp"
+#include "normal_host.hpp"
+#include "shading_normal.hpp"
 #include "texture_host.hpp"
 
 #include <chrono>
@@ -28,6 +30,10 @@ rt::ScenePrepArgs scene_prep_args(const Scene& s) {
 // what follows every launch_scene_prepare: the cumulative light table of RTPT_FLAG_EXT_NEE_POWER, where the scene has one
 // (defined beside the light list below)
 void rebuild_light_table(rtpt_ctx* c, Scene& s);
+
+// ... and the cofactor table of smooth shading, where the scene has vertex normals (rtpt_scene_set_normals): it follows the pose,
+// so repose_scene — the one routine that re-poses — rebuilds it on both of its routes (defined beside the entry point below)
+int rebuild_normal_cof(rtpt_ctx* c, Scene& s, const float* model, bool on_device);
 
 rt::RefitArgs refit_args(const Scene& s) {
   rt::RefitArgs ra;
@@ -289,6 +295,50 @@ void rebuild_light_table(rtpt_ctx* c, Scene& s) {
   la.scratch = s.light_table.scratch.ptr;
   rt::launch_light_table(la, c->stream);
 }
+// The cofactor table of scene s under `model` (shading_normal.hpp: cof_rows), one matrix per instance; nothing without normals.
+// on_device: a small kernel on the context's stream from the transforms as they stand there — no upload, no synchronisation.
+// Otherwise the same function on the host, into a staging vector the scene owns, and one copy; the caller synchronises.
+// The transforms of a scene that has any are on the device (mesh_dev.xf, xf_dev_current), on the host (inst_xf), or both.
+int rebuild_normal_cof(rtpt_ctx* c, Scene& s, const float* model, bool on_device) {
+  if (!s.normals.records.ptr || !s.normals.cof.ptr) return RTPT_OK;
+  const uint32_t ni = s.n_instances ? s.n_instances : 1u;
+  const bool on_dev = s.xf_dev_current && s.mesh_dev.xf.ptr, on_host = !s.inst_xf.empty();
+  const bool with_xf = on_dev || on_host;
+  if (on_host && s.inst_xf.size() != 12 * static_cast<size_t>(ni)) return fail(RTPT_E_INVALID, "internal: the host copy of the instance transforms is missing");
+  if (on_device) {
+    const float* xf = nullptr;
+    if (on_dev) {
+      xf = static_cast<const float*>(s.mesh_dev.xf.ptr);
+    } else if (on_host) {
+      // transforms that never went to the device mesh, or went stale there on the host route: the normals' own copy, which
+      // rtpt_scene_set_normals uploaded.  Only where it is stale (a host-route move, then a route that changed) it goes up
+      // again, and the stream drains before the pageable source may change
+      if (!s.normals.xf_current) {
+        int rc;
+        if (s.normals.xf.bytes != static_cast<size_t>(ni) * 48 && (rc = alloc_buf(s.normals.xf, static_cast<size_t>(ni) * 48))) return rc;
+        HIP_TRY(hipMemcpyAsync(s.normals.xf.ptr, s.inst_xf.data(), s.normals.xf.bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        s.normals.xf_current = true;
+      }
+      xf = static_cast<const float*>(s.normals.xf.ptr);
+    }
+    rt::RefitModel rm;
+    std::memcpy(rm.m, model, sizeof rm.m);
+    rm.identity = is_identity(model) ? 1 : 0;
+    rt::launch_normal_cof(ni, xf, rm, static_cast<float4*>(s.normals.cof.ptr), c->stream);
+    return RTPT_OK;
+  }
+  if (with_xf && !on_host) return fail(RTPT_E_INVALID, "internal: the host copy of the instance transforms is missing");
+  try {
+    s.normals.cof_host.resize(12 * static_cast<size_t>(ni));
+  } catch (const std::bad_alloc&) {
+    return fail(RTPT_E_NOMEM, "host allocation failed (normal cofactors)");
+  }
+  for (uint32_t i = 0; i < ni; i++)
+    rt::nrm::cof_rows(model, with_xf ? s.inst_xf.data() + 12 * static_cast<size_t>(i) : nullptr, s.normals.cof_host.data() + 12 * static_cast<size_t>(i));
+  HIP_TRY(hipMemcpyAsync(s.normals.cof.ptr, s.normals.cof_host.data(), s.normals.cof.bytes, hipMemcpyHostToDevice, c->stream));
+  return RTPT_OK;
+}
 int join_materials(rtpt_ctx* c, Buf& recs, Buf& ids, size_t n_lights, Scene::LightTable& tab) {
   c->scene.materials = std::move(recs);
   if (ids.ptr) {
@@ -467,6 +517,9 @@ int finish_scene(const rtpt_ctx* c, Scene& s, const MeshIn& in, std::vector<floa
     s.mesh_xyz.assign(in.xyz, in.xyz + 3 * static_cast<size_t>(in.n_verts));
     s.mesh_idx.assign(in.idx, in.idx + 3 * static_cast<size_t>(in.n_tris));
     if (small) s.host_tris = tris;
+    // the transforms, where the device mesh does not hold them (a device-flatten upload copied them there): nothing else does,
+    // and the cofactor table of rtpt_scene_set_normals is built from them
+    if (in.xf && !s.mesh_dev.xf.ptr) s.inst_xf.assign(in.xf, in.xf + 12 * static_cast<size_t>(in.ni));
   } catch (const std::bad_alloc&) {
     return fail(RTPT_E_NOMEM, "host allocation failed (mesh copy)");
   }
@@ -516,6 +569,7 @@ int rtpt_scene_upload(rtpt_ctx* c, const float* xyz, uint32_t n_verts, const uin
       if ((rc = upload_host_tree(c, s, tris, leaf_pairs, too_deep ? RTPT_BVH_FALLBACK_DEPTH : RTPT_BVH_FALLBACK_NONE))) return rc;
   }
   if ((rc = finish_scene(c, s, in, tris, paired_all))) return rc;
+  s.xf_dev_current = xf && s.mesh_dev.xf.ptr;  // (a device-flatten upload copied them there)
   if (flatten_there && !too_deep) c->upload_info[1] = c->upload_info[2] = 1;
   s.build_info.upload_ms = static_cast<float>(now_ms() - t_call);
   c->scene = std::move(s);
@@ -551,6 +605,7 @@ int repose_scene(rtpt_ctx* c, const float* model) {
     rt::launch_refit(refit_args(s), s.tree.refit_level_first.data(), static_cast<int>(s.tree.refit_level_first.size()) - 1, s.tree.n_nodes, 1e-5f, c->stream);
     rt::launch_scene_prepare(scene_prep_args(s), c->stream);
     rebuild_light_table(c, s);
+    if ((rc = rebuild_normal_cof(c, s, model, true))) return rc;
     if ((rc = launch_check("device refit"))) return rc;
   } else {
     rt::refit_bvh(posed.data(), total, s.tree.bvh_host);
@@ -563,6 +618,7 @@ int repose_scene(rtpt_ctx* c, const float* model) {
   if ((rc = upload_grid(c, s, grid_h))) return rc;
     rt::launch_scene_prepare(scene_prep_args(s), c->stream);
     rebuild_light_table(c, s);
+    if ((rc = rebuild_normal_cof(c, s, model, false))) return rc;
     if ((rc = launch_check("scene_prepare"))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // host staging vectors die at return
   }
@@ -665,11 +721,32 @@ int rtpt_scene_set_instances(rtpt_ctx* c, const float* xf, uint32_t n_instances)
   }
   const bool paired_before = s.tris_paired;
   s.tris_paired = paired;
+  // The transforms the cofactor table of smooth shading is built from (repose_scene: rebuild_normal_cof).  On the device route
+  // they are in the device mesh (stage_transforms above) and a scene without normals keeps no host copy: the call allocates what
+  // it allocated before there were normals.  The host route, which flattens into a vector of its own anyway, and a scene that
+  // holds normals keep one.
+  std::vector<float> xf_before;  // the new copy until the swap, the replaced one after it
+  if (!on_device || s.normals.records.ptr) {
+    try {
+      xf_before.assign(xf, xf + 12 * static_cast<size_t>(ni));
+    } catch (const std::bad_alloc&) {
+      if (!on_device) s.obj_tris.swap(obj);
+      s.tris_paired = paired_before;
+      return fail(RTPT_E_NOMEM, "host allocation failed (instance transforms)");
+    }
+  }
+  s.inst_xf.swap(xf_before);
+  const bool xf_dev_before = s.xf_dev_current, nxf_before = s.normals.xf_current;
+  s.xf_dev_current = on_device;
+  s.normals.xf_current = false;  // (of the normals' own device copy, which is read only while the device mesh is stale)
   const int rc = repose_scene(c, s.model);
   if (rc) {
     if (!on_device) {  // nothing reached the device: the scene is the one before the call
       s.obj_tris.swap(obj);
       s.tris_paired = paired_before;
+      s.inst_xf.swap(xf_before);
+      s.xf_dev_current = xf_dev_before;
+      s.normals.xf_current = nxf_before;
     }
     return rc;
   }
@@ -793,6 +870,59 @@ int rtpt_scene_set_materials_ext(rtpt_ctx* c, const uint32_t* tri_material, uint
   rc = join_materials(c, recs, ids, lights.size(), tab);
   c->scene.materials_specular = any_specular;
   return rc;
+}
+
+int rtpt_scene_set_normals(rtpt_ctx* c, const float* tri_normals, const uint32_t* tri_smooth, uint32_t n_tris) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  const bool drop = !tri_normals && n_tris == 0;
+  // everything that can refuse the call comes first: a refused call leaves the scene, and the normals it has, untouched
+  if (!drop)
+    if (const char* why = rtpt_nrm::check_normals(tri_normals, n_tris, c->scene.n_base_tris, c->cfg.flags)) return fail(RTPT_E_INVALID, why);
+  std::vector<float> rec;
+  if (!drop) {
+    try {
+      rec.resize(static_cast<size_t>(n_tris) * rtpt_nrm::kRecordFloats);
+    } catch (const std::bad_alloc&) {
+      return fail(RTPT_E_NOMEM, "host allocation failed (normal records)");
+    }
+    rtpt_nrm::pack_records(tri_normals, tri_smooth, n_tris, rec.data());
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the set being replaced
+  Scene& s = c->scene;
+  const bool bvh_without = (s.n_tris > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);  // finish_scene's choice
+  if (drop) {
+    s.normals = Scene::Normals{};
+    if (s.use_bvh != bvh_without) {
+      s.use_bvh = bvh_without;
+      c->scene_gen++;  // brute force may resolve a tie between equally near triangles differently
+    }
+    return RTPT_OK;
+  }
+  Scene::Normals nn;  // joins the scene when it is complete; the set it replaces stays until then
+  const uint32_t ni = s.n_instances ? s.n_instances : 1u;
+  // the normals' own device copy of the transforms, only where the device mesh does not hold them
+  const bool with_xf = !(s.xf_dev_current && s.mesh_dev.xf.ptr) && !s.inst_xf.empty();
+  int rc;
+  if ((rc = alloc_buf(nn.records, rec.size() * sizeof(float))) || (rc = alloc_buf(nn.cof, static_cast<size_t>(ni) * 48))) return rc;
+  if (with_xf && (rc = alloc_buf(nn.xf, static_cast<size_t>(ni) * 48))) return rc;
+  HIP_TRY(hipMemcpyAsync(nn.records.ptr, rec.data(), nn.records.bytes, hipMemcpyHostToDevice, c->stream));
+  if (with_xf) HIP_TRY(hipMemcpyAsync(nn.xf.ptr, s.inst_xf.data(), nn.xf.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays and `rec` may die at return
+  nn.xf_current = with_xf;
+  std::swap(s.normals, nn);
+  const bool bvh_before = s.use_bvh;
+  s.use_bvh = true;  // (refits_on_device reads it: the table below is built by the route the next re-pose takes)
+  if ((rc = rebuild_normal_cof(c, s, s.model, refits_on_device(c, s))) || (rc = launch_check("normal cofactors"))) {
+    std::swap(s.normals, nn);  // the scene is the one before the call
+    s.use_bvh = bvh_before;
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!bvh_before) c->scene_gen++;  // the tree may resolve a tie between equally near triangles differently
+  return RTPT_OK;
 }
 
 int rtpt_scene_set_textures(rtpt_ctx* c, const float* tri_uv, const uint32_t* tri_texture, uint32_t n_tris, const rtpt_texture* textures,

@@ -195,6 +195,25 @@ int rtpt_selftest_mis_weight(rtpt_ctx* c, const float* in, float* out, size_t n)
   return RTPT_OK;
 }
 
+int rtpt_selftest_shading_normal(rtpt_ctx* c, const float* in, float* out, size_t n) {
+  if (!c || !in || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t in_bytes = n * 36 * sizeof(float), out_bytes = n * 8 * sizeof(float);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, in_bytes)) || (rc = alloc_buf(dout, out_bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_shading_normal(static_cast<const float*>(din.ptr), static_cast<float*>(dout.ptr), n, c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_shading_normal: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_light_find(rtpt_ctx* c, const uint32_t* ids, size_t n, const uint32_t* queries, size_t k, uint32_t* index_out) {
   if (!c || !queries || !index_out || (n && !ids)) return fail(RTPT_E_INVALID, "NULL argument");
   if (n > (static_cast<size_t>(1) << 24)) return fail(RTPT_E_INVALID, "a light list has at most 2^24 entries");

@@ -227,6 +227,17 @@ int rtpt_util_load_obj_texcoords(const char* path, float* tri_uv, uint32_t* n_tr
   return o.bad_texcoord_index ? fail(RTPT_E_INVALID, rtpt_obj::kBadTexcoordIndex) : RTPT_OK;
 }
 
+// the vn side of the same parse (rtpt_scene_set_normals takes the two arrays as they are); a vn index out of range is not refused:
+// its face is not smooth
+int rtpt_util_load_obj_normals(const char* path, float* tri_normals, uint32_t* tri_smooth, uint32_t* n_tris) {
+  if (!path || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
+  rtpt_obj::Obj o;
+  if (int rc = parse_obj(path, o)) return rc;
+  if (tri_normals) rtpt_obj::copy_tri_normals(o, tri_normals, tri_smooth);
+  *n_tris = rtpt_obj::n_tris(o);
+  return RTPT_OK;
+}
+
 // the `map_Kd` names, NUL-terminated, one after the other; none without a readable library
 int rtpt_util_load_obj_map_kd(const char* path, char* names, size_t* names_bytes, uint32_t* n_materials) {
   if (!path || !names_bytes || !n_materials) return fail(RTPT_E_INVALID, "NULL argument");

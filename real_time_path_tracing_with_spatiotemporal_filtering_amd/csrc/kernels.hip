@@ -154,14 +154,14 @@ template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_pathtrace(PathtraceArgs a, TexView tex, LV... lights) {
-  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
   pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
 }
 template <bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_pathtrace_small(PathtraceArgs a, TexView tex, LV... lights) {
-  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
   pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
 }
 
@@ -176,14 +176,14 @@ template <int BVH, bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
 void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
-  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
   gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights...);
 }
 template <bool DEMOD, int TEX, int SPEC, class... LV>
 __global__ __launch_bounds__(kPtThreads)
 __attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
 void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
-  static_assert(sizeof...(LV) <= 1 && spec_takes<SPEC, LV...>(), "the light argument is the one SPEC asks for");
+  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
   gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights...);
 }
 
@@ -229,8 +229,11 @@ void k_pathtrace_final(PathtraceArgs a, TexView tex, AtrousArgs f, FinalSplit sp
   }
 }
 
-template <int BVH, int TEX, int SPEC>
-__global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex) {
+// NV: nothing, or the scene's NormalView (kernels.hpp: the NRM axis).  The queue record does not change: a shading normal belongs to
+// a hit, not to a path.
+template <int BVH, int TEX, int SPEC, class... NV>
+__global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a, TexView tex, NV... normals) {
+  static_assert(sizeof...(NV) == 0 || (sizeof...(NV) == 1 && pack_nrm<NV...>()), "a NormalView or nothing");
   extern __shared__ __attribute__((aligned(16))) uint32_t stack[];
   PathState& st = *reinterpret_cast<PathState*>(stack);
   __shared__ uint32_t wave_cnt[kPtRows];
@@ -265,7 +268,13 @@ __global__ __launch_bounds__(kPtThreads) void k_pathtrace_queue(PathtraceArgs a,
         closest_hit<BVH>(a.scene, o, d, h, stack, tid, kPtThreads, 1 + static_cast<int>(seg));  // :208-222
         const int x = static_cast<int>(pix & 0xFFFFu), y = static_cast<int>(pix >> 16);
         if (y >= a.count_y0 && y < a.count_y1) rays++;
-        if (shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex)) {
+        bool done;
+        if constexpr (sizeof...(NV) != 0)
+          done = shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0, SPEC, NoNee, NormalView>(a, h, seg, light_c, o, d, acc, rng, tex, nullptr, NoNee{},
+                                                                                                      normals...);
+        else
+          done = shade_segment<TEX, BVH, (RTPT_TRACE_ITEMS & 8) && BVH == 0, SPEC>(a, h, seg, light_c, o, d, acc, rng, tex);
+        if (done) {
           alive = false;
           const size_t gi = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
           a.image[gi] = make_float4(acc.x, acc.y, acc.z, a.depth[gi]);  // :328,:343 (+ depth in alpha)
@@ -393,7 +402,7 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
                           runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol, uint32_t* run_info, const LightTableView& lights) {
+                      const FilterPolicy* pol, uint32_t* run_info, const LightTableView& lights, const NormalView& normals) {
   if (run_info) {
     run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
     run_info[1] = run_info[2] = 0u;
@@ -408,7 +417,10 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   if (nee && !may_be_empty && (!lights.ids || !lights.n || !a.scene.materials)) std::abort();
   if (nee && may_be_empty && lights.n && (!lights.ids || !a.scene.materials)) std::abort();
   if (spec_power(spec) && !lights.cdf) std::abort();  // the weighted pick reads the list's table
-  const bool pool = !nee && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
+  // rtpt_scene_set_normals: the scene is traced through its tree by a compacting launch (api_scene.hip, api_passes.hip see to both)
+  const bool nrm = normals.records != nullptr;
+  if (nrm && (!normals.cof || !a.scene.use_bvh || (!gb && !a.compact) || fin)) std::abort();
+  const bool pool = !nee && !nrm && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
@@ -453,7 +465,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       hipLaunchKernelGGL((k_pathtrace_pool<false>), grid, block, dyn, s, b, GbufferArgs{});
   } else
 #endif
-  // the instantiation list of the family: scene mode x DEMOD x TEX x SPEC (x COMPACT for the unfused launch), here and nowhere else
+  // the instantiation list of the family: scene mode x DEMOD x TEX x SPEC (x COMPACT for the unfused launch) x NRM (kernels.hpp: in
+  // the BVH modes and the compacting forms only), here and nowhere else
   with_mode<3>(scene_mode(a.scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     with_bool(a.albedo != nullptr, [&](auto demod) {  // RTPT_FLAG_EXT_DEMODULATE: the instantiations that store the albedo plane
@@ -467,27 +480,44 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
           // l: the light argument S asks for, spec_lights_t<S>.  (The launch syntax, because a kernel template with a parameter pack
           // left to deduction is no argument for hipLaunchKernelGGL's deduced kernel type: a call deduces it from its arguments.)
           const auto go = [&](auto... l) {
-            if (gb) {
-              if constexpr (M != 0)
+            if constexpr (pack_nrm<decltype(l)...>()) {  // NRM: the fused launch and the unfused compacting one
+              if (gb)
                 k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
               else
-                k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
+                k_pathtrace<M, true, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
+            } else {
+              if (gb) {
+                if constexpr (M != 0)
+                  k_gbuffer_pathtrace<M, D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
+                else
+                  k_gbuffer_pathtrace_small<D, T, S><<<grid, block, dyn, s>>>(b, *gb, tex, l...);
+                return;
+              }
+              with_bool(a.compact != 0, [&](auto compact) {
+                constexpr bool C = decltype(compact)::value;
+                if constexpr (M != 0)
+                  k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
+                else
+                  k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
+              });
+            }
+          };
+          // n: the scene's NormalView behind it, or nothing
+          const auto with_lights = [&](auto... n) {
+            if constexpr (spec_power(S))
+              go(lights, n...);
+            else if constexpr (spec_lights(S))
+              go(LightView{lights.ids, lights.n}, n...);
+            else
+              go(n...);
+          };
+          if constexpr (M != 0) {
+            if (nrm) {
+              with_lights(normals);
               return;
             }
-            with_bool(a.compact != 0, [&](auto compact) {
-              constexpr bool C = decltype(compact)::value;
-              if constexpr (M != 0)
-                k_pathtrace<M, C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
-              else
-                k_pathtrace_small<C, D, T, S><<<grid, block, dyn, s>>>(b, tex, l...);
-            });
-          };
-          if constexpr (spec_power(S))
-            go(lights);
-          else if constexpr (spec_lights(S))
-            go(LightView{lights.ids, lights.n});
-          else
-            go();
+          }
+          with_lights();
         });
       });
     });
@@ -510,8 +540,14 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
     with_mode<3>(scene_mode(a.scene), [&](auto mode) {
       with_mode<3>(tex_mode(tex), [&](auto tmode) {
         with_mode<3>(spec_mode(specular), [&](auto spec) {
-          hipLaunchKernelGGL((k_pathtrace_queue<decltype(mode)::value, decltype(tmode)::value, decltype(spec)::value>), qgrid, block,
-                             dyn_queue, s, c, tex);
+          constexpr int QM = decltype(mode)::value, QT = decltype(tmode)::value, QS = decltype(spec)::value;
+          if constexpr (QM != 0) {
+            if (nrm) {
+              k_pathtrace_queue<QM, QT, QS><<<qgrid, block, dyn_queue, s>>>(c, tex, normals);
+              return;
+            }
+          }
+          k_pathtrace_queue<QM, QT, QS><<<qgrid, block, dyn_queue, s>>>(c, tex);  // (the launch syntax: see `go` above)
         });
       });
     });

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "bvh.hpp"
@@ -123,6 +124,56 @@ using spec_lights_t = std::conditional_t<spec_power(SPEC), LightTableView, std::
 template <int SPEC, class... LV>
 constexpr bool spec_takes() {
   return sizeof...(LV) == (spec_lights(SPEC) ? 1u : 0u) && (std::is_same<LV, spec_lights_t<SPEC>>::value && ...);
+}
+
+// Smooth shading (rtpt_scene_set_normals; shading_normal.hpp states the two arrays and the rules): the corner normals of the BASE
+// mesh and the cofactor matrix of every instance's pose.  It travels as the LAST parameter of the tracing kernels that shade with
+// it, behind TexView and the light argument, and of those instantiations only — TexView's reason: inside SceneView it would move
+// every later argument offset and change every existing kernel.  THE NRM AXIS of shade_segment and the tracing kernels is whether
+// an instantiation's trailing parameter pack ends in a NormalView (pack_nrm): the instantiations without one keep their names,
+// their argument segments and their code.  Instantiated where a scene with normals can be launched: the BVH scene modes (such a
+// scene is traced through its tree), the fused launch and the unfused compacting one, the queue kernels; no
+// RTPT_FLAG_NO_PATH_COMPACTION form, no brute-force form.
+struct NormalView {
+  const float4* records;  // 3 per base triangle
+  const float4* cof;      // 3 per instance
+};
+template <class... P>
+struct pack_last {
+  using type = void;
+};
+template <class A>
+struct pack_last<A> {
+  using type = A;
+};
+template <class A, class B, class... P>
+struct pack_last<A, B, P...> {
+  using type = typename pack_last<B, P...>::type;
+};
+template <class... P>
+constexpr bool pack_nrm() {
+  return std::is_same<typename pack_last<P...>::type, NormalView>::value;
+}
+// a tracing kernel's pack: the light argument of its SPEC (spec_takes), then a NormalView or nothing
+template <int SPEC, class... P>
+constexpr bool pack_takes() {
+  if constexpr (sizeof...(P) == 0) return !spec_lights(SPEC);
+  else if constexpr (sizeof...(P) == 1) return spec_takes<SPEC, P...>() || (!spec_lights(SPEC) && pack_nrm<P...>());
+  else if constexpr (sizeof...(P) == 2) return spec_lights(SPEC) && pack_nrm<P...>() && std::is_same<std::tuple_element_t<0, std::tuple<P...>>, spec_lights_t<SPEC>>::value;
+  else return false;
+}
+// the first and the last argument of a pack
+template <class A, class... P>
+constexpr const A& pack_first(const A& a, const P&...) {
+  return a;
+}
+template <class A>
+constexpr const A& pack_back(const A& a) {
+  return a;
+}
+template <class A, class B, class... P>
+constexpr const auto& pack_back(const A&, const B& b, const P&... p) {
+  return pack_back(b, p...);
 }
 
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
@@ -359,6 +410,10 @@ struct RefitArgs {
   float* grid;                 // 8 floats: origin xyz, cell xyz, pad, 0
 };
 void launch_pose(uint32_t n_verts, const float* src, float* dst, const RefitModel& m, hipStream_t s);
+// the cofactor table of smooth shading (shading_normal.hpp: cof_rows; NormalView::cof), three float4 per instance, from the model
+// and the instance transforms as they stand on the stream (xf: n_instances x 12 floats on the device, or NULL: one instance, the
+// model's own linear part); no synchronisation
+void launch_normal_cof(uint32_t n_instances, const float* xf, const RefitModel& m, float4* cof, hipStream_t s);
 // level_first[h] .. level_first[h + 1]: the slice of `order` holding the nodes of height h (n_levels + 1 entries)
 void launch_refit(const RefitArgs& a, const uint32_t* level_first, int n_levels, uint32_t n_nodes, float pad_rel, hipStream_t s);
 // device-side flatten + fan-pair test (scene_flatten.hip): mesh x instance transforms -> the un-posed triangles
@@ -406,6 +461,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // lights: the light list in its host form, handed to a kernel as spec_lights_t<SPEC> says: not at all, as a LightView (its first
 // two fields) or whole.  It has entries where the launch samples the list's triangles (with spec_sphere alone it may be empty),
 // and a table (cdf) where it picks by weight (spec_power).
+// normals: the scene's vertex normals (rtpt_scene_set_normals), records NULL without: with them the scene traces through its BVH, the
+// unfused launch compacts, and the launch carries no final pass.
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -415,7 +472,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
                       const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr,
-                      const LightTableView& lights = LightTableView{nullptr, 0u, nullptr});
+                      const LightTableView& lights = LightTableView{nullptr, 0u, nullptr},
+                      const NormalView& normals = NormalView{nullptr, nullptr});
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
@@ -503,6 +561,9 @@ void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, 
 // light::hit_weight, light::mis_bounce and light::mis_light (light_sample.hpp: RTPT_FLAG_EXT_NEE_MIS) on n cases of 20 words (v0, v1,
 // v2, o, d, b1, b2, cb, inv_p, one word not read): out = n x (g_hit, wb(g_hit), g_hit * m(g_hit))
 void launch_selftest_mis_weight(const float* in, float* out, size_t n, hipStream_t s);
+// shading_normal.hpp's rules and side tests on n cases of 36 words (n0, n1, n2, b1, b2, the cof rows, ng, d, d', wd, ray_offset, three
+// words not read): out = n x (smooth as 1.0f / 0.0f, ns, absorbed, sample_side, the dielectric's offset, 0)
+void launch_selftest_shading_normal(const float* in, float* out, size_t n, hipStream_t s);
 // rtpt_light::find (light_list_host.hpp) of k queries on the ascending list ids[0, n): index_out[j], n where the id is not in it
 void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out, hipStream_t s);
 

@@ -33,14 +33,18 @@ struct Triangle {
   uint32_t v[3];      // resolved vertex indices (0-based), in range unless bad_vertex_index
   float uv[6];        // u0 v0 u1 v1 u2 v2; a corner without a usable vt is (0, 0)
   uint32_t material;  // index into Obj::materials, 0 without a usable `usemtl`
+  float n[9];         // the corners' vn records; all 0 unless smooth
+  uint32_t smooth;    // 1: every corner of the triangle's FACE names a vn record that exists (rtpt_util_load_obj_normals)
 };
 
 struct Obj {
   std::vector<float> v;   // 3 floats per `v` record
   std::vector<float> vt;  // 2 floats per `vt` record
+  std::vector<float> vn;  // 3 floats per `vn` record
   std::vector<Triangle> tris;  // polygons fanned (0, k, k + 1) in file order (D5)
   // recorded, not refused: each matters to one loader only
   bool bad_vertex_index = false, bad_texcoord_index = false;
+  bool bad_normal_index = false;  // (no loader refuses it: the face is not smooth)
   bool any_library = false;  // some `mtllib` of the OBJ could be read
   std::vector<Material> materials;
 };
@@ -138,6 +142,8 @@ inline int parse(const char* path, Obj* o, std::string* err) {
   struct Corner {
     uint32_t v;
     float uv[2];
+    bool has_n;
+    float n[3];
   };
   std::vector<Corner> poly;
   uint32_t cur_mat = 0;
@@ -164,6 +170,16 @@ inline int parse(const char* path, Obj* o, std::string* err) {
       if (end == q) v = 0.0f;  // `vt u` is legal: v defaults to 0
       o->vt.push_back(u);
       o->vt.push_back(v);
+    } else if ((q = after_keyword(p, "vn"))) {
+      char* end = nullptr;
+      float v[3];
+      bool ok = true;
+      for (int k = 0; k < 3; k++) {
+        v[k] = std::strtof(q, &end);
+        if (end == q) ok = false;
+        q = end;
+      }
+      if (ok) o->vn.insert(o->vn.end(), v, v + 3);  // a `vn` with fewer than three numbers takes no index, like such a `v`
     } else if ((q = after_keyword(p, "mtllib"))) {
       if (FILE* mf = std::fopen((dir + word(q)).c_str(), "r")) {
         o->any_library = true;
@@ -186,7 +202,7 @@ inline int parse(const char* path, Obj* o, std::string* err) {
         if (end == q) break;
         const long rv = resolve_index(vi, o->v.size() / 3);
         if (rv < 0 || rv >= static_cast<long>(o->v.size() / 3)) o->bad_vertex_index = true;
-        Corner c{static_cast<uint32_t>(rv), {0.0f, 0.0f}};
+        Corner c{static_cast<uint32_t>(rv), {0.0f, 0.0f}, false, {0.0f, 0.0f, 0.0f}};
         q = end;
         // the vt number follows the slash at once (strtol would skip a blank and take the next corner's vertex number)
         if (*q == '/' && (q[1] == '-' || q[1] == '+' || (q[1] >= '0' && q[1] <= '9'))) {
@@ -202,9 +218,26 @@ inline int parse(const char* path, Obj* o, std::string* err) {
             q = end;
           }
         }
+        // the vn number follows the corner's second slash at once: `v/vt/vn` (q stands behind the vt), `v//vn`
+        const char* sl = (*q == '/' && q[1] == '/') ? q + 1 : q;
+        if (*sl == '/' && (sl[1] == '-' || sl[1] == '+' || (sl[1] >= '0' && sl[1] <= '9'))) {
+          const long ni = std::strtol(sl + 1, &end, 10);
+          if (end != sl + 1) {
+            const long rn = resolve_index(ni, o->vn.size() / 3);
+            if (rn < 0 || rn >= static_cast<long>(o->vn.size() / 3)) {
+              o->bad_normal_index = true;
+            } else {
+              c.has_n = true;
+              std::memcpy(c.n, o->vn.data() + 3 * static_cast<size_t>(rn), sizeof c.n);
+            }
+            q = end;
+          }
+        }
         poly.push_back(c);
-        while (!at_end(q) && !blank(*q)) q++;  // the rest of the corner ("/vn")
+        while (!at_end(q) && !blank(*q)) q++;  // the rest of the corner
       }
+      bool face_smooth = true;  // every corner of the face has its vn
+      for (const Corner& c : poly) face_smooth = face_smooth && c.has_n;
       for (size_t k = 1; k + 1 < poly.size(); k++) {
         const Corner* c[3] = {&poly[0], &poly[k], &poly[k + 1]};
         Triangle t;
@@ -212,7 +245,9 @@ inline int parse(const char* path, Obj* o, std::string* err) {
           t.v[j] = c[j]->v;
           t.uv[2 * j] = c[j]->uv[0];
           t.uv[2 * j + 1] = c[j]->uv[1];
+          for (int a = 0; a < 3; a++) t.n[3 * j + a] = face_smooth ? c[j]->n[a] : 0.0f;
         }
+        t.smooth = face_smooth ? 1u : 0u;
         t.material = cur_mat;
         o->tris.push_back(t);
       }
@@ -230,6 +265,12 @@ inline void copy_indices(const Obj& o, uint32_t* idx) {
 }
 inline void copy_tri_uv(const Obj& o, float* tri_uv) {
   for (size_t t = 0; t < o.tris.size(); t++) std::memcpy(tri_uv + 6 * t, o.tris[t].uv, sizeof o.tris[t].uv);
+}
+inline void copy_tri_normals(const Obj& o, float* tri_normals, uint32_t* tri_smooth) {  // tri_smooth may be NULL
+  for (size_t t = 0; t < o.tris.size(); t++) {
+    std::memcpy(tri_normals + 9 * t, o.tris[t].n, sizeof o.tris[t].n);
+    if (tri_smooth) tri_smooth[t] = o.tris[t].smooth;
+  }
 }
 inline void copy_tri_material(const Obj& o, uint32_t* tri_material) {
   for (size_t t = 0; t < o.tris.size(); t++) tri_material[t] = o.tris[t].material;

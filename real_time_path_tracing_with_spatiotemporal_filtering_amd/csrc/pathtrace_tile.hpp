@@ -117,7 +117,8 @@ __device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
 template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0, class... LV>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
                                                const uint32_t role_gy = 0, const LV&... lights) {
-  static_assert(spec_takes<SPEC, LV...>(), "an instantiation takes the light argument of its SPEC, spec_lights_t<SPEC>");
+  static_assert(pack_takes<SPEC, LV...>(), "an instantiation takes the light argument of its SPEC, spec_lights_t<SPEC>, then a NormalView or nothing");
+  constexpr bool NRM = pack_nrm<LV...>();  // kernels.hpp: the NRM axis; the pack's last argument is then the scene's NormalView
   // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -231,7 +232,14 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if constexpr (spec_lights(SPEC)) nee.valid = false;
         if constexpr (spec_sphere(SPEC)) nee.sphere_valid = false;
         bool done;
-        if constexpr (spec_lights(SPEC))
+        if constexpr (NRM && spec_lights(SPEC))
+          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs<spec_lights_t<SPEC>>, NormalView>(
+              a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
+              NeeArgs<spec_lights_t<SPEC>>{pack_first(lights...), &nee}, pack_back(lights...));
+        else if constexpr (NRM)
+          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NoNee, NormalView>(a, h, seg, light_c, o, d, acc, rng, tex,
+                                                                             (DEMOD && seg == 0) ? a.albedo + gi : nullptr, NoNee{}, pack_back(lights...));
+        else if constexpr (spec_lights(SPEC))
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs<spec_lights_t<SPEC>>>(a, h, seg, light_c, o, d, acc, rng, tex,
                                                                                         (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
                                                                                         NeeArgs<spec_lights_t<SPEC>>{lights..., &nee});

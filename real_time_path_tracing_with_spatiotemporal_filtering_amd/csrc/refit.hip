@@ -12,6 +12,7 @@
 // device refit need not — and does not try to — reproduce the host refit's boxes bit for bit; it keeps their guarantees.
 #include "bvh.hpp"
 #include "device_common.hpp"
+#include "shading_normal.hpp"
 
 namespace rt {
 namespace {
@@ -32,6 +33,18 @@ __global__ void k_pose(uint32_t n_verts, const float* __restrict__ src, float* _
     o[1] = exact::mat_row_point(m.m, 1, p);
     o[2] = exact::mat_row_point(m.m, 2, p);
   }
+}
+
+// smooth shading: the cofactor matrix of every instance's pose (shading_normal.hpp: cof_rows — the host route calls the same
+// function), one instance per thread.  xf NULL: the scene has no transforms, n_instances is 1
+__global__ void k_normal_cof(uint32_t n_instances, const float* __restrict__ xf, float4* __restrict__ cof, RefitModel m) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_instances) return;
+  float x[12], r[12];
+  if (xf)
+    for (int k = 0; k < 12; k++) x[k] = xf[12 * static_cast<size_t>(i) + k];
+  nrm::cof_rows(m.m, xf ? x : nullptr, r);
+  for (int k = 0; k < 3; k++) cof[3 * static_cast<size_t>(i) + k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
 }
 
 __device__ __forceinline__ void box_reset(float* mn, float* mx) {
@@ -141,6 +154,11 @@ __global__ void k_refit_quantise(RefitArgs a, uint32_t n_nodes) {
 void launch_pose(uint32_t n_verts, const float* src, float* dst, const RefitModel& m, hipStream_t s) {
   if (!n_verts) return;
   hipLaunchKernelGGL(k_pose, dim3((n_verts + 255) / 256), dim3(256), 0, s, n_verts, src, dst, m);
+}
+
+void launch_normal_cof(uint32_t n_instances, const float* xf, const RefitModel& m, float4* cof, hipStream_t s) {
+  if (!n_instances) return;
+  hipLaunchKernelGGL(k_normal_cof, dim3((n_instances + 255) / 256), dim3(256), 0, s, n_instances, xf, cof, m);
 }
 
 void launch_refit(const RefitArgs& a, const uint32_t* level_first, int n_levels, uint32_t n_nodes, float pad_rel, hipStream_t s) {

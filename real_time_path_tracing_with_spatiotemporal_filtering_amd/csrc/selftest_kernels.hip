@@ -265,6 +265,31 @@ __global__ void k_selftest_mis_weight(const float* in, float* out, size_t n) {
   out[3 * i + 2] = g * light::mis_light(g);
 }
 
+// shading_normal.hpp's rules 1 to 7 and its three side tests, one case per thread, by the functions shade_segment calls: in = 36 words,
+// n0, n1, n2, (b1, b2), the three cof rows, ng, d, d', wd, ray_offset (33 floats; words 33 to 35 are not read); out = 8 words: smooth as
+// 1.0f / 0.0f, ns (ng where the hit is not smooth), absorbed(d') and sample_side(wd) as 1.0f / 0.0f, the dielectric's offset, 0.
+// b0 as hit_barycentrics forms it (rtpt_selftest_shading_normal)
+__global__ void k_selftest_shading_normal(const float* in, float* out, size_t n) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* w = in + 36 * i;
+  const float b1 = w[9], b2 = w[10];
+  const float b0 = 1.0f - b1 - b2;
+  const f3 ng = ld3(w + 20), d = ld3(w + 23);
+  f3 ns;
+  const bool smooth = nrm::interpolate(ld3(w), ld3(w + 3), ld3(w + 6), b0, b1, b2, ld3(w + 11), ld3(w + 14), ld3(w + 17), &ns);
+  ns = smooth ? nrm::orient(ns, ng, d) : ng;
+  float* r = out + 8 * i;
+  r[0] = smooth ? 1.0f : 0.0f;
+  r[1] = ns.x;
+  r[2] = ns.y;
+  r[3] = ns.z;
+  r[4] = nrm::absorbed(ld3(w + 26), ng) ? 1.0f : 0.0f;
+  r[5] = nrm::sample_side(ld3(w + 29), ng) ? 1.0f : 0.0f;
+  r[6] = nrm::dielectric_offset(ld3(w + 26), ng, w[32]);
+  r[7] = 0.0f;
+}
+
 // rtpt_light::find (light_list_host.hpp) of k queries on the ascending list ids[0, n): the entry's index, n where the list does not
 // hold the id (rtpt_selftest_light_find)
 __global__ void k_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out) {
@@ -367,6 +392,10 @@ void launch_selftest_sphere_sample(const uint32_t* in, uint32_t* out, size_t n, 
 void launch_selftest_mis_weight(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_mis_weight, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_shading_normal(const float* in, float* out, size_t n, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_shading_normal, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
 }
 void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out, hipStream_t s) {
   if (!k) return;

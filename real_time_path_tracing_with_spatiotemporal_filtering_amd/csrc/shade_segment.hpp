@@ -7,6 +7,7 @@
 #include "closest_hit.hpp"
 #include "dielectric.hpp"
 #include "light_sample.hpp"
+#include "shading_normal.hpp"
 #include "specular.hpp"
 
 #include <type_traits>
@@ -148,12 +149,36 @@ struct NeeArgs {
   NeeState* st;
 };
 struct NoNee {};
-template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE = NoNee>
+// NRM (NV = NormalView; every other instantiation takes NoNormals there, nothing, and is the instantiation before the axis, statement
+// for statement): the scene has vertex normals (rtpt_scene_set_normals; shading_normal.hpp states the rules).  A hit on a triangle
+// whose record is smooth bounces, refracts and samples lights about the interpolated normal ns; the offset origin and everything
+// above the bounce keep the geometric normal.  These instantiations return early on every last segment, like the specular ones.
+struct NoNormals {};
+// the hit's ns by rules 1 to 7, from the records of base triangle (id1 - 1) % n_base and the matrix of instance (id1 - 1) / n_base;
+// false (ns = ng) where the hit is not smooth.  The matrix is loaded only behind a smooth record.
+__device__ __forceinline__ bool hit_shading_normal(const NormalView& nv, uint32_t id1, uint32_t n_base, float b0, float b1, float b2, f3 ng, f3 d,
+                                                   f3* ns) {
+  *ns = ng;
+  const uint32_t t = (id1 - 1) % n_base, i = (id1 - 1) / n_base;
+  const float4* r = nv.records + 3 * static_cast<size_t>(t);
+  const float4 r0 = r[0];
+  if (__float_as_uint(r0.w) == 0u) return false;
+  const float4 r1 = r[1], r2 = r[2];
+  const float4* c = nv.cof + 3 * static_cast<size_t>(i);
+  const float4 c0 = c[0], c1 = c[1], c2 = c[2];
+  f3 n;
+  if (!nrm::interpolate(xyz(r0), xyz(r1), xyz(r2), b0, b1, b2, xyz(c0), xyz(c1), xyz(c2), &n)) return false;
+  *ns = nrm::orient(n, ng, d);
+  return true;
+}
+template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE = NoNee, class NV = NoNormals>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr,
-                                              [[maybe_unused]] NEE nee_args = NEE{}) {
+                                              [[maybe_unused]] NEE nee_args = NEE{}, [[maybe_unused]] NV normals = NV{}) {
   static_assert(std::is_same<NEE, std::conditional_t<spec_lights(SPEC), NeeArgs<spec_lights_t<SPEC>>, NoNee>>::value,
                 "the instantiations that sample lights, and only they, take NeeArgs, with the list their SPEC asks for");
+  constexpr bool NRM = std::is_same<NV, NormalView>::value;
+  static_assert(NRM || std::is_same<NV, NoNormals>::value, "NormalView or nothing");
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
     if constexpr (spec_sphere(SPEC)) {
@@ -169,7 +194,7 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
   float4 s0 = s[0], s1 = s[1], s2 = s[2];
-  const bool last = (RTPT_TRACE_ITEMS & 1) && (spec_material(SPEC) != 0 || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
+  const bool last = (RTPT_TRACE_ITEMS & 1) && (spec_material(SPEC) != 0 || NRM || (!(BVH == 2 && TEX == 0) && !alb_px)) && seg + 1 >= a.max_segments;  // block-uniform
   float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
   f3 pos{0.f, 0.f, 0.f};
   if (!last) {
@@ -255,6 +280,15 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       exact::rng_skip(rng);                                        // :257 (drawn, unused)
       bool transmitted;
       float fresnel;
+      if constexpr (NRM) {
+        f3 ns;
+        const bool smooth = hit_shading_normal(normals, h.id1, a.scene.n_base_tris, b0, b1, b2, n, d, &ns);
+        d = diel::interface(ns, entering, d, u1, spec_w, diel_inv, diel_r0, &transmitted, &fresnel);
+        float off = transmitted ? -a.ray_offset : a.ray_offset;
+        if (smooth) off = nrm::dielectric_offset(d, n, a.ray_offset);
+        o = f3{fmaf_(off, n.x, pos.x), fmaf_(off, n.y, pos.y), fmaf_(off, n.z, pos.z)};
+        return seg + 1 >= a.max_segments;
+      }
       d = diel::interface(n, entering, d, u1, spec_w, diel_inv, diel_r0, &transmitted, &fresnel);
       const float off = transmitted ? -a.ray_offset : a.ray_offset;
       o = f3{fmaf_(off, n.x, pos.x), fmaf_(off, n.y, pos.y), fmaf_(off, n.z, pos.z)};
@@ -263,6 +297,10 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
   }
   if (!(exact::dot(n, d) < 0.0f)) n = -n;                          // :247 faceforward
   o = f3{fmaf_(a.ray_offset, n.x, pos.x), fmaf_(a.ray_offset, n.y, pos.y), fmaf_(a.ray_offset, n.z, pos.z)};  // :250
+  // NRM: from here on n is the shading normal ns and ng the geometric one (shading_normal.hpp); without the axis both names are gone
+  [[maybe_unused]] f3 ng = n;
+  [[maybe_unused]] bool smooth = false;
+  if constexpr (NRM) smooth = hit_shading_normal(normals, h.id1, a.scene.n_base_tris, b0, b1, b2, ng, d, &n);
   if constexpr (spec_lights(SPEC)) {
     // next-event estimation (light_sample.hpp): o is the sample's x, n its nf, acc its T
     const spec_lights_t<SPEC> lights = nee_args.lights;
@@ -296,6 +334,9 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
         nee->c = f3{(acc.x * ke.x) * g, (acc.y * ke.y) * g, (acc.z * ke.z) * g};  // two roundings a channel, in this order
         nee->id1 = id1;
         nee->valid = sm.valid;
+        if constexpr (NRM) {
+          if (smooth) nee->valid = sm.valid && nrm::sample_side(sm.wd, ng);
+        }
         nee->sampled = true;
       }
       if constexpr (spec_sphere(SPEC)) {  // the sphere sample: light_c, a.light_r2 and a.light_col are ray_hits_light's light
@@ -305,6 +346,9 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
         const f3 lc = ld3(a.light_col);
         nee->sphere_c = f3{(acc.x * lc.x) * ss.g, (acc.y * lc.y) * ss.g, (acc.z * lc.z) * ss.g};
         nee->sphere_valid = ss.valid;
+        if constexpr (NRM) {
+          if (smooth) nee->sphere_valid = ss.valid && nrm::sample_side(ss.wd, ng);
+        }
         nee->sphere = ss.taken;
       }
     } else if (!diffuse) {
@@ -321,12 +365,23 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
       bool absorbed;
       d = spec::lobe(n, d, r, ct, st_, u, spec::roughness(spec_w), &absorbed);
       if (seg + 1 >= a.max_segments) return true;  // (only builds without the early return get here)
+      if constexpr (NRM) {
+        if (smooth && nrm::absorbed(d, ng)) absorbed = true;
+      }
       if (absorbed) acc = f3{0.f, 0.f, 0.f};
       return absorbed;
     }
   }
   d = exact::normalize(f3{fmaf_(r, ct, n.x), fmaf_(r, st_, n.y), n.z + u});  // :259-261
   if constexpr (spec_mis(SPEC)) nee_args.st->cb = exact::dot(n, d);  // (a last segment returned above: this hit took the triangle draw)
+  if constexpr (NRM) {
+    if (seg + 1 >= a.max_segments) return true;  // (only builds without the early return get here)
+    if (smooth && nrm::absorbed(d, ng)) {
+      acc = f3{0.f, 0.f, 0.f};
+      return true;
+    }
+    return false;
+  }
   return seg + 1 >= a.max_segments;  // budget exhausted: the path returns its throughput (:270)
 }
 

@@ -73,23 +73,49 @@ static void check_file(const std::string& path) {
   std::vector<float> uv1(6 * static_cast<size_t>(n0), -1.0f);
   CHECK(rtpt_tex::load_obj_texcoords(path.c_str(), uv1.data(), &n1, &err) == (o.bad_texcoord_index ? -1 : 0) && n1 == nt);
   CHECK(uv1.empty() || !std::memcmp(uv1.data(), uv.data(), uv.size() * sizeof(float)));
+  // the vn projection (rtpt_util_load_obj_normals): a smooth triangle's corners are vn records of the file bit for bit, any other is 0
+  CHECK(o.vn.size() % 3 == 0);
+  std::vector<float> nrm(static_cast<size_t>(nt) * 9, -1.0f);
+  std::vector<uint32_t> smooth(nt, 7u);
+  if (nt) rtpt_obj::copy_tri_normals(o, nrm.data(), smooth.data());
+  if (nt) rtpt_obj::copy_tri_normals(o, nrm.data(), nullptr);
+  uint32_t n_smooth = 0;
+  for (uint32_t t = 0; t < nt; t++) {
+    CHECK(smooth[t] <= 1u);
+    n_smooth += smooth[t];
+    for (int k = 0; k < 3; k++) {
+      const float* c = nrm.data() + 9 * static_cast<size_t>(t) + 3 * k;
+      bool found = !smooth[t];
+      if (!smooth[t]) {
+        const float zero[3] = {0.0f, 0.0f, 0.0f};
+        CHECK(!std::memcmp(c, zero, sizeof zero));
+      }
+      for (size_t r = 0; !found && r < o.vn.size() / 3; r++) found = !std::memcmp(c, o.vn.data() + 3 * r, 12);
+      CHECK(found);
+    }
+  }
+  CHECK(!o.vn.empty() || n_smooth == 0);
+
   std::vector<std::string> maps{"stale"};
   CHECK(rtpt_tex::load_obj_map_kd(path.c_str(), &maps, &err) == 0);
   CHECK(maps.size() == (o.any_library ? o.materials.size() : 0));
 
-  std::printf("obj_host_check: %s %u vertices, %u triangles, %zu materials%s%s%s\n", std::filesystem::path(path).filename().c_str(), nv, nt,
-              o.materials.size(), o.any_library ? "" : ", no library", o.bad_vertex_index ? ", bad vertex index" : "",
-              o.bad_texcoord_index ? ", bad texcoord index" : "");
+  std::printf("obj_host_check: %s %u vertices, %u triangles (%u smooth), %zu materials%s%s%s%s\n", std::filesystem::path(path).filename().c_str(), nv, nt,
+              n_smooth, o.materials.size(), o.any_library ? "" : ", no library", o.bad_vertex_index ? ", bad vertex index" : "",
+              o.bad_texcoord_index ? ", bad texcoord index" : "", o.bad_normal_index ? ", bad normal index" : "");
 }
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: obj_host_check <corpus directory> <scratch directory>\n");
+    std::fprintf(stderr, "usage: obj_host_check <corpus directory> <scratch directory> [<second corpus directory>]\n");
     return 2;
   }
   std::vector<std::string> files;
   for (const auto& e : std::filesystem::directory_iterator(argv[1]))
     if (e.path().extension() == ".obj") files.push_back(e.path().string());
+  if (argc > 3)  // the hostile vn files (tests/golden/obj_normals)
+    for (const auto& e : std::filesystem::directory_iterator(argv[3]))
+      if (e.path().extension() == ".obj") files.push_back(e.path().string());
   std::sort(files.begin(), files.end());
   CHECK(!files.empty());
 
@@ -107,7 +133,14 @@ int main(int argc, char** argv) {
   }
   write_file(dir + "/three_hundred_materials.mtl", mtl);
   write_file(dir + "/three_hundred_materials.obj", faces);
-  for (const char* name : {"empty.obj", "one_long_line.obj", "thousand_corners.obj", "three_hundred_materials.obj"}) files.push_back(dir + "/" + name);
+  // vn extremes: a fan whose every corner names a normal by a negative index; slashes with nothing behind them; numbers no long holds
+  std::string nfan = "v 0 0 0\nv 1 0 0\nv 0 1 0\nvn 0 0 1\nvn 0 1 0\nf";
+  for (int i = 0; i < 300; i++) nfan += " " + std::to_string(1 + i % 3) + "//-" + std::to_string(1 + i % 2);
+  write_file(dir + "/normal_fan.obj", nfan + "\n");
+  write_file(dir + "/normal_slashes.obj", "v 0 0 0\nv 1 0 0\nv 0 1 0\nvn 1 2 3\nvn\nvn 1\nf 1/ 2// 3///\nf 1//1 2//+1 3//-1\nf 1//99999999999999999999 2//1 3//1\n"
+                                           "f 1//-99999999999999999999 2//1 3//1\nf 1/1/1 2/1/1 3/1/1\nf 1//1x 2//1 3//1 /1\n");
+  for (const char* name : {"empty.obj", "one_long_line.obj", "thousand_corners.obj", "three_hundred_materials.obj", "normal_fan.obj", "normal_slashes.obj"})
+    files.push_back(dir + "/" + name);
 
   for (const std::string& f : files) check_file(f);
 
@@ -119,6 +152,13 @@ int main(int argc, char** argv) {
   CHECK(o.materials.size() == 301 && rtpt_obj::n_tris(o) == 300 && o.tris[299].material == 300 && o.materials[300].map_kd == "t299.ppm");
   CHECK(rtpt_obj::parse((dir + "/empty.obj").c_str(), &o, &err) == 0 && o.v.empty() && o.tris.empty() && !o.any_library);
   CHECK(rtpt_obj::parse((dir + "/no_such_file.obj").c_str(), &o, &err) == -1 && err == "cannot open " + dir + "/no_such_file.obj");
+  CHECK(rtpt_obj::parse((dir + "/normal_fan.obj").c_str(), &o, &err) == 0);
+  CHECK(rtpt_obj::n_tris(o) == 298 && o.tris[0].smooth == 1 && o.tris[297].smooth == 1 && !o.bad_normal_index);
+  CHECK(o.tris[0].n[2] == 0.0f && o.tris[0].n[1] == 1.0f && o.tris[0].n[5] == 1.0f);  // corner 0: -1 = the last vn, corner 1: -2 = the first
+  CHECK(rtpt_obj::parse((dir + "/normal_slashes.obj").c_str(), &o, &err) == 0);
+  CHECK(o.vn.size() == 3 && rtpt_obj::n_tris(o) == 6 && o.bad_normal_index);
+  CHECK(!o.tris[0].smooth && o.tris[1].smooth && !o.tris[2].smooth && !o.tris[3].smooth && o.tris[4].smooth && o.tris[5].smooth);
+  CHECK(o.tris[1].n[0] == 1.0f && o.tris[1].n[4] == 2.0f && o.tris[1].n[8] == 3.0f);
   std::puts("obj_host_check: ok");
   return 0;
 }

@@ -75,6 +75,21 @@ void PathTracingApplication::loadMesh() {
                                                                                                  objMaterialsExt.data(), &nm),
           "loadMesh");
   }
+  triNormals.clear();
+  triSmooth.clear();
+  if (opt_.smooth_normals) {
+    if (opt_.tessellate > 1) throw std::runtime_error("--tessellate does not carry vertex normals over");
+    uint32_t nn = 0;
+    check(rtpt_util_load_obj_normals(opt_.scene.c_str(), nullptr, nullptr, &nn), "loadMesh");
+    if (nn == nt) {
+      triNormals.resize(static_cast<size_t>(nn) * 9);
+      triSmooth.resize(nn);
+      check(rtpt_util_load_obj_normals(opt_.scene.c_str(), triNormals.data(), triSmooth.data(), &nn), "loadMesh");
+      bool any = false;
+      for (uint32_t s : triSmooth) any = any || s != 0;
+      if (!any) triNormals.clear(), triSmooth.clear();  // no vn in the file: nothing to set
+    }
+  }
   // configs[4]: tessellated quads on a lattice of instances (scene_gen.hpp); camera, light and far plane frame the lattice
   sceneTextures_ = SceneTextures{};
   if (opt_.textures) {
@@ -187,6 +202,8 @@ void PathTracingApplication::buildAccelerationStructure() {
   // world-space bounds of the scene: strips bound the reprojection reach with them (strips.hpp)
   sceneBounds();
   auto materials = [&](rtpt_ctx* ctx) {
+    if (!triSmooth.empty())
+      check(rtpt_scene_set_normals(ctx, triNormals.data(), triSmooth.data(), static_cast<uint32_t>(triSmooth.size())), "rtpt_scene_set_normals");
     if (!objMaterialsExt.empty())
       check(rtpt_scene_set_materials_ext(ctx, triMaterial.data(), static_cast<uint32_t>(triMaterial.size()), objMaterialsExt.data(),
                                          static_cast<uint32_t>(objMaterialsExt.size())),

@@ -40,6 +40,35 @@ def tessellate_quads(xyz: np.ndarray, idx: np.ndarray, n: int):
     return np.concatenate(verts).astype(np.float32), np.array(tris, np.uint32)
 
 
+def uv_sphere(n_lat: int, n_lon: int, radius: float = 1.0, centre=(0.0, 0.0, 0.0)):
+    """(xyz [v, 3] f32, idx [t, 3] u32, tri_normals [t, 9] f32) of a latitude / longitude sphere: n_lat bands from the north
+    pole (+y) to the south pole, n_lon sectors, wound counter-clockwise seen from outside.  The two polar bands are single
+    triangles, every other cell is a fan pair (a, b, c), (a, c, d): 2 n_lon (n_lat - 1) triangles, 2 + (n_lat - 1) n_lon
+    vertices.  tri_normals are the EXACT vertex normals (position - centre) / radius of each triangle's corners, rounded once to
+    binary32 from float64 — what rtpt_scene_set_normals takes; the project's curved test and demo mesh."""
+    assert n_lat >= 2 and n_lon >= 3
+    lat = np.pi * np.arange(1, n_lat, dtype=np.float64) / n_lat           # the rings between the poles
+    lon = 2.0 * np.pi * np.arange(n_lon, dtype=np.float64) / n_lon
+    ring = np.stack([np.sin(lat)[:, None] * np.cos(lon)[None, :], np.repeat(np.cos(lat)[:, None], n_lon, 1),
+                     -np.sin(lat)[:, None] * np.sin(lon)[None, :]], -1).reshape(-1, 3)
+    unit = np.concatenate([[[0.0, 1.0, 0.0]], ring, [[0.0, -1.0, 0.0]]])
+    north, south = 0, len(unit) - 1
+    at = lambda r, s: 1 + r * n_lon + (s % n_lon)
+    tris = []
+    for s in range(n_lon):
+        tris.append((north, at(0, s), at(0, s + 1)))
+    for r in range(n_lat - 2):
+        for s in range(n_lon):
+            a, b, c, d = at(r, s), at(r + 1, s), at(r + 1, s + 1), at(r, s + 1)
+            tris.append((a, b, c))
+            tris.append((a, c, d))
+    for s in range(n_lon):
+        tris.append((south, at(n_lat - 2, s + 1), at(n_lat - 2, s)))
+    idx = np.array(tris, np.uint32)
+    xyz = (unit * float(radius) + np.asarray(centre, np.float64)).astype(np.float32)
+    return xyz, idx, unit.astype(np.float32)[idx].reshape(-1, 9)
+
+
 def lattice_xforms(nx: int, ny: int, nz: int, pitch: float = 2.5) -> np.ndarray:
     """nx*ny*nz translations (3x4 row-major), lattice centred on x and z, resting on y = 0, the
     nearest layer's front face staying near z = +1 like the single box."""
