@@ -1,5 +1,5 @@
-"""Operands, scenes, the numpy restatement of the dielectric interface (csrc/dielectric.hpp) and a numpy float32 path walker for
-test_dielectric_*.py.
+"""Operands, scenes, material records, the contract functions on arrays and the numpy restatement of the dielectric interface
+(csrc/dielectric.hpp) for test_dielectric_*.py; the path walker that uses them is tests/path_walker.py.
 
 refract32 follows the arithmetic as dielectric.hpp states it, one float32 operation per device operation: dot and normalize
 through the oracle's statement of the numerics contract (oracle.contract_array), every fused multiply-add through the contract's
@@ -7,11 +7,9 @@ dot as well (fma below: exact, where texture_scenes.fma32 rounds twice), the squ
 two divisions of the record in numpy float32 (all correctly rounded, like the device's).  refract64 is the same interface in
 float64 libm from the float32 operands as they are.
 
-walk() restates K2 for one sample per pixel, materials and no textures: primary-ray generation and shade_segment (csrc/pathtrace_tile.hpp, csrc/shade_segment.hpp)
-in numpy float32 over the contract functions, with oracle_closest_hit through ctypes for t, b1 and b2 of every ray.  The oracle
-knows no dielectric, so walk() is the reference of the dielectric frames — after tests/test_dielectric_cpu.py has held it to
+_rng_next and _primary are the walker's random stream and primary-ray generation (csrc/pathtrace_tile.hpp).  The oracle knows no
+dielectric, so path_walker.walk is the reference of the dielectric frames — after tests/test_dielectric_cpu.py has held it to
 oracle.raytrace_ext on scenes without one, IMAGE and HIT_ID bit for bit."""
-import ctypes as C
 import os
 from functools import lru_cache
 
@@ -222,55 +220,11 @@ def records(scene, specular=None, dielectric=None):
     return rec[np.asarray(scene.tri_material, np.int64)]
 
 
-# ------------------------------------------------------------------------------------------ the walker
-def _closest_hits(O, tris, o, d, tmax):
-    """oracle_closest_hit per ray: (id [k] uint32, b1 [k], b2 [k])"""
-    lib = O.lib()
-    tris = np.ascontiguousarray(tris, F32)
-    o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
-    k = len(o)
-    ids, b1s, b2s = np.zeros(k, np.uint32), np.zeros(k, F32), np.zeros(k, F32)
-    t, b1, b2 = C.c_float(), C.c_float(), C.c_float()
-    tp, n, tm = C.c_void_p(tris.ctypes.data), C.c_uint32(len(tris)), C.c_float(tmax)
-    ob, db = o.ctypes.data, d.ctypes.data
-    fn = lib.oracle_closest_hit
-    for i in range(k):
-        ids[i] = fn(tp, n, C.c_void_p(ob + 12 * i), C.c_void_p(db + 12 * i), tm, C.byref(t), C.byref(b1), C.byref(b2))
-        if ids[i]:
-            b1s[i], b2s[i] = b1.value, b2.value
-    return ids, b1s, b2s
-
-
+# ------------------------------------------------------------------------------------------ the walker's stream and primary rays
 def _rng_next(O, state):
     """(new state [k] uint32, float [k]) of exact::rng_next"""
     w = O.contract_array(CC.fn_index("rng_next_skip"), np.ascontiguousarray(state, np.uint32).reshape(-1, 1))
     return w[:, 0].copy(), w[:, 1].copy().view(F32)
-
-
-def walk(O, scene, W, H, segments, rec, frame=0, rows=None, spp=1):
-    """K2 of `scene` with per-triangle records `rec` (records() above; the normal-keyed colours of a scene without a table are not
-    restated): dict of IMAGE [H, W, 4], HIT_ID [H, W] and rays, rows [y0, y1) computed.  spp > 1: every further sample goes on
-    with the pixel's random stream where the one before left it"""
-    cfg = P.configure(O.config_default(W, H), scene, segments, spp)
-    pc = fill_push_constants(O.PushConstants(), P.push_constants(scene), frame)
-    y0, y1 = rows or (0, H)
-    ys, xs = np.meshgrid(np.arange(y0, y1), np.arange(W), indexing="ij")
-    xs, ys = xs.ravel().astype(np.uint32), ys.ravel().astype(np.uint32)
-    k = len(xs)
-    seeds = np.stack([xs, ys, np.full(k, pc.frameNumber, np.uint32), np.full(k, pc.sample_batch, np.uint32)], 1)
-    rng = O.contract_array(CC.fn_index("rng_seed"), np.ascontiguousarray(seeds, np.uint32))[:, 0].copy()     # :297
-    total, rays, first_id = np.zeros((k, 3), F32), 0, None
-    for _ in range(spp):
-        rng, d = _primary(O, cfg, rng, xs, ys)
-        acc, rng, ids, n = _path(O, cfg, pc, scene, np.ascontiguousarray(rec, F32), rng, d)
-        total = (total + acc).astype(F32)                                                                    # :325
-        rays += n
-        first_id = ids if first_id is None else first_id
-    image = np.zeros((H, W, 4), F32)
-    hit_id = np.zeros((H, W), np.uint32)
-    image[y0:y1, :, :3] = (total / F32(spp)).astype(F32).reshape(y1 - y0, W, 3)                              # :328
-    hit_id[y0:y1] = first_id.reshape(y1 - y0, W)
-    return dict(IMAGE=image, HIT_ID=hit_id, rays=rays)
 
 
 def _primary(O, cfg, rng, xs, ys):
@@ -293,7 +247,7 @@ def _primary(O, cfg, rng, xs, ys):
 
 
 def primary_rays(O, scene, W, H, frame=0):
-    """(rng state behind the jitter [H, W] uint32, direction [H, W, 3]) of every pixel's primary ray, as walk() forms them"""
+    """(rng state behind the jitter [H, W] uint32, direction [H, W, 3]) of every pixel's primary ray, as path_walker.walk forms them"""
     cfg = P.configure(O.config_default(W, H), scene, 1, 1)
     pc = fill_push_constants(O.PushConstants(), P.push_constants(scene), frame)
     ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
@@ -308,87 +262,6 @@ def stored_normals(O, tris):
     """[t, 3]: the unit normal the device stores per triangle, normalize(cross(v1 - v0, v2 - v0)) (:150)"""
     tri = np.asarray(tris, F32).reshape(-1, 9)
     return normalize(O, _contract(O, "cross", (tri[:, 3:6] - tri[:, 0:3]).astype(F32), (tri[:, 6:9] - tri[:, 0:3]).astype(F32)))
-
-
-def _path(O, cfg, pc, scene, rec, rng, d):
-    """one sample's paths from the camera along d [k, 3]: (throughput [k, 3], rng state [k], first hit id [k], closest-hit queries)"""
-    tris = np.ascontiguousarray(scene.tris, F32)
-    n_base, segments, k = len(rec), int(cfg.max_segments), len(d)
-    rng = rng.copy()
-    light_c = F32(list(pc.lightPos))
-    light_col = (F32(list(pc.currentCameraColor)) * F32(cfg.light_intensity)).astype(F32)                   # :281
-    light_first = (light_col / F32(cfg.first_hit_light_divisor)).astype(F32)                                 # :229
-    radius, ray_offset, tmax = F32(cfg.light_radius), F32(cfg.ray_offset), float(cfg.ray_tmax)
-    o = np.broadcast_to(F32(scene.cam), (k, 3)).astype(F32).copy()
-    d = d.copy()
-    acc = np.ones((k, 3), F32)
-    alive = np.ones(k, bool)
-    first_id = np.zeros(k, np.uint32)
-    rays = 0
-    for seg in range(segments):
-        idx = np.flatnonzero(alive)
-        if not len(idx):
-            break
-        oo, dd = o[idx], d[idx]
-        ids, b1, b2 = _closest_hits(O, tris, oo, dd, tmax)
-        rays += len(idx)
-        if seg == 0:
-            first_id[idx] = ids
-        lit = O.contract_array(CC.fn_index("ray_hits_light"), np.ascontiguousarray(np.concatenate(
-            [oo, dd, np.broadcast_to(light_c, oo.shape), np.full((len(idx), 1), radius, F32)], 1), F32).view(np.uint32))[:, 0] != 0
-        acc[idx[lit]] = (acc[idx[lit]] * (light_first if seg == 0 else light_col)).astype(F32)       # :229, :233
-        sky = ~lit & (ids == 0)
-        acc[idx[sky]] = (acc[idx[sky]] * _contract(O, "sky_color", dd[sky])).astype(F32)             # :266
-        alive[idx[lit | sky]] = False
-        hit = ~lit & (ids != 0)
-        m = rec[(ids[hit].astype(np.int64) - 1) % n_base]
-        emissive = m[:, 7] != 0
-        j = idx[hit]
-        acc[j[emissive]] = (acc[j[emissive]] * m[emissive, 4:7]).astype(F32)
-        alive[j[emissive]] = False
-        keep = ~emissive
-        j, m = j[keep], m[keep]
-        acc[j] = (acc[j] * m[:, 0:3]).astype(F32)                                                    # :244
-        if seg + 1 >= segments:                       # the path returns its throughput: the bounce would feed nothing but the
-            rng[j] = _rng_next(O, _rng_next(O, rng[j])[0])[0]      # stream, which the pixel's next sample goes on with (:256-257)
-            break
-        tri = tris[ids[hit][keep].astype(np.int64) - 1]
-        b1, b2, dd = b1[hit][keep], b2[hit][keep], dd[hit][keep]
-        b0 = ((F32(1.0) - b1).astype(F32) - b2).astype(F32)                                          # :134
-        pos = fma(O, tri[:, 6:9], b2[:, None], fma(O, tri[:, 3:6], b1[:, None], (tri[:, 0:3] * b0[:, None]).astype(F32)))   # :137
-        e1, e2 = (tri[:, 3:6] - tri[:, 0:3]).astype(F32), (tri[:, 6:9] - tri[:, 0:3]).astype(F32)
-        n = normalize(O, _contract(O, "cross", e1, e2))                                              # :150
-        rng_j, u1 = _rng_next(O, rng[j])                                                             # :256
-        rng_j, u2 = _rng_next(O, rng_j)                                                              # :257
-        rng[j] = rng_j
-        w = m[:, 3]
-        glass = w > 0
-        mirror = ~glass & (w.view(np.uint32) != 0)
-        nf = np.where((dot(O, n, dd) < 0)[:, None], n, -n).astype(F32)                               # :247
-        off = np.full(len(j), ray_offset, F32)
-        sn_cs = _contract(O, "sincos2pi", u1)
-        sn, cs = sn_cs[:, 0], sn_cs[:, 1]
-        u = fma(O, F32(2.0), u2, F32(-1.0))
-        rho = np.sqrt(fma(O, -u, u, F32(1.0))).astype(F32)                                           # :258
-        dn = normalize(O, np.stack([fma(O, rho, cs, nf[:, 0]), fma(O, rho, sn, nf[:, 1]), (nf[:, 2] + u).astype(F32)], 1))   # :259-261
-        if mirror.any():                              # specular.hpp: the lobe around the mirror direction
-            nm, dm, g = nf[mirror], dd[mirror], np.abs(w[mirror])
-            c2 = (F32(-2.0) * dot(O, nm, dm)).astype(F32)
-            refl = fma(O, c2[:, None], nm, dm)
-            s = np.stack([(rho[mirror] * cs[mirror]).astype(F32), (rho[mirror] * sn[mirror]).astype(F32), u[mirror]], 1)
-            lobe = normalize(O, fma(O, g[:, None], s, refl))
-            dn[mirror] = lobe
-            absorbed = ~(dot(O, nm, lobe) > 0)
-            gone = j[mirror][absorbed]
-            acc[gone] = 0
-            alive[gone] = False
-        if glass.any():                               # dielectric.hpp
-            dg, transmitted, _, _ = interface32(O, n[glass], dd[glass], u1[glass], w[glass], m[glass, 4], m[glass, 5])
-            dn[glass] = dg
-            off[glass] = np.where(transmitted, -ray_offset, ray_offset)
-        o[j] = fma(O, off[:, None], nf, pos)                                                          # :250
-        d[j] = dn
-    return acc, rng, first_id, rays
 
 
 def oracle_ext_frame(O, scene, W, H, segments, specular=None, frame=0, rows=None, spp=1):

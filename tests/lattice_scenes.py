@@ -14,14 +14,14 @@ glossy room, its mixed atlas of distinct texels, its box of three instances.
                      texture and light records are the base triangle's, (id - 1) % n_base, in every SPEC
 
 A Case is a shading_scenes.Shading plus `glass` {material: (colour, ior)}.  setup() gives, per SPEC value of the GPU test, what the
-walker (tests/lattice_paths.py) and the upload take.  MEASURED holds the walker's counts tests/test_lattice_cpu.py asserts."""
+walker (tests/path_walker.py) and the upload take.  MEASURED holds the walker's counts tests/test_lattice_cpu.py asserts."""
 from collections import namedtuple
 from functools import lru_cache
 
 import numpy as np
 
 import dielectric_scenes as DS
-import lattice_paths as LP
+import path_walker as WK
 import nee_paths as NP
 import nee_power as PW
 import nee_sphere as NS
@@ -112,7 +112,7 @@ def n_instances(c):
 
 # ------------------------------------------------------------------------------------------ what a SPEC value walks and uploads
 def setup(O, c, spec):
-    """dict(rec, lights, sphere, power) for lattice_paths.walk at a SPEC value of SPECS: 2 the glass and the glossy materials, no
+    """dict(rec, lights, sphere, power) for path_walker.walk at a SPEC value of SPECS: 2 the glass and the glossy materials, no
     light sample; 3 / 4 / 5 / 6 the list, with the sphere (4, 6) and the weighted pick (5, 6); "4-without-list": no material table at
     all — the normal-keyed colours per POSED triangle, no list, the sphere sample alone"""
     sc = c.sh.scene
@@ -157,10 +157,10 @@ def measure(O, name, form):
     """the counts of REQUIRED (tests/test_lattice_cpu.py asserts at least half of each measured count, and > 0)"""
     c = case(O, name, form)
     W, H = SHAPES[0]
-    tex = LP.textures(c.sh, 2)
-    r2 = LP.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 2))
-    r6 = LP.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 6))
-    r3 = LP.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 3))
+    tex = WK.textures(c.sh, 2)
+    r2 = WK.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 2))
+    r6 = WK.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 6))
+    r3 = WK.walk(O, c.sh.scene, W, H, SEGMENTS, tex=tex, **setup(O, c, 3))
     dead = weightless(O, c)
     out = {k: int(r2[k]) for k in ("transmitted", "reflected", "mip_behind", "lod_levels_behind", "lod_fraction_behind")}
     out["alive1"], out["alive"] = P.alive_after(r2["seq_n"], [1, P.window_of(None, form)])

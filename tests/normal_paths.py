@@ -1,8 +1,8 @@
 """Smooth shading (rtpt_scene_set_normals, csrc/shading_normal.hpp) restated in numpy float32, for test_normal_paths_*.py: the rule
-functions operand by operand, the cofactor table, two curved test scenes and a path walker.
+functions operand by operand, the cofactor table and two curved test scenes.
 
-walk() is lattice_paths.walk's loop — its pieces are imported: closest_hits, _texels and the contract functions — with the weights of
-RTPT_FLAG_EXT_NEE_MIS from nee_mis.py and, at every hit whose record is smooth, the rules of section 2 of the header:
+tests/path_walker.py walks the paths (`normals=`): at every hit whose record is smooth it applies the rules of section 2 of the header
+through hit_shading_normal, interface_faced, absorbed, sample_side and dielectric_offset below:
 
   ng   the stored geometric normal after the faceforward (or after the dielectric's entering test): the offset origin, the
        entering test, the texture footprint, the side tests
@@ -11,26 +11,18 @@ RTPT_FLAG_EXT_NEE_MIS from nee_mis.py and, at every hit whose record is smooth, 
   side a diffuse or specular d' with !(dot(d', ng) > 0) ends the path with colour 0; a light or sphere sample needs dot(wd, ng) > 0
        too; a dielectric's offset takes the sign of dot(d', ng)
 
-With `normals` None, or every tri_smooth 0, walk() is lattice_paths.walk bit for bit (tests/test_normal_paths_cpu.py asserts it)."""
+With `normals` None, or every tri_smooth 0, the walk is the one without them bit for bit (tests/test_normal_paths_cpu.py asserts it
+against the recorded frames of the walker that knew no normals)."""
 from collections import namedtuple
 from functools import lru_cache
 
 import numpy as np
 
-import contract_cases as CC
 import dielectric_scenes as DS
-import lattice_paths as LP
-import nee_mis as NM
 import nee_paths as NP
-import nee_power as PW
-import nee_scenes as N
-import nee_sphere as NS
 import pathtrace_scenes as P
 import shading_scenes as SS
-import texture_mip_scenes as MS
-from dielectric_scenes import _contract, _primary, _rng_next, dot, fma, normalize
-from gbuffer_scenes import fill_push_constants
-from lattice_paths import _texels, closest_hits
+from dielectric_scenes import _contract, dot, fma, normalize
 
 F32, U32 = np.float32, np.uint32
 SHAPE = (70, 10)                              # one full tile column, a partial one, partial tile rows
@@ -150,265 +142,6 @@ def interface_faced(O, nf, entering, d, u1, ior, inv, r0):
         trans = fma(O, a[:, None], nf, (eta[:, None] * d).astype(F32))
         dn = normalize(O, np.where(reflect[:, None], refl, trans).astype(F32))
     return dn, ~reflect
-
-
-# ------------------------------------------------------------------------------------------ the walker
-COUNTS = LP.COUNTS + ("smooth", "fallback4", "fallback7", "flipped", "absorbed", "side_invalid", "offset_changed", "weighted")
-
-
-def walk(O, scene, W, H, segments, rec, normals=None, lights=(), sphere=False, power=False, mis=False, frame=0, rows=None, spp=1, tex=None,
-         demod=False, hits=None, n_base=None):
-    """lattice_paths.walk with `normals` (a Normals, or None) and `mis`; n_base: the base triangle count where rec is per POSED
-    triangle.  Besides that walker's planes and counts: smooth (hits shaded with ns), fallback4 / fallback7 (rule 4 / rule 7 fell
-    back), flipped (rule 6), absorbed (side test 1), side_invalid (side test 2 refused a sample the sample's own test allowed),
-    offset_changed (side test 3 chose another sign than `transmitted`)"""
-    assert not (demod and spp > 1), "rtpt_create refuses the two together"
-    cfg = P.configure(O.config_default(W, H), scene, segments, spp)
-    pc = fill_push_constants(O.PushConstants(), P.push_constants(scene), frame)
-    y0, y1 = rows or (0, H)
-    ys, xs = np.meshgrid(np.arange(y0, y1), np.arange(W), indexing="ij")
-    xs, ys = xs.ravel().astype(U32), ys.ravel().astype(U32)
-    k = len(xs)
-    seeds = np.stack([xs, ys, np.full(k, pc.frameNumber, U32), np.full(k, pc.sample_batch, U32)], 1)
-    rng = O.contract_array(CC.fn_index("rng_seed"), np.ascontiguousarray(seeds, U32))[:, 0].copy()          # :297
-    total, first_id = np.zeros((k, 3), F32), None
-    lights = np.ascontiguousarray(lights, U32)
-    count = {c: 0 for c in COUNTS}
-    count.update(picks=np.zeros(len(lights), np.int64), levels=set(), levels_behind=set())
-    rec = np.ascontiguousarray(rec, F32)
-    cdf = PW.table(PW.weights(O, scene.tris, rec, lights)) if power and len(lights) else None
-    albedo = np.zeros((k, 4), F32)
-    albedo[:, :3] = 1
-    seq_n = np.zeros(k, np.int32)
-    nb = int(n_base if n_base is not None else (len(normals.tri_smooth) if normals is not None else len(rec)))
-    for smp in range(spp):
-        rng, d = _primary(O, cfg, rng, xs, ys)
-        value, rng, ids = _path(O, cfg, pc, scene, rec, lights, cdf, bool(sphere), bool(mis) and len(lights) > 0, rng, d, count, tex, H,
-                                albedo if demod else None, seq_n, hits, smp, xs, ys, normals, nb)
-        total = (total + value).astype(F32)                                                                  # :325
-        first_id = ids if first_id is None else first_id
-    image = np.zeros((H, W, 4), F32)
-    hit_id = np.zeros((H, W), U32)
-    image[y0:y1, :, :3] = (total / F32(spp)).astype(F32).reshape(y1 - y0, W, 3)                              # :328
-    hit_id[y0:y1] = first_id.reshape(y1 - y0, W)
-    out = dict(IMAGE=image, HIT_ID=hit_id)
-    if demod:
-        out["ALBEDO"] = np.zeros((H, W, 4), F32)
-        out["ALBEDO"][y0:y1] = albedo.reshape(y1 - y0, W, 4)
-    out["seq_n"] = np.zeros((H, W), np.int32)
-    out["seq_n"][y0:y1] = seq_n.reshape(y1 - y0, W)
-    count["lod_levels"], count["lod_levels_behind"] = len(count.pop("levels")), len(count.pop("levels_behind"))
-    out.update(count)
-    return out
-
-
-def _path(O, cfg, pc, scene, rec, lights, cdf, sphere, mis, rng, d, count, tex, frame_h, albedo, seq_n, hits, smp, xs, ys, normals, nb):
-    """lattice_paths._path, statement for statement, but for the rules of `mis` (nee_mis._path's, marked MIS) and of `normals`
-    (marked NRM)"""
-    tris = np.ascontiguousarray(scene.tris, F32)
-    n_base, segments, k, L = len(rec), int(cfg.max_segments), len(d), len(lights)
-    rng = rng.copy()
-    light_c = F32(list(pc.lightPos))
-    light_col = (F32(list(pc.currentCameraColor)) * F32(cfg.light_intensity)).astype(F32)                   # :281
-    light_first = (light_col / F32(cfg.first_hit_light_divisor)).astype(F32)                                 # :229
-    radius, ray_offset, tmax = F32(cfg.light_radius), F32(cfg.ray_offset), float(cfg.ray_tmax)
-    r2 = NS.r2_of(radius)
-    spread0 = MS.primary_spread(cfg.fov_slope, frame_h)
-    o = np.broadcast_to(F32(scene.cam), (k, 3)).astype(F32).copy()
-    d = d.copy()
-    acc = np.ones((k, 3), F32)
-    radiance = np.zeros((k, 3), F32)
-    sampled = np.zeros(k, bool)
-    sbit = np.zeros(k, bool)
-    cb = np.zeros(k, F32)                             # MIS: the cosine of the last diffuse bounce; read only where `sampled`
-    glassed = np.zeros(k, bool)
-    alive = np.ones(k, bool)
-    first_id = np.zeros(k, U32)
-    seq_n[:] = 0
-    for seg in range(segments):
-        idx = np.flatnonzero(alive)
-        if not len(idx):
-            break
-        oo, dd = o[idx], d[idx]
-        ids, th, b1, b2 = closest_hits(O, tris, oo, dd, tmax)
-        count["rays"] += len(idx)
-        seq_n[idx] += 1
-        if seg == 0:
-            first_id[idx] = ids
-        lit = O.contract_array(CC.fn_index("ray_hits_light"), np.ascontiguousarray(np.concatenate(
-            [oo, dd, np.broadcast_to(light_c, oo.shape), np.full((len(idx), 1), radius, F32)], 1), F32).view(U32))[:, 0] != 0
-        acc[idx[lit]] = (acc[idx[lit]] * (light_first if seg == 0 else light_col)).astype(F32)       # :229, :233
-        acc[idx[lit][sbit[idx[lit]]]] = 0
-        if seg > 0:
-            count["sphere_dropped"] += int(sbit[idx[lit]].sum())
-            count["sphere_kept"] += int((~sbit[idx[lit]]).sum())
-        sky = ~lit & (ids == 0)
-        acc[idx[sky]] = (acc[idx[sky]] * _contract(O, "sky_color", dd[sky])).astype(F32)             # :266
-        alive[idx[lit | sky]] = False
-        hit = ~lit & (ids != 0)
-        m = rec[(ids[hit].astype(np.int64) - 1) % n_base]
-        emissive = m[:, 7] != 0
-        j = idx[hit]
-        acc[j[emissive]] = (acc[j[emissive]] * m[emissive, 4:7]).astype(F32)
-        again = sampled[j[emissive]]                  # the hit before sampled the lights
-        if mis:                                       # MIS: this emission is one of two estimators, (T * Ke) * wb(g_hit)
-            je = j[emissive][again]
-            if len(je):
-                eid = ids[hit][emissive][again]
-                et = tris[eid.astype(np.int64) - 1]
-                reached, inv_p = NM.hit_inv_p(lights, cdf, eid)
-                gh = NM.g_hit(O, et[:, 0:3], et[:, 3:6], et[:, 6:9], oo[hit][emissive][again], dd[hit][emissive][again],
-                              b1[hit][emissive][again], b2[hit][emissive][again], cb[je], inv_p)
-                w_b = np.where(reached, NM.wb(gh), F32(1.0)).astype(F32)
-                acc[je] = (acc[je] * w_b[:, None]).astype(F32)
-        else:
-            acc[j[emissive][again]] = 0               # ... this emission is counted there
-        if seg > 0:
-            count["dropped"] += int(again.sum())
-            count["weighted"] += int(again.sum()) if mis else 0
-            count["kept"] += int((~again).sum())
-        alive[j[emissive]] = False
-        keep = ~emissive
-        j, m = j[keep], m[keep]
-        hid = ids[hit][keep].astype(np.int64) - 1
-        th, b1, b2, dd, oo = th[hit][keep], b1[hit][keep], b2[hit][keep], dd[hit][keep], oo[hit][keep]
-        b0 = ((F32(1.0) - b1).astype(F32) - b2).astype(F32)                                          # :134
-        tri = tris[hid]
-        e1, e2 = (tri[:, 3:6] - tri[:, 0:3]).astype(F32), (tri[:, 6:9] - tri[:, 0:3]).astype(F32)
-        n = normalize(O, _contract(O, "cross", e1, e2))                                              # :150, the stored normal
-        alb = m[:, 0:3]
-        lam, textured, mipped = np.zeros(len(j), F32), np.zeros(len(j), bool), np.zeros(len(j), bool)
-        if tex is not None:
-            texel, lam, textured, mipped = _texels(O, tex, hid % len(tex.tri_texture), b0, b1, b2, th, dot(O, n, dd), tri.reshape(-1, 3, 3),
-                                                   spread0 if seg == 0 else MS.BOUNCE_SPREAD)
-            alb = (alb * texel).astype(F32)
-        if albedo is not None and seg == 0:
-            albedo[j, :3] = alb
-        else:
-            acc[j] = (acc[j] * alb).astype(F32)                                                      # :244
-        count["mip_behind"] += int((mipped & glassed[j]).sum())
-        if seg > 0:
-            for key, sel in (("", mipped), ("_behind", mipped & glassed[j])):
-                count["levels" + key] |= set(np.floor(lam[sel]).astype(int).tolist())
-                count["lod_fraction" + key] += int((lam[sel] % 1 != 0).sum())
-        if seg + 1 >= segments:                       # the last segment: no light draw, no shadow query; the bounce's two draws
-            rng[j] = _rng_next(O, _rng_next(O, rng[j])[0])[0]      # only move the stream (:256-257)
-            break
-        pos = fma(O, tri[:, 6:9], b2[:, None], fma(O, tri[:, 3:6], b1[:, None], (tri[:, 0:3] * b0[:, None]).astype(F32)))   # :137
-        w = m[:, 3]
-        glass = w > 0
-        mirror = ~glass & (w.view(U32) != 0)
-        diffuse = ~glass & ~mirror
-        entering = dot(O, n, dd) < 0
-        nf = np.where(entering[:, None], n, -n).astype(F32)                                          # :247: ng
-        ns, smooth = hit_shading_normal(O, normals, hid, nb, b0, b1, b2, nf, dd)                     # NRM
-        if normals is not None:
-            rs = np.asarray(normals.tri_smooth)[hid % nb] != 0
-            count["smooth"] += int(smooth.sum())
-            count["fallback4"] += int((rs & ~smooth).sum())
-            count["fallback7"] += int((smooth & (ns == nf).all(1)).sum())
-        q = np.flatnonzero(diffuse)
-        jq = j[q]
-        x = fma(O, ray_offset, nf[q], pos[q])                                                         # :250, the bounce's origin (ng)
-        tri_gain = None
-        if L:
-            r, u_l = _rng_next(O, rng[jq])
-            r, u_a = _rng_next(O, r)
-            r, u_b = _rng_next(O, r)
-            rng[jq] = r
-            if cdf is not None:
-                entry, inv_p = PW.pick_power(cdf, u_l)
-                id1 = lights[entry]
-                lt = tris[id1.astype(np.int64) - 1]
-                wd, g, valid = PW.sample32_inv_p(O, lt[:, 0:3], lt[:, 3:6], lt[:, 6:9], x, ns[q], u_a, u_b, inv_p)
-            else:
-                entry = N.pick(u_l, np.full(len(q), L))
-                id1 = lights[entry]
-                lt = tris[id1.astype(np.int64) - 1]
-                s = N.sample32(O, N.cases_of(lt[:, 0:3], lt[:, 3:6], lt[:, 6:9], x, ns[q], u_l, u_a, u_b, L))[:, :8].view(F32)
-                wd, g, valid = s[:, 3:6], s[:, 6], s[:, 7] != 0
-            side = ~smooth[q] | sample_side(O, wd, nf[q])                                             # NRM: the sample's side of ng
-            count["side_invalid"] += int((valid & ~side).sum())
-            valid = valid & side
-            if mis:                                   # MIS: gm = g * m(g)
-                g = NM.gm(g)
-            count["picks"] += np.bincount(entry, minlength=L)
-            ke = rec[(id1.astype(np.int64) - 1) % n_base, 4:7]
-            with np.errstate(all="ignore"):
-                gain = (((acc[jq] * ke).astype(F32)) * g[:, None]).astype(F32)                        # (T * Ke) * g
-            seen, _, _, _ = closest_hits(O, tris, x[valid], wd[valid], tmax)
-            reached = seen == id1[valid]
-            tri_gain = (jq[valid][reached], gain[valid][reached])
-            count["rays"] += int(valid.sum())
-            count["samples"] += len(q)
-            count["queries"] += int(valid.sum())
-            count["lit"] += int(reached.sum())
-            sampled[jq] = True
-            sampled[j[~diffuse]] = False
-        if sphere:
-            r, u_c = _rng_next(O, rng[jq])
-            r, u_p = _rng_next(O, r)
-            rng[jq] = r
-            s = NS.sphere32(O, NS.cases_of(x, ns[q], light_c, r2, u_c, u_p)).view(F32)
-            taken, valid = s[:, 4] != 0, s[:, 5] != 0
-            side = ~smooth[q] | sample_side(O, s[:, 0:3], nf[q])                                      # NRM
-            count["side_invalid"] += int((valid & ~side).sum())
-            valid = valid & side
-            gain = (((acc[jq] * light_col).astype(F32)) * s[:, 3:4]).astype(F32)                      # (T * light_col) * g
-            radiance[jq[valid]] = (radiance[jq[valid]] + gain[valid]).astype(F32)
-            count["sphere_samples"] += len(q)
-            count["sphere_taken"] += int(taken.sum())
-            count["sphere_valid"] += int(valid.sum())
-            sbit[jq] = taken
-            sbit[j[~diffuse]] = False
-        if tri_gain is not None:
-            radiance[tri_gain[0]] = (radiance[tri_gain[0]] + tri_gain[1]).astype(F32)
-        rng_j, u1 = _rng_next(O, rng[j])                                                             # :256
-        rng_j, u2 = _rng_next(O, rng_j)                                                              # :257
-        rng[j] = rng_j
-        off = np.full(len(j), ray_offset, F32)
-        sn_cs = _contract(O, "sincos2pi", u1)
-        sn, cs = sn_cs[:, 0], sn_cs[:, 1]
-        u = fma(O, F32(2.0), u2, F32(-1.0))
-        rho = np.sqrt(fma(O, -u, u, F32(1.0))).astype(F32)                                           # :258
-        dn = normalize(O, np.stack([fma(O, rho, cs, ns[:, 0]), fma(O, rho, sn, ns[:, 1]), (ns[:, 2] + u).astype(F32)], 1))   # :259-261 about ns
-        if mis:
-            cb[jq] = dot(O, ns[q], dn[q])
-        gone_side = np.zeros(len(j), bool)
-        gone_side[q] = smooth[q] & absorbed(O, dn[q], nf[q])                                          # NRM: a diffuse d' behind ng
-        if mirror.any():
-            nm, dm, gl = ns[mirror], dd[mirror], np.abs(w[mirror])
-            c2 = (F32(-2.0) * dot(O, nm, dm)).astype(F32)
-            refl = fma(O, c2[:, None], nm, dm)
-            sph = np.stack([(rho[mirror] * cs[mirror]).astype(F32), (rho[mirror] * sn[mirror]).astype(F32), u[mirror]], 1)
-            lobe = normalize(O, fma(O, gl[:, None], sph, refl))
-            dn[mirror] = lobe
-            side = smooth[mirror] & absorbed(O, lobe, nf[mirror])                                     # NRM: a specular d' behind ng
-            lost = ~(dot(O, nm, lobe) > 0)
-            gone_side[np.flatnonzero(mirror)] = side & ~lost
-            gone = j[mirror][lost | side]
-            acc[gone] = 0
-            alive[gone] = False
-        count["absorbed"] += int(gone_side.sum())
-        acc[j[gone_side]] = 0
-        alive[j[gone_side]] = False
-        if glass.any():
-            dg, transmitted = interface_faced(O, ns[glass], entering[glass], dd[glass], u1[glass], w[glass], m[glass, 4], m[glass, 5])
-            dn[glass] = dg
-            plain = np.where(transmitted, -ray_offset, ray_offset).astype(F32)
-            sided = dielectric_offset(O, dg, nf[glass], ray_offset)                                   # NRM: the side d' leaves on
-            off[glass] = np.where(smooth[glass], sided, plain)
-            count["offset_changed"] += int((smooth[glass] & (sided != plain)).sum())
-            count["transmitted"] += int(transmitted.sum())
-            count["reflected"] += int((~transmitted).sum())
-            glassed[j[glass]] = True
-        if hits is not None:
-            hits.append(dict(x=xs[j].copy(), y=ys[j].copy(), sample=np.full(len(j), smp), seg=np.full(len(j), seg), o=oo, d=dd, id=hid + 1,
-                             b0=b0, b1=b1, b2=b2, ng=nf, ns=ns, smooth=smooth, dn=dn.copy(), diffuse=diffuse, mirror=mirror, glass=glass,
-                             gone=gone_side.copy(), u=u, rho=rho, sn=sn, cs=cs, off=off.copy()))
-        o[j] = fma(O, off[:, None], nf, pos)                                                          # :250 (ng)
-        d[j] = dn
-    return (radiance + acc).astype(F32), rng, first_id
 
 
 # ------------------------------------------------------------------------------------------ the scenes
@@ -546,7 +279,7 @@ SPEC_FLAGS = {0: 0, 1: 0, 2: 0, 3: NEE, 4: NEE | SPHERE, 5: NEE | POWER, 10: NEE
 
 
 def setup(O, c, spec):
-    """dict(rec, lights, sphere, power, mis) for walk() at a SPEC value of the kernels: 0 every material diffuse (Kd / Ke only), 1 with
+    """dict(rec, lights, sphere, power, mis) for path_walker.walk at a SPEC value of the kernels: 0 every material diffuse (Kd / Ke only), 1 with
     the glossy and mirror materials, 2 with the glass too; 3, 4, 5 and 10 (kSpecNeeSpherePowerMis) the light samples on top"""
     sc = c.sh.scene
     rec = DS.records(sc, c.sh.spec if spec >= 1 else None, c.glass if spec >= 2 else None)

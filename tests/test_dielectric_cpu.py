@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import dielectric_scenes as DS
+import path_walker as WK
 import specular_scenes as S
 from conftest import ROOT, bits
 from filter_planes import same_bits
@@ -69,16 +70,16 @@ def test_walker_reproduces_the_oracle(oracle, name, form, segments):
     rec = DS.records(scene, spec)
     for W, H in DS.SIZES:
         want = DS.oracle_ext_frame(oracle, scene, W, H, segments, spec)
-        got = DS.walk(oracle, scene, W, H, segments, rec)
+        got = WK.walk(oracle, scene, W, H, segments, rec)
         same_bits(got["HIT_ID"], want["HIT_ID"], (name, form, W, H, "HIT_ID"))
         same_bits(got["IMAGE"], want["IMAGE"], (name, form, W, H, "IMAGE"))
         assert got["rays"] == want["rays"]
-    strip = DS.walk(oracle, scene, W, H, segments, rec, rows=(3, 8))
+    strip = WK.walk(oracle, scene, W, H, segments, rec, rows=(3, 8))
     same_bits(strip["IMAGE"][3:8], want["IMAGE"][3:8], (name, form, "strip"))
     if form == "small":      # more samples per pixel: every one goes on with the pixel's stream, also behind a path's last segment
         for seg, spp in ((1, 2), (2, 3), (segments, 2)):
             want = DS.oracle_ext_frame(oracle, scene, W, H, seg, spec, spp=spp)
-            got = DS.walk(oracle, scene, W, H, seg, rec, spp=spp)
+            got = WK.walk(oracle, scene, W, H, seg, rec, spp=spp)
             same_bits(got["IMAGE"], want["IMAGE"], (name, form, seg, spp, "IMAGE"))
             assert got["rays"] == want["rays"]
         want = DS.oracle_ext_frame(oracle, scene, W, H, segments, spec)
@@ -95,8 +96,8 @@ def test_walker_meets_glass(oracle):
     centre = (np.asarray(DS.BOX_LO) + np.asarray(DS.BOX_HI)) / 2
     out_of_box = np.asarray(scene.tris, np.float64).reshape(-1, 3, 3).mean(1) - centre
     assert ((DS.stored_normals(oracle, scene.tris) * out_of_box).sum(1)[box] > 0).all(), "the box's normals point out of the medium"
-    a = DS.walk(oracle, scene, 64, 48, 9, DS.records(scene, None, glass))
-    b = DS.walk(oracle, scene, 64, 48, 9, DS.records(scene))
+    a = WK.walk(oracle, scene, 64, 48, 9, DS.records(scene, None, glass))
+    b = WK.walk(oracle, scene, 64, 48, 9, DS.records(scene))
     assert a["rays"] != b["rays"] and not np.array_equal(bits(a["IMAGE"]), bits(b["IMAGE"]))
     on_glass = scene.tri_material[a["HIT_ID"][a["HIT_ID"] > 0] - 1] == 6
     assert on_glass.mean() > 0.05, "the box is in view"

@@ -13,6 +13,7 @@ import pytest
 
 import dielectric_scenes as DS
 import filter_planes as FP
+import path_walker as WK
 import pathtrace_scenes as P
 import specular_scenes as S
 import test_demodulate_gpu as D
@@ -54,7 +55,7 @@ def walked(oracle, form, W, H, segments, spp=1):
     key = (form, W, H, segments, spp)
     if key not in _walked:
         scene, glass = DS.glass_room(form)
-        r = DS.walk(oracle, scene, W, H, segments, DS.records(scene, None, glass), spp=spp)
+        r = WK.walk(oracle, scene, W, H, segments, DS.records(scene, None, glass), spp=spp)
         for a in r.values():
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)

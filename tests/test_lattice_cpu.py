@@ -1,12 +1,13 @@
-"""The lattice walker (tests/lattice_paths.py) held on the CPU before tests/test_lattice_gpu.py judges a GPU frame by it.  All
+"""The walker (tests/path_walker.py) held on the CPU over the whole lattice before tests/test_lattice_gpu.py judges a GPU frame by it.  All
 comparisons are bit for bit (filter_planes.same_bits) unless a bar is named:
 
   1. against the C oracle (oracle_raytrace_ext) on the scenes of tests/shading_scenes.py — SPEC 0 and 1, no glass, no list — IMAGE,
      HIT_ID, ALBEDO and the ray count for TEX 0 / 1 / 2, DEMOD off / on, forms small and odd, budgets 1, 2 and 9, three samples at
      budgets 1 and 2, a chain no box filter made, and a strip: the restatement of the mip level and of the ALBEDO plane is the
      oracle's, and the t it takes from oracle_closest_hit is the t the oracle's level takes;
-  2. against the older walkers: with level-0 textures and DEMOD off it is nee_power.walk_nee_power for every combination of sphere
-     and power; with an empty list and the sphere off it is dielectric_scenes.walk;
+  2. against the recorded frames of the older walkers (tests/golden/walker_frames.npz, IMAGE by its SHA-256): with level-0 textures
+     and DEMOD off it is nee_power.walk_nee_power for every combination of sphere and power; with an empty list and the sphere off
+     it is dielectric_scenes.walk;
   3. against float64: every recorded hit of the new scenes (tests/lattice_scenes.py) at 9 segments, its level replayed from the
      record's own ray by texture_mip_scenes.lod_of_rays, with the bar and the exclusions of
      test_shading_ext_cpu.test_recorded_hits_against_float64; hits behind the first glass hit are reported separately;
@@ -18,7 +19,7 @@ import numpy as np
 import pytest
 
 import dielectric_scenes as DS
-import lattice_paths as LP
+import path_walker as WK
 import lattice_scenes as LS
 import nee_power as PW
 import pathtrace_scenes as P
@@ -32,7 +33,10 @@ W0, H0 = LS.SHAPES[0]
 
 def same_frame(got, want, tag, demod=False):
     same_bits(got["HIT_ID"], want["HIT_ID"], tag + ("HIT_ID",))
-    same_bits(got["IMAGE"], want["IMAGE"], tag + ("IMAGE",))
+    if "IMAGE" in want:
+        same_bits(got["IMAGE"], want["IMAGE"], tag + ("IMAGE",))
+    else:
+        assert WK.same_image(got, want), tag + ("IMAGE", "SHA-256")
     if demod:
         same_bits(got["ALBEDO"], want["ALBEDO"], tag + ("ALBEDO",))
     assert got["rays"] == want["rays"], tag + ("rays", got["rays"], want["rays"])
@@ -45,18 +49,18 @@ def test_walker_equals_the_oracle(oracle, name, form):
     sh = SS.world(oracle, SS.scene(name, form))
     rec = DS.records(sh.scene, sh.spec)
     for tex in (0, 1, 2):
-        tx = LP.textures(sh, tex)
+        tx = WK.textures(sh, tex)
         for segments, spp, demod in [(s, 1, d) for s in (1, 2, SS.SEGMENTS) for d in (False, True)] + [(1, 3, False), (2, 3, False)]:
             tag = (name, form, tex, segments, spp, demod)
             ref = SS.oracle_frame(oracle, sh, W0, H0, segments, spp, tex, True, demod, records=False)
-            got = LP.walk(oracle, sh.scene, W0, H0, segments, rec, spp=spp, tex=tx, demod=demod)
+            got = WK.walk(oracle, sh.scene, W0, H0, segments, rec, spp=spp, tex=tx, demod=demod)
             same_frame(got, ref, tag, demod)
             if spp == 1:
                 assert np.array_equal(got["seq_n"], ref["seq_n"]), tag
     if name == "glossy_textured_room":
         W, H = SS.SHAPES[1]
         for demod in (False, True):
-            same_frame(LP.walk(oracle, sh.scene, W, H, SS.SEGMENTS, rec, tex=LP.textures(sh, 2), demod=demod),
+            same_frame(WK.walk(oracle, sh.scene, W, H, SS.SEGMENTS, rec, tex=WK.textures(sh, 2), demod=demod),
                        SS.oracle_frame(oracle, sh, W, H, demod=demod, records=False), (name, form, W, H, demod), demod)
 
 
@@ -67,14 +71,14 @@ def test_walker_reads_a_given_chain_and_walks_a_strip(oracle):
     chains = SS.random_chains(sh)
     for demod in (False, True):
         ref = SS.oracle_frame(oracle, sh, W0, H0, demod=demod, textures=SS.given_atlas(sh, chains), records=False)
-        got = LP.walk(oracle, sh.scene, W0, H0, SS.SEGMENTS, rec, tex=LP.textures(sh, 2, chains), demod=demod)
+        got = WK.walk(oracle, sh.scene, W0, H0, SS.SEGMENTS, rec, tex=WK.textures(sh, 2, chains), demod=demod)
         same_frame(got, ref, ("given", demod), demod)
-        generated = LP.walk(oracle, sh.scene, W0, H0, SS.SEGMENTS, rec, tex=LP.textures(sh, 2), demod=demod)
+        generated = WK.walk(oracle, sh.scene, W0, H0, SS.SEGMENTS, rec, tex=WK.textures(sh, 2), demod=demod)
         assert not np.array_equal(bits(got["IMAGE"]), bits(generated["IMAGE"]))
     W, H, y0, y1 = P.STRIP
     for demod in (False, True):
         ref = SS.oracle_frame(oracle, sh, W, H, demod=demod, rows=(y0, y1), records=False)
-        got = LP.walk(oracle, sh.scene, W, H, SS.SEGMENTS, rec, tex=LP.textures(sh, 2), demod=demod, rows=(y0, y1))
+        got = WK.walk(oracle, sh.scene, W, H, SS.SEGMENTS, rec, tex=WK.textures(sh, 2), demod=demod, rows=(y0, y1))
         for plane in ("IMAGE", "HIT_ID") + (("ALBEDO",) if demod else ()):
             same_bits(got[plane][y0:y1], ref[plane][y0:y1], ("strip", demod, plane))
         assert got["rays"] == ref["rays"]
@@ -91,24 +95,23 @@ def test_walker_equals_the_older_walkers_at_level_0(oracle, name, form):
     sc = c.sh.scene
     s = LS.setup(oracle, c, 6)
     rec, lights = s["rec"], s["lights"]
-    level0 = LP.textures(c.sh, 1)
+    level0 = WK.textures(c.sh, 1)
     assert level0.chains is None and len(lights) > 0
     for segments, spp in ((2, 1), (LS.SEGMENTS, 1), (2, 3)):
         for tx in (None, level0):
-            old_tex = None if tx is None else (tx.tri_uv, tx.tri_texture, tx.desc, tx.texels)
             for sphere in (False, True):
                 for power in (False, True):
                     tag = (name, form, segments, spp, tx is not None, sphere, power)
-                    want = PW.walk_nee_power(oracle, sc, W0, H0, segments, rec, lights, sphere=sphere, power=power, spp=spp, texture=old_tex)
-                    got = LP.walk(oracle, sc, W0, H0, segments, rec, lights, sphere=sphere, power=power, spp=spp, tex=tx)
+                    want = WK.recorded("lattice/PW", *tag)      # walk_nee_power's, with the level-0 tuple (tri_uv, tri_texture, desc, texels)
+                    got = WK.walk(oracle, sc, W0, H0, segments, rec, lights, sphere=sphere, power=power, spp=spp, tex=tx)
                     same_frame(got, want, tag)
                     assert all(got[k] == want[k] for k in OLD_COUNTS) and np.array_equal(got["picks"], want["picks"]), tag
-        want = DS.walk(oracle, sc, W0, H0, segments, rec, spp=spp)
-        same_frame(LP.walk(oracle, sc, W0, H0, segments, rec, spp=spp), want, (name, form, segments, spp, "no list"))
+        tag = (name, form, segments, spp, "no list")
+        same_frame(WK.walk(oracle, sc, W0, H0, segments, rec, spp=spp), WK.recorded("lattice/DS", *tag), tag)
     # a mixed atlas whose flagged textures hold one value per channel at every level: any level reads what level 0 reads
     flat = c.sh._replace(images=tuple(np.broadcast_to(im[:1, :1], im.shape).copy() for im in c.sh.images))
-    a = LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, rec, lights, sphere=True, power=True, tex=LP.textures(flat, 2))
-    b = LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, rec, lights, sphere=True, power=True, tex=LP.textures(flat, 1))
+    a = WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, rec, lights, sphere=True, power=True, tex=WK.textures(flat, 2))
+    b = WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, rec, lights, sphere=True, power=True, tex=WK.textures(flat, 1))
     same_frame(a, b, (name, form, "constant images"))
     assert a["lod_levels"] >= 3 and a["lod_fraction"] > 0, "levels were chosen"
 
@@ -124,8 +127,8 @@ def test_recorded_hits_against_float64(oracle, name, form):
     c = LS.case(oracle, name, form)
     sh, sc = c.sh, c.sh.scene
     hits = []
-    LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=LP.textures(sh, 2), hits=hits, **LS.setup(oracle, c, 6))
-    h = LP.hit_table(hits)
+    WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=WK.textures(sh, 2), hits=hits, **LS.setup(oracle, c, 6))
+    h = WK.hit_table(hits)
     tris = MS.posed(sh.mesh[0], sh.mesh[1], sh.xforms) if sh.mesh else np.asarray(sc.tris, np.float64).reshape(-1, 3, 3)
     assert np.abs(tris - np.asarray(sc.tris, np.float64).reshape(-1, 3, 3)).max() < 1e-5
     rays = np.concatenate([h["o"], h["d"]], 1).astype(np.float64)
@@ -182,19 +185,19 @@ def test_scenes_exercise_what_they_claim(oracle, name, form):
     w = np.unique(PW.counted(PW.weights(oracle, sc.tris, LS.setup(oracle, c, 5)["rec"], LS.setup(oracle, c, 5)["lights"])))
     assert len(w) >= 3 and w[0] == 0
     # the frames of the six SPEC values differ pairwise, and real mips differ from level 0
-    tex = LP.textures(sh, 2)
-    frames = {s: LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=tex, **LS.setup(oracle, c, s)) for s in LS.SPECS}
+    tex = WK.textures(sh, 2)
+    frames = {s: WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=tex, **LS.setup(oracle, c, s)) for s in LS.SPECS}
     for i, a in enumerate(LS.SPECS):
         assert not np.isnan(frames[a]["IMAGE"]).any()
         for b in LS.SPECS[i + 1:]:
             assert not np.array_equal(bits(frames[a]["IMAGE"]), bits(frames[b]["IMAGE"])), (a, b)
     for s in (2, 6, "4-without-list"):
-        level0 = LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=LP.textures(sh, 1), **LS.setup(oracle, c, s))
+        level0 = WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=WK.textures(sh, 1), **LS.setup(oracle, c, s))
         assert not np.array_equal(bits(frames[s]["IMAGE"]), bits(level0["IMAGE"])), s
-        plain = LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, **LS.setup(oracle, c, s))
+        plain = WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, **LS.setup(oracle, c, s))
         assert not np.array_equal(bits(level0["IMAGE"]), bits(plain["IMAGE"])), s
     # the ALBEDO plane holds texels, ones where a path ends at segment 0, and the demodulated image is another image
-    d = LP.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=tex, demod=True, **LS.setup(oracle, c, 6))
+    d = WK.walk(oracle, sc, W0, H0, LS.SEGMENTS, tex=tex, demod=True, **LS.setup(oracle, c, 6))
     ended = (d["ALBEDO"][..., :3] == 1).all(-1)
     assert 0 < ended.sum() < ended.size and not d["ALBEDO"][..., 3].any()
     assert len(np.unique(bits(d["ALBEDO"][..., :3]).reshape(-1, 3), axis=0)) > 100
@@ -204,6 +207,6 @@ def test_scenes_exercise_what_they_claim(oracle, name, form):
     assert d["rays"] == frames[6]["rays"]
     if sh.mesh:      # the moved instances of the GPU test: still glass, light samples and levels behind glass
         moved = LS.case(oracle, name, form, SS.box_xforms(moved=True))
-        r = LP.walk(oracle, moved.sh.scene, W0, H0, LS.SEGMENTS, tex=tex, **LS.setup(oracle, moved, 6))
+        r = WK.walk(oracle, moved.sh.scene, W0, H0, LS.SEGMENTS, tex=tex, **LS.setup(oracle, moved, 6))
         assert r["transmitted"] and r["lit"] and r["mip_behind"] and r["sphere_valid"], (name, form, "moved")
         assert not np.array_equal(moved.sh.scene.tris, sc.tris)

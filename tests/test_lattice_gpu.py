@@ -4,7 +4,7 @@ and, with RTPT_FLAG_EXT_DEMODULATE, ALBEDO (same_bits of filter_planes.py: bits,
 launch_pathtrace picks the tile kernel from scene mode (3) x DEMOD (2) x TEX (3) x SPEC (7) x {fused, unfused compact, unfused
 non-compact}, and k_pathtrace_queue from scene mode x TEX x SPEC 0 .. 2.  tests/test_shading_ext_gpu.py covers SPEC 0 and 1 cell by
 cell against the C oracle, which knows neither glass nor a light sample; this file covers SPEC 2 .. 6 the same way against the walker
-of tests/lattice_paths.py, which tests/test_lattice_cpu.py holds to that oracle (SPEC 0 / 1), to the older walkers (level 0) and to
+of tests/path_walker.py, which tests/test_lattice_cpu.py holds to that oracle (SPEC 0 / 1), to the older walkers (level 0) and to
 float64.  The scenes (tests/lattice_scenes.py) put mip-mapped, textured hits inside and behind glass and take light samples of
 every kind at textured hits, so that a wrong level, a wrong texel in ALBEDO or a gain demodulated twice shows in the bits.
 
@@ -34,7 +34,7 @@ import numpy as np
 import pytest
 
 import filter_planes as FP
-import lattice_paths as LP
+import path_walker as WK
 import lattice_scenes as LS
 import pathtrace_scenes as P
 import shading_scenes as SS
@@ -70,7 +70,7 @@ def reference(oracle, c, W, H, tex, spec, segments=LS.SEGMENTS, spp=1, demod=Fal
     sc = c.sh.scene
     k = (sc.name, sc.form, tex, spec, segments, spp, demod, W, H, rows, frame) + key
     if k not in _ref_cache:
-        r = LP.walk(oracle, sc, W, H, segments, spp=spp, tex=LP.textures(c.sh, tex), demod=demod, rows=rows, frame=frame, **LS.setup(oracle, c, spec))
+        r = WK.walk(oracle, sc, W, H, segments, spp=spp, tex=WK.textures(c.sh, tex), demod=demod, rows=rows, frame=frame, **LS.setup(oracle, c, spec))
         FP.check_ids(r["HIT_ID"], len(sc.tris))
         for a in r.values():
             if isinstance(a, np.ndarray):

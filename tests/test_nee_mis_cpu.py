@@ -1,7 +1,7 @@
 """Multiple importance sampling of next-event estimation without a device (RTPT_FLAG_EXT_NEE_MIS; csrc/light_sample.hpp states
 the rules): the numpy restatement of tests/nee_mis.py, which tests/test_nee_mis_gpu.py holds the device functions and the tile
-kernels to bit for bit, is first held to exact values and to float64, its search to np.searchsorted, then to the walkers it
-extends, and then to the estimator it replaces — the mean of its frames against the flag-off walker's, and its variance against
+kernels to bit for bit, is first held to exact values and to float64, its search to np.searchsorted, then the walker of
+tests/path_walker.py with the flag off to the recorded frames of the walkers without it, and then to the estimator it replaces — the mean of its frames against the flag-off walker's, and its variance against
 plain next-event estimation's where an emitter is close."""
 import os
 import subprocess
@@ -14,7 +14,7 @@ import nee_mis as M
 import nee_paths as NP
 import nee_power as PW
 import nee_scenes as N
-import nee_sphere as NS
+import path_walker as WK
 from conftest import bits
 
 F32, U32 = np.float32, np.uint32
@@ -156,39 +156,39 @@ def _same(got, want, counts=True):
 
 @pytest.mark.parametrize("power,sphere", [(False, False), (True, False), (True, True)], ids=["uniform", "weighted", "weighted_sphere"])
 def test_mis_off_is_the_power_walker(oracle, power, sphere):
-    """with `mis` off walk_nee_mis is nee_power.walk_nee_power bit for bit — IMAGE, HIT_ID, rays, every count and the picks — on
+    """with `mis` off the walker is the recorded nee_power.walk_nee_power bit for bit — IMAGE, HIT_ID, rays, every count and the picks — on
     nee_two_lamps and on the glass room with two lamps (diffuse, dielectric and emissive hits; 9 segments, two samples); and with
     it on the frame differs while the samples, the queries and the rays do not"""
     room, glass, rec = PW.glass_room_two_lamps()
     two = NP.two_lamps()
     for sc, r, li, seg, spp in ((two, DS.records(two), NP.light_list(two), 5, 1), (room, rec, NP.light_list(room, 1, rec), 9, 2)):
-        want = PW.walk_nee_power(oracle, sc, W1, H1, seg, r, li, sphere=sphere, power=power, spp=spp)
-        got = M.walk_nee_mis(oracle, sc, W1, H1, seg, r, li, mis=False, power=power, sphere=sphere, spp=spp)
+        want = WK.recorded("nee_mis/PW", sc.name, seg, spp, power, sphere)
+        got = WK.walk(oracle, sc, W1, H1, seg, r, li, mis=False, power=power, sphere=sphere, spp=spp)
         _same(got, want)
-        on = M.walk_nee_mis(oracle, sc, W1, H1, seg, r, li, mis=True, power=power, sphere=sphere, spp=spp)
+        on = WK.walk(oracle, sc, W1, H1, seg, r, li, mis=True, power=power, sphere=sphere, spp=spp)
         assert not np.array_equal(bits(on["IMAGE"]), bits(want["IMAGE"]))
         assert on["rays"] == want["rays"] and on["samples"] == want["samples"] and on["queries"] == want["queries"]
         assert np.array_equal(on["HIT_ID"], want["HIT_ID"]) and np.array_equal(on["picks"], want["picks"])
 
 
 def test_one_segment_and_an_empty_list_ignore_the_flag(oracle):
-    """max_segments = 1 with the flag is flag off (no hit samples, no bit is ever set); an empty list is walk_nee_sphere, with the
-    sphere sample and without; a batch of frames is the frames one by one"""
+    """max_segments = 1 with the flag is flag off (no hit samples, no bit is ever set); an empty list is the recorded
+    nee_sphere.walk_nee_sphere, with the sphere sample and without; a batch of frames is the frames one by one"""
     room, glass, rec = PW.glass_room_two_lamps()
     lights = NP.light_list(room, 1, rec)
-    one = M.walk_nee_mis(oracle, room, W1, H1, 1, rec, lights, power=True)
-    _same(one, DS.walk(oracle, room, W1, H1, 1, rec), counts=False)
+    one = WK.walk(oracle, room, W1, H1, 1, rec, lights, mis=True, power=True)
+    _same(one, WK.recorded("nee_mis/DS", "one"), counts=False)
     assert one["samples"] == 0 and one["weighted"] == 0
     for sphere in (False, True):
-        empty = M.walk_nee_mis(oracle, room, W1, H1, 9, rec, NONE, sphere=sphere, power=True)
-        want = NS.walk_nee_sphere(oracle, room, W1, H1, 9, rec, NONE, sphere)
+        empty = WK.walk(oracle, room, W1, H1, 9, rec, NONE, mis=True, sphere=sphere, power=True)
+        want = WK.recorded("nee_mis/NS", "empty", sphere)
         _same(empty, want, counts=False)
         assert empty["rays"] == want["rays"]
     sc = M.wall_lamp()
     r, li = DS.records(sc), NP.light_list(sc)
-    batch = M.walk_nee_mis(oracle, sc, W1, H1, 2, r, li, frames=[0, 7, 3])
+    batch = WK.walk(oracle, sc, W1, H1, 2, r, li, mis=True, frames=[0, 7, 3])
     for i, f in enumerate((0, 7, 3)):
-        single = M.walk_nee_mis(oracle, sc, W1, H1, 2, r, li, frame=f)
+        single = WK.walk(oracle, sc, W1, H1, 2, r, li, mis=True, frame=f)
         assert np.array_equal(bits(batch["IMAGE"][i]), bits(single["IMAGE"])) and np.array_equal(batch["HIT_ID"][i], single["HIT_ID"])
 
 
@@ -199,13 +199,13 @@ def test_every_scene_has_weighted_terminals(oracle):
     cases = [(sc, DS.records(sc), NP.light_list(sc)) for sc in (M.wall_lamp(), NP.two_lamps(), NP.occluder(), PW.unequal_lamps())]
     cases.append((room, rec, NP.light_list(room, 1, rec)))
     for sc, r, li in cases:
-        got = M.walk_nee_mis(oracle, sc, W0, H0, 2, r, li)
+        got = WK.walk(oracle, sc, W0, H0, 2, r, li, mis=True)
         print(f"{sc.name}: {got['weighted']} weighted terminals, wb in [{got['wb_min']:.3g}, {got['wb_max']:.3g}]")
         assert got["dropped"] == got["weighted"] > 0 and 0 <= got["wb_min"] < got["wb_max"] < 1, sc.name
-    wall = M.walk_nee_mis(oracle, M.wall_lamp(), W0, H0, 2, *cases[0][1:])
+    wall = WK.walk(oracle, M.wall_lamp(), W0, H0, 2, *cases[0][1:], mis=True)
     lit = set(int(i) for i in cases[0][2])
     assert not lit & set(np.unique(wall["HIT_ID"]).tolist()), "the wall stands outside the view"
-    nine = M.walk_nee_mis(oracle, room, W0, H0, 9, rec, cases[-1][2])
+    nine = WK.walk(oracle, room, W0, H0, 9, rec, cases[-1][2], mis=True)
     assert nine["kept"] > 0 and nine["weighted"] > 0, "behind a mirror or glass hit the bit is clear"
 
 
@@ -215,7 +215,7 @@ _var = {}
 
 @pytest.mark.parametrize("name", ["nee_wall_lamp", "nee_two_lamps", "nee_occluder"])
 def test_mis_estimates_what_the_path_tracer_estimates(oracle, name):
-    """70 x 10, two segments, frames 0 .. 2047, uniform pick: the per-pixel mean of walk_nee_mis's frames against the mean of the
+    """70 x 10, two segments, frames 0 .. 2047, uniform pick: the per-pixel mean of the walker's frames with `mis` against the mean of the
     flag-off walker's (the same walker on an empty list) within 5 standard errors of the difference at every pixel and channel,
     none left out — the bar of test_nee_paths_cpu.py, test_nee_sphere_cpu.py and test_nee_power_cpu.py; pixels whose two sides
     never vary have to differ by exactly 0.  On nee_wall_lamp the summed per-pixel variance with MIS is below plain next-event
@@ -226,7 +226,7 @@ def test_mis_estimates_what_the_path_tracer_estimates(oracle, name):
     rec = DS.records(scene)
     lights = NP.light_list(scene)
     n = ESTIMATOR_FRAMES
-    run = lambda li, mis: M.walk_nee_mis(oracle, scene, W1, H1, 2, rec, li, mis=mis, frames=range(n))
+    run = lambda li, mis: WK.walk(oracle, scene, W1, H1, 2, rec, li, mis=mis, frames=range(n))
     on_r = run(lights, True)
     on = on_r["IMAGE"][..., :3].reshape(n, -1)
     nee = run(lights, False)["IMAGE"][..., :3].reshape(n, -1)

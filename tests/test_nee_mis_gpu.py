@@ -18,6 +18,7 @@ import nee_mis as M
 import nee_paths as NP
 import nee_power as PW
 import nee_scenes as N
+import path_walker as WK
 import pathtrace_scenes as P
 import refit_moves as RM
 import test_demodulate_gpu as D
@@ -57,7 +58,8 @@ def walked(oracle, key, scene, W, H, segments, rec, lights, flags=NEE | MIS, spp
     mis, power, sphere = bool(flags & MIS), bool(flags & POWER), bool(flags & SPHERE)
     key = (key, W, H, segments, spp, len(lights), mis, power, sphere, texture is not None)
     if key not in _walked:
-        r = M.walk_nee_mis(oracle, scene, W, H, segments, rec, lights, mis=mis, power=power, sphere=sphere, spp=spp, texture=texture)
+        r = WK.walk(oracle, scene, W, H, segments, rec, lights, mis=mis, power=power, sphere=sphere, spp=spp,
+                    tex=None if texture is None else WK.Tex(*texture, None))
         for a in r.values():
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)
@@ -123,7 +125,7 @@ def test_light_find_equals_the_restatement(hip_lib, n):
 @pytest.mark.parametrize("vflags", [0, FORCE_BVH], ids=["brute", "bvh"])
 @pytest.mark.parametrize("name", ["nee_wall_lamp", "nee_two_lamps", "nee_occluder", "nee_unequal_lamps", "glass_room_two_lamps"])
 def test_frames_equal_the_walker(hip_lib, oracle, name, vflags, flags):
-    """IMAGE, HIT_ID and the ray count against walk_nee_mis, at 2 segments and at 5 (the glass room: 9), by brute force and with
+    """IMAGE, HIT_ID and the ray count against path_walker.walk, at 2 segments and at 5 (the glass room: 9), by brute force and with
     RTPT_FLAG_FORCE_BVH, with flags 0x90000, 0xD0000, 0xB0000 and 0xF0000; weighted terminals occur, and the frame is not the one
     without the MIS bit"""
     abi = hip_lib

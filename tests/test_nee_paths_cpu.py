@@ -1,6 +1,6 @@
 """Next-event estimation without a device (RTPT_FLAG_EXT_NEE; csrc/light_sample.hpp states the rules): the numpy path walker of
-tests/nee_paths.py, which tests/test_nee_paths_gpu.py holds the tile kernels to bit for bit, is first held to
-dielectric_scenes.walk where no light is sampled, then to the estimator it replaces — the mean of its frames against the mean of
+tests/path_walker.py, which tests/test_nee_paths_gpu.py holds the tile kernels to bit for bit, is first held to the recorded frames of
+the walker without light samples where no light is sampled, then to the estimator it replaces — the mean of its frames against the mean of
 the flag-off walker's, the integral both estimate; the light list's rule on hand-made cases and in a program of its own under
 the sanitizers (csrc/tests/light_list_host_check.cpp); and every entry point of the binding has its ctypes signature."""
 import os
@@ -12,6 +12,7 @@ import pytest
 import dielectric_scenes as DS
 import nee_paths as NP
 import nee_scenes as N
+import path_walker as WK
 import pathtrace_scenes as P
 from conftest import ROOT, bits
 
@@ -28,27 +29,27 @@ ESTIMATOR_FRAMES = 8192
 @pytest.mark.parametrize("form", ["small", "pairs"])
 def test_walker_without_lights_is_the_dielectric_walker(oracle, form, segments):
     """the glass room (diffuse, mirror-free, dielectric and emissive hits) at 70 x 10: with an empty list — NEE off, or L = 0 —
-    walk_nee takes no light draw and is dielectric_scenes.walk bit for bit, IMAGE, HIT_ID and rays; and a room whose lamp is dark has
-    an empty list of its own"""
+    the walker takes no light draw and is the recorded dielectric_scenes.walk bit for bit, IMAGE, HIT_ID and rays; and a room whose
+    lamp is dark has an empty list of its own"""
     scene, glass = DS.glass_room(form)
     rec = DS.records(scene, None, glass)
-    want = DS.walk(oracle, scene, W1, H1, segments, rec)
-    got = NP.walk_nee(oracle, scene, W1, H1, segments, rec, np.zeros(0, U32))
+    want = WK.recorded("nee_paths/DS", form, segments, "lit")
+    got = WK.walk(oracle, scene, W1, H1, segments, rec, np.zeros(0, U32))
     assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and np.array_equal(got["HIT_ID"], want["HIT_ID"])
     assert got["rays"] == want["rays"] and got["samples"] == 0
     dark = scene._replace(materials=P._frozen(np.where(np.arange(6)[None, :] >= 3, 0, np.asarray(scene.materials))))
     rec_dark = DS.records(dark, None, glass)
     assert len(NP.light_list(dark, 1, rec_dark)) == 0 and len(NP.light_list(scene, 1, rec)) == (2 if form == "small" else 18)
     if segments == 9:
-        want = DS.walk(oracle, dark, W1, H1, segments, rec_dark, spp=2)
-        got = NP.walk_nee(oracle, dark, W1, H1, segments, rec_dark, NP.light_list(dark, 1, rec_dark), spp=2)
+        want = WK.recorded("nee_paths/DS", form, segments, "dark")
+        got = WK.walk(oracle, dark, W1, H1, segments, rec_dark, NP.light_list(dark, 1, rec_dark), spp=2)
         assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and got["rays"] == want["rays"]
 
 
 # ------------------------------------------------------------------------------------------ the estimator is right
 def test_nee_estimates_what_the_path_tracer_estimates(oracle):
-    """nee_scenes.receiver() at 70 x 10, two segments, pixel_jitter 0, frames 0 .. N - 1: the per-pixel mean of walk_nee's frames
-    against the mean of the flag-off walker's (dielectric_scenes.walk, the code the oracle pins) — the same integral, the lamp seen
+    """nee_scenes.receiver() at 70 x 10, two segments, pixel_jitter 0, frames 0 .. N - 1: the per-pixel mean of the walker's frames
+    against the mean of its frames without the list (the code the oracle pins) — the same integral, the lamp seen
     by a sample from the first hit on one side and by running into it on the other — within 5 standard errors of the difference
     at every pixel and channel, none left out; and the summed per-pixel variance of the NEE frames is below the flag-off frames'.
     At 70 x 10 the frame is seven times wider than tall: 160 pixels meet the receiver, the other 540 see the sky along their
@@ -66,8 +67,8 @@ def test_nee_estimates_what_the_path_tracer_estimates(oracle):
     on = np.zeros((n, H1 * W1 * 3), F32)
     off = np.zeros_like(on)
     for f in range(n):
-        on[f] = NP.walk_nee(oracle, scene, W1, H1, 2, rec, lights, frame=f)["IMAGE"][..., :3].ravel()
-        off[f] = DS.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
+        on[f] = WK.walk(oracle, scene, W1, H1, 2, rec, lights, frame=f)["IMAGE"][..., :3].ravel()
+        off[f] = WK.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
     a, b = on.astype(np.float64), off.astype(np.float64)
     se = np.sqrt(a.var(0, ddof=1) / n + b.var(0, ddof=1) / n)
     diff = a.mean(0) - b.mean(0)
@@ -83,7 +84,7 @@ def test_nee_estimates_what_the_path_tracer_estimates(oracle):
 
 def test_receiver_form_factor_bounds_the_frame_count(oracle):
     """the reasoning behind ESTIMATOR_FRAMES: the lamp's form factor at the receiver's hit points"""
-    hit = DS.walk(oracle, N.receiver(), W1, H1, 1, DS.records(N.receiver()))["HIT_ID"]
+    hit = WK.walk(oracle, N.receiver(), W1, H1, 1, DS.records(N.receiver()))["HIT_ID"]
     ys, xs = np.nonzero(hit)
     assert len(ys) == 160 and set(hit[ys, xs]) == {1, 2}
     ux, uy = (2 * (xs + 0.5) - W1) / H1, -(2 * (ys + 0.5) - H1) / H1       # raytrace.comp.glsl:315-316, pixel_jitter 0

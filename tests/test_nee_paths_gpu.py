@@ -1,6 +1,6 @@
 """Next-event estimation in the tile kernels (RTPT_FLAG_EXT_NEE; csrc/light_sample.hpp states the rules), in the order of what each
 check can catch: the light list as it stands on the device against tests/nee_paths.light_list — the narrowest test of the upload,
-able to run alone — then whole frames against the numpy walker nee_paths.walk_nee (held on the CPU by
+able to run alone — then whole frames against the numpy walker path_walker.walk (held on the CPU by
 tests/test_nee_paths_cpu.py), IMAGE, HIT_ID and the ray count bit for bit; demodulation; the identities of a context whose list is
 empty; lifetime and the launches a sampling frame does not take; and the two hosts.  Every test but
 test_flag_off_is_the_existing_walker fails on a library without the feature."""
@@ -16,6 +16,7 @@ import dielectric_scenes as DS
 import filter_planes as FP
 import nee_paths as NP
 import nee_scenes as N
+import path_walker as WK
 import pathtrace_scenes as P
 import test_demodulate_gpu as D
 import test_pathtrace_scenes_gpu as T
@@ -64,7 +65,7 @@ def walked(oracle, key, scene, W, H, segments, rec, lights, spp=1, rows=None, te
     """the walker's frame, computed once and left unchanged"""
     key = (key, W, H, segments, spp, len(lights))
     if key not in _walked:
-        r = NP.walk_nee(oracle, scene, W, H, segments, rec, lights, spp=spp, texture=texture)
+        r = WK.walk(oracle, scene, W, H, segments, rec, lights, spp=spp, tex=None if texture is None else WK.Tex(*texture, None))
         for a in r.values():
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)
@@ -165,7 +166,7 @@ def test_glass_room_equals_the_walker(hip_lib, oracle, form, base, segments):
     abi = hip_lib
     scene, glass, rec, lights = glass_room(form)
     want = walked(oracle, "glass_room_" + form, scene, W0, H0, segments, rec, lights)
-    off = DS.walk(oracle, scene, W0, H0, segments, rec) if segments == 9 and form == "small" and not base else None
+    off = WK.walk(oracle, scene, W0, H0, segments, rec) if segments == 9 and form == "small" and not base else None
     assert want["lit"] > 0 and want["queries"] > want["lit"], "the box shadows some samples"
     if off is not None:
         assert not np.array_equal(bits(off["IMAGE"]), bits(want["IMAGE"])) and want["rays"] > off["rays"]
@@ -346,10 +347,10 @@ def test_flag_on_without_an_emitter_is_flag_off(hip_lib, oracle):
 
 
 def test_flag_off_is_the_existing_walker(hip_lib, oracle):
-    """without the flag the glass room with its lamp is dielectric_scenes.walk's frame (this one passes without the feature too)"""
+    """without the flag the glass room with its lamp is the walker's frame without lights (this one passes without the feature too)"""
     abi = hip_lib
     scene, glass = DS.glass_room("small")
-    want = DS.walk(oracle, scene, W0, H0, 9, DS.records(scene, None, glass))
+    want = WK.walk(oracle, scene, W0, H0, 9, DS.records(scene, None, glass))
     with context(abi, scene, W0, H0, 9, flags=0) as ctx:
         upload(abi, ctx, scene, glass)
         got = frame(abi, oracle, ctx, scene, W0, H0)

@@ -1,7 +1,8 @@
 """The weighted light pick of next-event estimation without a device (RTPT_FLAG_EXT_NEE_POWER; csrc/light_sample.hpp states the
 rules): the numpy restatement of tests/nee_power.py, which tests/test_nee_power_gpu.py holds the table builder, the pick and the
 tile kernels to bit for bit, is first held to exact arithmetic — the table to Python integers and Fractions on hostile weights,
-the pick to an enumeration of all 2^24 draws — then to the walkers it extends, and then to the estimator it replaces: the mean
+the pick to an enumeration of all 2^24 draws — then the walker of tests/path_walker.py with the flag off to the recorded frames of the
+walkers without it, and then to the estimator it replaces: the mean
 of its frames against the mean of the flag-off walker's."""
 from fractions import Fraction
 
@@ -12,7 +13,7 @@ import dielectric_scenes as DS
 import nee_paths as NP
 import nee_power as PW
 import nee_scenes as N
-import nee_sphere as NS
+import path_walker as WK
 from conftest import bits
 
 F32, U32, U64 = np.float32, np.uint32, np.uint64
@@ -119,16 +120,17 @@ def test_pick_enumerated_over_every_draw(name):
 
 # ------------------------------------------------------------------------------------------ the walker against the walkers
 def test_equal_weights_pick_as_the_uniform_walker(oracle):
-    """nee_power.equal_lamps(): four emitters of one weight, L = 4 divides 2^16 and u_l * 4 is exact, so the weighted walker picks
-    the entries walk_nee picks and, with inv_p = 4.0f = float(L), renders its frame bit for bit, rays included"""
+    """nee_power.equal_lamps(): four emitters of one weight, L = 4 divides 2^16 and u_l * 4 is exact, so the weighted walk picks
+    the entries the uniform one picks and, with inv_p = 4.0f = float(L), renders the recorded frame of nee_paths.walk_nee bit for bit,
+    rays included"""
     scene = PW.equal_lamps()
     rec = DS.records(scene)
     lights = NP.light_list(scene)
     assert PW.table(PW.weights(oracle, scene.tris, rec, lights)).tolist() == [65536, 131072, 196608, 262144]
     for segments in (2, 5):
-        got = PW.walk_nee_power(oracle, scene, W0, H0, segments, rec, lights)
-        off = PW.walk_nee_power(oracle, scene, W0, H0, segments, rec, lights, power=False)
-        want = NP.walk_nee(oracle, scene, W0, H0, segments, rec, lights)
+        got = WK.walk(oracle, scene, W0, H0, segments, rec, lights, power=True)
+        off = WK.walk(oracle, scene, W0, H0, segments, rec, lights, power=False)
+        want = WK.recorded("nee_power_equal/NP", segments)
         assert (got["picks"] == off["picks"]).all() and got["picks"].min() > 0
         assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and np.array_equal(got["HIT_ID"], want["HIT_ID"])
         assert got["rays"] == want["rays"] and got["lit"] == want["lit"] > 0
@@ -136,23 +138,23 @@ def test_equal_weights_pick_as_the_uniform_walker(oracle):
 
 @pytest.mark.parametrize("sphere", [False, True], ids=["triangles", "both"])
 def test_power_off_is_the_sphere_walker(oracle, sphere):
-    """with `power` off walk_nee_power is nee_sphere.walk_nee_sphere bit for bit — IMAGE, HIT_ID, rays and every count — on the
+    """with `power` off the walker is the recorded nee_sphere.walk_nee_sphere bit for bit — IMAGE, HIT_ID, rays and every count — on the
     glass room with its second lamp (diffuse, dielectric and emissive hits), 9 segments and two samples, and on two_lamps; and
     with it on the frame differs"""
     scene, glass, rec = PW.glass_room_two_lamps()
     lights = NP.light_list(scene, 1, rec)
     assert len(lights) == 4
     for sc, r, li, seg, spp in ((scene, rec, lights, 9, 2), (NP.two_lamps(), DS.records(NP.two_lamps()), NP.light_list(NP.two_lamps()), 5, 1)):
-        want = NS.walk_nee_sphere(oracle, sc, W1, H1, seg, r, li, sphere, spp=spp)
-        got = PW.walk_nee_power(oracle, sc, W1, H1, seg, r, li, sphere=sphere, power=False, spp=spp)
+        want = WK.recorded("nee_power/NS", sc.name, seg, spp, sphere)
+        got = WK.walk(oracle, sc, W1, H1, seg, r, li, sphere=sphere, power=False, spp=spp)
         assert np.array_equal(bits(got["IMAGE"]), bits(want["IMAGE"])) and np.array_equal(got["HIT_ID"], want["HIT_ID"])
         for k in want:
             if not isinstance(want[k], np.ndarray):
                 assert got[k] == want[k], k
-        on = PW.walk_nee_power(oracle, sc, W1, H1, seg, r, li, sphere=sphere, spp=spp)
+        on = WK.walk(oracle, sc, W1, H1, seg, r, li, sphere=sphere, power=True, spp=spp)
         assert not np.array_equal(bits(on["IMAGE"]), bits(want["IMAGE"])) and on["samples"] == want["samples"]
-    empty = PW.walk_nee_power(oracle, scene, W1, H1, 9, rec, NONE, sphere=True)
-    want = NS.walk_nee_sphere(oracle, scene, W1, H1, 9, rec, NONE, True)
+    empty = WK.walk(oracle, scene, W1, H1, 9, rec, NONE, sphere=True, power=True)
+    want = WK.recorded("nee_power/NS", "empty")
     assert np.array_equal(bits(empty["IMAGE"]), bits(want["IMAGE"])), "an empty list: nothing to pick"
 
 
@@ -164,8 +166,8 @@ def test_the_degenerate_emitter_is_never_picked(oracle):
     lights = NP.light_list(scene)
     w = PW.weights(oracle, scene.tris, rec, lights)
     assert len(lights) == 5 and w[4] == 0 and (w[:4] > 0).all()
-    on = PW.walk_nee_power(oracle, scene, W0, H0, 3, rec, lights)
-    off = PW.walk_nee_power(oracle, scene, W0, H0, 3, rec, lights, power=False)
+    on = WK.walk(oracle, scene, W0, H0, 3, rec, lights, power=True)
+    off = WK.walk(oracle, scene, W0, H0, 3, rec, lights, power=False)
     assert on["picks"][4] == 0 and off["picks"][4] > 0 and on["queries"] > off["queries"]
 
 
@@ -173,7 +175,7 @@ def test_the_degenerate_emitter_is_never_picked(oracle):
 @pytest.mark.parametrize("name", ["two_lamps", "receiver"])
 def test_weighted_nee_estimates_what_the_path_tracer_estimates(oracle, name):
     """nee_paths.two_lamps() and nee_scenes.receiver() at 70 x 10, two segments, frames 0 .. 8191: the per-pixel mean of
-    walk_nee_power's frames against the mean of the flag-off walker's (dielectric_scenes.walk) within 5 standard errors of the
+    the weighted walker's frames against the mean of the flag-off walker's (no list) within 5 standard errors of the
     difference at every pixel and channel, none left out — the bar of test_nee_paths_cpu.py and test_nee_sphere_cpu.py, where the
     pixels that see the sky store the same bits on both sides and have to differ by exactly 0.  The ratio of the summed per-pixel
     variance, weighted against uniform, is printed: a measurement, not a bar.
@@ -187,9 +189,9 @@ def test_weighted_nee_estimates_what_the_path_tracer_estimates(oracle, name):
     uni = np.zeros_like(on)
     off = np.zeros_like(on)
     for f in range(n):
-        on[f] = PW.walk_nee_power(oracle, scene, W1, H1, 2, rec, lights, frame=f)["IMAGE"][..., :3].ravel()
-        uni[f] = PW.walk_nee_power(oracle, scene, W1, H1, 2, rec, lights, power=False, frame=f)["IMAGE"][..., :3].ravel()
-        off[f] = DS.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
+        on[f] = WK.walk(oracle, scene, W1, H1, 2, rec, lights, power=True, frame=f)["IMAGE"][..., :3].ravel()
+        uni[f] = WK.walk(oracle, scene, W1, H1, 2, rec, lights, power=False, frame=f)["IMAGE"][..., :3].ravel()
+        off[f] = WK.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
     a, b, c = on.astype(np.float64), off.astype(np.float64), uni.astype(np.float64)
     se = np.sqrt(a.var(0, ddof=1) / n + b.var(0, ddof=1) / n)
     diff = a.mean(0) - b.mean(0)

@@ -16,6 +16,7 @@ import filter_planes as FP
 import nee_paths as NP
 import nee_power as PW
 import nee_scenes as N
+import path_walker as WK
 import pathtrace_scenes as P
 import refit_moves as RM
 import test_demodulate_gpu as D
@@ -58,7 +59,8 @@ def walked(oracle, key, scene, W, H, segments, rec, lights, sphere=False, power=
     """the walker's frame, computed once and left unchanged"""
     key = (key, W, H, segments, spp, len(lights), sphere, power, texture is not None)
     if key not in _walked:
-        r = PW.walk_nee_power(oracle, scene, W, H, segments, rec, lights, sphere=sphere, power=power, spp=spp, texture=texture)
+        r = WK.walk(oracle, scene, W, H, segments, rec, lights, sphere=sphere, power=power, spp=spp,
+                    tex=None if texture is None else WK.Tex(*texture, None))
         for a in r.values():
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)
@@ -154,7 +156,7 @@ def test_pick_equals_the_restatement(hip_lib, name):
 @pytest.mark.parametrize("vflags", [0, FORCE_BVH], ids=["brute", "bvh"])
 @pytest.mark.parametrize("name", ["nee_two_lamps", "nee_occluder", "nee_unequal_lamps", "glass_room_two_lamps"])
 def test_frames_equal_the_walker(hip_lib, oracle, name, vflags, flags):
-    """IMAGE, HIT_ID and the ray count against walk_nee_power, at 2 segments and at 5 (the glass room: 9), by brute force and with
+    """IMAGE, HIT_ID and the ray count against path_walker.walk, at 2 segments and at 5 (the glass room: 9), by brute force and with
     RTPT_FLAG_FORCE_BVH, with flags 0x50000 and 0x70000; and the frame is not the uniform pick's"""
     abi = hip_lib
     scene, glass, rec, lights = scenes()[name]

@@ -1,7 +1,8 @@
 """The sphere sample of next-event estimation without a device (RTPT_FLAG_EXT_NEE_SPHERE; csrc/light_sample.hpp states the rules):
 the float32 restatement tests/test_nee_sphere_gpu.py holds the device function to is itself held to float64 on seeded cases and
 to the closed form of a sphere's irradiance through the mean of the weight on the contract's own draws; the walker of
-tests/nee_sphere.py is first held to the existing walkers where no sphere is sampled, then to the estimator it replaces; and the
+tests/path_walker.py is first held to the recorded frames of the walkers without it where no sphere is sampled, then to the estimator
+it replaces; and the
 entry point has its signature in the binding."""
 import os
 import re
@@ -14,6 +15,7 @@ import dielectric_scenes as DS
 import nee_paths as NP
 import nee_scenes as N
 import nee_sphere as NS
+import path_walker as WK
 import pathtrace_scenes as P
 from conftest import ROOT, bits
 
@@ -85,7 +87,7 @@ def _hit_points(oracle, scene, W, H):
     _, d = DS._primary(oracle, cfg, rng0, xs, ys)
     tris = np.ascontiguousarray(scene.tris, F32)
     o = np.broadcast_to(F32(scene.cam), (k, 3)).astype(F32).copy()
-    ids, b1, b2 = DS._closest_hits(oracle, tris, o, d, float(cfg.ray_tmax))
+    ids, _, b1, b2 = WK.closest_hits(oracle, tris, o, d, float(cfg.ray_tmax))
     assert (ids >= 1).all() and (ids <= 2).all(), "every primary ray meets the receiver"
     tri = tris[ids.astype(np.int64) - 1]
     b0 = ((F32(1.0) - b1).astype(F32) - b2).astype(F32)
@@ -202,23 +204,23 @@ def _same(got, want):
 
 
 def test_walker_reduces_to_the_existing_walkers(oracle):
-    """at 70 x 10 on the glass room with the light inside, 9 segments and two samples of 5: sphere=False with an empty list is
-    dielectric_scenes.walk, sphere=False with the room's list is nee_paths.walk_nee, and max_segments = 1 with sphere=True is flag
-    off — IMAGE, HIT_ID and rays bit for bit"""
+    """at 70 x 10 on the glass room with the light inside, 9 segments and two samples of 5: sphere=False with an empty list is the
+    recorded dielectric_scenes.walk, sphere=False with the room's list is the recorded nee_paths.walk_nee, and max_segments = 1 with
+    sphere=True is flag off — IMAGE, HIT_ID and rays bit for bit"""
     scene, glass = NS.glass_room_lit("small")
     rec = DS.records(scene, None, glass)
     lights = NP.light_list(scene, 1, rec)
     none = np.zeros(0, U32)
     for segments, spp in ((9, 1), (5, 2)):
-        off = NS.walk_nee_sphere(oracle, scene, W1, H1, segments, rec, none, False, spp=spp)
-        assert _same(off, DS.walk(oracle, scene, W1, H1, segments, rec, spp=spp)) and off["sphere_samples"] == 0
-        tri = NS.walk_nee_sphere(oracle, scene, W1, H1, segments, rec, lights, False, spp=spp)
-        assert _same(tri, NP.walk_nee(oracle, scene, W1, H1, segments, rec, lights, spp=spp)) and tri["samples"] > 0
-        on = NS.walk_nee_sphere(oracle, scene, W1, H1, segments, rec, none, True, spp=spp)
+        off = WK.walk(oracle, scene, W1, H1, segments, rec, none, False, spp=spp)
+        assert _same(off, WK.recorded("nee_sphere/DS", segments, spp)) and off["sphere_samples"] == 0
+        tri = WK.walk(oracle, scene, W1, H1, segments, rec, lights, False, spp=spp)
+        assert _same(tri, WK.recorded("nee_sphere/NP", segments, spp)) and tri["samples"] > 0
+        on = WK.walk(oracle, scene, W1, H1, segments, rec, none, True, spp=spp)
         assert on["sphere_valid"] > 0 and on["sphere_dropped"] > 0 and not np.array_equal(bits(on["IMAGE"]), bits(off["IMAGE"]))
         assert on["queries"] == 0, "the sphere sample sends no query"
-    one = NS.walk_nee_sphere(oracle, scene, W1, H1, 1, rec, lights, True, spp=2)
-    assert _same(one, DS.walk(oracle, scene, W1, H1, 1, rec, spp=2)) and one["sphere_samples"] == 0 and one["samples"] == 0
+    one = WK.walk(oracle, scene, W1, H1, 1, rec, lights, True, spp=2)
+    assert _same(one, WK.recorded("nee_sphere/DS", 1, 2)) and one["sphere_samples"] == 0 and one["samples"] == 0
 
 
 def test_normal_keyed_records_are_the_oracles_colours(oracle):
@@ -226,14 +228,14 @@ def test_normal_keyed_records_are_the_oracles_colours(oracle):
     scene = NS.three_ends_plain()
     rec = NS.normal_keyed_records(oracle, scene)
     want = P.oracle_frame(oracle, scene, W1, H1, 5)
-    got = NS.walk_nee_sphere(oracle, scene, W1, H1, 5, rec, np.zeros(0, U32), False)
+    got = WK.walk(oracle, scene, W1, H1, 5, rec, np.zeros(0, U32), False)
     assert _same(got, want)
 
 
 # ------------------------------------------------------------------------------------------ the estimator is right
 def test_sphere_nee_estimates_what_the_path_tracer_estimates(oracle):
     """the receiver under the near sphere at 70 x 10, two segments, pixel_jitter 0, frames 0 .. N - 1 (N = test_nee_paths_cpu's): the
-    per-pixel mean of walk_nee_sphere's frames (sphere alone, no list) against the mean of the flag-off walker's — the same
+    per-pixel mean of the walker's frames (sphere alone, no list) against the mean of the flag-off walker's — the same
     integral — within 5 standard errors of the difference at every pixel and channel, none left out (a pixel whose two sides
     store the same bits in every frame has to differ by exactly 0).
     Measured: max |z| 3.89 over 2100 values (none above 4; 474 with a standard error above 0); summed variance sphere / flag-off
@@ -245,8 +247,8 @@ def test_sphere_nee_estimates_what_the_path_tracer_estimates(oracle):
     on = np.zeros((n, H1 * W1 * 3), F32)
     off = np.zeros_like(on)
     for f in range(n):
-        on[f] = NS.walk_nee_sphere(oracle, scene, W1, H1, 2, rec, none, True, frame=f)["IMAGE"][..., :3].ravel()
-        off[f] = DS.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
+        on[f] = WK.walk(oracle, scene, W1, H1, 2, rec, none, True, frame=f)["IMAGE"][..., :3].ravel()
+        off[f] = WK.walk(oracle, scene, W1, H1, 2, rec, frame=f)["IMAGE"][..., :3].ravel()
     a, b = on.astype(np.float64), off.astype(np.float64)
     se = np.sqrt(a.var(0, ddof=1) / n + b.var(0, ddof=1) / n)
     diff = a.mean(0) - b.mean(0)

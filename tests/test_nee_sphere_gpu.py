@@ -16,6 +16,7 @@ import filter_planes as FP
 import nee_paths as NP
 import nee_scenes as N
 import nee_sphere as NS
+import path_walker as WK
 import test_demodulate_gpu as D
 import test_pathtrace_scenes_gpu as T
 from conftest import bits
@@ -61,7 +62,7 @@ def walked(oracle, scene, W, H, segments, rec, lights, sphere=True, spp=1, frame
     """the walker's frame, computed once and left unchanged"""
     key = (scene.name, scene.form, W, H, segments, spp, len(lights), sphere, frame_no)
     if key not in _walked:
-        r = NS.walk_nee_sphere(oracle, scene, W, H, segments, rec, lights, sphere, frame=frame_no, spp=spp)
+        r = WK.walk(oracle, scene, W, H, segments, rec, lights, sphere, frame=frame_no, spp=spp)
         for a in r.values():
             if isinstance(a, np.ndarray):
                 a.setflags(write=False)
@@ -209,7 +210,7 @@ def test_light_far(hip_lib, oracle):
     rec = DS.records(scene, None, glass)
     want = walked(oracle, scene, W0, H0, 5, rec, NONE)
     assert want["sphere_taken"] == want["sphere_samples"] > want["sphere_valid"] > 0.1 * want["sphere_samples"], want
-    off = DS.walk(oracle, scene, W0, H0, 5, rec)
+    off = WK.walk(oracle, scene, W0, H0, 5, rec)
     assert not np.array_equal(bits(off["IMAGE"]), bits(want["IMAGE"]))
     with context(abi, scene, W0, H0, 5) as ctx:
         upload(abi, ctx, scene, glass)
@@ -280,10 +281,10 @@ def test_one_segment_with_the_flag_is_flag_off(hip_lib, oracle):
 
 
 def test_flag_off_is_the_existing_walker(hip_lib, oracle):
-    """without the flag the lit glass room is dielectric_scenes.walk's frame (this one passes without the feature too)"""
+    """without the flag the lit glass room is the walker's frame without lights (this one passes without the feature too)"""
     abi = hip_lib
     scene, glass, rec = lit_room("small")
-    want = DS.walk(oracle, scene, W0, H0, 9, rec)
+    want = WK.walk(oracle, scene, W0, H0, 9, rec)
     with context(abi, scene, W0, H0, 9, flags=0) as ctx:
         upload(abi, ctx, scene, glass)
         got = frame(abi, oracle, ctx, scene, W0, H0)

@@ -1,5 +1,5 @@
 """tests/normal_paths.py — the numpy restatement of smooth shading (csrc/shading_normal.hpp) — held to what it rests on, without a GPU:
-lattice_paths.walk where no triangle is smooth, float64 where they are, the exact sphere, float64 det(L) inv(L)^T for the cofactor
+the recorded frames of the walker that knew no normals where no triangle is smooth, float64 where they are, the exact sphere, float64 det(L) inv(L)^T for the cofactor
 function, and the `vn` reader against the files of tests/golden/obj_normals/."""
 import ctypes as C
 import os
@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-import lattice_paths as LP
+import path_walker as WK
 import normal_paths as NP
 
 F32 = np.float32
@@ -25,20 +25,24 @@ def _same(a, b, tag):
 @pytest.mark.parametrize("name", list(NP.CASES))
 @pytest.mark.parametrize("spec", [2, 4, 5])
 def test_without_a_smooth_triangle_it_is_the_lattice_walker(oracle, name, spec):
-    """every tri_smooth 0 (and no normals at all): lattice_paths.walk bit for bit, the mixed atlas, DEMOD off and on"""
+    """every tri_smooth 0 (and no normals at all): the recorded lattice_paths.walk bit for bit, the mixed atlas, DEMOD off and on;
+    and the two ways of having nothing smooth give each other's frame"""
     c, nrm = NP.case(oracle, name)
     s = NP.setup(oracle, c, spec)
     off = nrm._replace(tri_smooth=np.zeros_like(nrm.tri_smooth))
-    tex = LP.textures(c.sh, 2)
+    tex = WK.textures(c.sh, 2)
     for demod in (False, True):
         kw = dict(rec=s["rec"], lights=s["lights"], sphere=s["sphere"], power=s["power"], tex=tex, demod=demod)
-        ref = LP.walk(oracle, c.sh.scene, W, H, 4, **kw)
+        ref = WK.recorded("normal_paths/LP" + ("/demod" if demod else ""), name, spec, demod)
+        frames = []
         for n in (off, None):
-            got = NP.walk(oracle, c.sh.scene, W, H, 4, normals=n, n_base=len(nrm.tri_smooth), **kw)
+            got = WK.walk(oracle, c.sh.scene, W, H, 4, normals=n, n_base=len(nrm.tri_smooth), **kw)
             _same(got, ref, (name, spec, demod, n is None))
             if demod:
                 assert np.array_equal(got["ALBEDO"].view(np.uint32), ref["ALBEDO"].view(np.uint32))
             assert got["smooth"] == 0 and got["absorbed"] == 0 and got["side_invalid"] == 0 and got["offset_changed"] == 0
+            frames.append(got)
+        _same(frames[0], frames[1], (name, spec, demod, "tri_smooth 0 against None"))
 
 
 # ------------------------------------------------------------------------------------------ 2. with normals: float64
@@ -79,8 +83,9 @@ def test_with_normals_it_matches_float64(oracle, name):
     c, nrm = NP.case(oracle, name)
     s = NP.setup(oracle, c, 10)
     hits = []
-    r = NP.walk(oracle, c.sh.scene, W, H, 4, normals=nrm, hits=hits, **s)
-    h = LP.hit_table(hits)
+    r = WK.walk(oracle, c.sh.scene, W, H, 4, normals=nrm, hits=hits, **s)
+    h = WK.hit_table(hits)
+    h = {k: v[h["bounced"]] for k, v in h.items()}      # a hit on a path's last segment has no bounce to judge
     n_base = len(nrm.tri_smooth)
     rec_smooth = np.asarray(nrm.tri_smooth)[(h["id"] - 1) % n_base] != 0
     ns64, flip, facing, ok4 = _replay64(nrm, n_base, {k: v[rec_smooth] for k, v in h.items()})
@@ -110,7 +115,7 @@ def test_with_normals_it_matches_float64(oracle, name):
     _offset_changed[name] = r["offset_changed"]
     # what the scenes must show, by the walker alone
     for k in ("smooth", "fallback4", "fallback7", "absorbed", "transmitted", "reflected", "lit", "sphere_valid"):
-        assert r[k] > 0, (name, k, {q: r[q] for q in NP.COUNTS if q in r})
+        assert r[k] > 0, (name, k, {q: r[q] for q in WK.COUNTS if q in r})
 
 
 def test_the_offset_rule_decides_somewhere(oracle):
@@ -118,7 +123,7 @@ def test_the_offset_rule_decides_somewhere(oracle):
     for name in NP.CASES:
         if name not in _offset_changed:
             c, nrm = NP.case(oracle, name)
-            _offset_changed[name] = NP.walk(oracle, c.sh.scene, W, H, 4, normals=nrm, **NP.setup(oracle, c, 10))["offset_changed"]
+            _offset_changed[name] = WK.walk(oracle, c.sh.scene, W, H, 4, normals=nrm, **NP.setup(oracle, c, 10))["offset_changed"]
     assert max(_offset_changed.values()) > 0, _offset_changed
 
 

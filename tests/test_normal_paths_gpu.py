@@ -1,6 +1,6 @@
 """Smooth shading (rtpt_scene_set_normals) on the device against tests/normal_paths.py, whole frames bit for bit: IMAGE, HIT_ID, the
 ray count and, with RTPT_FLAG_EXT_DEMODULATE, ALBEDO.  No tolerance appears anywhere.  tests/test_normal_paths_cpu.py holds the walker
-to lattice_paths.walk and to float64 first.
+to the walker without normals and to float64 first.
 
 Frames are 70 x 10: one full tile column, a partial one, partial tile rows.  Both scenes have more than 64 triangles in three
 instances — the identity, a rotation with a non-uniform scale, a mirror — so they trace through the BVH: over triangles (uv_sphere,
@@ -17,7 +17,7 @@ import pytest
 
 import filter_planes as FP
 import gbuffer_scenes as G
-import lattice_paths as LP
+import path_walker as WK
 import normal_paths as NP
 import pathtrace_scenes as P
 import shading_scenes as SS
@@ -67,7 +67,7 @@ def reference(oracle, name, spec, tex, demod, spp, segments, moved=False, model=
         c, nrm = NP.case(oracle, name, moved, model)
         if not smooth:
             nrm = nrm._replace(tri_smooth=np.zeros_like(nrm.tri_smooth))
-        r = NP.walk(oracle, c.sh.scene, W, H, segments, normals=nrm, spp=spp, tex=LP.textures(c.sh, tex), demod=demod, rows=rows, frame=frame,
+        r = WK.walk(oracle, c.sh.scene, W, H, segments, normals=nrm, spp=spp, tex=WK.textures(c.sh, tex), demod=demod, rows=rows, frame=frame,
                     **NP.setup(oracle, c, spec))
         FP.check_ids(r["HIT_ID"], len(c.sh.scene.tris))
         for a in r.values():
@@ -295,7 +295,7 @@ def test_a_small_scene_moves_onto_its_tree_and_back(hip_lib, oracle, monkeypatch
     s = NP.setup(oracle, c, spec)
 
     def want(normals, frame_no):
-        return NP.walk(oracle, sc, W, H, seg, normals=normals, frame=frame_no, n_base=len(nrm.tri_smooth), **s)
+        return WK.walk(oracle, sc, W, H, seg, normals=normals, frame=frame_no, n_base=len(nrm.tri_smooth), **s)
     with context(abi, c, seg, flags_of(spec, False)) as ctx:
         ctx.scene_upload(c.sh.mesh[0], c.sh.mesh[1])
         ctx.set_materials_ext(sc.tri_material, abi.materials_ext(sc.materials, c.sh.spec, c.glass))
@@ -304,7 +304,7 @@ def test_a_small_scene_moves_onto_its_tree_and_back(hip_lib, oracle, monkeypatch
         ctx.set_normals(c.tri_normals, c.tri_smooth)
         compare(frame(abi, oracle, ctx, c, False, 1), want(nrm, 1), ("small", "smooth"))
         ctx.end_frame()
-        compare(frame(abi, oracle, ctx, c, False, 2, MODEL), NP.walk(oracle, _posed(oracle, sc), W, H, seg, normals=nrm._replace(cof=NP.cof_table(oracle, MODEL)),
+        compare(frame(abi, oracle, ctx, c, False, 2, MODEL), WK.walk(oracle, _posed(oracle, sc), W, H, seg, normals=nrm._replace(cof=NP.cof_table(oracle, MODEL)),
                                                                        frame=2, **s), ("small", "smooth, model"))
         ctx.end_frame()
         ctx.set_normals(None)
