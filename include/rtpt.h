@@ -307,6 +307,32 @@ typedef struct rtpt_visibility_data {
                                       segment in the tile kernel, no queues, no deferred final filter pass).
                                       Additive: the ABI version stays 5 */
 
+#define RTPT_FLAG_EXT_SMOOTH_GUIDE 0x100000u /* the filter's edge stop reads INTERPOLATED normals (NOT reference behaviour, default off;
+                                      DESIGN.md 8, csrc/shading_normal.hpp states the rules G1-G5).  It is ACTIVE while the context has
+                                      the flag and the scene holds normals (rtpt_scene_set_normals); in every other case it is ignored
+                                      (as the POWER bit is without the NEE bit), and then every frame, plane, ray count, kernel and
+                                      allocation is that of a context without it, bit for bit.
+                                      While active, K0 (rtpt_gbuffer, alone or inside the tracing launch) writes, for every pixel whose
+                                      pixel-centre ray hits a triangle, the GUIDE NORMAL into a per-pixel plane of 16 bytes a pixel,
+                                      which the context then holds for any triangle count: the corner normals interpolated with K0's
+                                      own barycentrics, carried through the hit instance's pose and normalised (rules 1-3 of smooth
+                                      shading); the triangle's normal where the record is not smooth or the result is NaN, infinite or
+                                      zero; turned to the side of the triangle's unfaced normal (inverted vn records and mirrored poses
+                                      agree with their not-smooth neighbours); independent of the ray.  The cell's fourth word is
+                                      pow(max(0, dot(ns, ns)), sigma_n).  Pixels that hit nothing keep (0, 0, 1).
+                                      Every filter kernel then weighs a tap by pow(max(0, dot(n_p, n_q)), sigma_n) of the two pixels'
+                                      cells: the LDS-staged per-pixel-normal kernel for every scene size (a scene of at most 63
+                                      triangles is treated as if it had no id-pair table: no chained launches, no deferred final pass),
+                                      the per-pixel form of the direct-load kernel for strides above 16 and RTPT_FLAG_DIRECT_FILTER, and
+                                      the per-pixel form of the generic kernel for every RTPT_FLAG_EXT_* filter mode.  K1's Phong normal,
+                                      the LUT, the reprojection, the same-primitive tests of RTPT_FLAG_EXT_DISOCCLUSION / _VARIANCE and
+                                      the id plane keep the triangle's normal and id.
+                                      STALE PLANE: a filter call whose rows read are not all covered by what K0 wrote of the plane in
+                                      this frame (rtpt_set_plane(RTPT_PLANE_VIS_ID) is one cause: the plane no longer matches the ids)
+                                      is filtered with the triangles' normals, by the kernels of a context without the flag.
+                                      The guide is part of what frame reuse keys K0 on; rtpt_scene_set_normals, setting or removing,
+                                      makes the next frame run K0 again.  Additive: the ABI version stays 5 */
+
 typedef struct rtpt_config {
   uint32_t struct_size;          /* = sizeof(rtpt_config), ABI guard */
   uint32_t width, height;        /* full frame; main.cpp:52-53 (1000x800) */
@@ -546,8 +572,9 @@ int rtpt_scene_set_textures(rtpt_ctx* ctx, const float* tri_uv, const uint32_t* 
  * included: a hit whose interpolated normal does not normalise to finite numbers shades with the geometric normal
  * (csrc/shading_normal.hpp states the rules: which normal each step of a bounce uses, and the side tests that keep rays off the
  * wrong side of the real surface).  The diffuse, specular and dielectric bounces and the light samples use the interpolated
- * normal; the offset origin, the normal-keyed colours, the texture footprint, K0, K1, the LUT and the filter keep the
- * triangle's.  A scene that holds normals is traced through its BVH, as under RTPT_FLAG_FORCE_BVH, however small it is.
+ * normal; the offset origin, the normal-keyed colours, the texture footprint, K0, K1 and the LUT keep the triangle's, and so
+ * does the filter unless the context has RTPT_FLAG_EXT_SMOOTH_GUIDE, which feeds interpolated normals to its edge stop.  A scene
+ * that holds normals is traced through its BVH, as under RTPT_FLAG_FORCE_BVH, however small it is.
  * tri_normals == NULL with n_tris == 0 removes them; rtpt_scene_upload drops them with the materials; moved instances, a changed
  * ubo.model, rtpt_scene_rebuild and rtpt_resize keep them.  RTPT_E_NO_SCENE before an upload.  RTPT_E_INVALID, with the scene
  * untouched, for: n_tris other than the uploaded mesh's; tri_normals == NULL with n_tris != 0; a context created with
@@ -616,6 +643,17 @@ int rtpt_debug_upload_info(rtpt_ctx* ctx, uint64_t out[4]);
  * freed.  Not counted: pinned host staging, events and streams, and planes bound with rtpt_bind_plane (the caller's).
  * After rtpt_destroy of every context it is 0; a test compares readings instead of the device-wide hipMemGetInfo. */
 int rtpt_debug_live_device_bytes(uint64_t* out);
+
+/* The per-pixel normal plane of the filter's edge stop: stored rows x width cells of four floats (n.xyz, self weight), what K0
+ * writes for scenes without an id-pair table (more than 63 triangles) and while RTPT_FLAG_EXT_SMOOTH_GUIDE is active.  Additive:
+ * RTPT_ABI_VERSION stays 5.
+ * rtpt_debug_guide_normals: blocking readback into out (bytes >= stored rows x width x 16).  RTPT_E_INVALID when the context has no
+ * such plane; it works without the flag too.
+ * rtpt_debug_set_guide_normals: blocking upload.  The plane then counts as written for all stored rows of the current frame, as if
+ * K0 had, until the next K0 writes it; it is allocated if needed.  Only while RTPT_FLAG_EXT_SMOOTH_GUIDE is active or the scene has
+ * no id-pair table (RTPT_E_INVALID otherwise: no filter kernel would read it). */
+int rtpt_debug_guide_normals(rtpt_ctx* ctx, float* out, size_t bytes);
+int rtpt_debug_set_guide_normals(rtpt_ctx* ctx, const float* src, size_t bytes);
 
 /* Frame reuse.  K0 and K1 (rtpt_gbuffer, rtpt_temporal_gradient) read the camera, the light, the posed scene and the LUTs
  * and nothing that changes from frame to frame by itself: no frame number, no random stream.  While all of those rest,

@@ -34,6 +34,7 @@ FLAG_EXT_NEE = 0x10000  # next-event estimation: rtpt_raytrace samples the scene
 FLAG_EXT_NEE_SPHERE = 0x20000  # next-event estimation of the analytic sphere light: every diffuse hit samples its cone, no shadow ray (csrc/light_sample.hpp); not in FLAG_EXT_MASK
 FLAG_EXT_NEE_POWER = 0x40000  # with FLAG_EXT_NEE: the emissive triangle is picked by area x emission from a cumulative table built on the device (csrc/light_table.hip); ignored alone; not in FLAG_EXT_MASK
 FLAG_EXT_NEE_MIS = 0x80000  # with FLAG_EXT_NEE: the light sample and the bounce that meets the same emitter are weighed by the power heuristic (csrc/light_sample.hpp); the sphere sample is not; ignored alone; not in FLAG_EXT_MASK
+FLAG_EXT_SMOOTH_GUIDE = 0x100000  # while the scene holds normals (set_normals): K0 writes interpolated guide normals and the filter's edge stop reads them per pixel (csrc/shading_normal.hpp G1-G5); ignored without normals; not in FLAG_EXT_MASK
 BVH_BUILDER_HOST_SAH, BVH_BUILDER_DEVICE_LBVH = 0, 1
 BUILDER_DEVICE_SAH = 2
 BVH_FALLBACK_NONE, BVH_FALLBACK_DEPTH = 0, 1
@@ -156,6 +157,7 @@ SYMBOLS = [
     "rtpt_selftest_light_table", "rtpt_selftest_light_pick", "rtpt_debug_light_table",
     "rtpt_selftest_mis_weight", "rtpt_selftest_light_find",
     "rtpt_scene_set_normals", "rtpt_selftest_shading_normal", "rtpt_util_load_obj_normals",
+    "rtpt_debug_guide_normals", "rtpt_debug_set_guide_normals",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -254,6 +256,8 @@ def load() -> C.CDLL:
         "rtpt_scene_set_normals": [vp, vp, vp, u32],
         "rtpt_selftest_shading_normal": [vp, vp, vp, sz],
         "rtpt_util_load_obj_normals": [C.c_char_p, vp, vp, C.POINTER(u32)],
+        "rtpt_debug_guide_normals": [vp, vp, sz],
+        "rtpt_debug_set_guide_normals": [vp, vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -634,6 +638,19 @@ class Context:
     def set_plane(self, which: int, arr: np.ndarray):
         arr = np.ascontiguousarray(arr)
         _check(self._lib.rtpt_set_plane(self._h, which, _ptr(arr), arr.nbytes))
+
+    def debug_guide_normals(self) -> np.ndarray:
+        """the per-pixel normal plane of the filter's edge stop (rtpt_debug_guide_normals): float32 [rows, width, 4] = (n.xyz, self
+        weight); RtptError when the context has none (a scene with an id-pair table and FLAG_EXT_SMOOTH_GUIDE not active)"""
+        out = np.zeros((self.rows, self.cfg.width, 4), np.float32)
+        _check(self._lib.rtpt_debug_guide_normals(self._h, _ptr(out), out.nbytes))
+        return out
+
+    def debug_set_guide_normals(self, cells: np.ndarray):
+        """inject that plane ([rows, width, 4] float32; rtpt_debug_set_guide_normals): it counts as written by K0 for every stored
+        row of the current frame, until the next K0"""
+        cells = np.ascontiguousarray(cells, np.float32)
+        _check(self._lib.rtpt_debug_set_guide_normals(self._h, _ptr(cells), cells.nbytes))
 
     def reset_counters(self):
         _check(self._lib.rtpt_reset_counters(self._h))

@@ -764,7 +764,7 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
              specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, nee_mis=False, smooth_normals=False,
-             **app_kw):
+             smooth_guide=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -792,7 +792,12 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     `smooth_normals` (off by default): shade with the OBJ's interpolated `vn` records (abi.load_obj_normals,
     rtpt_scene_set_normals) on every context of this rank: bounces, refraction and light samples use the interpolated normal, a
     face without normals keeps its own.  An OBJ without any `vn` is left as it is.  With `mesh`, pass the normals yourself:
-    app.backend.set_normals(tri_normals, tri_smooth)."""
+    app.backend.set_normals(tri_normals, tri_smooth).
+    `smooth_guide` (off by default): abi.FLAG_EXT_SMOOTH_GUIDE on every context of this rank — the filter's edge stop reads
+    interpolated normals too.  It implies nothing: without `smooth_normals` (or a set_normals call of the caller's) no frame
+    changes."""
+    if smooth_guide:
+        flags |= abi.FLAG_EXT_SMOOTH_GUIDE
     if smooth_normals and mesh is not None:
         raise ValueError("smooth_normals=True reads the OBJ's vn records: it needs `scene`, not `mesh`")
     if nee or nee_power or nee_mis:

@@ -186,8 +186,13 @@ rt::LightTableView light_view(const rtpt_ctx* c) {
 
 rt::NormalView normal_view(const rtpt_ctx* c) {
   const bool has = c->scene.normals.records.ptr && c->scene.normals.cof.ptr;
+  const bool guide = guide_active(c);
   return rt::NormalView{has ? static_cast<const float4*>(c->scene.normals.records.ptr) : nullptr,
-                        has ? static_cast<const float4*>(c->scene.normals.cof.ptr) : nullptr};
+                        has ? static_cast<const float4*>(c->scene.normals.cof.ptr) : nullptr, guide ? 1u : 0u, guide ? c->cfg.sigma_n : 0};
+}
+
+bool guide_active(const rtpt_ctx* c) {
+  return (c->cfg.flags & RTPT_FLAG_EXT_SMOOTH_GUIDE) && c->scene.normals.records.ptr && c->scene.normals.cof.ptr;
 }
 
 // Conservative screen bounds of the triangles of a small scene for a pinhole camera at `org` whose
@@ -653,6 +658,38 @@ int rtpt_debug_light_table(rtpt_ctx* c, uint64_t* cdf, uint32_t cap, uint32_t* n
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(cdf, c->scene.light_table.cdf.ptr, static_cast<size_t>(take) * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return RTPT_OK;
+}
+
+// the per-pixel normal plane of the filter's edge stop, as it stands on the device
+int rtpt_debug_guide_normals(rtpt_ctx* c, float* out, size_t bytes) {
+  if (!c || !out) return fail(RTPT_E_INVALID, "NULL argument");
+  FLUSH_FILTER(c);
+  if (!c->normals.ptr) return fail(RTPT_E_INVALID, "the context has no per-pixel normal plane");
+  const size_t need = c->pixels() * 16;
+  if (bytes < need || c->normals.bytes < need) return fail(RTPT_E_INVALID, "destination too small");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, c->normals.ptr, need, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RTPT_OK;
+}
+
+// ... and injected: the plane counts as written by K0 for every stored row of the current frame
+int rtpt_debug_set_guide_normals(rtpt_ctx* c, const float* src, size_t bytes) {
+  if (!c || !src) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->scene.n_tris) return fail(RTPT_E_NO_SCENE, "rtpt_scene_upload has not been called");
+  if (!no_pair_table(c)) return fail(RTPT_E_INVALID, "no filter kernel of this context reads per-pixel normals (id-pair table, RTPT_FLAG_EXT_SMOOTH_GUIDE not active)");
+  FLUSH_FILTER(c);
+  const size_t need = c->pixels() * 16;
+  if (bytes < need) return fail(RTPT_E_INVALID, "source too small");
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->normals.bytes != need)
+    if (int rc = alloc_buf(c->normals, need)) return rc;
+  reuse_invalidate(c, &c->normals);
+  HIP_TRY(hipMemcpyAsync(c->normals.ptr, src, need, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->frame.normals = c->stored_rows();
+  c->frame.normals_frame = c->frames_ended;
   return RTPT_OK;
 }
 

@@ -83,6 +83,8 @@ struct K0Key {
   float PV[16], p00, p11, tmax;
   int32_t W, H, row_base, y0, y1;
   int32_t normals_on;                 // the per-pixel normal plane is written too
+  int32_t guide;                      // ... with guide normals (RTPT_FLAG_EXT_SMOOTH_GUIDE is active), formed with ...
+  int32_t guide_sigma_n;              // ... this exponent in the self weight; both 0 without
   uint64_t model_version, scene_gen;
 };
 struct K1Key {
@@ -387,7 +389,11 @@ rt::FrameGeom geom(const rtpt_ctx* c, uint32_t y0, uint32_t y1);
 rt::SceneView scene_view(const rtpt_ctx* c);
 rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
 rt::LightTableView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights), and its table or NULL
-rt::NormalView normal_view(const rtpt_ctx* c);     // the vertex normals, both NULL without (rtpt_scene_set_normals)
+rt::NormalView normal_view(const rtpt_ctx* c);     // the vertex normals, both NULL without (rtpt_scene_set_normals), and the guide switch
+// RTPT_FLAG_EXT_SMOOTH_GUIDE is active: the context has the flag and the scene holds normals.  K0 then writes guide normals into
+// rtpt_ctx::normals, and the context behaves as if the scene had no id-pair table
+bool guide_active(const rtpt_ctx* c);
+inline bool no_pair_table(const rtpt_ctx* c) { return !c->scene.pair_tab.ptr || guide_active(c); }
 bool screen_bounds(const rtpt_ctx* c, const double org[3], const double c0[3], const double c1[3], const double c2[3], double p00, double p11,
                    double jitter_px, rt::TriBounds* out);
 bool is_identity(const float* m);

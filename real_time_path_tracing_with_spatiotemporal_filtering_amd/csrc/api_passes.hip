@@ -98,6 +98,8 @@ K0Key gbuffer_key(const rtpt_ctx* c, const rt::GbufferArgs& a) {
   k.y0 = a.g.y0;
   k.y1 = a.g.y1;
   k.normals_on = a.normals ? 1 : 0;
+  k.guide = (a.normals && guide_active(c)) ? 1 : 0;  // (the normals themselves: rtpt_scene_set_normals drops the plane's tag)
+  k.guide_sigma_n = k.guide ? c->cfg.sigma_n : 0;
   k.model_version = c->scene.model_version;
   k.scene_gen = c->scene_gen;
   return k;
@@ -215,7 +217,7 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
       ((c->cfg.flags & RTPT_FLAG_NO_FILTER_FUSION) || std::memcmp(ubo->model, c->scene.model, sizeof c->scene.model) != 0 ||
        c->scene.lut_version[c->lut_cur] != c->scene.model_version || !c->tables_valid || !c->scene.lut_prev_valid || !c->ray_tab.ptr ||
        c->ray_tab_p00 != ubo->proj[0] || c->ray_tab_p11 != ubo->proj[5] || c->ray_tab_w != c->cfg.width || c->ray_tab_h != c->cfg.height ||
-       (!c->scene.pair_tab.ptr && !c->normals.ptr)) &&
+       (no_pair_table(c) && !c->normals.ptr)) &&
       (rc = final_flush(c)))
     return rc;
   {
@@ -280,7 +282,9 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   a.normals = nullptr;
   a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
   a.area_tab = a.normal_tab + (c->scene.n_tris + 1);
-  if (!c->scene.pair_tab.ptr) {  // more than 63 triangles: the filter stages per-pixel normals instead of ids
+  // more than 63 triangles: the filter stages per-pixel normals instead of ids.  RTPT_FLAG_EXT_SMOOTH_GUIDE, while active: any
+  // triangle count, and the cells are guide normals (launch_gbuffer / launch_pathtrace take the switch in their NormalView)
+  if (no_pair_table(c)) {
     if (!c->normals.ptr) {
       int rc2 = alloc_buf(c->normals, c->pixels() * 16);
       if (rc2) return rc2;
@@ -310,7 +314,7 @@ int rtpt_gbuffer(rtpt_ctx* c, const rtpt_ubo* ubo, uint32_t y0, uint32_t y1) {
   tag_outputs(c, a, nullptr);  // launched unrecorded: the planes are rewritten, nothing keeps track of with what
   {
     Timer tm(c, RTPT_K_GBUFFER);
-    rt::launch_gbuffer(a, c->stream);
+    rt::launch_gbuffer(a, c->stream, normal_view(c));
   }
   return launch_check("gbuffer");
 }
@@ -344,7 +348,7 @@ int gbuffer_flush(rtpt_ctx* c) {
   tag_outputs(c, c->pending_gb, &c->pending_key);
   {
     Timer tm(c, c->pending_gb.grad_on ? RTPT_K_GBUFFER_GRADIENT : RTPT_K_GBUFFER);
-    rt::launch_gbuffer(c->pending_gb, c->stream);
+    rt::launch_gbuffer(c->pending_gb, c->stream, normal_view(c));
   }
   return launch_check(c->pending_gb.grad_on ? "gbuffer + temporal_gradient" : "gbuffer");
 }
@@ -531,8 +535,8 @@ Rows rows_read(const rtpt_ctx* c, uint32_t y0, uint32_t y1, int64_t reach) {
 
 // does rtpt_temporal_filter record its calls in this context (to launch consecutive iterations as one chain)?
 bool records_filter_calls(const rtpt_ctx* c) {
-  return !(c->cfg.flags & (RTPT_FLAG_NO_FILTER_FUSION | RTPT_FLAG_DIRECT_FILTER)) && !(c->cfg.flags & rt::kExtMask) && c->scene.pair_tab.ptr &&
-         c->chain_max > 1;
+  return !(c->cfg.flags & (RTPT_FLAG_NO_FILTER_FUSION | RTPT_FLAG_DIRECT_FILTER)) && !(c->cfg.flags & rt::kExtMask) && !no_pair_table(c) &&
+         c->chain_max > 1;  // (the chained kernel and the deferred final pass need the id-pair table)
 }
 
 int filter_validate(rtpt_ctx* c, const rtpt_push_constants* pc, const rtpt_ubo* ubo, uint32_t& y0, uint32_t& y1) {
@@ -686,7 +690,10 @@ void filter_prelaunch(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f) {
 }
 
 // the kernel's arguments.  Besides `a` this writes the reuse counters and FrameState::present_fused; *store as reproj_policy
-int fill_atrous_args(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, rt::AtrousArgs& a, PlaneTag<ReprojKey>* store) {
+// *px_normals (launch_atrous's): RTPT_FLAG_EXT_SMOOTH_GUIDE is active and the per-pixel plane covers the rows read — the launch
+// has no id-pair table and every kernel weighs two pixels' cells.  A plane that does not (not written in this frame, or
+// rtpt_set_plane(RTPT_PLANE_VIS_ID) since) leaves the call what it is without the flag: filtered with the triangles' normals.
+int fill_atrous_args(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, rt::AtrousArgs& a, PlaneTag<ReprojKey>* store, bool* px_normals) {
   FrameState& fr = c->frame;
   std::memset(&a, 0, sizeof a);
   a.g = geom(c, f.y0, f.y1);
@@ -709,6 +716,8 @@ int fill_atrous_args(rtpt_ctx* c, const FilterPlan& p, const FilterCall& f, rt::
   a.normal_tab = static_cast<const float4*>(c->scene.normal_tab.ptr);
   const Rows read = rows_read(c, f.y0, f.y1, p.tap.reach);
   if (c->normals.ptr && fr.normals_frame == c->frames_ended && fr.normals.covers(read.y0, read.y1)) a.normals = static_cast<const float4*>(c->normals.ptr);
+  *px_normals = guide_active(c) && a.normals;
+  if (*px_normals) a.pair_tab = nullptr;
   if (a.ext & rt::kExtVariance) {  // (filter_prelaunch left variance_last naming the buffer this pass writes)
     a.var_in = static_cast<const float*>(c->variance[fr.variance_last ^ 1].ptr);
     a.var_out = static_cast<float*>(c->variance[fr.variance_last].ptr);
@@ -781,7 +790,8 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels, bool defer = fal
   filter_prelaunch(c, p, f);
   rt::AtrousArgs a;
   PlaneTag<ReprojKey> stored;
-  int rc = fill_atrous_args(c, p, f, a, &stored);
+  bool px_normals = false;
+  int rc = fill_atrous_args(c, p, f, a, &stored, &px_normals);
   if (rc) return rc;
   if (defer && defers(c, p, a)) {
     c->deferred.args = a;
@@ -796,7 +806,7 @@ int filter_launch(rtpt_ctx* c, const FilterCall& f, int levels, bool defer = fal
     if (levels > 1)
       rt::launch_atrous_chain(a, levels, p.final_pass, c->filter_policy, c->stream);
     else
-      rt::launch_atrous(a, p.final_pass, c->stream);
+      rt::launch_atrous(a, p.final_pass, c->stream, px_normals);
   }
   if ((rc = launch_check("temporal_filter"))) return rc;
   commit_filter(c, p, f, stored);

@@ -892,9 +892,16 @@ int rtpt_scene_set_normals(rtpt_ctx* c, const float* tri_normals, const uint32_t
   FLUSH_FILTER(c);
   HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the set being replaced
   Scene& s = c->scene;
+  if (c->cfg.flags & RTPT_FLAG_EXT_SMOOTH_GUIDE) {
+    // the guide normals K0 wrote belong to the set being replaced: the next frame runs K0 again, and until then a filter call
+    // takes the triangles' normals (the stale plane)
+    reuse_invalidate(c, &c->normals);
+    c->frame.normals = Rows();
+  }
   const bool bvh_without = (s.n_tris > 64) || (c->cfg.flags & RTPT_FLAG_FORCE_BVH);  // finish_scene's choice
   if (drop) {
     s.normals = Scene::Normals{};
+    if ((c->cfg.flags & RTPT_FLAG_EXT_SMOOTH_GUIDE) && s.pair_tab.ptr) free_buf(c->normals);  // (the scene's filter reads its id-pair table again)
     if (s.use_bvh != bvh_without) {
       s.use_bvh = bvh_without;
       c->scene_gen++;  // brute force may resolve a tie between equally near triangles differently

@@ -72,7 +72,11 @@ __device__ __forceinline__ void xcd_strip_tile(int tiles_x, int tiles_y, int& bx
   bx = static_cast<int>(strip * kStripTiles + (rem - row * sw));
 }
 
-template <bool FINAL, bool EXACT>
+// PX (launch_atrous's px_normals; RTPT_FLAG_EXT_SMOOTH_GUIDE): a pixel's normal is its cell of a.normals, which covers every row
+// read, instead of normal_tab[id]; every tap's weight is computed from the two cells (two pixels of one triangle no longer share
+// a normal), the centre takes its cell's self weight — the comb kernel's NRM form tap for tap, so the two agree bit for bit on any
+// plane.  The id is read only for the final pass's reprojection.
+template <bool FINAL, bool EXACT, bool PX = false>
 __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
   int bx, by;
   xcd_strip_tile(a.tiles_x, a.tiles_y, bx, by);
@@ -87,8 +91,8 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
   const float4 cp4 = a.in[rowp + x];
   const f3 cp = xyz(cp4);
   const float dp = cp4.w;  // rgbd
-  const uint32_t idp = a.vis[rowp + x];
-  const float4 np4 = a.normal_tab[idp];
+  const uint32_t idp = (!PX || FINAL) ? a.vis[rowp + x] : 0u;
+  const float4 np4 = PX ? a.normals[rowp + x] : a.normal_tab[idp];
   const f3 np = xyz(np4);
   const EdgeStop es{a.sigma_z, a.sigma_l, a.cz, a.cl};
   f3 num{0.f, 0.f, 0.f};
@@ -115,13 +119,17 @@ __global__ __launch_bounds__(kThreads) void k_atrous(AtrousArgs a) {
         const int qx = qxs[i];
         const float4 cq4 = a.in[rowq + qx];
         cq = xyz(cq4);
-        const uint32_t idq = a.vis[rowq + qx];
         float wn;
-        if (idq == idp) {
-          wn = np4.w;  // same primitive: the per-id self weight (same bits as recomputing it)
+        if constexpr (PX) {
+          wn = pow_sigma(glsl_max(0.0f, exact::dot(np, xyz(a.normals[rowq + qx]))), a.sigma_n);  // :62
         } else {
-          const f3 nq = xyz(a.normal_tab[idq]);
-          wn = pow_sigma(glsl_max(0.0f, exact::dot(np, nq)), a.sigma_n);  // :62
+          const uint32_t idq = a.vis[rowq + qx];
+          if (idq == idp) {
+            wn = np4.w;  // same primitive: the per-id self weight (same bits as recomputing it)
+          } else {
+            const f3 nq = xyz(a.normal_tab[idq]);
+            wn = pow_sigma(glsl_max(0.0f, exact::dot(np, nq)), a.sigma_n);  // :62
+          }
         }
         w = edge_weight<EXACT>(es, wn, cp, cq, dp, cq4.w);  // rgbd
       }
@@ -227,7 +235,8 @@ __global__ __launch_bounds__(kThreads) void k_var_prefilter(FrameGeom g, int row
   out[static_cast<size_t>(y - g.row_base) * g.W + x] = acc * 0.0625f;
 }
 
-template <bool FINAL, bool EXACT>
+// PX: as in k_atrous — every tap, the centre included, weighs the two pixels' cells of a.normals
+template <bool FINAL, bool EXACT, bool PX = false>
 __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
   int bx, by;
   xcd_strip_tile(a.tiles_x, a.tiles_y, bx, by);
@@ -242,8 +251,8 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
   const float4 cp4 = a.in[rowp + x];
   const f3 cp = xyz(cp4);
   const float dp = cp4.w;  // rgbd
-  const uint32_t idp = a.vis[rowp + x];
-  const float4 np4 = a.normal_tab[idp];
+  const uint32_t idp = (!PX || FINAL) ? a.vis[rowp + x] : 0u;
+  const float4 np4 = PX ? a.normals[rowp + x] : a.normal_tab[idp];
   const f3 np = xyz(np4);
   f3 num{0.f, 0.f, 0.f};
   float den = 0.f, vsum = 0.f;
@@ -258,8 +267,13 @@ __global__ __launch_bounds__(kThreads) void k_atrous_ext(AtrousArgs a) {
       const size_t rowq = static_cast<size_t>(qy - a.g.row_base) * W;
       const float4 cq4 = a.in[rowq + qx];
       const f3 cq = xyz(cq4);
-      const uint32_t idq = a.vis[rowq + qx];
-      const f3 nq = xyz(a.normal_tab[idq]);
+      f3 nq;
+      if constexpr (PX) {
+        nq = xyz(a.normals[rowq + qx]);
+      } else {
+        const uint32_t idq = a.vis[rowq + qx];
+        nq = xyz(a.normal_tab[idq]);
+      }
       const float wn = pow_sigma(glsl_max(0.0f, exact::dot(np, nq)), a.sigma_n);  // :62
       const float w = edge_weight<EXACT>(es, wn, cp, cq, dp, cq4.w, use_var, vg);
       const float h = gauss ? gauss5(i, j) * (1.0f / 273.0f) : 1.0f / 9.0f;  // :145
@@ -504,8 +518,9 @@ bool atrous_final_role(AtrousArgs& a) {
   return true;
 }
 
-void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
+void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s, bool px_normals) {
   if (a0.g.y1 <= a0.g.y0) return;
+  if (px_normals && (!a0.normals || a0.pair_tab)) std::abort();  // (api_passes.hip: filter_launch sees to both)
   AtrousArgs a = a0;
   a.cz = -1.44269504088896341f / a.sigma_z;
   a.cl = -1.44269504088896341f / a.sigma_l;
@@ -541,7 +556,9 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
     a.tiles_y = static_cast<int32_t>(g2.y);
     dim3 grid(g2.x * g2.y);
     with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
-      hipLaunchKernelGGL((k_atrous_ext<decltype(fin)::value, decltype(ex)::value>), grid, block, 0, s, a);
+      with_bool(px_normals, [&](auto px) {
+        hipLaunchKernelGGL((k_atrous_ext<decltype(fin)::value, decltype(ex)::value, decltype(px)::value>), grid, block, 0, s, a);
+      });
     });
     return;
   }
@@ -568,7 +585,9 @@ void launch_atrous(const AtrousArgs& a0, bool final_pass, hipStream_t s) {
   a.tiles_y = static_cast<int32_t>(g2.y);
   dim3 grid(g2.x * g2.y);
   with_final_exact(final_pass, a.exact != 0, [&](auto fin, auto ex) {
-    hipLaunchKernelGGL((k_atrous<decltype(fin)::value, decltype(ex)::value>), grid, block, 0, s, a);
+    with_bool(px_normals, [&](auto px) {
+      hipLaunchKernelGGL((k_atrous<decltype(fin)::value, decltype(ex)::value, decltype(px)::value>), grid, block, 0, s, a);
+    });
   });
 }
 

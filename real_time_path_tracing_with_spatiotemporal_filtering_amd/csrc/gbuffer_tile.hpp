@@ -5,6 +5,7 @@
 #pragma once
 
 #include "closest_hit.hpp"
+#include "shading_normal.hpp"
 
 namespace rt {
 namespace {
@@ -60,13 +61,32 @@ __device__ __forceinline__ void store_gradient(float4* grad, size_t i, float lam
 // ------------------------------------------------------------------------------------------
 // K0 G-buffer
 // ------------------------------------------------------------------------------------------
+// RTPT_FLAG_EXT_SMOOTH_GUIDE: the cell of the per-pixel normal plane at a hit with id1 > 0, the guide normal of shading_normal.hpp
+// (G1-G5) from K0's own barycentrics; normal_tab[id1] where G4 says so.  The matrix is loaded only behind a smooth record.
+__device__ __forceinline__ float4 guide_cell(const NormalView& nv, const float4* normal_tab, uint32_t id1, uint32_t n_base, float b0, float b1, float b2) {
+  const float4 tab = normal_tab[id1];
+  const uint32_t t = (id1 - 1) % n_base, i = (id1 - 1) / n_base;
+  const float4* r = nv.records + 3 * static_cast<size_t>(t);
+  const float4 r0 = r[0];
+  if (__float_as_uint(r0.w) == 0u) return tab;
+  const float4 r1 = r[1], r2 = r[2];
+  const float4* c = nv.cof + 3 * static_cast<size_t>(i);
+  const float4 c0 = c[0], c1 = c[1], c2 = c[2];
+  f3 ns;
+  if (!nrm::guide(xyz(r0), xyz(r1), xyz(r2), b0, b1, b2, xyz(c0), xyz(c1), xyz(c2), xyz(tab), &ns)) return tab;
+  return make_float4(ns.x, ns.y, ns.z, nrm::guide_self_weight(ns, nv.sigma_n));
+}
+
 // K0 (+ K1 when a.grad_on) for pixel (x, y), which must lie inside the frame and inside a's rows; `cand` = span_candidates of
 // the pixel's wave (brute force with culling only).  alpha_image != NULL (the fused K0 + K1 + K2 launch): the depth also goes
 // into the alpha of that image's pixel for rows [ay0, ay1) — the traced image is "rgbd" (atrous.hip) and the tracing
 // workgroups of that launch store the colour's 12 bytes only.
-template <int BVH>
+// NV: nothing, or the scene's NormalView (kernels.hpp: the NRM axis).  With one, and while its `guide` word is set, the pixel's cell
+// of a.normals is guide_cell's; every other instantiation, and every launch without the switch, stores normal_tab[id1].
+template <int BVH, class... NV>
 __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, int x, int y, unsigned long long cand, uint32_t* stack, int tid, int nt,
-                                              float4* alpha_image = nullptr, int ay0 = 0, int ay1 = 0) {
+                                              float4* alpha_image = nullptr, int ay0 = 0, int ay1 = 0, const NV&... nv) {
+  static_assert(sizeof...(NV) == 0 || (sizeof...(NV) == 1 && pack_nrm<NV...>()), "a NormalView or nothing");
   // view-space direction of the pixel-centre ray: (ndc.x / P00, ndc.y / P11, -1) with ndc = (2 (x + .5) - W) / W.  Each
   // component is a function of the column or of the row alone: k_ray_tables evaluates the two divisions per column / row
   // once (same operands, same correctly-rounded operations), K0 reads them back — 4 divisions less per pixel
@@ -81,12 +101,17 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, int x, int y
     closest_hit<BVH>(a.scene, o, d, h, stack, tid, nt);
   const size_t i = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
   a.vis[i] = h.id1;  // visibility.frag.glsl:23
-  if (a.normals) a.normals[i] = a.normal_tab[h.id1];
+  bool guide = false;  // the cell is written below, behind the barycentrics
+  if constexpr (sizeof...(NV) != 0) guide = a.normals && pack_back(nv...).guide != 0u && h.id1 != 0u;
+  if (a.normals && !guide) a.normals[i] = a.normal_tab[h.id1];
   f3 wp{0.f, 0.f, 0.f};
   float dep = 1.0f;  // clear depth  main.cpp:1421
   if (h.id1) {
     float b1 = RTPT_DIV_SH(-h.u, h.ad), b2 = RTPT_DIV_SH(h.v, h.ad);
     float b0 = 1.0f - b1 - b2;
+    if constexpr (sizeof...(NV) != 0) {
+      if (guide) a.normals[i] = guide_cell(pack_back(nv...), a.normal_tab, h.id1, a.scene.n_base_tris, b0, b1, b2);
+    }
     const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
     wp = bary_point(xyz(s[0]), xyz(s[1]), xyz(s[2]), b0, b1, b2);
     a.worldpos[i] = make_float4(wp.x, wp.y, wp.z, 1.0f);
@@ -107,9 +132,9 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, int x, int y
 }
 
 // the 64 x 4-pixel tile (bx, by) of a's rows (k_gbuffer's workgroup, and the G-buffer workgroups of the fused launch)
-template <int BVH>
+template <int BVH, class... NV>
 __device__ __forceinline__ void gbuffer_tile(const GbufferArgs& a, uint32_t bx, uint32_t by, uint32_t* stack, float4* alpha_image = nullptr, int ay0 = 0,
-                                             int ay1 = 0) {
+                                             int ay1 = 0, const NV&... nv) {
   const int tid = threadIdx.y * kBlockX + threadIdx.x;
   const uint32_t tp = tile_pixel(static_cast<int>(threadIdx.y), threadIdx.x);
   const int x = static_cast<int>(bx) * kBlockX + static_cast<int>(tp & 63u);
@@ -119,7 +144,7 @@ __device__ __forceinline__ void gbuffer_tile(const GbufferArgs& a, uint32_t bx, 
     cand = span_candidates(a.bounds, a.scene.n_tris, static_cast<int>(bx) * kBlockX + wave_x0(static_cast<int>(threadIdx.y)),
                            a.g.y0 + static_cast<int>(by) * kBlockY);
   if (x >= a.g.W || y >= a.g.y1) return;
-  gbuffer_pixel<BVH>(a, x, y, cand, stack, tid, kThreads, alpha_image, ay0, ay1);
+  gbuffer_pixel<BVH>(a, x, y, cand, stack, tid, kThreads, alpha_image, ay0, ay1, nv...);
 }
 
 }  // namespace

@@ -126,13 +126,18 @@ __global__ void k_ray_tables(int W, int H, float p00, float p11, float* dvx, flo
   }
 }
 
-template <int BVH>
-__global__ __launch_bounds__(kThreads) void k_gbuffer(GbufferArgs a) {
+// NV: nothing, or the scene's NormalView while RTPT_FLAG_EXT_SMOOTH_GUIDE is active (kernels.hpp; the two BVH modes only)
+template <int BVH, class... NV>
+__global__ __launch_bounds__(kThreads) void k_gbuffer(GbufferArgs a, NV... normals) {
+  static_assert(sizeof...(NV) == 0 || (sizeof...(NV) == 1 && pack_nrm<NV...>() && BVH != 0), "a NormalView or nothing");
   extern __shared__ uint32_t stack[];  // BVH: stack_depth x 256 entries (dynamic); unused otherwise
 #if RTPT_TILE_TIMELINE
   TimelineScope tl_(0, blockIdx.y * gridDim.x + blockIdx.x);
 #endif
-  gbuffer_tile<BVH>(a, blockIdx.x, blockIdx.y, stack);
+  if constexpr (sizeof...(NV) != 0)
+    gbuffer_tile<BVH>(a, blockIdx.x, blockIdx.y, stack, nullptr, 0, 0, normals...);
+  else
+    gbuffer_tile<BVH>(a, blockIdx.x, blockIdx.y, stack);
 }
 
 __global__ __launch_bounds__(kThreads) void k_gradient(GradientArgs a) {
@@ -349,11 +354,19 @@ void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dv
   const int n = W > H ? W : H;
   hipLaunchKernelGGL(k_ray_tables, dim3((n + 255) / 256), dim3(256), 0, s, W, H, p00, p11, dvx, dvy);
 }
-void launch_gbuffer(const GbufferArgs& a, hipStream_t s) {
+void launch_gbuffer(const GbufferArgs& a, hipStream_t s, const NormalView& normals) {
   if (a.g.y1 <= a.g.y0) return;
+  const bool guide = normals.guide != 0u;  // RTPT_FLAG_EXT_SMOOTH_GUIDE is active: a scene with normals, traced through its tree
+  if (guide && (!normals.records || !normals.cof || !a.scene.use_bvh || !a.normals)) std::abort();
   with_mode<3>(scene_mode(a.scene), [&](auto mode) {
     constexpr int M = decltype(mode)::value;
-    hipLaunchKernelGGL(k_gbuffer<M>, grid_for(a.g), dim3(kBlockX, kBlockY), M ? a.scene.stack_lds * kThreads * 4 : 0, s, a);
+    if constexpr (M != 0) {
+      if (guide) {  // (the launch syntax: launch_pathtrace's `go` says why)
+        k_gbuffer<M><<<grid_for(a.g), dim3(kBlockX, kBlockY), a.scene.stack_lds * kThreads * 4, s>>>(a, normals);
+        return;
+      }
+    }
+    k_gbuffer<M><<<grid_for(a.g), dim3(kBlockX, kBlockY), M ? a.scene.stack_lds * kThreads * 4 : 0, s>>>(a);
   });
 }
 void launch_gradient(const GradientArgs& a, hipStream_t s) {

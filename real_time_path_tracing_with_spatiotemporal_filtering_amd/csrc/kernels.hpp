@@ -134,9 +134,15 @@ constexpr bool spec_takes() {
 // their argument segments and their code.  Instantiated where a scene with normals can be launched: the BVH scene modes (such a
 // scene is traced through its tree), the fused launch and the unfused compacting one, the queue kernels; no
 // RTPT_FLAG_NO_PATH_COMPACTION form, no brute-force form.
+// RTPT_FLAG_EXT_SMOOTH_GUIDE rides here too, for the same reason: `guide` != 0 while the switch is active, and K0 of these
+// instantiations (gbuffer_tile.hpp; k_gbuffer's two with a NormalView, the G-buffer workgroups of the fused launch) then writes the
+// guide normal of shading_normal.hpp (G1-G5) into the per-pixel plane, its self weight formed with `sigma_n` (k_lut's formula).
+// With guide == 0 they store normal_tab[id], like every instantiation without a NormalView.
 struct NormalView {
   const float4* records;  // 3 per base triangle
   const float4* cof;      // 3 per instance
+  uint32_t guide;         // RTPT_FLAG_EXT_SMOOTH_GUIDE is active
+  int32_t sigma_n;        // rtpt_config::sigma_n, read only while guide != 0
 };
 template <class... P>
 struct pack_last {
@@ -450,7 +456,10 @@ size_t sah_scratch_bytes(uint32_t n_prims);  // 0: the sort's size query failed
 hipError_t launch_sah_build(const LbvhArgs& a, void* scratch, size_t scratch_bytes, hipStream_t s);
 // gather isect records into class order: out[t] = isect_id[ids[t]] (3 float4 each), n entries
 void launch_lut(const LutArgs& a, hipStream_t s);
-void launch_gbuffer(const GbufferArgs& a, hipStream_t s);
+// normals.guide != 0 (RTPT_FLAG_EXT_SMOOTH_GUIDE is active: the scene holds normals, so it traces through its tree, and a.normals is
+// the per-pixel plane): the BVH-mode instantiation with a NormalView, which writes the guide normal there.  Every other launch is the
+// kernel without one.
+void launch_gbuffer(const GbufferArgs& a, hipStream_t s, const NormalView& normals = NormalView{nullptr, nullptr, 0u, 0});
 void launch_ray_tables(int W, int H, float p00, float p11, float* dvx, float* dvy, hipStream_t s);
 void launch_gradient(const GradientArgs& a, hipStream_t s);
 // gb != NULL: K0 (+ K1) of gb's rows run inside the tile kernel's launch, behind the tracing tiles (pathtrace_fuses_gbuffer says
@@ -473,13 +482,17 @@ struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
                       const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr,
                       const LightTableView& lights = LightTableView{nullptr, 0u, nullptr},
-                      const NormalView& normals = NormalView{nullptr, nullptr});
+                      const NormalView& normals = NormalView{nullptr, nullptr, 0u, 0});
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
 bool pathtrace_uses_pool(const PathtraceArgs& a);
 size_t pathtrace_pool_bytes(int W, int rows);
-void launch_atrous(const AtrousArgs& a, bool final_pass, hipStream_t s);
+// px_normals (RTPT_FLAG_EXT_SMOOTH_GUIDE is active and a.normals covers the rows read; then a.pair_tab is NULL): the normals of a
+// tap are the two pixels' cells of a.normals in every kernel — the comb kernel's NRM form, or the per-pixel instantiation of the
+// two direct-load kernels where today's launch reads normal_tab by id.  It travels beside the arguments, like launch_pathtrace's
+// `specular`: AtrousArgs and the argument segment of every filter kernel stay what they were.
+void launch_atrous(const AtrousArgs& a, bool final_pass, hipStream_t s, bool px_normals = false);
 bool atrous_final_fuses_present(const AtrousArgs& a);
 // true when a launch of `a` runs in the plain comb kernel (no extension mode, not forced direct, 1 <= k <= 16, id-pair table
 // or per-pixel normals): the only kernel whose final pass takes reproj_out / reproj_in

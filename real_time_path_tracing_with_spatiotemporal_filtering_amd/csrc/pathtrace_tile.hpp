@@ -433,7 +433,10 @@ __device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, c
 #if RTPT_TILE_TIMELINE
     TimelineScope tl_(0, (blockIdx.y - a.tiles_y) * gridDim.x + blockIdx.x);
 #endif
-    gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
+    if constexpr (pack_nrm<LV...>())  // the scene's NormalView: K0 writes the guide normal while its switch is set (gbuffer_tile.hpp)
+      gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1, pack_back(lights...));
+    else
+      gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }
 }
 

@@ -21,8 +21,23 @@
 //   6. dot(ns, ng) < 0: ns = -ns      (inverted vn records and mirrored poses shade like their proper twins)
 //   7. !(dot(ns, d) < 0): ns = ng     (the silhouette: the interpolated normal faces away from the incoming ray; the hit stays smooth)
 // ng keeps: the offset origin, the dielectric's entering test, the normal-keyed albedo, the texture footprint, an emitter's own
-// cosine and area, K0, K1, the LUT and every filter kernel.  ns takes: the diffuse direction normalize(ns + point), spec::lobe's
+// cosine and area, K0's ids, world positions and depth, K1, the LUT, the reprojection, the same-primitive tests, and every filter
+// kernel of a context without RTPT_FLAG_EXT_SMOOTH_GUIDE.  ns takes: the diffuse direction normalize(ns + point), spec::lobe's
 // mirror axis, diel::interface's normal, nf of light::sample and light::sphere_sample, the cosine cb of RTPT_FLAG_EXT_NEE_MIS.
+//
+// THE GUIDE NORMAL (RTPT_FLAG_EXT_SMOOTH_GUIDE, active while the context has the flag and the scene holds normals): what K0
+// (gbuffer_tile.hpp) writes into the per-pixel normal plane that the filter's edge stop reads, at a pixel whose pixel-centre ray
+// hits id1 > 0, from K0's own barycentrics b0, b1, b2 (the ones that form its world position):
+//   G1-G3. rules 1 to 3 (interpolate), with record (id1 - 1) % n_base_tris and the cof rows of instance (id1 - 1) / n_base_tris
+//   G4.    the record is not smooth, or interpolate returns false (a NaN or infinite ns; a zero w gives NaN), or ns is the zero vector
+//          (a w whose squared length overflows binary32, normals of length 1e20: normalize scales it by 1 / inf; in a path rule 7
+//          catches that ns, here nothing would, and a zero cell weighs every tap of its pixel 0): the cell is normal_tab[id1], all
+//          four words, as without the switch
+//   G5.    ng = xyz(normal_tab[id1]), the LUT's unfaced normal that G4 stores; dot(ns, ng) < 0: ns = -ns   (inverted vn records and
+//          mirrored poses agree with their not-smooth neighbours)
+//   Rules 5 and 7 are not applied: the guide does not depend on the incoming ray.
+//   The cell is (ns.x, ns.y, ns.z, powi(max(0, dot(ns, ns)), sigma_n)), k_lut's formula for normal_tab[t + 1].w; id 0 keeps
+//   normal_tab[0].  tests/guide_normals.py restates G1-G5 in numpy.
 // THE SIDE TESTS, at a smooth hit (rule 4 passed), keep rays off the wrong side of the real surface:
 //   * a diffuse or specular direction d' with !(dot(d', ng) > 0) is absorbed: the path ends with colour 0 (what R holds is kept);
 //   * a light sample or sphere sample is valid only if dot(wd, ng) > 0 as well (draws, sampled bit and sphere bit as they were);
@@ -90,6 +105,18 @@ RT_HD f3 orient(f3 ns, f3 ng, f3 d) {
   if (!(exact::dot(ns, d) < 0.0f)) ns = ng;
   return ns;
 }
+
+// G1 to G5 without the cell: false where the cell is normal_tab[id1] (G4; *ns is then not to be read).  ng = xyz(normal_tab[id1])
+RT_HD bool guide(f3 n0, f3 n1, f3 n2, float b0, float b1, float b2, f3 c0, f3 c1, f3 c2, f3 ng, f3* ns) {
+  f3 n;
+  if (!interpolate(n0, n1, n2, b0, b1, b2, c0, c1, c2, &n)) return false;
+  if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return false;  // |w|^2 overflowed: normalize scaled w by 1 / inf
+  if (exact::dot(n, ng) < 0.0f) n = -n;
+  *ns = n;
+  return true;
+}
+// the fourth word of a guide cell: the self weight pow(max(0, dot(ns, ns)), sigma_n) as k_lut forms it
+RT_HD float guide_self_weight(f3 ns, int sigma_n) { return exact::powi(glsl_max(0.0f, exact::dot(ns, ns)), sigma_n); }
 
 // the side tests
 RT_HD bool absorbed(f3 d_new, f3 ng) { return !(exact::dot(d_new, ng) > 0.0f); }          // a diffuse or specular direction

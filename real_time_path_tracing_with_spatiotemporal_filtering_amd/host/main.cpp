@@ -26,6 +26,8 @@ static void usage(const char* argv0) {
       "           --texture-mips: from generated mip chains, at the level of the ray's footprint, RTPT_TEX_MIPMAP)]\n"
       "          [--specular  (a newmtl with illum >= 3 and Ks != 0 bounces as a mirror, or glossy by its Ns: rtpt_scene_set_materials_ext)]\n"
       "          [--smooth-normals  (with --scene: bounces, refraction and light samples use the OBJ's interpolated vn records)]\n"
+      "          [--smooth-guide  (the filter's edge stop reads interpolated normals too, RTPT_FLAG_EXT_SMOOTH_GUIDE = --flags 0x100000;\n"
+      "           without --smooth-normals the frames are unchanged)]\n"
       "          [--dielectric  (--specular's rule, and a newmtl with illum 4 / 6 / 7 / 9 and an Ni >= 1 is glass: Fresnel reflection or refraction)]\n"
       "          [--nee  (next-event estimation: every diffuse hit samples one of the triangles whose material has a Ke, one shadow ray each,\n"
       "           RTPT_FLAG_EXT_NEE = --flags 0x10000; on every context of a rank; without an emissive material the frames are unchanged)]\n"
@@ -105,6 +107,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
     else if (!std::strcmp(argv[i], "--dielectric")) opt.dielectric = true;
     else if (!std::strcmp(argv[i], "--smooth-normals")) opt.smooth_normals = true;
+    else if (!std::strcmp(argv[i], "--smooth-guide")) opt.flags |= RTPT_FLAG_EXT_SMOOTH_GUIDE;
     else if (!std::strcmp(argv[i], "--texture-filter")) {
       const char* v = need("--texture-filter");
       if (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear")) { std::fprintf(stderr, "--texture-filter nearest|bilinear\n"); return 2; }

@@ -13,7 +13,13 @@ per variant, the closest-hit queries per pixel from the ray counter of that wind
 variants trace through the BVH: 1,656,000 triangles.
 Re-pose: frames in which rtpt_scene_set_instances moves every instance (the lattice shifted by a millimetre and back), normals off
 against on: what a move adds to a resting frame with normals, minus what it adds without, is the cofactor table's kernel — one
-thread per instance — behind the re-pose.  Prints one JSON line."""
+thread per instance — behind the re-pose.  Prints one JSON line.
+
+--guide adds RTPT_FLAG_EXT_SMOOTH_GUIDE (interpolated normals in the filter's edge stop) as a third variant beside "smooth", the same
+way: frame time in alternating windows, the tracing launch (K0 writes the guide normals inside it) and the filter launches from the
+library's event timing, moved frames.  And what it buys, at --benefit-size (default 1920 x 1080) on the same lattice at rest: the RMSE
+of the FIRST filtered frame (no history yet) against the mean of --benefit-frames unfiltered frames, off against on, over the whole
+frame and over the pixels within one pixel of a facet edge (a 3 x 3 neighbourhood of the id plane that holds another id)."""
 import argparse
 import json
 import os
@@ -37,6 +43,9 @@ def main():
     ap.add_argument("--lattice", type=int, nargs=3, default=(10, 10, 10))
     ap.add_argument("--lat", type=int, default=24)
     ap.add_argument("--lon", type=int, default=36)
+    ap.add_argument("--guide", action="store_true")
+    ap.add_argument("--benefit-size", type=int, nargs=2, default=(1920, 1080))
+    ap.add_argument("--benefit-frames", type=int, default=32)
     a = ap.parse_args()
     import torch  # noqa: F401  (before the library: one ROCm runtime for both)
     from real_time_path_tracing_with_spatiotemporal_filtering_amd import abi, scenes
@@ -55,8 +64,9 @@ def main():
     mats[:, :3] = [(0.7, 0.7, 0.7), (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)]
     mext = abi.materials_ext(mats, {1: ((0.9, 0.9, 0.9), 0.0)}, {2: ((0.95, 0.97, 1.0), 1.5)})
 
-    def app_of(smooth):
-        app = make_app(a.width, a.height, max_segments=a.segments, iterations=5, mesh=(xyz, idx), instance_xforms=xf,
+    def app_of(smooth, guide=False, size=None):
+        w, h = size or (a.width, a.height)
+        app = make_app(w, h, max_segments=a.segments, iterations=5, mesh=(xyz, idx), instance_xforms=xf, smooth_guide=guide,
                        cameraOrigin=cam, z_far=float(dist + nz * pitch + 10.0), lightPos=(1.0, float(cam[1]), float(cam[2]) - 8.0))
         ctx = app.backend.ctx
         ctx.set_materials_ext(band, mext)
@@ -64,6 +74,8 @@ def main():
             ctx.set_normals(nrm)
         return app
     apps = {"flat": app_of(False), "smooth": app_of(True)}
+    if a.guide:
+        apps["guide"] = app_of(True, True)
 
     def run(app, frames, move=False):
         for f in range(frames):
@@ -75,7 +87,7 @@ def main():
         app.backend.sync()
     ms = {name: [] for name in apps}
     for r in range(a.repeats):
-        for name in (("flat", "smooth") if r % 2 == 0 else ("smooth", "flat")):     # both orders
+        for name in (tuple(apps) if r % 2 == 0 else tuple(apps)[::-1]):     # both orders
             run(apps[name], a.warmup)
             t0 = time.perf_counter()
             run(apps[name], a.frames)
@@ -88,7 +100,7 @@ def main():
         run(app, 10)
         tm = ctx.timing_collect()
         ctx.timing_enable(0)
-        kernels[name] = {k: round(v[0] / v[1] * 1e3, 1) for k, v in tm.items() if v[1] and "pathtrace" in k}
+        kernels[name] = {k: round(v[0] / v[1] * 1e3, 1) for k, v in tm.items() if v[1] and ("pathtrace" in k or (a.guide and "atrous" in k))}
         rays[name] = round(ctx.raycount() / (10 * a.width * a.height), 4)
         t = []
         for _ in range(a.repeats):
@@ -108,7 +120,47 @@ def main():
            "moved_frame_ms": moved_ms, "moved_frame_ms_median": {k: round(v, 4) for k, v in mm.items()},
            # what a move costs with normals beyond what it costs without: (moved - resting) smooth minus (moved - resting) flat
            "cofactor_table_ms_per_move": round((mm["smooth"] - med["smooth"]) - (mm["flat"] - med["flat"]), 4)}
+    if a.guide:
+        out["frame_ms_ratio_guide_smooth"] = round(med["guide"] / med["smooth"], 4)
+        out["benefit"] = benefit(abi, app_of, tuple(a.benefit_size), a.benefit_frames)
     print(json.dumps(out))
+
+
+def benefit(abi, app_of, size, n):
+    """RMSE of the first filtered frame against the mean of n unfiltered frames at rest, guide off / on, whole frame and facet edges"""
+    res = {}
+    for name, guide in (("off", False), ("on", True)):
+        app = app_of(True, guide, size)
+        ctx = app.backend.ctx
+        mean, first, ids = None, None, None
+        for f in range(n):
+            app.updateScene(())
+            app.drawVisbilityBuffer()
+            app.computeTemporalGradient()
+            app.drawSceneToImage()
+            traced = ctx.readback(abi.PLANE_IMAGE)[..., :3].astype(np.float64)
+            mean = traced if mean is None else mean + traced
+            if f == 0:
+                ids = ctx.readback(abi.PLANE_VIS_ID)
+            app.applyTemporalFiltering()
+            if f == 0:
+                first = ctx.readback(abi.PLANE_IMAGE)[..., :3].astype(np.float64)
+            app.copyImageToSwapChainsCurrentImage()
+            app.frameCount += 1
+        app.backend.close()
+        mean /= n
+        edge = np.zeros(ids.shape, bool)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                edge |= np.roll(np.roll(ids, dy, 0), dx, 1) != ids
+        edge &= ids > 0
+        err = ((first - mean) ** 2).sum(-1)
+        res[name] = {"rmse": float(np.sqrt(err.mean())), "rmse_facet_edges": float(np.sqrt(err[edge].mean())), "edge_pixels": int(edge.sum())}
+    res["frames_in_the_mean"] = n
+    res["size"] = list(size)
+    res["rmse_ratio_on_off"] = round(res["on"]["rmse"] / res["off"]["rmse"], 4)
+    res["rmse_facet_edges_ratio_on_off"] = round(res["on"]["rmse_facet_edges"] / res["off"]["rmse_facet_edges"], 4)
+    return res
 
 
 if __name__ == "__main__":
