@@ -581,6 +581,53 @@ int rtpt_scene_set_textures(rtpt_ctx* ctx, const float* tri_uv, const uint32_t* 
  * RTPT_FLAG_NO_PATH_COMPACTION (that A/B form of the tracing kernels has no smooth instantiation). */
 int rtpt_scene_set_normals(rtpt_ctx* ctx, const float* tri_normals, const uint32_t* tri_smooth, uint32_t n_tris);
 
+/* The environment map: a path that meets nothing reads an HDR image where the reference has its fixed sky (NOT reference
+ * behaviour, off until this call; additive: RTPT_ABI_VERSION stays 5).  texels_rgba: n x n RGBA32F texels of an
+ * OCTAHEDRAL map, row-major (alpha is carried and ignored); rotation: the 3 x 3 matrix, row-major, that takes a world direction into
+ * the map's frame (NULL = identity); scale: one factor per colour channel (NULL = 1, 1, 1).  flags: RTPT_TEX_NEAREST or 0
+ * (bilinear).  The lookup of a direction d, in binary32 with the contract's operations only (csrc/env.hpp states it for the device,
+ * bit for bit):
+ *   E1  e = (dot(r0, d), dot(r1, d), dot(r2, d)), r0, r1, r2 the rows of the rotation, dot(a, b) = fma(a.z, b.z, fma(a.y, b.y,
+ *       a.x * b.x)); always computed (without a rotation the identity is stored).
+ *   E2  s = (|e.x| + |e.y|) + |e.z|.  If !(s > 0) or s is infinite the colour is (0, 0, 0) and no texel is read: a NaN, the zero
+ *       direction, an infinite or overflowing component.
+ *   E3  p = e.x / s, q = e.z / s, correctly rounded.  The upper sheet is e.y >= 0.0f.
+ *   E4  upper sheet: (u, v) = (p, q); lower sheet: u = copysign(1 - |q|, p), v = copysign(1 - |p|, q).
+ *   E5  U = fma(u, 0.5, 0.5), V = fma(v, 0.5, 0.5); row 0 holds V in [0, 1/n), column 0 U in [0, 1/n).  Bilinear: x = U * n - 0.5,
+ *       x0 = floor(x), f = x - x0, taps clamp(x0, 0, n - 1) and clamp(x0 + 1, 0, n - 1), likewise in V; the four texels combine as
+ *       the albedo textures' do, a + f * (b - a) along x for both rows, then along y.  RTPT_TEX_NEAREST: the texel (min(n - 1,
+ *       int(floor(U * n))), the same of V).  Addressing is CLAMPED, not repeated: the square's edges are the folds of the lower
+ *       hemisphere, and the clamp costs half a texel of error along those four lines (a known limit).
+ *   E6  colour = texel.rgb * scale.rgb, one multiply per channel.
+ * What does not change: the analytic sphere light is tested first; a path that ends in the environment at its first segment
+ * stores ALBEDO (1, 1, 1) under RTPT_FLAG_EXT_DEMODULATE; no path changes direction, length or random stream, so HIT_ID and
+ * RAYCOUNT of a frame are those of the same frame without an environment.  The environment is collected by paths that miss, not
+ * sampled by next-event estimation: a small bright sun is noisy.
+ * The call acts on the CONTEXT, not on the scene, and needs none: the map survives rtpt_scene_upload, every rtpt_scene_set_*,
+ * rtpt_scene_rebuild, moved instances and rtpt_resize.  texels_rgba == NULL or n == 0 drops it, and every launch is again the one of
+ * a context that never had one, bit for bit.  Everything is copied; the call flushes what is recorded and blocks until the stream
+ * is idle, like rtpt_scene_set_textures.  K0, K1 and the filter read nothing of it: frame reuse and reprojection reuse go on across
+ * the call.  Device memory held, counted by rtpt_debug_live_device_bytes: exactly 16 * n * n bytes.
+ * A launch with an environment has the limits of a launch that samples lights (RTPT_FLAG_EXT_NEE): every segment runs in the tile
+ * kernel, there are no queue kernels and no deferred final filter pass rides in the tracing launch.  The tile kernels that read an
+ * environment exist for every scene mode, DEMOD, textures with and without mips, every material and light-sampling mode, with and
+ * without vertex normals, fused with K0 + K1 and unfused — and not for RTPT_FLAG_NO_PATH_COMPACTION: a context created with that
+ * A/B flag refuses the call.
+ * RTPT_E_INVALID, with the previous environment untouched, for: n above 4096; a flag other than RTPT_TEX_NEAREST; a texel, a
+ * rotation entry or a scale that is not finite; a context with RTPT_FLAG_NO_PATH_COMPACTION.  No kernel can index outside the
+ * map: that is decided here, on the host. */
+int rtpt_set_environment(rtpt_ctx* ctx, const float* texels_rgba, uint32_t n, uint32_t flags, const float rotation[9], const float scale[3]);
+/* A lat-long (equirectangular) image, width x height RGB32F pixels with row 0 at +y, to the n x n octahedral map above; runs on the
+ * host in double.  For the centre of each texel it inverts E5, E4 and E3 and normalises; the column fraction of that direction is
+ * atan2(d.x, -d.z) / (2 pi) + 0.5 (the image's centre is the camera's forward, -z), the row fraction acos(d.y) / pi; it takes ONE
+ * bilinear sample there (x = fraction * size - 0.5; wrapped horizontally, clamped vertically) and rounds to binary32; alpha is 1.
+ * Known limit: one sample per texel, no prefiltering when n is much smaller than the image.  RTPT_E_INVALID for a NULL pointer,
+ * an image of no pixels or beyond 65536 in either dimension, n == 0 or n above 4096.  Needs no context and no device. */
+int rtpt_util_environment_from_latlong(const float* rgb, uint32_t width, uint32_t height, uint32_t n, float* texels_rgba_out);
+/* env::color (csrc/env.hpp, the rules above) of the context's environment on n directions of 3 floats, on the device: rgb_out = n x
+ * 3 floats.  Directions are not checked: rule E2 is what meets a hostile one.  RTPT_E_INVALID without an environment. */
+int rtpt_selftest_environment(rtpt_ctx* ctx, const float* dirs, size_t n, float* rgb_out);
+
 /* What built the tree that is on the device now.  (A struct tag without a typedef: the entry point below carries the
  * same name, and C keeps tags and functions apart.) */
 enum { RTPT_BVH_BUILDER_HOST_SAH = 0, RTPT_BVH_BUILDER_DEVICE_LBVH = 1 };

@@ -158,6 +158,7 @@ SYMBOLS = [
     "rtpt_selftest_mis_weight", "rtpt_selftest_light_find",
     "rtpt_scene_set_normals", "rtpt_selftest_shading_normal", "rtpt_util_load_obj_normals",
     "rtpt_debug_guide_normals", "rtpt_debug_set_guide_normals",
+    "rtpt_set_environment", "rtpt_util_environment_from_latlong", "rtpt_selftest_environment",
 ]
 
 # rtpt_selftest_contract: (input words, output words) per item of every fn, in the order of the table of rtpt.h
@@ -258,6 +259,9 @@ def load() -> C.CDLL:
         "rtpt_util_load_obj_normals": [C.c_char_p, vp, vp, C.POINTER(u32)],
         "rtpt_debug_guide_normals": [vp, vp, sz],
         "rtpt_debug_set_guide_normals": [vp, vp, sz],
+        "rtpt_set_environment": [vp, vp, u32, u32, vp, vp],
+        "rtpt_util_environment_from_latlong": [vp, u32, u32, u32, vp],
+        "rtpt_selftest_environment": [vp, vp, sz, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -364,6 +368,17 @@ def load_obj_normals(path: str):
     nrm, smooth = np.zeros((nt.value, 9), np.float32), np.zeros(nt.value, np.uint32)
     _check(load().rtpt_util_load_obj_normals(path.encode(), _ptr(nrm), _ptr(smooth), C.byref(nt)))
     return nrm, smooth
+
+
+def environment_from_latlong(rgb: np.ndarray, n: int) -> np.ndarray:
+    """the [n, n, 4] f32 octahedral map of the lat-long image rgb [h, w, 3] (row 0 at +y, the centre column at -z), one bilinear
+    sample per texel, computed on the host in double (rtpt_util_environment_from_latlong)"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("a lat-long image is [height, width, 3]")
+    out = np.zeros((max(int(n), 0), max(int(n), 0), 4), np.float32)
+    _check(load().rtpt_util_environment_from_latlong(_ptr(rgb), rgb.shape[1], rgb.shape[0], int(n), _ptr(out) if out.size else None))
+    return out
 
 
 def load_obj_map_kd(path: str):
@@ -759,6 +774,27 @@ class Context:
         cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 20)
         out = np.zeros((len(cases), 3), np.float32)
         _check(self._lib.rtpt_selftest_mis_weight(self._h, _ptr(cases), _ptr(out), len(cases)))
+        return out
+
+    def set_environment(self, texels=None, flags: int = 0, rotation=None, scale=None):
+        """the environment map (rtpt_set_environment): texels [n, n, 4] f32 of an octahedral map, flags TEX_NEAREST or 0, rotation
+        [3, 3] row-major (None: the identity), scale [3] (None: 1, 1, 1); texels None drops it.  Of the context, not of the scene"""
+        if texels is None:
+            _check(self._lib.rtpt_set_environment(self._h, None, 0, 0, None, None))
+            return
+        tx = np.ascontiguousarray(texels, np.float32)
+        if tx.ndim != 3 or tx.shape[0] != tx.shape[1] or tx.shape[2] != 4:
+            raise ValueError("an environment map is [n, n, 4]")
+        rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32).reshape(9)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.float32).reshape(3)
+        _check(self._lib.rtpt_set_environment(self._h, _ptr(tx), tx.shape[0], int(flags), None if rot is None else _ptr(rot),
+                                              None if sc is None else _ptr(sc)))
+
+    def selftest_environment(self, dirs: np.ndarray) -> np.ndarray:
+        """[n, 3] f32: the device lookup of the context's environment map at directions [n, 3] (rtpt_selftest_environment)"""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros((len(dirs), 3), np.float32)
+        _check(self._lib.rtpt_selftest_environment(self._h, _ptr(dirs), len(dirs), _ptr(out)))
         return out
 
     def selftest_shading_normal(self, cases: np.ndarray) -> np.ndarray:

@@ -86,6 +86,9 @@ class HipBackend:
     def set_normals(self, tri_normals=None, tri_smooth=None):
         self.ctx.set_normals(tri_normals, tri_smooth)
 
+    def set_environment(self, texels=None, flags=0, rotation=None, scale=None):
+        self.ctx.set_environment(texels, flags, rotation, scale)
+
     def gbuffer(self, ubo, y0, y1):
         self.ctx.gbuffer(ubo, y0, y1)
 
@@ -291,6 +294,10 @@ class PipelinedBackend:
     def set_normals(self, tri_normals=None, tri_smooth=None):
         for b in self.be:
             b.set_normals(tri_normals, tri_smooth)
+
+    def set_environment(self, texels=None, flags=0, rotation=None, scale=None):
+        for b in self.be:   # both contexts trace
+            b.set_environment(texels, flags, rotation, scale)
 
     def gbuffer(self, ubo, y0, y1):
         self.cur.gbuffer(ubo, y0, y1)
@@ -764,7 +771,8 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
              torch_planes=None, debug_mask=0, scene=DEFAULT_SCENE, instance_xforms=None, group=None, mesh=None,
              frames_in_flight=1, samples_per_pixel=1, splits=(), textures=False, texture_filter="bilinear", texture_mips=False,
              specular=False, dielectric=False, nee=False, nee_sphere=False, nee_power=False, nee_mis=False, smooth_normals=False,
-             smooth_guide=False, **app_kw):
+             smooth_guide=False, environment=None, environment_size=None, environment_yaw=0.0, environment_scale=1.0,
+             environment_nearest=False, **app_kw):
     """createBuffers + loadMesh + buildAccelerationStructure for one rank.  `mesh` = (xyz, idx) replaces
     the OBJ (synthetic scenes of scenes.py); `splits` = unequal strips (strips.StripPlan.splits, the same on every rank).
     `textures` (off by default: an OBJ with a library then renders with the normal-keyed colours, as ever): apply the OBJ's
@@ -795,7 +803,12 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
     app.backend.set_normals(tri_normals, tri_smooth).
     `smooth_guide` (off by default): abi.FLAG_EXT_SMOOTH_GUIDE on every context of this rank — the filter's edge stop reads
     interpolated normals too.  It implies nothing: without `smooth_normals` (or a set_normals call of the caller's) no frame
-    changes."""
+    changes.
+    `environment` (off by default): the path of a lat-long (equirectangular) HDR image, PFM or P6 through textures.load_image, that
+    paths which meet nothing read instead of the fixed sky (rtpt_set_environment) on every context of this rank; it is converted
+    to an octahedral map of `environment_size` texels a side (default: the largest power of two <= min(image height, 1024)) by
+    abi.environment_from_latlong.  `environment_yaw`: degrees the map is turned about +y; `environment_scale`: a factor on its
+    colours; `environment_nearest`: the nearest texel instead of the bilinear filter."""
     if smooth_guide:
         flags |= abi.FLAG_EXT_SMOOTH_GUIDE
     if smooth_normals and mesh is not None:
@@ -847,4 +860,33 @@ def make_app(width, height, max_segments=4, iterations=5, rank=0, world=1, mode=
         tri_normals, tri_smooth = abi.load_obj_normals(scene)
         if tri_smooth.any():
             be.set_normals(tri_normals, tri_smooth)
+    if environment is not None:
+        be.set_environment(*load_environment(environment, environment_size, environment_yaw, environment_scale, environment_nearest))
     return app
+
+
+def environment_default_size(image_height):
+    """the largest power of two <= min(image_height, 1024)"""
+    n = 1
+    while 2 * n <= min(int(image_height), 1024):
+        n *= 2
+    return n
+
+
+def environment_rotation(yaw_deg):
+    """[3, 3] float32, row-major: the map frame's e = (c d.x + s d.z, d.y, -s d.x + c d.z) with c, s the cosine and sine of the yaw
+    (libm's, in double, rounded to binary32: what rtpt_app computes)"""
+    import math
+    a = float(yaw_deg) * (math.pi / 180.0)
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]], np.float64).astype(np.float32)
+
+
+def load_environment(path, size=None, yaw_deg=0.0, scale=1.0, nearest=False):
+    """(texels [n, n, 4], flags, rotation [3, 3], scale [3]) for set_environment from the lat-long image at `path`"""
+    from .textures import load_image
+    im = load_image(path)                       # row 0 = the bottom row of the picture
+    rgb = np.ascontiguousarray(im[::-1, :, :3])  # the conversion takes row 0 at +y
+    n = int(size) if size else environment_default_size(rgb.shape[0])
+    texels = abi.environment_from_latlong(rgb, n)
+    return texels, abi.TEX_NEAREST if nearest else 0, environment_rotation(yaw_deg), np.full(3, scale, np.float32)

@@ -1,6 +1,7 @@
 // api_context.hip — the context of the C ABI (include/rtpt.h): creation, planes, streams, copies, counters, timing, and the
 // helpers shared by the other api_*.hip units (api_internal.hpp).
 #include "api_internal.hpp"
+#include "env_host.hpp"
 
 #include <atomic>
 
@@ -189,6 +190,19 @@ rt::NormalView normal_view(const rtpt_ctx* c) {
   const bool guide = guide_active(c);
   return rt::NormalView{has ? static_cast<const float4*>(c->scene.normals.records.ptr) : nullptr,
                         has ? static_cast<const float4*>(c->scene.normals.cof.ptr) : nullptr, guide ? 1u : 0u, guide ? c->cfg.sigma_n : 0};
+}
+
+rt::EnvView env_view(const rtpt_ctx* c) {
+  const rtpt_ctx::Environment& e = c->envmap;
+  rt::EnvView v{};
+  v.texels = static_cast<const float4*>(e.texels.ptr);
+  v.n = e.texels.ptr ? e.n : 0u;
+  v.flags = e.flags;
+  v.r0 = make_float4(e.rot[0], e.rot[1], e.rot[2], 0.0f);
+  v.r1 = make_float4(e.rot[3], e.rot[4], e.rot[5], 0.0f);
+  v.r2 = make_float4(e.rot[6], e.rot[7], e.rot[8], 0.0f);
+  v.scale = make_float4(e.scale[0], e.scale[1], e.scale[2], 0.0f);
+  return v;
 }
 
 bool guide_active(const rtpt_ctx* c) {
@@ -690,6 +704,34 @@ int rtpt_debug_set_guide_normals(rtpt_ctx* c, const float* src, size_t bytes) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->frame.normals = c->stored_rows();
   c->frame.normals_frame = c->frames_ended;
+  return RTPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the environment map
+int rtpt_set_environment(rtpt_ctx* c, const float* texels_rgba, uint32_t n, uint32_t flags, const float* rotation, const float* scale) {
+  if (!c) return fail(RTPT_E_INVALID, "ctx is NULL");
+  const bool drop = !texels_rgba || !n;
+  // everything that can refuse the call comes first: a refused call leaves the environment the context has untouched
+  if (!drop)
+    if (const char* why = rtpt_env::check_environment(texels_rgba, n, flags, rotation, scale, c->cfg.flags)) return fail(RTPT_E_INVALID, why);
+  HIP_TRY(hipSetDevice(c->device));
+  FLUSH_FILTER(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));  // launches that read the map being replaced
+  // K0, K1 and the filter read nothing of it: no plane tag, no scene generation changes — frame reuse and reprojection reuse go on
+  if (drop) {
+    c->envmap = rtpt_ctx::Environment{};
+    return RTPT_OK;
+  }
+  rtpt_ctx::Environment e;  // joins the context when it is complete; the map it replaces stays until then
+  const size_t bytes = 16 * static_cast<size_t>(n) * n;
+  if (int rc = alloc_buf(e.texels, bytes)) return rc;
+  HIP_TRY(hipMemcpyAsync(e.texels.ptr, texels_rgba, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's array may die at return
+  e.n = n;
+  e.flags = flags;
+  if (rotation) std::memcpy(e.rot, rotation, sizeof e.rot);
+  if (scale) std::memcpy(e.scale, scale, sizeof e.scale);
+  c->envmap = std::move(e);
   return RTPT_OK;
 }
 

@@ -265,6 +265,14 @@ struct rtpt_ctx {
   // The scene.  The context owns every device buffer through a Buf member, of itself or of the scene: `delete` frees
   // them all.  What follows the scene here survives an upload: switches, the builder's work area, staging, counters.
   Scene scene;
+  // The environment map (rtpt_set_environment; env.hpp): of the context, not of the scene — it survives uploads, resizes and
+  // everything between.  texels: exactly 16 n^2 bytes; empty without an environment
+  struct Environment {
+    Buf texels;
+    uint32_t n = 0, flags = 0;
+    float rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // row-major
+    float scale[3] = {1, 1, 1};
+  } envmap;
   bool no_pairing = false;   // RTPT_NO_TRI_PAIRS=1: A/B switch
   bool host_refit = false;   // RTPT_HOST_REFIT=1: round 2's host path for every scene (A/B)
   // device-side BVH build (bvh_build.hip): RTPT_FLAG_DEVICE_BVH_BUILD, or RTPT_DEVICE_BVH=1 at rtpt_create
@@ -390,6 +398,7 @@ rt::SceneView scene_view(const rtpt_ctx* c);
 rt::TexView tex_view(const rtpt_ctx* c);  // the albedo textures, all NULL without (rtpt_scene_set_textures)
 rt::LightTableView light_view(const rtpt_ctx* c);  // the light list, NULL and 0 without (Scene::lights), and its table or NULL
 rt::NormalView normal_view(const rtpt_ctx* c);     // the vertex normals, both NULL without (rtpt_scene_set_normals), and the guide switch
+rt::EnvView env_view(const rtpt_ctx* c);           // the environment map, texels NULL without (rtpt_set_environment)
 // RTPT_FLAG_EXT_SMOOTH_GUIDE is active: the context has the flag and the scene holds normals.  K0 then writes guide normals into
 // rtpt_ctx::normals, and the context behaves as if the scene had no id-pair table
 bool guide_active(const rtpt_ctx* c);

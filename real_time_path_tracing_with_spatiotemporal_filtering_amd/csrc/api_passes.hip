@@ -168,7 +168,7 @@ int trace_material_mode(const rtpt_ctx* c) {
 int ensure_path_pool(rtpt_ctx* c, rt::PathtraceArgs& a) {
   a.pool_slab = nullptr;
   if (!(c->trace_pool && c->scene.use_bvh && c->scene.tree.leaf_pairs && a.compact && a.spp == 1 && !a.albedo && !c->scene.textures.records.ptr &&
-        !trace_material_mode(c) && !c->scene.normals.records.ptr))
+        !trace_material_mode(c) && !c->scene.normals.records.ptr && !c->envmap.texels.ptr))
     return RTPT_OK;  // (the pool form stores no albedo, samples no texture, bounces diffusely about the triangle's normal: such frames take the tile kernel)
   const size_t need = rt::pathtrace_pool_bytes(static_cast<int>(c->cfg.width), static_cast<int>(c->rows()));  // 0: not built in
   if (need && c->path_pool.bytes < need)
@@ -186,6 +186,7 @@ int ensure_path_queues(rtpt_ctx* c, rt::PathtraceArgs& a, uint32_t window) {
   a.queue_region = 0;
   if (!(a.compact && a.spp == 1 && a.max_segments > window && !(c->cfg.flags & RTPT_FLAG_SINGLE_LAUNCH_PATHS))) return RTPT_OK;
   if (rt::spec_lights(trace_material_mode(c))) return RTPT_OK;  // every segment runs in the tile kernel: the queue kernels sample no light
+  if (c->envmap.texels.ptr) return RTPT_OK;                      // ... and read no environment map (kernels.hpp: the ENV axis)
   const size_t blocks = ((static_cast<size_t>(c->cfg.width) + 63) / 64) * ((c->rows() + 3) / 4);
   const size_t region = ((blocks + rt::kPathQueues - 1) / rt::kPathQueues) * 256;
   const size_t cap = region * rt::kPathQueues;
@@ -469,7 +470,8 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   // it and the trace covers every stored row (so that the spare buffer it writes then holds what IMAGE would).  The pass reads
   // the buffer IMAGE names now (the old history), so the trace goes to the buffer no role names and the two change places.
   // Every other call sends the pass out first.
-  const bool take = c->deferred_valid && !fused && rt::pathtrace_takes_final(a, tex_view(c), trace_material_mode(c)) &&
+  // (a context with an environment map has no tile kernel that carries a final pass: kernels.hpp, the ENV axis)
+  const bool take = c->deferred_valid && !fused && !c->envmap.texels.ptr && rt::pathtrace_takes_final(a, tex_view(c), trace_material_mode(c)) &&
                     a.g.y0 == static_cast<int32_t>(c->cfg.row_begin) && a.g.y1 == static_cast<int32_t>(c->cfg.row_end);
   if (!take && (rc = final_flush(c))) return rc;
   if (take) {
@@ -495,7 +497,7 @@ int rtpt_raytrace(rtpt_ctx* c, const rtpt_push_constants* pc, uint32_t y0, uint3
   {
     Timer tm(c, joined ? RTPT_K_GBUFFER_PATHTRACE : RTPT_K_PATHTRACE);
     rt::launch_pathtrace(a, fused ? &c->pending_gb : nullptr, tex_view(c), trace_material_mode(c), c->stream,
-                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c), normal_view(c));
+                         take ? &c->deferred.args : nullptr, &c->filter_policy, c->empty_run_info, light_view(c), normal_view(c), env_view(c));
   }
   if (take) {
     c->deferred_valid = false;

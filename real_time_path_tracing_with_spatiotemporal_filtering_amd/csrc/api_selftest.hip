@@ -214,6 +214,26 @@ int rtpt_selftest_shading_normal(rtpt_ctx* c, const float* in, float* out, size_
   return RTPT_OK;
 }
 
+int rtpt_selftest_environment(rtpt_ctx* c, const float* dirs, size_t n, float* rgb_out) {
+  if (!c || !dirs || !rgb_out) return fail(RTPT_E_INVALID, "NULL argument");
+  if (!c->envmap.texels.ptr) return fail(RTPT_E_INVALID, "the context has no environment map (rtpt_set_environment)");
+  if (n == 0) return RTPT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = n * 3 * sizeof(float);
+  Buf din, dout;
+  int rc;
+  if ((rc = alloc_buf(din, bytes)) || (rc = alloc_buf(dout, bytes))) return rc;
+  hipError_t e = hipMemcpyAsync(din.ptr, dirs, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    rt::launch_selftest_environment(env_view(c), static_cast<const float*>(din.ptr), n, static_cast<float*>(dout.ptr), c->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, dout.ptr, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RTPT_E_DEVICE, std::string("selftest_environment: ") + hipGetErrorString(e));
+  return RTPT_OK;
+}
+
 int rtpt_selftest_light_find(rtpt_ctx* c, const uint32_t* ids, size_t n, const uint32_t* queries, size_t k, uint32_t* index_out) {
   if (!c || !queries || !index_out || (n && !ids)) return fail(RTPT_E_INVALID, "NULL argument");
   if (n > (static_cast<size_t>(1) << 24)) return fail(RTPT_E_INVALID, "a light list has at most 2^24 entries");

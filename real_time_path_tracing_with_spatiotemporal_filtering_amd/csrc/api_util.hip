@@ -2,6 +2,7 @@
 // tinyobjloader, the host BVH checker and the mip-chain arithmetic.  No kernels.  The OBJ loaders are projections of
 // obj_host.hpp's one parse: argument checks, the parse, the arrays, the hand-out.
 #include "api_internal.hpp"
+#include "env_host.hpp"
 #include "obj_host.hpp"
 #include "texture_host.hpp"
 
@@ -190,6 +191,11 @@ int rtpt_util_texture_chain(uint32_t width, uint32_t height, uint32_t* n_levels,
 
 // ------------------------------------------------------------------------------------------ the OBJ loaders
 // `v` and `f` records.  A face index out of range is an error, reported after the counts (and the arrays, when given) are written.
+int rtpt_util_environment_from_latlong(const float* rgb, uint32_t width, uint32_t height, uint32_t n, float* texels_rgba_out) {
+  if (const char* why = rtpt_env::from_latlong(rgb, width, height, n, texels_rgba_out)) return fail(RTPT_E_INVALID, why);
+  return RTPT_OK;
+}
+
 int rtpt_util_load_obj(const char* path, float* xyz, uint32_t* n_verts, uint32_t* idx, uint32_t* n_tris) {
   if (!path || !n_verts || !n_tris) return fail(RTPT_E_INVALID, "NULL argument");
   rtpt_obj::Obj o;

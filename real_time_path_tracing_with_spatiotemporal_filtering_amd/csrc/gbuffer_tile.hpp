@@ -102,7 +102,7 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, int x, int y
   const size_t i = static_cast<size_t>(y - a.g.row_base) * a.g.W + x;
   a.vis[i] = h.id1;  // visibility.frag.glsl:23
   bool guide = false;  // the cell is written below, behind the barycentrics
-  if constexpr (sizeof...(NV) != 0) guide = a.normals && pack_back(nv...).guide != 0u && h.id1 != 0u;
+  if constexpr (sizeof...(NV) != 0) guide = a.normals && pack_get<NormalView>(nv...).guide != 0u && h.id1 != 0u;
   if (a.normals && !guide) a.normals[i] = a.normal_tab[h.id1];
   f3 wp{0.f, 0.f, 0.f};
   float dep = 1.0f;  // clear depth  main.cpp:1421
@@ -110,7 +110,7 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, int x, int y
     float b1 = RTPT_DIV_SH(-h.u, h.ad), b2 = RTPT_DIV_SH(h.v, h.ad);
     float b0 = 1.0f - b1 - b2;
     if constexpr (sizeof...(NV) != 0) {
-      if (guide) a.normals[i] = guide_cell(pack_back(nv...), a.normal_tab, h.id1, a.scene.n_base_tris, b0, b1, b2);
+      if (guide) a.normals[i] = guide_cell(pack_get<NormalView>(nv...), a.normal_tab, h.id1, a.scene.n_base_tris, b0, b1, b2);
     }
     const float4* s = a.scene.shade + 3 * static_cast<size_t>(h.id1 - 1);
     wp = bary_point(xyz(s[0]), xyz(s[1]), xyz(s[2]), b0, b1, b2);

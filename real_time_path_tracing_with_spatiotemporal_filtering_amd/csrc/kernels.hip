@@ -27,6 +27,7 @@
 #include "final_split.hpp"
 #include "pathtrace_tile.hpp"
 #include "select.hpp"
+#include "tile_kernels.hpp"
 
 namespace rt {
 namespace {
@@ -149,47 +150,6 @@ __global__ __launch_bounds__(kThreads) void k_gradient(GradientArgs a) {
   const f3 wp = id ? xyz(a.worldpos[i]) : f3{0.f, 0.f, 0.f};
   store_gradient(a.grad, i, gradient_lambda(id, wp, a.lut, a.lut_prev, a.normal_tab, a.area_tab, ld3(a.cam), ld3(a.light), ld3(a.light_prev), ld3(a.color),
                                             ld3(a.color_prev)));
-}
-
-// The four tile kernels.  LV: the light list of an instantiation that samples lights, as a trailing parameter pack that is empty
-// for every other one or holds spec_lights_t<SPEC> (kernels.hpp): a LightView, or a LightTableView where the pick is weighted.
-// The list travels as a parameter of its own, and of those instantiations only, so that the argument segments of the kernels
-// that take none — the kernels of a build that samples no light — stay what they were.
-template <int BVH, bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_pathtrace(PathtraceArgs a, TexView tex, LV... lights) {
-  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
-  pathtrace_tile<BVH, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
-}
-template <bool COMPACT, bool DEMOD, int TEX, int SPEC, class... LV>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_pathtrace_small(PathtraceArgs a, TexView tex, LV... lights) {
-  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
-  pathtrace_tile<0, COMPACT, false, DEMOD, TEX, SPEC>(a, tex, 0, 0, 0, lights...);
-}
-
-// K0 + K1 + K2 in one launch (rtpt_gbuffer / rtpt_temporal_gradient recorded right before rtpt_raytrace: main.cpp:1105-1107
-// is that order; compacting variants only, the default policy).  Workgroups are dispatched in the order of their linear
-// index: rows [0, a.tiles_y) of the grid are the tracing tiles — long ones first, pathtrace_tile — and the rows behind them
-// the G-buffer's 64 x 4 tiles, a few microseconds each, which therefore start while the last tracing tiles drain: the
-// G-buffer's work fills the tail of the trace instead of having a launch, a ramp and a tail of its own.  Nothing in the
-// trace reads what the G-buffer writes except the depth in the traced image's alpha, and that the G-buffer workgroups
-// store themselves (gbuffer_pixel) while the tracing ones store the colour's 12 bytes — disjoint bytes, any order.
-template <int BVH, bool DEMOD, int TEX, int SPEC, class... LV>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtBvhWaves, kPtBvhWaves)))
-void k_gbuffer_pathtrace(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
-  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
-  gbuffer_pathtrace_body<BVH, DEMOD, TEX, SPEC>(a, g, tex, lights...);
-}
-template <bool DEMOD, int TEX, int SPEC, class... LV>
-__global__ __launch_bounds__(kPtThreads)
-__attribute__((amdgpu_waves_per_eu(kPtWaves, kPtWaves)))
-void k_gbuffer_pathtrace_small(PathtraceArgs a, GbufferArgs g, TexView tex, LV... lights) {
-  static_assert(pack_takes<SPEC, LV...>(), "the light argument SPEC asks for, then a NormalView or nothing");
-  gbuffer_pathtrace_body<0, DEMOD, TEX, SPEC>(a, g, tex, lights...);
 }
 
 // K2 of frame n + 1 and the final filter pass of frame n in one launch (api_passes.hip: DeferredFinal).  The trace is bound by VALU
@@ -415,7 +375,7 @@ static FinalSplit final_split(const PathtraceArgs& a, const AtrousArgs& f, const
                           runs ? static_cast<uint32_t>(pol.empty_run) : 0u);
 }
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin,
-                      const FilterPolicy* pol, uint32_t* run_info, const LightTableView& lights, const NormalView& normals) {
+                      const FilterPolicy* pol, uint32_t* run_info, const LightTableView& lights, const NormalView& normals, const EnvView& envmap) {
   if (run_info) {
     run_info[0] = a.g.y1 > a.g.y0 ? static_cast<uint32_t>((a.g.W + kBlockX - 1) / kBlockX) : 0u;
     run_info[1] = run_info[2] = 0u;
@@ -433,7 +393,10 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   // rtpt_scene_set_normals: the scene is traced through its tree by a compacting launch (api_scene.hip, api_passes.hip see to both)
   const bool nrm = normals.records != nullptr;
   if (nrm && (!normals.cof || !a.scene.use_bvh || (!gb && !a.compact) || fin)) std::abort();
-  const bool pool = !nee && !nrm && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
+  // rtpt_set_environment: the launch is fused or compacts and carries no final pass (api_context.hip, api_passes.hip see to both)
+  const bool envl = envmap.texels != nullptr;
+  if (envl && (!envmap.n || envmap.n > 4096u || (!gb && !a.compact) || fin)) std::abort();
+  const bool pool = !nee && !nrm && !envl && pathtrace_uses_pool(a);  // never with textures: ensure_path_pool (api_passes.hip) hands out no slab then
   const int tile_rows = pool ? kPoolRows : kPtRows;
   const uint32_t tiles_y = (a.g.y1 - a.g.y0 + tile_rows - 1) / tile_rows;
   const dim3 grid((a.g.W + kBlockX - 1) / kBlockX, tiles_y + (gb ? (gb->g.y1 - gb->g.y0 + kBlockY - 1) / kBlockY : 0), 1);
@@ -451,8 +414,8 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
   if (spec_mis(spec)) dyn += kPtThreads * 4;  // cb_pix behind them, for the instantiations of RTPT_FLAG_EXT_NEE_MIS only
   if (a.spp > 1) dyn += 4 * kPtThreads * 4;  // sum_r, sum_g, sum_b, rng_pix
   const uint32_t phase0 = a.first_window ? a.first_window : pt_first_window(a.scene.use_bvh != 0);
-  const bool split = !nee && a.spp == 1 && a.compact && a.queue[0] && a.queue_count && a.max_segments > phase0 &&
-                     (a.max_segments <= 2 * phase0 || a.queue[1]);  // (the queue kernels sample no light)
+  const bool split = !nee && !envl && a.spp == 1 && a.compact && a.queue[0] && a.queue_count && a.max_segments > phase0 &&
+                     (a.max_segments <= 2 * phase0 || a.queue[1]);  // (the queue kernels sample no light and read no environment)
   b.seg_begin = 0;
   b.seg_end = split ? phase0 : a.max_segments;
   b.q_in = nullptr;
@@ -478,6 +441,12 @@ void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexVi
       hipLaunchKernelGGL((k_pathtrace_pool<false>), grid, block, dyn, s, b, GbufferArgs{});
   } else
 #endif
+  if (envl) {
+    // the ENV axis (kernels.hpp): its instantiations are kernels_env.hip's, one part per scene mode with and without a NormalView
+    const int m = scene_mode(a.scene);
+    const auto part = m == 0 ? launch_pathtrace_env_p0 : (m == 1 ? (nrm ? launch_pathtrace_env_p2 : launch_pathtrace_env_p1) : (nrm ? launch_pathtrace_env_p4 : launch_pathtrace_env_p3));
+    part(b, gb, tex, spec, grid, block, dyn, s, lights, normals, envmap);
+  } else
   // the instantiation list of the family: scene mode x DEMOD x TEX x SPEC (x COMPACT for the unfused launch) x NRM (kernels.hpp: in
   // the BVH modes and the compacting forms only), here and nowhere else
   with_mode<3>(scene_mode(a.scene), [&](auto mode) {

@@ -144,6 +144,21 @@ struct NormalView {
   uint32_t guide;         // RTPT_FLAG_EXT_SMOOTH_GUIDE is active
   int32_t sigma_n;        // rtpt_config::sigma_n, read only while guide != 0
 };
+// The environment map (rtpt_set_environment; env.hpp states the rules E1 to E6): n x n RGBA32F texels of an octahedral map, the rows
+// of its rotation and its scale.  It travels as the LAST parameter of the tracing kernels that read it, behind TexView, the light
+// argument and the NormalView, and of those instantiations only — NormalView's reason.  THE ENV AXIS of shade_segment and the tile
+// kernels is whether an instantiation's trailing parameter pack ends in an EnvView (pack_env): there a path that meets nothing is
+// multiplied by env::color(d), everywhere else by sky_color(d), and the instantiations without one keep their names, their argument
+// segments and their code.  An environment launch has the limits of a launch that samples lights: every segment runs in the tile
+// kernel (no queue kernels) and the launch carries no final pass.  Instantiated for the fused launch and the unfused compacting
+// one, in every scene mode, with and without a NormalView; no RTPT_FLAG_NO_PATH_COMPACTION form (rtpt_set_environment refuses such
+// a context).  n in [1, 4096] and texels non-NULL wherever a kernel takes it.
+struct EnvView {
+  const float4* texels;
+  uint32_t n, flags;  // flags: RTPT_TEX_NEAREST (kTexNearest) or 0
+  float4 r0, r1, r2;  // rows of the rotation, .w spare
+  float4 scale;       // rgb, .w spare
+};
 template <class... P>
 struct pack_last {
   using type = void;
@@ -156,30 +171,45 @@ template <class A, class B, class... P>
 struct pack_last<A, B, P...> {
   using type = typename pack_last<B, P...>::type;
 };
+// ... and the one in front of the last
+template <class... P>
+struct pack_last2 {
+  using type = void;
+};
+template <class A, class B>
+struct pack_last2<A, B> {
+  using type = A;
+};
+template <class A, class B, class C, class... P>
+struct pack_last2<A, B, C, P...> {
+  using type = typename pack_last2<B, C, P...>::type;
+};
+template <class... P>
+constexpr bool pack_env() {
+  return std::is_same<typename pack_last<P...>::type, EnvView>::value;
+}
 template <class... P>
 constexpr bool pack_nrm() {
-  return std::is_same<typename pack_last<P...>::type, NormalView>::value;
+  return std::is_same<typename pack_last<P...>::type, NormalView>::value ||
+         (pack_env<P...>() && std::is_same<typename pack_last2<P...>::type, NormalView>::value);
 }
-// a tracing kernel's pack: the light argument of its SPEC (spec_takes), then a NormalView or nothing
+// a tracing kernel's pack: the light argument of its SPEC (spec_takes), then a NormalView or nothing, then an EnvView or nothing
 template <int SPEC, class... P>
 constexpr bool pack_takes() {
-  if constexpr (sizeof...(P) == 0) return !spec_lights(SPEC);
-  else if constexpr (sizeof...(P) == 1) return spec_takes<SPEC, P...>() || (!spec_lights(SPEC) && pack_nrm<P...>());
-  else if constexpr (sizeof...(P) == 2) return spec_lights(SPEC) && pack_nrm<P...>() && std::is_same<std::tuple_element_t<0, std::tuple<P...>>, spec_lights_t<SPEC>>::value;
-  else return false;
+  constexpr size_t want = (spec_lights(SPEC) ? 1u : 0u) + (pack_nrm<P...>() ? 1u : 0u) + (pack_env<P...>() ? 1u : 0u);
+  if constexpr (sizeof...(P) != want) return false;
+  else if constexpr (spec_lights(SPEC)) return std::is_same<std::tuple_element_t<0, std::tuple<P...>>, spec_lights_t<SPEC>>::value;
+  else return true;
 }
-// the first and the last argument of a pack
+// the first argument of a pack, and its first argument of type T
 template <class A, class... P>
 constexpr const A& pack_first(const A& a, const P&...) {
   return a;
 }
-template <class A>
-constexpr const A& pack_back(const A& a) {
-  return a;
-}
-template <class A, class B, class... P>
-constexpr const auto& pack_back(const A&, const B& b, const P&... p) {
-  return pack_back(b, p...);
+template <class T, class A, class... P>
+constexpr const T& pack_get(const A& a, const P&... p) {
+  if constexpr (std::is_same<A, T>::value) return a;
+  else return pack_get<T>(p...);
 }
 
 // Texel (x, y) of level l + 1 of a mip chain = ((a + b) + (c + d)) * 0.25f of the texels (2x, 2y), (min(2x + 1, sw - 1), 2y)
@@ -472,6 +502,8 @@ void launch_gradient(const GradientArgs& a, hipStream_t s);
 // and a table (cdf) where it picks by weight (spec_power).
 // normals: the scene's vertex normals (rtpt_scene_set_normals), records NULL without: with them the scene traces through its BVH, the
 // unfused launch compacts, and the launch carries no final pass.
+// envmap: the context's environment (rtpt_set_environment), texels NULL without: with it the launch is fused or compacts, runs every
+// segment in the tile kernel and carries no final pass (the ENV axis above).
 // fin != NULL (then gb == NULL and pol != NULL): the launch also holds the workgroups of the final filter pass `fin`, which
 // atrous_final_role finished — in front of and behind the tracing tiles as pol says (kernels.hip: k_pathtrace_final).
 // pathtrace_takes_final says whether the launch can carry one: the brute-force tile kernel, one sample, no albedo plane, no
@@ -482,7 +514,18 @@ struct FilterPolicy;
 void launch_pathtrace(const PathtraceArgs& a, const GbufferArgs* gb, const TexView& tex, int specular, hipStream_t s, const AtrousArgs* fin = nullptr,
                       const FilterPolicy* pol = nullptr, uint32_t* run_info = nullptr,
                       const LightTableView& lights = LightTableView{nullptr, 0u, nullptr},
-                      const NormalView& normals = NormalView{nullptr, nullptr, 0u, 0});
+                      const NormalView& normals = NormalView{nullptr, nullptr, 0u, 0}, const EnvView& envmap = EnvView{});
+// the instantiations of the ENV axis (kernels_env.hip), in five parts so that they compile side by side: scene mode 0; mode 1
+// without and with a NormalView; mode 2 without and with one.  launch_pathtrace finishes the arguments (b: tiles_y, multi_off and
+// the segment window set; spec: the launch's SPEC; dyn: its dynamic LDS) and calls the part of its scene; nothing else does.
+#define RTPT_ENV_PART_DECL(p)                                                                                                          \
+  void launch_pathtrace_env_p##p(const PathtraceArgs& b, const GbufferArgs* gb, const TexView& tex, int spec, dim3 grid, dim3 block, \
+                                 size_t dyn, hipStream_t s, const LightTableView& lights, const NormalView& normals, const EnvView& envmap)
+RTPT_ENV_PART_DECL(0);
+RTPT_ENV_PART_DECL(1);
+RTPT_ENV_PART_DECL(2);
+RTPT_ENV_PART_DECL(3);
+RTPT_ENV_PART_DECL(4);
 bool pathtrace_takes_final(const PathtraceArgs& a, const TexView& tex, int specular);
 bool pathtrace_fuses_gbuffer(const PathtraceArgs& a, const GbufferArgs& g);
 uint32_t pathtrace_grid_blocks(const PathtraceArgs& a, const GbufferArgs* gb);
@@ -577,6 +620,8 @@ void launch_selftest_mis_weight(const float* in, float* out, size_t n, hipStream
 // shading_normal.hpp's rules and side tests on n cases of 36 words (n0, n1, n2, b1, b2, the cof rows, ng, d, d', wd, ray_offset, three
 // words not read): out = n x (smooth as 1.0f / 0.0f, ns, absorbed, sample_side, the dielectric's offset, 0)
 void launch_selftest_shading_normal(const float* in, float* out, size_t n, hipStream_t s);
+// env::color (env.hpp) of n directions of 3 floats: rgb_out = n x 3 (rtpt_selftest_environment)
+void launch_selftest_environment(const EnvView& envmap, const float* dirs, size_t n, float* rgb_out, hipStream_t s);
 // rtpt_light::find (light_list_host.hpp) of k queries on the ascending list ids[0, n): index_out[j], n where the id is not in it
 void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t* queries, size_t k, uint32_t* index_out, hipStream_t s);
 

@@ -114,11 +114,23 @@ __device__ __forceinline__ uint32_t tile_lin(uint32_t role_lin) {
 // shift the dynamic LDS of every kernel of kernels.hip.
 // lights: the light list as SPEC takes it (spec_lights_t<SPEC>), the tile kernels' trailing parameter pack: nothing where no light is
 // sampled
+// what shade_segment takes for the lights and for the normals, out of a tile kernel's pack (the ENV instantiations)
+template <int SPEC, class... LV>
+__device__ __forceinline__ auto tile_nee_args([[maybe_unused]] NeeState* st, const LV&... lights) {
+  if constexpr (spec_lights(SPEC)) return NeeArgs<spec_lights_t<SPEC>>{pack_first(lights...), st};
+  else return NoNee{};
+}
+template <bool NRM, class... LV>
+__device__ __forceinline__ auto tile_normals(const LV&... lights) {
+  if constexpr (NRM) return pack_get<NormalView>(lights...);
+  else return NoNormals{};
+}
 template <int BVH, bool COMPACT, bool GB, bool DEMOD, int TEX, int SPEC = 0, int ROLE = 0, class... LV>
 __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const TexView& tex, const uint32_t role_lin = 0, const uint32_t role_gx = 0,
                                                const uint32_t role_gy = 0, const LV&... lights) {
-  static_assert(pack_takes<SPEC, LV...>(), "an instantiation takes the light argument of its SPEC, spec_lights_t<SPEC>, then a NormalView or nothing");
-  constexpr bool NRM = pack_nrm<LV...>();  // kernels.hpp: the NRM axis; the pack's last argument is then the scene's NormalView
+  static_assert(pack_takes<SPEC, LV...>(), "an instantiation takes the light argument of its SPEC, spec_lights_t<SPEC>, then a NormalView or nothing, then an EnvView or nothing");
+  constexpr bool NRM = pack_nrm<LV...>();  // kernels.hpp: the NRM axis; the pack then holds the scene's NormalView
+  constexpr bool ENV = pack_env<LV...>();  // kernels.hpp: the ENV axis; the pack's last argument is then the context's EnvView
   // ROLE: the workgroup is tile role_lin of a role_gx x role_gy tile grid that is not the launch's own grid
   // dynamic LDS, two tenants that are never live together: the BVH node stack (stack_depth x 256 entries, only
   // inside closest_hit) and the compaction exchange buffer (only between the barriers of the compaction step).
@@ -232,13 +244,19 @@ __device__ __forceinline__ void pathtrace_tile(const PathtraceArgs& a, const Tex
         if constexpr (spec_lights(SPEC)) nee.valid = false;
         if constexpr (spec_sphere(SPEC)) nee.sphere_valid = false;
         bool done;
-        if constexpr (NRM && spec_lights(SPEC))
+        if constexpr (ENV) {  // the same four forms with the EnvView behind them, their arguments picked from the pack by type
+          using NeeT = std::conditional_t<spec_lights(SPEC), NeeArgs<spec_lights_t<SPEC>>, NoNee>;
+          using NrmT = std::conditional_t<NRM, NormalView, NoNormals>;
+          done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeT, NrmT, EnvView>(a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
+                                                                               tile_nee_args<SPEC>(&nee, lights...), tile_normals<NRM>(lights...),
+                                                                               pack_get<EnvView>(lights...));
+        } else if constexpr (NRM && spec_lights(SPEC))
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs<spec_lights_t<SPEC>>, NormalView>(
               a, h, seg, light_c, o, d, acc, rng, tex, (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
-              NeeArgs<spec_lights_t<SPEC>>{pack_first(lights...), &nee}, pack_back(lights...));
+              NeeArgs<spec_lights_t<SPEC>>{pack_first(lights...), &nee}, pack_get<NormalView>(lights...));
         else if constexpr (NRM)
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NoNee, NormalView>(a, h, seg, light_c, o, d, acc, rng, tex,
-                                                                             (DEMOD && seg == 0) ? a.albedo + gi : nullptr, NoNee{}, pack_back(lights...));
+                                                                             (DEMOD && seg == 0) ? a.albedo + gi : nullptr, NoNee{}, pack_get<NormalView>(lights...));
         else if constexpr (spec_lights(SPEC))
           done = shade_segment<TEX, BVH, kShortDiv, SPEC, NeeArgs<spec_lights_t<SPEC>>>(a, h, seg, light_c, o, d, acc, rng, tex,
                                                                                         (DEMOD && seg == 0) ? a.albedo + gi : nullptr,
@@ -434,7 +452,7 @@ __device__ __forceinline__ void gbuffer_pathtrace_body(const PathtraceArgs& a, c
     TimelineScope tl_(0, (blockIdx.y - a.tiles_y) * gridDim.x + blockIdx.x);
 #endif
     if constexpr (pack_nrm<LV...>())  // the scene's NormalView: K0 writes the guide normal while its switch is set (gbuffer_tile.hpp)
-      gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1, pack_back(lights...));
+      gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1, pack_get<NormalView>(lights...));
     else
       gbuffer_tile<BVH>(g, blockIdx.x, blockIdx.y - a.tiles_y, stack, a.image, a.g.y0, a.g.y1);
   }

@@ -311,6 +311,16 @@ __global__ __launch_bounds__(kThreads) void k_selftest_trace(SceneView sc, const
   if (out_t) out_t[i] = h.id1 ? h.t : 0.0f;
 }
 
+// env::color (env.hpp) of the context's environment map at arbitrary directions (rtpt_selftest_environment)
+__global__ void k_selftest_environment(EnvView envmap, const float* dirs, size_t n, float* rgb) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const f3 c = env::color(envmap, f3{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]});
+  rgb[3 * i] = c.x;
+  rgb[3 * i + 1] = c.y;
+  rgb[3 * i + 2] = c.z;
+}
+
 // the sampler of texture.hpp at arbitrary uv (rtpt_selftest_texture)
 __global__ void k_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out) {
   const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -404,6 +414,10 @@ void launch_selftest_light_find(const uint32_t* ids, uint32_t n, const uint32_t*
 void launch_selftest_refract(const float* in, float* out, size_t n, hipStream_t s) {
   if (!n) return;
   hipLaunchKernelGGL(k_selftest_refract, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n);
+}
+void launch_selftest_environment(const EnvView& envmap, const float* dirs, size_t n, float* rgb_out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_selftest_environment, dim3((n + 255) / 256), dim3(256), 0, s, envmap, dirs, n, rgb_out);
 }
 void launch_selftest_texture(const TexDesc* desc, const float4* texels, const float* uv, size_t n, float4* out, hipStream_t s) {
   if (!n) return;

@@ -6,6 +6,7 @@
 
 #include "closest_hit.hpp"
 #include "dielectric.hpp"
+#include "env.hpp"
 #include "light_sample.hpp"
 #include "shading_normal.hpp"
 #include "specular.hpp"
@@ -154,6 +155,11 @@ struct NoNee {};
 // whose record is smooth bounces, refracts and samples lights about the interpolated normal ns; the offset origin and everything
 // above the bounce keep the geometric normal.  These instantiations return early on every last segment, like the specular ones.
 struct NoNormals {};
+// ENV (EV = EnvView; every other instantiation takes NoEnv there, nothing, and is the instantiation before the axis, statement for
+// statement): the context has an environment map (rtpt_set_environment; env.hpp states the lookup).  A path that meets nothing is
+// multiplied by env::color(d) where the others multiply by sky_color(d).  Nothing else changes: the light test comes first, the albedo
+// plane of such a path is (1, 1, 1), and no path changes direction, length or random stream.
+struct NoEnv {};
 // the hit's ns by rules 1 to 7, from the records of base triangle (id1 - 1) % n_base and the matrix of instance (id1 - 1) / n_base;
 // false (ns = ng) where the hit is not smooth.  The matrix is loaded only behind a smooth record.
 __device__ __forceinline__ bool hit_shading_normal(const NormalView& nv, uint32_t id1, uint32_t n_base, float b0, float b1, float b2, f3 ng, f3 d,
@@ -171,14 +177,17 @@ __device__ __forceinline__ bool hit_shading_normal(const NormalView& nv, uint32_
   *ns = nrm::orient(n, ng, d);
   return true;
 }
-template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE = NoNee, class NV = NoNormals>
+template <int TEX, int BVH = 1, bool SHORT_DIV = false, int SPEC = 0, class NEE = NoNee, class NV = NoNormals, class EV = NoEnv>
 __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitRec& h, uint32_t seg, f3 light_c, f3& o, f3& d,
                                               f3& acc, uint32_t& rng, const TexView& tex, float4* alb_px = nullptr,
-                                              [[maybe_unused]] NEE nee_args = NEE{}, [[maybe_unused]] NV normals = NV{}) {
+                                              [[maybe_unused]] NEE nee_args = NEE{}, [[maybe_unused]] NV normals = NV{},
+                                              [[maybe_unused]] EV envmap = EV{}) {
   static_assert(std::is_same<NEE, std::conditional_t<spec_lights(SPEC), NeeArgs<spec_lights_t<SPEC>>, NoNee>>::value,
                 "the instantiations that sample lights, and only they, take NeeArgs, with the list their SPEC asks for");
   constexpr bool NRM = std::is_same<NV, NormalView>::value;
   static_assert(NRM || std::is_same<NV, NoNormals>::value, "NormalView or nothing");
+  constexpr bool ENV = std::is_same<EV, EnvView>::value;
+  static_assert(ENV || std::is_same<EV, NoEnv>::value, "EnvView or nothing");
   if (ray_hits_light(o, d, light_c, a.light_r2)) {  // :226
     acc = acc * (seg == 0 ? ld3(a.light_col_first) : ld3(a.light_col));  // :229,:233
     if constexpr (spec_sphere(SPEC)) {
@@ -188,7 +197,10 @@ __device__ __forceinline__ bool shade_segment(const PathtraceArgs& a, const HitR
     return true;
   }
   if (h.id1 == 0) {
-    acc = acc * sky_color(d);  // :266
+    if constexpr (ENV)
+      acc = acc * env::color(envmap, d);  // the environment map where the reference has its sky
+    else
+      acc = acc * sky_color(d);  // :266
     if (alb_px) *alb_px = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     return true;
   }

@@ -3,6 +3,7 @@
 #include "scene_gen.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -198,10 +199,35 @@ void PathTracingApplication::createBuffers() {
   ctx_ = last_ = ctxs_[0];
 }
 
+// --environment: the lat-long image to the octahedral map every context gets (the Python host's load_environment, restated)
+void PathTracingApplication::loadEnvironment() {
+  if (opt_.environment.empty() || !envTexels_.empty()) return;
+  const rtpt_host::Image im = rtpt_host::load_image(opt_.environment);  // row 0 = the bottom row of the picture
+  std::vector<float> rgb(static_cast<size_t>(im.width) * im.height * 3);
+  for (uint32_t y = 0; y < im.height; y++)  // the conversion takes row 0 at +y
+    for (uint32_t x = 0; x < im.width; x++)
+      for (int c = 0; c < 3; c++)
+        rgb[3 * (static_cast<size_t>(y) * im.width + x) + c] = im.rgba[4 * (static_cast<size_t>(im.height - 1 - y) * im.width + x) + c];
+  uint32_t n = opt_.environment_size;
+  if (!n)
+    for (n = 1; 2 * n <= std::min<uint32_t>(im.height, 1024u);) n *= 2;
+  envTexels_.assign(4 * static_cast<size_t>(n) * n, 0.0f);
+  check(rtpt_util_environment_from_latlong(rgb.data(), im.width, im.height, n, envTexels_.data()), "--environment");
+  envSize_ = n;
+  const double a = opt_.environment_yaw * (3.14159265358979323846 / 180.0), c = std::cos(a), s = std::sin(a);
+  const double rot[9] = {c, 0.0, s, 0.0, 1.0, 0.0, -s, 0.0, c};
+  for (int i = 0; i < 9; i++) envRotation_[i] = static_cast<float>(rot[i]);
+  for (float& v : envScale_) v = opt_.environment_scale;
+}
+
 void PathTracingApplication::buildAccelerationStructure() {
   // world-space bounds of the scene: strips bound the reprojection reach with them (strips.hpp)
   sceneBounds();
+  loadEnvironment();
   auto materials = [&](rtpt_ctx* ctx) {
+    if (!envTexels_.empty())  // of the context, not of the scene: set on every context this host creates
+      check(rtpt_set_environment(ctx, envTexels_.data(), envSize_, opt_.environment_nearest ? RTPT_TEX_NEAREST : 0u, envRotation_, envScale_),
+            "rtpt_set_environment");
     if (!triSmooth.empty())
       check(rtpt_scene_set_normals(ctx, triNormals.data(), triSmooth.data(), static_cast<uint32_t>(triSmooth.size())), "rtpt_scene_set_normals");
     if (!objMaterialsExt.empty())

@@ -25,6 +25,9 @@ static void usage(const char* argv0) {
       "           PPM / PFM next to the OBJ, at every hit: rtpt_scene_set_textures; without it an OBJ with map_Kd renders as it always did;\n"
       "           --texture-mips: from generated mip chains, at the level of the ray's footprint, RTPT_TEX_MIPMAP)]\n"
       "          [--specular  (a newmtl with illum >= 3 and Ks != 0 bounces as a mirror, or glossy by its Ns: rtpt_scene_set_materials_ext)]\n"
+      "          [--environment sky.pfm [--environment-size N] [--environment-yaw DEG] [--environment-scale S] [--environment-nearest]\n"
+      "           (a lat-long HDR image, PFM / P6, that paths which meet nothing read instead of the fixed sky: rtpt_set_environment on\n"
+      "           every context; N texels a side of the octahedral map, default the largest power of two <= min(image height, 1024))]\n"
       "          [--smooth-normals  (with --scene: bounces, refraction and light samples use the OBJ's interpolated vn records)]\n"
       "          [--smooth-guide  (the filter's edge stop reads interpolated normals too, RTPT_FLAG_EXT_SMOOTH_GUIDE = --flags 0x100000;\n"
       "           without --smooth-normals the frames are unchanged)]\n"
@@ -107,6 +110,11 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--specular")) opt.specular = true;
     else if (!std::strcmp(argv[i], "--dielectric")) opt.dielectric = true;
     else if (!std::strcmp(argv[i], "--smooth-normals")) opt.smooth_normals = true;
+    else if (!std::strcmp(argv[i], "--environment")) opt.environment = need("--environment");
+    else if (!std::strcmp(argv[i], "--environment-size")) opt.environment_size = static_cast<uint32_t>(std::strtoul(need("--environment-size"), nullptr, 10));
+    else if (!std::strcmp(argv[i], "--environment-yaw")) opt.environment_yaw = std::strtod(need("--environment-yaw"), nullptr);
+    else if (!std::strcmp(argv[i], "--environment-scale")) opt.environment_scale = std::strtof(need("--environment-scale"), nullptr);
+    else if (!std::strcmp(argv[i], "--environment-nearest")) opt.environment_nearest = true;
     else if (!std::strcmp(argv[i], "--smooth-guide")) opt.flags |= RTPT_FLAG_EXT_SMOOTH_GUIDE;
     else if (!std::strcmp(argv[i], "--texture-filter")) {
       const char* v = need("--texture-filter");
